@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput benchmark of the polishing engine (contract: see the task prompt / DESIGN.md §5).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One *step* = one full `generate_caption` pass over one batch of synthetic images on every rank:
@@ -11,9 +11,14 @@ vision encode of the batch (once per image).  value = captions/s of the whole jo
 (N * 256 * K / max-over-ranks time).  Weak scaling: per-GPU work is fixed; `--total-images N` fixes the TOTAL instead
 (strong scaling: BASELINE configs[3] 2048 / configs[4] 512 images split over the ranks by `dist.shard_range`).
 
-Two legs, SAME steps and warm-up: `value` = the bf16 engine on HF-init weights (logit scale 14.3, the engine north_star
-names); `scale100_mode.value` (= `value_scale100`) = the engine `runtime.choose_precision` selects for the published
-checkpoints (logit scale 100: screen-then-refine).  `roofline` divides out of the timed region `value` is measured on.
+A plain run sets up, warms up, times `--steps` steps of the bf16 engine on HF-init weights (logit scale 14.3, the engine
+north_star names; no HIP events in the timed region), writes the last timed step's outputs with `--dump-outputs`, and prints
+the line: `value`, `ms_per_step`.  `--full` adds everything else, as separate passes after the timed region unless noted:
+`roofline` (HIP events around the roofline family inside the timed region, which `value` then includes), the per-class
+breakdown and the single-stream pass, the batch-invariance check, `captions_crc32`, a second leg with the SAME steps and
+warm-up -- `scale100_mode.value` (= `value_scale100`) = the engine `runtime.choose_precision` selects for the published
+checkpoints (logit scale 100: screen-then-refine) --, `box_calibration` and the CPU baseline.  The `--no-*` switches turn
+single parts of `--full` off.
 """
 import argparse
 import json
@@ -27,6 +32,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 PEAK_BF16_TFLOPS = 2500.0  # dense bf16 MFMA, /opt/skills/guides/MI355X_MICROARCH.md
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all files together
 
 
 def f_step(K, T, Tc):
@@ -55,6 +61,24 @@ def metric_name(L, K, order, gamma=None, samples=1):
 def per_caption(total, images, samples=1):
     """A per-step total (FLOPs, ...) of one rank divided by the captions that step produced: images x samples_num."""
     return total / (images * max(1, samples))
+
+
+def dump_outputs(out_dir, embeds, ids, cos, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what a caller of the timed path received in the last timed step, one .npy per array --
+    image_embeds [B, proj] fp32 (encode_images), ids [samples, snapshots, B, T] as float64 (exact for int32 token ids) and
+    cos [samples, snapshots, B] fp32 (generate, one call per sample), image_index [n] float64 = the images written.  All
+    images while the files fit in `limit` bytes, else a fixed seeded sample of them (same images on every run)."""
+    embeds = np.asarray(embeds, np.float32)
+    ids, cos = np.asarray(ids, np.float64), np.asarray(cos, np.float32)
+    B = embeds.shape[0]
+    per_image = (embeds[0].nbytes + ids[:, :, 0].nbytes + cos[:, :, 0].nbytes + 8)
+    n = min(B, max(1, (limit - 4096) // per_image))  # 4 KiB: the .npy headers
+    keep = np.arange(B) if n == B else np.sort(np.random.default_rng(0).choice(B, size=n, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = dict(image_embeds=embeds[keep], ids=ids[:, :, keep], cos=cos[:, :, keep], image_index=keep.astype(np.float64))
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(arr))
+    return sum(arr.nbytes for arr in arrays.values())
 
 
 def physical_cores():
@@ -216,16 +240,23 @@ def main():
     ap.add_argument("--logit-scale", type=float, default=2.6592, help="CLIP logit_scale (HF init 2.6592; published checkpoint ln 100 = 4.6052)")
     ap.add_argument("--gamma", type=float, default=None, help="sentiment control weight (BASELINE configs[4]: 5.0)")
     ap.add_argument("--sentiment", default="positive", choices=["positive", "negative"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true", help="skip the HIP-event kernel timing (roofline)")
-    ap.add_argument("--no-alt", action="store_true", help="skip the second leg (the engine the product path selects at the published logit scale)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: roofline and per-kernel figures, batch "
+                         "invariance, captions_crc32, the scale-100 leg, box_calibration, the CPU baseline (the --no-* switches "
+                         "below turn single parts off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (image_embeds, ids, cos of every image; "
+                         "rank 0 gathers the ranks' images) as DIR/<name>.npy, float32 / float64, 64 MB at most")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: skip the HIP-event kernel timing (roofline)")
+    ap.add_argument("--no-alt", action="store_true", help="with --full: skip the second leg (the engine the product path selects at the published logit scale)")
     ap.add_argument("--alt-steps", type=int, default=None,
                     help="timed steps of the scale-100 leg (default: --steps, with --warmup warm-up steps: both legs on equal footing)")
     ap.add_argument("--total-images", type=int, default=None,
                     help="strong scaling: polish this many images in total, split over the ranks by dist.shard_range "
                          "(BASELINE configs[3]: 2048, configs[4]: 512); default: --images per GPU (weak scaling)")
     ap.add_argument("--alt-split", action="store_true", help="also time the all-split-fp16 engine at the published logit scale (the round-2 product mode)")
-    ap.add_argument("--no-invariance", action="store_true", help="skip the batch-invariance check after the timed loop")
+    ap.add_argument("--no-invariance", action="store_true", help="with --full: skip the batch-invariance check after the timed loop")
     ap.add_argument("--streams", type=int, default=2,
                     help="concurrent image sub-batches per GPU, each on its own HIP stream over the same weights "
                          "(czc_replicate); 1 = one engine, one stream")
@@ -238,6 +269,10 @@ def main():
     if pre.config is not None:
         ap.set_defaults(**CONFIG_PRESETS[pre.config])
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not a.full:  # a plain run: the timed steps of the headline leg and nothing else
+        a.no_cpu_baseline = a.no_profile = a.no_alt = a.no_invariance = True
     if a.share_gpu:
         os.environ["CZC_SHARE_GPU"] = "1"
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -311,8 +346,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def run_mode(prec_, logit_scale, steps, warmup, profile, opts=(), invariance=False, control="table"):
-        """Engine in one precision at one logit scale: warm up, time `steps` passes, return the measurements."""
+    def run_mode(prec_, logit_scale, steps, warmup, profile, opts=(), invariance=False, control="table", dump_dir=None):
+        """Engine in one precision at one logit scale: warm up, time `steps` passes, return the measurements (with
+        `dump_dir`: write the last timed pass's outputs there first)."""
         exact = a.gamma is not None and control == "exact"
         bcfg, ccfg = synth.bert_base(), synth.clip_b32()
         ccfg.logit_scale = logit_scale  # make_clip_weights writes it into the "logit_scale" tensor
@@ -377,8 +413,8 @@ def main():
                     scorer.sent_memo.clear()
                 a0, s0 = scorer.asked, scorer.scored
             last["embeds"] = grp.encode_images(pixels)  # once per image and step; every sample re-uses the resident embeddings
-            for sp, sn, se in sample_plans:
-                out_ = grp.generate(B, init, L, seed_len, K, sp, hp, n_mask=sn, snapshot_every=se)
+            last["gen"] = [grp.generate(B, init, L, seed_len, K, sp, hp, n_mask=sn, snapshot_every=se) for sp, sn, se in sample_plans]
+            out_ = last["gen"][-1]
             if scorer is not None:
                 per_step_scoring.append((scorer.asked - a0, scorer.scored - s0))
             return out_
@@ -402,6 +438,18 @@ def main():
         barrier()
         dt = time.perf_counter() - t0
         timed_scoring = list(per_step_scoring)
+        if dump_dir is not None:
+            embeds_ = last["embeds"]
+            ids_ = np.stack([g_[0] for g_ in last["gen"]])
+            cos_ = np.stack([g_[1] for g_ in last["gen"]])
+            if world > 1:  # every rank's images, in image order (shard order = rank order)
+                embeds_ = czd.gather_along(embeds_, world, axis=0)
+                ids_ = czd.gather_along(ids_, world, axis=2)
+                cos_ = czd.gather_along(cos_, world, axis=2)
+            if rank == 0:
+                nbytes = dump_outputs(dump_dir, embeds_, ids_, cos_)
+                print(f"bench.py: wrote {nbytes / 2 ** 20:.1f} MB of outputs of the last timed step to {dump_dir}",
+                      file=sys.stderr, flush=True)
         host_s_timed = (scorer.host_seconds - host_s0) if scorer is not None else 0.0
         grp.profile(False)
         stats = grp.stats()
@@ -458,11 +506,13 @@ def main():
             breakdown = {k: eng.profile_get(k) for k in kinds}
         # the captions of the last timed step over ALL ranks (image order = rank order = shard order), as a checksum: an N-rank
         # strong-scaling run must reproduce the 1-rank run's ids exactly (tests/test_dist_gpu.py)
-        import zlib
-        tg = time.perf_counter()
-        all_ids = czd.gather_along(ids, world, axis=1) if world > 1 else ids
-        gather_s = round(time.perf_counter() - tg, 4) if world > 1 else None
-        ids_crc = zlib.crc32(np.ascontiguousarray(all_ids, dtype=np.int32).tobytes()) & 0xFFFFFFFF
+        ids_crc = gather_s = None
+        if a.full:
+            import zlib
+            tg = time.perf_counter()
+            all_ids = czd.gather_along(ids, world, axis=1) if world > 1 else ids
+            gather_s = round(time.perf_counter() - tg, 4) if world > 1 else None
+            ids_crc = zlib.crc32(np.ascontiguousarray(all_ids, dtype=np.int32).tobytes()) & 0xFFFFFFFF
         ctl = None
         if scorer is not None:
             ctl = dict(scorer="conzic_amd.control.HostScorer over tests/nltk_standin.py installed as nltk (a stand-in: nltk and its "
@@ -480,7 +530,7 @@ def main():
             scorer.close()
         res = dict(host=host_info, broadcast_s=broadcast_s, gather_s=gather_s, dt=dt, prof=prof, prof_timed=prof_timed, breakdown=breakdown, stats=stats, setup_s=t_setup, invariance=None, control=ctl,
                    streams=n_streams, single_ms=single_ms, per_rank=per_rank, steps=prof_steps, events_in_region=events_in_region, ids_crc=ids_crc,
-                   n_ids=int(all_ids.shape[1]))
+                   n_ids=n_total)
         if invariance and rank == 0 and B > 2:
             # batch invariance: images 0-1 encoded and polished ALONE (B = 2) by the same engine must come out as they did
             # inside the batch of B (per-image work is independent: gen_utils.py:65-81 has no cross-image term), with no
@@ -499,7 +549,8 @@ def main():
         return res
 
     main_res = run_mode(prec, a.logit_scale, a.steps, a.warmup, not a.no_profile, opts=a.opt,
-                        invariance=not a.no_invariance, control="exact" if a.control == "exact" else "table")
+                        invariance=not a.no_invariance, control="exact" if a.control == "exact" else "table",
+                        dump_dir=a.dump_outputs)
     exact_res = None
     if a.gamma is not None and a.control == "both":
         exact_res = run_mode(prec, a.logit_scale, a.steps, a.warmup, False, opts=a.opt, control="exact")
@@ -644,7 +695,7 @@ def main():
                                         f"L={L}, K={K}, I={I}, alpha=0.02 beta=2.0 tau=0.1, bert-base + CLIP ViT-B/32 shapes, "
                                         f"random-init weights (logit_scale {a.logit_scale}), synthetic vocab (1 CLIP token per word); "
                                         f"`value` = the {a.precision} engine at exp(logit_scale) = {np.exp(a.logit_scale):.1f}; "
-                                        "`value_scale100` / `scale100_mode` = the same workload, same steps and warm-up, through the engine the "
+                                        "`value_scale100` / `scale100_mode` (with --full) = the same workload, same steps and warm-up, through the engine the "
                                         "product path selects for the published checkpoints (logit scale 100)",
                                preset=a.config, samples_num=a.samples, images_per_gpu=B, total_images=n_total, sentence_len=L, candidate_k=K, num_iterations=I, order=a.order,
                                gamma=a.gamma, sentiment=a.sentiment if a.gamma is not None else None,
@@ -685,9 +736,10 @@ def main():
                                                "sweeps, ten leave at near-ties of 2.3e-5 or less",
                                where="tests/test_step_gpu.py; profiles/r06_gpu_tests_summary.txt, profiles/r06_refine_validate_*.jsonl"),
                    batch_invariance=main_res["invariance"],
-                   captions_crc32=dict(value=main_res["ids_crc"], images=main_res["n_ids"],
-                                       note="crc32 of the final token ids of every image of the last timed step, gathered over the ranks in "
-                                            "image order: equal between an N-rank --total-images run and the 1-rank run of the same images"))
+                   captions_crc32=None if main_res["ids_crc"] is None else dict(
+                       value=main_res["ids_crc"], images=main_res["n_ids"],
+                       note="crc32 of the final token ids of every image of the last timed step, gathered over the ranks in "
+                            "image order: equal between an N-rank --total-images run and the 1-rank run of the same images"))
         if a.gamma is not None:
             def ctl_block(res, mode):
                 v = n_total * a.steps * max(1, a.samples) / res["dt"]
@@ -732,7 +784,7 @@ def main():
         if split_res is not None:
             out["scale100_all_split"] = alt_block(split_res, native.PREC_SPLIT,
                                                   "the same with every tower on split-fp16 MFMA (the round-2 product mode)")
-        out["box_calibration"] = box_calibration()  # after the timed legs: it shares nothing with them
+        out["box_calibration"] = box_calibration() if a.full else None  # after the timed legs: it shares nothing with them
         if world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(L, K, I, a.cpu_threads)
         else:
@@ -742,8 +794,8 @@ def main():
         import torch.distributed as dist
         dist.destroy_process_group()
     sys.stdout.flush()
-    if not os.environ.get('CZC_NORMAL_EXIT'):
-        os._exit(0)  # skip interpreter/HIP teardown (it can hang on this image); rocprofv3 runs set CZC_NORMAL_EXIT=1
+    # the process ends through the interpreter (atexit handlers, library destructors): profilers and other tools that
+    # record at process exit see the run; every engine was closed at the end of its leg
 
 
 if __name__ == "__main__":

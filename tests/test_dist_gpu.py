@@ -143,14 +143,16 @@ def test_run_cli_sharded_over_two_ranks_matches_single_process(tmp_path):
         assert len(outs[1][k]) == 6
 
 
-def test_bench_gpus_2_spawns_two_ranks_on_a_shared_gpu():
+def test_bench_gpus_2_spawns_two_ranks_on_a_shared_gpu(tmp_path):
     """`python bench.py --gpus 2` without a launcher starts two ranks itself (a plain --gpus N run
     must never report n_gpus 1).  On this one-GPU box the ranks share the device under the explicit test flag
-    (gloo rendezvous: RCCL cannot put two ranks on one device); on a node they are rank r <-> GPU r over RCCL."""
+    (gloo rendezvous: RCCL cannot put two ranks on one device); on a node they are rank r <-> GPU r over RCCL.
+    A plain run (no --full) times --steps steps and measures nothing else; --dump-outputs writes the last timed step's
+    outputs of both ranks' images."""
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--images", "64", "--steps", "1",
-                        "--warmup", "0", "--no-cpu-baseline", "--no-alt", "--no-invariance", "--share-gpu"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--images", "64", "--steps", "2",
+                        "--warmup", "0", "--share-gpu", "--dump-outputs", str(tmp_path / "out")],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -159,24 +161,34 @@ def test_bench_gpus_2_spawns_two_ranks_on_a_shared_gpu():
     assert out["ranks"]["world_size"] == 2 and out["ranks"]["reported_by_backend"] == 2
     assert out["ranks"]["shared_gpu"] is True and "TEST RUN" in out["config"]["parallelism"]
     assert out["value"] > 0 and out["config"]["images_per_gpu"] == 64
+    assert out["steps"] == 2 and out["ms_per_step"] > 0
+    assert abs(out["value"] - 128 / (out["ms_per_step"] * 1e-3)) / out["value"] < 1e-3
+    assert out["roofline"] is None and out["cpu_baseline"] is None and out["box_calibration"] is None
+    assert out["batch_invariance"] is None and out["captions_crc32"] is None and "scale100_mode" not in out
+    d = {f[:-4]: np.load(tmp_path / "out" / f) for f in os.listdir(tmp_path / "out")}
+    assert sorted(d) == ["cos", "ids", "image_embeds", "image_index"]
+    assert d["image_embeds"].dtype == np.float32 and d["image_embeds"].shape[0] == 128
+    assert d["ids"].dtype == np.float64 and d["ids"].shape[:3] == (1, 10, 128) and (d["ids"] == np.round(d["ids"])).all()
+    assert d["cos"].dtype == np.float32 and d["cos"].shape == (1, 10, 128) and np.isfinite(d["cos"]).all()
+    np.testing.assert_array_equal(d["image_index"], np.arange(128))
 
 
-def test_bench_strong_scaling_two_ranks_reproduce_the_one_rank_captions():
+def test_bench_strong_scaling_two_ranks_reproduce_the_one_rank_captions(tmp_path):
     """`--total-images N` fixes the TOTAL (BASELINE configs[3]/[4] are fixed-total runs): 130 images split 65 + 65 over two
     ranks (uneven per-stream sub-batches inside each rank) give, image for image, the captions of the same 130 images on
     one rank -- compared through the crc32 of the gathered final ids; the line says `scaling: strong`, reports per-rank
-    captions/s, and carries the scale-100 leg under world > 1 too."""
+    captions/s, and carries the scale-100 leg under world > 1 too.  The --dump-outputs files agree as well."""
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    common = ["--steps", "1", "--warmup", "0", "--iters", "2", "--no-cpu-baseline", "--no-invariance", "--no-profile"]
+    common = ["--steps", "1", "--warmup", "0", "--iters", "2", "--full", "--no-cpu-baseline", "--no-invariance", "--no-profile"]
 
     def run(extra):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra + common,
                            capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
         assert r.returncode == 0, r.stderr[-2000:]
         return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
-    one = run(["--gpus", "1", "--images", "130", "--no-alt"])
-    two = run(["--gpus", "2", "--share-gpu", "--total-images", "130"])
+    one = run(["--gpus", "1", "--images", "130", "--no-alt", "--dump-outputs", str(tmp_path / "one")])
+    two = run(["--gpus", "2", "--share-gpu", "--total-images", "130", "--dump-outputs", str(tmp_path / "two")])
     assert two["scaling"] == "strong" and one["scaling"] == "weak"
     assert two["config"]["total_images"] == 130 and two["ranks"]["per_rank_images"] == [65, 65]
     assert len(two["ranks"]["per_rank_captions_per_s"]) == 2 and min(two["ranks"]["per_rank_captions_per_s"]) > 0
@@ -184,6 +196,10 @@ def test_bench_strong_scaling_two_ranks_reproduce_the_one_rank_captions():
     assert two["captions_crc32"]["value"] == one["captions_crc32"]["value"]
     assert two["scale100_mode"]["value"] > 0 and two["scale100_mode"]["steps"] == two["steps"]
     assert abs(two["value"] - sum(two["ranks"]["per_rank_captions_per_s"])) / two["value"] < 0.2
+    for name in ("ids", "image_index"):
+        np.testing.assert_array_equal(np.load(tmp_path / "one" / f"{name}.npy"), np.load(tmp_path / "two" / f"{name}.npy"))
+    for name in ("cos", "image_embeds"):
+        np.testing.assert_allclose(np.load(tmp_path / "one" / f"{name}.npy"), np.load(tmp_path / "two" / f"{name}.npy"), atol=1e-4)
 
 
 def test_bench_config3_preset_with_samples_reproduces_the_one_rank_captions():
@@ -193,7 +209,7 @@ def test_bench_config3_preset_with_samples_reproduces_the_one_rank_captions():
     last sample's final ids), and the line names the preset and the sample count."""
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    common = ["--config", "3", "--total-images", "64", "--steps", "1", "--warmup", "0", "--iters", "1", "--no-cpu-baseline",
+    common = ["--config", "3", "--total-images", "64", "--steps", "1", "--warmup", "0", "--iters", "1", "--full", "--no-cpu-baseline",
               "--no-invariance", "--no-profile", "--no-alt"]
 
     def run(extra):
@@ -225,7 +241,7 @@ def test_bench_eight_ranks_on_a_shared_gpu_reproduce_the_one_rank_captions():
     host share of each rank)."""
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "LOCAL_WORLD_SIZE")}
-    common = ["--steps", "1", "--warmup", "0", "--iters", "1", "--no-cpu-baseline", "--no-invariance", "--no-profile", "--no-alt"]
+    common = ["--steps", "1", "--warmup", "0", "--iters", "1", "--full", "--no-cpu-baseline", "--no-invariance", "--no-profile", "--no-alt"]
 
     def run(extra):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra + common,

@@ -363,6 +363,40 @@ def test_bench_line_bookkeeping_follows_the_shape_it_ran():
         assert j["metric"] == bench.metric_name(c["sentence_len"], c["candidate_k"], c["order"], c["gamma"], c["samples_num"]), path
 
 
+def test_bench_dump_outputs_types_and_size_limit(tmp_path):
+    """bench.py --dump-outputs: float32 / float64 files only, token ids exact, every image while the files fit, beyond the
+    byte limit the same seeded sample of images on every call, and the files together never above the limit."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    rng = np.random.default_rng(3)
+    B, S, T = 40, 3, 16
+    emb = rng.standard_normal((B, 512)).astype(np.float32)
+    ids = rng.integers(0, 30522, size=(2, S, B, T)).astype(np.int32)
+    cos = rng.standard_normal((2, S, B)).astype(np.float32)
+
+    def load(d):
+        return {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+    bench.dump_outputs(str(tmp_path / "all"), emb, ids, cos)
+    a = load(tmp_path / "all")
+    assert sorted(a) == ["cos", "ids", "image_embeds", "image_index"]
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    np.testing.assert_array_equal(a["ids"], ids)
+    np.testing.assert_array_equal(a["image_embeds"], emb)
+    np.testing.assert_array_equal(a["cos"], cos)
+    np.testing.assert_array_equal(a["image_index"], np.arange(B))
+    limit = 4096 + 10 * (512 * 4 + 2 * S * T * 8 + 2 * S * 4 + 8)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), emb, ids, cos, limit=limit)
+    s1, s2 = load(tmp_path / "s1"), load(tmp_path / "s2")
+    keep = s1["image_index"].astype(np.int64)
+    assert len(keep) == 10 and (np.diff(keep) > 0).all()
+    np.testing.assert_array_equal(s2["image_index"], s1["image_index"])
+    np.testing.assert_array_equal(s1["ids"], ids[:, :, keep])
+    np.testing.assert_array_equal(s1["image_embeds"], emb[keep])
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1")) <= limit
+
+
 def test_image_cache_key_follows_the_pixels_not_only_the_object():
     """The drop-in CLIP caches the last batch's embeddings per image OBJECT (demo.py:83 polishes one image samples_num
     times); a caller that refills the same buffer in place must not get the old embeddings back."""

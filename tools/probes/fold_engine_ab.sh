@@ -2,7 +2,7 @@
 # the LayerNorm fold inside the engine, both arms on one box: captions/s (two streams, 3 steps) and rocprofv3 kernel stats of a one-stream pass
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/r05t; mkdir -p $O
-C="--steps 3 --warmup 1 --no-cpu-baseline --no-alt --no-invariance"
+C="--steps 3 --warmup 1 --full --no-cpu-baseline --no-alt --no-invariance"
 for rep in 1 2; do for arm in 0 1; do
   python bench.py $C --opt fold_ln=$arm > $O/b_fold${arm}_$rep.json 2> $O/b.err
 done; done

@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 export CZC_NORMAL_EXIT=1
 O=gpurun_out/r03p
 mkdir -p $O
-COMMON="--no-cpu-baseline --no-alt --no-invariance"
+COMMON="--full --no-cpu-baseline --no-alt --no-invariance"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bf16_1s -o p -- python bench.py --streams 1 --steps 2 --warmup 1 $COMMON > $O/bf16_1s.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bf16_2s -o p -- python bench.py --steps 2 --warmup 1 --no-profile $COMMON > $O/bf16_2s.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/refine_1s -o p -- python bench.py --precision refine --logit-scale 4.6052 --streams 1 --steps 2 --warmup 1 $COMMON > $O/refine_1s.log 2>&1

@@ -10,18 +10,18 @@ O=gpurun_out/r05e
 mkdir -p $O
 if [ "$1" != "quick" ]; then
   python -m pytest tests -m gpu -q > $O/gpu_tests_summary.txt 2>&1
-  python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err
 fi
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
-python bench.py --config 1 --steps 3 --no-alt > $O/bench_cfg1.json 2> $O/bench_cfg1.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --config 1 --steps 3 --full --no-alt > $O/bench_cfg1.json 2> $O/bench_cfg1.err
 if [ "$1" != "kernels" ]; then
-python bench.py --config 3 --total-images 256 --steps 1 --warmup 1 --no-cpu-baseline > $O/bench_cfg3.json 2> $O/bench_cfg3.err
-python bench.py --config 4 --total-images 64 --control both --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_cfg4.json 2> $O/bench_cfg4.err
+python bench.py --config 3 --total-images 256 --steps 1 --warmup 1 --full --no-cpu-baseline > $O/bench_cfg3.json 2> $O/bench_cfg3.err
+python bench.py --config 4 --total-images 64 --control both --steps 2 --warmup 1 --full --no-cpu-baseline > $O/bench_cfg4.json 2> $O/bench_cfg4.err
 python tools/refine_validate.py 128 10 12 2000 > $O/refine_validate_128x10.jsonl 2> $O/refine_validate.err
 if [ "$1" != "quick" ]; then GEN_SWEEPS=10 python tools/refine_validate.py 256 10 12 2000 > $O/refine_validate_256x10_fullcaptions.jsonl 2>> $O/refine_validate.err; fi
 fi
 export CZC_NORMAL_EXIT=1
-COMMON="--no-cpu-baseline --no-alt --no-invariance"
+COMMON="--full --no-cpu-baseline --no-alt --no-invariance"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bf16_1s -o p -- python bench.py --streams 1 --steps 2 --warmup 1 $COMMON > $O/bf16_1s.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bf16_2s -o p -- python bench.py --steps 2 --warmup 1 $COMMON > $O/bf16_2s.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/refine_1s -o p -- python bench.py --precision refine --logit-scale 4.6052 --streams 1 --steps 2 --warmup 1 $COMMON > $O/refine_1s.log 2>&1

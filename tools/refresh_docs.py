@@ -186,7 +186,7 @@ KERNELS = [
 
 def block_kernels(f):
     """what runs in one caption batch of configs[2] on ONE stream, from the rocprofv3 kernel stats of
-    `bench.py --streams 1 --steps 2 --warmup 1` (4 caption batches in the process) and the workload's row counts."""
+    `bench.py --streams 1 --steps 2 --warmup 1 --full` (4 caption batches in the process) and the workload's row counts."""
     import csv
     path = os.path.join(P, f"{ROUND}_bench_bf16_kernel_stats.csv")
     dflt = jload(f"{ROUND}_bench_default.json") or jload(f"{ROUND}_bench_driver_cmd.json")

@@ -154,6 +154,11 @@ struct czc_engine {
   // nltk scorer where it is installed) between the two halves of a step; replaces the table look-ups of the bridge kernel
   czc_control_fn ctl_fn = nullptr; void* ctl_user = nullptr;
   int32_t* h_ctl_ids = nullptr; float* h_ctl_scores = nullptr; size_t h_ctl_cap = 0;  // pinned: [B*T + B*K] ids, [B*K] scores
+  // option "memo" (czc_generate only; memo.hip): a step runs only for the images whose masked row differs from the one they
+  // had on their last visit of the same (position, n_mask) key in this call; the others take the entry's row and cosine back
+  int memo = 0;
+  int memo_branch_floor = 0;  // compacted step: longest branch the HIT images had (the full batch's attention-kernel choice)
+  int64_t stat_memo_hits = 0, stat_memo_images = 0;  // image-steps that took an entry / all image-steps of memo calls
 };
 
 namespace {
@@ -660,6 +665,9 @@ int clip_tower(czc_engine* e, const int* cids, int B, int K, int share, int M, i
 int read_totals(czc_engine* e, int* M, int* max_len, int* max_branch, int* n_trunk) {
   const czc_config& c = e->cfg;
   *M = e->h_totals[0]; *max_len = e->h_totals[3]; *max_branch = e->h_totals[4]; *n_trunk = e->h_totals[6];
+  // a compacted memo step: a branch longer than 32 rows among the images it skipped would have sent the full batch's launch
+  // to the per-segment attention kernel, so it goes there too (round 3: the one batch coupling of the text tower)
+  if (e->memo_branch_floor > 32 && *max_branch < e->memo_branch_floor) *max_branch = e->memo_branch_floor;
   e->plan_pairs = (double)e->h_totals[7];
   if (e->h_totals[8]) return fail(e, CZC_ERR_OVERFLOW, "non-finite CLIP cosine: an fp16 quantity overflowed in a tower (fp16 residual rows: set option resid16 = 0 on the bf16 engine, refine_rows16 = 0 on the refine engine; fp16 operands: use CZC_PREC_SPLIT)%s");
   if (e->h_totals[2]) return fail(e, CZC_ERR_OVERFLOW, "text bridge overflow (row text > CZC_BRIDGE_MAX_BYTES)%s");
@@ -901,6 +909,117 @@ void free_layer_set(std::vector<LayerW>& L) {
   L.clear();
 }
 
+// ---- option "memo" (czc_generate): the step memo of memo.hip ----------------------------------------------------------
+// A step group is one n_mask >= 1 step plus the n_mask = 0 steps that re-use its forward (span order: 2 then 0,
+// gen_utils.py:160-179).  Its key is the (position, n_mask) list of its steps; an image's entry at that key holds the masked
+// row of the group's first step (which fixes the outcome of every step of the group), the row and winner cosine each step
+// left, and each step's longest CLIP branch.  Entries live for one call.
+constexpr int MEMO_SUB = 2;  // steps per group the entry has room for (a longer group runs without the memo)
+struct MemoPlan {
+  std::vector<int> slot, sub;  // per step: entry slot of its group (-1: never memoised), index inside the group
+  std::vector<char> check;     // per group-start step: the host knows the key was visited before and the step may hit
+  std::vector<int> group_len;  // per group-start step
+  int *key = nullptr, *rows = nullptr, *imax = nullptr, *hit = nullptr, *list = nullptr, *tot = nullptr, *inp_c = nullptr;
+  float *cos = nullptr, *bcos = nullptr, *img_c = nullptr;
+  int n_act = 0;  // of the group in progress
+  int branch_max[MEMO_SUB] = {0, 0};
+};
+
+int memo_begin(czc_engine* e, int B, int T, int n_steps, const int32_t* positions, const int32_t* n_mask, int snapshot_every,
+               bool want_cos, const std::vector<char>& audit, MemoPlan* mp) {
+  mp->slot.assign(n_steps, -1); mp->sub.assign(n_steps, 0); mp->check.assign(n_steps, 0); mp->group_len.assign(n_steps, 0);
+  std::map<std::vector<int>, int> slots;
+  for (int s = 0; s < n_steps;) {
+    int g = 1;
+    while (s + g < n_steps && n_mask && n_mask[s + g] <= 0) ++g;
+    const int nm0 = n_mask ? n_mask[s] : 1;
+    mp->group_len[s] = g;
+    for (int j = 0; j < g; ++j) mp->sub[s + j] = j;
+    if (nm0 >= 1 && g <= MEMO_SUB) {
+      std::vector<int> key;
+      bool hittable = true;
+      for (int j = 0; j < g; ++j) {
+        key.push_back(positions[s + j]); key.push_back(n_mask ? n_mask[s + j] : 1);
+        // CZC_PREC_REFINE: audit steps keep the guard on every image, and a step whose winner cosine the call returns takes
+        // it from a split re-encode whose last bits can depend on which other candidates were re-encoded with the winner
+        const bool cos_out = want_cos && (s + j + 1) % snapshot_every == 0;
+        if (e->refine && (audit[s + j] || cos_out)) hittable = false;
+      }
+      auto it = slots.find(key);
+      const bool seen = it != slots.end();
+      const int sl = seen ? it->second : (int)slots.size();
+      if (!seen) slots[key] = sl;
+      for (int j = 0; j < g; ++j) mp->slot[s + j] = sl;
+      mp->check[s] = seen && hittable;
+    }
+    s += g;
+  }
+  const size_t n_slots = slots.size() ? slots.size() : 1, D = (size_t)e->cfg.clip_proj;
+  E_CHECK(ensure(e, "m_key", n_slots * B * T * 4, (void**)&mp->key));
+  E_CHECK(ensure(e, "m_rows", n_slots * MEMO_SUB * B * T * 4, (void**)&mp->rows));
+  E_CHECK(ensure(e, "m_cos", n_slots * MEMO_SUB * B * 4, (void**)&mp->cos));
+  E_CHECK(ensure(e, "m_imax", n_slots * MEMO_SUB * B * 4, (void**)&mp->imax));
+  E_CHECK(ensure(e, "m_hit", (size_t)B * 4, (void**)&mp->hit));
+  E_CHECK(ensure(e, "m_list", (size_t)B * 4, (void**)&mp->list));
+  E_CHECK(ensure(e, "m_tot", 16, (void**)&mp->tot));
+  E_CHECK(ensure(e, "m_bcos", (size_t)B * 4, (void**)&mp->bcos));
+  E_CHECK(ensure(e, "m_inp_c", (size_t)B * T * 4, (void**)&mp->inp_c));
+  E_CHECK(ensure(e, "m_img_c", (size_t)B * D * 4, (void**)&mp->img_c));
+  return 0;
+}
+
+// One step of czc_generate with the memo on.  First step of a group whose key this call has seen: the check kernel and one
+// 16-byte read (the second host round trip of such a step) give the active images; then all of them run as usual (and
+// record), none of them runs (BERT, the towers and the combine kernel are skipped), or the step runs on a compact batch of
+// them.  The group's other steps keep its active set: the n_mask = 0 step re-uses the forward of exactly those rows.
+int memo_step(czc_engine* e, MemoPlan& mp, int s, int* d_inp, int B, int T, int gen_idx, int n_mask, int dot_allowed, int K,
+              const czc_hyper* hp) {
+  const int slot = mp.slot[s], j = mp.sub[s], mask_id = e->cfg.mask_id, D = e->cfg.clip_proj;
+  int* key = slot >= 0 ? mp.key + (size_t)slot * B * T : nullptr;
+  int* rows = slot >= 0 ? mp.rows + ((size_t)slot * MEMO_SUB + j) * B * T : nullptr;
+  float* cos = slot >= 0 ? mp.cos + ((size_t)slot * MEMO_SUB + j) * B : nullptr;
+  int* imax = slot >= 0 ? mp.imax + ((size_t)slot * MEMO_SUB + j) * B : nullptr;
+  if (j == 0) {
+    mp.n_act = B;
+    mp.branch_max[0] = mp.branch_max[1] = 0;
+    if (mp.check[s]) {
+      E_CHECK(launch_memo_check(d_inp, B, T, gen_idx, n_mask, mask_id, key, mp.imax + (size_t)slot * MEMO_SUB * B, mp.group_len[s],
+                                mp.hit, mp.list, mp.tot, e->st));
+      E_HIP(hipMemcpyAsync(e->h_totals + 32, mp.tot, 16, hipMemcpyDeviceToHost, e->st));
+      E_HIP(hipStreamSynchronize(e->st));
+      mp.n_act = e->h_totals[32];
+      mp.branch_max[0] = e->h_totals[33]; mp.branch_max[1] = e->h_totals[34];
+      if (mp.n_act < 0 || mp.n_act > B) return fail(e, CZC_ERR_STATE, "memo check returned an impossible count%s");
+      // the split-fp16 text tower picks its GEMM forms (split-K slices, ring / tiled kernels) by row count, so a compact batch
+      // moves its cosines in the last bits: that engine skips the steps every image hits and runs the others whole
+      if (e->pc == PREC_F16X3 && mp.n_act > 0) mp.n_act = B;
+    }
+  }
+  const int n_act = mp.n_act;
+  e->stat_memo_images += B;
+  e->stat_memo_hits += B - n_act;
+  if (n_act < B) E_CHECK(launch_memo_fill(mp.hit, B, T, rows, cos, d_inp, mp.bcos, e->st));
+  if (n_act == 0) return 0;
+  if (n_act == B) {  // the whole batch, in place, as without the memo; then the entry is recorded
+    if (key && j == 0) E_CHECK(launch_memo_gather(d_inp, nullptr, B, T, gen_idx, n_mask, mask_id, key, nullptr, nullptr, D, nullptr, e->st));
+    E_CHECK(step_device(e, d_inp, B, T, gen_idx, n_mask, dot_allowed, K, hp));
+    return launch_memo_scatter(d_inp, (const float*)e->ws["s_bcos"].p, (const int*)e->ws["p_img_max"].p, nullptr, B, T, d_inp,
+                               mp.bcos, rows, cos, imax, e->st) ? fail(e, CZC_ERR_HIP, "%s", g_err) : 0;
+  }
+  // compact batch: rows and normalised image embeds of the active images, the step on them (step_device needs image embeds
+  // of its own batch size), then their rows and cosines back into the full batch and into the entry
+  E_CHECK(launch_memo_gather(d_inp, mp.list, n_act, T, gen_idx, n_mask, mask_id, j == 0 ? key : nullptr, mp.inp_c, e->d_img_n, D,
+                             mp.img_c, e->st));
+  float* img_full = e->d_img_n;
+  const int img_B = e->img_B;
+  e->d_img_n = mp.img_c; e->img_B = n_act; e->memo_branch_floor = mp.branch_max[j];
+  const int rc = step_device(e, mp.inp_c, n_act, T, gen_idx, n_mask, dot_allowed, K, hp);
+  e->d_img_n = img_full; e->img_B = img_B; e->memo_branch_floor = 0;
+  E_CHECK(rc);
+  return launch_memo_scatter(mp.inp_c, (const float*)e->ws["s_bcos"].p, (const int*)e->ws["p_img_max"].p, mp.list, n_act, T, d_inp,
+                             mp.bcos, rows, cos, imax, e->st) ? fail(e, CZC_ERR_HIP, "%s", g_err) : 0;
+}
+
 }  // namespace
 
 // =================================================================================================
@@ -995,6 +1114,7 @@ int czc_replicate(czc_engine* p, czc_engine** out) {
   e->refine = p->refine; e->refine_theta_x = p->refine_theta_x; e->refine_samples = p->refine_samples; e->refine_samples_step = p->refine_samples_step;
   e->refine_guard_dev = p->refine_guard_dev; e->refine_gate_delta = p->refine_gate_delta; e->refine_theta_gen = p->refine_theta_gen;
   e->refine_rows16 = p->refine_rows16; e->refine_rows16_factor = p->refine_rows16_factor;
+  e->memo = p->memo;
   e->w = p->w; e->bert = p->bert; e->ctext = p->ctext; e->cvis = p->cvis; e->ctext_x = p->ctext_x;
   e->mlm_dense_w = p->mlm_dense_w; e->decoder_w = p->decoder_w; e->tproj_w = p->tproj_w; e->vproj_w = p->vproj_w;
   e->patch_w = p->patch_w; e->tproj_wx = p->tproj_wx;
@@ -1430,33 +1550,40 @@ int czc_generate(czc_engine* e, int B, int T, int L, int seed_len, const int32_t
   E_CHECK(ensure(e, "g_row", (size_t)T * 4, (void**)&d_row));
   E_HIP(hipMemcpyAsync(d_row, init_ids_host, (size_t)T * 4, hipMemcpyHostToDevice, e->st));
   E_CHECK(launch_broadcast_rows_i32(d_row, T, B, d_inp, e->st));
+  for (int s = 0; s < n_steps; ++s)
+    if (positions_host[s] < 0 || positions_host[s] >= L) return fail(e, CZC_ERR_ARG, "generate: position out of range%s");
+  // what this call returns of a step: the ids it leaves in d_inp and, at the snapshot steps, the winner's cosine
+  // AUDIT steps -- the snapshot step of every fourth sweep, starting with the first -- take the full selection for every
+  // image: there the guard (czc_refine_guard) measures the screening tower on all images although most other steps are
+  // gated (a checkpoint the fp16 tower carries badly trips it in the first sweep).  At the other snapshot steps a gated
+  // image re-encodes its winner alone, for the cosine this call returns.  The gate is the guard's dependant: with the guard
+  // switched off (refine_guard_x1e6 = 0) nothing polices the bound the gate rests on, so nothing is gated
+  // (whether or not the caller reads cosines: the guard must see the screening tower on every call -- and a call too short
+  // to reach a snapshot step is audited at its last step)
+  std::vector<char> audit(n_steps, 0);
+  { bool audited = false;
+    for (int s = 0; s < n_steps; ++s) {
+      const bool snap_idx = (s + 1) % snapshot_every == 0;
+      audit[s] = (snap_idx && (s / snapshot_every) % 4 == 0) || (s + 1 == n_steps && !audited);
+      audited = audited || audit[s];
+    } }
+  MemoPlan mp;
+  if (e->memo) E_CHECK(memo_begin(e, B, T, n_steps, positions_host, n_mask_host, snapshot_every, out_cos != nullptr, audit, &mp));
   int snap = 0;
-  bool audited = false;
   for (int s = 0; s < n_steps; ++s) {
     const int pos = positions_host[s];
-    if (pos < 0 || pos >= L) return fail(e, CZC_ERR_ARG, "generate: position out of range%s");
     const int nm = n_mask_host ? n_mask_host[s] : 1;
-    // what this call returns of a step: the ids it leaves in d_inp and, at the snapshot steps, the winner's cosine
-    // AUDIT steps -- the snapshot step of every fourth sweep, starting with the first -- take the full selection for every
-    // image: there the guard (czc_refine_guard) measures the screening tower on all images although most other steps are
-    // gated (a checkpoint the fp16 tower carries badly trips it in the first sweep).  At the other snapshot steps a gated
-    // image re-encodes its winner alone, for the cosine this call returns.  The gate is the guard's dependant: with the guard
-    // switched off (refine_guard_x1e6 = 0) nothing polices the bound the gate rests on, so nothing is gated
     const bool snap_idx = (s + 1) % snapshot_every == 0;
-    const bool snap_step = snap_idx && out_cos != nullptr;
-    // (whether or not the caller reads cosines: the guard must see the screening tower on every call -- and a call too short
-    // to reach a snapshot step is audited at its last step)
-    const bool audit = (snap_idx && (s / snapshot_every) % 4 == 0) || (s + 1 == n_steps && !audited);
-    audited = audited || audit;
-    e->gate_now = e->refine && e->refine_gate_delta > 0.f && e->refine_guard_dev > 0.f && !audit;
-    e->gate_need_cos = snap_step;
+    e->gate_now = e->refine && e->refine_gate_delta > 0.f && e->refine_guard_dev > 0.f && !audit[s];
+    e->gate_need_cos = snap_idx && out_cos != nullptr;
     e->in_generate = true;
-    E_CHECK(step_device(e, d_inp, B, T, seed_len + pos, nm, pos == L - 1 ? 1 : 0, top_k, hp));
-    if ((s + 1) % snapshot_every == 0) {
+    if (e->memo) E_CHECK(memo_step(e, mp, s, d_inp, B, T, seed_len + pos, nm, pos == L - 1 ? 1 : 0, top_k, hp));
+    else E_CHECK(step_device(e, d_inp, B, T, seed_len + pos, nm, pos == L - 1 ? 1 : 0, top_k, hp));
+    if (snap_idx) {
       if (out_ids)
         E_HIP(hipMemcpyAsync(out_ids + (size_t)snap * B * T, d_inp, (size_t)B * T * 4, hipMemcpyDefault, e->st));
-      if (out_cos)
-        E_HIP(hipMemcpyAsync(out_cos + (size_t)snap * B, e->ws["s_bcos"].p, (size_t)B * 4, hipMemcpyDefault, e->st));
+      if (out_cos)  // memo: the full-batch cosines (a compacted step leaves B_act of them in s_bcos)
+        E_HIP(hipMemcpyAsync(out_cos + (size_t)snap * B, e->memo ? mp.bcos : e->ws["s_bcos"].p, (size_t)B * 4, hipMemcpyDefault, e->st));
       ++snap;
     }
   }
@@ -1498,6 +1625,7 @@ int czc_set_option(czc_engine* e, const char* name, int value) {
   if (!strcmp(name, "refine_guard_x1e6")) { e->refine_guard_dev = (float)value * 1e-6f; return CZC_OK; }
   if (!strcmp(name, "refine_gate_x1e6")) { e->refine_gate_delta = value < 0 ? 0.f : (float)value * 1e-6f; return CZC_OK; }
   if (!strcmp(name, "refine_rows16")) { const int old = e->refine_rows16; e->refine_rows16 = value ? 1 : 0; const int rc = fold_ready(); if (rc) e->refine_rows16 = old; return rc; }
+  if (!strcmp(name, "memo")) { e->memo = value ? 1 : 0; return CZC_OK; }
   if (!strcmp(name, "refine_rows16_x1000")) { e->refine_rows16_factor = value < 1000 ? 1.f : (float)value / 1000.f; return CZC_OK; }
   return fail(e, CZC_ERR_ARG, "unknown option %s", name);
 }
@@ -1512,7 +1640,7 @@ int czc_get_option(czc_engine* e, const char* name, int* value) {
       {"refine_samples", e->refine_samples}, {"refine_samples_step", e->refine_samples_step}, {"refine_theta_x1000", (int)lrintf(e->refine_theta_x * 1000.f)},
       {"refine_theta_gen_x1000", (int)lrintf(e->refine_theta_gen * 1000.f)},
       {"refine_guard_x1e6", (int)lrintf(e->refine_guard_dev * 1e6f)}, {"refine_gate_x1e6", (int)lrintf(e->refine_gate_delta * 1e6f)},
-      {"refine_rows16", e->refine_rows16}, {"refine_rows16_x1000", (int)lrintf(e->refine_rows16_factor * 1000.f)},
+      {"refine_rows16", e->refine_rows16}, {"memo", e->memo}, {"refine_rows16_x1000", (int)lrintf(e->refine_rows16_factor * 1000.f)},
       // read-only, derived: the trip point / gate bound in force inside czc_generate (x refine_rows16_factor on fp16 rows)
       {"refine_guard_generate_x1e6", (int)lrintf(e->refine_guard_dev * f16x * 1e6f)},
       {"refine_gate_generate_x1e6", (int)lrintf(e->refine_gate_delta * f16x * 1e6f)},
@@ -1546,6 +1674,7 @@ int czc_profile_reset(czc_engine* e) {
   e->stat_refine_rows = e->stat_refine_seqs = 0;
   e->stat_dedup_seqs = 0;
   e->stat_gated = e->stat_gate_images = 0;
+  e->stat_memo_hits = e->stat_memo_images = 0;
   return CZC_OK;
 }
 
@@ -1626,6 +1755,13 @@ int czc_refine_gate_stats(czc_engine* e, int64_t* gated, int64_t* image_steps) {
   if (!e) return CZC_ERR_ARG;
   if (gated) *gated = e->stat_gated;
   if (image_steps) *image_steps = e->stat_gate_images;
+  return CZC_OK;
+}
+
+int czc_memo_stats(czc_engine* e, int64_t* hit_image_steps, int64_t* image_steps) {
+  if (!e) return CZC_ERR_ARG;
+  if (hit_image_steps) *hit_image_steps = e->stat_memo_hits;
+  if (image_steps) *image_steps = e->stat_memo_images;
   return CZC_OK;
 }
 

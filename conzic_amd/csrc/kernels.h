@@ -124,6 +124,22 @@ int launch_l2_normalize(const float* x, int M, int D, float* y, hipStream_t st);
 int launch_mask_positions(int* inp, int B, int T, int gen_idx, int n_mask, int mask_id, hipStream_t st);
 int launch_broadcast_rows_i32(const int* row, int T, int B, int* dst, hipStream_t st);
 
+// ---- memo.hip (czc_generate option "memo") --------------------------------------------------------------------------
+// check: hit[b] = (d_inp[b] with columns gen_idx .. gen_idx+n_mask-1 set to mask_id) == key[b]; list = the other images in
+// ascending order; tot[0] = their count, tot[1 + j] = max over the hit images of img_max[j * B + b] (j < n_sub <= 2)
+int launch_memo_check(const int* inp, int B, int T, int gen_idx, int n_mask, int mask_id, const int* key, const int* img_max,
+                      int n_sub, int* hit, int* list, int* tot, hipStream_t st);
+// for i < n, b = list ? list[i] : i: key[b] = masked row b; inp_c[i] = row b; img_c[i] = img_n[b] (each output may be null)
+int launch_memo_gather(const int* inp, const int* list, int n, int T, int gen_idx, int n_mask, int mask_id, int* key, int* inp_c,
+                       const float* img_n, int D, float* img_c, hipStream_t st);
+// for i < n, b = list ? list[i] : i: (list) inp[b] = rows[i]; bcos_full[b] = bcos[i]; out_rows[b] = rows[i], out_cos[b] =
+// bcos[i], out_max[b] = img_max[i] (each record may be null)
+int launch_memo_scatter(const int* rows, const float* bcos, const int* img_max, const int* list, int n, int T, int* inp,
+                        float* bcos_full, int* out_rows, float* out_cos, int* out_max, hipStream_t st);
+// images with hit[b]: inp[b] = out_rows[b], bcos_full[b] = out_cos[b]
+int launch_memo_fill(const int* hit, int B, int T, const int* out_rows, const float* out_cos, int* inp, float* bcos_full,
+                     hipStream_t st);
+
 // ---- attention.hip ------------------------------------------------------------------------
 // Segment s = `own_len[s]` rows starting at own_off[s] (queries and keys/values) preceded by
 // `pre_len[s]` key/value-only rows starting at pre_off[s] (the shared causal prefix of an image's

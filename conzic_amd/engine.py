@@ -394,6 +394,13 @@ class Engine:
         return dict(clip_rows=a.value, clip_seqs=b.value, bert_rows=c_.value, steps=d.value, refine_seqs=rs.value,
                     refine_rows=rr.value, gated_image_steps=g.value, gate_image_steps=gi.value, dedup_seqs=dd.value)
 
+    def memo_stats(self):
+        """Option "memo" (czc_memo_stats): image-steps of memo-on czc_generate calls since profile_reset, and how many of them
+        took a memo entry instead of running."""
+        h, n = C.c_int64(), C.c_int64()
+        self._ck(self.lib.czc_memo_stats(self.h, C.byref(h), C.byref(n)), "czc_memo_stats")
+        return dict(hit_image_steps=h.value, image_steps=n.value)
+
     def refine_guard(self, reset: bool = True):
         """(max |screening error - mean| seen on re-encoded candidates, image-steps above the trip point) of a
         CZC_PREC_REFINE engine since the last reset (czc_refine_guard)."""
@@ -517,6 +524,10 @@ class EngineGroup:
     def stats(self):
         ss = [e.stats() for e in self.engines]
         return {k: sum(s_[k] for s_ in ss) for k in ss[0]}
+
+    def memo_stats(self):
+        ms = [e.memo_stats() for e in self.engines]
+        return {k: sum(m[k] for m in ms) for k in ms[0]}
 
     def refine_guard(self, reset: bool = True):
         gs = [e.refine_guard(reset) for e in self.engines]

@@ -139,3 +139,94 @@ def first_divergence(engine, emb_row, init_row, ref_snaps, got_snaps, L, seed_le
     gap = float(srt[0] - fin[where].max()) if where.size else None
     return dict(sweep=s, position=int(order[p_idx]), reference_top2_margin=float(srt[0] - srt[1]),
                 gap_to_other_engines_choice=gap, other_choice_rank=(int((fin > fin[where].max()).sum()) if where.size else None))
+
+
+# ---- option "memo" (czc_generate's exact step memo) ------------------------------------------------------------------------
+MEMO_SUB = 2  # steps per (n_mask >= 1 step + its n_mask = 0 followers) group the engine's entries hold (engine.hip)
+
+
+def memo_groups(n_mask, n_steps: int):
+    """[(first step, number of steps)] of the step groups of czc_generate: one n_mask >= 1 step and the n_mask = 0 steps that
+    re-use its forward (span order, gen_utils.py:160-179)."""
+    nm = [1] * n_steps if n_mask is None else [int(x) for x in n_mask]
+    out, s = [], 0
+    while s < n_steps:
+        g = 1
+        while s + g < n_steps and nm[s + g] <= 0:
+            g += 1
+        out.append((s, g))
+        s += g
+    return out
+
+
+def memo_refine_no_hit(n_steps: int, snapshot_every: int, want_cos: bool = True) -> np.ndarray:
+    """Steps of a CZC_PREC_REFINE czc_generate call that never hit (include/conzic_hip.h, option "memo"): its audit steps and
+    the steps whose winner cosine the call returns."""
+    never = np.zeros(n_steps, bool)
+    audited = False
+    for s in range(n_steps):
+        snap = (s + 1) % snapshot_every == 0
+        audit = (snap and (s // snapshot_every) % 4 == 0) or (s + 1 == n_steps and not audited)
+        audited = audited or audit
+        never[s] = audit or (snap and want_cos)
+    return never
+
+
+def memo_expected_hits(snapshots, positions, n_mask, seed_len: int, mask_id: int, never=None) -> np.ndarray:
+    """The memo rule stated on the host.  `snapshots` int32 [n_steps, B, T]: a memo-OFF trajectory recorded with
+    snapshot_every = 1 (row of every image after every step).  Returns bool [n_steps, B]: whether image b hits at step s
+    (the engine's czc_memo_stats counts their sum).
+
+    Step s at position p with n_mask = m >= 1 sees R_s(b) = the row before the step with columns seed_len+p .. seed_len+p+m-1
+    set to [MASK].  Its key is the (position, n_mask) list of its group (the step and the n_mask = 0 steps that follow it);
+    image b hits when an earlier group of the call had the same key and left R(b) equal to R_s(b), bit for bit.  Every step
+    of a group hits with its first step; a group with more than MEMO_SUB steps, a group that does not start with n_mask >= 1
+    and a group with a step in `never` (bool [n_steps]) do not hit.  Every visit replaces the entry."""
+    snaps = np.asarray(snapshots)
+    n_steps, B, T = snaps.shape
+    assert len(positions) == n_steps
+    nm = [1] * n_steps if n_mask is None else [int(x) for x in n_mask]
+    never = np.zeros(n_steps, bool) if never is None else np.asarray(never, bool)
+    hits = np.zeros((n_steps, B), bool)
+    entries = {}
+    for s, g in memo_groups(nm, n_steps):
+        if nm[s] < 1 or g > MEMO_SUB:
+            continue
+        key = tuple((int(positions[s + j]), nm[s + j]) for j in range(g))
+        # a step writes inside the columns it masked only, so the row it left, masked again, is the row it saw
+        rows = snaps[s].copy()
+        c0 = seed_len + int(positions[s])
+        rows[:, c0:min(c0 + nm[s], T)] = mask_id
+        prev = entries.get(key)
+        if prev is not None and not never[s:s + g].any():
+            hits[s:s + g] = (prev == rows).all(axis=1)[None, :]
+        entries[key] = rows
+    return hits
+
+
+def converging_setup(B: int = 16, L: int = 6, precision: int = native.PREC_BF16, n_hot: int = 150, seed: int = 0,
+                     alpha: float = 0.02, beta: float = 2.0, logit_scale: float = 4.6052, flat_top: int = 8):
+    """Full-size towers with a trained-like MLM head (`n_hot` regular tokens 5.6..16 logit units above a bulk that softmax(logits /
+    0.1) sends to zero, tests/test_step_gpu.py::_peaky_bert_weights), the first `flat_top` of them level at the top so that the
+    CLIP term (published logit scale x100 by default) chooses among them image by image.  The fluency term keeps the choice
+    to a few words: at B = 16, L = 6 every image still moves in sweep 2, about half have reached a fixed point of the polishing
+    sweep during sweep 3, nearly all by sweep 4 -- the step memo's ground, with partly converged batches on the way (flat_top = 0:
+    every image settles in sweep 2).  Returns (setup, image embeds [B, 512], hyper, init row, seed_len)."""
+    bcfg = synth.bert_base()
+    w = synth.make_bert_weights(bcfg, 11)
+    sv = cached_vocab(False)
+    regular = np.nonzero(synth.make_token_mask(sv, regular_only=True)[0] > 0)[0]
+    hot = np.random.default_rng(5).choice(regular, size=n_hot, replace=False)
+    bias = w["cls.predictions.bias"].copy()
+    lift = np.linspace(16.0, 5.6, n_hot).astype(np.float32)
+    lift[:flat_top] = 16.0   # `flat_top` hot tokens share the top logit: the CLIP term picks among them, per image
+    bias[hot] += lift
+    w["cls.predictions.bias"] = bias
+    if "cls.predictions.decoder.bias" in w:
+        w["cls.predictions.decoder.bias"] = bias
+    su = build_synthetic(False, precision, logit_scale=logit_scale, regular_only=True, bert_w=w, bert_cfg=bcfg)
+    emb = np.random.default_rng(100 + seed).standard_normal((B, su.clip_cfg.proj)).astype(np.float32)
+    su.engine.set_image_embeds(emb)
+    prompt = "Image of a"
+    init = np.array(su.bert_tok.encode(prompt + su.bert_tok.mask_token * L), dtype=np.int32)
+    return su, emb, Engine.hyper(alpha, beta, 0.1), init, len(prompt.split()) + 1

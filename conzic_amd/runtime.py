@@ -223,6 +223,18 @@ def _mask_to_numpy(token_mask) -> np.ndarray:
     return np.asarray(token_mask, dtype=np.float32)
 
 
+def memo_setting() -> int:
+    """CZC_MEMO=0|1 (default 0): engine option "memo" of every generation call -- czc_generate runs a step only for the
+    images whose masked row differs from their last visit of the same position in the call (exact: the others would get
+    the same winner and cosine again; include/conzic_hip.h)."""
+    v = os.environ.get("CZC_MEMO", "0").strip().lower()
+    if v in ("0", "", "off", "false", "no"):
+        return 0
+    if v in ("1", "on", "true", "yes"):
+        return 1
+    raise ValueError(f"CZC_MEMO={v!r}: expected 0 or 1")
+
+
 def run_generation(order: str, img_name, model, clip, tokenizer, image_instance, token_mask, prompt, logger, max_len,
                    top_k, temperature, alpha, beta, max_iters, batch_size, verbose=True, gamma=None,
                    ctl_signal="positive", print_every: Optional[int] = None, pos_template=None):
@@ -256,6 +268,7 @@ def run_generation(order: str, img_name, model, clip, tokenizer, image_instance,
     def polish(eng):
         """One whole *_generation call on `eng` (which must hold the batch's image embeddings)."""
         eng.set_token_mask(_mask_to_numpy(token_mask))
+        eng.set_option("memo", memo_setting())  # exact step memo (CZC_MEMO); forwarded to the replicas of a group
         if gamma is not None:
             # control scores: caller-provided tables, else (default, CZC_CONTROL=auto) the reference's own sentence scorer
             # called back per step while the CLIP tower runs, else -- CZC_CONTROL=table -- tables built once per tokenizer

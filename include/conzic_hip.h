@@ -249,7 +249,8 @@ int czc_step(czc_engine* e, int32_t* inp, int B, int T, int gen_idx, int n_mask,
              const czc_hyper* hp, const czc_step_out* out);
 
 /* Throughput granularity: a whole *_generation call with no host round trips except one 8-byte
- * size read per step.  init_ids int32 [T] = `[CLS] prompt [MASK]xL [SEP]` (utils.py:46-51),
+ * size read per step (option "memo": plus one 16-byte read of the active-image count at the first step of a (position,
+ * n_mask) key the call has visited before).  init_ids int32 [T] = `[CLS] prompt [MASK]xL [SEP]` (utils.py:46-51),
  * seed_len = len(prompt.split())+1 (gen_utils.py:56), positions[n_steps] / n_mask[n_steps] as in
  * czc_step, snapshot_every = steps per bookkeeping snapshot (gen_utils.py:82-92).
  * out_ids int32 [n_steps/snapshot_every, B, T], out_cos fp32 [n_steps/snapshot_every, B]
@@ -290,7 +291,35 @@ int czc_generate(czc_engine* e, int B, int T, int L, int seed_len, const int32_t
  *   "refine_rows16"   (1) CZC_PREC_REFINE inside czc_generate: the screening pass on the 2-byte residual stream with the folded
  *                         LayerNorms (the "resid16" + "fold_ln" tower form on fp16 operands); gate bound and guard trip point
  *                         are multiplied by "refine_rows16_x1000" / 1000 (1750) while it is on and the selection's mass threshold
- *                         divided by it.  czc_step is not affected */
+ *                         divided by it.  czc_step is not affected
+ *   "memo"            (0) czc_generate only: exact step memo.  A step at position p with n_mask = m >= 1 sees, per image b, the
+ *                         masked row R(b) = the row with columns seed_len+p .. seed_len+p+m-1 set to [MASK] (what BERT reads).
+ *                         Key (b, p, m): the entry holds R(b) from the image's last visit of the key in this call, the winner
+ *                         id(s) and cosine(s) that visit produced.  An image whose R(b) equals its entry bit for bit (whole row,
+ *                         no hashing) HITS: it does not run, takes the stored winner(s) back (for m = 1 a no-op) and the stored
+ *                         cosine.  The polishing rule is a deterministic argmax (gen_utils.py:66-79) and an image's result does
+ *                         not depend on the other images of the batch, so the outcome is the one the step would compute.  Span
+ *                         order (m = 2 then m = 0, gen_utils.py:160-179): the m = 0 step re-uses the m = 2 forward, hits exactly
+ *                         when its m = 2 step hit, and the m = 2 entry holds both winners and cosines.  Sequential, shuffle and
+ *                         random orders are all m = 1 keyed by position.  The memo lives for one call (cleared at its start;
+ *                         czc_step is not affected).  The first visit of a key runs every image (no check); a later visit runs a
+ *                         check kernel, reads the active count, and runs the step as without the memo (all active), not at all
+ *                         (none: no BERT, no tower, no combine) or on a compact batch of the active images.  What the compact
+ *                         batch keeps: the CLIP-text tower gives every row the same bits at any row count, and a branch longer
+ *                         than 32 rows among the skipped images still sends the launch to the per-segment attention kernel as
+ *                         the full batch would; BERT below 33 rows runs on the K-split skinny kernel (1e-6 relative on the
+ *                         fluency probabilities, 1e-8 on the fused score: an id could only move on a fused-score tie that
+ *                         close, the batch coupling the engine already has).  CZC_PREC_SPLIT: its text tower chooses GEMM forms by
+ *                         row count (last bits of a cosine), so it runs a step whole unless every image hits.  CZC_PREC_REFINE: audit steps and steps
+ *                         whose winner cosine the call returns (snapshot steps with out_cos) never hit -- the guard keeps seeing
+ *                         every image, and that cosine comes from a split re-encode whose last bits can depend on which other
+ *                         candidates were re-encoded with the winner (gated: the winner alone; full selection: ~20 per image).
+ *                         Elsewhere only ids are output.  One case stays theoretical: the last visit took the full selection and
+ *                         this one would have been gated; the two winners agree whenever the gate's bound holds, which the guard
+ *                         polices.  A control callback (czc_set_control_callback) is called for the images that run only: B is
+ *                         the active count and the rows are compacted, so it must be a pure function of its rows (the
+ *                         reference scorer is).  Replicas (czc_replicate) inherit the option and keep memos of their own.
+ *                         czc_memo_stats counts the hits; czc_stats / czc_refine_gate_stats keep counting what ran */
 int czc_set_option(czc_engine* e, const char* name, int value);
 /* Reads an option back (same names and units as czc_set_option), plus three read-only derived values:
  *   "refine_guard_generate_x1e6" / "refine_gate_generate_x1e6": the guard's trip point / the margin gate's bound in force inside
@@ -343,6 +372,10 @@ int czc_refine_stats(czc_engine* e, int64_t* refine_seqs, int64_t* refine_rows);
  * conzic_amd/runtime.py then repeats the call on the all-split engine (CZC_REFINE_GUARD=rerun | warn | off).  Inside czc_generate
  * gated image-steps re-encode nothing and are not measured: the audit steps (czc_refine_gate_stats) are. */
 int czc_refine_guard(czc_engine* e, int reset, float* max_dev, int64_t* tripped);
+/* Option "memo": image-steps of czc_generate calls made with the memo on since czc_profile_reset (*image_steps, B per step), of
+ * which *hit_image_steps took a memo entry instead of running (CZC_PREC_SPLIT: only steps on which every image hits).  Zero with
+ * the option off. */
+int czc_memo_stats(czc_engine* e, int64_t* hit_image_steps, int64_t* image_steps);
 /* CZC_PREC_REFINE engines, margin gate of czc_generate: a whole *_generation call returns the winner's id of every step and
  * the winner's cosine at the snapshot steps (gen_utils.py:78-81, :92), not the K fused scores.  An image-step whose screening
  * (single-pass fp16) winner stays the winner under EVERY assignment of cosine errors |d_k - common| <= delta (delta = option

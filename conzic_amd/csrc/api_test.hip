@@ -43,8 +43,6 @@ static const Hooks& HK() {
 #define g_gemm_small_tiles (*HK().gemm_small_tiles)
 #define g_use_wreg (*HK().use_wreg)
 #define g_use_gemm256s (*HK().use_gemm256s)
-#define g_w_dbg (*HK().w_dbg)
-#define g_ln_lean (*HK().ln_lean)
 #define g_rowln_min_m (*HK().rowln_min_m)
 #define g_wreg_min_m (*HK().wreg_min_m)
 #define g_gemm256_min_m (*HK().gemm256_min_m)
@@ -335,8 +333,6 @@ int czc_test_set_option(const char* name, int value) {
   if (!strcmp(name, "wreg")) { g_use_wreg = value; return 0; }
   if (!strcmp(name, "gemm256s")) { g_use_gemm256s = value; return 0; }
   if (!strcmp(name, "bench_pad")) { g_bench_pad = value; return 0; }
-  if (!strcmp(name, "w_dbg")) { g_w_dbg = value; return 0; }
-  if (!strcmp(name, "ln_lean")) { g_ln_lean = value; return 0; }
   if (!strcmp(name, "rowln_min_m")) { g_rowln_min_m = value; return 0; }
   if (!strcmp(name, "wreg_min_m")) { g_wreg_min_m = value; return 0; }
   if (!strcmp(name, "gemm256_min_m")) { g_gemm256_min_m = value; return 0; }

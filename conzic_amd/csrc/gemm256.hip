@@ -62,9 +62,7 @@ __device__ __forceinline__ float sum8_dpp(float v) {
   return v;
 }
 
-// EPI (A/B experiments of the fp32 path): bit 0 = request the residual rows of block n+1 before block n is processed
-// (two residual register sets), bit 1 = non-temporal residual loads and output stores
-template <int ACT, bool OUT_F32, typename HT = bf16_t, int EPI = 0>
+template <int ACT, bool OUT_F32, typename HT = bf16_t>
 __device__ __forceinline__ void tile_epilogue(const GemmArgs& g, f32x16_t (&acc)[4][2], unsigned char* patch, int m0,
                                               int n0, int wm, int wn, int lane) {
   const int half = lane >> 5;
@@ -111,19 +109,9 @@ __device__ __forceinline__ void tile_epilogue(const GemmArgs& g, f32x16_t (&acc)
         for (int pass = 0; pass < 4; ++pass) {
           const int row = m0 + wm * 128 + i * 32 + pass * 8 + rrow;
           r[pass] = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (g.resid && row < g.M && col < g.N) {
-            const float* p = g.resid + (long)row * g.ldr + col;
-            if (EPI & 2) {
-              const f32x4_t t = __builtin_nontemporal_load((const f32x4_t*)p);
-              r[pass] = make_float4(t[0], t[1], t[2], t[3]);
-            } else {
-              r[pass] = *(const float4*)p;
-            }
-          }
+          if (g.resid && row < g.M && col < g.N) r[pass] = *(const float4*)(g.resid + (long)row * g.ldr + col);
         }
       };
-      float4 rnext[4];
-      if (EPI & 1) load_resid(0, 0, rnext);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
 #pragma unroll
@@ -133,13 +121,7 @@ __device__ __forceinline__ void tile_epilogue(const GemmArgs& g, f32x16_t (&acc)
           if (g.bias && col < g.N) b4 = *(const float4*)(g.bias + col);
           // residual rows first: four independent 16-byte loads in flight across the LDS round trip
           float4 r4[4];
-          if (EPI & 1) {
-#pragma unroll
-            for (int pass = 0; pass < 4; ++pass) r4[pass] = rnext[pass];
-            if (i * 2 + j + 1 < 8) load_resid((i * 2 + j + 1) >> 1, (i * 2 + j + 1) & 1, rnext);
-          } else {
-            load_resid(i, j, r4);
-          }
+          load_resid(i, j, r4);
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             const int slot = (2 * q + half) ^ (l31 & 7);
@@ -155,12 +137,7 @@ __device__ __forceinline__ void tile_epilogue(const GemmArgs& g, f32x16_t (&acc)
             v.x += b4.x; v.y += b4.y; v.z += b4.z; v.w += b4.w;
             v.x = act_fn<ACT>(v.x); v.y = act_fn<ACT>(v.y); v.z = act_fn<ACT>(v.z); v.w = act_fn<ACT>(v.w);
             v.x += r4[pass].x; v.y += r4[pass].y; v.z += r4[pass].z; v.w += r4[pass].w;
-            if (row < g.M && col < g.N) {
-              if (g.out_f32) {
-                if (EPI & 2) __builtin_nontemporal_store(f32x4_t{v.x, v.y, v.z, v.w}, (f32x4_t*)(g.out_f32 + (long)row * g.ldc + col));
-                else *(float4*)(g.out_f32 + (long)row * g.ldc + col) = v;
-              }
-            }
+            if (row < g.M && col < g.N && g.out_f32) *(float4*)(g.out_f32 + (long)row * g.ldc + col) = v;
             pk[pass] = make_uint2(Half<HT>::pack2(v.x, v.y), Half<HT>::pack2(v.z, v.w));
           }
           if (oa) {
@@ -195,8 +172,7 @@ __device__ __forceinline__ void tile_epilogue(const GemmArgs& g, f32x16_t (&acc)
 // (vmcnt = stores of n-1 + loads of n+1 still allowed in flight) never includes a store; rows / columns past the edge
 // are handled by the buffer descriptors (reads return 0, writes are dropped), so there are no branches.
 // Same arithmetic, same order (acc + bias, + residual) as tile_epilogue: bit-identical results.  NJ = 32-column blocks per wave.
-// ABL (timing ablations, EXPERIMENTS build): 1 no residual loads, 2 no output stores
-template <int NJ, int ABL = 0>
+template <int NJ>
 __device__ __forceinline__ void tile_epilogue_f32_asm(const GemmArgs& g, f32x16_t (&acc)[4][NJ], unsigned char* patch, int m0, int n0,
                                                       int wm, int wcol0, int lane) {
   const int half = lane >> 5, l31 = lane & 31, rrow = lane >> 3, rslot = lane & 7;
@@ -236,10 +212,8 @@ __device__ __forceinline__ void tile_epilogue_f32_asm(const GemmArgs& g, f32x16_
   f32x4_t rr[2][4];
   auto load_resid = [&](int blk, f32x4_t (&r)[4]) {
 #pragma unroll
-    for (int pass = 0; pass < 4; ++pass) {
-      if (ABL & 1) asm volatile("v_mov_b32 %0, 0\n\tv_mov_b32 %1, 0\n\tv_mov_b32 %2, 0\n\tv_mov_b32 %3, 0" : "=v"(r[pass][0]), "=v"(r[pass][1]), "=v"(r[pass][2]), "=v"(r[pass][3]));
-      else asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=v"(r[pass]) : "v"(off(blk, pass, g.ldr)), "s"(rsR) : "memory");
-    }
+    for (int pass = 0; pass < 4; ++pass)
+      asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=v"(r[pass]) : "v"(off(blk, pass, g.ldr)), "s"(rsR) : "memory");
   };
   load_resid(0, rr[0]);
 #pragma unroll
@@ -254,11 +228,7 @@ __device__ __forceinline__ void tile_epilogue_f32_asm(const GemmArgs& g, f32x16_
     }
     f32x4_t(&r)[4] = rr[blk & 1];
     // residual rows of this block (and, first time round, the bias) have landed: younger = stores of block blk-1, loads of blk+1
-    if (ABL) {  // the counts below assume four loads and four stores per block
-      if (blk == 0) asm volatile("s_waitcnt vmcnt(0)" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(bias4[j]) : : "memory");
-      else if (ABL == 1) asm volatile("s_waitcnt vmcnt(8)" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(bias4[j]) : : "memory");
-      else if (ABL == 2) asm volatile("s_waitcnt vmcnt(4)" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(bias4[j]) : : "memory");
-    } else if (blk == 0 || blk + 1 == NB)
+    if (blk == 0 || blk + 1 == NB)
       asm volatile("s_waitcnt vmcnt(4)" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(bias4[j]) : : "memory");
     else
       asm volatile("s_waitcnt vmcnt(8)" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(bias4[j]) : : "memory");
@@ -271,8 +241,7 @@ __device__ __forceinline__ void tile_epilogue_f32_asm(const GemmArgs& g, f32x16_
       v[0] += r[pass][0]; v[1] += r[pass][1]; v[2] += r[pass][2]; v[3] += r[pass][3];
       // s_nop 1: a > 64-bit asm store must not be followed at once by a write of its data registers (hipcc pads its own
       // stores, not an asm string: without it some lanes stored the next instruction's operands)
-      if (ABL & 2) asm volatile("" : : "v"(v), "v"(off(blk, pass, g.ldc)));
-      else asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen\n\ts_nop 1" : : "v"(v), "v"(off(blk, pass, g.ldc)), "s"(rsO) : "memory");
+      asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen\n\ts_nop 1" : : "v"(v), "v"(off(blk, pass, g.ldc)), "s"(rsO) : "memory");
     }
   }
 }
@@ -669,9 +638,6 @@ __global__ __launch_bounds__(768) void gemm256q_kernel(GemmArgs g, int tiles_m, 
 // counted vmcnt just before that barrier (4 resp. 8 younger pieces may stay in flight).  At a tile end group 0 waits
 // one interval for group 1's last M, then both groups run the epilogue together; the ring runs on across tiles.
 // ================================================================================================
-// DBG (timing ablations only, results are garbage): 1 no MFMA, 2 no DMA, 4 no fragment reads, 8 no epilogue;
-// 16 / 32: epilogue A/B forms (tile_epilogue EPI bits 0 / 1; results stay correct); 64 / 128: asm epilogue without its
-// residual loads / without its stores
 // Control flow (round 5, second half): the K loop is branch-free in its steady state.  The first form carried its conditions
 // into every K step -- the `step + ahead < total` guards, the group-dependent choice of the counted waits in front of both
 // barriers, run-time switches of the A/B arms, an integer division for the stage's tile -- which hipcc laid out as ~10 scalar
@@ -680,8 +646,9 @@ __global__ __launch_bounds__(768) void gemm256q_kernel(GemmArgs g, int tiles_m, 
 // groups run their own copies of the loop (GRP is a compile-time constant in each), every tile but the last three K steps
 // of a work-group runs the STEADY body (all guards true: one DMA issue, twelve fragment reads, one counted wait, two
 // barriers, sixteen MFMAs, one loop branch) and the stage counter of the issue side advances incrementally.
-template <int ACT, bool OUT_F32, bool F16 = false, int DBG = 0>
-__global__ __launch_bounds__(512) void gemm256x_kernel(GemmArgs g, int tiles_m, int tiles_n, int var) {
+// X16: the 2-byte residual stream (GemmArgs::x16; launch_gemm256 only instantiates it for ACT_NONE, OUT_F32).
+template <int ACT, bool OUT_F32, bool F16 = false, bool X16 = false>
+__global__ __launch_bounds__(512) void gemm256x_kernel(GemmArgs g, int tiles_m, int tiles_n, int stagger) {
   using HT = std::conditional_t<F16, f16_t, bf16_t>;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
@@ -689,14 +656,9 @@ __global__ __launch_bounds__(512) void gemm256x_kernel(GemmArgs g, int tiles_m, 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nk = g.K >> 5;  // 32-wide K steps
   const int lda_b = g.lda * 2, ldw_b = g.ldw * 2;
-  start_stagger(var >> 8, tiles_m * tiles_n, tiles_n);
+  start_stagger(stagger, tiles_m * tiles_n, tiles_n);
   const int my_tiles = tile_count(tiles_m, tiles_n);
   const int total = my_tiles * nk;
-#ifdef CZC_EXPERIMENTS
-  const bool prio = !(var & 1), dma_late = var & 2;  // A/B arms (w_dbg bits 0 / 1)
-#else
-  constexpr bool prio = true, dma_late = false;
-#endif
 
   // ---- DMA side: pieces ii = 0, 1 land tile rows wave*32 + ii*16 + (lane>>2); physical chunk lane&3 ----
   const unsigned lds0 = __builtin_amdgcn_readfirstlane(
@@ -722,19 +684,17 @@ __global__ __launch_bounds__(512) void gemm256x_kernel(GemmArgs g, int tiles_m, 
     const unsigned dstA = lds0 + (is & (QS - 1)) * QSTAGE + wave * (32 * QROWB);
     const unsigned dstW = dstA + QA_BYTES;
     const unsigned so = is_kt * QROWB;
-    if (!(DBG & 2)) {
-      unsigned keep;
-      asm volatile(
-          "s_mov_b32 %0, m0\n\t"
-          "s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %3, %7, %9 offen lds\n\t"
-          "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tbuffer_load_dwordx4 %4, %7, %9 offen lds\n\t"
-          "s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %5, %8, %9 offen lds\n\t"
-          "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tbuffer_load_dwordx4 %6, %8, %9 offen lds\n\t"
-          "s_mov_b32 m0, %0"
-          : "=&s"(keep)
-          : "s"(dstA), "s"(dstW), "v"(a0), "v"(a0 + a16), "v"(w0), "v"(w0 + w16), "s"(rsA), "s"(rsW), "s"(so)
-          : "memory", "scc");
-    }
+    unsigned keep;
+    asm volatile(
+        "s_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %3, %7, %9 offen lds\n\t"
+        "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tbuffer_load_dwordx4 %4, %7, %9 offen lds\n\t"
+        "s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %5, %8, %9 offen lds\n\t"
+        "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tbuffer_load_dwordx4 %6, %8, %9 offen lds\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(keep)
+        : "s"(dstA), "s"(dstW), "v"(a0), "v"(a0 + a16), "v"(w0), "v"(w0 + w16), "s"(rsA), "s"(rsW), "s"(so)
+        : "memory", "scc");
     ++is;
     if (++is_kt == nk) {  // the next stage opens a tile (once per tile: the only branch of the issue side)
       is_kt = 0;
@@ -784,22 +744,15 @@ __global__ __launch_bounds__(512) void gemm256x_kernel(GemmArgs g, int tiles_m, 
         // ------------------------------- L(step) -------------------------------
         const unsigned char* sA = smem + (step & (QS - 1)) * QSTAGE;
         const unsigned char* sB = sA + QA_BYTES;
-        if (!dma_late && (STEADY || step + AHEAD < total)) issue_next();
+        if (STEADY || step + AHEAD < total) issue_next();
         uint4 fa[2][4], fb[2][2];
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
 #pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            if (DBG & 4) fb[ks][j] = make_uint4(lane, step, ks, j);
-            else fb[ks][j] = *(const uint4*)(sB + swzq(brow + 32 * j, 2 * ks + half));
-          }
+          for (int j = 0; j < 2; ++j) fb[ks][j] = *(const uint4*)(sB + swzq(brow + 32 * j, 2 * ks + half));
 #pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            if (DBG & 4) fa[ks][i] = make_uint4(lane, step, ks, i);
-            else fa[ks][i] = *(const uint4*)(sA + swzq(arow + 32 * i, 2 * ks + half));
-          }
+          for (int i = 0; i < 4; ++i) fa[ks][i] = *(const uint4*)(sA + swzq(arow + 32 * i, 2 * ks + half));
         }
-        if (dma_late && (STEADY || step + AHEAD < total)) issue_next();
         if (GRP) {  // stage step+1 is published by the barrier below: this wave's pieces of it must have landed
           if (STEADY || step + 3 < total) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
           else if (step + 2 < total) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
@@ -809,24 +762,14 @@ __global__ __launch_bounds__(512) void gemm256x_kernel(GemmArgs g, int tiles_m, 
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         // ------------------------------- M(step) -------------------------------
-        if (prio) __builtin_amdgcn_s_setprio(1);
-        if (DBG & 1) {
+        __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-          for (int ks = 0; ks < 2; ++ks) {  // keep the fragments (and their LDS reads) alive without the matrix work
+        for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) asm volatile("" ::"v"(__builtin_bit_cast(u32x4_t, fb[ks][j])));
+          for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) asm volatile("" ::"v"(__builtin_bit_cast(u32x4_t, fa[ks][i])));
-          }
-        } else {
-#pragma unroll
-          for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-              for (int j = 0; j < 2; ++j) acc[i][j] = Half<HT>::mfma(fb[ks][j], fa[ks][i], acc[i][j]);
-        }
-        if (prio) __builtin_amdgcn_s_setprio(0);
+            for (int j = 0; j < 2; ++j) acc[i][j] = Half<HT>::mfma(fb[ks][j], fa[ks][i], acc[i][j]);
+        __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
         if (!GRP) {
           if (STEADY || step + 2 < total) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
@@ -842,219 +785,20 @@ __global__ __launch_bounds__(512) void gemm256x_kernel(GemmArgs g, int tiles_m, 
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
       }
-      if (DBG & 8) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) asm volatile("" ::"v"(acc[i][j]));
+      unsigned char* patch = smem + QS * QSTAGE + wave * 4096;
+      if constexpr (X16) {
+        tile_epilogue_x16_asm<2>(g, acc, patch, m0, n0, GRP, wn * 64, lane);
+      } else if constexpr (OUT_F32 && ACT == ACT_NONE) {
+        if (g.resid && g.out_f32 && !g.out_act) tile_epilogue_f32_asm<2>(g, acc, patch, m0, n0, GRP, wn * 64, lane);
+        else tile_epilogue<ACT, OUT_F32, HT>(g, acc, patch, m0, n0, GRP, wn, lane);
       } else {
-        if constexpr (DBG == 256) {  // 2-byte residual stream (GemmArgs::x16; launch_gemm256 only instantiates it for ACT_NONE, OUT_F32)
-          tile_epilogue_x16_asm<2>(g, acc, smem + QS * QSTAGE + wave * 4096, m0, n0, GRP, wn * 64, lane);
-        } else if constexpr (OUT_F32 && ACT == ACT_NONE) {
-          if (!(var & 8) && g.resid && g.out_f32 && !g.out_act)
-            tile_epilogue_f32_asm<2, (DBG >> 6) & 3>(g, acc, smem + QS * QSTAGE + wave * 4096, m0, n0, GRP, wn * 64, lane);
-          else
-            tile_epilogue<ACT, OUT_F32, HT, (DBG >> 4) & 3>(g, acc, smem + QS * QSTAGE + wave * 4096, m0, n0, GRP, wn, lane);
-        } else {
-          tile_epilogue<ACT, OUT_F32, HT, (DBG >> 4) & 3>(g, acc, smem + QS * QSTAGE + wave * 4096, m0, n0, GRP, wn, lane);
-        }
+        tile_epilogue<ACT, OUT_F32, HT>(g, acc, patch, m0, n0, GRP, wn, lane);
       }
     }
   };
   if (wave >> 2) run(std::integral_constant<int, 1>());
   else run(std::integral_constant<int, 0>());
 }
-
-#ifdef CZC_EXPERIMENTS  // an A/B arm that lost (profiles/r04_gemm256r_ablations.txt): `make EXPERIMENTS=1` builds only, not in the product library
-// ================================================================================================
-// gemm256r (round 4, A/B arm: test option gemm256 = 9): the vendor library's structure for the fp32-residual layers --
-// FOUR waves, each 128 x 128 of C (16 v_mfma_f32_32x32x16 accumulators = 256 registers, one wave per SIMD), operands
-// REGISTER-staged: every lane requests its 8 sixteen-byte pieces of a k32 stage (buffer loads, descriptor bounds) three
-// stages before they are needed, holds them in VGPRs for two stages (two alternating sets, 64 registers) and writes
-// them into the 4-slot LDS ring with ds_write_b128 two stages before they are read; one s_barrier per stage; the
-// fragments of the next half stage are read while the current half's 16 MFMAs run.  Per half stage a wave issues 16
-// MFMAs and 16 other instructions (8 ds_read_b128, 4 buffer loads, 4 ds_write_b128), pinned one to one behind the
-// MFMAs with sched_group_barrier.  LDS reads per FLOP are a third lower than with eight 128 x 64 waves, and there is
-// no M0 / s_nop traffic of the LDS-DMA form.  Same k order per accumulator and the same epilogue code as gemm256x:
-// bit-identical results.  Ring slot protocol (QS = 4): stage s is read from slot s & 3 during stage s (its first
-// fragments already during stage s - 1), written during stage s - 2; the barrier at the end of every stage orders
-// both hand-overs.
-// ================================================================================================
-// DBG (timing ablations, results are garbage): 1 no MFMA, 2 no global loads, 4 no ring writes, 8 no epilogue, 16 no fragment reads
-template <bool F16, int DBG = 0>
-__global__ __launch_bounds__(256) void gemm256r_kernel(GemmArgs g, int tiles_m, int tiles_n, int var) {
-  using HT = std::conditional_t<F16, f16_t, bf16_t>;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const int nk = g.K >> 5;
-  const int lda_b = g.lda * 2, ldw_b = g.ldw * 2;
-  start_stagger(var >> 8, tiles_m * tiles_n, tiles_n);
-  const int my_tiles = tile_count(tiles_m, tiles_n);
-  const int total = my_tiles * nk;
-
-  // staging map: lane moves chunk (lane & 3) of rows wave * 64 + 16 * p + (lane >> 2), p = 0..3, of both operands
-  const int srow = wave * 64 + (lane >> 2), sc = lane & 3;
-  const int voA = srow * lda_b + sc * 16, voW = srow * ldw_b + sc * 16;
-  const int soff = swzq(srow, sc);  // rows + 16 p: same swizzle phase, + 1024 p bytes
-  const auto rsNone = __builtin_amdgcn_make_buffer_rsrc((void*)g.A, (short)0, 0, 0x00020000);
-  auto rsA = rsNone, rsW = rsNone;
-  int cur_ti = -1;
-  u32x4_t st0[8], st1[8];
-  auto load_stage = [&](int s, u32x4_t (&r)[8]) {
-    const int ti = s / nk, kt = s - ti * nk;
-    if (s < total && ti != cur_ti) {
-      cur_ti = ti;
-      int tm, tn;
-      tile_at(ti, tiles_m, tiles_n, tm, tn);
-      const int m0 = tm * TM, n0 = tn * TN;
-      rsA = __builtin_amdgcn_make_buffer_rsrc((void*)((const unsigned char*)g.A + (long)m0 * lda_b), (short)0, min(TM, g.M - m0) * lda_b, 0x00020000);
-      rsW = __builtin_amdgcn_make_buffer_rsrc((void*)((const unsigned char*)g.W + (long)n0 * ldw_b), (short)0, min(TN, g.N - n0) * ldw_b, 0x00020000);
-    }
-    const auto ra = s < total ? rsA : rsNone;
-    const auto rw = s < total ? rsW : rsNone;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      r[p] = __builtin_amdgcn_raw_buffer_load_b128(ra, voA + 16 * p * lda_b, kt * QROWB, 0);
-      r[4 + p] = __builtin_amdgcn_raw_buffer_load_b128(rw, voW + 16 * p * ldw_b, kt * QROWB, 0);
-    }
-  };
-  auto store_stage = [&](int s, const u32x4_t (&r)[8]) {
-    unsigned char* dst = smem + (s & (QS - 1)) * QSTAGE + soff;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      *(u32x4_t*)(dst + 1024 * p) = r[p];
-      *(u32x4_t*)(dst + QA_BYTES + 1024 * p) = r[4 + p];
-    }
-  };
-  const int half = lane >> 5;
-  const int arow = wm * 128 + (lane & 31);
-  const int brow = wn * 128 + (lane & 31);
-  uint4 fa[2][4], fb[2][4];
-  auto read_frags = [&](int s, int ks, uint4 (&a)[4], uint4 (&b)[4]) {
-    const unsigned char* sA = smem + (s & (QS - 1)) * QSTAGE;
-    const unsigned char* sB = sA + QA_BYTES;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      if (DBG & 16) { b[i] = make_uint4(lane, s, ks, i); a[i] = make_uint4(lane, s, i, ks); continue; }
-      b[i] = *(const uint4*)(sB + swzq(brow + 32 * i, 2 * ks + half));
-      a[i] = *(const uint4*)(sA + swzq(arow + 32 * i, 2 * ks + half));
-    }
-  };
-  // prologue: stages 0, 1 into the ring, 2 and 3 in flight in the two register sets
-  load_stage(0, st0);
-  load_stage(1, st1);
-  store_stage(0, st0);
-  load_stage(2, st0);
-  store_stage(1, st1);
-  load_stage(3, st1);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-  read_frags(0, 0, fa[0], fb[0]);
-  // steady state at stage s (even: set 0, odd: set 1): the set holds stage s + 2, is written to the ring and refilled with s + 4
-  int step = 0;
-  int ti4 = 3 / nk, kt4 = 3 - ti4 * nk;  // (tile, k step) of the last stage requested so far; rsA / rsW are that tile's
-  if (ti4 >= my_tiles) { rsA = rsNone; rsW = rsNone; }
-  for (int ti = 0; ti < my_tiles; ++ti) {
-    int tm, tn;
-    tile_at(ti, tiles_m, tiles_n, tm, tn);
-    const int m0 = tm * TM, n0 = tn * TN;
-    f32x16_t acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-#define CZC_R_HALF(FA_, FB_)                                                                       \
-  if (DBG & 1) {                                                                                    \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i) { asm volatile("" ::"v"(__builtin_bit_cast(u32x4_t, FA_[i]))); asm volatile("" ::"v"(__builtin_bit_cast(u32x4_t, FB_[i]))); } \
-  } else {                                                                                          \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                    \
-      _Pragma("unroll") for (int j = 0; j < 4; ++j) acc[i][j] = Half<HT>::mfma(FB_[j], FA_[i], acc[i][j]); \
-  }
-#define CZC_R_PIN()                                                                                 \
-  _Pragma("unroll") for (int q = 0; q < 8; ++q) {                                                    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                              \
-    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                              \
-  }                                                                                                 \
-  _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                              \
-    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                                              \
-  }                                                                                                 \
-  _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                              \
-    __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);                                              \
-  }
-    // one stage: WR = the set that holds stage s + 2 (written to the ring, then refilled with stage s + 4).  The scalar
-    // bookkeeping of the refill (descriptors of the tile stage s + 4 belongs to) sits in front, so that everything from
-    // the first fragment read to the barrier is ONE basic block the interleave can be pinned in.
-#define CZC_R_STAGE(WR_)                                                                            \
-  {                                                                                                 \
-    const int s = step;                                                                             \
-    if (++kt4 == nk) {                                                                              \
-      kt4 = 0;                                                                                      \
-      ++ti4;                                                                                        \
-      if (ti4 < my_tiles) {                                                                         \
-        int tm4, tn4;                                                                               \
-        tile_at(ti4, tiles_m, tiles_n, tm4, tn4);                                                   \
-        const int mm = tm4 * TM, nn = tn4 * TN;                                                     \
-        rsA = __builtin_amdgcn_make_buffer_rsrc((void*)((const unsigned char*)g.A + (long)mm * lda_b), (short)0, min(TM, g.M - mm) * lda_b, 0x00020000); \
-        rsW = __builtin_amdgcn_make_buffer_rsrc((void*)((const unsigned char*)g.W + (long)nn * ldw_b), (short)0, min(TN, g.N - nn) * ldw_b, 0x00020000); \
-      } else {                                                                                      \
-        rsA = rsNone;                                                                               \
-        rsW = rsNone;                                                                               \
-      }                                                                                             \
-    }                                                                                               \
-    const int so4 = kt4 * QROWB;                                                                    \
-    unsigned char* wdst = smem + ((s + 2) & (QS - 1)) * QSTAGE + soff;                              \
-    __builtin_amdgcn_sched_barrier(0);                                                              \
-    /* first half: MFMAs of k16 step 0 | fragments of step 1, the A half of the ring write and of the refill */ \
-    read_frags(s, 1, fa[1], fb[1]);                                                                 \
-    _Pragma("unroll") for (int p = 0; p < 4; ++p) {                                                 \
-      if (DBG & 4) asm volatile("" ::"v"(WR_[p])); else *(u32x4_t*)(wdst + 1024 * p) = WR_[p];      \
-      if (DBG & 2) WR_[p].x += 1; else WR_[p] = __builtin_amdgcn_raw_buffer_load_b128(rsA, voA + 16 * p * lda_b, so4, 0); \
-    }                                                                                               \
-    CZC_R_HALF(fa[0], fb[0])                                                                        \
-    CZC_R_PIN()                                                                                     \
-    __builtin_amdgcn_sched_barrier(0);                                                              \
-    /* second half: MFMAs of step 1 | first fragments of stage s + 1, the W half of the write and of the refill */ \
-    read_frags(s + 1, 0, fa[0], fb[0]);                                                             \
-    _Pragma("unroll") for (int p = 0; p < 4; ++p) {                                                 \
-      if (DBG & 4) asm volatile("" ::"v"(WR_[4 + p])); else *(u32x4_t*)(wdst + QA_BYTES + 1024 * p) = WR_[4 + p]; \
-      if (DBG & 2) WR_[4 + p].x += 1; else WR_[4 + p] = __builtin_amdgcn_raw_buffer_load_b128(rsW, voW + 16 * p * ldw_b, so4, 0); \
-    }                                                                                               \
-    CZC_R_HALF(fa[1], fb[1])                                                                        \
-    CZC_R_PIN()                                                                                     \
-    __builtin_amdgcn_sched_barrier(0);                                                              \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                              \
-    __builtin_amdgcn_s_barrier();                                                                   \
-    asm volatile("" ::: "memory");                                                                  \
-    ++step;                                                                                         \
-  }
-    for (int kt = 0; kt < nk; ++kt) {  // nk is even (K % 64 == 0): even stages use set 0, odd ones set 1
-      CZC_R_STAGE(st0)
-      ++kt;
-      CZC_R_STAGE(st1)
-    }
-    if (DBG & 8) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) asm volatile("" ::"v"(acc[i][j]));
-    } else {
-      tile_epilogue_f32_asm<4, 0>(g, acc, smem + QS * QSTAGE + wave * 4096, m0, n0, wm, wn * 128, lane);
-    }
-  }
-#undef CZC_R_STAGE
-#undef CZC_R_PIN
-#undef CZC_R_HALF
-}
-
-#endif  // CZC_EXPERIMENTS (gemm256r)
 
 // ================================================================================================
 // gemm256sq: gemm256q's 4-deep ring of 32 KiB stages for the SPLIT-fp16 precision.  A 64-byte tile row holds 16
@@ -1207,12 +951,10 @@ constexpr int RL_W_BASE = RL_AS * RL_A_BYTES;
 constexpr int RL_PATCH = RL_W_BASE + RL_WS * RL_W_BYTES;
 constexpr int RL_LDS = RL_PATCH + 8 * 4096;  // 160 KiB
 
-// DBG (timing ablations, EXPERIMENTS build, results are garbage): 1 no MFMA, 2 no LDS-DMA, 4 no fragment reads, 8 no epilogue,
-// 16 y not stored (-1 KB per row), 32 only the first 64 bytes of every x line stored, 64 only every other x line stored (-1 KB per row each)
-// AE: the x phase of the epilogue with every VMEM instruction in inline asm and counted waits (below); false = the
-// compiler-scheduled form it replaces (test option w_dbg bit 3), which waits vmcnt(0) in front of every 32 x 32 block --
-// for the block's residual rows AND the previous block's stores: eight full memory round trips per tile.
-template <bool F16, int DBG = 0, bool AE = true>
+// The x phase of the epilogue has every VMEM instruction in inline asm with counted waits (below): compiler-scheduled, it
+// waits vmcnt(0) in front of every 32 x 32 block -- for the block's residual rows AND the previous block's stores: eight
+// full memory round trips per tile.
+template <bool F16>
 __global__ __launch_bounds__(512) void gemm_rowln_kernel(GemmArgs g, const float* __restrict__ gamma,
                                                           const float* __restrict__ beta, int tiles_m, int stagger_us = 0) {  // stagger_us: start_stagger()
   using HT = std::conditional_t<F16, f16_t, bf16_t>;
@@ -1251,7 +993,6 @@ __global__ __launch_bounds__(512) void gemm_rowln_kernel(GemmArgs g, const float
     }
     const unsigned dst = lds0 + (s & (RL_AS - 1)) * RL_A_BYTES + wave * (16 * QROWB);
     const unsigned so = kt * QROWB;
-    if (DBG & 2) return;
     unsigned keep;
     asm volatile(
         "s_mov_b32 %0, m0\n\t"
@@ -1265,7 +1006,6 @@ __global__ __launch_bounds__(512) void gemm_rowln_kernel(GemmArgs g, const float
     const int kt = s % nk;
     const unsigned dst = lds0 + RL_W_BASE + slot * RL_W_BYTES + wave * (64 * QROWB);
     const unsigned so = kt * QROWB;
-    if (DBG & 2) return;
     unsigned keep;
     asm volatile(
         "s_mov_b32 %0, m0\n\t"
@@ -1314,12 +1054,6 @@ __global__ __launch_bounds__(512) void gemm_rowln_kernel(GemmArgs g, const float
       const unsigned char* sA = smem + (step & (RL_AS - 1)) * RL_A_BYTES;
       const unsigned char* sB = smem + RL_W_BASE + wslot * RL_W_BYTES;
       uint4 b0[2], a0f[4], b1[2], a1f[4];
-      if (DBG & 4) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) { b0[j] = make_uint4(lane, step, j, 0); b1[j] = make_uint4(lane, step, j, 1); }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { a0f[i] = make_uint4(lane, step, i, 2); a1f[i] = make_uint4(lane, step, i, 3); }
-      } else {
 #pragma unroll
       for (int j = 0; j < 2; ++j) b0[j] = *(const uint4*)(sB + swzq(brow + 32 * j, half));
 #pragma unroll
@@ -1328,151 +1062,92 @@ __global__ __launch_bounds__(512) void gemm_rowln_kernel(GemmArgs g, const float
       for (int j = 0; j < 2; ++j) b1[j] = *(const uint4*)(sB + swzq(brow + 32 * j, 2 + half));
 #pragma unroll
       for (int i = 0; i < 4; ++i) a1f[i] = *(const uint4*)(sA + swzq(l31 + 32 * i, 2 + half));
-      }
       __builtin_amdgcn_sched_barrier(0);
-      if (DBG & 1) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) asm volatile("" ::"v"(__builtin_bit_cast(u32x4_t, b0[j])));
-#pragma unroll
-        for (int i = 0; i < 4; ++i) asm volatile("" ::"v"(__builtin_bit_cast(u32x4_t, a0f[i])));
-      } else {
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) acc[i][j] = Half<HT>::mfma(b0[j], a0f[i], acc[i][j]);
-      }
       __builtin_amdgcn_sched_barrier(0);
       if (late) {
         if (step + 3 < total) issueA(step + 3);
         if (step + 2 < total) issueW(step + 2, wnext);
       }
-      if (DBG & 1) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) asm volatile("" ::"v"(__builtin_bit_cast(u32x4_t, b1[j])));
-#pragma unroll
-        for (int i = 0; i < 4; ++i) asm volatile("" ::"v"(__builtin_bit_cast(u32x4_t, a1f[i])));
-      } else {
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) acc[i][j] = Half<HT>::mfma(b1[j], a1f[i], acc[i][j]);
-      }
       wslot = wslot == 2 ? 0 : wslot + 1;
     }
 
-    if (DBG & 8) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) asm volatile("" ::"v"(acc[i][j]));
-      continue;
-    }
     // ---- epilogue: x (fp32) out, exact LayerNorm statistics across the eight waves, y out ----
     float4 vx[4][2][4];  // [i][j][pass]: row i*32 + pass*8 + rrow, columns wave*64 + j*32 + rslot*4 .. +3
-    f32x4_t gmv[2], btv[2];  // AE: gamma / beta of this lane's columns, requested behind block 6 (they land under block 7 and the statistics)
-    if constexpr (AE) {
-      // Residual rows one block ahead of the block being finished (32 VGPRs), bias / gamma / beta through the same path,
-      // bounds through the buffer descriptors (reads of rows past M return 0, writes are dropped): no branch, no
-      // compiler-placed vmcnt(0).  VMEM order per tile: B B | L0 L1 | S0 L2 | S1 L3 | ... | S5 L7 | S6 G | S7 (L / S / G four
-      // instructions each); gfx9 retires them in order, so "block b's rows have landed" is a count of the younger
-      // instructions.  Same arithmetic in the same order as the other form (patch value + bias, + residual).
-      const int rows = min(RL_TM, g.M - m0);
-      auto desc = [&](const void* base, long first_row, int ld, int n_rows) {
-        const unsigned long long pa = (unsigned long long)base + (unsigned long long)first_row * ld * 4;
-        u32x4_t r;
-        r.x = __builtin_amdgcn_readfirstlane((unsigned)pa);
-        r.y = __builtin_amdgcn_readfirstlane((unsigned)(pa >> 32) & 0xffffu);
-        r.z = __builtin_amdgcn_readfirstlane((unsigned)(base ? n_rows * ld * 4 : 0));
-        r.w = 0x00020000u;
-        return r;
-      };
-      const u32x4_t rsR = desc(g.resid, m0, g.ldr, rows), rsO = desc(g.out_f32, m0, g.ldc, rows);
-      const u32x4_t rsB = desc(g.bias, 0, RL_N, 1), rsG = desc(gamma, 0, RL_N, 1), rsT = desc(beta, 0, RL_N, 1);
-      asm volatile("s_nop 4" ::: "memory");  // descriptors fresh from v_readfirstlane -> buffer_* inside asm strings
-      const int colb = (wave * 64 + rslot * 4) * 4;
-      auto off = [&](int blk, int pass, int ld) -> unsigned {
-        return (unsigned)((((blk >> 1) * 32 + pass * 8 + rrow) * ld + (blk & 1) * 32) * 4 + colb);
-      };
-      f32x4_t bias4[2];
+    f32x4_t gmv[2], btv[2];  // gamma / beta of this lane's columns, requested behind block 6 (they land under block 7 and the statistics)
+    // Residual rows one block ahead of the block being finished (32 VGPRs), bias / gamma / beta through the same path,
+    // bounds through the buffer descriptors (reads of rows past M return 0, writes are dropped): no branch, no
+    // compiler-placed vmcnt(0).  VMEM order per tile: B B | L0 L1 | S0 L2 | S1 L3 | ... | S5 L7 | S6 G | S7 (L / S / G four
+    // instructions each); gfx9 retires them in order, so "block b's rows have landed" is a count of the younger
+    // instructions.  Same arithmetic in the same order as tile_epilogue (patch value + bias, + residual).
+    const int rows = min(RL_TM, g.M - m0);
+    auto desc = [&](const void* base, long first_row, int ld, int n_rows) {
+      const unsigned long long pa = (unsigned long long)base + (unsigned long long)first_row * ld * 4;
+      u32x4_t r;
+      r.x = __builtin_amdgcn_readfirstlane((unsigned)pa);
+      r.y = __builtin_amdgcn_readfirstlane((unsigned)(pa >> 32) & 0xffffu);
+      r.z = __builtin_amdgcn_readfirstlane((unsigned)(base ? n_rows * ld * 4 : 0));
+      r.w = 0x00020000u;
+      return r;
+    };
+    const u32x4_t rsR = desc(g.resid, m0, g.ldr, rows), rsO = desc(g.out_f32, m0, g.ldc, rows);
+    const u32x4_t rsB = desc(g.bias, 0, RL_N, 1), rsG = desc(gamma, 0, RL_N, 1), rsT = desc(beta, 0, RL_N, 1);
+    asm volatile("s_nop 4" ::: "memory");  // descriptors fresh from v_readfirstlane -> buffer_* inside asm strings
+    const int colb = (wave * 64 + rslot * 4) * 4;
+    auto off = [&](int blk, int pass, int ld) -> unsigned {
+      return (unsigned)((((blk >> 1) * 32 + pass * 8 + rrow) * ld + (blk & 1) * 32) * 4 + colb);
+    };
+    f32x4_t bias4[2];
 #pragma unroll
-      for (int j = 0; j < 2; ++j)
-        asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=v"(bias4[j]) : "v"((unsigned)(colb + j * 128)), "s"(rsB) : "memory");
-      f32x4_t rr[2][4];
-      auto load_resid = [&](int blk, f32x4_t (&r)[4]) {
+    for (int j = 0; j < 2; ++j)
+      asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=v"(bias4[j]) : "v"((unsigned)(colb + j * 128)), "s"(rsB) : "memory");
+    f32x4_t rr[2][4];
+    auto load_resid = [&](int blk, f32x4_t (&r)[4]) {
 #pragma unroll
-        for (int pass = 0; pass < 4; ++pass)
-          asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=v"(r[pass]) : "v"(off(blk, pass, g.ldr)), "s"(rsR) : "memory");
-      };
-      load_resid(0, rr[0]); load_resid(1, rr[1]);
+      for (int pass = 0; pass < 4; ++pass)
+        asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=v"(r[pass]) : "v"(off(blk, pass, g.ldr)), "s"(rsR) : "memory");
+    };
+    load_resid(0, rr[0]); load_resid(1, rr[1]);
 #pragma unroll
-      for (int blk = 0; blk < 8; ++blk) {
-        const int i = blk >> 1, j = blk & 1;
+    for (int blk = 0; blk < 8; ++blk) {
+      const int i = blk >> 1, j = blk & 1;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int slot = (2 * q + half) ^ (l31 & 7);
-          *(float4*)(patch + l31 * 128 + slot * 16) =
-              make_float4(acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]);
-        }
-        f32x4_t(&r)[4] = rr[blk & 1];
-        if (blk == 0)  // younger: L1
-          asm volatile("s_waitcnt vmcnt(4)" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(bias4[j]) : : "memory");
-        else  // younger: the previous block's stores and the next block's rows (block 7: S6 and G)
-          asm volatile("s_waitcnt vmcnt(8)" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(bias4[j]) : : "memory");
+      for (int q = 0; q < 4; ++q) {
+        const int slot = (2 * q + half) ^ (l31 & 7);
+        *(float4*)(patch + l31 * 128 + slot * 16) =
+            make_float4(acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]);
+      }
+      f32x4_t(&r)[4] = rr[blk & 1];
+      if (blk == 0)  // younger: L1
+        asm volatile("s_waitcnt vmcnt(4)" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(bias4[j]) : : "memory");
+      else  // younger: the previous block's stores and the next block's rows (block 7: S6 and G)
+        asm volatile("s_waitcnt vmcnt(8)" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(bias4[j]) : : "memory");
 #pragma unroll
-        for (int pass = 0; pass < 4; ++pass) {
-          const int rw = pass * 8 + rrow;
-          const float4 t = *(const float4*)(patch + rw * 128 + ((rslot ^ (rw & 7)) << 4));
-          f32x4_t v;
-          v[0] = t.x + bias4[j][0]; v[1] = t.y + bias4[j][1]; v[2] = t.z + bias4[j][2]; v[3] = t.w + bias4[j][3];
-          v[0] += r[pass][0]; v[1] += r[pass][1]; v[2] += r[pass][2]; v[3] += r[pass][3];
-          // s_nop 1: a > 64-bit asm store must not be followed at once by a write of its data registers
-          asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen\n\ts_nop 1" : : "v"(v), "v"(off(blk, pass, g.ldc)), "s"(rsO) : "memory");
-          vx[i][j][pass] = make_float4(v[0], v[1], v[2], v[3]);
-        }
-        if (blk + 2 < 8) load_resid(blk + 2, rr[blk & 1]);
-        if (blk == 6) {
+      for (int pass = 0; pass < 4; ++pass) {
+        const int rw = pass * 8 + rrow;
+        const float4 t = *(const float4*)(patch + rw * 128 + ((rslot ^ (rw & 7)) << 4));
+        f32x4_t v;
+        v[0] = t.x + bias4[j][0]; v[1] = t.y + bias4[j][1]; v[2] = t.z + bias4[j][2]; v[3] = t.w + bias4[j][3];
+        v[0] += r[pass][0]; v[1] += r[pass][1]; v[2] += r[pass][2]; v[3] += r[pass][3];
+        // s_nop 1: a > 64-bit asm store must not be followed at once by a write of its data registers
+        asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen\n\ts_nop 1" : : "v"(v), "v"(off(blk, pass, g.ldc)), "s"(rsO) : "memory");
+        vx[i][j][pass] = make_float4(v[0], v[1], v[2], v[3]);
+      }
+      if (blk + 2 < 8) load_resid(blk + 2, rr[blk & 1]);
+      if (blk == 6) {
 #pragma unroll
-          for (int jj = 0; jj < 2; ++jj) {
-            asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=v"(gmv[jj]) : "v"((unsigned)(colb + jj * 128)), "s"(rsG) : "memory");
-            asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=v"(btv[jj]) : "v"((unsigned)(colb + jj * 128)), "s"(rsT) : "memory");
-          }
+        for (int jj = 0; jj < 2; ++jj) {
+          asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=v"(gmv[jj]) : "v"((unsigned)(colb + jj * 128)), "s"(rsG) : "memory");
+          asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=v"(btv[jj]) : "v"((unsigned)(colb + jj * 128)), "s"(rsT) : "memory");
         }
       }
-    } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int col = wave * 64 + j * 32 + rslot * 4;
-        float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (g.bias) b4 = *(const float4*)(g.bias + col);
-        float4 r4[4];
-#pragma unroll
-        for (int pass = 0; pass < 4; ++pass) {
-          const int row = m0 + i * 32 + pass * 8 + rrow;
-          r4[pass] = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (g.resid && row < g.M) r4[pass] = *(const float4*)(g.resid + (long)row * g.ldr + col);
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int slot = (2 * q + half) ^ (l31 & 7);
-          *(float4*)(patch + l31 * 128 + slot * 16) =
-              make_float4(acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]);
-        }
-#pragma unroll
-        for (int pass = 0; pass < 4; ++pass) {
-          const int r = pass * 8 + rrow;
-          float4 v = *(const float4*)(patch + r * 128 + ((rslot ^ (r & 7)) << 4));
-          const int row = m0 + i * 32 + r;
-          v.x += b4.x; v.y += b4.y; v.z += b4.z; v.w += b4.w;
-          v.x += r4[pass].x; v.y += r4[pass].y; v.z += r4[pass].z; v.w += r4[pass].w;
-          if (DBG & 32) { if (row < g.M && g.out_f32 && rslot < 4) *(float4*)(g.out_f32 + (long)row * g.ldc + col) = v; }  // ablation: first 64 B of every x line
-          else if (DBG & 64) { if (row < g.M && g.out_f32 && j == 0) *(float4*)(g.out_f32 + (long)row * g.ldc + col) = v; }  // ablation: every other x line
-          else if (row < g.M && g.out_f32) *(float4*)(g.out_f32 + (long)row * g.ldc + col) = v;
-          vx[i][j][pass] = v;
-        }
-      }
-    }
     }
     // mean: this wave's 64-column partial per row -> its patch [0, 512); then every row group sums the eight partials
     float mean[4][4], rstd[4][4];
@@ -1519,19 +1194,12 @@ __global__ __launch_bounds__(512) void gemm_rowln_kernel(GemmArgs g, const float
       }
     HT* oa = (HT*)g.out_act;
     const bool odd = rslot & 1;
-    if constexpr (AE)  // gamma / beta have landed: the only younger VMEM instructions are the stores of block 7
-      asm volatile("s_waitcnt vmcnt(4)" : "+v"(gmv[0]), "+v"(gmv[1]), "+v"(btv[0]), "+v"(btv[1]) : : "memory");
+    // gamma / beta have landed: the only younger VMEM instructions are the stores of block 7
+    asm volatile("s_waitcnt vmcnt(4)" : "+v"(gmv[0]), "+v"(gmv[1]), "+v"(btv[0]), "+v"(btv[1]) : : "memory");
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      const int col = wave * 64 + j * 32 + rslot * 4;
-      float4 gm, bt;
-      if constexpr (AE) {
-        gm = make_float4(gmv[j][0], gmv[j][1], gmv[j][2], gmv[j][3]);
-        bt = make_float4(btv[j][0], btv[j][1], btv[j][2], btv[j][3]);
-      } else {
-        gm = *(const float4*)(gamma + col);
-        bt = *(const float4*)(beta + col);
-      }
+      const float4 gm = make_float4(gmv[j][0], gmv[j][1], gmv[j][2], gmv[j][3]);
+      const float4 bt = make_float4(btv[j][0], btv[j][1], btv[j][2], btv[j][3]);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         uint2 pk[4];
@@ -1554,8 +1222,7 @@ __global__ __launch_bounds__(512) void gemm_rowln_kernel(GemmArgs g, const float
                               : make_uint4(pk[pp].x, pk[pp].y, recv.x, recv.y);
           const int row = m0 + i * 32 + (pp + (odd ? 1 : 0)) * 8 + rrow;
           const int c8 = wave * 64 + j * 32 + (rslot & 6) * 4;
-          if (DBG & 16) asm volatile("" ::"v"(d.x), "v"(d.y), "v"(d.z), "v"(d.w));  // ablation: y not stored
-          else if (row < g.M) *(uint4*)(oa + (long)row * RL_N + c8) = d;
+          if (row < g.M) *(uint4*)(oa + (long)row * RL_N + c8) = d;
         }
       }
     }
@@ -1565,7 +1232,6 @@ __global__ __launch_bounds__(512) void gemm_rowln_kernel(GemmArgs g, const float
 }  // namespace
 
 int g_gemm256_min_m = 8192;  // below: the tiled kernel (64-wide tiles on small grids) is 1.6-2x faster at 2-5 k rows, equal at 9.6 k (tools/probes/mid_m_gemm.py)
-int g_w_dbg = 0;  // gemm256x / gemm_rowln A/B switches (test option w_dbg): bit0 no s_setprio, bit1 DMA after the fragment reads, bit3 compiler-scheduled fp32 epilogue (gemm_rowln: x phase) instead of the asm-counted one; bits 8.. timing ablations
 
 // x <- x + A.W^T + b with y = LayerNorm(x) from the same launch (gemm_rowln_kernel): N = 512 rows only.
 int g_rowln_min_m = 8192;  // below: tiled GEMM + LayerNorm pass (19 vs 27 us at 4.8 k rows, equal at 9.6 k; tools/probes/mid_m_rowln.py)
@@ -1579,8 +1245,6 @@ int launch_gemm_rowln(const GemmArgs& g, hipStream_t st) {
   const LaunchInit init = per_dev.get([](LaunchInit&) -> int {
     CZC_HIP_CHECK(hipFuncSetAttribute((const void*)gemm_rowln_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, RL_LDS));
     CZC_HIP_CHECK(hipFuncSetAttribute((const void*)gemm_rowln_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, RL_LDS));
-    CZC_HIP_CHECK(hipFuncSetAttribute((const void*)gemm_rowln_kernel<false, 0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, RL_LDS));
-    CZC_HIP_CHECK(hipFuncSetAttribute((const void*)gemm_rowln_kernel<true, 0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, RL_LDS));
     return 0;
   });
   if (init.rc) return launch_init_failed("gemm_rowln");
@@ -1590,30 +1254,10 @@ int launch_gemm_rowln(const GemmArgs& g, hipStream_t st) {
   }
   const int tiles_m = cdiv(g.M, RL_TM);
   dim3 grid(tiles_m < init.n_cu ? tiles_m : init.n_cu), block(512);
-#ifdef CZC_EXPERIMENTS
-  if ((g_w_dbg >> 8) && !g.f16) {  // timing ablations (tools/ab_gemm.py, out_mode 4)
-#define CZC_RL_ABL(D_) case D_: \
-    CZC_HIP_CHECK(hipFuncSetAttribute((const void*)gemm_rowln_kernel<false, D_>, hipFuncAttributeMaxDynamicSharedMemorySize, RL_LDS)); \
-    hipLaunchKernelGGL((gemm_rowln_kernel<false, D_>), grid, block, RL_LDS, st, g, g.ln_gamma, g.ln_beta, tiles_m); break;
-    switch (g_w_dbg >> 8) {
-      CZC_RL_ABL(1) CZC_RL_ABL(2) CZC_RL_ABL(3) CZC_RL_ABL(7) CZC_RL_ABL(8) CZC_RL_ABL(9) CZC_RL_ABL(10) CZC_RL_ABL(13) CZC_RL_ABL(15) CZC_RL_ABL(16) CZC_RL_ABL(32) CZC_RL_ABL(64)
-      default: snprintf(g_err, sizeof(g_err), "gemm_rowln: ablation %d not built", g_w_dbg >> 8); return 1;
-    }
-#undef CZC_RL_ABL
-    CZC_HIP_CHECK(hipGetLastError());
-    return 0;
-  }
-#endif
   // start stagger (start_stagger): 2 us per phase + 16 us for the work-groups with a tile less, from four tiles per
-  // work-group on (fewer: the delay costs more than the de-synchronised epilogues return); w_dbg bit 2 = off, bits 4-7 /
-  // 8.. = tau / bonus of an A/B run
-  int stagger = tiles_m / (int)grid.x >= 4 ? (2 | 16 << 8) : 0;
-  if (g_w_dbg & 4) stagger = 0;
-  if (g_w_dbg >> 4) stagger = ((g_w_dbg >> 4) & 15) | ((g_w_dbg >> 8) << 8);
-  if (g_w_dbg & 8) {  // compiler-scheduled x phase (A/B, bit-identical)
-    if (g.f16) hipLaunchKernelGGL((gemm_rowln_kernel<true, 0, false>), grid, block, RL_LDS, st, g, g.ln_gamma, g.ln_beta, tiles_m);
-    else hipLaunchKernelGGL((gemm_rowln_kernel<false, 0, false>), grid, block, RL_LDS, st, g, g.ln_gamma, g.ln_beta, tiles_m);
-  } else if (g.f16) hipLaunchKernelGGL(gemm_rowln_kernel<true>, grid, block, RL_LDS, st, g, g.ln_gamma, g.ln_beta, tiles_m, stagger);
+  // work-group on (fewer: the delay costs more than the de-synchronised epilogues return)
+  const int stagger = tiles_m / (int)grid.x >= 4 ? (2 | 16 << 8) : 0;
+  if (g.f16) hipLaunchKernelGGL(gemm_rowln_kernel<true>, grid, block, RL_LDS, st, g, g.ln_gamma, g.ln_beta, tiles_m, stagger);
   else hipLaunchKernelGGL(gemm_rowln_kernel<false>, grid, block, RL_LDS, st, g, g.ln_gamma, g.ln_beta, tiles_m, stagger);
   CZC_HIP_CHECK(hipGetLastError());
   return 0;
@@ -1639,12 +1283,8 @@ int launch_gemm256(const GemmArgs& g, hipStream_t st) {
                       CZC_ATTR((K_<ACT_QUICK_GELU, false, true>)); CZC_ATTR((K_<ACT_QUICK_GELU, true, true>))
     CZC_ATTR4(gemm256q_kernel);
     CZC_ATTR4(gemm256x_kernel);
-#ifdef CZC_EXPERIMENTS
-    CZC_ATTR((gemm256r_kernel<false>));
-    CZC_ATTR((gemm256r_kernel<true>));
-#endif
-    CZC_ATTR((gemm256x_kernel<ACT_NONE, true, false, 256>));
-    CZC_ATTR((gemm256x_kernel<ACT_NONE, true, true, 256>));
+    CZC_ATTR((gemm256x_kernel<ACT_NONE, true, false, true>));
+    CZC_ATTR((gemm256x_kernel<ACT_NONE, true, true, true>));
 #undef CZC_ATTR4
 #undef CZC_ATTR
     return 0;
@@ -1655,24 +1295,6 @@ int launch_gemm256(const GemmArgs& g, hipStream_t st) {
   const bool f32 = g.out_f32 != nullptr || g.resid != nullptr;
   dim3 gq(tiles_m * tiles_n < n_cu ? tiles_m * tiles_n : n_cu);
   const bool pp = g_use_gemm256 == 5 || (g_use_gemm256 != 3 && f32);
-#ifdef CZC_EXPERIMENTS
-  if (pp && g_use_gemm256 != 9 && (g_w_dbg >> 8) && f32 && g.act == ACT_NONE && !g.f16) {  // timing ablations of the ping-pong kernel
-#define CZC_GOXD(D_)                                                                                                     \
-  case D_:                                                                                                               \
-    CZC_HIP_CHECK(hipFuncSetAttribute((const void*)gemm256x_kernel<ACT_NONE, true, false, D_>, hipFuncAttributeMaxDynamicSharedMemorySize, shp)); \
-    hipLaunchKernelGGL((gemm256x_kernel<ACT_NONE, true, false, D_>), gq, dim3(512), shp, st, g, tiles_m, tiles_n, g_w_dbg & 255); \
-    break
-    switch (g_w_dbg >> 8) {
-      CZC_GOXD(1); CZC_GOXD(2); CZC_GOXD(3); CZC_GOXD(4); CZC_GOXD(5); CZC_GOXD(6); CZC_GOXD(8); CZC_GOXD(9); CZC_GOXD(10); CZC_GOXD(12); CZC_GOXD(14);
-      CZC_GOXD(16); CZC_GOXD(32); CZC_GOXD(48); CZC_GOXD(13); CZC_GOXD(7);
-      CZC_GOXD(64); CZC_GOXD(128); CZC_GOXD(71); CZC_GOXD(135); CZC_GOXD(199);
-      default: snprintf(g_err, sizeof(g_err), "gemm256x: ablation %d not built", g_w_dbg >> 8); return 1;
-    }
-#undef CZC_GOXD
-    CZC_HIP_CHECK(hipGetLastError());
-    return 0;
-  }
-#endif
 #define CZC_GO(K_, A_, F_, H_, T_, ...) hipLaunchKernelGGL((K_<A_, F_, H_>), gq, dim3(T_), shp, st, g, tiles_m, tiles_n, ##__VA_ARGS__)
 #define CZC_DISPATCH(K_, T_, ...)                                                                                          \
   do {                                                                                                                     \
@@ -1686,35 +1308,12 @@ int launch_gemm256(const GemmArgs& g, hipStream_t st) {
   } while (0)
   // gemm256x with the fp32-residual epilogue (the HBM burst at the end of every tile): start stagger (start_stagger) of 2 us
   // per phase + 32 us for the work-groups with a tile less, from four tiles per work-group on: fc2 -1.7 % at 312 k rows,
-  // -1.9 % at 156 k (its epilogue is a fifth of a tile; gemm_rowln's is two thirds and gains 10 %).  w_dbg bit 2 = off,
-  // bits 4-7 / 8.. = tau / bonus of an A/B run
-  int stagger256 = (f32 && tiles_m * tiles_n / (int)gq.x >= 4) ? (2 | 32 << 8) : 0;
-  if (g_w_dbg & 4) stagger256 = 0;
-  if (f32 && (g_w_dbg >> 4)) stagger256 = ((g_w_dbg >> 4) & 15) | ((g_w_dbg >> 8) << 8);
+  // -1.9 % at 156 k (its epilogue is a fifth of a tile; gemm_rowln's is two thirds and gains 10 %)
+  const int stagger256 = (f32 && tiles_m * tiles_n / (int)gq.x >= 4) ? (2 | 32 << 8) : 0;
   if (g.x16) {  // fp16 residual stream: ping-pong kernel with the 2-byte epilogue (eligibility: gemm256_eligible)
-    if (g.f16) hipLaunchKernelGGL((gemm256x_kernel<ACT_NONE, true, true, 256>), gq, dim3(512), shp, st, g, tiles_m, tiles_n, (g_w_dbg & 7) | stagger256 << 8);
-    else hipLaunchKernelGGL((gemm256x_kernel<ACT_NONE, true, false, 256>), gq, dim3(512), shp, st, g, tiles_m, tiles_n, (g_w_dbg & 7) | stagger256 << 8);
-  } else if (g_use_gemm256 == 9 && f32 && g.act == ACT_NONE && g.resid && g.out_f32 && !g.out_act) {  // register-staged four-wave arm (A/B)
-#ifdef CZC_EXPERIMENTS
-    if ((g_w_dbg >> 8) && !g.f16) {
-#define CZC_GORD(D_) case D_: \
-      CZC_HIP_CHECK(hipFuncSetAttribute((const void*)gemm256r_kernel<false, D_>, hipFuncAttributeMaxDynamicSharedMemorySize, shp)); \
-      hipLaunchKernelGGL((gemm256r_kernel<false, D_>), gq, dim3(256), shp, st, g, tiles_m, tiles_n, stagger256 << 8); break
-      switch (g_w_dbg >> 8) {
-        CZC_GORD(1); CZC_GORD(2); CZC_GORD(4); CZC_GORD(8); CZC_GORD(16); CZC_GORD(3); CZC_GORD(6); CZC_GORD(9); CZC_GORD(10); CZC_GORD(14); CZC_GORD(22); CZC_GORD(30); CZC_GORD(29); CZC_GORD(17); CZC_GORD(24);
-        default: snprintf(g_err, sizeof(g_err), "gemm256r: ablation %d not built", g_w_dbg >> 8); return 1;
-      }
-#undef CZC_GORD
-      CZC_HIP_CHECK(hipGetLastError());
-      return 0;
-    }
-    if (g.f16) hipLaunchKernelGGL((gemm256r_kernel<true>), gq, dim3(256), shp, st, g, tiles_m, tiles_n, stagger256 << 8);
-    else hipLaunchKernelGGL((gemm256r_kernel<false>), gq, dim3(256), shp, st, g, tiles_m, tiles_n, stagger256 << 8);
-#else
-    snprintf(g_err, sizeof(g_err), "gemm256 = 9 (gemm256r, the register-staged A/B arm) exists in EXPERIMENTS=1 builds only");
-    return 1;
-#endif
-  } else if (pp) CZC_DISPATCH(gemm256x_kernel, 512, (g_w_dbg & 15) | stagger256 << 8);
+    if (g.f16) hipLaunchKernelGGL((gemm256x_kernel<ACT_NONE, true, true, true>), gq, dim3(512), shp, st, g, tiles_m, tiles_n, stagger256);
+    else hipLaunchKernelGGL((gemm256x_kernel<ACT_NONE, true, false, true>), gq, dim3(512), shp, st, g, tiles_m, tiles_n, stagger256);
+  } else if (pp) CZC_DISPATCH(gemm256x_kernel, 512, stagger256);
   else CZC_DISPATCH(gemm256q_kernel, 768);
 #undef CZC_DISPATCH
 #undef CZC_GO

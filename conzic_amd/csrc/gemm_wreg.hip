@@ -35,12 +35,6 @@ namespace czc {
 
 namespace {
 
-// compile-time timing ablations of the folded-LayerNorm form (make ABL=n LIB=...; tools/ab_gemm.py out_mode 7; results are
-// garbage): 1 no statistics DMA, 2 plain bias epilogue, 4 bf16 MFMA opcode on the same bytes
-#ifndef CZC_LNF_ABL
-#define CZC_LNF_ABL 0
-#endif
-constexpr int LNF_ABL = CZC_LNF_ABL;
 constexpr int WR_K = 512;
 constexpr int WR_ROWB = WR_K * 2;              // 1 KiB per activation row
 constexpr int WR_BLK = 32;                     // rows per block
@@ -163,29 +157,21 @@ __global__ __launch_bounds__(512, 2) void gemm_wreg_kernel(GemmArgs g, int ncg, 
   // operand rows (its counted wait + the block barrier).  Two halves suffice: the pairs of blocks 4G..4G+3 are read in the
   // streams of blocks 4G+1..4G+4, the request that overwrites them (group G+2) is issued in the stream of block 4G+5.
   const unsigned stat0 = lds0 + WR_LDS;
-  constexpr bool T4 = !(LNF_ABL & 8);  // ablation 8: one dword request per block (ring of WR_TS slots of 256 bytes)
-  const unsigned voffT = (unsigned)(lane * (T4 ? 16 : 4));
+  const unsigned voffT = (unsigned)(lane * 16);
   auto stat_dma = [&](int j) {
-    if (LNF_ABL & 1) return;
-    const bool mine = wave == 0 && (!T4 || (j & 3) == 0) && !stats_here;
+    const bool mine = wave == 0 && (j & 3) == 0 && !stats_here;
     if (__builtin_expect(!mine, 1)) return;
     const long row0 = (long)(b0 + j) * WR_BLK;
     const unsigned long long pt = (unsigned long long)g.ln_stat + (unsigned long long)row0 * 8;
     u32x4_t rsT;
     rsT.x = __builtin_amdgcn_readfirstlane((unsigned)pt); rsT.y = __builtin_amdgcn_readfirstlane((unsigned)(pt >> 32) & 0xffffu);
-    rsT.z = __builtin_amdgcn_readfirstlane((unsigned)(min((long)(T4 ? 4 * WR_BLK : WR_BLK), (long)g.M - row0) * 8)); rsT.w = 0x00020000u;
-    const unsigned dst = stat0 + (T4 ? ((j >> 2) & 1) * 1024 : (j & (WR_TS - 1)) * 256);
+    rsT.z = __builtin_amdgcn_readfirstlane((unsigned)(min((long)(4 * WR_BLK), (long)g.M - row0) * 8)); rsT.w = 0x00020000u;
+    const unsigned dst = stat0 + ((j >> 2) & 1) * 1024;
     unsigned keep;
-    if constexpr (T4)
-      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                   : "=&s"(keep)
-                   : "s"(dst), "v"(voffT), "s"(rsT)
-                   : "memory");
-    else
-      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dword %2, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                   : "=&s"(keep)
-                   : "s"(dst), "v"(voffT), "s"(rsT)
-                   : "memory");
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "s"(dst), "v"(voffT), "s"(rsT)
+                 : "memory");
   };
   auto issue = [&](int j) {  // block j of this work-group -> ring slot j % WR_D
     const long row0 = (long)(b0 + j) * WR_BLK;
@@ -257,9 +243,9 @@ __global__ __launch_bounds__(512, 2) void gemm_wreg_kernel(GemmArgs g, int ncg, 
   auto epi_quad = [&](int qd, int js) {  // accP quad qd -> (LayerNorm correction,) bias, activation, 2-byte -> patch
     const float4 b4 = *(const float4*)(bias_s + 8 * qd + 4 * half);
     float4 v;
-    if constexpr (LNF && !(LNF_ABL & 2)) {
+    if constexpr (LNF) {
       if (qd == 0)  // read once per block: the area is refilled (statistics of a later group of blocks) in this same stream
-        ln_rstd = *(const float*)(stat_s + (LNF_ABL & 8 ? (js & (WR_TS - 1)) * 256 : ((js >> 2) & 1) * 1024 + (js & 3) * 256) + l31 * 8 + 4);
+        ln_rstd = *(const float*)(stat_s + (((js >> 2) & 1) * 1024 + (js & 3) * 256) + l31 * 8 + 4);
       v = make_float4(__fmaf_rn(accP[4 * qd], ln_rstd, b4.x), __fmaf_rn(accP[4 * qd + 1], ln_rstd, b4.y),
                       __fmaf_rn(accP[4 * qd + 2], ln_rstd, b4.z), __fmaf_rn(accP[4 * qd + 3], ln_rstd, b4.w));
     } else {
@@ -300,13 +286,8 @@ __global__ __launch_bounds__(512, 2) void gemm_wreg_kernel(GemmArgs g, int ncg, 
 #pragma unroll
       for (int k = 0; k < 4; k += 2) {
         const int t = 4 * sgm + k;
-        if constexpr (LNF && (LNF_ABL & 4)) {  // timing ablation: the bf16 opcode on the same bytes
-          acc0 = Half<bf16_t>::mfma(wreg[t], fr[sgm & 1][k], acc0);
-          acc1 = Half<bf16_t>::mfma(wreg[t + 1], fr[sgm & 1][k + 1], acc1);
-        } else {
-          acc0 = Half<HT>::mfma(wreg[t], fr[sgm & 1][k], acc0);
-          acc1 = Half<HT>::mfma(wreg[t + 1], fr[sgm & 1][k + 1], acc1);
-        }
+        acc0 = Half<HT>::mfma(wreg[t], fr[sgm & 1][k], acc0);
+        acc1 = Half<HT>::mfma(wreg[t + 1], fr[sgm & 1][k + 1], acc1);
       }
       __builtin_amdgcn_sched_barrier(0);
       // descriptor arithmetic (a few dozen SALU) rides in the slots too: nothing but the wait and the barrier

@@ -10,7 +10,7 @@ import os
 from typing import Optional
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# CZC_LIB_PATH: a differently-built library for the kernel tools (`make EXPERIMENTS=1 LIB=...`: timing-ablation kernels)
+# CZC_LIB_PATH: a differently-built library, e.g. the baseline of an A/B (csrc/Makefile: `make LIB=...`)
 LIB_PATH = os.environ.get("CZC_LIB_PATH") or os.path.join(_HERE, "lib", "libconzic_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "conzic_hip.h")
 # kernel-level parity hooks + GEMM microbenchmark: a second library over the product one, for tests/ and tools/ only

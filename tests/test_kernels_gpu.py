@@ -297,38 +297,6 @@ def test_gemm256_variants(variant, M, N, K, act, resid):
     assert err < 3e-3 * np.sqrt(K / 64), err
 
 
-@pytest.mark.parametrize("M,N,K", [(2500, 512, 2048), (70000, 512, 512), (2304, 320, 192), (12345, 512, 2048), (300, 512, 128),
-                                   (700, 256, 64), (100, 40, 64), (80000, 512, 2048)])
-def test_register_staged_four_wave_gemm_equals_the_ring_kernel_bitwise(M, N, K):
-    """Round-4 A/B arm `gemm256 = 9` (gemm256r: four waves x 128 x 128 accumulators, operands staged through registers
-    two stages ahead, ds_write into the ring, MFMAs interleaved one to one with the memory instructions) on the
-    fp32-residual layers: same k order per accumulator and the same epilogue as the ping-pong ring kernel (gemm256 = 5), so
-    the fp32 outputs are identical bit for bit -- ragged M / N edges, one to many tiles per work-group, two to 64 stages."""
-    lib = native.load_test()
-    rng = np.random.default_rng(M + N + K)
-    A = rng.standard_normal((M, K)).astype(np.float32)
-    W = (rng.standard_normal((N, K)) * 0.05).astype(np.float32)
-    bias = rng.standard_normal(N).astype(np.float32)
-    R = rng.standard_normal((M, N)).astype(np.float32)
-    out = {}
-    try:
-        assert lib.czc_test_set_option(b"gemm256_min_m", 1) == 0
-        for v in (5, 9):
-            assert lib.czc_test_set_option(b"gemm256", v) == 0
-            try:
-                out[v] = KH.gemm(BF16, A, W, bias=bias, resid=R)
-            except native.NativeError as exc:
-                if v == 9 and "EXPERIMENTS=1 builds only" in str(exc):
-                    pytest.skip("gemm256r is an A/B arm: built by `make EXPERIMENTS=1` only, not into the product library")
-                raise
-    finally:
-        lib.czc_test_set_option(b"gemm256", 1)
-        lib.czc_test_set_option(b"gemm256_min_m", 8192)
-    ref = (_bf16_round(A).astype(np.float64) @ _bf16_round(W).astype(np.float64).T + bias).astype(np.float32) + R
-    assert np.abs(out[5] - ref).max() < 3e-3 * np.sqrt(K / 64)
-    np.testing.assert_array_equal(out[9], out[5])
-
-
 @pytest.mark.parametrize("M,N,act", [(2048, 512, 0), (3000, 1536, 0), (5000, 2048, 1), (70001, 512, 1), (2304, 320, 0),
                                      (2049, 1536, 1), (40000, 2048, 0)])
 def test_gemm_weight_stationary(M, N, act):
@@ -592,7 +560,7 @@ def test_tiled_and_ring_gemms_agree_bitwise_on_fp32_residual_layers(prec, N, K):
 
 
 @pytest.mark.parametrize("prec", [0, 4])
-def test_full_row_kernel_and_gemm_plus_layernorm_agree_bitwise(prec):
+def test_full_row_kernel_equals_gemm_plus_layernorm_on_every_run(prec):
     """out-proj + LN2: the full-row kernel with the LayerNorm in its epilogue (>= 4096 rows) against the ring / tiled
     GEMM followed by the stand-alone LayerNorm kernel, which for 512-wide half-precision rows restates the epilogue's
     arithmetic operation for operation (rowops.hip layernorm512_kernel)."""
@@ -604,33 +572,15 @@ def test_full_row_kernel_and_gemm_plus_layernorm_agree_bitwise(prec):
     resid = (rng.standard_normal((M, 512)) * 1.5 + 0.7).astype(np.float32)
     gamma = (1.0 + 0.3 * rng.standard_normal(512)).astype(np.float32)
     beta = (0.2 * rng.standard_normal(512)).astype(np.float32)
-    x, y = KH.gemm_rowln(prec, A, W, b, resid, gamma, beta, 1e-5)
-    x2 = KH.gemm(prec, A, W, bias=b, resid=resid)
-    np.testing.assert_array_equal(x, x2)
-    y2 = KH.layernorm(prec, x2, gamma, beta, 1e-5)
-    np.testing.assert_array_equal(y, y2)
-    # the 30-VGPR LayerNorm kernel (ds_swizzle partners, default) against the ds_bpermute form: same tree, same bits
-    lib = native.load_test()
-    try:
-        assert lib.czc_test_set_option(b"ln_lean", 0) == 0
-        np.testing.assert_array_equal(KH.layernorm(prec, x2, gamma, beta, 1e-5), y2)
-    finally:
-        lib.czc_test_set_option(b"ln_lean", 1)
-    # the asm-counted x phase of the epilogue (default) against the compiler-scheduled one it replaces, twice (a mis-counted
-    # wait shows up as a few stale lanes on some run), with and without a bias, ragged last tile
-    lib = native.load_test()
+    # the x phase of the epilogue waits on counted vmcnt, and a mis-counted wait shows up as a few stale lanes on some run:
+    # three runs each, with and without a bias, ragged last tile
     for bias in (b, None):
-        outs = []
-        try:
-            for dbg in (0, 8, 0):
-                assert lib.czc_test_set_option(b"w_dbg", dbg) == 0
-                outs.append(KH.gemm_rowln(prec, A, W, bias, resid, gamma, beta, 1e-5))
-        finally:
-            lib.czc_test_set_option(b"w_dbg", 0)
-        for xo, yo in outs[1:]:
-            np.testing.assert_array_equal(xo, outs[0][0])
-            np.testing.assert_array_equal(yo, outs[0][1])
-    np.testing.assert_array_equal(outs[0][0], KH.gemm(prec, A, W, resid=resid))
+        x2 = KH.gemm(prec, A, W, bias=bias, resid=resid)
+        y2 = KH.layernorm(prec, x2, gamma, beta, 1e-5)
+        for _ in range(3):
+            x, y = KH.gemm_rowln(prec, A, W, bias, resid, gamma, beta, 1e-5)
+            np.testing.assert_array_equal(x, x2)
+            np.testing.assert_array_equal(y, y2)
 
 
 @pytest.mark.parametrize("act", [0, 1])

@@ -160,7 +160,7 @@ def block_status(f):
 #   work model: ("gemm", N, Kdim, which rows) FLOPs = 2 * rows * N * Kdim per pass;  ("bytes", bytes per row, which rows);  None
 KERNELS = [
     (r"gemm_wreg_kernel<1,", "fc1 512->2048 + quick-GELU, LayerNorm folded in (weights in registers, `gemm_wreg.hip`)", "MFMA", ("gemm", 2048, 512, "mlp")),
-    (r"gemm256x_kernel<0, true, (false|true), 256>", "fc2 2048->512 + residual on fp16 rows (256x256 ping-pong ring, `gemm256.hip`)", "MFMA", ("gemm", 512, 2048, "mlp")),
+    (r"gemm256x_kernel<0, true, (false|true), (256|true)>", "fc2 2048->512 + residual on fp16 rows (256x256 ping-pong ring, `gemm256.hip`)", "MFMA", ("gemm", 512, 2048, "mlp")),
     (r"gemm_wreg_kernel<0,", "q/k/v 512->1536, LayerNorm folded in (weights in registers)", "MFMA", ("gemm", 1536, 512, "all")),
     (r"attention_image_kernel", "branch attention, one work-group per (image, 4 heads) (`attention.hip`)", "HBM: 4 KB per row (q, k, v in, context out)", ("bytes", 4096, "all")),
     (r"gemm_wreg_resid_kernel", "out-projection 512->512 + residual, x updated in place, LayerNorm partials out", "HBM: 3 KB per row (context, x in, x out; the second column group's context read hits L2)", ("gemmbytes", 512, 512, "mlp", 3072)),

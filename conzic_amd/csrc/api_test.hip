@@ -27,6 +27,8 @@ static const Hooks& HK() {
 #define launch_convert HK().convert
 #define launch_act_to_f32 HK().act_to_f32
 #define launch_attention HK().attention
+#define launch_attention_shared HK().attention_shared
+#define launch_attention_shared_split HK().attention_shared_split
 #define launch_softmax_mask_topk HK().softmax_mask_topk
 #define launch_bridge_precompute HK().bridge_precompute
 #define launch_bridge HK().bridge
@@ -375,6 +377,82 @@ int czc_test_attention(int precision, int n_seq, const int32_t* seq_len, int hea
   T_HIP(hipDeviceSynchronize());
   T_CHECK(down_act(pool, precision, dout, M * Hd, out));
   return 0;
+}
+
+// One attention launch on a shared-prefix plan laid out as the engine lays it out (kernels.h: launch_prefix_plan /
+// launch_prefix_finish): segments 0..B-1 are the trunks (pre_len 0), segment B + b*K + k is branch (b,k) with pre_off =
+// own_off[b], pre_len = trunk_len[b]; rows back to back, own_off = exclusive scan.  kernel 0: launch_attention (the generic
+// per-segment kernels in their prefix form); 1: launch_attention_shared[_split] with the per-image kernel off; 2: the same with
+// the per-image kernel forced.  qkv and out carry CZC_TEST_PLAN_GUARD rows in front of and behind the plan rows inside their
+// own allocations: NaN patterns of the operand type in qkv, bytes 0x5a in out, so that a stray read or write shows in the
+// result instead of leaving the buffer.  `out` receives all rows + 2 * guard rows.
+int czc_test_attention_plan(int precision, int kernel, int B, int K, int heads, float scale, const int32_t* trunk_len,
+                            const int32_t* own_len, int pass_img_max, const float* qkv, float* out) {
+  const bool half = precision == PREC_BF16 || precision == PREC_F16;
+  if (!(half || precision == PREC_F32 || precision == PREC_F16X3) || kernel < 0 || kernel > 2 || (kernel && precision == PREC_F32) ||
+      (kernel == 2 && !half) || B < 1 || K < 1 || heads < 1 || (long)B * K > (1 << 22)) {
+    snprintf(TEST_ERR, 512, "attention_plan: no kernel %d for precision %d (B %d K %d heads %d)", kernel, precision, B, K, heads);
+    return CZC_ERR_ARG;
+  }
+  const int n_seg = B + B * K, GR = CZC_TEST_PLAN_GUARD;
+  std::vector<int> len(n_seg), off(n_seg + 1, 0), poff(n_seg, 0), plen(n_seg, 0), imax(B, 0);
+  int max_own = 0, max_keys = 0;
+  for (int b = 0; b < B; ++b) len[b] = trunk_len[b];
+  for (int i = 0; i < B * K; ++i) len[B + i] = own_len[i];
+  for (int s = 0; s < n_seg; ++s) {
+    if (len[s] < 0 || len[s] > 4096) { snprintf(TEST_ERR, 512, "attention_plan: segment %d has %d rows", s, len[s]); return CZC_ERR_ARG; }
+    off[s + 1] = off[s] + len[s];
+  }
+  for (int b = 0; b < B; ++b) {
+    for (int k = 0; k < K; ++k) {
+      const int s = B + b * K + k;
+      poff[s] = off[b]; plen[s] = len[b];
+      imax[b] = std::max(imax[b], len[s]);
+    }
+    max_own = std::max(max_own, imax[b]);
+    max_keys = std::max(max_keys, len[b] + imax[b]);
+  }
+  const size_t rows = off[n_seg], Hd = (size_t)heads * 64, es = prec_bytes(precision);
+  const size_t qrow = 3 * Hd * es, orow = Hd * es, all = rows + 2 * GR;
+  DevPool pool;
+  unsigned char* dq = (unsigned char*)pool.alloc(all * qrow); T_PTR(dq);
+  unsigned char* dout = (unsigned char*)pool.alloc(all * orow); T_PTR(dout);
+  {  // guard rows of qkv: quiet NaNs of the operand type (fp16 planes for the split type)
+    std::vector<uint32_t> nan((size_t)GR * qrow / 4,
+                              precision == PREC_F32 ? 0x7fc00000u : precision == PREC_BF16 ? 0x7fc07fc0u : 0x7e007e00u);
+    T_HIP(hipMemcpy(dq, nan.data(), (size_t)GR * qrow, hipMemcpyHostToDevice));
+    T_HIP(hipMemcpy(dq + (GR + rows) * qrow, nan.data(), (size_t)GR * qrow, hipMemcpyHostToDevice));
+  }
+  if (rows) {
+    float* f = (float*)pool.up(qkv, rows * 3 * Hd * 4); T_PTR(f);
+    if (precision == PREC_F32) T_HIP(hipMemcpy(dq + GR * qrow, f, rows * qrow, hipMemcpyDeviceToDevice));
+    else T_CHECK(launch_convert(precision, f, dq + GR * qrow, (long)(rows * 3 * Hd), nullptr));
+  }
+  T_HIP(hipMemset(dout, 0x5a, all * orow));
+  int* doff = (int*)pool.up(off.data(), (size_t)(n_seg + 1) * 4); T_PTR(doff);
+  int* dlen = (int*)pool.up(len.data(), (size_t)n_seg * 4); T_PTR(dlen);
+  int* dpoff = (int*)pool.up(poff.data(), (size_t)n_seg * 4); T_PTR(dpoff);
+  int* dplen = (int*)pool.up(plen.data(), (size_t)n_seg * 4); T_PTR(dplen);
+  int* dimax = (int*)pool.up(imax.data(), (size_t)B * 4); T_PTR(dimax);
+  T_HIP(hipDeviceSynchronize());
+  SegTable tab{dpoff, dplen, doff, dlen, n_seg, 0};
+  tab.img_max = pass_img_max ? dimax : nullptr;
+  const void* q0 = dq + GR * qrow;
+  void* o0 = dout + GR * orow;
+  int rc;
+  if (kernel == 0) {
+    rc = launch_attention(precision, q0, tab, max_keys, heads, 1, scale, o0, nullptr);
+  } else {
+    const int saved = g_use_attention_image;
+    g_use_attention_image = kernel == 2 ? 2 : 0;
+    rc = half ? launch_attention_shared(q0, tab, B, K, max_own, max_keys, heads, scale, o0, nullptr, precision == PREC_F16)
+              : launch_attention_shared_split(q0, tab, B, K, max_own, max_keys, heads, scale, o0, nullptr);
+    g_use_attention_image = saved;
+  }
+  if (rc > 0) return rc;
+  T_HIP(hipDeviceSynchronize());
+  T_CHECK(down_act(pool, precision, dout, all * Hd, out));
+  return rc < 0 ? CZC_TEST_REFUSED : 0;
 }
 
 int czc_test_topk(int B, int V, int K, const float* logits, const float* mask, float temperature, int dot_id,

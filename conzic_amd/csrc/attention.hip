@@ -380,6 +380,7 @@ __global__ __launch_bounds__(256) void attention_branch_kernel(const bf16_t* qkv
   const int pre_off = tab.pre_off[s0], pre_len = tab.pre_len[s0];
   const int r0 = tab.own_off[s0];
   const int n_own = tab.own_off[s0 + Gc - 1] + tab.own_len[s0 + Gc - 1] - r0;  // <= 32 by construction
+  if (n_own <= 0) return;  // a group of empty slots (de-duplicated candidates): nothing to store, and row r0 - 1 is not this group's to read
   const int nkt_t = (pre_len + 31) >> 5;
   const int Hd = heads * 64;
   const long pitch = 3L * Hd;

@@ -262,7 +262,7 @@ int launch_refine_finish(const int* own_off, const int* own_len, const int* coun
 // ---- czc_internal_hooks (declared below, private to the build): what libconzic_hip_test.so may reach inside this library -----------
 // The product library has hidden visibility; the hook library (api_test.hip) gets the launchers it wraps and the
 // process-wide kernel-family switches it flips through this table instead of through exported C++ symbols.
-constexpr int HOOKS_ABI = 0x0602;
+constexpr int HOOKS_ABI = 0x0603;
 struct Hooks {
   char* (*err_buf)();  // the calling host thread's g_err [512]
   decltype(&launch_gemm) gemm;
@@ -271,6 +271,8 @@ struct Hooks {
   decltype(&launch_convert) convert;
   decltype(&launch_act_to_f32) act_to_f32;
   decltype(&launch_attention) attention;
+  decltype(&launch_attention_shared) attention_shared;
+  decltype(&launch_attention_shared_split) attention_shared_split;
   decltype(&launch_softmax_mask_topk) softmax_mask_topk;
   decltype(&launch_bridge_precompute) bridge_precompute;
   decltype(&launch_bridge) bridge;

@@ -136,6 +136,7 @@ TEST_SIGNATURES = {
     "czc_test_set_option": (_I, [C.c_char_p, _I]),
     "czc_test_layernorm": (_I, [_I, _I, _I, _P, _P, _P, C.c_float, _P]),
     "czc_test_attention": (_I, [_I, _I, _P, _I, _I, C.c_float, _P, _P]),
+    "czc_test_attention_plan": (_I, [_I, _I, _I, _I, _I, C.c_float, _P, _P, _I, _P, _P]),
     "czc_test_topk": (_I, [_I, _I, _I, _P, _P, C.c_float, _I, _I, _P, _P, _P]),
     "czc_test_bridge": (_I, [C.POINTER(BridgeTables), C.POINTER(Config), _I, _I, _P, _P, _P]),
     "czc_test_combine": (_I, [_I, _I, _I, _P, _P, C.c_float, _P, _P, _P, C.POINTER(Hyper), _P, _P, _P, _P]),

@@ -54,6 +54,28 @@ int czc_test_layernorm(int precision, int M, int H, const float* x, const float*
 /* qkv [sum(len), 3*heads*64] packed sequences; causal 0/1; scale; out [sum(len), heads*64] */
 int czc_test_attention(int precision, int n_seq, const int32_t* seq_len, int heads, int causal, float scale,
                        const float* qkv, float* out);
+/* One attention launch on a host-given SHARED-PREFIX plan, laid out as the engine lays it out: B trunk segments (trunk_len[B]
+ * rows, no prefix), then the B*K branch segments back to back (own_len[B*K] rows; branch (b,k) sees the trunk of image b as
+ * key/value-only prefix and its own rows causally); own_off = exclusive scan, max_own / max_keys / the per-image maxima
+ * computed as the engine computes them (pass_img_max 0: SegTable::img_max is null).
+ *   kernel 0: launch_attention with the prefix tables (attention_mfma_kernel / attention_mfma_split_kernel /
+ *             attention_valu_kernel, whichever `precision` and the "mfma_attention" switch select);
+ *          1: launch_attention_shared / _split with the per-group kernels (attention_branch_kernel / _split_kernel);
+ *          2: launch_attention_shared with attention_image_kernel forced (bf16 / fp16; the launcher still falls back to the
+ *             per-group kernel where the per-image one cannot serve the plan).
+ *   precision: 1 f32 (kernel 0 only), 0 bf16, 4 fp16, 3 split-fp16 (kernels 0, 1).  The "attention_image" switch is set for the
+ *   call and restored.
+ * qkv: fp32 [rows, 3*heads*64] (rows = sum of all lengths), rounded to the operand type on the device.
+ * out: fp32 [CZC_TEST_PLAN_GUARD + rows + CZC_TEST_PLAN_GUARD, heads*64]: the device output buffer WITH the guard rows the
+ *   hook keeps in front of and behind the plan rows inside its own allocations.  The output is pre-filled with bytes 0x5a (so
+ *   an unwritten element reads back as that pattern in the output type) and the guard rows of the device qkv hold NaNs of the
+ *   operand type: a stray read or write shows in the result, and stays inside the hook's buffers.
+ * Returns 0, CZC_TEST_REFUSED (not an error: the packed launcher returned -1 for this plan, nothing was launched, `out` is
+ * the untouched pattern) or a CZC_ERR_* status. */
+#define CZC_TEST_REFUSED 100
+#define CZC_TEST_PLAN_GUARD 32
+int czc_test_attention_plan(int precision, int kernel, int B, int K, int heads, float scale, const int32_t* trunk_len,
+                            const int32_t* own_len, int pass_img_max, const float* qkv, float* out);
 int czc_test_topk(int B, int V, int K, const float* logits, const float* mask, float temperature, int dot_id,
                   int dot_allowed, float* probs, int32_t* idxs, int32_t* cand);
 int czc_test_bridge(const czc_bridge_tables* t, const czc_config* cfg, int n_rows, int T, const int32_t* rows,

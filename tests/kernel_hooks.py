@@ -119,6 +119,35 @@ def attention(prec, qkv, seq_len, heads, causal, scale):
     return out
 
 
+PLAN_REFUSED = 100   # include/conzic_hip_test.h CZC_TEST_REFUSED
+PLAN_GUARD = 32      # CZC_TEST_PLAN_GUARD: rows in front of and behind the plan rows of the hook's device buffers
+# what the output pre-fill (bytes 0x5a) reads back as through each precision's output type
+PLAN_SENTINEL = {1: float(np.array([0x5A5A5A5A], np.uint32).view(np.float32)[0]),
+                 0: float(np.array([0x5A5A0000], np.uint32).view(np.float32)[0]),
+                 4: float(np.array([0x5A5A], np.uint16).view(np.float16)[0]),
+                 3: 2.0 * float(np.array([0x5A5A], np.uint16).view(np.float16)[0])}
+
+
+def attention_plan(prec, kernel, trunk_len, own_len, heads, scale, qkv, img_max=True):
+    """One attention launch on a shared-prefix plan (czc_test_attention_plan): kernel 0 generic per-segment kernels in their
+    prefix form, 1 packed per-group kernel, 2 packed per-image kernel (forced).  trunk_len [B], own_len [B, K], qkv fp32
+    [rows, 3*heads*64].  -> (refused, out [rows, heads*64], guard [2*PLAN_GUARD, heads*64]): `refused` when the packed launcher
+    returned -1 (nothing launched); `guard` = the output buffer's rows in front of and behind the plan rows."""
+    lib = native.load_test()
+    tl = np.ascontiguousarray(trunk_len, np.int32)
+    ol = np.ascontiguousarray(own_len, np.int32)
+    B, K = ol.shape
+    assert tl.shape == (B,)
+    rows = int(tl.sum()) + int(ol.sum())
+    qkv = np.ascontiguousarray(qkv, np.float32).reshape(rows, 3 * heads * 64)
+    full = np.empty((rows + 2 * PLAN_GUARD, heads * 64), np.float32)
+    rc = lib.czc_test_attention_plan(int(prec), int(kernel), B, K, int(heads), C.c_float(scale), tl.ctypes.data, ol.ctypes.data,
+                                     1 if img_max else 0, qkv.ctypes.data, full.ctypes.data)
+    if rc != PLAN_REFUSED:
+        native.check(rc, None, "czc_test_attention_plan")
+    return rc == PLAN_REFUSED, full[PLAN_GUARD:PLAN_GUARD + rows], np.concatenate([full[:PLAN_GUARD], full[PLAN_GUARD + rows:]])
+
+
 def topk(logits, mask, K, temperature, dot_id, dot_allowed):
     lib = native.load_test()
     lg = np.ascontiguousarray(logits, np.float32)

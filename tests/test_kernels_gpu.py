@@ -12,6 +12,7 @@ import kernel_hooks as KH
 from conzic_amd import harness, native, synth
 from conzic_amd.bridge import tables_from_tokenizers
 from conzic_amd.text import tokenizers_from_vocab
+from attn_ref import seq_ref
 from goldutil import GOLD
 
 pytestmark = pytest.mark.gpu
@@ -83,22 +84,7 @@ def test_layernorm(prec, H):
         assert np.abs(y - ref).max() < tol
 
 
-def _attn_ref(qkv, lens, heads, causal, scale):
-    Hd = heads * 64
-    out = np.zeros((qkv.shape[0], Hd), np.float32)
-    o = 0
-    for L in lens:
-        blk = torch.from_numpy(qkv[o:o + L])
-        q, k, v = blk[:, :Hd], blk[:, Hd:2 * Hd], blk[:, 2 * Hd:]
-        q = q.view(L, heads, 64).transpose(0, 1)
-        k = k.view(L, heads, 64).transpose(0, 1)
-        v = v.view(L, heads, 64).transpose(0, 1)
-        s = q @ k.transpose(-1, -2) * scale
-        if causal:
-            s = s + torch.full((L, L), float("-inf")).triu(1)
-        out[o:o + L] = (torch.softmax(s, -1) @ v).transpose(0, 1).reshape(L, Hd).numpy()
-        o += L
-    return out
+_attn_ref = seq_ref   # the per-sequence formula (fp32 here), tests/attn_ref.py
 
 
 @pytest.mark.parametrize("prec", [F32, BF16])

@@ -41,7 +41,10 @@ __device__ __forceinline__ bool merge_lookup(const BridgeDev& bd, int l, int r, 
   }
 }
 
-__global__ __launch_bounds__(BR_THREADS) void bridge_kernel(BridgeDev bd, const int* inp, int B, int T, int gen_idx,
+// ROWS: the substituted column is the row's own (gen_rows[b], czc_generate_rows).  One thread serves one candidate row and a
+// wave can span several rows of inp (K need not be a multiple of 64), so the column is a per-thread value, not a wave-uniform one
+template <bool ROWS>
+__global__ __launch_bounds__(BR_THREADS) void bridge_kernel(BridgeDev bd, const int* inp, int B, int T, int gen_idx_, const int* gen_rows,
                                                             const int* cand, int K, const float* lexicon, const float* lex_pos,
                                                             const uint8_t* lex_cls, int negative, PosDev pos, int* clip_ids, int* clip_len, float* senti_raw,
                                                             float* repeats, int* overflow) {
@@ -61,6 +64,7 @@ __global__ __launch_bounds__(BR_THREADS) void bridge_kernel(BridgeDev bd, const 
   if (row >= (long)B * K) return;
   const int b = (int)(row / K);
   const int cid = cand ? cand[row] : -1;
+  const int gen_idx = ROWS ? gen_rows[b] : gen_idx_;
 
   // ---- 1. decode to bytes ------------------------------------------------------------------
   int n = 0;
@@ -216,17 +220,33 @@ int launch_bridge_precompute(const BridgeDev& bd, int* tok_ids, uint8_t* tok_len
   return 0;
 }
 
-int launch_bridge(const BridgeDev& bd, const int* inp, int B, int T, int gen_idx, const int* cand, int K,
-                  const float* lexicon, const float* lex_pos, const uint8_t* lex_cls, int negative, const PosDev& pos, int* clip_ids, int* clip_len, float* senti_raw,
-                  float* repeats, int* overflow_flag, hipStream_t st) {
+template <bool ROWS>
+static int launch_bridge_t(const BridgeDev& bd, const int* inp, int B, int T, int gen_idx, const int* gen_rows, const int* cand, int K,
+                           const float* lexicon, const float* lex_pos, const uint8_t* lex_cls, int negative, const PosDev& pos, int* clip_ids,
+                           int* clip_len, float* senti_raw, float* repeats, int* overflow_flag, hipStream_t st) {
   const long rows = (long)B * K;
   if (rows <= 0) return 0;
   const size_t shmem = (size_t)BR_THREADS * (2 * BR_MAXB + BR_MAXSYM * 4 + BR_MAXP * 8);
-  CZC_HIP_CHECK(hipFuncSetAttribute((const void*)bridge_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-  hipLaunchKernelGGL(bridge_kernel, dim3(cdiv(rows, BR_THREADS)), dim3(BR_THREADS), shmem, st, bd, inp, B, T, gen_idx,
+  CZC_HIP_CHECK(hipFuncSetAttribute((const void*)bridge_kernel<ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+  hipLaunchKernelGGL(bridge_kernel<ROWS>, dim3(cdiv(rows, BR_THREADS)), dim3(BR_THREADS), shmem, st, bd, inp, B, T, gen_idx, gen_rows,
                      cand, K, lexicon, lex_pos, lex_cls, negative, pos, clip_ids, clip_len, senti_raw, repeats, overflow_flag);
   CZC_HIP_CHECK(hipGetLastError());
   return 0;
+}
+
+int launch_bridge(const BridgeDev& bd, const int* inp, int B, int T, int gen_idx, const int* cand, int K,
+                  const float* lexicon, const float* lex_pos, const uint8_t* lex_cls, int negative, const PosDev& pos, int* clip_ids, int* clip_len, float* senti_raw,
+                  float* repeats, int* overflow_flag, hipStream_t st) {
+  return launch_bridge_t<false>(bd, inp, B, T, gen_idx, nullptr, cand, K, lexicon, lex_pos, lex_cls, negative, pos, clip_ids, clip_len,
+                                senti_raw, repeats, overflow_flag, st);
+}
+
+int launch_bridge_rows(const BridgeDev& bd, const int* inp, int B, int T, const int* gen_rows, const int* cand, int K,
+                       const float* lexicon, const float* lex_pos, const uint8_t* lex_cls, int negative, const PosDev& pos, int* clip_ids, int* clip_len,
+                       float* senti_raw, float* repeats, int* overflow_flag, hipStream_t st) {
+  if (!gen_rows || !cand) { snprintf(g_err, sizeof(g_err), "bridge: the per-row form needs gen_rows and cand"); return 1; }
+  return launch_bridge_t<true>(bd, inp, B, T, 0, gen_rows, cand, K, lexicon, lex_pos, lex_cls, negative, pos, clip_ids, clip_len,
+                               senti_raw, repeats, overflow_flag, st);
 }
 
 // ---- exclusive scan of sequence lengths --------------------------------------------------------

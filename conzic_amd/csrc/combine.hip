@@ -47,6 +47,8 @@ __global__ __launch_bounds__(256) void cosine_kernel(const float* text_feat, con
   }
 }
 
+// ROWS: the write-back column is the row's own (a.gen_rows[b], czc_generate_rows)
+template <bool ROWS>
 __global__ __launch_bounds__(CB_THREADS) void combine_kernel(CombineArgs a) {
   __shared__ float s_cos[CB_MAXK];
   __shared__ float s_fin[CB_MAXK];
@@ -146,7 +148,7 @@ __global__ __launch_bounds__(CB_THREADS) void combine_kernel(CombineArgs a) {
     const int bi = s_best < K ? s_best : 0;  // all-NaN scores: keep candidate 0
     a.best[b] = bi;
     a.best_cos[b] = (a.refine_kind && (a.refine_kind[(long)b * K + bi] & 3) == 3) ? a.refine_cos[(long)b * K + bi] : s_cos[bi];
-    if (a.inp) a.inp[(long)b * a.T + a.gen_idx] = a.cand[(long)b * K + bi];
+    if (a.inp) a.inp[(long)b * a.T + (ROWS ? a.gen_rows[b] : a.gen_idx)] = a.cand[(long)b * K + bi];
   }
 }
 
@@ -308,7 +310,8 @@ int launch_combine(const CombineArgs& a, hipStream_t st) {
   if (a.text_feat)  // null: clip_ref already holds the cosines (second combine of the screen-then-refine engine)
     hipLaunchKernelGGL(cosine_kernel, dim3((unsigned)cdiv((long)a.B * a.K, 4)), dim3(256), 0, st, a.text_feat, a.img_n, a.B, a.K, a.D,
                        a.clip_ref, a.nonfinite);
-  hipLaunchKernelGGL(combine_kernel, dim3(a.B), dim3(CB_THREADS), 0, st, a);
+  if (a.gen_rows) hipLaunchKernelGGL(combine_kernel<true>, dim3(a.B), dim3(CB_THREADS), 0, st, a);
+  else hipLaunchKernelGGL(combine_kernel<false>, dim3(a.B), dim3(CB_THREADS), 0, st, a);
   CZC_HIP_CHECK(hipGetLastError());
   return 0;
 }

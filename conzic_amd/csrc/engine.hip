@@ -127,6 +127,9 @@ struct czc_engine {
   int last_BT = 0, last_B = 0, last_T = 0;  // shape of the forward whose rows b_x / b_xg hold (n_mask = 0 re-use needs the same B AND T)
   int bert_prune = 1;       // last BERT layer behind the attention on the one row per sequence the MLM head reads (n_mask == 1 steps)
   int bert_pruned_idx = -1; // row the previous forward kept (-1: all rows of b_x are valid)
+  // czc_generate_rows: the previous forward kept row bert_pruned_rows[b] of sequence b (bert_pruned_idx == PRUNED_ROWS); host
+  // copy of that step's columns, valid inside the call only (null afterwards: nothing can re-use such a forward then)
+  const int32_t* bert_pruned_rows = nullptr;
   int bert_fuse_splitk_ln = 1;  // BERT fc2: the LayerNorm kernel sums the split-K slabs itself (no reduce kernel); 0 = two kernels
   int share_prefix = 1;  // encode the candidates' common causal prefix once per image
   int dedup = 1;         // candidates of one image with identical CLIP id rows are encoded once (bridge.hip prefix_plan_kernel; exact)
@@ -162,6 +165,8 @@ struct czc_engine {
 };
 
 namespace {
+
+constexpr int PRUNED_ROWS = 1 << 30;  // czc_engine::bert_pruned_idx: one row per sequence was kept, each sequence its own
 
 #define E_CHECK(expr)                                                                         \
   do {                                                                                        \
@@ -468,7 +473,9 @@ int clip_stack(czc_engine* e, int P, const char* gk, std::vector<LayerW>& L, flo
 // keep_idx >= 0: only row keep_idx of every sequence is read afterwards (the masked slot, gen_utils.py:69): the last layer
 // still forms q/k/v and the attention for all rows, then gathers that row and runs out-proj / LN / MLP / LN on B rows
 // instead of B*T; the result goes to ws "b_xg" [B,H].  Same kernels per row, so the row's values do not change.
-int bert_forward(czc_engine* e, const int* d_inp, int B, int T, int keep_idx = -1) {
+// keep_rows (device, [B]; with keep_rows_host its host copy): the kept row is keep_rows[b] of sequence b (czc_generate_rows).
+int bert_forward(czc_engine* e, const int* d_inp, int B, int T, int keep_idx = -1, const int* keep_rows = nullptr,
+                 const int32_t* keep_rows_host = nullptr) {
   const czc_config& c = e->cfg;
   const int P = e->pb, M = B * T, H = c.bert_hidden, I = c.bert_inter;
   void *xa, *qkv, *ctx, *hbuf; float *x, *tmp;
@@ -488,6 +495,7 @@ int bert_forward(czc_engine* e, const int* d_inp, int B, int T, int keep_idx = -
     E_CHECK(launch_bert_embed(P, d_inp, B, T, H, word, pos, typ, g, b, c.bert_eps, xa, x, e->st)); }
   const float scale = 1.0f / sqrtf(64.0f);
   e->bert_pruned_idx = -1;
+  e->bert_pruned_rows = nullptr;
   // fc2 + residual + LayerNorm (HF:bert/modeling_bert.py:488-496): xr <- LN(xr + h.W2^T + b), xa <- the same in the operand type.
   // Where the launcher splits K (fc2's K = 3072 at every row count above the skinny kernel's 32) the slice sums stay in its slab
   // workspace and the LayerNorm kernel sums them itself (GemmArgs::splitk_pending): one launch less per layer, no fp32 round trip
@@ -515,7 +523,8 @@ int bert_forward(czc_engine* e, const int* d_inp, int B, int T, int keep_idx = -
       E_CHECK(ensure(e, "b_cg", (size_t)B * H * e->eb, &ctx_g));
       E_CHECK(ensure(e, "b_xg", (size_t)B * H * 4, (void**)&x_g));
       { ProfScope ps(e, "rowops", 0);
-        E_CHECK(launch_make_row_index(idx, B, T, keep_idx, e->st));
+        if (keep_rows) E_CHECK(launch_make_row_index_rows(idx, B, T, keep_rows, e->st));
+        else E_CHECK(launch_make_row_index(idx, B, T, keep_idx, e->st));
         E_CHECK(launch_gather_rows_bytes(ctx, idx, B, H * (int)e->eb, ctx_g, e->st));
         E_CHECK(launch_gather_rows_f32(x, idx, B, H, x_g, e->st)); }
       // tmp / xa / hbuf: their first B rows are free here (xa fed this layer's q/k/v, hbuf the previous layer's fc2)
@@ -523,7 +532,8 @@ int bert_forward(czc_engine* e, const int* d_inp, int B, int T, int keep_idx = -
       { ProfScope ps(e, "rowops", 0); E_CHECK(launch_layernorm(P, tmp, nullptr, l.ln1_g, l.ln1_b, c.bert_eps, B, H, xa, x_g, e->st)); }
       E_CHECK(gemm(e, P, "gemm_bert", xa, H, l.fc1_w, H, l.fc1_b, nullptr, 0, hbuf, nullptr, I, B, I, H, ACT_GELU_ERF));
       E_CHECK(fc2_ln(hbuf, l, x_g, B));
-      e->bert_pruned_idx = keep_idx;
+      e->bert_pruned_idx = keep_rows ? PRUNED_ROWS : keep_idx;
+      e->bert_pruned_rows = keep_rows ? keep_rows_host : nullptr;
       break;
     }
     E_CHECK(gemm(e, P, "gemm_bert", ctx, H, l.o_w, H, l.o_b, x, H, nullptr, tmp, H, M, H, H, ACT_NONE));
@@ -535,7 +545,9 @@ int bert_forward(czc_engine* e, const int* d_inp, int B, int T, int keep_idx = -
 }
 
 // MLM head on row gen_idx of every sequence -> logits fp32 [B,V] in ws "b_logits"
-int mlm_head(czc_engine* e, int B, int T, int gen_idx, float** logits_out) {
+// gen_rows (device, [B]) / gen_rows_host: row gen_rows[b] of sequence b instead (czc_generate_rows)
+int mlm_head(czc_engine* e, int B, int T, int gen_idx, float** logits_out, const int* gen_rows = nullptr,
+             const int32_t* gen_rows_host = nullptr) {
   const czc_config& c = e->cfg;
   const int P = e->pb, H = c.bert_hidden, V = c.bert_vocab;
   float* x = (float*)e->ws["b_x"].p;
@@ -551,13 +563,18 @@ int mlm_head(czc_engine* e, int B, int T, int gen_idx, float** logits_out) {
   E_CHECK(need(e, "cls.predictions.transform.LayerNorm.weight", H, &g));
   E_CHECK(need(e, "cls.predictions.transform.LayerNorm.bias", H, &b));
   E_CHECK(need(e, "cls.predictions.bias", V, &bias));
-  if (e->bert_pruned_idx >= 0 && e->bert_pruned_idx != gen_idx)
+  // the rule holds per row: every sequence must read the one row its forward kept
+  const bool kept_same = gen_rows ? (e->bert_pruned_idx == PRUNED_ROWS && e->bert_pruned_rows && gen_rows_host &&
+                                     !memcmp(e->bert_pruned_rows, gen_rows_host, (size_t)B * 4))
+                                  : e->bert_pruned_idx == gen_idx;
+  if (e->bert_pruned_idx >= 0 && !kept_same)
     return fail(e, CZC_ERR_STATE, "n_mask=0 re-use of a forward that kept one row only (it follows an n_mask >= 2 step, gen_utils.py:164-166)%s");
   { ProfScope ps(e, "rowops", 0);
     if (e->bert_pruned_idx >= 0) {
       gx = (float*)e->ws["b_xg"].p;  // the forward left exactly these rows
     } else {
-      E_CHECK(launch_make_row_index(idx, B, T, gen_idx, e->st));
+      if (gen_rows) E_CHECK(launch_make_row_index_rows(idx, B, T, gen_rows, e->st));
+      else E_CHECK(launch_make_row_index(idx, B, T, gen_idx, e->st));
       E_CHECK(launch_gather_rows_f32(x, idx, B, H, gx, e->st));
     }
     E_CHECK(launch_convert(P, gx, ga, (long)B * H, e->st)); }
@@ -692,6 +709,9 @@ int clip_text_forward(czc_engine* e, const int* cids, const int* clen, int B, in
 struct StepArgs {
   int* d_inp; int B, T, gen_idx, n_mask, dot_allowed, K;
   czc_hyper hp;
+  // czc_generate_rows: column / '.' rule of every row (device, [B]) and the columns' host copy; null = the scalars above
+  // (gen_idx then still holds row 0's column: what a control callback is told when all rows share one)
+  const int* gen_rows = nullptr; const int* dot_rows = nullptr; const int32_t* gen_rows_host = nullptr;
 };
 struct StepBufs { float *probs, *senti, *reps; int *idxs, *cand, *cids, *clen, *totals; };
 
@@ -712,22 +732,33 @@ int step_phase_a(czc_engine* e, const StepArgs& a) {
   const czc_config& c = e->cfg;
   const czc_hyper* hp = &a.hp;
   if (a.n_mask > 0) {
-    E_CHECK(launch_mask_positions(a.d_inp, a.B, a.T, a.gen_idx, a.n_mask, c.mask_id, e->st));
-    E_CHECK(bert_forward(e, a.d_inp, a.B, a.T, e->bert_prune && a.n_mask == 1 ? a.gen_idx : -1));
+    const bool prune = e->bert_prune && a.n_mask == 1;
+    if (a.gen_rows) {
+      E_CHECK(launch_mask_positions_rows(a.d_inp, a.B, a.T, a.gen_rows, a.n_mask, c.mask_id, e->st));
+      E_CHECK(bert_forward(e, a.d_inp, a.B, a.T, prune ? a.gen_idx : -1, prune ? a.gen_rows : nullptr, a.gen_rows_host));
+    } else {
+      E_CHECK(launch_mask_positions(a.d_inp, a.B, a.T, a.gen_idx, a.n_mask, c.mask_id, e->st));
+      E_CHECK(bert_forward(e, a.d_inp, a.B, a.T, prune ? a.gen_idx : -1));
+    }
   }
   float* logits;
-  E_CHECK(mlm_head(e, a.B, a.T, a.gen_idx, &logits));
+  E_CHECK(mlm_head(e, a.B, a.T, a.gen_idx, &logits, a.gen_rows, a.gen_rows_host));
   StepBufs b;
   E_CHECK(step_bufs(e, a.B * a.K, &b));
   { ProfScope ps(e, "topk", 0);
-    E_CHECK(launch_softmax_mask_topk(logits, a.B, c.bert_vocab, a.K, e->d_mask, hp->temperature, c.dot_id, a.dot_allowed,
-                                     b.probs, b.idxs, b.cand, e->st)); }
+    if (a.dot_rows) E_CHECK(launch_softmax_mask_topk_rows(logits, a.B, c.bert_vocab, a.K, e->d_mask, hp->temperature, c.dot_id, a.dot_rows,
+                                                          b.probs, b.idxs, b.cand, e->st));
+    else E_CHECK(launch_softmax_mask_topk(logits, a.B, c.bert_vocab, a.K, e->d_mask, hp->temperature, c.dot_id, a.dot_allowed,
+                                          b.probs, b.idxs, b.cand, e->st)); }
   E_HIP(hipMemsetAsync(b.totals, 0, 32, e->st));
   { ProfScope ps(e, "bridge", 0);
     PosDev pos{hp->control == 2 ? e->d_pos_tags : nullptr, e->d_pos_masks, e->pos_n};
-    E_CHECK(launch_bridge(e->bd, a.d_inp, a.B, a.T, a.gen_idx, b.cand, a.K, hp->control == 1 ? e->d_lex : nullptr,
-                          hp->control == 1 ? e->d_lex_pos : nullptr, e->d_lex_cls, hp->negative,
-                          pos, b.cids, b.clen, b.senti, b.reps, b.totals + 2, e->st)); }
+    if (a.gen_rows) E_CHECK(launch_bridge_rows(e->bd, a.d_inp, a.B, a.T, a.gen_rows, b.cand, a.K, hp->control == 1 ? e->d_lex : nullptr,
+                                               hp->control == 1 ? e->d_lex_pos : nullptr, e->d_lex_cls, hp->negative,
+                                               pos, b.cids, b.clen, b.senti, b.reps, b.totals + 2, e->st));
+    else E_CHECK(launch_bridge(e->bd, a.d_inp, a.B, a.T, a.gen_idx, b.cand, a.K, hp->control == 1 ? e->d_lex : nullptr,
+                               hp->control == 1 ? e->d_lex_pos : nullptr, e->d_lex_cls, hp->negative,
+                               pos, b.cids, b.clen, b.senti, b.reps, b.totals + 2, e->st)); }
   E_CHECK(clip_plan(e, b.cids, b.clen, a.B, a.K, e->share_prefix, b.totals));
   return 0;
 }
@@ -795,6 +826,7 @@ int step_phase_b(czc_engine* e, const StepArgs& a, int M, int max_len, int max_b
   ca.senti_raw = b.senti; ca.repeats = b.reps; ca.alpha = hp->alpha; ca.beta = hp->beta; ca.gamma = hp->gamma;
   ca.use_senti = hp->control; ca.B = a.B; ca.K = a.K; ca.D = c.clip_proj; ca.clip_score = cscore; ca.clip_ref = cref;
   ca.final_score = fin; ca.best = best; ca.best_cos = bcos; ca.inp = a.d_inp; ca.T = a.T; ca.gen_idx = a.gen_idx;
+  ca.gen_rows = a.gen_rows;  // both passes of the refine engine write back through the same per-row column
   E_CHECK(ensure(e, "s_nonfinite", 32, (void**)&ca.nonfinite));
   if (!e->refine) {
     ProfScope ps(e, "combine", 0);
@@ -855,8 +887,10 @@ int step_phase_b(czc_engine* e, const StepArgs& a, int M, int max_len, int max_b
   return 0;
 }
 
+// gen_rows / dot_rows (device, [B]) + gen_rows_host: czc_generate_rows' per-row column and '.' rule (gen_idx = row 0's then)
 int step_device(czc_engine* e, int* d_inp, int B, int T, int gen_idx, int n_mask, int dot_allowed, int K,
-                const czc_hyper* hp) {
+                const czc_hyper* hp, const int* gen_rows = nullptr, const int* dot_rows = nullptr,
+                const int32_t* gen_rows_host = nullptr) {
   const czc_config& c = e->cfg;
   if (!e->finalized) return fail(e, CZC_ERR_STATE, "weights not finalized%s");
   if (c.bert_layers <= 0) return fail(e, CZC_ERR_STATE, "this engine was created without the BERT tower%s");
@@ -872,6 +906,7 @@ int step_device(czc_engine* e, int* d_inp, int B, int T, int gen_idx, int n_mask
   if (n_mask <= 0 && (e->last_B != B || e->last_T != T))
     return fail(e, CZC_ERR_STATE, "n_mask=0 needs a previous forward of the same [B,T] shape%s");
   StepArgs a{d_inp, B, T, gen_idx, n_mask, dot_allowed, K, *hp};
+  a.gen_rows = gen_rows; a.dot_rows = dot_rows; a.gen_rows_host = gen_rows_host;
   E_CHECK(step_phase_a(e, a));
   if (n_mask > 0) { e->stat_bert_rows += B * T; e->last_BT = B * T; e->last_B = B; e->last_T = T; }
   if (hp->control && e->ctl_fn) E_CHECK(control_fetch(e, a));  // ids for the host scorer ride on the same round trip
@@ -1536,22 +1571,66 @@ int czc_step(czc_engine* e, int32_t* inp, int B, int T, int gen_idx, int n_mask,
   return CZC_OK;
 }
 
-int czc_generate(czc_engine* e, int B, int T, int L, int seed_len, const int32_t* init_ids_host, int top_k,
-                 int n_steps, const int32_t* positions_host, const int32_t* n_mask_host, int snapshot_every,
-                 const czc_hyper* hp, int32_t* out_ids, float* out_cos) {
+// czc_generate and czc_generate_rows.  rows = false: positions_host [n_steps], one column for the whole batch at every step (the
+// scalar kernels, the memo where the option is on).  rows = true: positions_host [n_steps, B], image_of_row_host [B] or null; the
+// schedule (column seed_len + position and the '.' rule of every row and step) is uploaded once and every step reads its slice.
+static int generate_impl(czc_engine* e, bool rows, int B, int T, int L, int seed_len, const int32_t* init_ids_host,
+                         const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
+                         const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp, int32_t* out_ids, float* out_cos) {
   if (!e || !init_ids_host || !positions_host || !hp || B <= 0 || n_steps < 0 || snapshot_every <= 0)
     return CZC_ERR_ARG;
   if (seed_len + L > T) return fail(e, CZC_ERR_ARG, "generate: seed_len + L > T%s");
   E_HIP(hipSetDevice(e->dev));
   e->err[0] = 0;
-  int *d_inp, *d_row;
+  const size_t n_pos = rows ? (size_t)n_steps * B : (size_t)n_steps;
+  for (size_t i = 0; i < n_pos; ++i)
+    if (positions_host[i] < 0 || positions_host[i] >= L) return fail(e, CZC_ERR_ARG, "generate: position out of range%s");
+  std::vector<int32_t> sched;  // rows: [n_steps][B] columns, then [n_steps][B] '.' rules (utils.py:53-59: position == L-1)
+  if (rows) {
+    if (B > CZC_MAX_ROWS || seed_len < 0 || T > CZC_MAX_BERT_LEN) return fail(e, CZC_ERR_ARG, "generate_rows: R > CZC_MAX_ROWS, seed_len < 0 or T > CZC_MAX_BERT_LEN%s");
+    if (!e->d_img_n || e->img_B <= 0) return fail(e, CZC_ERR_STATE, "image embeds not set%s");
+    if (!image_of_row_host && e->img_B != B)
+      return fail(e, CZC_ERR_ARG, "generate_rows: image_of_row = NULL needs R equal to the resident image batch%s");
+    if (image_of_row_host)
+      for (int r = 0; r < B; ++r)
+        if (image_of_row_host[r] < 0 || image_of_row_host[r] >= e->img_B)
+          return fail(e, CZC_ERR_ARG, "generate_rows: image_of_row outside the resident image batch%s");
+    if (e->ctl_fn && hp->control)  // the callback is only called on controlled steps
+      for (size_t i = 0; i < n_pos; ++i)
+        if (positions_host[i] != positions_host[i - i % B])
+          return fail(e, CZC_ERR_ARG, "generate_rows: a control callback carries one gen_idx, so every row must visit the same position at a step; "
+                                      "use the control tables (czc_set_lexicon / czc_set_lexicon_pos / czc_set_pos) or one czc_generate call per order%s");
+    sched.resize(2 * n_pos);
+    for (size_t i = 0; i < n_pos; ++i) {
+      sched[i] = seed_len + positions_host[i];
+      sched[n_pos + i] = positions_host[i] == L - 1 ? 1 : 0;
+    }
+  }
+  int *d_inp, *d_row, *d_sched = nullptr;
   { int* flag; E_CHECK(ensure(e, "s_nonfinite", 32, (void**)&flag)); E_HIP(hipMemsetAsync(flag, 0, 32, e->st)); }
   E_CHECK(ensure(e, "g_inp", (size_t)B * T * 4, (void**)&d_inp));
   E_CHECK(ensure(e, "g_row", (size_t)T * 4, (void**)&d_row));
   E_HIP(hipMemcpyAsync(d_row, init_ids_host, (size_t)T * 4, hipMemcpyHostToDevice, e->st));
   E_CHECK(launch_broadcast_rows_i32(d_row, T, B, d_inp, e->st));
-  for (int s = 0; s < n_steps; ++s)
-    if (positions_host[s] < 0 || positions_host[s] >= L) return fail(e, CZC_ERR_ARG, "generate: position out of range%s");
+  // rows: the embedding of row r is that of image image_of_row[r] -- one gather of the normalised embeds to [R, D] here, and the
+  // step sees a resident batch of R images (what the memo's compact batches do), so no tower or combine kernel changes
+  float* img_full = e->d_img_n;
+  const int img_B = e->img_B;
+  if (rows) {
+    const int D = e->cfg.clip_proj;
+    int* d_ior = nullptr; float* img_r = nullptr;
+    if (n_pos) E_CHECK(ensure(e, "g_sched", 2 * n_pos * 4, (void**)&d_sched));
+    if (image_of_row_host) {
+      E_CHECK(ensure(e, "g_ior", (size_t)B * 4, (void**)&d_ior));
+      E_CHECK(ensure(e, "g_img_r", (size_t)B * D * 4, (void**)&img_r));
+    }
+    if (n_pos) E_HIP(hipMemcpyAsync(d_sched, sched.data(), 2 * n_pos * 4, hipMemcpyHostToDevice, e->st));
+    if (image_of_row_host) {
+      E_HIP(hipMemcpyAsync(d_ior, image_of_row_host, (size_t)B * 4, hipMemcpyHostToDevice, e->st));
+      E_CHECK(launch_gather_rows_f32(img_full, d_ior, B, D, img_r, e->st));
+      e->d_img_n = img_r; e->img_B = B;
+    }
+  }
   // what this call returns of a step: the ids it leaves in d_inp and, at the snapshot steps, the winner's cosine
   // AUDIT steps -- the snapshot step of every fourth sweep, starting with the first -- take the full selection for every
   // image: there the guard (czc_refine_guard) measures the screening tower on all images although most other steps are
@@ -1568,31 +1647,55 @@ int czc_generate(czc_engine* e, int B, int T, int L, int seed_len, const int32_t
       audited = audited || audit[s];
     } }
   MemoPlan mp;
-  if (e->memo) E_CHECK(memo_begin(e, B, T, n_steps, positions_host, n_mask_host, snapshot_every, out_cos != nullptr, audit, &mp));
-  int snap = 0;
-  for (int s = 0; s < n_steps; ++s) {
-    const int pos = positions_host[s];
+  const bool memo = e->memo && !rows;  // the memo's keys are (image, position, n_mask): a rows call runs every step whole
+  if (memo) E_CHECK(memo_begin(e, B, T, n_steps, positions_host, n_mask_host, snapshot_every, out_cos != nullptr, audit, &mp));
+  int snap = 0, rc = 0;
+  for (int s = 0; s < n_steps && !rc; ++s) {
+    const int pos = positions_host[rows ? (size_t)s * B : (size_t)s];
     const int nm = n_mask_host ? n_mask_host[s] : 1;
     const bool snap_idx = (s + 1) % snapshot_every == 0;
     e->gate_now = e->refine && e->refine_gate_delta > 0.f && e->refine_guard_dev > 0.f && !audit[s];
     e->gate_need_cos = snap_idx && out_cos != nullptr;
     e->in_generate = true;
-    if (e->memo) E_CHECK(memo_step(e, mp, s, d_inp, B, T, seed_len + pos, nm, pos == L - 1 ? 1 : 0, top_k, hp));
-    else E_CHECK(step_device(e, d_inp, B, T, seed_len + pos, nm, pos == L - 1 ? 1 : 0, top_k, hp));
+    if (rows) rc = step_device(e, d_inp, B, T, seed_len + pos, nm, pos == L - 1 ? 1 : 0, top_k, hp, d_sched + (size_t)s * B,
+                               d_sched + n_pos + (size_t)s * B, sched.data() + (size_t)s * B);
+    else if (memo) rc = memo_step(e, mp, s, d_inp, B, T, seed_len + pos, nm, pos == L - 1 ? 1 : 0, top_k, hp);
+    else rc = step_device(e, d_inp, B, T, seed_len + pos, nm, pos == L - 1 ? 1 : 0, top_k, hp);
+    if (rc) break;
     if (snap_idx) {
+      hipError_t h = hipSuccess;
       if (out_ids)
-        E_HIP(hipMemcpyAsync(out_ids + (size_t)snap * B * T, d_inp, (size_t)B * T * 4, hipMemcpyDefault, e->st));
-      if (out_cos)  // memo: the full-batch cosines (a compacted step leaves B_act of them in s_bcos)
-        E_HIP(hipMemcpyAsync(out_cos + (size_t)snap * B, e->memo ? mp.bcos : e->ws["s_bcos"].p, (size_t)B * 4, hipMemcpyDefault, e->st));
+        h = hipMemcpyAsync(out_ids + (size_t)snap * B * T, d_inp, (size_t)B * T * 4, hipMemcpyDefault, e->st);
+      if (out_cos && h == hipSuccess)  // memo: the full-batch cosines (a compacted step leaves B_act of them in s_bcos)
+        h = hipMemcpyAsync(out_cos + (size_t)snap * B, memo ? mp.bcos : e->ws["s_bcos"].p, (size_t)B * 4, hipMemcpyDefault, e->st);
+      if (h != hipSuccess) { snprintf(e->err, sizeof(e->err), "generate: snapshot copy -> %s", hipGetErrorString(h)); rc = CZC_ERR_HIP; }
       ++snap;
     }
   }
+  // rows: the resident image batch comes back whatever happened, and no later call may re-use a forward by this call's columns
+  e->d_img_n = img_full; e->img_B = img_B;
+  if (rows) { e->bert_pruned_rows = nullptr; if (rc) (void)hipStreamSynchronize(e->st); }
+  if (rc) return rc;
   E_HIP(hipMemcpyAsync(e->h_totals + 9, e->ws["s_nonfinite"].p, 24, hipMemcpyDeviceToHost, e->st));
   E_HIP(hipStreamSynchronize(e->st));
   if (e->h_totals[9]) return fail(e, CZC_ERR_OVERFLOW, "non-finite CLIP cosine: an fp16 quantity overflowed in a tower (fp16 residual rows: set option resid16 = 0 on the bf16 engine, refine_rows16 = 0 on the refine engine; fp16 operands: use CZC_PREC_SPLIT)%s");
   { float dev; memcpy(&dev, e->h_totals + 10, 4); e->guard_max_dev = fmaxf(e->guard_max_dev, dev); e->guard_trips += e->h_totals[11];
     e->stat_gated += e->h_totals[13]; e->stat_gate_images += e->h_totals[14]; }
   return CZC_OK;
+}
+
+int czc_generate(czc_engine* e, int B, int T, int L, int seed_len, const int32_t* init_ids_host, int top_k,
+                 int n_steps, const int32_t* positions_host, const int32_t* n_mask_host, int snapshot_every,
+                 const czc_hyper* hp, int32_t* out_ids, float* out_cos) {
+  return generate_impl(e, false, B, T, L, seed_len, init_ids_host, nullptr, top_k, n_steps, positions_host, n_mask_host,
+                       snapshot_every, hp, out_ids, out_cos);
+}
+
+int czc_generate_rows(czc_engine* e, int R, int T, int L, int seed_len, const int32_t* init_ids_host,
+                      const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
+                      const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp, int32_t* out_ids, float* out_cos) {
+  return generate_impl(e, true, R, T, L, seed_len, init_ids_host, image_of_row_host, top_k, n_steps, positions_host, n_mask_host,
+                       snapshot_every, hp, out_ids, out_cos);
 }
 
 int czc_set_control_callback(czc_engine* e, czc_control_fn fn, void* user) {

@@ -115,11 +115,15 @@ int launch_gather_rows_f32(const float* src, const int* idx, int M, int H, float
 int launch_gather_rows_bytes(const void* src, const int* idx, int M, int row_bytes, void* dst, hipStream_t st);
 // rows b*T+gen_idx
 int launch_make_row_index(int* idx, int B, int T, int gen_idx, hipStream_t st);
+// rows b*T+gen[b] (gen: device, [B]; czc_generate_rows)
+int launch_make_row_index_rows(int* idx, int B, int T, const int* gen, hipStream_t st);
 // idx[s] = off[s] + len[s] - 1
 int launch_eos_index(const int* off, const int* len, int n, int* idx, hipStream_t st);
 int launch_l2_normalize(const float* x, int M, int D, float* y, hipStream_t st);
 // inp[b, gen_idx .. gen_idx+n_mask) = mask_id
 int launch_mask_positions(int* inp, int B, int T, int gen_idx, int n_mask, int mask_id, hipStream_t st);
+// inp[b, gen[b] .. gen[b]+n_mask) = mask_id
+int launch_mask_positions_rows(int* inp, int B, int T, const int* gen, int n_mask, int mask_id, hipStream_t st);
 int launch_broadcast_rows_i32(const int* row, int T, int B, int* dst, hipStream_t st);
 
 // ---- memo.hip (czc_generate option "memo") --------------------------------------------------------------------------
@@ -167,6 +171,9 @@ int launch_attention_shared_split(const void* qkv, const SegTable& tab, int B, i
 // ---- topk.hip -----------------------------------------------------------------------------
 int launch_softmax_mask_topk(const float* logits, int B, int V, int K, const float* mask, float temperature, int dot_id,
                              int dot_allowed, float* probs, int* idxs, int* cand, hipStream_t st);
+// the same with the '.' rule per row: dot_rows[b] (device, [B]) in place of dot_allowed
+int launch_softmax_mask_topk_rows(const float* logits, int B, int V, int K, const float* mask, float temperature, int dot_id,
+                                  const int* dot_rows, float* probs, int* idxs, int* cand, hipStream_t st);
 
 // ---- bridge.hip ---------------------------------------------------------------------------
 struct BridgeDev {
@@ -203,6 +210,10 @@ struct PosDev {
 int launch_bridge(const BridgeDev& bd, const int* inp, int B, int T, int gen_idx, const int* cand, int K,
                   const float* lexicon, const float* lex_pos, const uint8_t* lex_cls, int negative, const PosDev& pos, int* clip_ids, int* clip_len, float* senti_raw,
                   float* repeats, int* overflow_flag, hipStream_t st);
+// the same with the substituted column per row of inp: gen_rows[b] (device, [B]) in place of gen_idx (cand must not be null)
+int launch_bridge_rows(const BridgeDev& bd, const int* inp, int B, int T, const int* gen_rows, const int* cand, int K,
+                       const float* lexicon, const float* lex_pos, const uint8_t* lex_cls, int negative, const PosDev& pos, int* clip_ids, int* clip_len,
+                       float* senti_raw, float* repeats, int* overflow_flag, hipStream_t st);
 // exclusive scan of len[n] -> off[n+1]; totals[0] = sum, totals[1] = max
 int launch_scan(const int* len, int n, int* off, int* totals, hipStream_t st);
 // Shared-prefix plan for B images x K candidates (segments: B trunks, then B*K branches):
@@ -241,6 +252,8 @@ struct CombineArgs {
   // guard of the screen-then-refine scores: nonfinite[1] <- max over the re-encoded candidates of |screening error - its
   // estimated mean| (float bits), nonfinite[2] += images where that exceeds refine_guard (0 = no guard)
   float refine_guard = 0.f;
+  // czc_generate_rows: the write-back column of row b is gen_rows[b] (device, [B]) instead of gen_idx; null = gen_idx
+  const int* gen_rows = nullptr;
 };
 // text_feat == null: clip_ref already holds the cosines
 int launch_combine(const CombineArgs& a, hipStream_t st);

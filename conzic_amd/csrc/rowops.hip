@@ -647,6 +647,17 @@ int launch_make_row_index(int* idx, int B, int T_, int gen_idx, hipStream_t st) 
   return 0;
 }
 
+// per-row columns (czc_generate_rows): idx[b] = b * T + gen[b]
+__global__ void make_row_index_rows_kernel(int* idx, int B, int T_, const int* gen) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < B) idx[b] = b * T_ + gen[b];
+}
+int launch_make_row_index_rows(int* idx, int B, int T_, const int* gen, hipStream_t st) {
+  hipLaunchKernelGGL(make_row_index_rows_kernel, dim3(cdiv(B, 256)), dim3(256), 0, st, idx, B, T_, gen);
+  CZC_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
 __global__ void eos_index_kernel(const int* off, const int* len, int n, int* idx) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) idx[i] = off[i] + len[i] - 1;
@@ -683,6 +694,23 @@ __global__ void mask_positions_kernel(int* inp, int B, int T_, int gen_idx, int 
 int launch_mask_positions(int* inp, int B, int T_, int gen_idx, int n_mask, int mask_id, hipStream_t st) {
   if (n_mask <= 0) return 0;
   hipLaunchKernelGGL(mask_positions_kernel, dim3(cdiv(B * n_mask, 256)), dim3(256), 0, st, inp, B, T_, gen_idx, n_mask,
+                     mask_id);
+  CZC_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// per-row columns (czc_generate_rows): inp[b, gen[b] .. gen[b]+n_mask) = mask_id
+__global__ void mask_positions_rows_kernel(int* inp, int B, int T_, const int* gen, int n_mask, int mask_id) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < B * n_mask) {
+    const int b = i / n_mask, j = i % n_mask;
+    const int g = gen[b];
+    if (g >= 0 && g + j < T_) inp[b * T_ + g + j] = mask_id;
+  }
+}
+int launch_mask_positions_rows(int* inp, int B, int T_, const int* gen, int n_mask, int mask_id, hipStream_t st) {
+  if (n_mask <= 0) return 0;
+  hipLaunchKernelGGL(mask_positions_rows_kernel, dim3(cdiv(B * n_mask, 256)), dim3(256), 0, st, inp, B, T_, gen, n_mask,
                      mask_id);
   CZC_HIP_CHECK(hipGetLastError());
   return 0;

@@ -52,6 +52,9 @@ def get_args(argv=None):
                    help="controllable runs: the reference's own nltk sentence scorer called back once per step (exact; what "
                         "auto picks when nltk imports) or per-token tables built from nltk and evaluated inside the engine's "
                         "kernels (table: the throughput mode, context-free approximation); sets CZC_CONTROL")
+    p.add_argument("--batch_samples", action="store_true",
+                   help="polish the samples_num samples of a batch in ONE engine call (one row per image and sample, every "
+                        "sample with the visiting order the sample loop would have drawn for it) instead of one call per sample")
     a = p.parse_args(argv)
     if a.control_scores:
         os.environ["CZC_CONTROL"] = a.control_scores
@@ -103,6 +106,15 @@ def main(argv=None):
     image_instance = images if args.batch_size > 1 else images[0]
     img_name = [f"img{j}" for j in range(args.batch_size)]
     t0 = time.time()
+    if args.batch_samples:
+        from conzic_amd.runtime import caption_samples
+        caption_samples(args.samples_num, args.run_type, img_name, lm_model, clip, lm_tokenizer, image_instance, token_mask, logger,
+                        prompt=args.prompt, batch_size=args.batch_size, max_len=args.sentence_len, top_k=args.candidate_k,
+                        temperature=args.lm_temperature, max_iter=args.num_iterations, alpha=args.alpha, beta=args.beta,
+                        generate_order=args.order, gamma=args.gamma, ctl_type=args.control_type,
+                        style_type=args.sentiment_type, pos_type=args.pos_type)
+        logger.info("total %.2fs" % (time.time() - t0))
+        return
     for sample_id in range(args.samples_num):                                   # demo.py:83 (no reseeding)
         logger.info(f"Sample {sample_id}: ")
         kw = dict(prompt=args.prompt, batch_size=args.batch_size, max_len=args.sentence_len, top_k=args.candidate_k,

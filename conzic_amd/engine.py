@@ -348,6 +348,35 @@ class Engine:
         self._ck(rc, "czc_generate")
         return ids, cos
 
+    def generate_rows(self, init_ids: Sequence[int], L: int, seed_len: int, top_k: int, positions, hyper: native.Hyper,
+                      image_of_row: Optional[Sequence[int]] = None, n_mask: Optional[Sequence[int]] = None,
+                      snapshot_every: Optional[int] = None, want_cos: bool = True):
+        """czc_generate_rows: `positions` int [n_steps, R], row r visits positions[s][r] at step s and polishes a caption for
+        resident image image_of_row[r] (None: row r = image r).  Returns (ids int32 [S,R,T], cos fp32 [S,R]) per snapshot."""
+        init = np.ascontiguousarray(init_ids, dtype=np.int32)
+        T = init.size
+        pos = np.ascontiguousarray(positions, dtype=np.int32)
+        if pos.ndim != 2 or pos.shape[1] < 1:
+            raise ValueError("generate_rows: positions must be [n_steps, R]")
+        n_steps, R = pos.shape
+        ior = None if image_of_row is None else np.ascontiguousarray(image_of_row, dtype=np.int32).reshape(-1)
+        if ior is not None and ior.size != R:
+            raise ValueError(f"generate_rows: image_of_row has {ior.size} entries for {R} rows")
+        nm = None if n_mask is None else np.ascontiguousarray(n_mask, dtype=np.int32).reshape(-1)
+        if nm is not None and nm.size != n_steps:
+            raise ValueError(f"generate_rows: n_mask has {nm.size} entries for {n_steps} steps")
+        every = snapshot_every or L
+        S = n_steps // every
+        ids = np.empty((S, R, T), dtype=np.int32)
+        cos = np.empty((S, R), dtype=np.float32) if want_cos else None
+        rc = self.lib.czc_generate_rows(self.h, R, T, L, seed_len, init.ctypes.data, None if ior is None else ior.ctypes.data,
+                                        top_k, n_steps, pos.ctypes.data, None if nm is None else nm.ctypes.data, every,
+                                        C.byref(hyper), ids.ctypes.data, None if cos is None else cos.ctypes.data)
+        if rc:
+            self._raise_scorer_error()
+        self._ck(rc, "czc_generate_rows")
+        return ids, cos
+
     def similarity(self, image_embeds, text_embeds, K: int):
         """clip/clip.py:86-98: (softmax_K(cos * exp(logit_scale)), cos), both [B, K], from un-normalised embeddings."""
         ie = np.ascontiguousarray(image_embeds, np.float32)
@@ -454,6 +483,7 @@ class EngineGroup:
         self.min_images = int(min_images)
         self._pool = ThreadPoolExecutor(max_workers=len(self.engines)) if len(self.engines) > 1 else None
         self._full_embeds = None
+        self._encoded = None  # what encode_images returned (un-normalised, as set_image_embeds takes them): generate_rows re-deals it by row
 
     @property
     def streams(self) -> int:
@@ -482,11 +512,13 @@ class EngineGroup:
         outs = self._run([(lambda e=e, lo=lo, hi=hi: e.encode_images(pixels[lo:hi])) for e, (lo, hi) in zip(self.engines, parts)])
         self._full_embeds = None  # every engine now holds its own slice
         self._resident = parts
-        return np.concatenate(outs, axis=0)
+        self._encoded = np.concatenate(outs, axis=0)  # generate_rows hands every member the embeds of its own rows
+        return self._encoded
 
     def set_image_embeds(self, embeds):
         self._full_embeds = np.ascontiguousarray(embeds, dtype=np.float32)
         self._resident = None
+        self._encoded = None
 
     def generate(self, B: int, init_ids, L: int, seed_len: int, top_k: int, positions, hyper, n_mask=None,
                  snapshot_every=None):
@@ -498,6 +530,31 @@ class EngineGroup:
             raise NativeError("EngineGroup.generate: encode_images / set_image_embeds of the same batch first")
         outs = self._run([(lambda e=e, lo=lo, hi=hi: e.generate(hi - lo, init_ids, L, seed_len, top_k, positions, hyper,
                                                                 n_mask=n_mask, snapshot_every=snapshot_every))
+                          for e, (lo, hi) in zip(self.engines, parts)])
+        return np.concatenate([o[0] for o in outs], axis=1), np.concatenate([o[1] for o in outs], axis=1)
+
+    def generate_rows(self, init_ids, L: int, seed_len: int, top_k: int, positions, hyper, image_of_row=None, n_mask=None,
+                      snapshot_every=None):
+        """Engine.generate_rows with the rows split contiguously over the streams.  `image_of_row` is resolved here: every
+        member gets the embeds of its own rows (the normalisation is per row, so they are the bits the whole batch had) and
+        runs its rows with the identity."""
+        pos = np.ascontiguousarray(positions, dtype=np.int32)
+        if pos.ndim != 2:
+            raise ValueError("generate_rows: positions must be [n_steps, R]")
+        R = pos.shape[1]
+        embeds = self._full_embeds if self._full_embeds is not None else self._encoded
+        if embeds is None:
+            raise NativeError("EngineGroup.generate_rows: encode_images / set_image_embeds first")
+        ior = np.arange(R) if image_of_row is None else np.asarray(image_of_row, dtype=np.int64).reshape(-1)
+        if ior.size != R or (R and (ior.min() < 0 or ior.max() >= embeds.shape[0])):
+            raise NativeError("EngineGroup.generate_rows: image_of_row outside the resident image batch", code=native.ERR_ARG)
+        parts = self.parts(R)
+        for e, (lo, hi) in zip(self.engines, parts):
+            e.set_image_embeds(embeds[ior[lo:hi]])
+        # the members now hold their rows' embeds: a later generate() hands the image slices over again
+        self._full_embeds, self._resident = embeds, None
+        outs = self._run([(lambda e=e, lo=lo, hi=hi: e.generate_rows(init_ids, L, seed_len, top_k, pos[:, lo:hi], hyper,
+                                                                     n_mask=n_mask, snapshot_every=snapshot_every))
                           for e, (lo, hi) in zip(self.engines, parts)])
         return np.concatenate([o[0] for o in outs], axis=1), np.concatenate([o[1] for o in outs], axis=1)
 

@@ -110,6 +110,31 @@ def order_positions(order: str, L: int, iters: int, order_list=None, random_posi
     raise ValueError(order)
 
 
+def sample_schedules(order: str, L: int, max_iters: int, S: int):
+    """Visiting orders of S samples of one *_generation call each, drawn in the order and from the process-global RNG streams
+    the serial sample loop would (demo.py:83 / run.py around the call): one `random.shuffle` per sample for `shuffle`
+    (gen_utils.py:110-111), `max_iters` `np.random.randint` per sample for `random` (gen_utils.py:210; `max_iters` as the
+    *_generation function receives it: steps for `random`, sweeps otherwise), nothing for `sequential` / `span`.  Afterwards
+    both streams are where S serial calls would have left them.  Returns (positions int32 [n_steps, S] for
+    czc_generate_rows, n_mask [n_steps], snapshot_every, order_lists: the S shuffled lists, or None)."""
+    import random
+    cols, order_lists, n_mask, every = [], ([] if order == "shuffle" else None), None, None
+    for _ in range(S):
+        if order == "shuffle":
+            order_list = list(range(L))
+            random.shuffle(order_list)
+            order_lists.append(order_list)
+            pos, n_mask, every = order_positions(order, L, max_iters, order_list=order_list)
+        elif order == "random":
+            pos = [int(np.random.randint(0, L)) for _ in range(max_iters)]
+            n_mask, every = [1] * len(pos), 1
+        else:
+            pos, n_mask, every = order_positions(order, L, max_iters)
+        cols.append(pos)
+    positions = np.ascontiguousarray(np.array(cols, dtype=np.int32).reshape(S, -1).T)
+    return positions, list(n_mask), every, order_lists
+
+
 def first_divergence(engine, emb_row, init_row, ref_snaps, got_snaps, L, seed_len, K, hp, positions_per_sweep=None):
     """Where and how closely one image left a reference trajectory.  `ref_snaps` / `got_snaps`: int32 [S, T] per-sweep snapshots
     of that image from the reference engine (`engine`, e.g. the all-split one) and from the engine under test, sequential

@@ -51,6 +51,47 @@ def batches(names, batch_size):
         yield names[s:s + batch_size]
 
 
+def batched_samples(args, run_type, all_batches, own_lo, own_hi, rank, world, img_dir, lm_model, clip, lm_tokenizer, token_mask,
+                    logger):
+    """--batch_samples: every batch polishes its samples_num samples in one engine call (runtime.run_generation_samples).  The
+    visiting orders of ALL (sample, batch) pairs are drawn first, in the sample loop's order, so every pair sees the order it
+    sees without the flag (and every rank the same ones); the files are written sample for sample as without it."""
+    from PIL import Image
+    from conzic_amd.harness import sample_schedules
+    from conzic_amd.runtime import caption_order, caption_samples
+    S, nb = args.samples_num, len(all_batches)
+    order, max_iters = caption_order(args.run_type, args.order, args.control_type, args.num_iterations, args.sentence_len)
+    positions, n_mask, every, order_lists = sample_schedules(order, args.sentence_len, max_iters, S * nb)
+    results = [[None] * (args.num_iterations + 1) for _ in range(S)]
+    for batch_idx, name_batch in enumerate(all_batches):
+        if not (own_lo <= batch_idx < own_hi):
+            continue
+        logger.info(f"The {batch_idx + 1}-th batch:")
+        cols = [s * nb + batch_idx for s in range(S)]   # the serial loop walks samples outside, batches inside
+        sched = (positions[:, cols], n_mask, every, None if order_lists is None else [order_lists[c] for c in cols])
+        imgs = [Image.open(os.path.join(img_dir, n)).convert("RGB") for n in name_batch]
+        outs = caption_samples(S, args.run_type, name_batch, lm_model, clip, lm_tokenizer, imgs, token_mask, logger,
+                               prompt=args.prompt, batch_size=args.batch_size, max_len=args.sentence_len, top_k=args.candidate_k,
+                               temperature=args.lm_temperature, max_iter=args.num_iterations, alpha=args.alpha, beta=args.beta,
+                               generate_order=args.order, gamma=args.gamma, ctl_type=args.control_type,
+                               style_type=args.sentiment_type, pos_type=args.pos_type, schedules=sched)
+        for s, (gen_texts, _) in enumerate(outs):
+            results[s] = merge_results(results[s], gen_texts, name_batch)
+    for sample_id in range(S):
+        all_results = results[sample_id]
+        if world > 1:
+            import torch.distributed as tdist
+            parts = [None] * world
+            tdist.all_gather_object(parts, all_results)
+            all_results = [None] * (args.num_iterations + 1)
+            for part in parts:  # rank order == batch order
+                for it, d in enumerate(part):
+                    if d is not None:
+                        all_results[it] = {**(all_results[it] or {}), **d}
+        if rank == 0:
+            write_results(result_dir(args, run_type, sample_id), all_results)
+
+
 def main(argv=None):
     args = get_args(argv)
     import logging
@@ -114,6 +155,10 @@ def main(argv=None):
     all_batches = list(batches(names, args.batch_size))
     own_lo, own_hi = czd.shard_range(len(all_batches), rank, world)
     embed_cache = {}  # batch index -> image_embeds [B, proj]: the ViT runs once per image, not once per sample
+    if args.batch_samples:
+        batched_samples(args, run_type, all_batches, own_lo, own_hi, rank, world, img_dir, lm_model, clip, lm_tokenizer,
+                        token_mask, logger)
+        return
     for sample_id in range(args.samples_num):
         all_results = [None] * (args.num_iterations + 1)
         logger.info(f"Sample {sample_id + 1}: ")

@@ -22,7 +22,7 @@ import numpy as np
 from . import native, synth
 from .bridge import tables_from_tokenizers
 from .engine import Engine
-from .harness import order_positions
+from .harness import order_positions, sample_schedules
 
 # bf16 CLIP towers carry a cosine error of up to ~4e-3; clip/clip.py:95-98 multiplies the cosine by
 # logit_scale.exp() ahead of softmax_K, so the fused score stays inside the 1e-3 budget only while that factor is
@@ -235,6 +235,75 @@ def memo_setting() -> int:
     raise ValueError(f"CZC_MEMO={v!r}: expected 0 or 1")
 
 
+def _polish_guarded(polish, eng, model, clip, tokenizer, image_instance, logger):
+    """`polish(engine) -> ((ids, cos), runner)` with what every generation call does around it: the overflow retry on fp32 rows
+    and the screen-then-refine guard's rerun on the all-split engine."""
+    try:
+        (ids, cos), runner = polish(eng)
+    except native.NativeError as exc:
+        # the bf16 engine -- and, inside czc_generate, the screening pass of the screen-then-refine engine -- keep the text tower's
+        # residual stream as fp16 rows (|x| < 65504): a checkpoint whose rows leave that range shows up as a non-finite cosine
+        # (CZC_ERR_OVERFLOW); its engine then goes back to fp32 rows for good
+        opt = {native.PREC_BF16: "resid16", native.PREC_REFINE: "refine_rows16"}.get(eng.precision)
+        if getattr(exc, "code", None) != native.ERR_OVERFLOW or "non-finite" not in str(exc) or opt is None \
+                or getattr(eng, "_resid16_off", False):
+            raise   # (CZC_ERR_OVERFLOW also names the text bridge's scratch overflow: no other rows would help there)
+        logger.info(f"the fp16 residual stream overflowed on this checkpoint; repeating the call with fp32 rows "
+                    f"(engine option {opt} = 0, kept for this engine)")
+        eng.set_option(opt, 0)
+        eng._resid16_off = True
+        (ids, cos), runner = polish(eng)
+    guard_mode = os.environ.get("CZC_REFINE_GUARD", "rerun").lower()
+    if eng.precision == native.PREC_REFINE and guard_mode != "off":
+        # the screen-then-refine engine's 1e-3 bound rests on the single-pass fp16 tower's error staying near what it is
+        # on the validated weights; every step measures that error on the candidates it re-encodes exactly
+        g = runner.refine_guard(reset=True)
+        if g["tripped"]:
+            trip = eng.get_option("refine_guard_generate_x1e6") * 1e-6   # the trip point the engine applied inside czc_generate
+            logger.info(f"screen-then-refine guard: |screening error - mean| reached {g['max_dev']:.2e} on {g['tripped']} "
+                        f"image-steps (trip point {trip:.1e})" + ("; repeating the call on the all-split engine" if guard_mode == "rerun" else ""))
+            if guard_mode == "rerun":
+                from clip.clip import ImageEmbeds
+                emb = image_instance.embeds if isinstance(image_instance, ImageEmbeds) else clip.last_image_embeds()
+                # the replicas' workspaces (one per stream) go before the second engine is built on the same GPU
+                grp = getattr(eng, "_group", None)
+                if grp is not None:
+                    grp.close(parent=False)
+                    eng._group = None
+                eng2 = get_engine(model, clip, tokenizer, precision=native.PREC_SPLIT)
+                eng2.set_image_embeds(emb)   # the refine engine's vision tower is the split-fp16 one: same embeddings
+                (ids, cos), _ = polish(eng2)
+                clip._engine = eng
+    return ids, cos
+
+
+def _bookkeeping(order, ids, cos, tokenizer, img_name, logger, batch_size, verbose, print_every):
+    """gen_utils.py:82-96 on the snapshots of one *_generation call: (gen_texts_list, clip_score_sequence)."""
+    best_score = [0] * batch_size
+    best_cap = ['None'] * batch_size
+    texts_out, scores_out = [], []
+    pe = print_every or 1
+    for s in range(ids.shape[0]):
+        cur = [float(x) for x in cos[s]]
+        cur_text = tokenizer.batch_decode(ids[s].tolist(), skip_special_tokens=True)
+        for jj in range(batch_size):
+            if best_score[jj] < cur[jj]:
+                best_score[jj] = cur[jj]
+                best_cap[jj] = cur_text[jj]
+        if order == "random" and not (verbose and (s + 1) % pe == 0):
+            continue  # gen_utils.py:232-238: the random order only records a snapshot inside its verbose branch
+        if verbose:
+            for_print = tokenizer.batch_decode(ids[s].tolist())
+            for jj in range(batch_size):
+                logger.info(f"iter {s + 1}, The {jj + 1}-th image: {img_name[jj]},"
+                            f"clip score {cur[jj]:.3f}: " + for_print[jj])
+        texts_out.append(cur_text)
+        scores_out.append(cur)
+    texts_out.append(best_cap)
+    scores_out.append(best_score)
+    return texts_out, scores_out
+
+
 def run_generation(order: str, img_name, model, clip, tokenizer, image_instance, token_mask, prompt, logger, max_len,
                    top_k, temperature, alpha, beta, max_iters, batch_size, verbose=True, gamma=None,
                    ctl_signal="positive", print_every: Optional[int] = None, pos_template=None):
@@ -294,67 +363,129 @@ def run_generation(order: str, img_name, model, clip, tokenizer, image_instance,
             eng.set_image_embeds(emb)  # the first engine holds the whole batch again, as after a single-stream call
         return out, runner
 
-    try:
-        (ids, cos), runner = polish(eng)
-    except native.NativeError as exc:
-        # the bf16 engine -- and, inside czc_generate, the screening pass of the screen-then-refine engine -- keep the text tower's
-        # residual stream as fp16 rows (|x| < 65504): a checkpoint whose rows leave that range shows up as a non-finite cosine
-        # (CZC_ERR_OVERFLOW); its engine then goes back to fp32 rows for good
-        opt = {native.PREC_BF16: "resid16", native.PREC_REFINE: "refine_rows16"}.get(eng.precision)
-        if getattr(exc, "code", None) != native.ERR_OVERFLOW or "non-finite" not in str(exc) or opt is None \
-                or getattr(eng, "_resid16_off", False):
-            raise   # (CZC_ERR_OVERFLOW also names the text bridge's scratch overflow: no other rows would help there)
-        logger.info(f"the fp16 residual stream overflowed on this checkpoint; repeating the call with fp32 rows "
-                    f"(engine option {opt} = 0, kept for this engine)")
-        eng.set_option(opt, 0)
-        eng._resid16_off = True
-        (ids, cos), runner = polish(eng)
-    guard_mode = os.environ.get("CZC_REFINE_GUARD", "rerun").lower()
-    if eng.precision == native.PREC_REFINE and guard_mode != "off":
-        # the screen-then-refine engine's 1e-3 bound rests on the single-pass fp16 tower's error staying near what it is
-        # on the validated weights; every step measures that error on the candidates it re-encodes exactly
-        g = runner.refine_guard(reset=True)
-        if g["tripped"]:
-            trip = eng.get_option("refine_guard_generate_x1e6") * 1e-6   # the trip point the engine applied inside czc_generate
-            logger.info(f"screen-then-refine guard: |screening error - mean| reached {g['max_dev']:.2e} on {g['tripped']} "
-                        f"image-steps (trip point {trip:.1e})" + ("; repeating the call on the all-split engine" if guard_mode == "rerun" else ""))
-            if guard_mode == "rerun":
-                from clip.clip import ImageEmbeds
-                emb = image_instance.embeds if isinstance(image_instance, ImageEmbeds) else clip.last_image_embeds()
-                # the replicas' workspaces (one per stream) go before the second engine is built on the same GPU
-                grp = getattr(eng, "_group", None)
-                if grp is not None:
-                    grp.close(parent=False)
-                    eng._group = None
-                eng2 = get_engine(model, clip, tokenizer, precision=native.PREC_SPLIT)
-                eng2.set_image_embeds(emb)   # the refine engine's vision tower is the split-fp16 one: same embeddings
-                (ids, cos), _ = polish(eng2)
-                clip._engine = eng
+    ids, cos = _polish_guarded(polish, eng, model, clip, tokenizer, image_instance, logger)
     # utils.update_token_mask mutates the caller's mask in place (utils.py:53-59): leave it as the
     # reference would after the last visited position
     if positions:
         ref_utils.update_token_mask(tokenizer, token_mask, max_len, positions[-1])
-    # bookkeeping (gen_utils.py:82-96)
-    best_score = [0] * batch_size
-    best_cap = ['None'] * batch_size
-    texts_out, scores_out = [], []
-    pe = print_every or 1
-    for s in range(ids.shape[0]):
-        cur = [float(x) for x in cos[s]]
-        cur_text = tokenizer.batch_decode(ids[s].tolist(), skip_special_tokens=True)
-        for jj in range(batch_size):
-            if best_score[jj] < cur[jj]:
-                best_score[jj] = cur[jj]
-                best_cap[jj] = cur_text[jj]
-        if order == "random" and not (verbose and (s + 1) % pe == 0):
-            continue  # gen_utils.py:232-238: the random order only records a snapshot inside its verbose branch
-        if verbose:
-            for_print = tokenizer.batch_decode(ids[s].tolist())
-            for jj in range(batch_size):
-                logger.info(f"iter {s + 1}, The {jj + 1}-th image: {img_name[jj]},"
-                            f"clip score {cur[jj]:.3f}: " + for_print[jj])
-        texts_out.append(cur_text)
-        scores_out.append(cur)
-    texts_out.append(best_cap)
-    scores_out.append(best_score)
-    return texts_out, scores_out
+    return _bookkeeping(order, ids, cos, tokenizer, img_name, logger, batch_size, verbose, print_every)
+
+
+def run_generation_samples(order: str, samples_num: int, img_name, model, clip, tokenizer, image_instance, token_mask, prompt,
+                           logger, max_len, top_k, temperature, alpha, beta, max_iters, batch_size, verbose=True, gamma=None,
+                           ctl_signal="positive", print_every: Optional[int] = None, pos_template=None, schedules=None):
+    """The sample loop around a *_generation call (demo.py:83, run.py) as ONE engine call: `samples_num` samples of a batch of
+    `batch_size` images ride as batch_size * samples_num rows of czc_generate_rows, every sample with the visiting order the
+    serial loop would have drawn for it (harness.sample_schedules); the images are encoded once.  Returns a list of
+    `samples_num` (gen_texts_list, clip_score_sequence) pairs, the s-th as the s-th serial `run_generation` call returns it,
+    and logs every sample's lines in the serial loop's order.  The reference's own sentence scorer (exact control mode) is
+    told one position per step, so with orders that differ between samples the engine is called once per sample, as the serial
+    loop calls it (same orders, same results, the images still encoded once), and the log says why.
+    `schedules`: what harness.sample_schedules returned for these samples when the caller drew the orders itself (run_cli draws
+    those of all batches first, in the serial loop's sample-major order); None: drawn here."""
+    import utils as ref_utils
+    S, B = int(samples_num), int(batch_size)
+    eng = get_engine(model, clip, tokenizer)
+    seed_len = len(prompt.split()) + 1
+    batch = ref_utils.get_init_text(tokenizer, prompt, max_len, B)
+    clip.compute_image_representation_from_image_instance(image_instance)   # once per image, not once per sample
+    if getattr(eng, "_precision_logged", None) is None:
+        scale = _logit_scale_of(clip)
+        logger.info(f"engine precision: {PRECISION_NAMES.get(eng.precision, eng.precision)}"
+                    + (f" (exp(logit_scale) = {math.exp(scale):.1f})" if scale is not None else ""))
+        eng._precision_logged = True
+    positions, n_mask, every, order_lists = schedules if schedules is not None else sample_schedules(order, max_len, max_iters, S)
+    positions = np.asarray(positions, dtype=np.int32)
+    assert positions.ndim == 2 and positions.shape[1] == S, positions.shape
+    rows_pos = np.ascontiguousarray(np.repeat(positions, B, axis=1))   # row s * B + b: sample s of image b
+    image_of_row = np.tile(np.arange(B, dtype=np.int32), S)
+    orders_differ = bool((positions != positions[:, :1]).any())
+    hp = Engine.hyper(alpha, beta, temperature, gamma, ctl_signal == "negative",
+                      control="pos" if pos_template is not None else None)
+
+    def polish(eng):
+        eng.set_token_mask(_mask_to_numpy(token_mask))
+        eng.set_option("memo", memo_setting())  # a rows call runs every step whole (include/conzic_hip.h)
+        chosen = None
+        if gamma is not None:
+            from . import control
+            chosen = control.configure(eng, clip, tokenizer, pos_template=pos_template, ctl_signal=ctl_signal)
+            if chosen != getattr(eng, "_control_logged", None):
+                logger.info(f"control scores: {chosen}")
+                eng._control_logged = chosen
+        # the exact control scorer (a callback with ONE gen_idx per step) cannot serve rows at different positions
+        one_by_one = gamma is not None and chosen == "exact" and orders_differ
+        if one_by_one and not getattr(eng, "_one_by_one_logged", False):
+            logger.info("batched samples: the exact control scorer is called with one position per step and the samples' "
+                        f"{order} orders differ; running the {S} samples one call at a time (CZC_CONTROL=table batches them)")
+            eng._one_by_one_logged = True
+        runner = _group_for(eng, B if one_by_one else B * S)
+        emb = None
+        if runner is not eng:
+            from clip.clip import ImageEmbeds
+            emb = image_instance.embeds if isinstance(image_instance, ImageEmbeds) else clip.last_image_embeds()
+            runner.set_image_embeds(emb)
+        if eng.precision == native.PREC_REFINE:
+            runner.refine_guard(reset=True)
+        if one_by_one:
+            outs = [runner.generate(B, batch[0], max_len, seed_len, top_k, positions[:, s].tolist(), hp, n_mask=n_mask,
+                                    snapshot_every=every) for s in range(S)]
+            out = tuple(np.concatenate([o[j] for o in outs], axis=1) for j in (0, 1))
+        else:
+            out = runner.generate_rows(batch[0], max_len, seed_len, top_k, rows_pos, hp, image_of_row=image_of_row,
+                                       n_mask=n_mask, snapshot_every=every)
+        if runner is not eng:
+            eng.set_image_embeds(emb)
+        return out, runner
+
+    ids, cos = _polish_guarded(polish, eng, model, clip, tokenizer, image_instance, logger)
+    if positions.shape[0]:   # the caller's mask as after the LAST sample's last position (utils.py:53-59)
+        ref_utils.update_token_mask(tokenizer, token_mask, max_len, int(positions[-1, S - 1]))
+    out = []
+    for s in range(S):
+        if order_lists is not None:
+            logger.info(f"Order_list:{order_lists[s]}")
+        out.append(_bookkeeping(order, ids[:, s * B:(s + 1) * B], cos[:, s * B:(s + 1) * B], tokenizer, img_name, logger, B,
+                                verbose, print_every))
+    return out
+
+
+def caption_order(run_type: str, generate_order: str, ctl_type: str, max_iter: int, max_len: int):
+    """(visiting order, max_iters) the *_generation function behind generate_caption / control_generate_caption runs with."""
+    if run_type == "caption":
+        return generate_order, (max_iter * max_len if generate_order == "random" else max_iter)   # gen_utils.py:305-306
+    if ctl_type == "sentiment":
+        return ("sequential" if generate_order == "sequential" else "shuffle"), max_iter         # control_gen_utils.py:205-217
+    return "sequential", max_iter                                                                 # control_gen_utils.py:218-223
+
+
+def caption_samples(samples_num: int, run_type: str, img_name, model, clip, tokenizer, image_instance, token_mask, logger, *,
+                    prompt="", batch_size=1, max_len=15, top_k=100, temperature=1.0, max_iter=500, alpha=0.7, beta=1,
+                    generate_order="sequential", gamma=5, ctl_type="sentiment", style_type="positive", pos_type=None,
+                    schedules=None):
+    """`--batch_samples` of the two CLIs: what `samples_num` calls of generate_caption (run_type 'caption', gen_utils.py:289-333)
+    or control_generate_caption (control_gen_utils.py:197-232) return, from one run_generation_samples call.  Returns the list
+    of (generate_texts, clip_scores) pairs and logs every sample's final and best captions as those functions do."""
+    start_time = time.time()
+    kw = dict(verbose=True)
+    if run_type == "caption" and generate_order not in ("sequential", "shuffle", "span", "random"):
+        raise ValueError(f"generate_order must be sequential|shuffle|random|span, got {generate_order!r}")
+    order, max_iters = caption_order(run_type, generate_order, ctl_type, max_iter, max_len)
+    if run_type == "caption":
+        if order == "random":
+            kw["print_every"] = max_len
+    elif ctl_type == "sentiment":
+        kw.update(gamma=gamma, ctl_signal=style_type)
+    else:
+        logger.info(pos_type)
+        kw.update(gamma=gamma, pos_template=pos_type)
+    outs = run_generation_samples(order, samples_num, img_name, model, clip, tokenizer, image_instance, token_mask, prompt,
+                                  logger, max_len, top_k, temperature, alpha, beta, max_iters, batch_size, schedules=schedules, **kw)
+    logger.info("Finished %d samples in %.3fs" % (samples_num, time.time() - start_time))
+    for sample_id, (generate_texts, _) in enumerate(outs):
+        logger.info(f"Sample {sample_id}: ")
+        for i in range(batch_size):
+            logger.info(f"The {i + 1}-th image: {img_name[i]}")
+            logger.info(f"final caption: {generate_texts[-2][i]}")
+            logger.info(f"best caption: {generate_texts[-1][i]}")
+    return outs

@@ -82,6 +82,7 @@ extern "C" {
  */
 #define CZC_MAX_TOPK 1024
 #define CZC_MAX_BERT_LEN 64
+#define CZC_MAX_ROWS 16384 /* rows of one czc_generate_rows call */
 
 typedef struct czc_engine czc_engine;
 
@@ -258,6 +259,29 @@ int czc_step(czc_engine* e, int32_t* inp, int B, int T, int gen_idx, int n_mask,
 int czc_generate(czc_engine* e, int B, int T, int L, int seed_len, const int32_t* init_ids_host, int top_k,
                  int n_steps, const int32_t* positions_host, const int32_t* n_mask_host, int snapshot_every,
                  const czc_hyper* hp, int32_t* out_ids, float* out_cos);
+
+/* czc_generate with a visiting order and an image PER ROW: R rows; row r polishes a caption for image image_of_row[r] (index
+ * into the resident embeds of the last czc_encode_images / czc_set_image_embeds; NULL = identity, then R must equal that
+ * batch; several rows may name one image) and visits positions[s*R + r] at step s.  Everything else as czc_generate: one
+ * init row for all rows, n_mask[n_steps] one value per step for all rows, out_ids int32 [n_steps/snapshot_every, R, T],
+ * out_cos fp32 [n_steps/snapshot_every, R].  This is the shape of the reference's sample loop (demo.py:83 / run.py: S calls for
+ * S samples of an image, each with a new shuffle / random order, gen_utils.py:110-111, :210) as ONE batch.  The schedule
+ * (column and '.' rule of every row and step) is uploaded once; a step reads its slice on the device, so the call has
+ * czc_generate's host traffic.  Rows are independent (gen_utils.py:64-81 has no cross-row term): row r returns what a
+ * czc_generate call with row r's order returns for its image at the same row count, and a call whose rows all share one order
+ * (image_of_row NULL or the identity) returns what czc_generate returns, bit for bit.  The n_mask = 0 re-use rule of czc_step
+ * holds per row.  Checked before any GPU work, CZC_ERR_ARG: positions in [0, L), image_of_row inside the resident batch,
+ * R <= CZC_MAX_ROWS.  Two limits:
+ *   - control callback (czc_set_control_callback): its signature carries one gen_idx, so a controlled call (czc_hyper.control
+ *     != 0) with a callback set is accepted only if at every step all rows share one position (it then behaves as in
+ *     czc_generate); otherwise CZC_ERR_ARG.
+ *     The way out: the control tables (czc_set_lexicon / czc_set_lexicon_pos / czc_set_pos), which work with differing
+ *     positions, or one czc_generate call per order.
+ *   - option "memo": its keys are (image, position, n_mask) per step group, which a rows call does not have; a rows call runs
+ *     every step whole and czc_memo_stats counts nothing for it. */
+int czc_generate_rows(czc_engine* e, int R, int T, int L, int seed_len, const int32_t* init_ids_host,
+                      const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
+                      const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp, int32_t* out_ids, float* out_cos);
 
 /* Engine options (all are exact work reductions / kernel choices; results agree within the engine precision):
  *   "share_prefix"    (1) encode the causal prefix common to an image's K candidates once per step instead of K

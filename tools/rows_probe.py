@@ -1,0 +1,73 @@
+#!/usr/bin/env python3
+"""S samples of ONE image: the serial sample loop (S czc_generate calls at batch size 1, what demo.py:83 does) against one
+czc_generate_rows call with S rows, every sample under its own shuffle order.  Full-size towers, L = 10, K = 200, 10 sweeps,
+the precision the runtime picks for the logit scale (2.6592 -> bf16, 4.6052 -> screen-then-refine).
+
+    python tools/rows_probe.py [--S 1 2 4 8 16] [--reps 3] [--out profiles/r08_rows_probe.json]
+
+Per (logit scale, S): wall time of both arms, warm (one untimed call of each first), --reps repetitions alternating
+serial / rows, whether the ids of every sweep agree row for row, and the ratios.  The JSON file holds one object per case."""
+import argparse
+import json
+import os
+import random
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from conzic_amd import harness, runtime  # noqa: E402
+from conzic_amd.engine import Engine  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--S", type=int, nargs="+", default=[1, 2, 4, 8, 16])
+ap.add_argument("--L", type=int, default=10)
+ap.add_argument("--K", type=int, default=200)
+ap.add_argument("--sweeps", type=int, default=10)
+ap.add_argument("--reps", type=int, default=3)
+ap.add_argument("--scales", type=float, nargs="+", default=[2.6592, 4.6052])
+ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r08_rows_probe.json"))
+args = ap.parse_args()
+
+L, K, SEED_LEN = args.L, args.K, 4
+out = []
+for scale in args.scales:
+    prec = runtime.choose_precision(scale)
+    su = harness.build_synthetic(False, prec, logit_scale=scale, regular_only=True)
+    eng = su.engine
+    emb = np.random.default_rng(100).standard_normal((1, su.clip_cfg.proj)).astype(np.float32)
+    eng.set_image_embeds(emb)
+    init = su.bert_tok.encode("Image of a" + su.bert_tok.mask_token * L)
+    hp = Engine.hyper(0.02, 2.0, 0.1)
+    for S in args.S:
+        random.seed(42)
+        positions, n_mask, every, _ = harness.sample_schedules("shuffle", L, args.sweeps, S)
+
+        def serial():
+            return [eng.generate(1, init, L, SEED_LEN, K, positions[:, s].tolist(), hp, n_mask=n_mask, snapshot_every=every)
+                    for s in range(S)]
+
+        def rows():
+            return eng.generate_rows(init, L, SEED_LEN, K, positions, hp, image_of_row=[0] * S, n_mask=n_mask, snapshot_every=every)
+
+        ref, got = serial(), rows()  # warm-up (workspace growth) and the comparison
+        same = all(np.array_equal(ref[s][0][:, 0], got[0][:, s]) for s in range(S))
+        t_serial, t_rows = [], []
+        for _ in range(args.reps):
+            for fn, acc in ((serial, t_serial), (rows, t_rows)):
+                eng.sync()
+                t0 = time.perf_counter()
+                fn()
+                acc.append(time.perf_counter() - t0)
+        rec = dict(logit_scale=scale, precision=runtime.PRECISION_NAMES[prec], S=S, L=L, K=K, sweeps=args.sweeps, order="shuffle",
+                   wall_s_serial=t_serial, wall_s_rows=t_rows, captions_per_s_serial=S / min(t_serial), captions_per_s_rows=S / min(t_rows),
+                   speedup_best=min(t_serial) / min(t_rows), rows_faster_in_every_rep=all(r < s for r, s in zip(t_rows, t_serial)),
+                   ids_identical=bool(same))
+        print(json.dumps(rec), flush=True)
+        out.append(rec)
+    eng.close()
+os.makedirs(os.path.dirname(args.out), exist_ok=True)
+with open(args.out, "w") as f:
+    json.dump(out, f, indent=1)

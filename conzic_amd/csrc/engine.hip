@@ -162,6 +162,10 @@ struct czc_engine {
   int memo = 0;
   int memo_branch_floor = 0;  // compacted step: longest branch the HIT images had (the full batch's attention-kernel choice)
   int64_t stat_memo_hits = 0, stat_memo_images = 0;  // image-steps that took an entry / all image-steps of memo calls
+  // option "memo_rows" (czc_generate_rows only; memo_rows.hip): the same rule keyed per row, with counters of its own
+  int memo_rows = 0;
+  int64_t stat_memo_row_hits = 0, stat_memo_row_steps = 0;  // row-steps that took an entry / all row-steps of memo_rows calls
+  int32_t* h_memo_list = nullptr; size_t h_memo_list_cap = 0;  // pinned: the active rows of a checked step, read with their count
 };
 
 namespace {
@@ -1055,6 +1059,153 @@ int memo_step(czc_engine* e, MemoPlan& mp, int s, int* d_inp, int B, int T, int 
                              mp.bcos, rows, cos, imax, e->st) ? fail(e, CZC_ERR_HIP, "%s", g_err) : 0;
 }
 
+// ---- option "memo_rows" (czc_generate_rows): the per-row step memo of memo_rows.hip -----------------------------------
+// n_mask is one value per step for all rows, so the step groups are those of memo_begin and shared by the rows; the positions
+// are per row.  Row r's entry for a group sits in slot (first position of the group, r) under the group's signature (n_mask,
+// length, column of the second step): the same first position under another shape replaces it.
+struct MemoRowsPlan {
+  std::vector<int> first, sub;   // per step: first step of its group, index inside the group
+  std::vector<int> group_len;    // per group-start step
+  std::vector<char> record;      // per group-start step: the group has an entry (starts with n_mask >= 1, fits MEMO_ROWS_SUB)
+  std::vector<char> check;       // per group-start step: the host knows some row revisits a key and the step may hit
+  MemoRowsTab tab{};
+  int *hit = nullptr, *cnt = nullptr, *list = nullptr, *tot = nullptr, *inp_c = nullptr, *col_c = nullptr, *dot_c = nullptr;
+  float *bcos = nullptr, *img_c = nullptr;
+  std::vector<int32_t> h_col_c[MEMO_ROWS_SUB];  // compact batch of the group in progress: the active rows' column at every step
+  int n_act = 0;  // of the group in progress
+  int branch_max[MEMO_ROWS_SUB] = {0, 0};
+};
+
+// the signature word of memo_rows.hip (mr_sig) as the host keeps it to tell whether a step can hit at all
+static inline int memo_rows_sig(int n_mask0, int n_sub, int col1) { return (n_mask0 & 0xff) | (n_sub << 8) | ((n_sub > 1 ? col1 + 1 : 0) << 16); }
+
+int memo_rows_begin(czc_engine* e, int R, int T, int L, int seed_len, int n_steps, const int32_t* positions, const int32_t* n_mask,
+                    int snapshot_every, bool want_cos, const std::vector<char>& audit, MemoRowsPlan* mp) {
+  static_assert(MEMO_ROWS_SUB == MEMO_SUB, "the rows memo keeps the step memo's group size");
+  mp->first.assign(n_steps, 0); mp->sub.assign(n_steps, 0); mp->group_len.assign(n_steps, 0);
+  mp->record.assign(n_steps, 0); mp->check.assign(n_steps, 0);
+  std::vector<int> seen((size_t)R * L, -1);  // per slot: the signature it was last recorded under in this call
+  for (int s = 0; s < n_steps;) {
+    int g = 1;
+    while (s + g < n_steps && n_mask && n_mask[s + g] <= 0) ++g;
+    const int nm0 = n_mask ? n_mask[s] : 1;
+    mp->group_len[s] = g;
+    for (int j = 0; j < g; ++j) { mp->first[s + j] = s; mp->sub[s + j] = j; }
+    if (nm0 >= 1 && nm0 <= T && g <= MEMO_ROWS_SUB) {
+      bool hittable = true;  // CZC_PREC_REFINE: the step-level rule of memo_begin
+      for (int j = 0; j < g; ++j) {
+        const bool cos_out = want_cos && (s + j + 1) % snapshot_every == 0;
+        if (e->refine && (audit[s + j] || cos_out)) hittable = false;
+      }
+      bool revisit = false;
+      for (int r = 0; r < R; ++r) {
+        const int sig = memo_rows_sig(nm0, g, g > 1 ? seed_len + positions[(size_t)(s + 1) * R + r] : 0);
+        int& was = seen[(size_t)r * L + positions[(size_t)s * R + r]];
+        revisit = revisit || was == sig;
+        was = sig;
+      }
+      mp->record[s] = 1;
+      mp->check[s] = revisit && hittable;
+    }
+    s += g;
+  }
+  MemoRowsTab& m = mp->tab;
+  m.R = R; m.T = T; m.L = L; m.seed_len = seed_len;
+  const size_t n_slot = (size_t)L * R, D = (size_t)e->cfg.clip_proj;
+  E_CHECK(ensure(e, "mr_valid", n_slot * 4, (void**)&m.valid));
+  E_CHECK(ensure(e, "mr_sig", n_slot * 4, (void**)&m.sig));
+  E_CHECK(ensure(e, "mr_key", n_slot * T * 4, (void**)&m.key));
+  E_CHECK(ensure(e, "mr_rows", n_slot * MEMO_ROWS_SUB * T * 4, (void**)&m.rows));
+  E_CHECK(ensure(e, "mr_cos", n_slot * MEMO_ROWS_SUB * 4, (void**)&m.cos));
+  E_CHECK(ensure(e, "mr_imax", n_slot * MEMO_ROWS_SUB * 4, (void**)&m.imax));
+  E_CHECK(ensure(e, "mr_hit", (size_t)R * 4, (void**)&mp->hit));
+  E_CHECK(ensure(e, "mr_cnt", (size_t)((R + 255) / 256) * 4, (void**)&mp->cnt));
+  E_CHECK(ensure(e, "mr_list", (size_t)R * 4, (void**)&mp->list));
+  E_CHECK(ensure(e, "mr_tot", 16, (void**)&mp->tot));
+  E_CHECK(ensure(e, "mr_bcos", (size_t)R * 4, (void**)&mp->bcos));
+  E_CHECK(ensure(e, "mr_inp_c", (size_t)R * T * 4, (void**)&mp->inp_c));
+  E_CHECK(ensure(e, "mr_img_c", (size_t)R * D * 4, (void**)&mp->img_c));
+  E_CHECK(ensure(e, "mr_col_c", (size_t)R * 4, (void**)&mp->col_c));
+  E_CHECK(ensure(e, "mr_dot_c", (size_t)R * 4, (void**)&mp->dot_c));
+  E_HIP(hipMemsetAsync(m.valid, 0, n_slot * 4, e->st));  // entries live for one call
+  const size_t want = ((size_t)R + 4) * 4;  // the check's totals (16 bytes), then its list
+  if (e->h_memo_list_cap < want) {
+    E_HIP(hipStreamSynchronize(e->st));
+    if (e->h_memo_list) (void)hipHostFree(e->h_memo_list);
+    e->h_memo_list = nullptr; e->h_memo_list_cap = 0;
+    E_HIP(hipHostMalloc((void**)&e->h_memo_list, want + want / 4));
+    e->h_memo_list_cap = want + want / 4;
+  }
+  return 0;
+}
+
+// One step of czc_generate_rows with the rows memo on; sched / d_sched: the call's schedule ([n_steps][R] columns, then
+// [n_steps][R] '.' rules, n_pos = n_steps * R) on the host and on the device.  First step of a group in which some row
+// revisits a key: the check kernels and one read (totals and the ascending active list) give the active rows; then all of
+// them run as without the option (and record), none runs, or the step runs on a compact batch whose column / '.' arrays the
+// gather kernel builds.  The compact columns' host copy keeps the per-row n_mask = 0 re-use rule of mlm_head in force.
+int memo_rows_step(czc_engine* e, MemoRowsPlan& mp, int s, int* d_inp, int R, int T, int L, int seed_len, int n_mask, int n_mask0,
+                   int K, const czc_hyper* hp, const int32_t* sched, const int* d_sched, size_t n_pos) {
+  const int s0 = mp.first[s], j = mp.sub[s], g = mp.group_len[s0], mask_id = e->cfg.mask_id, D = e->cfg.clip_proj;
+  const int record = mp.record[s0];
+  const int* col0 = d_sched + (size_t)s0 * R;
+  const int* col1 = g > 1 ? d_sched + (size_t)(s0 + 1) * R : nullptr;
+  const int* col = d_sched + (size_t)s * R;
+  const int* dot = d_sched + n_pos + (size_t)s * R;
+  if (j == 0) {
+    mp.n_act = R;
+    mp.branch_max[0] = mp.branch_max[1] = 0;
+    if (mp.check[s]) {
+      E_CHECK(launch_memo_rows_check(d_inp, mp.tab, col0, col1, n_mask0, g, mask_id, mp.hit, mp.cnt, mp.list, mp.tot, e->st));
+      int32_t* h = e->h_memo_list;
+      E_HIP(hipMemcpyAsync(h, mp.tot, 16, hipMemcpyDeviceToHost, e->st));
+      E_HIP(hipMemcpyAsync(h + 4, mp.list, (size_t)R * 4, hipMemcpyDeviceToHost, e->st));
+      E_HIP(hipStreamSynchronize(e->st));
+      mp.n_act = h[0];
+      mp.branch_max[0] = h[1]; mp.branch_max[1] = h[2];
+      if (mp.n_act < 0 || mp.n_act > R) return fail(e, CZC_ERR_STATE, "memo_rows check returned an impossible count%s");
+      // CZC_PREC_SPLIT: a compact batch moves its cosines in the last bits (memo_step), so a step runs whole unless every row hits
+      if (e->pc == PREC_F16X3 && mp.n_act > 0) mp.n_act = R;
+      if (mp.n_act > 0 && mp.n_act < R) {
+        for (int jj = 0; jj < g; ++jj) mp.h_col_c[jj].resize(mp.n_act);
+        for (int i = 0; i < mp.n_act; ++i) {
+          const int r = h[4 + i];
+          if (r < 0 || r >= R || (i > 0 && r <= h[4 + i - 1])) return fail(e, CZC_ERR_STATE, "memo_rows check returned an impossible list%s");
+          for (int jj = 0; jj < g; ++jj) mp.h_col_c[jj][i] = sched[(size_t)(s0 + jj) * R + r];
+        }
+      }
+    }
+  }
+  const int n_act = mp.n_act;
+  e->stat_memo_row_steps += R;
+  e->stat_memo_row_hits += R - n_act;
+  if (n_act < R) E_CHECK(launch_memo_rows_fill(mp.hit, mp.tab, col0, j, d_inp, mp.bcos, e->st));
+  if (n_act == 0) return 0;
+  if (n_act == R) {  // every row, in place, as without the option; then the entries are recorded
+    const int32_t* col_h = sched + (size_t)s * R;
+    if (record && j == 0)
+      E_CHECK(launch_memo_rows_gather(d_inp, nullptr, R, mp.tab, col0, col1, n_mask0, g, mask_id, 1, col, dot, nullptr, nullptr, D,
+                                      nullptr, nullptr, nullptr, e->st));
+    E_CHECK(step_device(e, d_inp, R, T, col_h[0], n_mask, col_h[0] - seed_len == L - 1 ? 1 : 0, K, hp, col, dot, col_h));
+    return launch_memo_rows_scatter(d_inp, (const float*)e->ws["s_bcos"].p, (const int*)e->ws["p_img_max"].p, nullptr, R, mp.tab,
+                                    col0, j, record, d_inp, mp.bcos, e->st) ? fail(e, CZC_ERR_HIP, "%s", g_err) : 0;
+  }
+  // compact batch: rows, row-gathered image embeds, columns and '.' rules of the active rows, the step on them, then their
+  // rows and cosines back into the batch and into their own slots
+  E_CHECK(launch_memo_rows_gather(d_inp, mp.list, n_act, mp.tab, col0, col1, n_mask0, g, mask_id, record && j == 0 ? 1 : 0, col, dot,
+                                  mp.inp_c, e->d_img_n, D, mp.img_c, mp.col_c, mp.dot_c, e->st));
+  const int32_t* col_h = mp.h_col_c[j].data();
+  float* img_rows = e->d_img_n;
+  const int img_B = e->img_B;
+  e->d_img_n = mp.img_c; e->img_B = n_act; e->memo_branch_floor = mp.branch_max[j];
+  const int rc = step_device(e, mp.inp_c, n_act, T, col_h[0], n_mask, col_h[0] - seed_len == L - 1 ? 1 : 0, K, hp, mp.col_c, mp.dot_c,
+                             col_h);
+  e->d_img_n = img_rows; e->img_B = img_B; e->memo_branch_floor = 0;
+  E_CHECK(rc);
+  return launch_memo_rows_scatter(mp.inp_c, (const float*)e->ws["s_bcos"].p, (const int*)e->ws["p_img_max"].p, mp.list, n_act,
+                                  mp.tab, col0, j, record, d_inp, mp.bcos, e->st) ? fail(e, CZC_ERR_HIP, "%s", g_err) : 0;
+}
+
 }  // namespace
 
 // =================================================================================================
@@ -1131,6 +1282,7 @@ int czc_destroy(czc_engine* e) {
   if (e->prof_ref) (void)hipEventDestroy(e->prof_ref);
   if (e->h_totals) (void)hipHostFree(e->h_totals);
   if (e->h_ctl_ids) (void)hipHostFree(e->h_ctl_ids);
+  if (e->h_memo_list) (void)hipHostFree(e->h_memo_list);
   (void)hipStreamDestroy(e->st);
   delete e;
   return CZC_OK;
@@ -1149,7 +1301,7 @@ int czc_replicate(czc_engine* p, czc_engine** out) {
   e->refine = p->refine; e->refine_theta_x = p->refine_theta_x; e->refine_samples = p->refine_samples; e->refine_samples_step = p->refine_samples_step;
   e->refine_guard_dev = p->refine_guard_dev; e->refine_gate_delta = p->refine_gate_delta; e->refine_theta_gen = p->refine_theta_gen;
   e->refine_rows16 = p->refine_rows16; e->refine_rows16_factor = p->refine_rows16_factor;
-  e->memo = p->memo;
+  e->memo = p->memo; e->memo_rows = p->memo_rows;
   e->w = p->w; e->bert = p->bert; e->ctext = p->ctext; e->cvis = p->cvis; e->ctext_x = p->ctext_x;
   e->mlm_dense_w = p->mlm_dense_w; e->decoder_w = p->decoder_w; e->tproj_w = p->tproj_w; e->vproj_w = p->vproj_w;
   e->patch_w = p->patch_w; e->tproj_wx = p->tproj_wx;
@@ -1647,9 +1799,13 @@ static int generate_impl(czc_engine* e, bool rows, int B, int T, int L, int seed
       audited = audited || audit[s];
     } }
   MemoPlan mp;
-  const bool memo = e->memo && !rows;  // the memo's keys are (image, position, n_mask): a rows call runs every step whole
+  const bool memo = e->memo && !rows;  // the memo's keys are (image, position, n_mask); a rows call has option "memo_rows"
   if (memo) E_CHECK(memo_begin(e, B, T, n_steps, positions_host, n_mask_host, snapshot_every, out_cos != nullptr, audit, &mp));
   int snap = 0, rc = 0;
+  MemoRowsPlan mrp;
+  const bool memo_rows = rows && e->memo_rows && n_steps > 0;
+  // (a failure here leaves through the exit below, which hands the resident image batch back)
+  if (memo_rows) rc = memo_rows_begin(e, B, T, L, seed_len, n_steps, positions_host, n_mask_host, snapshot_every, out_cos != nullptr, audit, &mrp);
   for (int s = 0; s < n_steps && !rc; ++s) {
     const int pos = positions_host[rows ? (size_t)s * B : (size_t)s];
     const int nm = n_mask_host ? n_mask_host[s] : 1;
@@ -1657,7 +1813,9 @@ static int generate_impl(czc_engine* e, bool rows, int B, int T, int L, int seed
     e->gate_now = e->refine && e->refine_gate_delta > 0.f && e->refine_guard_dev > 0.f && !audit[s];
     e->gate_need_cos = snap_idx && out_cos != nullptr;
     e->in_generate = true;
-    if (rows) rc = step_device(e, d_inp, B, T, seed_len + pos, nm, pos == L - 1 ? 1 : 0, top_k, hp, d_sched + (size_t)s * B,
+    if (memo_rows) rc = memo_rows_step(e, mrp, s, d_inp, B, T, L, seed_len, nm, n_mask_host ? n_mask_host[mrp.first[s]] : 1, top_k, hp,
+                                       sched.data(), d_sched, n_pos);
+    else if (rows) rc = step_device(e, d_inp, B, T, seed_len + pos, nm, pos == L - 1 ? 1 : 0, top_k, hp, d_sched + (size_t)s * B,
                                d_sched + n_pos + (size_t)s * B, sched.data() + (size_t)s * B);
     else if (memo) rc = memo_step(e, mp, s, d_inp, B, T, seed_len + pos, nm, pos == L - 1 ? 1 : 0, top_k, hp);
     else rc = step_device(e, d_inp, B, T, seed_len + pos, nm, pos == L - 1 ? 1 : 0, top_k, hp);
@@ -1667,7 +1825,8 @@ static int generate_impl(czc_engine* e, bool rows, int B, int T, int L, int seed
       if (out_ids)
         h = hipMemcpyAsync(out_ids + (size_t)snap * B * T, d_inp, (size_t)B * T * 4, hipMemcpyDefault, e->st);
       if (out_cos && h == hipSuccess)  // memo: the full-batch cosines (a compacted step leaves B_act of them in s_bcos)
-        h = hipMemcpyAsync(out_cos + (size_t)snap * B, memo ? mp.bcos : e->ws["s_bcos"].p, (size_t)B * 4, hipMemcpyDefault, e->st);
+        h = hipMemcpyAsync(out_cos + (size_t)snap * B, memo ? mp.bcos : memo_rows ? mrp.bcos : e->ws["s_bcos"].p, (size_t)B * 4,
+                           hipMemcpyDefault, e->st);
       if (h != hipSuccess) { snprintf(e->err, sizeof(e->err), "generate: snapshot copy -> %s", hipGetErrorString(h)); rc = CZC_ERR_HIP; }
       ++snap;
     }
@@ -1729,6 +1888,7 @@ int czc_set_option(czc_engine* e, const char* name, int value) {
   if (!strcmp(name, "refine_gate_x1e6")) { e->refine_gate_delta = value < 0 ? 0.f : (float)value * 1e-6f; return CZC_OK; }
   if (!strcmp(name, "refine_rows16")) { const int old = e->refine_rows16; e->refine_rows16 = value ? 1 : 0; const int rc = fold_ready(); if (rc) e->refine_rows16 = old; return rc; }
   if (!strcmp(name, "memo")) { e->memo = value ? 1 : 0; return CZC_OK; }
+  if (!strcmp(name, "memo_rows")) { e->memo_rows = value ? 1 : 0; return CZC_OK; }
   if (!strcmp(name, "refine_rows16_x1000")) { e->refine_rows16_factor = value < 1000 ? 1.f : (float)value / 1000.f; return CZC_OK; }
   return fail(e, CZC_ERR_ARG, "unknown option %s", name);
 }
@@ -1743,7 +1903,7 @@ int czc_get_option(czc_engine* e, const char* name, int* value) {
       {"refine_samples", e->refine_samples}, {"refine_samples_step", e->refine_samples_step}, {"refine_theta_x1000", (int)lrintf(e->refine_theta_x * 1000.f)},
       {"refine_theta_gen_x1000", (int)lrintf(e->refine_theta_gen * 1000.f)},
       {"refine_guard_x1e6", (int)lrintf(e->refine_guard_dev * 1e6f)}, {"refine_gate_x1e6", (int)lrintf(e->refine_gate_delta * 1e6f)},
-      {"refine_rows16", e->refine_rows16}, {"memo", e->memo}, {"refine_rows16_x1000", (int)lrintf(e->refine_rows16_factor * 1000.f)},
+      {"refine_rows16", e->refine_rows16}, {"memo", e->memo}, {"memo_rows", e->memo_rows}, {"refine_rows16_x1000", (int)lrintf(e->refine_rows16_factor * 1000.f)},
       // read-only, derived: the trip point / gate bound in force inside czc_generate (x refine_rows16_factor on fp16 rows)
       {"refine_guard_generate_x1e6", (int)lrintf(e->refine_guard_dev * f16x * 1e6f)},
       {"refine_gate_generate_x1e6", (int)lrintf(e->refine_gate_delta * f16x * 1e6f)},
@@ -1778,6 +1938,7 @@ int czc_profile_reset(czc_engine* e) {
   e->stat_dedup_seqs = 0;
   e->stat_gated = e->stat_gate_images = 0;
   e->stat_memo_hits = e->stat_memo_images = 0;
+  e->stat_memo_row_hits = e->stat_memo_row_steps = 0;
   return CZC_OK;
 }
 
@@ -1865,6 +2026,13 @@ int czc_memo_stats(czc_engine* e, int64_t* hit_image_steps, int64_t* image_steps
   if (!e) return CZC_ERR_ARG;
   if (hit_image_steps) *hit_image_steps = e->stat_memo_hits;
   if (image_steps) *image_steps = e->stat_memo_images;
+  return CZC_OK;
+}
+
+int czc_memo_rows_stats(czc_engine* e, int64_t* hit_row_steps, int64_t* row_steps) {
+  if (!e) return CZC_ERR_ARG;
+  if (hit_row_steps) *hit_row_steps = e->stat_memo_row_hits;
+  if (row_steps) *row_steps = e->stat_memo_row_steps;
   return CZC_OK;
 }
 

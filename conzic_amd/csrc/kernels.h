@@ -142,6 +142,33 @@ int launch_memo_scatter(const int* rows, const float* bcos, const int* img_max, 
 int launch_memo_fill(const int* hit, int B, int T, const int* out_rows, const float* out_cos, int* inp, float* bcos_full,
                      hipStream_t st);
 
+// ---- memo_rows.hip (czc_generate_rows option "memo_rows") -----------------------------------------------------------
+// The entries of one call: slot (p, r) = first position p of a step group (column - seed_len) x row r, L x R slots.
+constexpr int MEMO_ROWS_SUB = 2;  // steps per group a slot has room for
+struct MemoRowsTab {
+  int* valid; int* sig;          // [L][R]: 1 once recorded in this call / the group shape it was recorded under
+  int* key;                      // [L][R][T] masked row of the last visit
+  int* rows; float* cos; int* imax;  // [L][MEMO_ROWS_SUB][R] x ([T] | 1 | 1): what each sub-step left
+  int R, T, L, seed_len;
+};
+// col0 / col1 (device, [R]): every row's column at the group's first / second step (col1 null for a one-step group).
+// check: hit[r] = slot (col0[r] - seed_len, r) is valid, has this group's signature and its key row equals the masked row r;
+// list = the other rows in ascending order; tot[0] = their count, tot[1 + j] = max over the hit rows of the slot's imax at
+// sub-step j (j < n_sub <= MEMO_ROWS_SUB); cnt: scratch, (R + 255) / 256 ints
+int launch_memo_rows_check(const int* inp, const MemoRowsTab& m, const int* col0, const int* col1, int n_mask0, int n_sub,
+                           int mask_id, int* hit, int* cnt, int* list, int* tot, hipStream_t st);
+// for i < n, r = list ? list[i] : i: (record) key of r's slot = masked row r, valid, signature; (inp_c) inp_c[i] = row r,
+// img_c[i] = img_n[r], col_c[i] = col[r], dot_c[i] = dot[r] (col / dot: this step's schedule slice)
+int launch_memo_rows_gather(const int* inp, const int* list, int n, const MemoRowsTab& m, const int* col0, const int* col1,
+                            int n_mask0, int n_sub, int mask_id, int record, const int* col, const int* dot, int* inp_c,
+                            const float* img_n, int D, float* img_c, int* col_c, int* dot_c, hipStream_t st);
+// for i < n, r = list ? list[i] : i: (list) inp[r] = rows[i]; bcos_full[r] = bcos[i]; (record) sub-step j of r's slot =
+// rows[i], bcos[i], img_max[i]
+int launch_memo_rows_scatter(const int* rows, const float* bcos, const int* img_max, const int* list, int n, const MemoRowsTab& m,
+                             const int* col0, int j, int record, int* inp, float* bcos_full, hipStream_t st);
+// rows with hit[r]: inp[r], bcos_full[r] = sub-step j of r's slot
+int launch_memo_rows_fill(const int* hit, const MemoRowsTab& m, const int* col0, int j, int* inp, float* bcos_full, hipStream_t st);
+
 // ---- attention.hip ------------------------------------------------------------------------
 // Segment s = `own_len[s]` rows starting at own_off[s] (queries and keys/values) preceded by
 // `pre_len[s]` key/value-only rows starting at pre_off[s] (the shared causal prefix of an image's

@@ -430,6 +430,13 @@ class Engine:
         self._ck(self.lib.czc_memo_stats(self.h, C.byref(h), C.byref(n)), "czc_memo_stats")
         return dict(hit_image_steps=h.value, image_steps=n.value)
 
+    def memo_rows_stats(self):
+        """Option "memo_rows" (czc_memo_rows_stats): row-steps of czc_generate_rows calls made with the option on since
+        profile_reset, and how many of them took their entry instead of running."""
+        h, n = C.c_int64(), C.c_int64()
+        self._ck(self.lib.czc_memo_rows_stats(self.h, C.byref(h), C.byref(n)), "czc_memo_rows_stats")
+        return dict(hit_row_steps=h.value, row_steps=n.value)
+
     def refine_guard(self, reset: bool = True):
         """(max |screening error - mean| seen on re-encoded candidates, image-steps above the trip point) of a
         CZC_PREC_REFINE engine since the last reset (czc_refine_guard)."""
@@ -584,6 +591,10 @@ class EngineGroup:
 
     def memo_stats(self):
         ms = [e.memo_stats() for e in self.engines]
+        return {k: sum(m[k] for m in ms) for k in ms[0]}
+
+    def memo_rows_stats(self):
+        ms = [e.memo_rows_stats() for e in self.engines]
         return {k: sum(m[k] for m in ms) for k in ms[0]}
 
     def refine_guard(self, reset: bool = True):

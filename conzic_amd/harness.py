@@ -229,6 +229,41 @@ def memo_expected_hits(snapshots, positions, n_mask, seed_len: int, mask_id: int
     return hits
 
 
+def memo_expected_hits_rows(snapshots, positions, n_mask, seed_len: int, mask_id: int, never=None) -> np.ndarray:
+    """The rows memo's rule (option "memo_rows" of czc_generate_rows) stated on the host.  `snapshots` int32 [n_steps, R, T]: an
+    option-OFF trajectory recorded with snapshot_every = 1; `positions` int [n_steps, R]: row r visits positions[s][r] at step
+    s.  Returns bool [n_steps, R]: whether row r hits at step s (czc_memo_rows_stats counts their sum).
+
+    The step groups are those of memo_expected_hits (n_mask is one value per step for all rows).  Row r's key at a group is
+    (its position at every step of the group, the group's n_mask list); its entry sits in the slot (r, first position of the
+    group), so a visit of that first position under another key replaces it.  Row r hits when its slot holds the same key
+    and the masked row it held then equals the one it holds now.  A group with more than MEMO_SUB steps or one that does not
+    start with n_mask >= 1 neither hits nor records; a group with a step in `never` (bool [n_steps]) records and does not
+    hit.  With the reference's orders a first position always comes with the same key, and the rule is memo_expected_hits
+    applied to every row with its own order."""
+    snaps = np.asarray(snapshots)
+    n_steps, R, T = snaps.shape
+    pos = np.asarray(positions).reshape(n_steps, R)
+    nm = [1] * n_steps if n_mask is None else [int(x) for x in n_mask]
+    never = np.zeros(n_steps, bool) if never is None else np.asarray(never, bool)
+    hits = np.zeros((n_steps, R), bool)
+    slots = [dict() for _ in range(R)]   # per row: first position -> (key, masked row)
+    for s, g in memo_groups(nm, n_steps):
+        if nm[s] < 1 or nm[s] > T or g > MEMO_SUB:
+            continue
+        hittable = not never[s:s + g].any()
+        for r in range(R):
+            key = tuple((int(pos[s + j, r]), nm[s + j]) for j in range(g))
+            row = snaps[s, r].copy()   # the row the step left, masked again, is the row it saw
+            c0 = seed_len + int(pos[s, r])
+            row[c0:min(c0 + nm[s], T)] = mask_id
+            prev = slots[r].get(key[0][0])
+            if hittable and prev is not None and prev[0] == key and np.array_equal(prev[1], row):
+                hits[s:s + g, r] = True
+            slots[r][key[0][0]] = (key, row)
+    return hits
+
+
 def converging_setup(B: int = 16, L: int = 6, precision: int = native.PREC_BF16, n_hot: int = 150, seed: int = 0,
                      alpha: float = 0.02, beta: float = 2.0, logit_scale: float = 4.6052, flat_top: int = 8):
     """Full-size towers with a trained-like MLM head (`n_hot` regular tokens 5.6..16 logit units above a bulk that softmax(logits /

@@ -122,6 +122,7 @@ SIGNATURES = {
     "czc_refine_guard": (_I, [_P, _I, C.POINTER(C.c_float), C.POINTER(C.c_int64)]),
     "czc_refine_gate_stats": (_I, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "czc_memo_stats": (_I, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "czc_memo_rows_stats": (_I, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 }
 # exported, but not part of the boundary and not in the public header: the hook library's door into this one (declared in
 # csrc/kernels.h; nothing in conzic_amd/ calls it)

@@ -235,6 +235,18 @@ def memo_setting() -> int:
     raise ValueError(f"CZC_MEMO={v!r}: expected 0 or 1")
 
 
+def memo_rows_setting() -> int:
+    """CZC_MEMO_ROWS=0|1 (default 0): engine option "memo_rows" of the batched sample call (run_generation_samples) --
+    czc_generate_rows runs a step only for the rows whose masked row differs from their last visit of the same position in
+    the call (the rule of CZC_MEMO keyed per row; include/conzic_hip.h)."""
+    v = os.environ.get("CZC_MEMO_ROWS", "0").strip().lower()
+    if v in ("0", "", "off", "false", "no"):
+        return 0
+    if v in ("1", "on", "true", "yes"):
+        return 1
+    raise ValueError(f"CZC_MEMO_ROWS={v!r}: expected 0 or 1")
+
+
 def _polish_guarded(polish, eng, model, clip, tokenizer, image_instance, logger):
     """`polish(engine) -> ((ids, cos), runner)` with what every generation call does around it: the overflow retry on fp32 rows
     and the screen-then-refine guard's rerun on the all-split engine."""
@@ -405,7 +417,8 @@ def run_generation_samples(order: str, samples_num: int, img_name, model, clip, 
 
     def polish(eng):
         eng.set_token_mask(_mask_to_numpy(token_mask))
-        eng.set_option("memo", memo_setting())  # a rows call runs every step whole (include/conzic_hip.h)
+        eng.set_option("memo", memo_setting())  # for the one-call-per-sample arm below; a rows call ignores it
+        eng.set_option("memo_rows", memo_rows_setting())  # per-row step memo of the rows call (CZC_MEMO_ROWS)
         chosen = None
         if gamma is not None:
             from . import control

@@ -277,8 +277,9 @@ int czc_generate(czc_engine* e, int B, int T, int L, int seed_len, const int32_t
  *     czc_generate); otherwise CZC_ERR_ARG.
  *     The way out: the control tables (czc_set_lexicon / czc_set_lexicon_pos / czc_set_pos), which work with differing
  *     positions, or one czc_generate call per order.
- *   - option "memo": its keys are (image, position, n_mask) per step group, which a rows call does not have; a rows call runs
- *     every step whole and czc_memo_stats counts nothing for it. */
+ *   - option "memo": its keys are (image, position, n_mask) per step group, which a rows call does not have; a rows call
+ *     ignores it and czc_memo_stats counts nothing for it.  The rows call has the same rule keyed per row under an option of
+ *     its own, "memo_rows" (below; czc_memo_rows_stats), off by default: with it off a rows call runs every step whole. */
 int czc_generate_rows(czc_engine* e, int R, int T, int L, int seed_len, const int32_t* init_ids_host,
                       const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
                       const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp, int32_t* out_ids, float* out_cos);
@@ -343,7 +344,28 @@ int czc_generate_rows(czc_engine* e, int R, int T, int L, int seed_len, const in
  *                         polices.  A control callback (czc_set_control_callback) is called for the images that run only: B is
  *                         the active count and the rows are compacted, so it must be a pure function of its rows (the
  *                         reference scorer is).  Replicas (czc_replicate) inherit the option and keep memos of their own.
- *                         czc_memo_stats counts the hits; czc_stats / czc_refine_gate_stats keep counting what ran */
+ *                         czc_memo_stats counts the hits; czc_stats / czc_refine_gate_stats keep counting what ran
+ *   "memo_rows"       (0) czc_generate_rows only (czc_generate ignores it; independent of "memo", which a rows call ignores):
+ *                         the rule of "memo" keyed per ROW.  n_mask is one value per step for all rows, so the step groups (one
+ *                         n_mask >= 1 step plus the n_mask = 0 steps behind it) are shared; the positions are row r's own.  Row
+ *                         r's key at a group: its position at every step of the group and the group's n_mask list.  Its entry
+ *                         sits in slot (r, first position of the group) -- at most L slots per row -- under a signature word
+ *                         (n_mask, group length, column of the second step) and a valid word cleared at the start of the call: a
+ *                         first visit, or a visit of the same first position under another group shape, is a miss, and every
+ *                         visit replaces the entry.  A row whose masked row R(r) equals its entry (whole row, no hashing) hits:
+ *                         it does not run and takes the stored row(s) and cosine(s) back.  A group longer than two steps, or one
+ *                         that does not start with n_mask >= 1, never hits.  The host knows the schedule: a step at which no row
+ *                         revisits a key (the whole first sweep) runs without a check; otherwise a check (one thread per row,
+ *                         R / 256 work-groups) and one read of the active count and the ascending active list, then the step runs
+ *                         on all rows, on none, or on a compact batch of the active rows with their own columns and '.' rules.
+ *                         The n_mask = 0 re-use rule of czc_step keeps holding per row on a compact batch.  What a compact
+ *                         batch keeps, CZC_PREC_SPLIT (a step is skipped only when every row hits) and CZC_PREC_REFINE (audit
+ *                         steps and steps whose cosine the call returns never hit) are as for "memo".  A control callback is
+ *                         called for the rows that run, compacted (a rows call accepts one only when all rows share a position
+ *                         per step).  Entry storage of a call: L x R x T x 12 bytes + L x R x 24 bytes on the device, i.e.
+ *                         8 MB + 1 MB at R = 4096, L = 10, T = 16 and, at its largest (R = CZC_MAX_ROWS, L = 62, T = 64), 780 MB + 24 MB,
+ *                         kept in the engine's workspace.  Replicas inherit the option and keep entries of their own.
+ *                         czc_memo_rows_stats counts the hits */
 int czc_set_option(czc_engine* e, const char* name, int value);
 /* Reads an option back (same names and units as czc_set_option), plus three read-only derived values:
  *   "refine_guard_generate_x1e6" / "refine_gate_generate_x1e6": the guard's trip point / the margin gate's bound in force inside
@@ -400,6 +422,10 @@ int czc_refine_guard(czc_engine* e, int reset, float* max_dev, int64_t* tripped)
  * which *hit_image_steps took a memo entry instead of running (CZC_PREC_SPLIT: only steps on which every image hits).  Zero with
  * the option off. */
 int czc_memo_stats(czc_engine* e, int64_t* hit_image_steps, int64_t* image_steps);
+/* Option "memo_rows": row-steps of czc_generate_rows calls made with the option on since czc_profile_reset (*row_steps, R per
+ * step), of which *hit_row_steps took their entry instead of running (CZC_PREC_SPLIT: only steps on which every row hits).
+ * Zero with the option off; czc_memo_stats stays zero for rows calls. */
+int czc_memo_rows_stats(czc_engine* e, int64_t* hit_row_steps, int64_t* row_steps);
 /* CZC_PREC_REFINE engines, margin gate of czc_generate: a whole *_generation call returns the winner's id of every step and
  * the winner's cosine at the snapshot steps (gen_utils.py:78-81, :92), not the K fused scores.  An image-step whose screening
  * (single-pass fp16) winner stays the winner under EVERY assignment of cosine errors |d_k - common| <= delta (delta = option

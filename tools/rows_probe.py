@@ -6,7 +6,15 @@ the precision the runtime picks for the logit scale (2.6592 -> bf16, 4.6052 -> s
     python tools/rows_probe.py [--S 1 2 4 8 16] [--reps 3] [--out profiles/r08_rows_probe.json]
 
 Per (logit scale, S): wall time of both arms, warm (one untimed call of each first), --reps repetitions alternating
-serial / rows, whether the ids of every sweep agree row for row, and the ratios.  The JSON file holds one object per case."""
+serial / rows, whether the ids of every sweep agree row for row, and the ratios.  The JSON file holds one object per case.
+
+    python tools/rows_probe.py --memo_rows [--S 4 16] [--reps 5] [--off_only] [--out profiles/r09_memo_rows_probe.json]
+
+The rows call with the per-row step memo (option "memo_rows") off and on, on the converging set-up (harness.converging_setup:
+a trained-like MLM head, rows settle after a few sweeps), one image x S rows, bf16 and screen-then-refine engines.  Per (engine,
+S): wall times of --reps alternating off / on calls after one warm-up of each, their spread ((max - min) / median), the hit
+fraction (czc_memo_rows_stats) and whether ids and cosines agree.  --off_only never touches the option: the option-off arm
+alone, e.g. on a library built from another commit (CZC_LIB_PATH) for an A/B of the unchanged path."""
 import argparse
 import json
 import os
@@ -28,12 +36,63 @@ ap.add_argument("--K", type=int, default=200)
 ap.add_argument("--sweeps", type=int, default=10)
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--scales", type=float, nargs="+", default=[2.6592, 4.6052])
-ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r08_rows_probe.json"))
+ap.add_argument("--out", default=None)
+ap.add_argument("--memo_rows", action="store_true", help="the memo_rows leg instead of the serial / rows comparison")
+ap.add_argument("--off_only", action="store_true", help="--memo_rows: time the option-off arm only and leave the option alone")
 args = ap.parse_args()
+if args.out is None:
+    args.out = os.path.join(ROOT, "profiles", "r09_memo_rows_probe.json" if args.memo_rows else "r08_rows_probe.json")
 
 L, K, SEED_LEN = args.L, args.K, 4
 out = []
-for scale in args.scales:
+
+
+def spread(ts):
+    return (max(ts) - min(ts)) / float(np.median(ts))
+
+
+def memo_rows_leg():
+    from conzic_amd import native
+    for prec in (native.PREC_BF16, native.PREC_REFINE):
+        su, _, hp, init, seed_len = harness.converging_setup(B=1, L=L, precision=prec)
+        eng = su.engine
+        for S in (args.S if args.S != [1, 2, 4, 8, 16] else [4, 16]):
+            random.seed(42)
+            positions, n_mask, every, _ = harness.sample_schedules("shuffle", L, args.sweeps, S)
+            arms = (0,) if args.off_only else (0, 1)
+
+            def call(on):
+                if not args.off_only:
+                    eng.set_option("memo_rows", on)
+                eng.profile_reset()
+                res = eng.generate_rows(init, L, seed_len, K, positions, hp, image_of_row=[0] * S, n_mask=n_mask, snapshot_every=every)
+                return res, (None if args.off_only else eng.memo_rows_stats())
+
+            warm = {on: call(on) for on in arms}
+            times = {on: [] for on in arms}
+            for _ in range(args.reps):
+                for on in arms:
+                    eng.sync()
+                    t0 = time.perf_counter()
+                    call(on)
+                    times[on].append(time.perf_counter() - t0)
+            rec = dict(precision=runtime.PRECISION_NAMES[prec], S=S, L=L, K=K, sweeps=args.sweeps, order="shuffle", images=1,
+                       wall_s_off=times[0], wall_s_off_median=float(np.median(times[0])), spread_off=spread(times[0]))
+            if not args.off_only:
+                ms = warm[1][1]
+                rec.update(wall_s_on=times[1], wall_s_on_median=float(np.median(times[1])), spread_on=spread(times[1]),
+                           speedup_median=float(np.median(times[0]) / np.median(times[1])),
+                           hit_fraction=ms["hit_row_steps"] / max(ms["row_steps"], 1),
+                           ids_identical=bool(np.array_equal(warm[0][0][0], warm[1][0][0])),
+                           cos_max_abs_diff=float(np.abs(warm[0][0][1] - warm[1][0][1]).max()))
+            print(json.dumps(rec), flush=True)
+            out.append(rec)
+        eng.close()
+
+
+if args.memo_rows:
+    memo_rows_leg()
+for scale in ([] if args.memo_rows else args.scales):
     prec = runtime.choose_precision(scale)
     su = harness.build_synthetic(False, prec, logit_scale=scale, regular_only=True)
     eng = su.engine

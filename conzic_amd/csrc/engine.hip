@@ -1071,27 +1071,34 @@ struct MemoRowsPlan {
   MemoRowsTab tab{};
   int *hit = nullptr, *cnt = nullptr, *list = nullptr, *tot = nullptr, *inp_c = nullptr, *col_c = nullptr, *dot_c = nullptr;
   float *bcos = nullptr, *img_c = nullptr;
-  std::vector<int32_t> h_col_c[MEMO_ROWS_SUB];  // compact batch of the group in progress: the active rows' column at every step
-  int n_act = 0;  // of the group in progress
+  std::vector<std::vector<int32_t>> h_col_c;  // compact batch of the group in progress: the active rows' column at every step
+  std::vector<int32_t> run_h;    // of the group in progress: the rows that run, ascending (host copy of list_d)
+  const int* list_d = nullptr;   // of the group in progress: the device list of the rows that run (null: every row)
+  bool table = false;            // the entries exist (option "memo_rows"); false: the plan only compacts idle rows away
+  int n_run = 0;  // of the group in progress: rows that are not idle
+  int n_act = 0;  // of the group in progress: rows that run (not idle and no hit)
   int branch_max[MEMO_ROWS_SUB] = {0, 0};
 };
 
 // the signature word of memo_rows.hip (mr_sig) as the host keeps it to tell whether a step can hit at all
 static inline int memo_rows_sig(int n_mask0, int n_sub, int col1) { return (n_mask0 & 0xff) | (n_sub << 8) | ((n_sub > 1 ? col1 + 1 : 0) << 16); }
 
-int memo_rows_begin(czc_engine* e, int R, int T, int L, int seed_len, int n_steps, const int32_t* positions, const int32_t* n_mask,
-                    int snapshot_every, bool want_cos, const std::vector<char>& audit, MemoRowsPlan* mp) {
+// table = false (czc_generate_rows_from with idle steps, option off): no entries, nothing is recorded or checked; the plan
+// then only carries the compact-batch buffers and the full-batch cosines.  Idle rows (position CZC_POS_IDLE) visit no key.
+int memo_rows_begin(czc_engine* e, bool table, int R, int T, int L, int seed_len, int n_steps, const int32_t* positions,
+                    const int32_t* n_mask, int snapshot_every, bool want_cos, const std::vector<char>& audit, MemoRowsPlan* mp) {
   static_assert(MEMO_ROWS_SUB == MEMO_SUB, "the rows memo keeps the step memo's group size");
   mp->first.assign(n_steps, 0); mp->sub.assign(n_steps, 0); mp->group_len.assign(n_steps, 0);
   mp->record.assign(n_steps, 0); mp->check.assign(n_steps, 0);
-  std::vector<int> seen((size_t)R * L, -1);  // per slot: the signature it was last recorded under in this call
+  mp->table = table;
+  std::vector<int> seen(table ? (size_t)R * L : 0, -1);  // per slot: the signature it was last recorded under in this call
   for (int s = 0; s < n_steps;) {
     int g = 1;
     while (s + g < n_steps && n_mask && n_mask[s + g] <= 0) ++g;
     const int nm0 = n_mask ? n_mask[s] : 1;
     mp->group_len[s] = g;
     for (int j = 0; j < g; ++j) { mp->first[s + j] = s; mp->sub[s + j] = j; }
-    if (nm0 >= 1 && nm0 <= T && g <= MEMO_ROWS_SUB) {
+    if (table && nm0 >= 1 && nm0 <= T && g <= MEMO_ROWS_SUB) {
       bool hittable = true;  // CZC_PREC_REFINE: the step-level rule of memo_begin
       for (int j = 0; j < g; ++j) {
         const bool cos_out = want_cos && (s + j + 1) % snapshot_every == 0;
@@ -1099,6 +1106,7 @@ int memo_rows_begin(czc_engine* e, int R, int T, int L, int seed_len, int n_step
       }
       bool revisit = false;
       for (int r = 0; r < R; ++r) {
+        if (positions[(size_t)s * R + r] < 0) continue;  // idle: not a visit
         const int sig = memo_rows_sig(nm0, g, g > 1 ? seed_len + positions[(size_t)(s + 1) * R + r] : 0);
         int& was = seen[(size_t)r * L + positions[(size_t)s * R + r]];
         revisit = revisit || was == sig;
@@ -1112,21 +1120,24 @@ int memo_rows_begin(czc_engine* e, int R, int T, int L, int seed_len, int n_step
   MemoRowsTab& m = mp->tab;
   m.R = R; m.T = T; m.L = L; m.seed_len = seed_len;
   const size_t n_slot = (size_t)L * R, D = (size_t)e->cfg.clip_proj;
-  E_CHECK(ensure(e, "mr_valid", n_slot * 4, (void**)&m.valid));
-  E_CHECK(ensure(e, "mr_sig", n_slot * 4, (void**)&m.sig));
-  E_CHECK(ensure(e, "mr_key", n_slot * T * 4, (void**)&m.key));
-  E_CHECK(ensure(e, "mr_rows", n_slot * MEMO_ROWS_SUB * T * 4, (void**)&m.rows));
-  E_CHECK(ensure(e, "mr_cos", n_slot * MEMO_ROWS_SUB * 4, (void**)&m.cos));
-  E_CHECK(ensure(e, "mr_imax", n_slot * MEMO_ROWS_SUB * 4, (void**)&m.imax));
-  E_CHECK(ensure(e, "mr_hit", (size_t)R * 4, (void**)&mp->hit));
-  E_CHECK(ensure(e, "mr_cnt", (size_t)((R + 255) / 256) * 4, (void**)&mp->cnt));
-  E_CHECK(ensure(e, "mr_list", (size_t)R * 4, (void**)&mp->list));
-  E_CHECK(ensure(e, "mr_tot", 16, (void**)&mp->tot));
+  if (table) {
+    E_CHECK(ensure(e, "mr_valid", n_slot * 4, (void**)&m.valid));
+    E_CHECK(ensure(e, "mr_sig", n_slot * 4, (void**)&m.sig));
+    E_CHECK(ensure(e, "mr_key", n_slot * T * 4, (void**)&m.key));
+    E_CHECK(ensure(e, "mr_rows", n_slot * MEMO_ROWS_SUB * T * 4, (void**)&m.rows));
+    E_CHECK(ensure(e, "mr_cos", n_slot * MEMO_ROWS_SUB * 4, (void**)&m.cos));
+    E_CHECK(ensure(e, "mr_imax", n_slot * MEMO_ROWS_SUB * 4, (void**)&m.imax));
+    E_CHECK(ensure(e, "mr_hit", (size_t)R * 4, (void**)&mp->hit));
+    E_CHECK(ensure(e, "mr_cnt", (size_t)((R + 255) / 256) * 4, (void**)&mp->cnt));
+    E_CHECK(ensure(e, "mr_list", (size_t)R * 4, (void**)&mp->list));
+    E_CHECK(ensure(e, "mr_tot", 16, (void**)&mp->tot));
+  }
   E_CHECK(ensure(e, "mr_bcos", (size_t)R * 4, (void**)&mp->bcos));
   E_CHECK(ensure(e, "mr_inp_c", (size_t)R * T * 4, (void**)&mp->inp_c));
   E_CHECK(ensure(e, "mr_img_c", (size_t)R * D * 4, (void**)&mp->img_c));
   E_CHECK(ensure(e, "mr_col_c", (size_t)R * 4, (void**)&mp->col_c));
   E_CHECK(ensure(e, "mr_dot_c", (size_t)R * 4, (void**)&mp->dot_c));
+  if (!table) return 0;
   E_HIP(hipMemsetAsync(m.valid, 0, n_slot * 4, e->st));  // entries live for one call
   const size_t want = ((size_t)R + 4) * 4;  // the check's totals (16 bytes), then its list
   if (e->h_memo_list_cap < want) {
@@ -1139,8 +1150,12 @@ int memo_rows_begin(czc_engine* e, int R, int T, int L, int seed_len, int n_step
   return 0;
 }
 
-// One step of czc_generate_rows with the rows memo on; sched / d_sched: the call's schedule ([n_steps][R] columns, then
-// [n_steps][R] '.' rules, n_pos = n_steps * R) on the host and on the device.  First step of a group in which some row
+// One step of czc_generate_rows with the rows memo on, and of czc_generate_rows_from wherever a call has idle steps (with the
+// option or without: mp.table); sched / d_sched: the call's schedule ([n_steps][R] columns, CZC_POS_IDLE where a row sits the
+// step out, then [n_steps][R] '.' rules, n_pos = n_steps * R; a call with idle steps: then [n_steps][R] run lists, the rows of
+// every step that are not idle in ascending order) on the host and on the device.  A row is idle for a whole group or for none
+// of it (checked by the caller), so the group's first step decides who runs: the rows that are not idle and, where the check
+// ran, did not hit.  First step of a group in which some row
 // revisits a key: the check kernels and one read (totals and the ascending active list) give the active rows; then all of
 // them run as without the option (and record), none runs, or the step runs on a compact batch whose column / '.' arrays the
 // gather kernel builds.  The compact columns' host copy keeps the per-row n_mask = 0 re-use rule of mlm_head in force.
@@ -1153,7 +1168,11 @@ int memo_rows_step(czc_engine* e, MemoRowsPlan& mp, int s, int* d_inp, int R, in
   const int* col = d_sched + (size_t)s * R;
   const int* dot = d_sched + n_pos + (size_t)s * R;
   if (j == 0) {
-    mp.n_act = R;
+    mp.run_h.clear();
+    for (int r = 0; r < R; ++r)
+      if (sched[(size_t)s0 * R + r] >= 0) mp.run_h.push_back(r);
+    mp.n_run = mp.n_act = (int)mp.run_h.size();
+    mp.list_d = mp.n_run < R ? d_sched + 2 * n_pos + (size_t)s0 * R : nullptr;  // the schedule's own run list of this step
     mp.branch_max[0] = mp.branch_max[1] = 0;
     if (mp.check[s]) {
       E_CHECK(launch_memo_rows_check(d_inp, mp.tab, col0, col1, n_mask0, g, mask_id, mp.hit, mp.cnt, mp.list, mp.tot, e->st));
@@ -1163,24 +1182,36 @@ int memo_rows_step(czc_engine* e, MemoRowsPlan& mp, int s, int* d_inp, int R, in
       E_HIP(hipStreamSynchronize(e->st));
       mp.n_act = h[0];
       mp.branch_max[0] = h[1]; mp.branch_max[1] = h[2];
-      if (mp.n_act < 0 || mp.n_act > R) return fail(e, CZC_ERR_STATE, "memo_rows check returned an impossible count%s");
-      // CZC_PREC_SPLIT: a compact batch moves its cosines in the last bits (memo_step), so a step runs whole unless every row hits
-      if (e->pc == PREC_F16X3 && mp.n_act > 0) mp.n_act = R;
-      if (mp.n_act > 0 && mp.n_act < R) {
-        for (int jj = 0; jj < g; ++jj) mp.h_col_c[jj].resize(mp.n_act);
+      if (mp.n_act < 0 || mp.n_act > mp.n_run) return fail(e, CZC_ERR_STATE, "memo_rows check returned an impossible count%s");
+      // CZC_PREC_SPLIT: a compact batch moves its cosines in the last bits (memo_step), so a step runs whole -- on every row
+      // that is not idle, which is what it runs on with the option off -- unless every such row hits
+      if (e->pc == PREC_F16X3 && mp.n_act > 0) mp.n_act = mp.n_run;
+      else if (mp.n_act > 0 && mp.n_act < R) {
+        mp.list_d = mp.list;
+        mp.run_h.resize(mp.n_act);
         for (int i = 0; i < mp.n_act; ++i) {
           const int r = h[4 + i];
-          if (r < 0 || r >= R || (i > 0 && r <= h[4 + i - 1])) return fail(e, CZC_ERR_STATE, "memo_rows check returned an impossible list%s");
-          for (int jj = 0; jj < g; ++jj) mp.h_col_c[jj][i] = sched[(size_t)(s0 + jj) * R + r];
+          if (r < 0 || r >= R || (i > 0 && r <= h[4 + i - 1]) || sched[(size_t)s0 * R + r] < 0)
+            return fail(e, CZC_ERR_STATE, "memo_rows check returned an impossible list%s");
+          mp.run_h[i] = r;
         }
+      }
+    }
+    if (mp.n_act > 0 && mp.n_act < R) {
+      mp.h_col_c.resize(g);
+      for (int jj = 0; jj < g; ++jj) {
+        mp.h_col_c[jj].resize(mp.n_act);
+        for (int i = 0; i < mp.n_act; ++i) mp.h_col_c[jj][i] = sched[(size_t)(s0 + jj) * R + mp.run_h[i]];
       }
     }
   }
   const int n_act = mp.n_act;
-  e->stat_memo_row_steps += R;
-  e->stat_memo_row_hits += R - n_act;
-  if (n_act < R) E_CHECK(launch_memo_rows_fill(mp.hit, mp.tab, col0, j, d_inp, mp.bcos, e->st));
-  if (n_act == 0) return 0;
+  if (mp.table) {  // an idle row-step is not a visit: neither counted nor a hit
+    e->stat_memo_row_steps += mp.n_run;
+    e->stat_memo_row_hits += mp.n_run - n_act;
+  }
+  if (n_act < mp.n_run) E_CHECK(launch_memo_rows_fill(mp.hit, mp.tab, col0, j, d_inp, mp.bcos, e->st));  // only after a check
+  if (n_act == 0) return 0;  // every row idle or hit: nothing runs
   if (n_act == R) {  // every row, in place, as without the option; then the entries are recorded
     const int32_t* col_h = sched + (size_t)s * R;
     if (record && j == 0)
@@ -1192,17 +1223,17 @@ int memo_rows_step(czc_engine* e, MemoRowsPlan& mp, int s, int* d_inp, int R, in
   }
   // compact batch: rows, row-gathered image embeds, columns and '.' rules of the active rows, the step on them, then their
   // rows and cosines back into the batch and into their own slots
-  E_CHECK(launch_memo_rows_gather(d_inp, mp.list, n_act, mp.tab, col0, col1, n_mask0, g, mask_id, record && j == 0 ? 1 : 0, col, dot,
+  E_CHECK(launch_memo_rows_gather(d_inp, mp.list_d, n_act, mp.tab, col0, col1, n_mask0, g, mask_id, record && j == 0 ? 1 : 0, col, dot,
                                   mp.inp_c, e->d_img_n, D, mp.img_c, mp.col_c, mp.dot_c, e->st));
   const int32_t* col_h = mp.h_col_c[j].data();
   float* img_rows = e->d_img_n;
   const int img_B = e->img_B;
-  e->d_img_n = mp.img_c; e->img_B = n_act; e->memo_branch_floor = mp.branch_max[j];
+  e->d_img_n = mp.img_c; e->img_B = n_act; e->memo_branch_floor = j < MEMO_ROWS_SUB ? mp.branch_max[j] : 0;
   const int rc = step_device(e, mp.inp_c, n_act, T, col_h[0], n_mask, col_h[0] - seed_len == L - 1 ? 1 : 0, K, hp, mp.col_c, mp.dot_c,
                              col_h);
   e->d_img_n = img_rows; e->img_B = img_B; e->memo_branch_floor = 0;
   E_CHECK(rc);
-  return launch_memo_rows_scatter(mp.inp_c, (const float*)e->ws["s_bcos"].p, (const int*)e->ws["p_img_max"].p, mp.list, n_act,
+  return launch_memo_rows_scatter(mp.inp_c, (const float*)e->ws["s_bcos"].p, (const int*)e->ws["p_img_max"].p, mp.list_d, n_act,
                                   mp.tab, col0, j, record, d_inp, mp.bcos, e->st) ? fail(e, CZC_ERR_HIP, "%s", g_err) : 0;
 }
 
@@ -1726,7 +1757,11 @@ int czc_step(czc_engine* e, int32_t* inp, int B, int T, int gen_idx, int n_mask,
 // czc_generate and czc_generate_rows.  rows = false: positions_host [n_steps], one column for the whole batch at every step (the
 // scalar kernels, the memo where the option is on).  rows = true: positions_host [n_steps, B], image_of_row_host [B] or null; the
 // schedule (column seed_len + position and the '.' rule of every row and step) is uploaded once and every step reads its slice.
-static int generate_impl(czc_engine* e, bool rows, int B, int T, int L, int seed_len, const int32_t* init_ids_host,
+// from = true (czc_generate_rows_from, a rows call): init_ids_host is [B, T], one start row per row, and a position may be
+// CZC_POS_IDLE.  A call with idle steps appends the run list of every step to the schedule and takes the compact-batch path of
+// memo_rows_step (with the entries where option "memo_rows" is on, without them otherwise); a call without any runs as
+// czc_generate_rows does.
+static int generate_impl(czc_engine* e, bool rows, bool from, int B, int T, int L, int seed_len, const int32_t* init_ids_host,
                          const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
                          const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp, int32_t* out_ids, float* out_cos) {
   if (!e || !init_ids_host || !positions_host || !hp || B <= 0 || n_steps < 0 || snapshot_every <= 0)
@@ -1736,7 +1771,26 @@ static int generate_impl(czc_engine* e, bool rows, int B, int T, int L, int seed
   e->err[0] = 0;
   const size_t n_pos = rows ? (size_t)n_steps * B : (size_t)n_steps;
   for (size_t i = 0; i < n_pos; ++i)
-    if (positions_host[i] < 0 || positions_host[i] >= L) return fail(e, CZC_ERR_ARG, "generate: position out of range%s");
+    if (positions_host[i] < (from ? CZC_POS_IDLE : 0) || positions_host[i] >= L)
+      return fail(e, CZC_ERR_ARG, from ? "generate_rows_from: position outside {CZC_POS_IDLE} and [0, L)%s" : "generate: position out of range%s");
+  bool any_idle = false;
+  if (from) {
+    for (size_t i = 0; i < (size_t)B * T; ++i)
+      if (init_ids_host[i] < 0 || init_ids_host[i] >= e->cfg.bert_vocab)
+        return fail(e, CZC_ERR_ARG, "generate_rows_from: start row holds an id outside the BERT vocabulary%s");
+    for (int s = 0; s < n_steps;) {  // a group: an n_mask >= 1 step plus the n_mask = 0 steps behind it
+      int g = 1;
+      while (s + g < n_steps && n_mask_host && n_mask_host[s + g] <= 0) ++g;
+      for (int r = 0; r < B; ++r) {
+        const bool idle = positions_host[(size_t)s * B + r] == CZC_POS_IDLE;
+        any_idle = any_idle || idle;
+        for (int j = 1; j < g; ++j)
+          if ((positions_host[(size_t)(s + j) * B + r] == CZC_POS_IDLE) != idle)
+            return fail(e, CZC_ERR_ARG, "generate_rows_from: a row must be idle for a whole step group (an n_mask >= 1 step and the n_mask = 0 steps behind it) or for none of it%s");
+      }
+      s += g;
+    }
+  }
   std::vector<int32_t> sched;  // rows: [n_steps][B] columns, then [n_steps][B] '.' rules (utils.py:53-59: position == L-1)
   if (rows) {
     if (B > CZC_MAX_ROWS || seed_len < 0 || T > CZC_MAX_BERT_LEN) return fail(e, CZC_ERR_ARG, "generate_rows: R > CZC_MAX_ROWS, seed_len < 0 or T > CZC_MAX_BERT_LEN%s");
@@ -1747,23 +1801,47 @@ static int generate_impl(czc_engine* e, bool rows, int B, int T, int L, int seed
       for (int r = 0; r < B; ++r)
         if (image_of_row_host[r] < 0 || image_of_row_host[r] >= e->img_B)
           return fail(e, CZC_ERR_ARG, "generate_rows: image_of_row outside the resident image batch%s");
-    if (e->ctl_fn && hp->control)  // the callback is only called on controlled steps
+    if (e->ctl_fn && hp->control && from) {  // the callback sees the rows that run, compacted: those must share one position
+      for (int s = 0; s < n_steps; ++s) {
+        int shared = CZC_POS_IDLE;
+        for (int r = 0; r < B; ++r) {
+          const int p = positions_host[(size_t)s * B + r];
+          if (p == CZC_POS_IDLE) continue;
+          if (shared != CZC_POS_IDLE && p != shared)
+            return fail(e, CZC_ERR_ARG, "generate_rows_from: a control callback carries one gen_idx, so the rows that are not idle must visit the same position at a step; "
+                                        "use the control tables (czc_set_lexicon / czc_set_lexicon_pos / czc_set_pos)%s");
+          shared = p;
+        }
+      }
+    } else if (e->ctl_fn && hp->control)  // the callback is only called on controlled steps
       for (size_t i = 0; i < n_pos; ++i)
         if (positions_host[i] != positions_host[i - i % B])
           return fail(e, CZC_ERR_ARG, "generate_rows: a control callback carries one gen_idx, so every row must visit the same position at a step; "
                                       "use the control tables (czc_set_lexicon / czc_set_lexicon_pos / czc_set_pos) or one czc_generate call per order%s");
-    sched.resize(2 * n_pos);
+    sched.resize((any_idle ? 3 : 2) * n_pos);
     for (size_t i = 0; i < n_pos; ++i) {
-      sched[i] = seed_len + positions_host[i];
+      sched[i] = positions_host[i] == CZC_POS_IDLE && from ? CZC_POS_IDLE : seed_len + positions_host[i];
       sched[n_pos + i] = positions_host[i] == L - 1 ? 1 : 0;
     }
+    if (any_idle)  // the host knows who runs: every step's rows that are not idle, ascending (the tail of a slice is not read)
+      for (int s = 0; s < n_steps; ++s) {
+        int32_t* list = sched.data() + 2 * n_pos + (size_t)s * B;
+        int n = 0;
+        for (int r = 0; r < B; ++r)
+          if (positions_host[(size_t)s * B + r] != CZC_POS_IDLE) list[n++] = r;
+        for (; n < B; ++n) list[n] = 0;
+      }
   }
   int *d_inp, *d_row, *d_sched = nullptr;
   { int* flag; E_CHECK(ensure(e, "s_nonfinite", 32, (void**)&flag)); E_HIP(hipMemsetAsync(flag, 0, 32, e->st)); }
   E_CHECK(ensure(e, "g_inp", (size_t)B * T * 4, (void**)&d_inp));
-  E_CHECK(ensure(e, "g_row", (size_t)T * 4, (void**)&d_row));
-  E_HIP(hipMemcpyAsync(d_row, init_ids_host, (size_t)T * 4, hipMemcpyHostToDevice, e->st));
-  E_CHECK(launch_broadcast_rows_i32(d_row, T, B, d_inp, e->st));
+  if (from) {  // every row brings its own start row: one upload, no broadcast
+    E_HIP(hipMemcpyAsync(d_inp, init_ids_host, (size_t)B * T * 4, hipMemcpyHostToDevice, e->st));
+  } else {
+    E_CHECK(ensure(e, "g_row", (size_t)T * 4, (void**)&d_row));
+    E_HIP(hipMemcpyAsync(d_row, init_ids_host, (size_t)T * 4, hipMemcpyHostToDevice, e->st));
+    E_CHECK(launch_broadcast_rows_i32(d_row, T, B, d_inp, e->st));
+  }
   // rows: the embedding of row r is that of image image_of_row[r] -- one gather of the normalised embeds to [R, D] here, and the
   // step sees a resident batch of R images (what the memo's compact batches do), so no tower or combine kernel changes
   float* img_full = e->d_img_n;
@@ -1771,12 +1849,12 @@ static int generate_impl(czc_engine* e, bool rows, int B, int T, int L, int seed
   if (rows) {
     const int D = e->cfg.clip_proj;
     int* d_ior = nullptr; float* img_r = nullptr;
-    if (n_pos) E_CHECK(ensure(e, "g_sched", 2 * n_pos * 4, (void**)&d_sched));
+    if (n_pos) E_CHECK(ensure(e, "g_sched", sched.size() * 4, (void**)&d_sched));
     if (image_of_row_host) {
       E_CHECK(ensure(e, "g_ior", (size_t)B * 4, (void**)&d_ior));
       E_CHECK(ensure(e, "g_img_r", (size_t)B * D * 4, (void**)&img_r));
     }
-    if (n_pos) E_HIP(hipMemcpyAsync(d_sched, sched.data(), 2 * n_pos * 4, hipMemcpyHostToDevice, e->st));
+    if (n_pos) E_HIP(hipMemcpyAsync(d_sched, sched.data(), sched.size() * 4, hipMemcpyHostToDevice, e->st));
     if (image_of_row_host) {
       E_HIP(hipMemcpyAsync(d_ior, image_of_row_host, (size_t)B * 4, hipMemcpyHostToDevice, e->st));
       E_CHECK(launch_gather_rows_f32(img_full, d_ior, B, D, img_r, e->st));
@@ -1803,9 +1881,11 @@ static int generate_impl(czc_engine* e, bool rows, int B, int T, int L, int seed
   if (memo) E_CHECK(memo_begin(e, B, T, n_steps, positions_host, n_mask_host, snapshot_every, out_cos != nullptr, audit, &mp));
   int snap = 0, rc = 0;
   MemoRowsPlan mrp;
-  const bool memo_rows = rows && e->memo_rows && n_steps > 0;
+  const bool memo_rows = rows && (e->memo_rows || any_idle) && n_steps > 0;  // the compact-batch path, with or without entries
   // (a failure here leaves through the exit below, which hands the resident image batch back)
-  if (memo_rows) rc = memo_rows_begin(e, B, T, L, seed_len, n_steps, positions_host, n_mask_host, snapshot_every, out_cos != nullptr, audit, &mrp);
+  if (memo_rows) rc = memo_rows_begin(e, e->memo_rows, B, T, L, seed_len, n_steps, positions_host, n_mask_host, snapshot_every, out_cos != nullptr, audit, &mrp);
+  // a row that has not run yet in this call reports cosine 0 (the reference's best_clip_score start value)
+  if (memo_rows && any_idle && !rc && hipMemsetAsync(mrp.bcos, 0, (size_t)B * 4, e->st) != hipSuccess) rc = fail(e, CZC_ERR_HIP, "generate_rows_from: clearing the cosines%s");
   for (int s = 0; s < n_steps && !rc; ++s) {
     const int pos = positions_host[rows ? (size_t)s * B : (size_t)s];
     const int nm = n_mask_host ? n_mask_host[s] : 1;
@@ -1846,14 +1926,21 @@ static int generate_impl(czc_engine* e, bool rows, int B, int T, int L, int seed
 int czc_generate(czc_engine* e, int B, int T, int L, int seed_len, const int32_t* init_ids_host, int top_k,
                  int n_steps, const int32_t* positions_host, const int32_t* n_mask_host, int snapshot_every,
                  const czc_hyper* hp, int32_t* out_ids, float* out_cos) {
-  return generate_impl(e, false, B, T, L, seed_len, init_ids_host, nullptr, top_k, n_steps, positions_host, n_mask_host,
+  return generate_impl(e, false, false, B, T, L, seed_len, init_ids_host, nullptr, top_k, n_steps, positions_host, n_mask_host,
                        snapshot_every, hp, out_ids, out_cos);
 }
 
 int czc_generate_rows(czc_engine* e, int R, int T, int L, int seed_len, const int32_t* init_ids_host,
                       const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
                       const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp, int32_t* out_ids, float* out_cos) {
-  return generate_impl(e, true, R, T, L, seed_len, init_ids_host, image_of_row_host, top_k, n_steps, positions_host, n_mask_host,
+  return generate_impl(e, true, false, R, T, L, seed_len, init_ids_host, image_of_row_host, top_k, n_steps, positions_host, n_mask_host,
+                       snapshot_every, hp, out_ids, out_cos);
+}
+
+int czc_generate_rows_from(czc_engine* e, int R, int T, int L, int seed_len, const int32_t* init_rows_host,
+                           const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
+                           const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp, int32_t* out_ids, float* out_cos) {
+  return generate_impl(e, true, true, R, T, L, seed_len, init_rows_host, image_of_row_host, top_k, n_steps, positions_host, n_mask_host,
                        snapshot_every, hp, out_ids, out_cos);
 }
 

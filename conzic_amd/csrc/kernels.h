@@ -152,8 +152,9 @@ struct MemoRowsTab {
   int R, T, L, seed_len;
 };
 // col0 / col1 (device, [R]): every row's column at the group's first / second step (col1 null for a one-step group).
-// check: hit[r] = slot (col0[r] - seed_len, r) is valid, has this group's signature and its key row equals the masked row r;
-// list = the other rows in ascending order; tot[0] = their count, tot[1 + j] = max over the hit rows of the slot's imax at
+// A row that sits the group out (czc_generate_rows_from) has col0[r] = CZC_POS_IDLE.
+// check: hit[r] = 1 where slot (col0[r] - seed_len, r) is valid, has this group's signature and its key row equals the masked
+// row r, 2 where row r is idle, else 0; list = the rows with hit[r] == 0 in ascending order; tot[0] = their count, tot[1 + j] = max over the hit rows of the slot's imax at
 // sub-step j (j < n_sub <= MEMO_ROWS_SUB); cnt: scratch, (R + 255) / 256 ints
 int launch_memo_rows_check(const int* inp, const MemoRowsTab& m, const int* col0, const int* col1, int n_mask0, int n_sub,
                            int mask_id, int* hit, int* cnt, int* list, int* tot, hipStream_t st);
@@ -166,7 +167,7 @@ int launch_memo_rows_gather(const int* inp, const int* list, int n, const MemoRo
 // rows[i], bcos[i], img_max[i]
 int launch_memo_rows_scatter(const int* rows, const float* bcos, const int* img_max, const int* list, int n, const MemoRowsTab& m,
                              const int* col0, int j, int record, int* inp, float* bcos_full, hipStream_t st);
-// rows with hit[r]: inp[r], bcos_full[r] = sub-step j of r's slot
+// rows with hit[r] == 1: inp[r], bcos_full[r] = sub-step j of r's slot (idle rows are left alone)
 int launch_memo_rows_fill(const int* hit, const MemoRowsTab& m, const int* col0, int j, int* inp, float* bcos_full, hipStream_t st);
 
 // ---- attention.hip ------------------------------------------------------------------------

@@ -6,10 +6,15 @@
 // Slot (p, r), p = first position of the group, e = p * R + r:  valid[e], sig[e], key[e][T] (the masked row R(r) of the last
 // visit), and per sub-step j < MEMO_ROWS_SUB with f = (p * MEMO_ROWS_SUB + j) * R + r:  rows[f][T] (the row the sub-step
 // left), cos[f] (winner cosine), imax[f] (longest CLIP branch of the plan).
+//
+// czc_generate_rows_from: a row that sits a step group out carries CZC_POS_IDLE in place of its column in the schedule slice
+// (col0[r] < 0).  It is neither a hit nor a miss: hit[r] = MR_IDLE keeps it off the active list and away from its slots.
 #include "../../include/conzic_hip.h"
 #include "kernels.h"
 
 namespace czc {
+
+constexpr int MR_MISS = 0, MR_HIT = 1, MR_IDLE = 2;  // hit[r] as the flag kernel leaves it
 
 __device__ __forceinline__ int mr_masked(const int* row, int t, int col, int n_mask, int mask_id) {
   return (t >= col && t < col + n_mask) ? mask_id : row[t];
@@ -28,7 +33,7 @@ __device__ __forceinline__ int mr_sig(int n_mask0, int n_sub, const int* col1, i
 // Check, first half.  One thread per row, 256 rows per work-group, R / 256 work-groups: the comparison reads 2 x T ints per row
 // (8 MB at R = 16384, T = 64), which one work-group walking the batch would pull through a single CU.  Thread r compares
 // R(r), built on the fly from the step's schedule slice, with the key row of r's own slot; hit[r] = 1 where valid, signature
-// and every column agree.  cnt[work-group] = its rows that did NOT hit; tot[1 + j] (zeroed by the launcher) = longest branch
+// and every column agree, MR_IDLE where the row sits the group out.  cnt[work-group] = its rows that run (MR_MISS); tot[1 + j] (zeroed by the launcher) = longest branch
 // a hit row had at sub-step j on its last visit.
 __global__ __launch_bounds__(256) void memo_rows_flag_kernel(const int* inp, MemoRowsTab m, const int* col0, const int* col1,
                                                              int n_mask0, int n_sub, int mask_id, int* hit, int* cnt, int* tot) {
@@ -40,7 +45,8 @@ __global__ __launch_bounds__(256) void memo_rows_flag_kernel(const int* inp, Mem
   __syncthreads();
   int act = 0;
   if (r < m.R) {
-    const int p = mr_pos(m, col0, r);
+    const bool idle = col0[r] < 0;
+    const int p = idle ? -1 : mr_pos(m, col0, r);
     bool same = false;
     if (p >= 0) {
       const size_t e = (size_t)p * m.R + r;
@@ -57,8 +63,8 @@ __global__ __launch_bounds__(256) void memo_rows_flag_kernel(const int* inp, Mem
           if (v > 0) atomicMax(&hmax[j], v);
         }
     }
-    hit[r] = same ? 1 : 0;
-    act = same ? 0 : 1;
+    hit[r] = idle ? MR_IDLE : same ? MR_HIT : MR_MISS;
+    act = (idle || same) ? 0 : 1;
   }
   const unsigned long long b = __ballot(act);
   if (lane == 0) wcount[w] = __popcll(b);
@@ -67,7 +73,7 @@ __global__ __launch_bounds__(256) void memo_rows_flag_kernel(const int* inp, Mem
   if (tid < MEMO_ROWS_SUB && hmax[tid] > 0) atomicMax(&tot[1 + tid], hmax[tid]);
 }
 
-// Check, second half: the rows that did not hit, in ascending order.  Work-group g adds up the counts of the work-groups in
+// Check, second half: the rows that run (neither hit nor idle), in ascending order.  Work-group g adds up the counts of the work-groups in
 // front of it (at most CZC_MAX_ROWS / 256 = 64 words), ranks its own rows by wave ballot, and the last one writes the total.
 __global__ __launch_bounds__(256) void memo_rows_list_kernel(const int* hit, int R, const int* cnt, int* list, int* tot) {
   __shared__ int wcount[4];
@@ -75,7 +81,7 @@ __global__ __launch_bounds__(256) void memo_rows_list_kernel(const int* hit, int
   const int r = blockIdx.x * 256 + tid;
   int base = 0;
   for (int i = 0; i < (int)blockIdx.x; ++i) base += cnt[i];
-  const int act = (r < R && !hit[r]) ? 1 : 0;
+  const int act = (r < R && hit[r] == MR_MISS) ? 1 : 0;
   const unsigned long long b = __ballot(act);
   const int before = __popcll(b & ((1ull << lane) - 1ull));
   if (lane == 0) wcount[w] = __popcll(b);
@@ -174,7 +180,7 @@ int launch_memo_rows_scatter(const int* rows, const float* bcos, const int* img_
 __global__ __launch_bounds__(64) void memo_rows_fill_kernel(const int* hit, MemoRowsTab m, const int* col0, int j, int* inp,
                                                             float* bcos_full) {
   const int r = blockIdx.x;
-  if (!hit[r]) return;
+  if (hit[r] != MR_HIT) return;  // a miss ran; an idle row keeps its ids and its last cosine
   const int p = mr_pos(m, col0, r);
   if (p < 0) return;
   const size_t f = ((size_t)p * MEMO_ROWS_SUB + j) * m.R + r;

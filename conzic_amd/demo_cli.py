@@ -24,7 +24,7 @@ def get_args(argv=None):
     p.add_argument("--seed", type=int, default=42)
     p.add_argument("--batch_size", type=int, default=1)
     p.add_argument("--device", type=str, default='cuda', choices=['cuda'])
-    p.add_argument('--run_type', default='controllable', nargs='?', choices=['caption', 'controllable'])
+    p.add_argument('--run_type', default='controllable', nargs='?', choices=['caption', 'controllable', 'infill'])
     p.add_argument('--prompt', default='Image of a', type=str)
     p.add_argument('--order', default='shuffle', nargs='?', choices=['sequential', 'shuffle', 'span', 'random'])
     p.add_argument('--control_type', default='sentiment', nargs='?', choices=["sentiment", "pos"])
@@ -55,7 +55,18 @@ def get_args(argv=None):
     p.add_argument("--batch_samples", action="store_true",
                    help="polish the samples_num samples of a batch in ONE engine call (one row per image and sample, every "
                         "sample with the visiting order the sample loop would have drawn for it) instead of one call per sample")
+    p.add_argument("--caption", action="append", default=None, metavar="TEMPLATE",
+                   help="--run_type infill (repeatable): a caption with blanks, e.g. \"a _ dog on a _\"; only the blanks are "
+                        "polished (num_iterations sweeps, --order sequential or shuffle over each caption's blanks), the given "
+                        "words stay as context; all captions go through one engine call per token length")
+    p.add_argument("--infill_positions", default="blanks", choices=["blanks", "all"],
+                   help="--run_type infill: polish the blanks only, or every position of every caption (polishing a draft / "
+                        "resuming an earlier result)")
     a = p.parse_args(argv)
+    if a.run_type == "infill" and not a.caption:
+        p.error("--run_type infill needs at least one --caption")
+    if a.run_type == "infill" and a.order not in ("sequential", "shuffle"):
+        p.error("--run_type infill visits the blanks in --order sequential or shuffle")
     if a.control_scores:
         os.environ["CZC_CONTROL"] = a.control_scores
     return a
@@ -106,6 +117,14 @@ def main(argv=None):
     image_instance = images if args.batch_size > 1 else images[0]
     img_name = [f"img{j}" for j in range(args.batch_size)]
     t0 = time.time()
+    if args.run_type == "infill":
+        # caption i describes image i (batch_size captions), or every caption the one image (batch_size 1)
+        from conzic_amd.runtime import infill_captions
+        infill_captions(args.caption, img_name, lm_model, clip, lm_tokenizer, image_instance, token_mask, logger, prompt=args.prompt,
+                        top_k=args.candidate_k, temperature=args.lm_temperature, max_iter=args.num_iterations, alpha=args.alpha,
+                        beta=args.beta, generate_order=args.order, positions=args.infill_positions)
+        logger.info("total %.2fs" % (time.time() - t0))
+        return
     if args.batch_samples:
         from conzic_amd.runtime import caption_samples
         caption_samples(args.samples_num, args.run_type, img_name, lm_model, clip, lm_tokenizer, image_instance, token_mask, logger,

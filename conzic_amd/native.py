@@ -26,6 +26,7 @@ PREC_SPLIT = 3
 PREC_FP16 = 4
 PREC_REFINE = 5
 CLIP_MAX_LEN = 77
+POS_IDLE = -1   # include/conzic_hip.h CZC_POS_IDLE: the row sits the step out (czc_generate_rows_from)
 
 
 ERR_ARG, ERR_HIP, ERR_STATE, ERR_OVERFLOW = 1, 2, 3, 4   # include/conzic_hip.h CZC_ERR_*
@@ -108,6 +109,7 @@ SIGNATURES = {
     "czc_step": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(Hyper), C.POINTER(StepOut)]),
     "czc_generate": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _P, _I, C.POINTER(Hyper), _P, _P]),
     "czc_generate_rows": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P, _I, C.POINTER(Hyper), _P, _P]),
+    "czc_generate_rows_from": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P, _I, C.POINTER(Hyper), _P, _P]),
     "czc_set_option": (_I, [_P, C.c_char_p, _I]),
     "czc_get_option": (_I, [_P, C.c_char_p, C.POINTER(_I)]),
     "czc_profile_enable": (_I, [_P, _I]),

@@ -92,6 +92,44 @@ def batched_samples(args, run_type, all_batches, own_lo, own_hi, rank, world, im
             write_results(result_dir(args, run_type, sample_id), all_results)
 
 
+def infill_batches(args, all_batches, own_lo, own_hi, rank, world, img_dir, lm_model, clip, lm_tokenizer, token_mask, logger):
+    """--run_type infill: every --caption template is infilled for every image of a batch, all of them rows of one engine call
+    per token length (runtime.run_infill); the images are encoded once per batch.  One pass (sample_0): iter_<k>.json holds the
+    captions after sweep k, keyed by image name (`name#c` for template c when there are several)."""
+    from PIL import Image
+    from conzic_amd.runtime import infill_captions
+    C = len(args.caption)
+    all_results = [None] * (args.num_iterations + 1)
+    for batch_idx, name_batch in enumerate(all_batches):
+        if not (own_lo <= batch_idx < own_hi):
+            continue
+        logger.info(f"The {batch_idx + 1}-th batch:")
+        imgs = [Image.open(os.path.join(img_dir, n)).convert("RGB") for n in name_batch]
+        caps = [c for _ in name_batch for c in args.caption]
+        image_of_caption = [b for b in range(len(name_batch)) for _ in range(C)]
+        outs = infill_captions(caps, name_batch, lm_model, clip, lm_tokenizer, imgs, token_mask, logger, prompt=args.prompt,
+                               top_k=args.candidate_k, temperature=args.lm_temperature, max_iter=args.num_iterations,
+                               alpha=args.alpha, beta=args.beta, generate_order=args.order, positions=args.infill_positions,
+                               image_of_caption=image_of_caption)
+        for i, (gen_texts, _) in enumerate(outs):
+            key = name_batch[i // C] if C == 1 else f"{name_batch[i // C]}#{i % C}"
+            # (a batch whose captions have no blank at all returns no snapshots: its files repeat the best entry)
+            texts = gen_texts[:-1] + [gen_texts[-2] if len(gen_texts) > 1 else gen_texts[-1]] * (args.num_iterations + 1 - len(gen_texts)) \
+                + gen_texts[-1:]
+            all_results = merge_results(all_results, texts, [key])
+    if world > 1:
+        import torch.distributed as tdist
+        parts = [None] * world
+        tdist.all_gather_object(parts, all_results)
+        all_results = [None] * (args.num_iterations + 1)
+        for part in parts:  # rank order == batch order
+            for it, d in enumerate(part):
+                if d is not None:
+                    all_results[it] = {**(all_results[it] or {}), **d}
+    if rank == 0:
+        write_results(result_dir(args, "infill", 0), all_results)
+
+
 def main(argv=None):
     args = get_args(argv)
     import logging
@@ -108,7 +146,7 @@ def main(argv=None):
     utils.set_seed(args.seed)
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     logger = logging.getLogger("ConZIC")
-    run_type = "caption" if args.run_type == "caption" else args.sentiment_type
+    run_type = "caption" if args.run_type == "caption" else "infill" if args.run_type == "infill" else args.sentiment_type
     if args.synthetic:
         sv = synth.make_vocab_tiny() if args.tiny else synth.make_vocab()
         bcfg = synth.bert_tiny(len(sv.bert_tokens)) if args.tiny else synth.bert_base()
@@ -155,6 +193,9 @@ def main(argv=None):
     all_batches = list(batches(names, args.batch_size))
     own_lo, own_hi = czd.shard_range(len(all_batches), rank, world)
     embed_cache = {}  # batch index -> image_embeds [B, proj]: the ViT runs once per image, not once per sample
+    if args.run_type == "infill":
+        infill_batches(args, all_batches, own_lo, own_hi, rank, world, img_dir, lm_model, clip, lm_tokenizer, token_mask, logger)
+        return
     if args.batch_samples:
         batched_samples(args, run_type, all_batches, own_lo, own_hi, rank, world, img_dir, lm_model, clip, lm_tokenizer,
                         token_mask, logger)

@@ -463,6 +463,103 @@ def run_generation_samples(order: str, samples_num: int, img_name, model, clip, 
     return out
 
 
+def run_infill(captions: Sequence[str], img_name, model, clip, tokenizer, image_instance, token_mask, prompt, logger, *,
+               order: str = "sequential", max_iters: int = 10, top_k: int = 200, temperature=0.1, alpha=0.02, beta=2.0,
+               positions: str = "blanks", image_of_caption: Optional[Sequence[int]] = None, blank: str = "_", verbose=True):
+    """Infilling, resume and draft polishing (beyond the reference's CLI; its loop body, gen_utils.py:64-81, unchanged): every
+    caption of `captions` is a template whose `blank` words are polished while the given words stay as context
+    (`positions="blanks"`), or a draft / earlier result of which every position is polished again (`positions="all"`: nothing is
+    idle).  Caption i describes image image_of_caption[i] of `image_instance` (None: caption i = image i, or all captions the
+    one image).  The images are encoded once; the captions are grouped by token length and each group is ONE
+    czc_generate_rows_from call, its rows with their own start rows and visiting orders (infill.infill_schedules, drawn for all
+    captions in caption order before the first call), a caption with fewer blanks sitting out the rest of every sweep.
+    `max_iters` sweeps; honours CZC_MEMO_ROWS.  Returns one (gen_texts_list, clip_score_sequence) pair per caption, in the
+    structure a *_generation call returns for a batch of one.  The caller's token_mask is left as after the last visited
+    position (utils.py:53-59)."""
+    import utils as ref_utils
+    from . import infill
+    captions = list(captions)
+    if not captions:
+        return []
+    eng = get_engine(model, clip, tokenizer)
+    clip.compute_image_representation_from_image_instance(image_instance)   # once, whatever the number of groups
+    from clip.clip import ImageEmbeds
+    emb = image_instance.embeds if isinstance(image_instance, ImageEmbeds) else clip.last_image_embeds()
+    n_img = int(emb.shape[0])
+    if image_of_caption is None:
+        if n_img not in (1, len(captions)):
+            raise ValueError(f"run_infill: {len(captions)} captions for {n_img} images need image_of_caption")
+        image_of_caption = [0] * len(captions) if n_img == 1 else list(range(len(captions)))
+    ioc = [int(i) for i in image_of_caption]
+    if len(ioc) != len(captions) or any(i < 0 or i >= n_img for i in ioc):
+        raise ValueError("run_infill: image_of_caption must name one resident image per caption")
+    if getattr(eng, "_precision_logged", None) is None:
+        scale = _logit_scale_of(clip)
+        logger.info(f"engine precision: {PRECISION_NAMES.get(eng.precision, eng.precision)}"
+                    + (f" (exp(logit_scale) = {math.exp(scale):.1f})" if scale is not None else ""))
+        eng._precision_logged = True
+    parsed = [infill.parse_template(tokenizer, prompt, c, blank=blank) for c in captions]
+    visits = infill.visit_lists(parsed, positions)
+    groups = infill.group_by_length(parsed)
+    # all orders first, in caption order (one draw per caption from the process-global stream for `shuffle`), so that a
+    # caption's order does not depend on how the captions group
+    pos_all, _, _ = infill.infill_schedules(visits, order, max_iters)
+    if order == "shuffle":
+        for i, v in enumerate(visits):
+            logger.info(f"Order_list:{[int(p) for p in pos_all[:len(v), i]]}")
+    hp = Engine.hyper(alpha, beta, temperature)
+    out = [None] * len(captions)
+    last = None
+    for T, members in groups.items():
+        L, seed_len = parsed[members[0]][2], parsed[members[0]][3]
+        pos, n_mask, every = infill.take_rows(pos_all, max_iters, members)
+        init_rows = np.stack([parsed[i][0] for i in members]).astype(np.int32)
+        image_of_row = np.asarray([ioc[i] for i in members], dtype=np.int32)
+
+        def polish(eng, init_rows=init_rows, L=L, seed_len=seed_len, pos=pos, n_mask=n_mask, every=every,
+                   image_of_row=image_of_row, R=len(members)):
+            eng.set_token_mask(_mask_to_numpy(token_mask))
+            eng.set_option("memo_rows", memo_rows_setting())  # per-row step memo (CZC_MEMO_ROWS); an idle step is not a visit
+            runner = _group_for(eng, R)
+            if runner is not eng:
+                runner.set_image_embeds(emb)
+            if eng.precision == native.PREC_REFINE:
+                runner.refine_guard(reset=True)
+            res = runner.generate_rows_from(init_rows, L, seed_len, top_k, pos, hp, image_of_row=image_of_row, n_mask=n_mask,
+                                            snapshot_every=every)
+            if runner is not eng:
+                eng.set_image_embeds(emb)
+            return res, runner
+
+        ids, cos = _polish_guarded(polish, eng, model, clip, tokenizer, ImageEmbeds(emb), logger)
+        lv = infill.last_visited(pos)
+        if lv is not None:
+            last = (L, lv)
+        for k, i in enumerate(members):
+            out[i] = _bookkeeping(order, ids[:, k:k + 1], cos[:, k:k + 1], tokenizer, [img_name[ioc[i]]], logger, 1, verbose, None)
+    if last is not None:
+        ref_utils.update_token_mask(tokenizer, token_mask, last[0], last[1])
+    return out
+
+
+def infill_captions(captions, img_name, model, clip, tokenizer, image_instance, token_mask, logger, *, prompt="", top_k=100,
+                    temperature=1.0, max_iter=10, alpha=0.7, beta=1, generate_order="sequential", positions="blanks",
+                    image_of_caption=None):
+    """`--run_type infill` of the two CLIs: one run_infill call over the `--caption` templates, logging every caption's final
+    and best text as generate_caption does (gen_utils.py:325-331)."""
+    start_time = time.time()
+    order = "sequential" if generate_order == "sequential" else "shuffle"
+    outs = run_infill(captions, img_name, model, clip, tokenizer, image_instance, token_mask, prompt, logger, order=order,
+                      max_iters=max_iter, top_k=top_k, temperature=temperature, alpha=alpha, beta=beta, positions=positions,
+                      image_of_caption=image_of_caption)
+    logger.info("Finished in %.3fs" % (time.time() - start_time))
+    for i, (generate_texts, _) in enumerate(outs):
+        logger.info(f"The {i + 1}-th caption: {captions[i]}")
+        logger.info(f"final caption: {generate_texts[-2][0] if len(generate_texts) > 1 else 'None'}")
+        logger.info(f"best caption: {generate_texts[-1][0]}")
+    return outs
+
+
 def caption_order(run_type: str, generate_order: str, ctl_type: str, max_iter: int, max_len: int):
     """(visiting order, max_iters) the *_generation function behind generate_caption / control_generate_caption runs with."""
     if run_type == "caption":

@@ -284,6 +284,44 @@ int czc_generate_rows(czc_engine* e, int R, int T, int L, int seed_len, const in
                       const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
                       const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp, int32_t* out_ids, float* out_cos);
 
+/* czc_generate_rows with a START ROW per row and steps a row may sit out: infilling (only the blanks of a given caption are
+ * polished, the given words stay as context), resume (more sweeps from where an earlier call stopped) and polishing a draft.
+ * The reference's CLI never exposed these, but its loop body does them unchanged (gen_utils.py:66 `inp[:, seed_len+ii] = mask`
+ * does not care what the rest of the row holds).  Everything not named here is as in czc_generate_rows, which keeps its
+ * behaviour bit for bit (as does czc_generate), position -1 refused included.
+ *   - init_rows int32 [R, T]: row r starts as init_rows[r].  Ids must lie in [0, bert_vocab); nothing else about their content
+ *     is checked -- the caller decides what is prompt, word or [MASK].  Uploaded once; no broadcast.
+ *   - positions[s*R + r] == CZC_POS_IDLE: row r does not take part in step s.  Its ids do not change; no BERT row, candidate,
+ *     tower row or combine work is spent on it; it is not handed to a control callback; czc_stats, czc_dedup_stats, the
+ *     czc_refine_ counters and czc_memo_rows_stats count only the rows that ran.  A step runs on all rows, on none (a step idle
+ *     in every row launches nothing) or on a compact batch of the rows that are not idle, with their own columns and '.' rules.
+ *     The host knows the schedule, so every step's run list travels with the schedule upload: with option "memo_rows" off an
+ *     idle call makes no device-to-host read beyond those of czc_generate_rows.  A call without any idle step runs as
+ *     czc_generate_rows does: from the same start row in every row it returns that call's bits.
+ *   - groups: n_mask stays one value per step for all rows.  A group is an n_mask >= 1 step plus the n_mask = 0 steps behind
+ *     it; a row must be idle for a whole group or for none of it, else CZC_ERR_ARG.  The n_mask = 0 re-use rule of czc_step
+ *     keeps holding per row on the compact batches.
+ *   - snapshots: out_ids = the rows as they stand; out_cos[snap][r] = the winner cosine of row r's most recent executed step
+ *     in this call, 0.0f while it has not executed one (the reference's best_clip_score start value, gen_utils.py:62).
+ *   - a step's result depends only on the rows it is given (deterministic argmax; the only state between steps is the
+ *     n_mask = 0 re-use inside a group), so resuming from a snapshot of czc_generate / czc_generate_rows with the remaining
+ *     positions returns the remaining snapshots of the one long call, bit for bit (CZC_PREC_REFINE places its audit steps by
+ *     sweep index within a call, so there the winner cosines of a resumed call may differ in the last bits).  What a compact
+ *     batch keeps, and CZC_PREC_SPLIT, are as described for option "memo_rows" below.
+ *   - option "memo_rows": an idle step is not a visit -- it neither reads nor replaces the row's entries and is neither a hit
+ *     nor a counted row-step.  The active set of a checked step is (not idle) and (miss); CZC_PREC_SPLIT runs a checked step on
+ *     every row that is not idle unless all of them hit.  A step at which no row that runs revisits a key needs no check.
+ *   - CZC_PREC_REFINE: audit and snapshot rules are unchanged for the rows that run; idle rows are not audited, and an audit
+ *     step that is idle in every row is skipped.
+ *   - control callback with czc_hyper.control != 0: the rows of a step that are not idle must share one position, else
+ *     CZC_ERR_ARG; the callback sees the running rows compacted (B = their count), as under "memo_rows".
+ * Checked before any GPU work, CZC_ERR_ARG, and the engine stays usable: a position outside {CZC_POS_IDLE} and [0, L), an id
+ * outside the vocabulary, the group rule, and everything czc_generate_rows checks. */
+#define CZC_POS_IDLE (-1)
+int czc_generate_rows_from(czc_engine* e, int R, int T, int L, int seed_len, const int32_t* init_rows_host,
+                           const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
+                           const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp, int32_t* out_ids, float* out_cos);
+
 /* Engine options (all are exact work reductions / kernel choices; results agree within the engine precision):
  *   "share_prefix"    (1) encode the causal prefix common to an image's K candidates once per step instead of K
  *                         times
@@ -345,7 +383,7 @@ int czc_generate_rows(czc_engine* e, int R, int T, int L, int seed_len, const in
  *                         the active count and the rows are compacted, so it must be a pure function of its rows (the
  *                         reference scorer is).  Replicas (czc_replicate) inherit the option and keep memos of their own.
  *                         czc_memo_stats counts the hits; czc_stats / czc_refine_gate_stats keep counting what ran
- *   "memo_rows"       (0) czc_generate_rows only (czc_generate ignores it; independent of "memo", which a rows call ignores):
+ *   "memo_rows"       (0) czc_generate_rows / czc_generate_rows_from only (czc_generate ignores it; independent of "memo", which a rows call ignores):
  *                         the rule of "memo" keyed per ROW.  n_mask is one value per step for all rows, so the step groups (one
  *                         n_mask >= 1 step plus the n_mask = 0 steps behind it) are shared; the positions are row r's own.  Row
  *                         r's key at a group: its position at every step of the group and the group's n_mask list.  Its entry

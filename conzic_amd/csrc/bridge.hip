@@ -45,7 +45,7 @@ __device__ __forceinline__ bool merge_lookup(const BridgeDev& bd, int l, int r, 
 // wave can span several rows of inp (K need not be a multiple of 64), so the column is a per-thread value, not a wave-uniform one
 template <bool ROWS>
 __global__ __launch_bounds__(BR_THREADS) void bridge_kernel(BridgeDev bd, const int* inp, int B, int T, int gen_idx_, const int* gen_rows,
-                                                            const int* cand, int K, const float* lexicon, const float* lex_pos,
+                                                            const int* row_len, const int* cand, int K, const float* lexicon, const float* lex_pos,
                                                             const uint8_t* lex_cls, int negative, PosDev pos, int* clip_ids, int* clip_len, float* senti_raw,
                                                             float* repeats, int* overflow) {
   extern __shared__ __attribute__((aligned(16))) unsigned char br_lds[];
@@ -65,6 +65,7 @@ __global__ __launch_bounds__(BR_THREADS) void bridge_kernel(BridgeDev bd, const 
   const int b = (int)(row / K);
   const int cid = cand ? cand[row] : -1;
   const int gen_idx = ROWS ? gen_rows[b] : gen_idx_;
+  const int n_tok = ROWS && row_len ? row_len[b] : T;  // czc_generate_rows_len: the row's own length, its padding tail is not read
 
   // ---- 1. decode to bytes ------------------------------------------------------------------
   int n = 0;
@@ -72,7 +73,7 @@ __global__ __launch_bounds__(BR_THREADS) void bridge_kernel(BridgeDev bd, const 
   float senti = 0.f;
   int rep = 0;
   int n_words = 0, pos_ok = 0;  // POS control: words = non-special pieces that do not continue a word
-  for (int t = 0; t < T; ++t) {
+  for (int t = 0; t < n_tok; ++t) {
     const int id = (cand && t == gen_idx) ? cid : inp[b * T + t];
     if (cand && id == cid) ++rep;
     const unsigned fl = bd.piece_flags[id];
@@ -221,7 +222,7 @@ int launch_bridge_precompute(const BridgeDev& bd, int* tok_ids, uint8_t* tok_len
 }
 
 template <bool ROWS>
-static int launch_bridge_t(const BridgeDev& bd, const int* inp, int B, int T, int gen_idx, const int* gen_rows, const int* cand, int K,
+static int launch_bridge_t(const BridgeDev& bd, const int* inp, int B, int T, int gen_idx, const int* gen_rows, const int* row_len, const int* cand, int K,
                            const float* lexicon, const float* lex_pos, const uint8_t* lex_cls, int negative, const PosDev& pos, int* clip_ids,
                            int* clip_len, float* senti_raw, float* repeats, int* overflow_flag, hipStream_t st) {
   const long rows = (long)B * K;
@@ -229,7 +230,7 @@ static int launch_bridge_t(const BridgeDev& bd, const int* inp, int B, int T, in
   const size_t shmem = (size_t)BR_THREADS * (2 * BR_MAXB + BR_MAXSYM * 4 + BR_MAXP * 8);
   CZC_HIP_CHECK(hipFuncSetAttribute((const void*)bridge_kernel<ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
   hipLaunchKernelGGL(bridge_kernel<ROWS>, dim3(cdiv(rows, BR_THREADS)), dim3(BR_THREADS), shmem, st, bd, inp, B, T, gen_idx, gen_rows,
-                     cand, K, lexicon, lex_pos, lex_cls, negative, pos, clip_ids, clip_len, senti_raw, repeats, overflow_flag);
+                     row_len, cand, K, lexicon, lex_pos, lex_cls, negative, pos, clip_ids, clip_len, senti_raw, repeats, overflow_flag);
   CZC_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -237,15 +238,15 @@ static int launch_bridge_t(const BridgeDev& bd, const int* inp, int B, int T, in
 int launch_bridge(const BridgeDev& bd, const int* inp, int B, int T, int gen_idx, const int* cand, int K,
                   const float* lexicon, const float* lex_pos, const uint8_t* lex_cls, int negative, const PosDev& pos, int* clip_ids, int* clip_len, float* senti_raw,
                   float* repeats, int* overflow_flag, hipStream_t st) {
-  return launch_bridge_t<false>(bd, inp, B, T, gen_idx, nullptr, cand, K, lexicon, lex_pos, lex_cls, negative, pos, clip_ids, clip_len,
+  return launch_bridge_t<false>(bd, inp, B, T, gen_idx, nullptr, nullptr, cand, K, lexicon, lex_pos, lex_cls, negative, pos, clip_ids, clip_len,
                                 senti_raw, repeats, overflow_flag, st);
 }
 
 int launch_bridge_rows(const BridgeDev& bd, const int* inp, int B, int T, const int* gen_rows, const int* cand, int K,
                        const float* lexicon, const float* lex_pos, const uint8_t* lex_cls, int negative, const PosDev& pos, int* clip_ids, int* clip_len,
-                       float* senti_raw, float* repeats, int* overflow_flag, hipStream_t st) {
+                       float* senti_raw, float* repeats, int* overflow_flag, hipStream_t st, const int* row_len) {
   if (!gen_rows || !cand) { snprintf(g_err, sizeof(g_err), "bridge: the per-row form needs gen_rows and cand"); return 1; }
-  return launch_bridge_t<true>(bd, inp, B, T, 0, gen_rows, cand, K, lexicon, lex_pos, lex_cls, negative, pos, clip_ids, clip_len,
+  return launch_bridge_t<true>(bd, inp, B, T, 0, gen_rows, row_len, cand, K, lexicon, lex_pos, lex_cls, negative, pos, clip_ids, clip_len,
                                senti_raw, repeats, overflow_flag, st);
 }
 

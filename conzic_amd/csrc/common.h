@@ -169,6 +169,44 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// ---- LayerNorm of one row by one wave (rowops.hip, ragged.hip) ----
+constexpr int LN_MAXV = 4;  // float4 per lane -> H <= 1024
+
+// one wave per row; returns this lane's normalised values in v[]
+template <int NV>
+__device__ __forceinline__ void ln_row(float4 (&v)[NV], int H, int lane, const float* gamma, const float* beta,
+                                       float eps) {
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int c = (i * 64 + lane) * 4;
+    if (c < H) s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
+  }
+  const float mean = wave_sum(s) / (float)H;
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int c = (i * 64 + lane) * 4;
+    if (c < H) {
+      const float a = v[i].x - mean, b = v[i].y - mean, cc = v[i].z - mean, d = v[i].w - mean;
+      q += (a * a + b * b) + (cc * cc + d * d);
+    }
+  }
+  const float rstd = rsqrtf(wave_sum(q) / (float)H + eps);
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int c = (i * 64 + lane) * 4;
+    if (c < H) {
+      const float4 gm = *(const float4*)(gamma + c);
+      const float4 bt = *(const float4*)(beta + c);
+      v[i].x = (v[i].x - mean) * rstd * gm.x + bt.x;
+      v[i].y = (v[i].y - mean) * rstd * gm.y + bt.y;
+      v[i].z = (v[i].z - mean) * rstd * gm.z + bt.z;
+      v[i].w = (v[i].w - mean) * rstd * gm.w + bt.w;
+    }
+  }
+}
+
 __device__ __forceinline__ float quick_gelu(float x) { return x / (1.0f + __expf(-1.702f * x)); }
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 

@@ -473,15 +473,23 @@ int clip_stack(czc_engine* e, int P, const char* gk, std::vector<LayerW>& L, flo
   return 0;
 }
 
+// czc_generate_rows_len: the B sequences of a step have their own lengths.  off [B + 1] / len [B] (device): sequence b has len[b]
+// tokens -- the first len[b] columns of row b of the [B, T] strided ids -- and packed rows off[b] ..; M = off[B], max_T = the
+// longest.  Null wherever a Ragged* is taken: B x T rows, the uniform path.
+struct Ragged { const int* off; const int* len; int M; int max_T; };
+
 // ---- BERT encoder (post-LN) on [B*T] rows: leaves the final hidden state in ws "b_x" ----------
 // keep_idx >= 0: only row keep_idx of every sequence is read afterwards (the masked slot, gen_utils.py:69): the last layer
 // still forms q/k/v and the attention for all rows, then gathers that row and runs out-proj / LN / MLP / LN on B rows
 // instead of B*T; the result goes to ws "b_xg" [B,H].  Same kernels per row, so the row's values do not change.
 // keep_rows (device, [B]; with keep_rows_host its host copy): the kept row is keep_rows[b] of sequence b (czc_generate_rows).
+// rag: the stack runs on the rag->M packed rows of ragged sequences (ragged.hip embedding, attention over each sequence's own
+// keys, kept row rag->off[b] + keep_rows[b]); the GEMMs and LayerNorms are the same launches on M rows.
 int bert_forward(czc_engine* e, const int* d_inp, int B, int T, int keep_idx = -1, const int* keep_rows = nullptr,
-                 const int32_t* keep_rows_host = nullptr) {
+                 const int32_t* keep_rows_host = nullptr, const Ragged* rag = nullptr) {
   const czc_config& c = e->cfg;
-  const int P = e->pb, M = B * T, H = c.bert_hidden, I = c.bert_inter;
+  const int P = e->pb, M = rag ? rag->M : B * T, H = c.bert_hidden, I = c.bert_inter;
+  if (rag && keep_idx >= 0 && !keep_rows) return fail(e, CZC_ERR_STATE, "ragged BERT rows keep a row per sequence (keep_rows)%s");
   void *xa, *qkv, *ctx, *hbuf; float *x, *tmp;
   E_CHECK(ensure(e, "b_x", (size_t)M * H * 4, (void**)&x));
   E_CHECK(ensure(e, "b_tmp", (size_t)M * H * 4, (void**)&tmp));
@@ -496,7 +504,8 @@ int bert_forward(czc_engine* e, const int* d_inp, int B, int T, int keep_idx = -
   E_CHECK(need(e, "bert.embeddings.LayerNorm.weight", H, &g));
   E_CHECK(need(e, "bert.embeddings.LayerNorm.bias", H, &b));
   { ProfScope ps(e, "rowops", 0);
-    E_CHECK(launch_bert_embed(P, d_inp, B, T, H, word, pos, typ, g, b, c.bert_eps, xa, x, e->st)); }
+    if (rag) E_CHECK(launch_bert_embed_ragged(P, d_inp, T, nullptr, rag->off, rag->len, B, rag->max_T, H, word, pos, typ, g, b, c.bert_eps, xa, x, e->st));
+    else E_CHECK(launch_bert_embed(P, d_inp, B, T, H, word, pos, typ, g, b, c.bert_eps, xa, x, e->st)); }
   const float scale = 1.0f / sqrtf(64.0f);
   e->bert_pruned_idx = -1;
   e->bert_pruned_rows = nullptr;
@@ -519,15 +528,16 @@ int bert_forward(czc_engine* e, const int* d_inp, int B, int T, int keep_idx = -
     LayerW& l = e->bert[n];
     E_CHECK(gemm(e, P, "gemm_bert", xa, H, l.qkv_w, H, l.qkv_b, nullptr, 0, qkv, nullptr, 3 * H, M, 3 * H, H, ACT_NONE));
     { ProfScope ps(e, "attention", 0);
-      SegTable tab{nullptr, nullptr, nullptr, nullptr, B, T};
-      E_CHECK(launch_attention(P, qkv, tab, T, c.bert_heads, 0, scale, ctx, e->st)); }
+      SegTable tab{nullptr, nullptr, rag ? rag->off : nullptr, rag ? rag->len : nullptr, B, rag ? 0 : T};
+      E_CHECK(launch_attention(P, qkv, tab, rag ? rag->max_T : T, c.bert_heads, 0, scale, ctx, e->st)); }
     if (keep_idx >= 0 && n + 1 == c.bert_layers) {
       int* idx; void* ctx_g; float* x_g;
       E_CHECK(ensure(e, "b_pidx", (size_t)B * 4, (void**)&idx));
       E_CHECK(ensure(e, "b_cg", (size_t)B * H * e->eb, &ctx_g));
       E_CHECK(ensure(e, "b_xg", (size_t)B * H * 4, (void**)&x_g));
       { ProfScope ps(e, "rowops", 0);
-        if (keep_rows) E_CHECK(launch_make_row_index_rows(idx, B, T, keep_rows, e->st));
+        if (rag) E_CHECK(launch_ragged_row_index(idx, B, rag->off, keep_rows, e->st));
+        else if (keep_rows) E_CHECK(launch_make_row_index_rows(idx, B, T, keep_rows, e->st));
         else E_CHECK(launch_make_row_index(idx, B, T, keep_idx, e->st));
         E_CHECK(launch_gather_rows_bytes(ctx, idx, B, H * (int)e->eb, ctx_g, e->st));
         E_CHECK(launch_gather_rows_f32(x, idx, B, H, x_g, e->st)); }
@@ -551,7 +561,7 @@ int bert_forward(czc_engine* e, const int* d_inp, int B, int T, int keep_idx = -
 // MLM head on row gen_idx of every sequence -> logits fp32 [B,V] in ws "b_logits"
 // gen_rows (device, [B]) / gen_rows_host: row gen_rows[b] of sequence b instead (czc_generate_rows)
 int mlm_head(czc_engine* e, int B, int T, int gen_idx, float** logits_out, const int* gen_rows = nullptr,
-             const int32_t* gen_rows_host = nullptr) {
+             const int32_t* gen_rows_host = nullptr, const Ragged* rag = nullptr) {
   const czc_config& c = e->cfg;
   const int P = e->pb, H = c.bert_hidden, V = c.bert_vocab;
   float* x = (float*)e->ws["b_x"].p;
@@ -577,7 +587,9 @@ int mlm_head(czc_engine* e, int B, int T, int gen_idx, float** logits_out, const
     if (e->bert_pruned_idx >= 0) {
       gx = (float*)e->ws["b_xg"].p;  // the forward left exactly these rows
     } else {
-      if (gen_rows) E_CHECK(launch_make_row_index_rows(idx, B, T, gen_rows, e->st));
+      if (rag && !gen_rows) return fail(e, CZC_ERR_STATE, "ragged BERT rows are read by a row per sequence (gen_rows)%s");
+      if (rag) E_CHECK(launch_ragged_row_index(idx, B, rag->off, gen_rows, e->st));
+      else if (gen_rows) E_CHECK(launch_make_row_index_rows(idx, B, T, gen_rows, e->st));
       else E_CHECK(launch_make_row_index(idx, B, T, gen_idx, e->st));
       E_CHECK(launch_gather_rows_f32(x, idx, B, H, gx, e->st));
     }
@@ -716,6 +728,9 @@ struct StepArgs {
   // czc_generate_rows: column / '.' rule of every row (device, [B]) and the columns' host copy; null = the scalars above
   // (gen_idx then still holds row 0's column: what a control callback is told when all rows share one)
   const int* gen_rows = nullptr; const int* dot_rows = nullptr; const int32_t* gen_rows_host = nullptr;
+  // czc_generate_rows_len: the rows' own lengths (T is then the stride of d_inp only); ctl_T: the one length the rows of a step
+  // share where a control callback is set -- what it is told as T, with the rows' first ctl_T columns
+  const Ragged* rag = nullptr; int ctl_T = 0;
 };
 struct StepBufs { float *probs, *senti, *reps; int *idxs, *cand, *cids, *clen, *totals; };
 
@@ -739,14 +754,14 @@ int step_phase_a(czc_engine* e, const StepArgs& a) {
     const bool prune = e->bert_prune && a.n_mask == 1;
     if (a.gen_rows) {
       E_CHECK(launch_mask_positions_rows(a.d_inp, a.B, a.T, a.gen_rows, a.n_mask, c.mask_id, e->st));
-      E_CHECK(bert_forward(e, a.d_inp, a.B, a.T, prune ? a.gen_idx : -1, prune ? a.gen_rows : nullptr, a.gen_rows_host));
+      E_CHECK(bert_forward(e, a.d_inp, a.B, a.T, prune ? a.gen_idx : -1, prune ? a.gen_rows : nullptr, a.gen_rows_host, a.rag));
     } else {
       E_CHECK(launch_mask_positions(a.d_inp, a.B, a.T, a.gen_idx, a.n_mask, c.mask_id, e->st));
       E_CHECK(bert_forward(e, a.d_inp, a.B, a.T, prune ? a.gen_idx : -1));
     }
   }
   float* logits;
-  E_CHECK(mlm_head(e, a.B, a.T, a.gen_idx, &logits, a.gen_rows, a.gen_rows_host));
+  E_CHECK(mlm_head(e, a.B, a.T, a.gen_idx, &logits, a.gen_rows, a.gen_rows_host, a.rag));
   StepBufs b;
   E_CHECK(step_bufs(e, a.B * a.K, &b));
   { ProfScope ps(e, "topk", 0);
@@ -759,7 +774,7 @@ int step_phase_a(czc_engine* e, const StepArgs& a) {
     PosDev pos{hp->control == 2 ? e->d_pos_tags : nullptr, e->d_pos_masks, e->pos_n};
     if (a.gen_rows) E_CHECK(launch_bridge_rows(e->bd, a.d_inp, a.B, a.T, a.gen_rows, b.cand, a.K, hp->control == 1 ? e->d_lex : nullptr,
                                                hp->control == 1 ? e->d_lex_pos : nullptr, e->d_lex_cls, hp->negative,
-                                               pos, b.cids, b.clen, b.senti, b.reps, b.totals + 2, e->st));
+                                               pos, b.cids, b.clen, b.senti, b.reps, b.totals + 2, e->st, a.rag ? a.rag->len : nullptr));
     else E_CHECK(launch_bridge(e->bd, a.d_inp, a.B, a.T, a.gen_idx, b.cand, a.K, hp->control == 1 ? e->d_lex : nullptr,
                                hp->control == 1 ? e->d_lex_pos : nullptr, e->d_lex_cls, hp->negative,
                                pos, b.cids, b.clen, b.senti, b.reps, b.totals + 2, e->st)); }
@@ -788,10 +803,12 @@ int control_pinned(czc_engine* e, size_t n_inp, size_t n_seq) {
 
 int control_fetch(czc_engine* e, const StepArgs& a) {
   StepBufs b;
-  const size_t n_seq = (size_t)a.B * a.K, n_inp = (size_t)a.B * a.T;
+  const int Tc = a.ctl_T > 0 ? a.ctl_T : a.T;
+  const size_t n_seq = (size_t)a.B * a.K, n_inp = (size_t)a.B * Tc;
   E_CHECK(step_bufs(e, (int)n_seq, &b));
   E_CHECK(control_pinned(e, n_inp, n_seq));
-  E_HIP(hipMemcpyAsync(e->h_ctl_ids, a.d_inp, n_inp * 4, hipMemcpyDeviceToHost, e->st));
+  if (Tc == a.T) E_HIP(hipMemcpyAsync(e->h_ctl_ids, a.d_inp, n_inp * 4, hipMemcpyDeviceToHost, e->st));
+  else E_HIP(hipMemcpy2DAsync(e->h_ctl_ids, (size_t)Tc * 4, a.d_inp, (size_t)a.T * 4, (size_t)Tc * 4, a.B, hipMemcpyDeviceToHost, e->st));
   E_HIP(hipMemcpyAsync(e->h_ctl_ids + n_inp, b.cand, n_seq * 4, hipMemcpyDeviceToHost, e->st));
   return 0;
 }
@@ -799,10 +816,11 @@ int control_fetch(czc_engine* e, const StepArgs& a) {
 // after the step's host round trip (the ids have landed) and after the tower's launches have been queued
 int control_score(czc_engine* e, const StepArgs& a) {
   StepBufs b;
-  const size_t n_seq = (size_t)a.B * a.K, n_inp = (size_t)a.B * a.T;
+  const int Tc = a.ctl_T > 0 ? a.ctl_T : a.T;
+  const size_t n_seq = (size_t)a.B * a.K, n_inp = (size_t)a.B * Tc;
   E_CHECK(step_bufs(e, (int)n_seq, &b));
   memset(e->h_ctl_scores, 0, n_seq * 4);
-  const int rc = e->ctl_fn(e->ctl_user, e->h_ctl_ids, e->h_ctl_ids + n_inp, a.B, a.T, a.K, a.gen_idx, e->h_ctl_scores);
+  const int rc = e->ctl_fn(e->ctl_user, e->h_ctl_ids, e->h_ctl_ids + n_inp, a.B, Tc, a.K, a.gen_idx, e->h_ctl_scores);
   if (rc) return fail(e, CZC_ERR_STATE, "the control callback reported an error%s");
   // pinned source: the copy is queued behind the tower; the buffer is next written after the next step's round trip
   E_HIP(hipMemcpyAsync(b.senti, e->h_ctl_scores, n_seq * 4, hipMemcpyHostToDevice, e->st));
@@ -894,7 +912,7 @@ int step_phase_b(czc_engine* e, const StepArgs& a, int M, int max_len, int max_b
 // gen_rows / dot_rows (device, [B]) + gen_rows_host: czc_generate_rows' per-row column and '.' rule (gen_idx = row 0's then)
 int step_device(czc_engine* e, int* d_inp, int B, int T, int gen_idx, int n_mask, int dot_allowed, int K,
                 const czc_hyper* hp, const int* gen_rows = nullptr, const int* dot_rows = nullptr,
-                const int32_t* gen_rows_host = nullptr) {
+                const int32_t* gen_rows_host = nullptr, const Ragged* rag = nullptr, int ctl_T = 0) {
   const czc_config& c = e->cfg;
   if (!e->finalized) return fail(e, CZC_ERR_STATE, "weights not finalized%s");
   if (c.bert_layers <= 0) return fail(e, CZC_ERR_STATE, "this engine was created without the BERT tower%s");
@@ -910,9 +928,10 @@ int step_device(czc_engine* e, int* d_inp, int B, int T, int gen_idx, int n_mask
   if (n_mask <= 0 && (e->last_B != B || e->last_T != T))
     return fail(e, CZC_ERR_STATE, "n_mask=0 needs a previous forward of the same [B,T] shape%s");
   StepArgs a{d_inp, B, T, gen_idx, n_mask, dot_allowed, K, *hp};
-  a.gen_rows = gen_rows; a.dot_rows = dot_rows; a.gen_rows_host = gen_rows_host;
+  a.gen_rows = gen_rows; a.dot_rows = dot_rows; a.gen_rows_host = gen_rows_host; a.rag = rag; a.ctl_T = ctl_T;
+  if (rag && (!gen_rows || !dot_rows || rag->max_T > T || rag->M > B * T)) return fail(e, CZC_ERR_ARG, "step: ragged rows need per-row columns and lengths within T%s");
   E_CHECK(step_phase_a(e, a));
-  if (n_mask > 0) { e->stat_bert_rows += B * T; e->last_BT = B * T; e->last_B = B; e->last_T = T; }
+  if (n_mask > 0) { e->stat_bert_rows += rag ? rag->M : B * T; e->last_BT = B * T; e->last_B = B; e->last_T = T; }
   if (hp->control && e->ctl_fn) E_CHECK(control_fetch(e, a));  // ids for the host scorer ride on the same round trip
   E_HIP(hipStreamSynchronize(e->st));  // the one host round trip per step (the reference has one too, gen_utils.py:81)
   int M, max_len, max_branch, n_trunk;
@@ -1078,6 +1097,14 @@ struct MemoRowsPlan {
   int n_run = 0;  // of the group in progress: rows that are not idle
   int n_act = 0;  // of the group in progress: rows that run (not idle and no hit)
   int branch_max[MEMO_ROWS_SUB] = {0, 0};
+  // czc_generate_rows_len (len_h null otherwise): every row's token count T_r on the host; the full batch's offsets / lengths
+  // and those of every step's run list in the schedule upload (d_rag_steps: [n_steps][2 R + 1], lengths then offsets; null in
+  // a call without idle steps); d_rag_c [2 R + 1]: those of a checked step's compact batch, uploaded after the list read
+  const int32_t* len_h = nullptr;
+  Ragged rag_full{}; const int* d_rag_steps = nullptr; int* d_rag_c = nullptr;
+  Ragged rag_c{};  // of the group in progress, where it runs on a compact batch
+  const Ragged* rag(bool full) const { return len_h ? (full ? &rag_full : &rag_c) : nullptr; }
+  int ctl_T() const { return len_h && !run_h.empty() ? len_h[run_h[0]] : 0; }
 };
 
 // the signature word of memo_rows.hip (mr_sig) as the host keeps it to tell whether a step can hit at all
@@ -1139,7 +1166,7 @@ int memo_rows_begin(czc_engine* e, bool table, int R, int T, int L, int seed_len
   E_CHECK(ensure(e, "mr_dot_c", (size_t)R * 4, (void**)&mp->dot_c));
   if (!table) return 0;
   E_HIP(hipMemsetAsync(m.valid, 0, n_slot * 4, e->st));  // entries live for one call
-  const size_t want = ((size_t)R + 4) * 4;  // the check's totals (16 bytes), then its list
+  const size_t want = ((size_t)R + 4 + 2 * (size_t)R + 1) * 4;  // the check's totals (16 bytes), then its list; then (len mode) the compact batch's lengths and offsets
   if (e->h_memo_list_cap < want) {
     E_HIP(hipStreamSynchronize(e->st));
     if (e->h_memo_list) (void)hipHostFree(e->h_memo_list);
@@ -1203,6 +1230,23 @@ int memo_rows_step(czc_engine* e, MemoRowsPlan& mp, int s, int* d_inp, int R, in
         mp.h_col_c[jj].resize(mp.n_act);
         for (int i = 0; i < mp.n_act; ++i) mp.h_col_c[jj][i] = sched[(size_t)(s0 + jj) * R + mp.run_h[i]];
       }
+      if (mp.len_h) {  // the compact batch's packed rows: the schedule's own for a run list, built here for a checked step's list
+        const bool own = mp.list_d == mp.list;
+        if (!own && !mp.d_rag_steps) return fail(e, CZC_ERR_STATE, "generate_rows_len: a run list without its offsets%s");
+        int32_t* h = own ? e->h_memo_list + 4 + R : nullptr;  // pinned; the previous upload from it was queued in front of this step's list read
+        int M = 0, mx = 0;
+        for (int i = 0; i < mp.n_act; ++i) {
+          const int t = mp.len_h[mp.run_h[i]];
+          if (own) { h[i] = t; h[R + i] = M; }
+          M += t; mx = t > mx ? t : mx;
+        }
+        if (own) {
+          h[R + mp.n_act] = M;
+          E_HIP(hipMemcpyAsync(mp.d_rag_c, h, ((size_t)2 * R + 1) * 4, hipMemcpyHostToDevice, e->st));
+        }
+        const int* base = own ? mp.d_rag_c : mp.d_rag_steps + (size_t)s0 * (2 * R + 1);
+        mp.rag_c = Ragged{base + R, base, M, mx};
+      }
     }
   }
   const int n_act = mp.n_act;
@@ -1217,7 +1261,7 @@ int memo_rows_step(czc_engine* e, MemoRowsPlan& mp, int s, int* d_inp, int R, in
     if (record && j == 0)
       E_CHECK(launch_memo_rows_gather(d_inp, nullptr, R, mp.tab, col0, col1, n_mask0, g, mask_id, 1, col, dot, nullptr, nullptr, D,
                                       nullptr, nullptr, nullptr, e->st));
-    E_CHECK(step_device(e, d_inp, R, T, col_h[0], n_mask, col_h[0] - seed_len == L - 1 ? 1 : 0, K, hp, col, dot, col_h));
+    E_CHECK(step_device(e, d_inp, R, T, col_h[0], n_mask, col_h[0] - seed_len == L - 1 ? 1 : 0, K, hp, col, dot, col_h, mp.rag(true), mp.ctl_T()));
     return launch_memo_rows_scatter(d_inp, (const float*)e->ws["s_bcos"].p, (const int*)e->ws["p_img_max"].p, nullptr, R, mp.tab,
                                     col0, j, record, d_inp, mp.bcos, e->st) ? fail(e, CZC_ERR_HIP, "%s", g_err) : 0;
   }
@@ -1230,7 +1274,7 @@ int memo_rows_step(czc_engine* e, MemoRowsPlan& mp, int s, int* d_inp, int R, in
   const int img_B = e->img_B;
   e->d_img_n = mp.img_c; e->img_B = n_act; e->memo_branch_floor = j < MEMO_ROWS_SUB ? mp.branch_max[j] : 0;
   const int rc = step_device(e, mp.inp_c, n_act, T, col_h[0], n_mask, col_h[0] - seed_len == L - 1 ? 1 : 0, K, hp, mp.col_c, mp.dot_c,
-                             col_h);
+                             col_h, mp.rag(false), mp.ctl_T());
   e->d_img_n = img_rows; e->img_B = img_B; e->memo_branch_floor = 0;
   E_CHECK(rc);
   return launch_memo_rows_scatter(mp.inp_c, (const float*)e->ws["s_bcos"].p, (const int*)e->ws["p_img_max"].p, mp.list_d, n_act,
@@ -1242,7 +1286,7 @@ int memo_rows_step(czc_engine* e, MemoRowsPlan& mp, int s, int* d_inp, int R, in
 // =================================================================================================
 extern "C" {
 
-int czc_version(void) { return 100; }
+int czc_version(void) { return 101; }
 
 const char* czc_last_error(const czc_engine* e) { return e ? e->err : czc::g_err; }
 
@@ -1761,9 +1805,14 @@ int czc_step(czc_engine* e, int32_t* inp, int B, int T, int gen_idx, int n_mask,
 // CZC_POS_IDLE.  A call with idle steps appends the run list of every step to the schedule and takes the compact-batch path of
 // memo_rows_step (with the entries where option "memo_rows" is on, without them otherwise); a call without any runs as
 // czc_generate_rows does.
+// len_rows (czc_generate_rows_len, a from call whose rows differ in length; null otherwise): row r polishes len_rows[r]
+// positions and holds seed_len + len_rows[r] + 1 tokens, T is the stride of the rows and L the longest length (already checked
+// by the caller: lengths within T, tails [PAD]).  The schedule upload then also carries the packed-row offsets and lengths of
+// the full batch and of every step's run list; BERT, the MLM head's row index and the bridge run on them (Ragged).
 static int generate_impl(czc_engine* e, bool rows, bool from, int B, int T, int L, int seed_len, const int32_t* init_ids_host,
                          const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
-                         const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp, int32_t* out_ids, float* out_cos) {
+                         const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp, int32_t* out_ids, float* out_cos,
+                         const int32_t* len_rows = nullptr) {
   if (!e || !init_ids_host || !positions_host || !hp || B <= 0 || n_steps < 0 || snapshot_every <= 0)
     return CZC_ERR_ARG;
   if (seed_len + L > T) return fail(e, CZC_ERR_ARG, "generate: seed_len + L > T%s");
@@ -1771,7 +1820,7 @@ static int generate_impl(czc_engine* e, bool rows, bool from, int B, int T, int 
   e->err[0] = 0;
   const size_t n_pos = rows ? (size_t)n_steps * B : (size_t)n_steps;
   for (size_t i = 0; i < n_pos; ++i)
-    if (positions_host[i] < (from ? CZC_POS_IDLE : 0) || positions_host[i] >= L)
+    if (positions_host[i] < (from ? CZC_POS_IDLE : 0) || positions_host[i] >= L)  // (len mode: checked per row by czc_generate_rows_len)
       return fail(e, CZC_ERR_ARG, from ? "generate_rows_from: position outside {CZC_POS_IDLE} and [0, L)%s" : "generate: position out of range%s");
   bool any_idle = false;
   if (from) {
@@ -1791,6 +1840,7 @@ static int generate_impl(czc_engine* e, bool rows, bool from, int B, int T, int 
       s += g;
     }
   }
+  int rag_M = 0, rag_max = 0;  // len mode: packed rows / longest row of the full batch
   std::vector<int32_t> sched;  // rows: [n_steps][B] columns, then [n_steps][B] '.' rules (utils.py:53-59: position == L-1)
   if (rows) {
     if (B > CZC_MAX_ROWS || seed_len < 0 || T > CZC_MAX_BERT_LEN) return fail(e, CZC_ERR_ARG, "generate_rows: R > CZC_MAX_ROWS, seed_len < 0 or T > CZC_MAX_BERT_LEN%s");
@@ -1803,10 +1853,15 @@ static int generate_impl(czc_engine* e, bool rows, bool from, int B, int T, int 
           return fail(e, CZC_ERR_ARG, "generate_rows: image_of_row outside the resident image batch%s");
     if (e->ctl_fn && hp->control && from) {  // the callback sees the rows that run, compacted: those must share one position
       for (int s = 0; s < n_steps; ++s) {
-        int shared = CZC_POS_IDLE;
+        int shared = CZC_POS_IDLE, first_r = 0;
         for (int r = 0; r < B; ++r) {
           const int p = positions_host[(size_t)s * B + r];
           if (p == CZC_POS_IDLE) continue;
+          // (the length is compared only between rows at one position: a row at another position is refused just below)
+          if (shared != CZC_POS_IDLE && p == shared && len_rows && len_rows[r] != len_rows[first_r])
+            return fail(e, CZC_ERR_ARG, "generate_rows_len: a control callback is told one T, so the rows of a step that are not idle must share one length as well "
+                                        "as one position; use the control tables (czc_set_lexicon / czc_set_lexicon_pos / czc_set_pos)%s");
+          if (shared == CZC_POS_IDLE) first_r = r;
           if (shared != CZC_POS_IDLE && p != shared)
             return fail(e, CZC_ERR_ARG, "generate_rows_from: a control callback carries one gen_idx, so the rows that are not idle must visit the same position at a step; "
                                         "use the control tables (czc_set_lexicon / czc_set_lexicon_pos / czc_set_pos)%s");
@@ -1818,10 +1873,11 @@ static int generate_impl(czc_engine* e, bool rows, bool from, int B, int T, int 
         if (positions_host[i] != positions_host[i - i % B])
           return fail(e, CZC_ERR_ARG, "generate_rows: a control callback carries one gen_idx, so every row must visit the same position at a step; "
                                       "use the control tables (czc_set_lexicon / czc_set_lexicon_pos / czc_set_pos) or one czc_generate call per order%s");
-    sched.resize((any_idle ? 3 : 2) * n_pos);
+    const size_t n_rag = len_rows ? (size_t)(2 * B + 1) * (any_idle ? 1 + n_steps : 1) : 0;
+    sched.resize((any_idle ? 3 : 2) * n_pos + n_rag);
     for (size_t i = 0; i < n_pos; ++i) {
       sched[i] = positions_host[i] == CZC_POS_IDLE && from ? CZC_POS_IDLE : seed_len + positions_host[i];
-      sched[n_pos + i] = positions_host[i] == L - 1 ? 1 : 0;
+      sched[n_pos + i] = positions_host[i] == (len_rows ? len_rows[i % B] : L) - 1 ? 1 : 0;
     }
     if (any_idle)  // the host knows who runs: every step's rows that are not idle, ascending (the tail of a slice is not read)
       for (int s = 0; s < n_steps; ++s) {
@@ -1831,6 +1887,23 @@ static int generate_impl(czc_engine* e, bool rows, bool from, int B, int T, int 
           if (positions_host[(size_t)s * B + r] != CZC_POS_IDLE) list[n++] = r;
         for (; n < B; ++n) list[n] = 0;
       }
+    if (len_rows) {  // [B] lengths then [B + 1] offsets: of the full batch, then (idle calls) of every step's run list
+      int32_t* blk = sched.data() + (any_idle ? 3 : 2) * n_pos;
+      for (int r = 0; r < B; ++r) {
+        blk[r] = seed_len + len_rows[r] + 1;
+        blk[B + r] = rag_M;
+        rag_M += blk[r]; rag_max = blk[r] > rag_max ? blk[r] : rag_max;
+      }
+      blk[2 * B] = rag_M;
+      for (int s = 0; s < n_steps && any_idle; ++s) {
+        int32_t* sb = blk + (size_t)(s + 1) * (2 * B + 1);
+        int n = 0, off = 0;
+        for (int r = 0; r < B; ++r)
+          if (positions_host[(size_t)s * B + r] != CZC_POS_IDLE) { sb[n] = blk[r]; sb[B + n] = off; off += blk[r]; ++n; }
+        sb[B + n] = off;
+        for (int i = n; i < B; ++i) { sb[i] = 0; sb[B + i + 1] = off; }
+      }
+    }
   }
   int *d_inp, *d_row, *d_sched = nullptr;
   { int* flag; E_CHECK(ensure(e, "s_nonfinite", 32, (void**)&flag)); E_HIP(hipMemsetAsync(flag, 0, 32, e->st)); }
@@ -1849,12 +1922,12 @@ static int generate_impl(czc_engine* e, bool rows, bool from, int B, int T, int 
   if (rows) {
     const int D = e->cfg.clip_proj;
     int* d_ior = nullptr; float* img_r = nullptr;
-    if (n_pos) E_CHECK(ensure(e, "g_sched", sched.size() * 4, (void**)&d_sched));
+    if (!sched.empty()) E_CHECK(ensure(e, "g_sched", sched.size() * 4, (void**)&d_sched));
     if (image_of_row_host) {
       E_CHECK(ensure(e, "g_ior", (size_t)B * 4, (void**)&d_ior));
       E_CHECK(ensure(e, "g_img_r", (size_t)B * D * 4, (void**)&img_r));
     }
-    if (n_pos) E_HIP(hipMemcpyAsync(d_sched, sched.data(), sched.size() * 4, hipMemcpyHostToDevice, e->st));
+    if (!sched.empty()) E_HIP(hipMemcpyAsync(d_sched, sched.data(), sched.size() * 4, hipMemcpyHostToDevice, e->st));
     if (image_of_row_host) {
       E_HIP(hipMemcpyAsync(d_ior, image_of_row_host, (size_t)B * 4, hipMemcpyHostToDevice, e->st));
       E_CHECK(launch_gather_rows_f32(img_full, d_ior, B, D, img_r, e->st));
@@ -1884,6 +1957,17 @@ static int generate_impl(czc_engine* e, bool rows, bool from, int B, int T, int 
   const bool memo_rows = rows && (e->memo_rows || any_idle) && n_steps > 0;  // the compact-batch path, with or without entries
   // (a failure here leaves through the exit below, which hands the resident image batch back)
   if (memo_rows) rc = memo_rows_begin(e, e->memo_rows, B, T, L, seed_len, n_steps, positions_host, n_mask_host, snapshot_every, out_cos != nullptr, audit, &mrp);
+  Ragged rag_full{};
+  if (len_rows && d_sched) {
+    const size_t base = (any_idle ? 3 : 2) * n_pos;
+    rag_full = Ragged{d_sched + base + B, d_sched + base, rag_M, rag_max};
+    if (memo_rows && !rc) {
+      mrp.len_h = sched.data() + base;
+      mrp.rag_full = rag_full;
+      mrp.d_rag_steps = any_idle ? d_sched + base + (2 * B + 1) : nullptr;
+      if (ensure(e, "mr_rag_c", ((size_t)2 * B + 1) * 4, (void**)&mrp.d_rag_c)) rc = CZC_ERR_HIP;
+    }
+  }
   // a row that has not run yet in this call reports cosine 0 (the reference's best_clip_score start value)
   if (memo_rows && any_idle && !rc && hipMemsetAsync(mrp.bcos, 0, (size_t)B * 4, e->st) != hipSuccess) rc = fail(e, CZC_ERR_HIP, "generate_rows_from: clearing the cosines%s");
   for (int s = 0; s < n_steps && !rc; ++s) {
@@ -1896,7 +1980,8 @@ static int generate_impl(czc_engine* e, bool rows, bool from, int B, int T, int 
     if (memo_rows) rc = memo_rows_step(e, mrp, s, d_inp, B, T, L, seed_len, nm, n_mask_host ? n_mask_host[mrp.first[s]] : 1, top_k, hp,
                                        sched.data(), d_sched, n_pos);
     else if (rows) rc = step_device(e, d_inp, B, T, seed_len + pos, nm, pos == L - 1 ? 1 : 0, top_k, hp, d_sched + (size_t)s * B,
-                               d_sched + n_pos + (size_t)s * B, sched.data() + (size_t)s * B);
+                               d_sched + n_pos + (size_t)s * B, sched.data() + (size_t)s * B, len_rows ? &rag_full : nullptr,
+                               len_rows ? seed_len + len_rows[0] + 1 : 0);  // (a callback call's rows share one length: checked above)
     else if (memo) rc = memo_step(e, mp, s, d_inp, B, T, seed_len + pos, nm, pos == L - 1 ? 1 : 0, top_k, hp);
     else rc = step_device(e, d_inp, B, T, seed_len + pos, nm, pos == L - 1 ? 1 : 0, top_k, hp);
     if (rc) break;
@@ -1942,6 +2027,37 @@ int czc_generate_rows_from(czc_engine* e, int R, int T, int L, int seed_len, con
                            const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp, int32_t* out_ids, float* out_cos) {
   return generate_impl(e, true, true, R, T, L, seed_len, init_rows_host, image_of_row_host, top_k, n_steps, positions_host, n_mask_host,
                        snapshot_every, hp, out_ids, out_cos);
+}
+
+int czc_generate_rows_len(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
+                          const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
+                          const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp, int32_t* out_ids, float* out_cos) {
+  if (!e || !init_rows_host || !len_of_row_host || !positions_host || !hp || R <= 0 || n_steps < 0 || snapshot_every <= 0)
+    return CZC_ERR_ARG;
+  e->err[0] = 0;
+  if (R > CZC_MAX_ROWS || seed_len < 0 || T > CZC_MAX_BERT_LEN) return fail(e, CZC_ERR_ARG, "generate_rows_len: R > CZC_MAX_ROWS, seed_len < 0 or T > CZC_MAX_BERT_LEN%s");
+  bool uniform = true;
+  int L_max = 0;
+  for (int r = 0; r < R; ++r) {
+    const int Lr = len_of_row_host[r];
+    if (Lr < 1 || Lr > T - seed_len - 1) return fail(e, CZC_ERR_ARG, "generate_rows_len: len_of_row outside [1, T - seed_len - 1]%s");
+    uniform = uniform && seed_len + Lr + 1 == T;
+    L_max = Lr > L_max ? Lr : L_max;
+    for (int t = seed_len + Lr + 1; t < T; ++t)
+      if (init_rows_host[(size_t)r * T + t] != 0) return fail(e, CZC_ERR_ARG, "generate_rows_len: the columns behind a row's seed_len + len_of_row + 1 tokens must hold id 0 ([PAD])%s");
+  }
+  for (int s = 0; s < n_steps; ++s) {
+    const int nm = n_mask_host ? n_mask_host[s] : 1;
+    for (int r = 0; r < R; ++r) {
+      const int p = positions_host[(size_t)s * R + r];
+      if (p < CZC_POS_IDLE || p >= len_of_row_host[r]) return fail(e, CZC_ERR_ARG, "generate_rows_len: position outside {CZC_POS_IDLE} and [0, len_of_row[r])%s");
+      if (p >= 0 && nm > 1 && p + nm > len_of_row_host[r])
+        return fail(e, CZC_ERR_ARG, "generate_rows_len: an n_mask >= 2 step masks past the row's last position (it needs position + n_mask <= len_of_row[r])%s");
+    }
+  }
+  // rows of one length that fill the stride: czc_generate_rows_from itself, bit for bit
+  return generate_impl(e, true, true, R, T, L_max, seed_len, init_rows_host, image_of_row_host, top_k, n_steps, positions_host, n_mask_host,
+                       snapshot_every, hp, out_ids, out_cos, uniform ? nullptr : len_of_row_host);
 }
 
 int czc_set_control_callback(czc_engine* e, czc_control_fn fn, void* user) {

@@ -126,6 +126,16 @@ int launch_mask_positions(int* inp, int B, int T, int gen_idx, int n_mask, int m
 int launch_mask_positions_rows(int* inp, int B, int T, const int* gen, int n_mask, int mask_id, hipStream_t st);
 int launch_broadcast_rows_i32(const int* row, int T, int B, int* dst, hipStream_t st);
 
+// ---- ragged.hip (czc_generate_rows_len: BERT on packed ragged rows) -------------------------------------------------------
+// Sequence b: row_len[b] tokens, packed rows row_off[b] .. (row_off [n + 1], the exclusive scan of row_len [n]; device).
+// BERT embeddings + LN of the first row_len[b] ids of row run[b] (run null: row b) of ids [*, ids_stride] -> packed rows; token t
+// of a sequence takes position embedding t.  max_T >= every row_len.  launch_bert_embed's arithmetic per row.
+int launch_bert_embed_ragged(int prec, const int* ids, int ids_stride, const int* run, const int* row_off, const int* row_len, int n,
+                             int max_T, int H, const float* word, const float* pos, const float* type0, const float* gamma,
+                             const float* beta, float eps, void* y_act, float* y_f32, hipStream_t st);
+// packed rows row_off[b] + gen[b] (gen: device, [n])
+int launch_ragged_row_index(int* idx, int n, const int* row_off, const int* gen, hipStream_t st);
+
 // ---- memo.hip (czc_generate option "memo") --------------------------------------------------------------------------
 // check: hit[b] = (d_inp[b] with columns gen_idx .. gen_idx+n_mask-1 set to mask_id) == key[b]; list = the other images in
 // ascending order; tot[0] = their count, tot[1 + j] = max over the hit images of img_max[j * B + b] (j < n_sub <= 2)
@@ -239,9 +249,11 @@ int launch_bridge(const BridgeDev& bd, const int* inp, int B, int T, int gen_idx
                   const float* lexicon, const float* lex_pos, const uint8_t* lex_cls, int negative, const PosDev& pos, int* clip_ids, int* clip_len, float* senti_raw,
                   float* repeats, int* overflow_flag, hipStream_t st);
 // the same with the substituted column per row of inp: gen_rows[b] (device, [B]) in place of gen_idx (cand must not be null)
+// row_len (device, [B]; czc_generate_rows_len) or null: row b holds row_len[b] tokens; the columns behind them are not read
+// (neither decoded nor counted as repeats of a [PAD] candidate, nor scored)
 int launch_bridge_rows(const BridgeDev& bd, const int* inp, int B, int T, const int* gen_rows, const int* cand, int K,
                        const float* lexicon, const float* lex_pos, const uint8_t* lex_cls, int negative, const PosDev& pos, int* clip_ids, int* clip_len,
-                       float* senti_raw, float* repeats, int* overflow_flag, hipStream_t st);
+                       float* senti_raw, float* repeats, int* overflow_flag, hipStream_t st, const int* row_len = nullptr);
 // exclusive scan of len[n] -> off[n+1]; totals[0] = sum, totals[1] = max
 int launch_scan(const int* len, int n, int* off, int* totals, hipStream_t st);
 // Shared-prefix plan for B images x K candidates (segments: B trunks, then B*K branches):

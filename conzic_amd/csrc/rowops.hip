@@ -5,43 +5,6 @@
 
 namespace czc {
 
-constexpr int LN_MAXV = 4;  // float4 per lane -> H <= 1024
-
-// one wave per row; returns this lane's normalised values in v[]
-template <int NV>
-__device__ __forceinline__ void ln_row(float4 (&v)[NV], int H, int lane, const float* gamma, const float* beta,
-                                       float eps) {
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int c = (i * 64 + lane) * 4;
-    if (c < H) s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-  }
-  const float mean = wave_sum(s) / (float)H;
-  float q = 0.f;
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int c = (i * 64 + lane) * 4;
-    if (c < H) {
-      const float a = v[i].x - mean, b = v[i].y - mean, cc = v[i].z - mean, d = v[i].w - mean;
-      q += (a * a + b * b) + (cc * cc + d * d);
-    }
-  }
-  const float rstd = rsqrtf(wave_sum(q) / (float)H + eps);
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int c = (i * 64 + lane) * 4;
-    if (c < H) {
-      const float4 gm = *(const float4*)(gamma + c);
-      const float4 bt = *(const float4*)(beta + c);
-      v[i].x = (v[i].x - mean) * rstd * gm.x + bt.x;
-      v[i].y = (v[i].y - mean) * rstd * gm.y + bt.y;
-      v[i].z = (v[i].z - mean) * rstd * gm.z + bt.z;
-      v[i].w = (v[i].w - mean) * rstd * gm.w + bt.w;
-    }
-  }
-}
-
 // sum over the wave in the association order of gemm_rowln_kernel's epilogue (gemm256.hip): lane = 8*w + r sums its
 // neighbours r^1, r^2, r^4 first (the 64-column partial of "wave" w there), then w^1, w^2, w^4.
 // Partners 1 .. 16 go through ds_swizzle's bit-mask mode (no address registers): layernorm512_kernel needs 30 VGPRs, one

@@ -55,10 +55,14 @@ def get_args(argv=None):
     p.add_argument("--batch_samples", action="store_true",
                    help="polish the samples_num samples of a batch in ONE engine call (one row per image and sample, every "
                         "sample with the visiting order the sample loop would have drawn for it) instead of one call per sample")
+    p.add_argument("--sentence_lens", type=lambda v: [int(n) for n in v.split(",") if n.strip()], default=None, metavar="L1,L2,...",
+                   help="several sentence lengths of every image in ONE engine call, e.g. 6,8,10,12 (each row at its own length; "
+                        "--order sequential or shuffle): one call per sample, or with --batch_samples one call of samples_num x "
+                        "len(lens) rows per image; --sentence_len is ignored while this is set")
     p.add_argument("--caption", action="append", default=None, metavar="TEMPLATE",
                    help="--run_type infill (repeatable): a caption with blanks, e.g. \"a _ dog on a _\"; only the blanks are "
                         "polished (num_iterations sweeps, --order sequential or shuffle over each caption's blanks), the given "
-                        "words stay as context; all captions go through one engine call per token length")
+                        "words stay as context; all captions, whatever their token lengths, go through one engine call")
     p.add_argument("--infill_positions", default="blanks", choices=["blanks", "all"],
                    help="--run_type infill: polish the blanks only, or every position of every caption (polishing a draft / "
                         "resuming an earlier result)")
@@ -67,6 +71,13 @@ def get_args(argv=None):
         p.error("--run_type infill needs at least one --caption")
     if a.run_type == "infill" and a.order not in ("sequential", "shuffle"):
         p.error("--run_type infill visits the blanks in --order sequential or shuffle")
+    if a.sentence_lens is not None:
+        if a.run_type == "infill":
+            p.error("--sentence_lens does not apply to --run_type infill (a template has its own length)")
+        if not a.sentence_lens or min(a.sentence_lens) < 1:
+            p.error("--sentence_lens needs a comma-separated list of lengths >= 1")
+        if a.run_type == "caption" and a.order not in ("sequential", "shuffle"):
+            p.error("--sentence_lens visits every row's positions in --order sequential or shuffle")
     if a.control_scores:
         os.environ["CZC_CONTROL"] = a.control_scores
     return a
@@ -123,6 +134,19 @@ def main(argv=None):
         infill_captions(args.caption, img_name, lm_model, clip, lm_tokenizer, image_instance, token_mask, logger, prompt=args.prompt,
                         top_k=args.candidate_k, temperature=args.lm_temperature, max_iter=args.num_iterations, alpha=args.alpha,
                         beta=args.beta, generate_order=args.order, positions=args.infill_positions)
+        logger.info("total %.2fs" % (time.time() - t0))
+        return
+    if args.sentence_lens:
+        # all lengths of a sample (with --batch_samples: of all samples) are rows of one engine call
+        from conzic_amd.runtime import caption_lengths
+        kw = dict(prompt=args.prompt, batch_size=args.batch_size, top_k=args.candidate_k, temperature=args.lm_temperature,
+                  max_iter=args.num_iterations, alpha=args.alpha, beta=args.beta, generate_order=args.order, gamma=args.gamma,
+                  ctl_type=args.control_type, style_type=args.sentiment_type, pos_type=args.pos_type)
+        for sample_id in ([None] if args.batch_samples else range(args.samples_num)):
+            if sample_id is not None:
+                logger.info(f"Sample {sample_id}: ")
+            caption_lengths(args.sentence_lens, args.samples_num if args.batch_samples else 1, args.run_type, img_name, lm_model, clip,
+                            lm_tokenizer, image_instance, token_mask, logger, **kw)
         logger.info("total %.2fs" % (time.time() - t0))
         return
     if args.batch_samples:

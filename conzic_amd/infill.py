@@ -1,4 +1,4 @@
-"""Infilling, resume and draft polishing on czc_generate_rows_from (include/conzic_hip.h): host-side parsing and schedules.
+"""Infilling, resume and draft polishing on czc_generate_rows_len (include/conzic_hip.h): host-side parsing and schedules.
 
 ConZIC names infilling as one of its control signals: given "a _ dog sitting on a _", only the blanks are polished and the
 given words stay as context.  The reference's CLI never exposed it, but its loop body (gen_utils.py:66 `inp[:, seed_len+ii] =
@@ -79,12 +79,24 @@ def take_rows(positions: np.ndarray, sweeps: int, rows: Sequence[int]):
 
 
 def group_by_length(parsed: Sequence[Tuple[np.ndarray, List[int], int, int]]) -> Dict[int, List[int]]:
-    """Caption indices grouped by token length T (one engine call per group: a call's rows share T, and with one prompt L), in
-    order of first appearance; the indices of a group ascend."""
+    """Caption indices grouped by token length T, in order of first appearance; the indices of a group ascend.  The order in which
+    run_infill logs and returns its captions (it was one engine call per group before czc_generate_rows_len; the call's rows are
+    now those of group_for_call)."""
     groups: Dict[int, List[int]] = {}
     for i, (ids, _, _, _) in enumerate(parsed):
         groups.setdefault(int(len(ids)), []).append(i)
     return groups
+
+
+def group_for_call(parsed: Sequence[Tuple[np.ndarray, List[int], int, int]]) -> Dict[int, List[int]]:
+    """The captions of one engine call, keyed by the call's row stride: ONE group with every caption in caption order under the
+    longest token length (czc_generate_rows_len gives each row its own length, so token lengths no longer split a call).  The
+    captions must share seed_len (one prompt)."""
+    if not parsed:
+        return {}
+    if len({int(p[3]) for p in parsed}) != 1:
+        raise ValueError("group_for_call: the captions of a call share one prompt (seed_len)")
+    return {max(int(len(p[0])) for p in parsed): list(range(len(parsed)))}
 
 
 def visit_lists(parsed, positions: str = "blanks") -> List[List[int]]:

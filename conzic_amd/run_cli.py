@@ -92,9 +92,68 @@ def batched_samples(args, run_type, all_batches, own_lo, own_hi, rank, world, im
             write_results(result_dir(args, run_type, sample_id), all_results)
 
 
+def lengths_batches(args, run_type, all_batches, own_lo, own_hi, rank, world, img_dir, lm_model, clip, lm_tokenizer, token_mask,
+                    logger):
+    """--sentence_lens: every batch polishes all lengths of a sample in one engine call (runtime.caption_lengths), or with
+    --batch_samples all lengths of all its samples; the images are encoded once per batch.  The orders are drawn as that loop
+    draws them -- samples outside and batches inside (with --batch_samples: batch by batch), lengths then samples inside a call --
+    and a rank draws those of the batches it does not own as well.  The files are written per length and sample in the layout of
+    a --sentence_len run at that length."""
+    import copy
+    from PIL import Image
+    from clip.clip import ImageEmbeds
+    from conzic_amd.runtime import advance_order_rng, caption_lengths, caption_order
+    S, lens = args.samples_num, args.sentence_lens
+    per_call = S if args.batch_samples else 1
+    order, _ = caption_order(args.run_type, args.order, args.control_type, args.num_iterations, max(lens))
+    results = [[[None] * (args.num_iterations + 1) for _ in range(S)] for _ in lens]
+    embed_cache = {}
+    for sample_id in ([None] if args.batch_samples else range(S)):
+        if sample_id is not None:
+            logger.info(f"Sample {sample_id + 1}: ")
+        for batch_idx, name_batch in enumerate(all_batches):
+            if not (own_lo <= batch_idx < own_hi):
+                for n in lens:
+                    for _ in range(per_call):
+                        advance_order_rng(order, n, args.num_iterations)
+                continue
+            logger.info(f"The {batch_idx + 1}-th batch:")
+            if batch_idx in embed_cache:
+                imgs = ImageEmbeds(embed_cache[batch_idx])
+            else:
+                imgs = [Image.open(os.path.join(img_dir, n)).convert("RGB") for n in name_batch]
+            outs = caption_lengths(lens, per_call, args.run_type, name_batch, lm_model, clip, lm_tokenizer, imgs, token_mask, logger,
+                                   prompt=args.prompt, batch_size=args.batch_size, top_k=args.candidate_k,
+                                   temperature=args.lm_temperature, max_iter=args.num_iterations, alpha=args.alpha, beta=args.beta,
+                                   generate_order=args.order, gamma=args.gamma, ctl_type=args.control_type,
+                                   style_type=args.sentiment_type, pos_type=args.pos_type)
+            if batch_idx not in embed_cache:
+                embed_cache[batch_idx] = clip.last_image_embeds()
+            for l, per_sample in enumerate(outs):
+                for s, (gen_texts, _) in enumerate(per_sample):
+                    sid = s if sample_id is None else sample_id
+                    results[l][sid] = merge_results(results[l][sid], gen_texts, name_batch)
+    for l, n in enumerate(lens):
+        at_len = copy.copy(args)
+        at_len.sentence_len = n
+        for sample_id in range(S):
+            all_results = results[l][sample_id]
+            if world > 1:
+                import torch.distributed as tdist
+                parts = [None] * world
+                tdist.all_gather_object(parts, all_results)
+                all_results = [None] * (args.num_iterations + 1)
+                for part in parts:  # rank order == batch order
+                    for it, d in enumerate(part):
+                        if d is not None:
+                            all_results[it] = {**(all_results[it] or {}), **d}
+            if rank == 0:
+                write_results(result_dir(at_len, run_type, sample_id), all_results)
+
+
 def infill_batches(args, all_batches, own_lo, own_hi, rank, world, img_dir, lm_model, clip, lm_tokenizer, token_mask, logger):
-    """--run_type infill: every --caption template is infilled for every image of a batch, all of them rows of one engine call
-    per token length (runtime.run_infill); the images are encoded once per batch.  One pass (sample_0): iter_<k>.json holds the
+    """--run_type infill: every --caption template is infilled for every image of a batch, all of them rows of one engine
+    call (runtime.run_infill); the images are encoded once per batch.  One pass (sample_0): iter_<k>.json holds the
     captions after sweep k, keyed by image name (`name#c` for template c when there are several)."""
     from PIL import Image
     from conzic_amd.runtime import infill_captions
@@ -195,6 +254,10 @@ def main(argv=None):
     embed_cache = {}  # batch index -> image_embeds [B, proj]: the ViT runs once per image, not once per sample
     if args.run_type == "infill":
         infill_batches(args, all_batches, own_lo, own_hi, rank, world, img_dir, lm_model, clip, lm_tokenizer, token_mask, logger)
+        return
+    if args.sentence_lens:
+        lengths_batches(args, run_type, all_batches, own_lo, own_hi, rank, world, img_dir, lm_model, clip, lm_tokenizer, token_mask,
+                        logger)
         return
     if args.batch_samples:
         batched_samples(args, run_type, all_batches, own_lo, own_hi, rank, world, img_dir, lm_model, clip, lm_tokenizer,

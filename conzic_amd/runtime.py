@@ -463,6 +463,101 @@ def run_generation_samples(order: str, samples_num: int, img_name, model, clip, 
     return out
 
 
+def run_generation_lengths(order: str, lens: Sequence[int], samples_num: int, img_name, model, clip, tokenizer, image_instance,
+                           token_mask, prompt, logger, top_k, temperature, alpha, beta, max_iters, batch_size, verbose=True,
+                           gamma=None, ctl_signal="positive", pos_template=None):
+    """The loop over sentence lengths around the sample loop (one CLI run per --sentence_len) as ONE engine call: `samples_num`
+    samples at each length of `lens` of a batch of `batch_size` images ride as len(lens) * samples_num * batch_size rows of
+    czc_generate_rows_len, row (l * samples_num + s) * batch_size + b = sample s at lens[l] of image b, at its own length
+    (lengths.length_rows: no row reads another's padding) and with the visiting order the serial loop -- lengths outside, samples
+    inside -- would have drawn for it (lengths.length_schedules: one draw per length and sample from the process-global stream);
+    the images are encoded once.  `order` is sequential or shuffle, `max_iters` the number of sweeps.  Returns, per length, a list
+    of `samples_num` (gen_texts_list, clip_score_sequence) pairs, each as the `run_generation` call at that length returns it, and
+    logs every call's lines in the serial loop's order.  The reference's own sentence scorer (exact control mode) is told one
+    position and one row length per step: with it the engine is called once per length and sample, as the serial loop calls it
+    (same orders, same results, the images still encoded once), and the log says why."""
+    import utils as ref_utils
+    from . import lengths
+    lens = [int(n) for n in lens]
+    S, B, NL = int(samples_num), int(batch_size), len(lens)
+    if S < 1 or B < 1:
+        raise ValueError(f"run_generation_lengths: samples_num = {S} and batch_size = {B} must be >= 1")
+    seed_len = len(prompt.split()) + 1
+    col_lens = [n for n in lens for _ in range(S)]                            # column l * S + s: sample s at lens[l]
+    positions, n_mask, every = lengths.length_schedules(col_lens, order, max_iters)   # (validates lens and order, draws the orders)
+    eng = get_engine(model, clip, tokenizer)
+    clip.compute_image_representation_from_image_instance(image_instance)   # once per image, whatever the lengths and samples
+    if getattr(eng, "_precision_logged", None) is None:
+        scale = _logit_scale_of(clip)
+        logger.info(f"engine precision: {PRECISION_NAMES.get(eng.precision, eng.precision)}"
+                    + (f" (exp(logit_scale) = {math.exp(scale):.1f})" if scale is not None else ""))
+        eng._precision_logged = True
+    col_rows = lengths.length_rows(tokenizer, prompt, col_lens)
+    init_rows = np.ascontiguousarray(np.repeat(col_rows, B, axis=0))
+    row_lens = np.repeat(np.asarray(col_lens, dtype=np.int32), B)
+    rows_pos = np.ascontiguousarray(np.repeat(positions, B, axis=1))
+    image_of_row = np.tile(np.arange(B, dtype=np.int32), NL * S)
+    T = init_rows.shape[1]
+    hp = Engine.hyper(alpha, beta, temperature, gamma, ctl_signal == "negative",
+                      control="pos" if pos_template is not None else None)
+
+    def polish(eng):
+        eng.set_token_mask(_mask_to_numpy(token_mask))
+        eng.set_option("memo", memo_setting())  # for the one-call-per-sample arm below; a rows call ignores it
+        eng.set_option("memo_rows", memo_rows_setting())  # per-row step memo of the rows call (CZC_MEMO_ROWS)
+        chosen = None
+        if gamma is not None:
+            from . import control
+            chosen = control.configure(eng, clip, tokenizer, pos_template=pos_template, ctl_signal=ctl_signal)
+            if chosen != getattr(eng, "_control_logged", None):
+                logger.info(f"control scores: {chosen}")
+                eng._control_logged = chosen
+        # the exact control scorer (a callback with ONE gen_idx and ONE row length per step) cannot serve mixed rows
+        one_by_one = gamma is not None and chosen == "exact" and (len(set(lens)) > 1 or bool((positions != positions[:, :1]).any()))
+        if one_by_one and not getattr(eng, "_one_by_one_lengths_logged", False):
+            logger.info("sentence lengths: the exact control scorer is called with one position and one length per step; running "
+                        f"the {NL * S} length/sample pairs one call at a time (CZC_CONTROL=table batches them)")
+            eng._one_by_one_lengths_logged = True
+        runner = _group_for(eng, B if one_by_one else B * S * NL)
+        emb = None
+        if runner is not eng:
+            from clip.clip import ImageEmbeds
+            emb = image_instance.embeds if isinstance(image_instance, ImageEmbeds) else clip.last_image_embeds()
+            runner.set_image_embeds(emb)
+        if eng.precision == native.PREC_REFINE:
+            runner.refine_guard(reset=True)
+        if one_by_one:
+            ids = np.zeros((max_iters, NL * S * B, T), dtype=np.int32)
+            cos = np.zeros((max_iters, NL * S * B), dtype=np.float32)
+            for c, n in enumerate(col_lens):
+                own = positions.reshape(max_iters, every, NL * S)[:, :n, c].reshape(-1).tolist()   # the column without its idle steps
+                i1, c1 = runner.generate(B, col_rows[c, :seed_len + n + 1].tolist(), n, seed_len, top_k, own, hp, snapshot_every=n)
+                ids[:, c * B:(c + 1) * B, :seed_len + n + 1], cos[:, c * B:(c + 1) * B] = i1, c1
+            out = (ids, cos)
+        else:
+            out = runner.generate_rows_len(init_rows, row_lens, seed_len, top_k, rows_pos, hp, image_of_row=image_of_row,
+                                           n_mask=n_mask, snapshot_every=every)
+        if runner is not eng:
+            eng.set_image_embeds(emb)
+        return out, runner
+
+    ids, cos = _polish_guarded(polish, eng, model, clip, tokenizer, image_instance, logger)
+    if positions.shape[0]:   # the caller's mask as after the LAST call's last position: the last sample at the last length
+        n = col_lens[-1]
+        ref_utils.update_token_mask(tokenizer, token_mask, n, int(positions[(max_iters - 1) * every + n - 1, -1]))
+    out = []
+    for l, n in enumerate(lens):
+        per_sample = []
+        for s in range(S):
+            c = l * S + s
+            if order == "shuffle":
+                logger.info(f"Order_list:{[int(p) for p in positions[:n, c]]}")
+            per_sample.append(_bookkeeping(order, ids[:, c * B:(c + 1) * B, :seed_len + n + 1], cos[:, c * B:(c + 1) * B], tokenizer,
+                                           img_name, logger, B, verbose, None))
+        out.append(per_sample)
+    return out
+
+
 def run_infill(captions: Sequence[str], img_name, model, clip, tokenizer, image_instance, token_mask, prompt, logger, *,
                order: str = "sequential", max_iters: int = 10, top_k: int = 200, temperature=0.1, alpha=0.02, beta=2.0,
                positions: str = "blanks", image_of_caption: Optional[Sequence[int]] = None, blank: str = "_", verbose=True):
@@ -470,10 +565,11 @@ def run_infill(captions: Sequence[str], img_name, model, clip, tokenizer, image_
     caption of `captions` is a template whose `blank` words are polished while the given words stay as context
     (`positions="blanks"`), or a draft / earlier result of which every position is polished again (`positions="all"`: nothing is
     idle).  Caption i describes image image_of_caption[i] of `image_instance` (None: caption i = image i, or all captions the
-    one image).  The images are encoded once; the captions are grouped by token length and each group is ONE
-    czc_generate_rows_from call, its rows with their own start rows and visiting orders (infill.infill_schedules, drawn for all
-    captions in caption order before the first call), a caption with fewer blanks sitting out the rest of every sweep.
-    `max_iters` sweeps; honours CZC_MEMO_ROWS.  Returns one (gen_texts_list, clip_score_sequence) pair per caption, in the
+    one image).  The images are encoded once and all captions, whatever their token lengths, are the rows of ONE
+    czc_generate_rows_len call, each at its own length (a shorter caption's padding is never read) with its own start row and
+    visiting order (infill.infill_schedules, drawn in caption order), a caption with fewer blanks sitting out the rest of every
+    sweep.  Logs, results and the token mask keep the order of infill.group_by_length (captions of one token length together,
+    lengths in order of first appearance).  `max_iters` sweeps; honours CZC_MEMO_ROWS.  Returns one (gen_texts_list, clip_score_sequence) pair per caption, in the
     structure a *_generation call returns for a batch of one.  The caller's token_mask is left as after the last visited
     position (utils.py:53-59)."""
     import utils as ref_utils
@@ -500,43 +596,48 @@ def run_infill(captions: Sequence[str], img_name, model, clip, tokenizer, image_
         eng._precision_logged = True
     parsed = [infill.parse_template(tokenizer, prompt, c, blank=blank) for c in captions]
     visits = infill.visit_lists(parsed, positions)
-    groups = infill.group_by_length(parsed)
-    # all orders first, in caption order (one draw per caption from the process-global stream for `shuffle`), so that a
-    # caption's order does not depend on how the captions group
-    pos_all, _, _ = infill.infill_schedules(visits, order, max_iters)
+    (T, members), = infill.group_for_call(parsed).items()   # every caption, in caption order: one call
+    # one draw per caption from the process-global stream for `shuffle`, in caption order
+    pos_all, n_mask, every = infill.infill_schedules(visits, order, max_iters)
     if order == "shuffle":
         for i, v in enumerate(visits):
             logger.info(f"Order_list:{[int(p) for p in pos_all[:len(v), i]]}")
     hp = Engine.hyper(alpha, beta, temperature)
+    seed_len = parsed[0][3]
+    init_rows = np.zeros((len(members), T), dtype=np.int32)   # id 0 ([PAD]) behind a shorter caption's [SEP]
+    for i in members:
+        init_rows[i, :parsed[i][0].size] = parsed[i][0]
+    row_lens = np.asarray([parsed[i][2] for i in members], dtype=np.int32)
+    image_of_row = np.asarray(ioc, dtype=np.int32)
+
+    def polish(eng):
+        eng.set_token_mask(_mask_to_numpy(token_mask))
+        eng.set_option("memo_rows", memo_rows_setting())  # per-row step memo (CZC_MEMO_ROWS); an idle step is not a visit
+        runner = _group_for(eng, len(members))
+        if runner is not eng:
+            runner.set_image_embeds(emb)
+        if eng.precision == native.PREC_REFINE:
+            runner.refine_guard(reset=True)
+        if int(row_lens.min()) == int(row_lens.max()):   # one token length: czc_generate_rows_from, as before there were lengths
+            res = runner.generate_rows_from(init_rows, int(row_lens[0]), seed_len, top_k, pos_all, hp, image_of_row=image_of_row,
+                                            n_mask=n_mask, snapshot_every=every)
+        else:
+            res = runner.generate_rows_len(init_rows, row_lens, seed_len, top_k, pos_all, hp, image_of_row=image_of_row,
+                                           n_mask=n_mask, snapshot_every=every)
+        if runner is not eng:
+            eng.set_image_embeds(emb)
+        return res, runner
+
+    ids, cos = _polish_guarded(polish, eng, model, clip, tokenizer, ImageEmbeds(emb), logger)
     out = [None] * len(captions)
     last = None
-    for T, members in groups.items():
-        L, seed_len = parsed[members[0]][2], parsed[members[0]][3]
-        pos, n_mask, every = infill.take_rows(pos_all, max_iters, members)
-        init_rows = np.stack([parsed[i][0] for i in members]).astype(np.int32)
-        image_of_row = np.asarray([ioc[i] for i in members], dtype=np.int32)
-
-        def polish(eng, init_rows=init_rows, L=L, seed_len=seed_len, pos=pos, n_mask=n_mask, every=every,
-                   image_of_row=image_of_row, R=len(members)):
-            eng.set_token_mask(_mask_to_numpy(token_mask))
-            eng.set_option("memo_rows", memo_rows_setting())  # per-row step memo (CZC_MEMO_ROWS); an idle step is not a visit
-            runner = _group_for(eng, R)
-            if runner is not eng:
-                runner.set_image_embeds(emb)
-            if eng.precision == native.PREC_REFINE:
-                runner.refine_guard(reset=True)
-            res = runner.generate_rows_from(init_rows, L, seed_len, top_k, pos, hp, image_of_row=image_of_row, n_mask=n_mask,
-                                            snapshot_every=every)
-            if runner is not eng:
-                eng.set_image_embeds(emb)
-            return res, runner
-
-        ids, cos = _polish_guarded(polish, eng, model, clip, tokenizer, ImageEmbeds(emb), logger)
-        lv = infill.last_visited(pos)
+    for same_len in infill.group_by_length(parsed).values():   # the order of the logs and of the mask's last visit
+        lv = infill.last_visited(pos_all[:, same_len])
         if lv is not None:
-            last = (L, lv)
-        for k, i in enumerate(members):
-            out[i] = _bookkeeping(order, ids[:, k:k + 1], cos[:, k:k + 1], tokenizer, [img_name[ioc[i]]], logger, 1, verbose, None)
+            last = (parsed[same_len[0]][2], lv)
+        for i in same_len:
+            out[i] = _bookkeeping(order, ids[:, i:i + 1, :parsed[i][0].size], cos[:, i:i + 1], tokenizer, [img_name[ioc[i]]], logger,
+                                  1, verbose, None)
     if last is not None:
         ref_utils.update_token_mask(tokenizer, token_mask, last[0], last[1])
     return out
@@ -598,4 +699,38 @@ def caption_samples(samples_num: int, run_type: str, img_name, model, clip, toke
             logger.info(f"The {i + 1}-th image: {img_name[i]}")
             logger.info(f"final caption: {generate_texts[-2][i]}")
             logger.info(f"best caption: {generate_texts[-1][i]}")
+    return outs
+
+
+def caption_lengths(lens: Sequence[int], samples_num: int, run_type: str, img_name, model, clip, tokenizer, image_instance, token_mask,
+                    logger, *, prompt="", batch_size=1, top_k=100, temperature=1.0, max_iter=500, alpha=0.7, beta=1,
+                    generate_order="sequential", gamma=5, ctl_type="sentiment", style_type="positive", pos_type=None):
+    """`--sentence_lens` of the two CLIs: what `samples_num` calls of generate_caption (run_type 'caption') or
+    control_generate_caption at max_len = n return for every n of `lens`, from one run_generation_lengths call.  Returns, per
+    length, the list of `samples_num` (generate_texts, clip_scores) pairs and logs every length's and sample's final and best
+    captions as those functions do.  The visiting order is sequential or shuffle (a caption run's `random` and `span` orders
+    have no per-length schedule: ValueError)."""
+    start_time = time.time()
+    kw = dict(verbose=True)
+    lens = [int(n) for n in lens]
+    if not lens:
+        raise ValueError("caption_lengths: no sentence lengths given")
+    order, max_iters = caption_order(run_type, generate_order, ctl_type, max_iter, max(lens))
+    if order not in ("sequential", "shuffle"):
+        raise ValueError(f"sentence lengths in one call need generate_order sequential|shuffle, got {generate_order!r}")
+    if run_type != "caption" and ctl_type == "sentiment":
+        kw.update(gamma=gamma, ctl_signal=style_type)
+    elif run_type != "caption":
+        logger.info(pos_type)
+        kw.update(gamma=gamma, pos_template=pos_type)
+    outs = run_generation_lengths(order, lens, samples_num, img_name, model, clip, tokenizer, image_instance, token_mask, prompt,
+                                  logger, top_k, temperature, alpha, beta, max_iters, batch_size, **kw)
+    logger.info("Finished %d lengths x %d samples in %.3fs" % (len(lens), samples_num, time.time() - start_time))
+    for n, per_sample in zip(lens, outs):
+        for sample_id, (generate_texts, _) in enumerate(per_sample):
+            logger.info(f"Sentence length {n}, sample {sample_id}: ")
+            for i in range(batch_size):
+                logger.info(f"The {i + 1}-th image: {img_name[i]}")
+                logger.info(f"final caption: {generate_texts[-2][i]}")
+                logger.info(f"best caption: {generate_texts[-1][i]}")
     return outs

@@ -322,6 +322,34 @@ int czc_generate_rows_from(czc_engine* e, int R, int T, int L, int seed_len, con
                            const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
                            const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp, int32_t* out_ids, float* out_cos);
 
+/* czc_generate_rows_from with a SENTENCE LENGTH per row: captions of different lengths (the reference's --sentence_len, one value
+ * per call there) polished in one batch.  Everything not named here is as in czc_generate_rows_from.
+ *   - layout: T is the row stride of init_rows / out_ids.  Row r has L_r = len_of_row[r] positions and T_r = seed_len + L_r + 1
+ *     tokens ([CLS] prompt, L_r words, [SEP]); columns T_r .. T-1 must hold id 0 ([PAD]) and hold 0 in every snapshot.
+ *   - what a row computes: BERT reads exactly the T_r tokens of row r at position embeddings 0 .. T_r-1 and attends over T_r
+ *     keys (the reference calls BERT without an attention mask, so padding inside a sequence would be attended to: a shorter
+ *     caption runs at its own length instead).  BERT runs on the packed sum of T_r rows of the rows that take part in a step.
+ *     The '.' rule of row r is position == L_r - 1; positions lie in {CZC_POS_IDLE} and [0, L_r); a step with n_mask >= 2 at
+ *     position p needs p + n_mask <= L_r.
+ *   - nothing that reads a row sees its padding: the text bridge (decoding, the repeat count of a candidate the token mask
+ *     turned into [PAD], the sentiment sum and the POS word count) stops at T_r.
+ *   - rows are independent: row r returns what a czc_generate_rows_from call at T = T_r, L = L_r returns for it, under the
+ *     caveats stated there for compact batches -- the form of BERT's GEMMs depends on the packed row count and CZC_PREC_SPLIT's
+ *     tower picks kernels by row count, so ids agree and winner cosines may differ in the last bits (1e-6).
+ *   - a call whose rows all have T_r == T takes czc_generate_rows_from's path and returns its bits.
+ *   - option "memo_rows" applies unchanged (rows are compared over the stride T); idle steps, image_of_row and the control
+ *     tables work as in czc_generate_rows_from.  The offsets of the full batch and of every step's run list travel with the
+ *     one schedule upload; those of a "memo_rows" compact batch are derived on the host from the list it already reads and
+ *     uploaded: no device-to-host read beyond czc_generate_rows_from's in either case.
+ *   - control callback with czc_hyper.control != 0: accepted only if the rows of a step that are not idle share one position
+ *     AND one length; the callback is then told T = T_r and sees the rows' first T_r columns.  Otherwise CZC_ERR_ARG.
+ *   - czc_stats' bert_rows counts the sum of T_r over the rows that ran.
+ * Checked before any GPU work, CZC_ERR_ARG, and the engine stays usable: len_of_row[r] outside [1, T - seed_len - 1], a position
+ * >= L_r, a non-zero id in a row's tail, the n_mask >= 2 overrun, and everything czc_generate_rows_from checks. */
+int czc_generate_rows_len(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
+                          const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
+                          const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp, int32_t* out_ids, float* out_cos);
+
 /* Engine options (all are exact work reductions / kernel choices; results agree within the engine precision):
  *   "share_prefix"    (1) encode the causal prefix common to an image's K candidates once per step instead of K
  *                         times

@@ -14,7 +14,14 @@ The rows call with the per-row step memo (option "memo_rows") off and on, on the
 a trained-like MLM head, rows settle after a few sweeps), one image x S rows, bf16 and screen-then-refine engines.  Per (engine,
 S): wall times of --reps alternating off / on calls after one warm-up of each, their spread ((max - min) / median), the hit
 fraction (czc_memo_rows_stats) and whether ids and cosines agree.  --off_only never touches the option: the option-off arm
-alone, e.g. on a library built from another commit (CZC_LIB_PATH) for an A/B of the unchanged path."""
+alone, e.g. on a library built from another commit (CZC_LIB_PATH) for an A/B of the unchanged path.
+
+    python tools/rows_probe.py --lengths 6,8,10,12 [--reps 5] [--out profiles/r09_lengths_probe.json]
+
+One image at several sentence lengths: the serial loop (one czc_generate call at batch size 1 per length) against one
+czc_generate_rows_len call with one row per length, every row under its own shuffle order (lengths.length_schedules).  Full-size
+towers, both logit scales; per scale the wall times of --reps alternating serial / one-call repetitions after one warm-up of
+each, their spread, whether the one call was faster in every repetition and whether every sweep's ids agree row for row."""
 import argparse
 import json
 import os
@@ -39,9 +46,12 @@ ap.add_argument("--scales", type=float, nargs="+", default=[2.6592, 4.6052])
 ap.add_argument("--out", default=None)
 ap.add_argument("--memo_rows", action="store_true", help="the memo_rows leg instead of the serial / rows comparison")
 ap.add_argument("--off_only", action="store_true", help="--memo_rows: time the option-off arm only and leave the option alone")
+ap.add_argument("--lengths", type=lambda v: [int(n) for n in v.split(",")], default=None, metavar="L1,L2,...",
+                help="the lengths leg: one call per length against one czc_generate_rows_len call")
 args = ap.parse_args()
 if args.out is None:
-    args.out = os.path.join(ROOT, "profiles", "r09_memo_rows_probe.json" if args.memo_rows else "r08_rows_probe.json")
+    args.out = os.path.join(ROOT, "profiles", "r09_lengths_probe.json" if args.lengths else
+                            "r09_memo_rows_probe.json" if args.memo_rows else "r08_rows_probe.json")
 
 L, K, SEED_LEN = args.L, args.K, 4
 out = []
@@ -90,9 +100,54 @@ def memo_rows_leg():
         eng.close()
 
 
+def lengths_leg():
+    from conzic_amd import lengths
+    lens = args.lengths
+    for scale in args.scales:
+        prec = runtime.choose_precision(scale)
+        su = harness.build_synthetic(False, prec, logit_scale=scale, regular_only=True)
+        eng = su.engine
+        eng.set_image_embeds(np.random.default_rng(100).standard_normal((1, su.clip_cfg.proj)).astype(np.float32))
+        hp = Engine.hyper(0.02, 2.0, 0.1)
+        init = lengths.length_rows(su.bert_tok, "Image of a", lens)
+        random.seed(42)
+        positions, n_mask, every = lengths.length_schedules(lens, "shuffle", args.sweeps)
+        own = [positions.reshape(args.sweeps, every, len(lens))[:, :n, r].reshape(-1).tolist() for r, n in enumerate(lens)]
+
+        def serial():
+            return [eng.generate(1, init[r, :SEED_LEN + n + 1].tolist(), n, SEED_LEN, K, own[r], hp, snapshot_every=n)
+                    for r, n in enumerate(lens)]
+
+        def one_call():
+            return eng.generate_rows_len(init, lens, SEED_LEN, K, positions, hp, image_of_row=[0] * len(lens), n_mask=n_mask,
+                                         snapshot_every=every)
+
+        ref, got = serial(), one_call()  # warm-up (workspace growth) and the comparison
+        same = all(np.array_equal(ref[r][0][:, 0], got[0][:, r, :SEED_LEN + n + 1]) for r, n in enumerate(lens))
+        cos_diff = max(float(np.abs(ref[r][1][:, 0] - got[1][:, r]).max()) for r in range(len(lens)))
+        t_serial, t_one = [], []
+        for _ in range(args.reps):
+            for fn, acc in ((serial, t_serial), (one_call, t_one)):
+                eng.sync()
+                t0 = time.perf_counter()
+                fn()
+                acc.append(time.perf_counter() - t0)
+        rec = dict(logit_scale=scale, precision=runtime.PRECISION_NAMES[prec], lengths=lens, K=K, sweeps=args.sweeps, order="shuffle",
+                   images=1, wall_s_serial=t_serial, wall_s_one_call=t_one, spread_serial=spread(t_serial), spread_one_call=spread(t_one),
+                   speedup_median=float(np.median(t_serial) / np.median(t_one)),
+                   speedup_min=min(a / b for a, b in zip(t_serial, t_one)), speedup_max=max(a / b for a, b in zip(t_serial, t_one)),
+                   one_call_faster_in_every_rep=all(b < a for a, b in zip(t_serial, t_one)), ids_identical=bool(same),
+                   cos_max_abs_diff=cos_diff)
+        print(json.dumps(rec), flush=True)
+        out.append(rec)
+        eng.close()
+
+
 if args.memo_rows:
     memo_rows_leg()
-for scale in ([] if args.memo_rows else args.scales):
+elif args.lengths:
+    lengths_leg()
+for scale in ([] if args.memo_rows or args.lengths else args.scales):
     prec = runtime.choose_precision(scale)
     su = harness.build_synthetic(False, prec, logit_scale=scale, regular_only=True)
     eng = su.engine

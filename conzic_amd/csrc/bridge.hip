@@ -43,11 +43,15 @@ __device__ __forceinline__ bool merge_lookup(const BridgeDev& bd, int l, int r, 
 
 // ROWS: the substituted column is the row's own (gen_rows[b], czc_generate_rows).  One thread serves one candidate row and a
 // wave can span several rows of inp (K need not be a multiple of 64), so the column is a per-thread value, not a wave-uniform one
-template <bool ROWS>
+// HP (czc_generate_rows_hp): the control signal is the row's own (hp_rows[b]).  The launch carries every table; the thread keeps
+// the ones its row's control reads and drops the others, so the loop below is the scalar form's: its branches test per-thread
+// pointers exactly as they do there, and they diverge only in a wave that spans rows under different signals (K = 200: one
+// wave in three).  A control == 0 row writes neither senti_raw nor repeats (its combine work-group reads neither).
+template <bool ROWS, bool HP>
 __global__ __launch_bounds__(BR_THREADS) void bridge_kernel(BridgeDev bd, const int* inp, int B, int T, int gen_idx_, const int* gen_rows,
-                                                            const int* row_len, const int* cand, int K, const float* lexicon, const float* lex_pos,
-                                                            const uint8_t* lex_cls, int negative, PosDev pos, int* clip_ids, int* clip_len, float* senti_raw,
-                                                            float* repeats, int* overflow) {
+                                                            const int* row_len, const int* cand, int K, const float* lexicon_, const float* lex_pos_,
+                                                            const uint8_t* lex_cls, int negative_, const RowHyper* hp_rows, PosDev pos_, int* clip_ids,
+                                                            int* clip_len, float* senti_raw_, float* repeats_, int* overflow) {
   extern __shared__ __attribute__((aligned(16))) unsigned char br_lds[];
   unsigned char* txt = br_lds + (size_t)threadIdx.x * BR_MAXB;
   unsigned char* cls = br_lds + (size_t)BR_THREADS * BR_MAXB + (size_t)threadIdx.x * BR_MAXB;
@@ -66,6 +70,14 @@ __global__ __launch_bounds__(BR_THREADS) void bridge_kernel(BridgeDev bd, const 
   const int cid = cand ? cand[row] : -1;
   const int gen_idx = ROWS ? gen_rows[b] : gen_idx_;
   const int n_tok = ROWS && row_len ? row_len[b] : T;  // czc_generate_rows_len: the row's own length, its padding tail is not read
+  const int ctl = HP ? hp_rows[b].control : 0;
+  const float* lexicon = HP && ctl != 1 ? nullptr : lexicon_;
+  const float* lex_pos = HP && ctl != 1 ? nullptr : lex_pos_;
+  const int negative = HP ? hp_rows[b].negative : negative_;
+  PosDev pos = pos_;
+  if (HP && ctl != 2) pos.tag_of_token = nullptr;
+  float* senti_raw = HP && ctl == 0 ? nullptr : senti_raw_;
+  float* repeats = HP && ctl == 0 ? nullptr : repeats_;
 
   // ---- 1. decode to bytes ------------------------------------------------------------------
   int n = 0;
@@ -221,16 +233,16 @@ int launch_bridge_precompute(const BridgeDev& bd, int* tok_ids, uint8_t* tok_len
   return 0;
 }
 
-template <bool ROWS>
+template <bool ROWS, bool HP>
 static int launch_bridge_t(const BridgeDev& bd, const int* inp, int B, int T, int gen_idx, const int* gen_rows, const int* row_len, const int* cand, int K,
-                           const float* lexicon, const float* lex_pos, const uint8_t* lex_cls, int negative, const PosDev& pos, int* clip_ids,
-                           int* clip_len, float* senti_raw, float* repeats, int* overflow_flag, hipStream_t st) {
+                           const float* lexicon, const float* lex_pos, const uint8_t* lex_cls, int negative, const RowHyper* hp_rows, const PosDev& pos,
+                           int* clip_ids, int* clip_len, float* senti_raw, float* repeats, int* overflow_flag, hipStream_t st) {
   const long rows = (long)B * K;
   if (rows <= 0) return 0;
   const size_t shmem = (size_t)BR_THREADS * (2 * BR_MAXB + BR_MAXSYM * 4 + BR_MAXP * 8);
-  CZC_HIP_CHECK(hipFuncSetAttribute((const void*)bridge_kernel<ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-  hipLaunchKernelGGL(bridge_kernel<ROWS>, dim3(cdiv(rows, BR_THREADS)), dim3(BR_THREADS), shmem, st, bd, inp, B, T, gen_idx, gen_rows,
-                     row_len, cand, K, lexicon, lex_pos, lex_cls, negative, pos, clip_ids, clip_len, senti_raw, repeats, overflow_flag);
+  CZC_HIP_CHECK(hipFuncSetAttribute((const void*)bridge_kernel<ROWS, HP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+  hipLaunchKernelGGL((bridge_kernel<ROWS, HP>), dim3(cdiv(rows, BR_THREADS)), dim3(BR_THREADS), shmem, st, bd, inp, B, T, gen_idx, gen_rows,
+                     row_len, cand, K, lexicon, lex_pos, lex_cls, negative, hp_rows, pos, clip_ids, clip_len, senti_raw, repeats, overflow_flag);
   CZC_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -238,7 +250,7 @@ static int launch_bridge_t(const BridgeDev& bd, const int* inp, int B, int T, in
 int launch_bridge(const BridgeDev& bd, const int* inp, int B, int T, int gen_idx, const int* cand, int K,
                   const float* lexicon, const float* lex_pos, const uint8_t* lex_cls, int negative, const PosDev& pos, int* clip_ids, int* clip_len, float* senti_raw,
                   float* repeats, int* overflow_flag, hipStream_t st) {
-  return launch_bridge_t<false>(bd, inp, B, T, gen_idx, nullptr, nullptr, cand, K, lexicon, lex_pos, lex_cls, negative, pos, clip_ids, clip_len,
+  return launch_bridge_t<false, false>(bd, inp, B, T, gen_idx, nullptr, nullptr, cand, K, lexicon, lex_pos, lex_cls, negative, nullptr, pos, clip_ids, clip_len,
                                 senti_raw, repeats, overflow_flag, st);
 }
 
@@ -246,8 +258,17 @@ int launch_bridge_rows(const BridgeDev& bd, const int* inp, int B, int T, const 
                        const float* lexicon, const float* lex_pos, const uint8_t* lex_cls, int negative, const PosDev& pos, int* clip_ids, int* clip_len,
                        float* senti_raw, float* repeats, int* overflow_flag, hipStream_t st, const int* row_len) {
   if (!gen_rows || !cand) { snprintf(g_err, sizeof(g_err), "bridge: the per-row form needs gen_rows and cand"); return 1; }
-  return launch_bridge_t<true>(bd, inp, B, T, 0, gen_rows, row_len, cand, K, lexicon, lex_pos, lex_cls, negative, pos, clip_ids, clip_len,
+  return launch_bridge_t<true, false>(bd, inp, B, T, 0, gen_rows, row_len, cand, K, lexicon, lex_pos, lex_cls, negative, nullptr, pos, clip_ids, clip_len,
                                senti_raw, repeats, overflow_flag, st);
+}
+
+int launch_bridge_rows_hp(const BridgeDev& bd, const int* inp, int B, int T, const int* gen_rows, const int* cand, int K,
+                          const float* lexicon, const float* lex_pos, const uint8_t* lex_cls, const RowHyper* hp_rows, const PosDev& pos,
+                          int* clip_ids, int* clip_len, float* senti_raw, float* repeats, int* overflow_flag, hipStream_t st,
+                          const int* row_len) {
+  if (!gen_rows || !cand || !hp_rows) { snprintf(g_err, sizeof(g_err), "bridge: the per-row form needs gen_rows, cand and hp_rows"); return 1; }
+  return launch_bridge_t<true, true>(bd, inp, B, T, 0, gen_rows, row_len, cand, K, lexicon, lex_pos, lex_cls, 0, hp_rows, pos, clip_ids, clip_len,
+                                     senti_raw, repeats, overflow_flag, st);
 }
 
 // ---- exclusive scan of sequence lengths --------------------------------------------------------

@@ -48,7 +48,9 @@ __global__ __launch_bounds__(256) void cosine_kernel(const float* text_feat, con
 }
 
 // ROWS: the write-back column is the row's own (a.gen_rows[b], czc_generate_rows)
-template <bool ROWS>
+// HP: so are alpha, beta, gamma and the control signal (a.hp_rows[b], czc_generate_rows_hp): one work-group serves one row, so
+// every branch on them is uniform over the work-group, as in the scalar form
+template <bool ROWS, bool HP>
 __global__ __launch_bounds__(CB_THREADS) void combine_kernel(CombineArgs a) {
   __shared__ float s_cos[CB_MAXK];
   __shared__ float s_fin[CB_MAXK];
@@ -57,6 +59,10 @@ __global__ __launch_bounds__(CB_THREADS) void combine_kernel(CombineArgs a) {
   const int b = blockIdx.x;
   const int tid = threadIdx.x;
   const int K = a.K;
+  if (HP) {
+    const RowHyper h = a.hp_rows[b];
+    a.alpha = h.alpha; a.beta = h.beta; a.gamma = h.gamma; a.use_senti = h.control;
+  }
 
   // cosines come from cosine_kernel through clip_ref (overwritten below with the reference's logits/scale form)
   for (int k = tid; k < K; k += CB_THREADS) s_cos[k] = a.clip_ref[(long)b * K + k];
@@ -170,15 +176,20 @@ __global__ __launch_bounds__(CB_THREADS) void combine_kernel(CombineArgs a) {
 // bound it) and require f_r < f_w.  Such an image re-encodes nothing (need_cos = 0) or only its winner, for the cosine the
 // caller reads back (kind 3: exact cosine for the OUTPUT, screening cosine in the scores, so that every score of the
 // image carries the same common error).  gated[0] counts those images, gated[1] all images.
+// HP (czc_generate_rows_hp): theta_ is the base threshold and beta_ the logit scale; the row's beta is hp_rows[b].beta and its
+// threshold theta_ / max(beta * scale, 1e-6), the expression the engine forms on the host for the scalar form
+template <bool HP>
 __global__ __launch_bounds__(CB_THREADS) void refine_select_kernel(const float* clip_score, const float* final_score, int K,
-                                                                   float theta, int m_samples, float gate_h, float beta, int need_cos,
-                                                                   int* gated, int* kind, int* list, int* count) {
+                                                                   float theta_, int m_samples, float gate_h, float beta_, int need_cos,
+                                                                   const RowHyper* hp_rows, int* gated, int* kind, int* list, int* count) {
   __shared__ float s_p[CB_MAXK];
   __shared__ float s_f[CB_MAXK];
   __shared__ int s_kind[CB_MAXK];
   __shared__ float red[8];
   __shared__ int s_arg;
   const int b = blockIdx.x, tid = threadIdx.x;
+  const float beta = HP ? hp_rows[b].beta : beta_;
+  const float theta = HP ? theta_ / fmaxf(beta * beta_, 1e-6f) : theta_;
   for (int k = tid; k < K; k += CB_THREADS) {
     s_p[k] = clip_score[(long)b * K + k];
     s_f[k] = final_score[(long)b * K + k];
@@ -266,8 +277,21 @@ int launch_refine_select(const float* clip_score, const float* final_score, int 
     snprintf(g_err, sizeof(g_err), "refine_select: K=%d > %d", K, CB_MAXK);
     return 1;
   }
-  hipLaunchKernelGGL(refine_select_kernel, dim3(B), dim3(CB_THREADS), 0, st, clip_score, final_score, K, theta, m_samples, gate_h, beta,
-                     need_cos, gated, kind, list, count);
+  hipLaunchKernelGGL(refine_select_kernel<false>, dim3(B), dim3(CB_THREADS), 0, st, clip_score, final_score, K, theta, m_samples, gate_h, beta,
+                     need_cos, nullptr, gated, kind, list, count);
+  CZC_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int launch_refine_select_rows(const float* clip_score, const float* final_score, int B, int K, float theta_base, float scale,
+                              int m_samples, float gate_h, const RowHyper* hp_rows, int need_cos, int* gated, int* kind, int* list,
+                              int* count, hipStream_t st) {
+  if (K > CB_MAXK || !hp_rows) {
+    snprintf(g_err, sizeof(g_err), "refine_select: K=%d > %d or no hp_rows", K, CB_MAXK);
+    return 1;
+  }
+  hipLaunchKernelGGL(refine_select_kernel<true>, dim3(B), dim3(CB_THREADS), 0, st, clip_score, final_score, K, theta_base, m_samples, gate_h,
+                     scale, need_cos, hp_rows, gated, kind, list, count);
   CZC_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -310,8 +334,10 @@ int launch_combine(const CombineArgs& a, hipStream_t st) {
   if (a.text_feat)  // null: clip_ref already holds the cosines (second combine of the screen-then-refine engine)
     hipLaunchKernelGGL(cosine_kernel, dim3((unsigned)cdiv((long)a.B * a.K, 4)), dim3(256), 0, st, a.text_feat, a.img_n, a.B, a.K, a.D,
                        a.clip_ref, a.nonfinite);
-  if (a.gen_rows) hipLaunchKernelGGL(combine_kernel<true>, dim3(a.B), dim3(CB_THREADS), 0, st, a);
-  else hipLaunchKernelGGL(combine_kernel<false>, dim3(a.B), dim3(CB_THREADS), 0, st, a);
+  if (a.hp_rows && !a.gen_rows) { snprintf(g_err, sizeof(g_err), "combine: hp_rows needs gen_rows"); return 1; }
+  if (a.hp_rows) hipLaunchKernelGGL((combine_kernel<true, true>), dim3(a.B), dim3(CB_THREADS), 0, st, a);
+  else if (a.gen_rows) hipLaunchKernelGGL((combine_kernel<true, false>), dim3(a.B), dim3(CB_THREADS), 0, st, a);
+  else hipLaunchKernelGGL((combine_kernel<false, false>), dim3(a.B), dim3(CB_THREADS), 0, st, a);
   CZC_HIP_CHECK(hipGetLastError());
   return 0;
 }

@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 
 #include "../../include/conzic_hip.h"
@@ -160,6 +161,9 @@ struct czc_engine {
   // option "memo" (czc_generate only; memo.hip): a step runs only for the images whose masked row differs from the one they
   // had on their last visit of the same (position, n_mask) key in this call; the others take the entry's row and cosine back
   int memo = 0;
+  // czc_generate_rows_hp, during its steps: the hyper-parameters of the rows the step at hand runs on (device, one record per
+  // row of that batch -- the call's upload, or a compact batch's gather of it); null everywhere else
+  const RowHyper* hp_rows = nullptr;
   int memo_branch_floor = 0;  // compacted step: longest branch the HIT images had (the full batch's attention-kernel choice)
   int64_t stat_memo_hits = 0, stat_memo_images = 0;  // image-steps that took an entry / all image-steps of memo calls
   // option "memo_rows" (czc_generate_rows only; memo_rows.hip): the same rule keyed per row, with counters of its own
@@ -765,14 +769,20 @@ int step_phase_a(czc_engine* e, const StepArgs& a) {
   StepBufs b;
   E_CHECK(step_bufs(e, a.B * a.K, &b));
   { ProfScope ps(e, "topk", 0);
-    if (a.dot_rows) E_CHECK(launch_softmax_mask_topk_rows(logits, a.B, c.bert_vocab, a.K, e->d_mask, hp->temperature, c.dot_id, a.dot_rows,
+    if (e->hp_rows) E_CHECK(launch_softmax_mask_topk_rows_hp(logits, a.B, c.bert_vocab, a.K, e->d_mask, e->hp_rows, c.dot_id, a.dot_rows,
+                                                             b.probs, b.idxs, b.cand, e->st));
+    else if (a.dot_rows) E_CHECK(launch_softmax_mask_topk_rows(logits, a.B, c.bert_vocab, a.K, e->d_mask, hp->temperature, c.dot_id, a.dot_rows,
                                                           b.probs, b.idxs, b.cand, e->st));
     else E_CHECK(launch_softmax_mask_topk(logits, a.B, c.bert_vocab, a.K, e->d_mask, hp->temperature, c.dot_id, a.dot_allowed,
                                           b.probs, b.idxs, b.cand, e->st)); }
   E_HIP(hipMemsetAsync(b.totals, 0, 32, e->st));
   { ProfScope ps(e, "bridge", 0);
     PosDev pos{hp->control == 2 ? e->d_pos_tags : nullptr, e->d_pos_masks, e->pos_n};
-    if (a.gen_rows) E_CHECK(launch_bridge_rows(e->bd, a.d_inp, a.B, a.T, a.gen_rows, b.cand, a.K, hp->control == 1 ? e->d_lex : nullptr,
+    // per-row hyper-parameters: every table there is goes along and a candidate's thread scores by its row's control
+    if (e->hp_rows) E_CHECK(launch_bridge_rows_hp(e->bd, a.d_inp, a.B, a.T, a.gen_rows, b.cand, a.K, e->d_lex, e->d_lex_pos, e->d_lex_cls, e->hp_rows,
+                                                  PosDev{e->d_pos_tags, e->d_pos_masks, e->pos_n}, b.cids, b.clen, b.senti, b.reps,
+                                                  b.totals + 2, e->st, a.rag ? a.rag->len : nullptr));
+    else if (a.gen_rows) E_CHECK(launch_bridge_rows(e->bd, a.d_inp, a.B, a.T, a.gen_rows, b.cand, a.K, hp->control == 1 ? e->d_lex : nullptr,
                                                hp->control == 1 ? e->d_lex_pos : nullptr, e->d_lex_cls, hp->negative,
                                                pos, b.cids, b.clen, b.senti, b.reps, b.totals + 2, e->st, a.rag ? a.rag->len : nullptr));
     else E_CHECK(launch_bridge(e->bd, a.d_inp, a.B, a.T, a.gen_idx, b.cand, a.K, hp->control == 1 ? e->d_lex : nullptr,
@@ -848,6 +858,7 @@ int step_phase_b(czc_engine* e, const StepArgs& a, int M, int max_len, int max_b
   ca.senti_raw = b.senti; ca.repeats = b.reps; ca.alpha = hp->alpha; ca.beta = hp->beta; ca.gamma = hp->gamma;
   ca.use_senti = hp->control; ca.B = a.B; ca.K = a.K; ca.D = c.clip_proj; ca.clip_score = cscore; ca.clip_ref = cref;
   ca.final_score = fin; ca.best = best; ca.best_cos = bcos; ca.inp = a.d_inp; ca.T = a.T; ca.gen_idx = a.gen_idx;
+  ca.hp_rows = e->hp_rows;   // czc_generate_rows_hp: alpha / beta / gamma / control per row, in both passes of the refine engine too
   ca.gen_rows = a.gen_rows;  // both passes of the refine engine write back through the same per-row column
   E_CHECK(ensure(e, "s_nonfinite", 32, (void**)&ca.nonfinite));
   if (!e->refine) {
@@ -871,13 +882,15 @@ int step_phase_b(czc_engine* e, const StepArgs& a, int M, int max_len, int max_b
   const int S = a.B + n_seq;
   // (on fp16 rows the deviation a kept screening cosine carries is refine_rows16_factor times larger: the mass threshold
   // shrinks by the same factor, so theta * deviation -- what such a candidate can move its score by -- stays what it was)
-  const float theta = (e->in_generate ? e->refine_theta_gen / (refine_rows16_now(e) ? e->refine_rows16_factor : 1.f) : e->refine_theta_x) /
-                      fmaxf(hp->beta * e->logit_scale_exp, 1e-6f);
+  const float theta_base = e->in_generate ? e->refine_theta_gen / (refine_rows16_now(e) ? e->refine_rows16_factor : 1.f) : e->refine_theta_x;
+  const float theta = theta_base / fmaxf(hp->beta * e->logit_scale_exp, 1e-6f);  // (per-row hyper-parameters: formed per row in the kernel)
   { ProfScope ps(e, "combine", 0);
     ca.inp = nullptr;
     E_CHECK(launch_combine(ca, e->st));
     const float gate_h = e->gate_now ? e->refine_gate_delta * (refine_rows16_now(e) ? e->refine_rows16_factor : 1.f) * e->logit_scale_exp : 0.f;
-    E_CHECK(launch_refine_select(cscore, fin, a.B, a.K, theta, e->in_generate ? e->refine_samples : e->refine_samples_step, gate_h, hp->beta, e->gate_need_cos ? 1 : 0,
+    if (e->hp_rows) E_CHECK(launch_refine_select_rows(cscore, fin, a.B, a.K, theta_base, e->logit_scale_exp, e->in_generate ? e->refine_samples : e->refine_samples_step,
+                                                      gate_h, e->hp_rows, e->gate_need_cos ? 1 : 0, ca.nonfinite + 4, kind, list, count, e->st));
+    else E_CHECK(launch_refine_select(cscore, fin, a.B, a.K, theta, e->in_generate ? e->refine_samples : e->refine_samples_step, gate_h, hp->beta, e->gate_need_cos ? 1 : 0,
                                  ca.nonfinite + 4, kind, list, count, e->st)); }
   { ProfScope ps(e, "bridge", 0);
     E_HIP(hipMemsetAsync(rtot, 0, 64, e->st));
@@ -929,6 +942,7 @@ int step_device(czc_engine* e, int* d_inp, int B, int T, int gen_idx, int n_mask
     return fail(e, CZC_ERR_STATE, "n_mask=0 needs a previous forward of the same [B,T] shape%s");
   StepArgs a{d_inp, B, T, gen_idx, n_mask, dot_allowed, K, *hp};
   a.gen_rows = gen_rows; a.dot_rows = dot_rows; a.gen_rows_host = gen_rows_host; a.rag = rag; a.ctl_T = ctl_T;
+  if (e->hp_rows && (!gen_rows || !dot_rows)) return fail(e, CZC_ERR_ARG, "step: per-row hyper-parameters need per-row columns%s");
   if (rag && (!gen_rows || !dot_rows || rag->max_T > T || rag->M > B * T)) return fail(e, CZC_ERR_ARG, "step: ragged rows need per-row columns and lengths within T%s");
   E_CHECK(step_phase_a(e, a));
   if (n_mask > 0) { e->stat_bert_rows += rag ? rag->M : B * T; e->last_BT = B * T; e->last_B = B; e->last_T = T; }
@@ -1090,6 +1104,7 @@ struct MemoRowsPlan {
   MemoRowsTab tab{};
   int *hit = nullptr, *cnt = nullptr, *list = nullptr, *tot = nullptr, *inp_c = nullptr, *col_c = nullptr, *dot_c = nullptr;
   float *bcos = nullptr, *img_c = nullptr;
+  RowHyper* hp_c = nullptr;      // czc_generate_rows_hp: the records of a compact batch's rows, gathered by its run list
   std::vector<std::vector<int32_t>> h_col_c;  // compact batch of the group in progress: the active rows' column at every step
   std::vector<int32_t> run_h;    // of the group in progress: the rows that run, ascending (host copy of list_d)
   const int* list_d = nullptr;   // of the group in progress: the device list of the rows that run (null: every row)
@@ -1272,10 +1287,16 @@ int memo_rows_step(czc_engine* e, MemoRowsPlan& mp, int s, int* d_inp, int R, in
   const int32_t* col_h = mp.h_col_c[j].data();
   float* img_rows = e->d_img_n;
   const int img_B = e->img_B;
+  const RowHyper* hp_full = e->hp_rows;
+  if (hp_full) {  // the running rows' own records, by the run list the batch is gathered with
+    if (!mp.hp_c || !mp.list_d) return fail(e, CZC_ERR_STATE, "generate_rows_hp: a compact batch without room for its hyper-parameters%s");
+    E_CHECK(launch_gather_row_hyper(hp_full, mp.list_d, n_act, mp.hp_c, e->st));
+    e->hp_rows = mp.hp_c;
+  }
   e->d_img_n = mp.img_c; e->img_B = n_act; e->memo_branch_floor = j < MEMO_ROWS_SUB ? mp.branch_max[j] : 0;
   const int rc = step_device(e, mp.inp_c, n_act, T, col_h[0], n_mask, col_h[0] - seed_len == L - 1 ? 1 : 0, K, hp, mp.col_c, mp.dot_c,
                              col_h, mp.rag(false), mp.ctl_T());
-  e->d_img_n = img_rows; e->img_B = img_B; e->memo_branch_floor = 0;
+  e->d_img_n = img_rows; e->img_B = img_B; e->memo_branch_floor = 0; e->hp_rows = hp_full;
   E_CHECK(rc);
   return launch_memo_rows_scatter(mp.inp_c, (const float*)e->ws["s_bcos"].p, (const int*)e->ws["p_img_max"].p, mp.list_d, n_act,
                                   mp.tab, col0, j, record, d_inp, mp.bcos, e->st) ? fail(e, CZC_ERR_HIP, "%s", g_err) : 0;
@@ -1286,7 +1307,7 @@ int memo_rows_step(czc_engine* e, MemoRowsPlan& mp, int s, int* d_inp, int R, in
 // =================================================================================================
 extern "C" {
 
-int czc_version(void) { return 101; }
+int czc_version(void) { return 102; }
 
 const char* czc_last_error(const czc_engine* e) { return e ? e->err : czc::g_err; }
 
@@ -1812,7 +1833,7 @@ int czc_step(czc_engine* e, int32_t* inp, int B, int T, int gen_idx, int n_mask,
 static int generate_impl(czc_engine* e, bool rows, bool from, int B, int T, int L, int seed_len, const int32_t* init_ids_host,
                          const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
                          const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp, int32_t* out_ids, float* out_cos,
-                         const int32_t* len_rows = nullptr) {
+                         const int32_t* len_rows = nullptr, const czc_hyper* hp_rows_host = nullptr) {
   if (!e || !init_ids_host || !positions_host || !hp || B <= 0 || n_steps < 0 || snapshot_every <= 0)
     return CZC_ERR_ARG;
   if (seed_len + L > T) return fail(e, CZC_ERR_ARG, "generate: seed_len + L > T%s");
@@ -1906,6 +1927,7 @@ static int generate_impl(czc_engine* e, bool rows, bool from, int B, int T, int 
     }
   }
   int *d_inp, *d_row, *d_sched = nullptr;
+  RowHyper* d_hp_rows = nullptr;
   { int* flag; E_CHECK(ensure(e, "s_nonfinite", 32, (void**)&flag)); E_HIP(hipMemsetAsync(flag, 0, 32, e->st)); }
   E_CHECK(ensure(e, "g_inp", (size_t)B * T * 4, (void**)&d_inp));
   if (from) {  // every row brings its own start row: one upload, no broadcast
@@ -1928,6 +1950,13 @@ static int generate_impl(czc_engine* e, bool rows, bool from, int B, int T, int 
       E_CHECK(ensure(e, "g_img_r", (size_t)B * D * 4, (void**)&img_r));
     }
     if (!sched.empty()) E_HIP(hipMemcpyAsync(d_sched, sched.data(), sched.size() * 4, hipMemcpyHostToDevice, e->st));
+    if (hp_rows_host) {  // one record per row, uploaded once with the schedule
+      static_assert(sizeof(RowHyper) == sizeof(czc_hyper) && offsetof(RowHyper, temperature) == offsetof(czc_hyper, temperature) &&
+                    offsetof(RowHyper, control) == offsetof(czc_hyper, control) && offsetof(RowHyper, negative) == offsetof(czc_hyper, negative),
+                    "RowHyper is czc_hyper as the kernels read it");
+      E_CHECK(ensure(e, "g_hp_rows", (size_t)B * sizeof(RowHyper), (void**)&d_hp_rows));
+      E_HIP(hipMemcpyAsync(d_hp_rows, hp_rows_host, (size_t)B * sizeof(RowHyper), hipMemcpyHostToDevice, e->st));
+    }
     if (image_of_row_host) {
       E_HIP(hipMemcpyAsync(d_ior, image_of_row_host, (size_t)B * 4, hipMemcpyHostToDevice, e->st));
       E_CHECK(launch_gather_rows_f32(img_full, d_ior, B, D, img_r, e->st));
@@ -1969,6 +1998,8 @@ static int generate_impl(czc_engine* e, bool rows, bool from, int B, int T, int 
     }
   }
   // a row that has not run yet in this call reports cosine 0 (the reference's best_clip_score start value)
+  if (memo_rows && d_hp_rows && !rc && ensure(e, "mr_hp_c", (size_t)B * sizeof(RowHyper), (void**)&mrp.hp_c)) rc = CZC_ERR_HIP;
+  e->hp_rows = rc ? nullptr : d_hp_rows;  // (handed back with the image batch below)
   if (memo_rows && any_idle && !rc && hipMemsetAsync(mrp.bcos, 0, (size_t)B * 4, e->st) != hipSuccess) rc = fail(e, CZC_ERR_HIP, "generate_rows_from: clearing the cosines%s");
   for (int s = 0; s < n_steps && !rc; ++s) {
     const int pos = positions_host[rows ? (size_t)s * B : (size_t)s];
@@ -1997,7 +2028,7 @@ static int generate_impl(czc_engine* e, bool rows, bool from, int B, int T, int 
     }
   }
   // rows: the resident image batch comes back whatever happened, and no later call may re-use a forward by this call's columns
-  e->d_img_n = img_full; e->img_B = img_B;
+  e->d_img_n = img_full; e->img_B = img_B; e->hp_rows = nullptr;
   if (rows) { e->bert_pruned_rows = nullptr; if (rc) (void)hipStreamSynchronize(e->st); }
   if (rc) return rc;
   E_HIP(hipMemcpyAsync(e->h_totals + 9, e->ws["s_nonfinite"].p, 24, hipMemcpyDeviceToHost, e->st));
@@ -2029,9 +2060,11 @@ int czc_generate_rows_from(czc_engine* e, int R, int T, int L, int seed_len, con
                        snapshot_every, hp, out_ids, out_cos);
 }
 
-int czc_generate_rows_len(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
-                          const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
-                          const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp, int32_t* out_ids, float* out_cos) {
+// czc_generate_rows_len, and czc_generate_rows_hp behind its own checks (hp_rows_host [R]: hp is then its first entry)
+static int rows_len_impl(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
+                         const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
+                         const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp, int32_t* out_ids, float* out_cos,
+                         const czc_hyper* hp_rows_host) {
   if (!e || !init_rows_host || !len_of_row_host || !positions_host || !hp || R <= 0 || n_steps < 0 || snapshot_every <= 0)
     return CZC_ERR_ARG;
   e->err[0] = 0;
@@ -2057,7 +2090,49 @@ int czc_generate_rows_len(czc_engine* e, int R, int T, int seed_len, const int32
   }
   // rows of one length that fill the stride: czc_generate_rows_from itself, bit for bit
   return generate_impl(e, true, true, R, T, L_max, seed_len, init_rows_host, image_of_row_host, top_k, n_steps, positions_host, n_mask_host,
-                       snapshot_every, hp, out_ids, out_cos, uniform ? nullptr : len_of_row_host);
+                       snapshot_every, hp, out_ids, out_cos, uniform ? nullptr : len_of_row_host, hp_rows_host);
+}
+
+int czc_generate_rows_len(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
+                          const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
+                          const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp, int32_t* out_ids, float* out_cos) {
+  return rows_len_impl(e, R, T, seed_len, init_rows_host, len_of_row_host, image_of_row_host, top_k, n_steps, positions_host, n_mask_host,
+                       snapshot_every, hp, out_ids, out_cos, nullptr);
+}
+
+int czc_generate_rows_hp(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
+                         const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
+                         const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp_of_row_host, int32_t* out_ids, float* out_cos) {
+  if (!e || !init_rows_host || !positions_host || !hp_of_row_host || R <= 0 || n_steps < 0 || snapshot_every <= 0) return CZC_ERR_ARG;
+  e->err[0] = 0;
+  if (R > CZC_MAX_ROWS) return fail(e, CZC_ERR_ARG, "generate_rows_hp: R > CZC_MAX_ROWS%s");
+  bool uniform = true, any_ctl = false, one_signal = true;
+  for (int r = 0; r < R; ++r) {
+    const czc_hyper& h = hp_of_row_host[r];
+    if (h.control < 0 || h.control > 2) return fail(e, CZC_ERR_ARG, "generate_rows_hp: control outside {0, 1, 2}%s");
+    if (!std::isfinite(h.temperature) || !(h.temperature > 0.f)) return fail(e, CZC_ERR_ARG, "generate_rows_hp: a temperature must be finite and > 0%s");
+    if (!std::isfinite(h.alpha) || !std::isfinite(h.beta) || !std::isfinite(h.gamma)) return fail(e, CZC_ERR_ARG, "generate_rows_hp: alpha, beta and gamma must be finite%s");
+    uniform = uniform && memcmp(&h, &hp_of_row_host[0], sizeof(czc_hyper)) == 0;
+    any_ctl = any_ctl || h.control != 0;
+    one_signal = one_signal && h.control == hp_of_row_host[0].control && (h.negative != 0) == (hp_of_row_host[0].negative != 0);
+  }
+  // the host scorer is configured for one signal, and it is called for every row of a controlled step
+  if (e->ctl_fn && any_ctl && !one_signal)
+    return fail(e, CZC_ERR_ARG, "generate_rows_hp: a control callback scores one signal, so every row must share control and negative; "
+                                "use the control tables (czc_set_lexicon / czc_set_lexicon_pos / czc_set_pos)%s");
+  for (int r = 0; r < R; ++r) {  // step_device's messages, before any GPU work
+    if (hp_of_row_host[r].control == 1 && !e->ctl_fn && !e->d_lex && !e->d_lex_pos)
+      return fail(e, CZC_ERR_STATE, "sentiment path needs a lexicon (czc_set_lexicon / czc_set_lexicon_pos) or czc_set_control_callback%s");
+    if (hp_of_row_host[r].control == 2 && !e->ctl_fn && !e->d_pos_tags)
+      return fail(e, CZC_ERR_STATE, "POS path needs czc_set_pos or czc_set_control_callback%s");
+  }
+  // equal entries: the existing call, bit for bit (its scalar kernels)
+  const czc_hyper* rows_hp = uniform ? nullptr : hp_of_row_host;
+  if (len_of_row_host)
+    return rows_len_impl(e, R, T, seed_len, init_rows_host, len_of_row_host, image_of_row_host, top_k, n_steps, positions_host, n_mask_host,
+                         snapshot_every, &hp_of_row_host[0], out_ids, out_cos, rows_hp);
+  return generate_impl(e, true, true, R, T, T - seed_len - 1, seed_len, init_rows_host, image_of_row_host, top_k, n_steps, positions_host,
+                       n_mask_host, snapshot_every, &hp_of_row_host[0], out_ids, out_cos, nullptr, rows_hp);
 }
 
 int czc_set_control_callback(czc_engine* e, czc_control_fn fn, void* user) {

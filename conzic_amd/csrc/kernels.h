@@ -206,12 +206,23 @@ int launch_attention_shared(const void* qkv, const SegTable& tab, int B, int K, 
 int launch_attention_shared_split(const void* qkv, const SegTable& tab, int B, int K, int max_own, int max_keys, int heads,
                                   float scale, void* out, hipStream_t st);
 
+// ---- per-row hyper-parameters (czc_generate_rows_hp) ----------------------------------------------------------------------
+// One record per row of a rows call, the layout of czc_hyper (engine.hip asserts it): uploaded once with the schedule and read
+// by the four kernels that take hyper-parameters.  Those run one work-group per row (top-K, combine, refine_select) or one
+// thread per candidate (bridge), so a row's record is uniform wherever a work-group reads it.
+struct RowHyper { float alpha, beta, gamma, temperature; int control, negative; };
+
+int launch_gather_row_hyper(const RowHyper* src, const int* idx, int n, RowHyper* dst, hipStream_t st);  // rowops.hip: dst[i] = src[idx[i]]
+
 // ---- topk.hip -----------------------------------------------------------------------------
 int launch_softmax_mask_topk(const float* logits, int B, int V, int K, const float* mask, float temperature, int dot_id,
                              int dot_allowed, float* probs, int* idxs, int* cand, hipStream_t st);
 // the same with the '.' rule per row: dot_rows[b] (device, [B]) in place of dot_allowed
 int launch_softmax_mask_topk_rows(const float* logits, int B, int V, int K, const float* mask, float temperature, int dot_id,
                                   const int* dot_rows, float* probs, int* idxs, int* cand, hipStream_t st);
+// the per-row form with the row's own temperature: hp_rows[b].temperature (device, [B]) in place of temperature
+int launch_softmax_mask_topk_rows_hp(const float* logits, int B, int V, int K, const float* mask, const RowHyper* hp_rows, int dot_id,
+                                     const int* dot_rows, float* probs, int* idxs, int* cand, hipStream_t st);
 
 // ---- bridge.hip ---------------------------------------------------------------------------
 struct BridgeDev {
@@ -254,6 +265,13 @@ int launch_bridge(const BridgeDev& bd, const int* inp, int B, int T, int gen_idx
 int launch_bridge_rows(const BridgeDev& bd, const int* inp, int B, int T, const int* gen_rows, const int* cand, int K,
                        const float* lexicon, const float* lex_pos, const uint8_t* lex_cls, int negative, const PosDev& pos, int* clip_ids, int* clip_len,
                        float* senti_raw, float* repeats, int* overflow_flag, hipStream_t st, const int* row_len = nullptr);
+// the per-row form with the control signal per row of inp: the launch is handed every table there is (each may be null) and the
+// thread of a candidate of row b scores by hp_rows[b].control (1: lexicon / lex_pos with hp_rows[b].negative, 2: pos, 0: writes
+// neither senti_raw nor repeats)
+int launch_bridge_rows_hp(const BridgeDev& bd, const int* inp, int B, int T, const int* gen_rows, const int* cand, int K,
+                          const float* lexicon, const float* lex_pos, const uint8_t* lex_cls, const RowHyper* hp_rows, const PosDev& pos,
+                          int* clip_ids, int* clip_len, float* senti_raw, float* repeats, int* overflow_flag, hipStream_t st,
+                          const int* row_len = nullptr);
 // exclusive scan of len[n] -> off[n+1]; totals[0] = sum, totals[1] = max
 int launch_scan(const int* len, int n, int* off, int* totals, hipStream_t st);
 // Shared-prefix plan for B images x K candidates (segments: B trunks, then B*K branches):
@@ -294,6 +312,9 @@ struct CombineArgs {
   float refine_guard = 0.f;
   // czc_generate_rows: the write-back column of row b is gen_rows[b] (device, [B]) instead of gen_idx; null = gen_idx
   const int* gen_rows = nullptr;
+  // czc_generate_rows_hp: alpha, beta, gamma and use_senti (= control) of row b come from hp_rows[b] (device, [B]; needs
+  // gen_rows); null = the scalars above
+  const RowHyper* hp_rows = nullptr;
 };
 // text_feat == null: clip_ref already holds the cosines
 int launch_combine(const CombineArgs& a, hipStream_t st);
@@ -301,6 +322,10 @@ int launch_combine(const CombineArgs& a, hipStream_t st);
 // gate_h > 0: margin gate of czc_generate (combine.hip); gated[0] += images that passed it, gated[1] += images
 int launch_refine_select(const float* clip_score, const float* final_score, int B, int K, float theta, int m_samples, float gate_h,
                          float beta, int need_cos, int* gated, int* kind, int* list, int* count, hipStream_t st);
+// the same with beta and the mass threshold per row: beta = hp_rows[b].beta, theta = theta_base / max(beta * scale, 1e-6)
+int launch_refine_select_rows(const float* clip_score, const float* final_score, int B, int K, float theta_base, float scale,
+                              int m_samples, float gate_h, const RowHyper* hp_rows, int need_cos, int* gated, int* kind, int* list,
+                              int* count, hipStream_t st);
 int launch_refine_cosine(const float* text_feat, const float* img_n, const int* rlist, const int* n_rows_dev, int n_rows_max, int K, int D,
                          float* cos_out, int* nonfinite, hipStream_t st);
 // segment plan of the refine pass (bridge.hip): B trunks (prefix lengths of the screening plan) + B x Kr branch slots

@@ -593,6 +593,19 @@ int launch_gather_rows_bytes(const void* src, const int* idx, int M, int row_byt
   return 0;
 }
 
+// czc_generate_rows_hp: the hyper-parameter records of a compact batch's rows, dst[i] = src[idx[i]] (one thread per record)
+__global__ void gather_row_hyper_kernel(const RowHyper* src, const int* idx, int n, RowHyper* dst) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dst[i] = src[idx[i]];
+}
+
+int launch_gather_row_hyper(const RowHyper* src, const int* idx, int n, RowHyper* dst, hipStream_t st) {
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(gather_row_hyper_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, src, idx, n, dst);
+  CZC_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
 int launch_gather_rows_f32(const float* src, const int* idx, int M, int H, float* dst, hipStream_t st) {
   if (M <= 0) return 0;
   hipLaunchKernelGGL(gather_rows_kernel, dim3(cdiv(M, 4)), dim3(256), 0, st, src, idx, M, H, dst);

@@ -26,12 +26,12 @@ __device__ __forceinline__ float block_reduce(float v, float* red, bool is_max) 
 }
 
 // ROWS: the '.' rule is the row's own (dot_rows[b], czc_generate_rows); one work-group serves one row, so the value is
-// uniform over the work-group either way
-template <bool ROWS>
+// uniform over the work-group either way.  HP: so is the temperature (hp_rows[b].temperature, czc_generate_rows_hp)
+template <bool ROWS, bool HP>
 __global__ __launch_bounds__(TK_THREADS) void softmax_mask_topk_kernel(const float* logits, int V, int K,
-                                                                        const float* mask, float temperature, int dot_id,
-                                                                        int dot_allowed_, const int* dot_rows, float* probs_out,
-                                                                        int* idx_out, int* cand_out) {
+                                                                        const float* mask, float temperature_, int dot_id,
+                                                                        int dot_allowed_, const int* dot_rows, const RowHyper* hp_rows,
+                                                                        float* probs_out, int* idx_out, int* cand_out) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   float* p = (float*)smem_raw;                       // [V] probabilities (as float / uint bits)
   unsigned* hist = (unsigned*)(p + ((V + 3) & ~3));  // [256]
@@ -47,6 +47,7 @@ __global__ __launch_bounds__(TK_THREADS) void softmax_mask_topk_kernel(const flo
   const int b = blockIdx.x;
   const float* lr = logits + (long)b * V;
   const int dot_allowed = ROWS ? dot_rows[b] : dot_allowed_;
+  const float temperature = HP ? hp_rows[b].temperature : temperature_;
 
   // 1. logits / temperature, row max
   float mx = -INFINITY;
@@ -165,9 +166,9 @@ __global__ __launch_bounds__(TK_THREADS) void softmax_mask_topk_kernel(const flo
   }
 }
 
-template <bool ROWS>
+template <bool ROWS, bool HP>
 static int launch_topk_t(const float* logits, int B, int V, int K, const float* mask, float temperature, int dot_id, int dot_allowed,
-                         const int* dot_rows, float* probs, int* idxs, int* cand, hipStream_t st) {
+                         const int* dot_rows, const RowHyper* hp_rows, float* probs, int* idxs, int* cand, hipStream_t st) {
   if (K > TK_MAXK || K <= 0 || K > V) {
     snprintf(g_err, sizeof(g_err), "topk: K=%d unsupported (1..%d, <= V)", K, TK_MAXK);
     return 1;
@@ -177,22 +178,28 @@ static int launch_topk_t(const float* logits, int B, int V, int K, const float* 
     snprintf(g_err, sizeof(g_err), "topk: V=%d does not fit the 160 KB LDS", V);
     return 1;
   }
-  CZC_HIP_CHECK(hipFuncSetAttribute((const void*)softmax_mask_topk_kernel<ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize,
+  CZC_HIP_CHECK(hipFuncSetAttribute((const void*)softmax_mask_topk_kernel<ROWS, HP>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)shmem));
-  hipLaunchKernelGGL(softmax_mask_topk_kernel<ROWS>, dim3(B), dim3(TK_THREADS), shmem, st, logits, V, K, mask, temperature,
-                     dot_id, dot_allowed, dot_rows, probs, idxs, cand);
+  hipLaunchKernelGGL((softmax_mask_topk_kernel<ROWS, HP>), dim3(B), dim3(TK_THREADS), shmem, st, logits, V, K, mask, temperature,
+                     dot_id, dot_allowed, dot_rows, hp_rows, probs, idxs, cand);
   CZC_HIP_CHECK(hipGetLastError());
   return 0;
 }
 
 int launch_softmax_mask_topk(const float* logits, int B, int V, int K, const float* mask, float temperature, int dot_id,
                              int dot_allowed, float* probs, int* idxs, int* cand, hipStream_t st) {
-  return launch_topk_t<false>(logits, B, V, K, mask, temperature, dot_id, dot_allowed, nullptr, probs, idxs, cand, st);
+  return launch_topk_t<false, false>(logits, B, V, K, mask, temperature, dot_id, dot_allowed, nullptr, nullptr, probs, idxs, cand, st);
 }
 
 int launch_softmax_mask_topk_rows(const float* logits, int B, int V, int K, const float* mask, float temperature, int dot_id,
                                   const int* dot_rows, float* probs, int* idxs, int* cand, hipStream_t st) {
-  return launch_topk_t<true>(logits, B, V, K, mask, temperature, dot_id, 0, dot_rows, probs, idxs, cand, st);
+  return launch_topk_t<true, false>(logits, B, V, K, mask, temperature, dot_id, 0, dot_rows, nullptr, probs, idxs, cand, st);
+}
+
+int launch_softmax_mask_topk_rows_hp(const float* logits, int B, int V, int K, const float* mask, const RowHyper* hp_rows, int dot_id,
+                                     const int* dot_rows, float* probs, int* idxs, int* cand, hipStream_t st) {
+  if (!hp_rows || !dot_rows) { snprintf(g_err, sizeof(g_err), "topk: the per-row hyper-parameter form needs hp_rows and dot_rows"); return 1; }
+  return launch_topk_t<true, true>(logits, B, V, K, mask, 1.0f, dot_id, 0, dot_rows, hp_rows, probs, idxs, cand, st);
 }
 
 }  // namespace czc

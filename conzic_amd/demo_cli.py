@@ -59,6 +59,11 @@ def get_args(argv=None):
                    help="several sentence lengths of every image in ONE engine call, e.g. 6,8,10,12 (each row at its own length; "
                         "--order sequential or shuffle): one call per sample, or with --batch_samples one call of samples_num x "
                         "len(lens) rows per image; --sentence_len is ignored while this is set")
+    p.add_argument("--signals", type=lambda v: [g.strip().lower() for g in v.split(",") if g.strip()], default=None,
+                   metavar="caption,positive,negative[,pos]",
+                   help="one image under several control signals in ONE engine call (one row per signal, each with its own "
+                        "hyper-parameters and the visiting order its own run would draw); combines with --sentence_lens and "
+                        "--batch_samples; --run_type / --control_type / --sentiment_type are ignored while this is set")
     p.add_argument("--caption", action="append", default=None, metavar="TEMPLATE",
                    help="--run_type infill (repeatable): a caption with blanks, e.g. \"a _ dog on a _\"; only the blanks are "
                         "polished (num_iterations sweeps, --order sequential or shuffle over each caption's blanks), the given "
@@ -78,6 +83,16 @@ def get_args(argv=None):
             p.error("--sentence_lens needs a comma-separated list of lengths >= 1")
         if a.run_type == "caption" and a.order not in ("sequential", "shuffle"):
             p.error("--sentence_lens visits every row's positions in --order sequential or shuffle")
+    if a.signals is not None:
+        from conzic_amd import signals as sg
+        if a.run_type == "infill":
+            p.error("--signals does not apply to --run_type infill")
+        try:
+            a.signals = sg.parse_signals(a.signals)
+        except ValueError as exc:
+            p.error(f"--signals: {exc}")
+        if a.order not in ("sequential", "shuffle"):
+            p.error("--signals visits every row's positions in --order sequential or shuffle")
     if a.control_scores:
         os.environ["CZC_CONTROL"] = a.control_scores
     return a
@@ -134,6 +149,19 @@ def main(argv=None):
         infill_captions(args.caption, img_name, lm_model, clip, lm_tokenizer, image_instance, token_mask, logger, prompt=args.prompt,
                         top_k=args.candidate_k, temperature=args.lm_temperature, max_iter=args.num_iterations, alpha=args.alpha,
                         beta=args.beta, generate_order=args.order, positions=args.infill_positions)
+        logger.info("total %.2fs" % (time.time() - t0))
+        return
+    if args.signals:
+        # all signals (and lengths) of a sample (with --batch_samples: of all samples) are rows of one engine call
+        from conzic_amd.runtime import caption_signals
+        for sample_id in ([None] if args.batch_samples else range(args.samples_num)):
+            if sample_id is not None:
+                logger.info(f"Sample {sample_id}: ")
+            caption_signals(args.signals, args.sentence_lens or [args.sentence_len], args.samples_num if args.batch_samples else 1,
+                            img_name, lm_model, clip, lm_tokenizer, image_instance, token_mask, logger, prompt=args.prompt,
+                            batch_size=args.batch_size, top_k=args.candidate_k, temperature=args.lm_temperature,
+                            max_iter=args.num_iterations, alpha=args.alpha, beta=args.beta, generate_order=args.order,
+                            gamma=args.gamma, pos_type=args.pos_type)
         logger.info("total %.2fs" % (time.time() - t0))
         return
     if args.sentence_lens:

@@ -151,6 +151,70 @@ def lengths_batches(args, run_type, all_batches, own_lo, own_hi, rank, world, im
                 write_results(result_dir(at_len, run_type, sample_id), all_results)
 
 
+def signals_batches(args, all_batches, own_lo, own_hi, rank, world, img_dir, lm_model, clip, lm_tokenizer, token_mask, logger):
+    """--signals: every batch polishes all control signals (and with --sentence_lens all lengths) of a sample in one engine call
+    (runtime.caption_signals), or with --batch_samples those of all its samples; the images are encoded once per batch.  The
+    orders are drawn as that loop draws them -- samples outside and batches inside (with --batch_samples: batch by batch), then
+    signals, lengths and samples inside a call -- and a rank draws those of the batches it does not own as well.  The files are
+    written per signal, length and sample in the layout of a run of that signal at that length; the POS signal's directories
+    start with `pos` (a --control_type pos run names its own after --sentiment_type, which a positive run here already uses)."""
+    import copy
+    from PIL import Image
+    from clip.clip import ImageEmbeds
+    from conzic_amd import signals as sg
+    from conzic_amd.runtime import advance_order_rng, caption_signals
+    S, sigs = args.samples_num, args.signals
+    lens = args.sentence_lens or [args.sentence_len]
+    per_call = S if args.batch_samples else 1
+    orders = [sg.signal_order(g, args.order, args.num_iterations, max(lens))[0] for g in sigs]
+    results = [[[[None] * (args.num_iterations + 1) for _ in range(S)] for _ in lens] for _ in sigs]
+    embed_cache = {}
+    for sample_id in ([None] if args.batch_samples else range(S)):
+        if sample_id is not None:
+            logger.info(f"Sample {sample_id + 1}: ")
+        for batch_idx, name_batch in enumerate(all_batches):
+            if not (own_lo <= batch_idx < own_hi):
+                for order in orders:
+                    for n in lens:
+                        for _ in range(per_call):
+                            advance_order_rng(order, n, args.num_iterations)
+                continue
+            logger.info(f"The {batch_idx + 1}-th batch:")
+            if batch_idx in embed_cache:
+                imgs = ImageEmbeds(embed_cache[batch_idx])
+            else:
+                imgs = [Image.open(os.path.join(img_dir, n)).convert("RGB") for n in name_batch]
+            outs = caption_signals(sigs, lens, per_call, name_batch, lm_model, clip, lm_tokenizer, imgs, token_mask, logger,
+                                   prompt=args.prompt, batch_size=args.batch_size, top_k=args.candidate_k,
+                                   temperature=args.lm_temperature, max_iter=args.num_iterations, alpha=args.alpha, beta=args.beta,
+                                   generate_order=args.order, gamma=args.gamma, pos_type=args.pos_type)
+            if batch_idx not in embed_cache:
+                embed_cache[batch_idx] = clip.last_image_embeds()
+            for g, per_len in enumerate(outs):
+                for l, per_sample in enumerate(per_len):
+                    for s, (gen_texts, _) in enumerate(per_sample):
+                        sid = s if sample_id is None else sample_id
+                        results[g][l][sid] = merge_results(results[g][l][sid], gen_texts, name_batch)
+    for g, sig in enumerate(sigs):
+        for l, n in enumerate(lens):
+            at = copy.copy(args)
+            at.sentence_len = n
+            at.run_type = "caption" if sig == "caption" else "controllable"
+            for sample_id in range(S):
+                all_results = results[g][l][sample_id]
+                if world > 1:
+                    import torch.distributed as tdist
+                    parts = [None] * world
+                    tdist.all_gather_object(parts, all_results)
+                    all_results = [None] * (args.num_iterations + 1)
+                    for part in parts:  # rank order == batch order
+                        for it, d in enumerate(part):
+                            if d is not None:
+                                all_results[it] = {**(all_results[it] or {}), **d}
+                if rank == 0:
+                    write_results(result_dir(at, sig, sample_id), all_results)
+
+
 def infill_batches(args, all_batches, own_lo, own_hi, rank, world, img_dir, lm_model, clip, lm_tokenizer, token_mask, logger):
     """--run_type infill: every --caption template is infilled for every image of a batch, all of them rows of one engine
     call (runtime.run_infill); the images are encoded once per batch.  One pass (sample_0): iter_<k>.json holds the
@@ -254,6 +318,9 @@ def main(argv=None):
     embed_cache = {}  # batch index -> image_embeds [B, proj]: the ViT runs once per image, not once per sample
     if args.run_type == "infill":
         infill_batches(args, all_batches, own_lo, own_hi, rank, world, img_dir, lm_model, clip, lm_tokenizer, token_mask, logger)
+        return
+    if args.signals:
+        signals_batches(args, all_batches, own_lo, own_hi, rank, world, img_dir, lm_model, clip, lm_tokenizer, token_mask, logger)
         return
     if args.sentence_lens:
         lengths_batches(args, run_type, all_batches, own_lo, own_hi, rank, world, img_dir, lm_model, clip, lm_tokenizer, token_mask,

@@ -734,3 +734,135 @@ def caption_lengths(lens: Sequence[int], samples_num: int, run_type: str, img_na
                 logger.info(f"final caption: {generate_texts[-2][i]}")
                 logger.info(f"best caption: {generate_texts[-1][i]}")
     return outs
+
+
+def _signal_kw(signal: str, gamma, pos_type) -> dict:
+    """The gamma / ctl_signal / pos_template keywords of the run_generation call behind `signal`."""
+    from . import signals as sg
+    run_type, ctl_type, style = sg.signal_run(signal)
+    if run_type == "caption":
+        return {}
+    if ctl_type == "sentiment":
+        return dict(gamma=gamma, ctl_signal=style)
+    return dict(gamma=gamma, pos_template=pos_type)
+
+
+def run_generation_signals(signals: Sequence[str], lens: Sequence[int], samples_num: int, generate_order: str, img_name, model, clip,
+                           tokenizer, image_instance, token_mask, prompt, logger, top_k, temperature, alpha, beta, max_iter,
+                           batch_size, verbose=True, gamma=5, pos_template=None):
+    """The loop over control signals around the loops over lengths and samples (one CLI run per --run_type / --control_type /
+    --sentiment_type) as ONE engine call: every signal x length x sample of a batch of `batch_size` images is a row of
+    czc_generate_rows_hp with its own czc_hyper (signals.expand / signals.batch_rows), at its own length and with the visiting
+    order the serial loop -- signals outside, then lengths, then samples -- would have drawn for it.  The control tables (lexicon
+    and POS tags) are configured once and the images encoded once.  Returns, per signal, what run_generation_lengths returns
+    for it (per length a list of `samples_num` (gen_texts_list, clip_score_sequence) pairs) and logs every call's lines in the
+    serial loop's order.  The reference's own sentence scorer (exact control mode) is configured for one signal: with it the
+    signals run one call each, as the serial loop runs them, and the log says why."""
+    import utils as ref_utils
+    from . import control, signals as sg
+    signals = sg.parse_signals(signals)
+    lens = [int(n) for n in lens]
+    S, B, NL = int(samples_num), int(batch_size), len(lens)
+    if "pos" in signals and pos_template is None:
+        raise ValueError("run_generation_signals: the pos signal needs a POS template")
+    eng = get_engine(model, clip, tokenizer)
+    # which control scores would each controlled signal get (control.configure's rule)?  The host scorer serves one signal.
+    mode = control.control_mode()
+    kinds = sorted({sg.signal_run(s)[1] == "pos" for s in signals if s != "caption"})
+    exact = False
+    for is_pos in kinds:
+        explicit = (getattr(clip, "pos_tags", None) is not None) if is_pos else (
+            getattr(clip, "lexicon_pos", None) is not None or getattr(clip, "lexicon", None) is not None)
+        exact = exact or (not (explicit and mode != "exact") and mode in ("exact", "auto"))
+    if exact:
+        if not getattr(eng, "_one_by_one_signals_logged", False):
+            logger.info("control signals: the exact control scorer is configured for one signal; running the "
+                        f"{len(signals)} signals one call at a time (CZC_CONTROL=table batches them)")
+            eng._one_by_one_signals_logged = True
+        out = []
+        for sig in signals:
+            order, max_iters = sg.signal_order(sig, generate_order, max_iter, max(lens))
+            out.append(run_generation_lengths(order, lens, S, img_name, model, clip, tokenizer, image_instance, token_mask, prompt, logger,
+                                              top_k, temperature, alpha, beta, max_iters, B, verbose=verbose,
+                                              **_signal_kw(sig, gamma, pos_template)))
+        return out
+    seed_len = len(prompt.split()) + 1
+    rows = sg.expand(signals, lens, S, generate_order, max_iter, alpha=alpha, beta=beta, temperature=temperature, gamma=gamma)
+    clip.compute_image_representation_from_image_instance(image_instance)   # once per image, whatever the signals
+    if getattr(eng, "_precision_logged", None) is None:
+        scale = _logit_scale_of(clip)
+        logger.info(f"engine precision: {PRECISION_NAMES.get(eng.precision, eng.precision)}"
+                    + (f" (exp(logit_scale) = {math.exp(scale):.1f})" if scale is not None else ""))
+        eng._precision_logged = True
+    init_rows, row_lens, rows_pos, hypers, image_of_row = sg.batch_rows(rows, tokenizer, prompt, B)
+
+    def polish(eng):
+        eng.set_token_mask(_mask_to_numpy(token_mask))
+        eng.set_option("memo_rows", memo_rows_setting())  # per-row step memo of the rows call (CZC_MEMO_ROWS)
+        for is_pos in kinds:   # both tables, once: a row reads the one its control names
+            chosen = control.configure(eng, clip, tokenizer, pos_template=pos_template if is_pos else None)
+            if chosen != getattr(eng, "_control_logged", None):
+                logger.info(f"control scores: {chosen}")
+                eng._control_logged = chosen
+        runner = _group_for(eng, len(hypers))
+        emb = None
+        if runner is not eng:
+            from clip.clip import ImageEmbeds
+            emb = image_instance.embeds if isinstance(image_instance, ImageEmbeds) else clip.last_image_embeds()
+            runner.set_image_embeds(emb)
+        if eng.precision == native.PREC_REFINE:
+            runner.refine_guard(reset=True)
+        res = runner.generate_rows_hp(init_rows, row_lens, seed_len, top_k, rows_pos, hypers, image_of_row=image_of_row,
+                                      n_mask=rows.n_mask, snapshot_every=rows.every)
+        if runner is not eng:
+            eng.set_image_embeds(emb)
+        return res, runner
+
+    ids, cos = _polish_guarded(polish, eng, model, clip, tokenizer, image_instance, logger)
+    if rows.positions.shape[0]:   # the caller's mask as after the LAST call's last position: the last sample at the last length
+        n = rows.col_lens[-1]
+        ref_utils.update_token_mask(tokenizer, token_mask, n, int(rows.positions[(rows.sweeps - 1) * rows.every + n - 1, -1]))
+    out = []
+    for g, sig in enumerate(signals):
+        if sig == "pos":
+            logger.info(pos_template)
+        per_len = []
+        for l, n in enumerate(lens):
+            per_sample = []
+            for s in range(S):
+                c = rows.column(g, l, s)
+                if rows.orders[g] == "shuffle":
+                    logger.info(f"Order_list:{[int(p) for p in rows.positions[:n, c]]}")
+                per_sample.append(_bookkeeping(rows.orders[g], ids[:, c * B:(c + 1) * B, :seed_len + n + 1], cos[:, c * B:(c + 1) * B],
+                                               tokenizer, img_name, logger, B, verbose, None))
+            per_len.append(per_sample)
+        out.append(per_len)
+    return out
+
+
+def caption_signals(signals: Sequence[str], lens: Sequence[int], samples_num: int, img_name, model, clip, tokenizer, image_instance,
+                    token_mask, logger, *, prompt="", batch_size=1, top_k=100, temperature=1.0, max_iter=500, alpha=0.7, beta=1,
+                    generate_order="sequential", gamma=5, pos_type=None):
+    """`--signals` of the two CLIs: what `samples_num` calls of generate_caption (signal `caption`) or control_generate_caption
+    (`positive`, `negative`: ctl_type sentiment; `pos`: ctl_type pos) at max_len = n return for every signal and every n of
+    `lens`, from one run_generation_signals call.  Returns, per signal, per length, the list of `samples_num` (generate_texts,
+    clip_scores) pairs and logs every signal's, length's and sample's final and best captions as those functions do."""
+    from . import signals as sg
+    start_time = time.time()
+    signals = sg.parse_signals(signals)
+    lens = [int(n) for n in lens]
+    if not lens:
+        raise ValueError("caption_signals: no sentence length given")
+    outs = run_generation_signals(signals, lens, samples_num, generate_order, img_name, model, clip, tokenizer, image_instance,
+                                  token_mask, prompt, logger, top_k, temperature, alpha, beta, max_iter, batch_size, gamma=gamma,
+                                  pos_template=pos_type)
+    logger.info("Finished %d signals x %d lengths x %d samples in %.3fs" % (len(signals), len(lens), samples_num, time.time() - start_time))
+    for sig, per_len in zip(signals, outs):
+        for n, per_sample in zip(lens, per_len):
+            for sample_id, (generate_texts, _) in enumerate(per_sample):
+                logger.info(f"Signal {sig}, sentence length {n}, sample {sample_id}: ")
+                for i in range(batch_size):
+                    logger.info(f"The {i + 1}-th image: {img_name[i]}")
+                    logger.info(f"final caption: {generate_texts[-2][i]}")
+                    logger.info(f"best caption: {generate_texts[-1][i]}")
+    return outs

@@ -350,6 +350,38 @@ int czc_generate_rows_len(czc_engine* e, int R, int T, int seed_len, const int32
                           const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
                           const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp, int32_t* out_ids, float* out_cos);
 
+/* czc_generate_rows_len with a czc_hyper PER ROW: one image under every control signal (plain caption, positive, negative, POS
+ * template -- the reference's --run_type / --control_type / --sentiment_type, one value per process there), or an alpha / beta /
+ * temperature sweep, in one batch.  Everything not named here is as in czc_generate_rows_len: idle steps, image_of_row, ragged
+ * lengths, snapshots, option "memo_rows".  top_k, n_mask and the POS template of czc_set_pos stay one value per call.
+ *   - len_of_row == NULL: every row has L = T - seed_len - 1 positions (the shape of czc_generate_rows_from).
+ *   - what row r computes: row r is polished with hp_of_row[r] -- its own temperature in the masked softmax
+ *     (gen_utils.py:43-44), its own alpha, beta and gamma in the fusion (gen_utils.py:77 / control_gen_utils.py:59) and its own
+ *     control (0 caption, 1 sentiment, 2 POS) and negative.  The text bridge is handed every control table that is set and
+ *     scores a candidate by its row's control; a control == 0 row takes no control score at all.
+ *   - rows are independent: row r returns what the same call returns for it when every row carries hp_of_row[r] (the caveats
+ *     of compact batches and CZC_PREC_SPLIT are those stated for czc_generate_rows_len).
+ *   - a call whose R entries are all equal takes the existing path -- czc_generate_rows_len, or czc_generate_rows_from where
+ *     len_of_row is NULL -- with that entry, and returns its bits.
+ *   - the [R] array is uploaded once, with the schedule.  A compact batch (idle rows, "memo_rows" hits) gathers the records
+ *     of the rows that run by the run list it already has: no device-to-host read beyond those of czc_generate_rows_len.
+ *   - option "memo_rows" stays exact: a row's hyper-parameters are constant over the call, so its key -- the masked row --
+ *     still determines the outcome.
+ *   - CZC_PREC_REFINE: the mass threshold theta / (beta * exp(logit_scale)) and the beta of the margin gate are row r's own,
+ *     formed on the device; guard, audit steps and the gate's bound are unchanged.
+ *   - control callback (czc_set_control_callback) with any row's control != 0: the host scorer is configured for one signal,
+ *     so every row must share control and negative, else CZC_ERR_ARG; the one-position and one-length rules of
+ *     czc_generate_rows_len apply; alpha, beta, gamma and temperature may still differ between rows.  The control tables
+ *     (czc_set_lexicon / czc_set_lexicon_pos / czc_set_pos) serve rows under different signals.
+ * Checked before any GPU work, and the engine stays usable.  CZC_ERR_ARG: a control outside {0, 1, 2}, a temperature that is
+ * not finite and > 0, a non-finite alpha, beta or gamma, and everything czc_generate_rows_len checks.  CZC_ERR_STATE, with the
+ * messages of czc_step: a control == 1 row without lexicon or callback, a control == 2 row without czc_set_pos or callback. */
+int czc_generate_rows_hp(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host,
+                         const int32_t* len_of_row_host /* NULL: every row has L = T - seed_len - 1 */,
+                         const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
+                         const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp_of_row_host /* [R] */,
+                         int32_t* out_ids, float* out_cos);
+
 /* Engine options (all are exact work reductions / kernel choices; results agree within the engine precision):
  *   "share_prefix"    (1) encode the causal prefix common to an image's K candidates once per step instead of K
  *                         times

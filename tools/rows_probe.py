@@ -48,9 +48,11 @@ ap.add_argument("--memo_rows", action="store_true", help="the memo_rows leg inst
 ap.add_argument("--off_only", action="store_true", help="--memo_rows: time the option-off arm only and leave the option alone")
 ap.add_argument("--lengths", type=lambda v: [int(n) for n in v.split(",")], default=None, metavar="L1,L2,...",
                 help="the lengths leg: one call per length against one czc_generate_rows_len call")
+ap.add_argument("--signals", default=None, metavar="caption,positive,negative",
+                help="the signals leg: one call per control signal against one czc_generate_rows_hp call (table mode)")
 args = ap.parse_args()
 if args.out is None:
-    args.out = os.path.join(ROOT, "profiles", "r09_lengths_probe.json" if args.lengths else
+    args.out = os.path.join(ROOT, "profiles", "r10_signals_probe.json" if args.signals else "r09_lengths_probe.json" if args.lengths else
                             "r09_memo_rows_probe.json" if args.memo_rows else "r08_rows_probe.json")
 
 L, K, SEED_LEN = args.L, args.K, 4
@@ -143,11 +145,58 @@ def lengths_leg():
         eng.close()
 
 
+def signals_leg():
+    """One image, every signal a row of L positions under its own run's order: one scalar call per signal (the serial arm)
+    against one czc_generate_rows_hp call, synthetic control tables, alternating repetitions."""
+    from conzic_amd import signals as sg, synth
+    sigs = sg.parse_signals(args.signals)
+    for scale in args.scales:
+        prec = runtime.choose_precision(scale)
+        su = harness.build_synthetic(False, prec, logit_scale=scale, regular_only=True, lexicon=True)
+        eng = su.engine
+        V = len(su.sv.bert_tokens)
+        eng.set_pos(synth.make_pos_tags(V), synth.pos_template_masks([["DET"], ["ADJ", "NOUN"], ["NOUN"], ["VERB"]]))
+        eng.set_image_embeds(np.random.default_rng(100).standard_normal((1, su.clip_cfg.proj)).astype(np.float32))
+        random.seed(42)
+        rows = sg.expand(sigs, [L], 1, "shuffle", args.sweeps, alpha=0.02, beta=2.0, temperature=0.1, gamma=5.0)
+        init, row_lens, positions, hypers, ior = sg.batch_rows(rows, su.bert_tok, "Image of a", 1)
+
+        def serial():
+            return [eng.generate(1, init[c].tolist(), L, SEED_LEN, K, positions[:, c].tolist(), hypers[c], n_mask=rows.n_mask,
+                                 snapshot_every=rows.every) for c in range(len(sigs))]
+
+        def one_call():
+            return eng.generate_rows_hp(init, row_lens, SEED_LEN, K, positions, hypers, image_of_row=ior, n_mask=rows.n_mask,
+                                        snapshot_every=rows.every)
+
+        ref, got = serial(), one_call()  # warm-up (workspace growth) and the comparison
+        same = all(np.array_equal(ref[c][0][:, 0], got[0][:, c]) for c in range(len(sigs)))
+        cos_diff = max(float(np.abs(ref[c][1][:, 0] - got[1][:, c]).max()) for c in range(len(sigs)))
+        t_serial, t_one = [], []
+        for _ in range(args.reps):
+            for fn, acc in ((serial, t_serial), (one_call, t_one)):
+                eng.sync()
+                t0 = time.perf_counter()
+                fn()
+                acc.append(time.perf_counter() - t0)
+        rec = dict(logit_scale=scale, precision=runtime.PRECISION_NAMES[prec], signals=sigs, L=L, K=K, sweeps=args.sweeps, order="shuffle",
+                   images=1, wall_s_serial=t_serial, wall_s_one_call=t_one, spread_serial=spread(t_serial), spread_one_call=spread(t_one),
+                   speedup_median=float(np.median(t_serial) / np.median(t_one)),
+                   speedup_min=min(a / b for a, b in zip(t_serial, t_one)), speedup_max=max(a / b for a, b in zip(t_serial, t_one)),
+                   one_call_faster_in_every_rep=all(b < a for a, b in zip(t_serial, t_one)), ids_identical=bool(same),
+                   cos_max_abs_diff=cos_diff)
+        print(json.dumps(rec), flush=True)
+        out.append(rec)
+        eng.close()
+
+
 if args.memo_rows:
     memo_rows_leg()
+elif args.signals:
+    signals_leg()
 elif args.lengths:
     lengths_leg()
-for scale in ([] if args.memo_rows or args.lengths else args.scales):
+for scale in ([] if args.memo_rows or args.lengths or args.signals else args.scales):
     prec = runtime.choose_precision(scale)
     su = harness.build_synthetic(False, prec, logit_scale=scale, regular_only=True)
     eng = su.engine

@@ -5,8 +5,8 @@ names and return conventions, executed by the native engine.
     clip = CLIP.from_state(cfg, state_dict, tokenizer)   # synthetic / already-loaded weights
 
 Returned tensors are torch CPU tensors when torch is importable (the reference returns torch
-tensors), numpy arrays otherwise.  Index-building helpers of the reference (clip/clip.py:105-144)
-belong to its retrieval baseline and are out of scope.
+tensors), numpy arrays otherwise.  The index-building helpers of the reference (clip/clip.py:105-144,
+`compute_batch_index_*`) are here too, over the same encoders; clip/clipretrieval.py is its retrieval baseline.
 """
 from __future__ import annotations
 
@@ -192,3 +192,10 @@ class CLIP:
     def compute_image_text_similarity_via_raw_text(self, image_embeds, text_list):
         text_embeds = self.compute_text_representation(text_list)
         return self.compute_image_text_similarity_via_embeddings(image_embeds, text_embeds)
+
+    # ---- clip/clip.py:105-144: what the reference builds and queries its retrieval index with -----
+    def compute_batch_index_image_features(self, image_list):
+        return self.compute_image_representation_from_image_instance(list(image_list))
+
+    def compute_batch_index_text_representation(self, text_list):
+        return self.compute_text_representation(text_list)

@@ -4,6 +4,7 @@
 // One engine = one GPU = one HIP stream.  Weights are resident for the engine's lifetime
 // (bf16 GEMM operands + fp32 LayerNorm/bias/embedding tables: ~0.75 GB of the 288 GB HBM);
 // activations live in a grow-only workspace sized by the packed CLIP row count of the step.
+#include <algorithm>
 #include <map>
 #include <string>
 #include <vector>
@@ -170,6 +171,10 @@ struct czc_engine {
   int memo_rows = 0;
   int64_t stat_memo_row_hits = 0, stat_memo_row_steps = 0;  // row-steps that took an entry / all row-steps of memo_rows calls
   int32_t* h_memo_list = nullptr; size_t h_memo_list_cap = 0;  // pinned: the active rows of a checked step, read with their count
+  // czc_index_set / czc_index_search (retrieve.hip): n L2-normalised text embeddings as split_t rows, this engine's own (a replica
+  // has none); option "index_groups": work-groups of the scan, 0 = the launcher's choice
+  split_t* d_index = nullptr; int64_t index_n = 0;
+  int index_groups = 0;
 };
 
 namespace {
@@ -1307,7 +1312,7 @@ int memo_rows_step(czc_engine* e, MemoRowsPlan& mp, int s, int* d_inp, int R, in
 // =================================================================================================
 extern "C" {
 
-int czc_version(void) { return 102; }
+int czc_version(void) { return 103; }
 
 const char* czc_last_error(const czc_engine* e) { return e ? e->err : czc::g_err; }
 
@@ -1374,6 +1379,7 @@ int czc_destroy(czc_engine* e) {
   for (void* p : e->bridge_allocs) (void)hipFree(p);
   (void)hipFree(e->d_mask); (void)hipFree(e->d_lex); (void)hipFree(e->d_lex_pos); (void)hipFree(e->d_lex_cls); (void)hipFree(e->d_img_n); (void)hipFree(e->d_staged);
   (void)hipFree(e->d_pos_tags); (void)hipFree(e->d_pos_masks);
+  (void)hipFree(e->d_index);
   for (auto& kv : e->pk) for (hipEvent_t ev : kv.second.ev) (void)hipEventDestroy(ev);
   if (e->prof_ref) (void)hipEventDestroy(e->prof_ref);
   if (e->h_totals) (void)hipHostFree(e->h_totals);
@@ -1782,6 +1788,111 @@ int czc_similarity(czc_engine* e, const float* image_embeds, const float* text_e
   return CZC_OK;
 }
 
+// ---- caption retrieval: the resident text index and its search (retrieve.hip) ---------------------------------------------------
+namespace {
+bool is_device_ptr(const void* p) {
+  hipPointerAttribute_t a;
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }  // plain host memory: not registered
+  return a.type == hipMemoryTypeDevice;
+}
+}  // namespace
+
+int czc_index_set(czc_engine* e, const float* embeds, int64_t n) {
+  if (!e || n < 0) return CZC_ERR_ARG;
+  E_HIP(hipSetDevice(e->dev));
+  e->err[0] = 0;
+  if (!embeds || n == 0) {
+    E_HIP(hipStreamSynchronize(e->st));
+    if (e->d_index) (void)hipFree(e->d_index);
+    e->d_index = nullptr; e->index_n = 0;
+    return CZC_OK;
+  }
+  const int D = e->cfg.clip_proj;
+  if (D <= 0 || D % 32 || D > 1024) return fail(e, CZC_ERR_ARG, "czc_index_set: clip_proj must be a multiple of 32 and at most 1024%s");
+  // ids are int32, and the scan's block indices run up to one stride (1024 work-groups x 4 blocks x 32 rows) past n
+  if (n > (int64_t)INT32_MAX - (1 << 18)) return fail(e, CZC_ERR_ARG, "czc_index_set: too many rows for int32 ids%s");
+  const size_t row_b = (size_t)D * 4;
+  split_t* fresh = nullptr;
+  int* flag = nullptr;
+  E_CHECK(ensure(e, "ix_flag", 32, (void**)&flag));
+  if (hipMalloc((void**)&fresh, (size_t)n * row_b) != hipSuccess) {
+    (void)hipGetLastError();
+    snprintf(e->err, sizeof(e->err), "czc_index_set: cannot allocate %zu bytes for %lld rows", (size_t)n * row_b, (long long)n);
+    return CZC_ERR_HIP;
+  }
+  int rc = 0, bad = 0;
+  auto run = [&]() -> int {
+    E_HIP(hipMemsetAsync(flag, 0, 4, e->st));
+    if (is_device_ptr(embeds)) {
+      E_CHECK(launch_normalize_split(embeds, n, D, fresh, flag, 0, e->st));
+    } else {
+      // host rows pass through a staging buffer of at most 64 MiB; each row is still read once by the kernel
+      const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n, ((int64_t)64 << 20) / (int64_t)row_b));
+      float* stage;
+      E_CHECK(ensure(e, "ix_stage", (size_t)chunk * row_b, (void**)&stage));
+      for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+        const int64_t m = std::min(chunk, n - r0);
+        E_HIP(hipMemcpyAsync(stage, embeds + r0 * D, (size_t)m * row_b, hipMemcpyDefault, e->st));
+        E_CHECK(launch_normalize_split(stage, m, D, (split_t*)((unsigned char*)fresh + (size_t)r0 * row_b), flag, 0, e->st));
+        E_HIP(hipStreamSynchronize(e->st));  // the pageable source of the next copy must not overtake this kernel's read
+      }
+    }
+    E_HIP(hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, e->st));
+    E_HIP(hipStreamSynchronize(e->st));
+    return 0;
+  };
+  rc = run();
+  if (!rc && bad) rc = fail(e, CZC_ERR_ARG, "czc_index_set: a row has norm 0 or is not finite; the previous index stays%s");
+  if (rc) { (void)hipFree(fresh); return rc; }
+  if (e->d_index) (void)hipFree(e->d_index);
+  e->d_index = fresh; e->index_n = n;
+  return CZC_OK;
+}
+
+int czc_index_size(czc_engine* e, int64_t* n) {
+  if (!e || !n) return CZC_ERR_ARG;
+  *n = e->d_index ? e->index_n : 0;
+  return CZC_OK;
+}
+
+int czc_index_search(czc_engine* e, const float* image_embeds, int Q, int k, int32_t* out_ids, float* out_cos) {
+  if (!e || !out_ids || !out_cos) return CZC_ERR_ARG;
+  E_HIP(hipSetDevice(e->dev));
+  e->err[0] = 0;
+  if (k < 1 || k > CZC_INDEX_MAX_K || Q < 1) return fail(e, CZC_ERR_ARG, "czc_index_search: need Q >= 1 and 1 <= k <= CZC_INDEX_MAX_K%s");
+  if (!e->d_index) return fail(e, CZC_ERR_STATE, "czc_index_search: no index (czc_index_set first)%s");
+  const int D = e->cfg.clip_proj;
+  const int n = (int)e->index_n;
+  const float* src = image_embeds;
+  if (!src) {
+    auto it = e->ws.find("img_raw");
+    if (e->img_B <= 0 || it == e->ws.end() || !it->second.p) return fail(e, CZC_ERR_STATE, "czc_index_search: no resident image embeddings%s");
+    if (Q > e->img_B) return fail(e, CZC_ERR_ARG, "czc_index_search: Q exceeds the resident image embeddings%s");
+    src = (const float*)it->second.p;
+  } else if (!is_device_ptr(src)) {
+    float* raw;
+    E_CHECK(ensure(e, "ix_qraw", (size_t)Q * D * 4, (void**)&raw));
+    E_HIP(hipMemcpyAsync(raw, src, (size_t)Q * D * 4, hipMemcpyDefault, e->st));
+    src = raw;
+  }
+  const int G = index_scan_groups(n, D, k, e->index_groups);
+  const size_t qk = (size_t)Q * k;
+  split_t* qs; unsigned long long* part; int32_t* out;
+  E_CHECK(ensure(e, "ix_qs", (size_t)Q * D * 4, (void**)&qs));
+  E_CHECK(ensure(e, "ix_part", qk * G * 8, (void**)&part));
+  E_CHECK(ensure(e, "ix_out", (2 * qk + Q) * 4, (void**)&out));  // ids [Q, k] | cosines [Q, k] | bad-query flags [Q]: one read
+  E_CHECK(launch_normalize_split(src, Q, D, qs, out + 2 * qk, 1, e->st));
+  E_CHECK(launch_index_search(e->d_index, n, D, qs, Q, k, G, part, out, (float*)(out + qk), e->st));
+  std::vector<int32_t> host(2 * qk + Q);
+  E_HIP(hipMemcpyAsync(host.data(), out, host.size() * 4, hipMemcpyDeviceToHost, e->st));
+  E_HIP(hipStreamSynchronize(e->st));
+  for (int q = 0; q < Q; ++q)
+    if (host[2 * qk + q]) return fail(e, CZC_ERR_ARG, "czc_index_search: a query row has norm 0 or is not finite%s");
+  memcpy(out_ids, host.data(), qk * 4);
+  memcpy(out_cos, host.data() + qk, qk * 4);
+  return CZC_OK;
+}
+
 int czc_step(czc_engine* e, int32_t* inp, int B, int T, int gen_idx, int n_mask, int dot_allowed, int top_k,
              const czc_hyper* hp, const czc_step_out* out) {
   if (!e || !inp || !hp || B <= 0) return CZC_ERR_ARG;
@@ -2167,6 +2278,11 @@ int czc_set_option(czc_engine* e, const char* name, int value) {
   if (!strcmp(name, "refine_rows16")) { const int old = e->refine_rows16; e->refine_rows16 = value ? 1 : 0; const int rc = fold_ready(); if (rc) e->refine_rows16 = old; return rc; }
   if (!strcmp(name, "memo")) { e->memo = value ? 1 : 0; return CZC_OK; }
   if (!strcmp(name, "memo_rows")) { e->memo_rows = value ? 1 : 0; return CZC_OK; }
+  if (!strcmp(name, "index_groups")) {
+    if (value < 0 || value > 1024) return fail(e, CZC_ERR_ARG, "option %s: 0 (chosen by the launcher) or 1..1024", name);
+    e->index_groups = value;
+    return CZC_OK;
+  }
   if (!strcmp(name, "refine_rows16_x1000")) { e->refine_rows16_factor = value < 1000 ? 1.f : (float)value / 1000.f; return CZC_OK; }
   return fail(e, CZC_ERR_ARG, "unknown option %s", name);
 }
@@ -2181,7 +2297,7 @@ int czc_get_option(czc_engine* e, const char* name, int* value) {
       {"refine_samples", e->refine_samples}, {"refine_samples_step", e->refine_samples_step}, {"refine_theta_x1000", (int)lrintf(e->refine_theta_x * 1000.f)},
       {"refine_theta_gen_x1000", (int)lrintf(e->refine_theta_gen * 1000.f)},
       {"refine_guard_x1e6", (int)lrintf(e->refine_guard_dev * 1e6f)}, {"refine_gate_x1e6", (int)lrintf(e->refine_gate_delta * 1e6f)},
-      {"refine_rows16", e->refine_rows16}, {"memo", e->memo}, {"memo_rows", e->memo_rows}, {"refine_rows16_x1000", (int)lrintf(e->refine_rows16_factor * 1000.f)},
+      {"refine_rows16", e->refine_rows16}, {"memo", e->memo}, {"memo_rows", e->memo_rows}, {"index_groups", e->index_groups}, {"refine_rows16_x1000", (int)lrintf(e->refine_rows16_factor * 1000.f)},
       // read-only, derived: the trip point / gate bound in force inside czc_generate (x refine_rows16_factor on fp16 rows)
       {"refine_guard_generate_x1e6", (int)lrintf(e->refine_guard_dev * f16x * 1e6f)},
       {"refine_gate_generate_x1e6", (int)lrintf(e->refine_gate_delta * f16x * 1e6f)},

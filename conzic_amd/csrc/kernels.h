@@ -337,6 +337,16 @@ int launch_refine_plan(const int* clip_len, const int* trunk_len, const int* lis
 int launch_refine_finish(const int* own_off, const int* own_len, const int* count, const int* count_off, const int* kr_dev, int B, int K,
                          int* pre_off, int* eos_idx, hipStream_t st);
 
+// ---- caption retrieval (retrieve.hip) ----------------------------------------------------------------------------------
+// fp32 rows -> L2-normalised split_t rows, one pass; a row whose norm is 0 or not finite raises bad[row * bad_stride]
+// (bad_stride = 0: one shared flag, only ever set) and is stored as zeros.  D % 32 == 0, D <= 1024.
+int launch_normalize_split(const float* src, long n, int D, split_t* dst, int* bad, int bad_stride, hipStream_t st);
+int index_scan_groups(int n, int D, int k, int groups);
+// Q normalised split_t queries against n normalised split_t index rows: out_ids / out_cos [Q, k], ordered by (cosine descending,
+// id ascending), tail (-1, -inf).  part: workspace of Q x G x k 8-byte keys, G = index_scan_groups(n, D, k, groups).
+int launch_index_search(const split_t* index, int n, int D, const split_t* queries, int Q, int k, int G,
+                        unsigned long long* part, int* out_ids, float* out_cos, hipStream_t st);
+
 // ---- czc_internal_hooks (declared below, private to the build): what libconzic_hip_test.so may reach inside this library -----------
 // The product library has hidden visibility; the hook library (api_test.hip) gets the launchers it wraps and the
 // process-wide kernel-family switches it flips through this table instead of through exported C++ symbols.

@@ -24,7 +24,7 @@ def get_args(argv=None):
     p.add_argument("--seed", type=int, default=42)
     p.add_argument("--batch_size", type=int, default=1)
     p.add_argument("--device", type=str, default='cuda', choices=['cuda'])
-    p.add_argument('--run_type', default='controllable', nargs='?', choices=['caption', 'controllable', 'infill'])
+    p.add_argument('--run_type', default='controllable', nargs='?', choices=['caption', 'controllable', 'infill', 'retrieve'])
     p.add_argument('--prompt', default='Image of a', type=str)
     p.add_argument('--order', default='shuffle', nargs='?', choices=['sequential', 'shuffle', 'span', 'random'])
     p.add_argument('--control_type', default='sentiment', nargs='?', choices=["sentiment", "pos"])
@@ -71,7 +71,40 @@ def get_args(argv=None):
     p.add_argument("--infill_positions", default="blanks", choices=["blanks", "all"],
                    help="--run_type infill: polish the blanks only, or every position of every caption (polishing a draft / "
                         "resuming an earlier result)")
+    p.add_argument("--index_matrix_path", type=str, default=None,
+                   help="--run_type retrieve: the text index, one row of space-separated floats per caption (or .npy), as the "
+                        "reference's clip/build_text_index.py writes it; with --mapping_dict_path")
+    p.add_argument("--mapping_dict_path", type=str, default=None,
+                   help="--run_type retrieve: JSON {row number: caption} of --index_matrix_path")
+    p.add_argument("--index_captions", type=str, default=None, metavar="FILE",
+                   help="--run_type retrieve: build the index on the spot from FILE, one caption per line, instead of loading one")
+    p.add_argument("--retrieve_k", type=int, default=1, help="--run_type retrieve: nearest captions per image (1..64)")
+    p.add_argument("--polish", action="store_true",
+                   help="--run_type retrieve: the retrieved captions are the drafts of a Gibbs polish of every position "
+                        "(num_iterations sweeps in --order sequential or shuffle, --candidate_k, alpha / beta / temperature), all "
+                        "of them rows of one engine call")
     a = p.parse_args(argv)
+    if a.run_type == "retrieve":
+        from conzic_amd import native
+        files = a.index_matrix_path is not None or a.mapping_dict_path is not None
+        if files and a.index_captions is not None:
+            p.error("--run_type retrieve takes --index_matrix_path with --mapping_dict_path, or --index_captions, not both")
+        if files and (a.index_matrix_path is None or a.mapping_dict_path is None):
+            p.error("--index_matrix_path and --mapping_dict_path go together")
+        if not files and a.index_captions is None:
+            p.error("--run_type retrieve needs --index_matrix_path with --mapping_dict_path, or --index_captions")
+        if not 1 <= a.retrieve_k <= native.INDEX_MAX_K:
+            p.error(f"--retrieve_k must be between 1 and {native.INDEX_MAX_K}")
+        if a.polish and a.order not in ("sequential", "shuffle"):
+            p.error("--run_type retrieve --polish visits the positions in --order sequential or shuffle")
+        if a.sentence_lens is not None:
+            p.error("--sentence_lens does not apply to --run_type retrieve (a retrieved caption has its own length)")
+        if a.signals is not None:
+            p.error("--signals does not apply to --run_type retrieve")
+        if a.caption:
+            p.error("--caption belongs to --run_type infill")
+    elif a.polish or a.index_matrix_path or a.mapping_dict_path or a.index_captions:
+        p.error("--index_matrix_path / --mapping_dict_path / --index_captions / --polish belong to --run_type retrieve")
     if a.run_type == "infill" and not a.caption:
         p.error("--run_type infill needs at least one --caption")
     if a.run_type == "infill" and a.order not in ("sequential", "shuffle"):
@@ -143,6 +176,15 @@ def main(argv=None):
     image_instance = images if args.batch_size > 1 else images[0]
     img_name = [f"img{j}" for j in range(args.batch_size)]
     t0 = time.time()
+    if args.run_type == "retrieve":
+        from conzic_amd.retrieval import index_from_args
+        from conzic_amd.runtime import retrieve_cli
+        retrieve_cli(index_from_args(args, clip, logger), args.polish, img_name, lm_model, clip, lm_tokenizer, image_instance,
+                     token_mask, logger, k=args.retrieve_k, prompt=args.prompt, top_k=args.candidate_k,
+                     temperature=args.lm_temperature, max_iter=args.num_iterations, alpha=args.alpha, beta=args.beta,
+                     generate_order=args.order)
+        logger.info("total %.2fs" % (time.time() - t0))
+        return
     if args.run_type == "infill":
         # caption i describes image i (batch_size captions), or every caption the one image (batch_size 1)
         from conzic_amd.runtime import infill_captions

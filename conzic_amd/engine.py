@@ -506,6 +506,43 @@ class Engine:
         self._ck(self.lib.czc_similarity(self.h, ie.ctypes.data, te.ctypes.data, B, K, cs.ctypes.data, cr.ctypes.data), "czc_similarity")
         return cs, cr
 
+    # ---- caption retrieval ---------------------------------------------------------------------
+    def index_set(self, embeds):
+        """czc_index_set: fp32 [n, proj] un-normalised text embeddings (numpy, or a device tensor) become this engine's index
+        (a replica has none of its own)."""
+        if isinstance(embeds, np.ndarray) or not hasattr(embeds, "data_ptr"):
+            embeds = np.ascontiguousarray(embeds, dtype=np.float32)
+        if embeds.ndim != 2 or int(embeds.shape[1]) != self.clip_cfg.proj:
+            raise ValueError(f"index rows must be [n, {self.clip_cfg.proj}], got {tuple(embeds.shape)}")
+        self._ck(self.lib.czc_index_set(self.h, _ptr(embeds), int(embeds.shape[0])), "czc_index_set")
+
+    def index_clear(self):
+        self._ck(self.lib.czc_index_set(self.h, None, 0), "czc_index_set")
+
+    def index_size(self) -> int:
+        n = C.c_int64()
+        self._ck(self.lib.czc_index_size(self.h, C.byref(n)), "czc_index_size")
+        return int(n.value)
+
+    def index_search(self, image_embeds=None, k: int = 1, Q: Optional[int] = None):
+        """czc_index_search: (ids int32 [Q, k], cosines fp32 [Q, k]) ordered by (cosine descending, id ascending).
+        image_embeds fp32 [Q, proj] un-normalised (numpy or device tensor); None = the first Q resident image embeddings."""
+        if image_embeds is None:
+            if Q is None:
+                raise ValueError("index_search(None) needs Q, the number of resident image embeddings to search with")
+        else:
+            if isinstance(image_embeds, np.ndarray) or not hasattr(image_embeds, "data_ptr"):
+                image_embeds = np.ascontiguousarray(image_embeds, dtype=np.float32)
+            if image_embeds.ndim != 2 or int(image_embeds.shape[1]) != self.clip_cfg.proj:
+                raise ValueError(f"queries must be [Q, {self.clip_cfg.proj}], got {tuple(image_embeds.shape)}")
+            Q = int(image_embeds.shape[0])
+        # (the C ABI checks Q and k: wrong values come back as CZC_ERR_ARG; the buffers only have to exist)
+        ids = np.empty((max(int(Q), 0), max(int(k), 0)), dtype=np.int32)
+        cos = np.empty(ids.shape, dtype=np.float32)
+        self._ck(self.lib.czc_index_search(self.h, _ptr(image_embeds), int(Q), int(k), ids.ctypes.data, cos.ctypes.data),
+                 "czc_index_search")
+        return ids, cos
+
     def set_option(self, name: str, value: int):
         self._ck(self.lib.czc_set_option(self.h, name.encode(), int(value)), f"czc_set_option({name})")
         self._record("option:" + name, "set_option", name, int(value))

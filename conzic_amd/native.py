@@ -26,6 +26,8 @@ PREC_SPLIT = 3
 PREC_FP16 = 4
 PREC_REFINE = 5
 CLIP_MAX_LEN = 77
+MAX_BERT_LEN = 64   # include/conzic_hip.h CZC_MAX_BERT_LEN: tokens of a BERT row, [CLS] and [SEP] included
+INDEX_MAX_K = 64  # include/conzic_hip.h CZC_INDEX_MAX_K: the largest k of czc_index_search
 POS_IDLE = -1   # include/conzic_hip.h CZC_POS_IDLE: the row sits the step out (czc_generate_rows_from)
 
 
@@ -106,6 +108,9 @@ SIGNATURES = {
     "czc_set_image_embeds": (_I, [_P, _P, _I]),
     "czc_encode_text": (_I, [_P, _P, _P, _I, _P]),
     "czc_similarity": (_I, [_P, _P, _P, _I, _I, _P, _P]),
+    "czc_index_set": (_I, [_P, _P, C.c_int64]),
+    "czc_index_size": (_I, [_P, C.POINTER(C.c_int64)]),
+    "czc_index_search": (_I, [_P, _P, _I, _I, _P, _P]),
     "czc_step": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(Hyper), C.POINTER(StepOut)]),
     "czc_generate": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _P, _I, C.POINTER(Hyper), _P, _P]),
     "czc_generate_rows": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P, _I, C.POINTER(Hyper), _P, _P]),

@@ -253,6 +253,50 @@ def infill_batches(args, all_batches, own_lo, own_hi, rank, world, img_dir, lm_m
         write_results(result_dir(args, "infill", 0), all_results)
 
 
+def retrieve_batches(args, all_batches, own_lo, own_hi, rank, world, img_dir, lm_model, clip, lm_tokenizer, token_mask, logger):
+    """--run_type retrieve: the --retrieve_k nearest index captions of every image (runtime.retrieve_captions), with --polish as
+    the drafts of one polishing call per batch (runtime.retrieve_then_polish).  One pass (sample_0), keyed by image name (`name#j`
+    for the j-th nearest when --retrieve_k > 1): without --polish best_clipscore.json holds the retrieved captions; with it
+    iter_0.json holds them, iter_<s>.json the captions after sweep s and best_clipscore.json the best-by-CLIP ones (a caption that
+    could not be a draft keeps its retrieved text throughout)."""
+    from PIL import Image
+    from conzic_amd.retrieval import index_from_args
+    from conzic_amd.runtime import retrieve_cli
+    index = index_from_args(args, clip, logger)
+    K = args.retrieve_k
+    n_files = args.num_iterations + 2 if args.polish else 1
+    all_results = [None] * n_files
+    for batch_idx, name_batch in enumerate(all_batches):
+        if not (own_lo <= batch_idx < own_hi):
+            continue
+        logger.info(f"The {batch_idx + 1}-th batch:")
+        imgs = [Image.open(os.path.join(img_dir, n)).convert("RGB") for n in name_batch]
+        out = retrieve_cli(index, args.polish, name_batch, lm_model, clip, lm_tokenizer, imgs, token_mask, logger, k=K,
+                           prompt=args.prompt, top_k=args.candidate_k, temperature=args.lm_temperature,
+                           max_iter=args.num_iterations, alpha=args.alpha, beta=args.beta, generate_order=args.order)
+        for b, res in enumerate(out):
+            polished = dict(zip(res["drafts"], res["polished"]))
+            for j, (caption, _, _) in enumerate(res["retrieved"]):
+                key = name_batch[b] if K == 1 else f"{name_batch[b]}#{j}"
+                texts = [caption] * n_files
+                if j in polished:
+                    gen_texts = [t[0] for t in polished[j][0]]
+                    sweeps = gen_texts[:-1] + [gen_texts[-2] if len(gen_texts) > 1 else caption] * (args.num_iterations + 1 - len(gen_texts))
+                    texts = [caption] + sweeps + gen_texts[-1:]
+                all_results = merge_results(all_results, [[t] for t in texts], [key])
+    if world > 1:
+        import torch.distributed as tdist
+        parts = [None] * world
+        tdist.all_gather_object(parts, all_results)
+        all_results = [None] * n_files
+        for part in parts:  # rank order == batch order
+            for it, d in enumerate(part):
+                if d is not None:
+                    all_results[it] = {**(all_results[it] or {}), **d}
+    if rank == 0:
+        write_results(result_dir(args, "retrieve_polish" if args.polish else "retrieve", 0), all_results)
+
+
 def main(argv=None):
     args = get_args(argv)
     import logging
@@ -316,6 +360,9 @@ def main(argv=None):
     all_batches = list(batches(names, args.batch_size))
     own_lo, own_hi = czd.shard_range(len(all_batches), rank, world)
     embed_cache = {}  # batch index -> image_embeds [B, proj]: the ViT runs once per image, not once per sample
+    if args.run_type == "retrieve":
+        retrieve_batches(args, all_batches, own_lo, own_hi, rank, world, img_dir, lm_model, clip, lm_tokenizer, token_mask, logger)
+        return
     if args.run_type == "infill":
         infill_batches(args, all_batches, own_lo, own_hi, rank, world, img_dir, lm_model, clip, lm_tokenizer, token_mask, logger)
         return

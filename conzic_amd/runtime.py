@@ -866,3 +866,85 @@ def caption_signals(signals: Sequence[str], lens: Sequence[int], samples_num: in
                     logger.info(f"final caption: {generate_texts[-2][i]}")
                     logger.info(f"best caption: {generate_texts[-1][i]}")
     return outs
+
+
+# ---- caption retrieval (conzic_amd/retrieval.py; czc_index_search) -------------------------------------------------------------
+def retrieve_captions(index, img_name, model, clip, tokenizer, image_instance, logger, k: int = 1):
+    """The reference's retrieval baseline (clip/clipretrieval.py `search_text`) for a batch and any k: per image of
+    `image_instance` the k captions of `index` (retrieval.TextIndex) nearest to it, as (caption, cosine, id), best first.  The
+    images are encoded once and scored against the engine's resident index in one czc_index_search call."""
+    if model is not None:
+        get_engine(model, clip, tokenizer)   # the index lives on the engine the generation calls use
+    hits = index.search(clip, image_instance, k)
+    for b, per_image in enumerate(hits):
+        for j, (caption, cosine, row) in enumerate(per_image):
+            logger.info(f"The {b + 1}-th image: {img_name[b]}, retrieved {j + 1}/{len(per_image)} (row {row}), "
+                        f"clip score {cosine:.3f}: {caption}")
+    return hits
+
+
+def draft_skip_reason(tokenizer, prompt: str, caption: str) -> Optional[str]:
+    """Why `caption` cannot be a draft row of run_infill, or None: infill.parse_template must give it at least one token behind the
+    prompt and at most CZC_MAX_BERT_LEN tokens with [CLS], the prompt and [SEP]."""
+    from . import infill
+    try:
+        ids, _, L, _ = infill.parse_template(tokenizer, prompt, caption)
+    except ValueError as exc:
+        return str(exc)
+    if L < 1:
+        return "empty after tokenising"
+    if int(ids.size) > native.MAX_BERT_LEN:
+        return f"{int(ids.size)} tokens with the prompt, more than the {native.MAX_BERT_LEN} a row holds"
+    return None
+
+
+def retrieve_then_polish(index, img_name, model, clip, tokenizer, image_instance, token_mask, prompt, logger, *, k: int = 1,
+                         **run_infill_kwargs):
+    """Start the Gibbs polish from the nearest known captions instead of from [MASK]s: the k retrieved captions of every image
+    are the drafts of ONE run_infill(..., positions="all", image_of_caption=...) call.  A caption that cannot be a draft
+    (draft_skip_reason) is skipped and logged.  Returns one dict per image: "retrieved": [(caption, cosine, id), ...] as
+    retrieve_captions gives them, "drafts": the positions in that list of the captions that were polished, "polished": run_infill's
+    (gen_texts_list, clip_score_sequence) pair of each of those, in the same order."""
+    for fixed in ("positions", "image_of_caption"):
+        if fixed in run_infill_kwargs:
+            raise TypeError(f"retrieve_then_polish sets run_infill's {fixed} itself")
+    hits = retrieve_captions(index, img_name, model, clip, tokenizer, image_instance, logger, k=k)
+    out = [dict(retrieved=per_image, drafts=[], polished=[]) for per_image in hits]
+    drafts, image_of_caption = [], []
+    for b, per_image in enumerate(hits):
+        for j, (caption, _, row) in enumerate(per_image):
+            why = draft_skip_reason(tokenizer, prompt, caption)
+            if why is not None:
+                logger.info(f"The {b + 1}-th image: {img_name[b]}, retrieved caption {j + 1} (row {row}) is not polished: {why}")
+                continue
+            out[b]["drafts"].append(j)
+            drafts.append(caption)
+            image_of_caption.append(b)
+    if drafts:
+        from clip.clip import ImageEmbeds
+        polished = run_infill(drafts, img_name, model, clip, tokenizer, ImageEmbeds(clip.last_image_embeds()), token_mask, prompt,
+                              logger, positions="all", image_of_caption=image_of_caption, **run_infill_kwargs)
+        for b, res in zip(image_of_caption, polished):
+            out[b]["polished"].append(res)
+    return out
+
+
+def retrieve_cli(index, polish: bool, img_name, model, clip, tokenizer, image_instance, token_mask, logger, *, k=1, prompt="",
+                 top_k=100, temperature=1.0, max_iter=10, alpha=0.7, beta=1, generate_order="sequential"):
+    """`--run_type retrieve [--polish]` of the two CLIs; returns what retrieve_then_polish returns (without --polish: nothing
+    polished), logging every polished caption's final and best text as infill_captions does."""
+    start_time = time.time()
+    if not polish:
+        out = [dict(retrieved=h, drafts=[], polished=[])
+               for h in retrieve_captions(index, img_name, model, clip, tokenizer, image_instance, logger, k=k)]
+    else:
+        out = retrieve_then_polish(index, img_name, model, clip, tokenizer, image_instance, token_mask, prompt, logger, k=k,
+                                   order="sequential" if generate_order == "sequential" else "shuffle", max_iters=max_iter,
+                                   top_k=top_k, temperature=temperature, alpha=alpha, beta=beta)
+        for b, res in enumerate(out):
+            for j, (generate_texts, _) in zip(res["drafts"], res["polished"]):
+                logger.info(f"The {b + 1}-th image: {img_name[b]}, draft: {res['retrieved'][j][0]}")
+                logger.info(f"final caption: {generate_texts[-2][0] if len(generate_texts) > 1 else 'None'}")
+                logger.info(f"best caption: {generate_texts[-1][0]}")
+    logger.info("Finished in %.3fs" % (time.time() - start_time))
+    return out

@@ -473,6 +473,27 @@ int czc_set_option(czc_engine* e, const char* name, int value);
  *       option on afterwards returns CZC_ERR_STATE). */
 int czc_get_option(czc_engine* e, const char* name, int* value);
 
+/* ---- caption retrieval ------------------------------------------------------------------- */
+/* A resident index of text embeddings and its search: "which of these n known captions is closest to this image?"  One launch
+ * scores Q images against the n rows (split-fp16 MFMA, three passes, fp32 accumulation: cosines within 2e-6 of fp64) and keeps
+ * the best k per image; the [Q, n] score matrix is never formed.  The search is the same in every engine precision. */
+#define CZC_INDEX_MAX_K 64
+/* fp32 [n, clip_proj] text embeddings, un-normalised, host or device pointer.  Replaces the engine's index; embeds == NULL or
+ * n == 0 drops it.  Rows are L2-normalised on the device.  A row whose norm is 0 or not finite -> CZC_ERR_ARG (one flag read at
+ * set time, none on the search path) and the previous index stays.  clip_proj must be a multiple of 32 and at most 1024
+ * (CZC_ERR_ARG otherwise); n is limited by int32 ids (2^31 - 2^18 rows) and by memory (4 bytes per element; CZC_ERR_HIP with a
+ * message when the allocation fails).  The index belongs to this engine: czc_destroy frees it, czc_replicate does not copy it. */
+int czc_index_set(czc_engine* e, const float* embeds, int64_t n);
+int czc_index_size(czc_engine* e, int64_t* n);
+/* Q images against the index.  image_embeds fp32 [Q, clip_proj] un-normalised (host or device); NULL = the engine's resident
+ * image embeddings (czc_encode_images / czc_set_image_embeds), the first Q of them.
+ * out_ids int32 [Q, k], out_cos fp32 [Q, k] (host): per image the k rows of largest cosine, ordered by (cosine descending, id
+ * ascending).  With fewer than k rows the tail is id -1, cosine -inf.  The cosine of an (image, row) pair has the same bits
+ * wherever the row sits in the index, whatever Q, n and option "index_groups" are; identical rows tie and come back lowest id
+ * first.  No index -> CZC_ERR_STATE; k < 1 or k > CZC_INDEX_MAX_K, Q < 1, a zero / non-finite query row -> CZC_ERR_ARG.
+ * Option "index_groups" (0): work-groups of the scan, 0 = chosen by the launcher, 1..1024 taken as given. */
+int czc_index_search(czc_engine* e, const float* image_embeds, int Q, int k, int32_t* out_ids, float* out_cos);
+
 /* ---- measurement ------------------------------------------------------------------------- */
 /* HIP-event timing of kernel classes on the engine's own stream (bench.py roofline leg).  on: 0 off, 1 an event pair
  * around every kernel class (3 % slower at B = 256, 37 % at B = 1), 2 only around the CLIP-text tower's classes: its

@@ -558,4 +558,38 @@ int czc_test_combine(int B, int K, int D, const float* text_feat, const float* i
   return 0;
 }
 
+int czc_test_combine_draw(int B, int K, int D, const float* text_feat, const float* img_embeds, float logit_scale,
+                          const float* probs, const float* senti_raw, const float* repeats, const czc_hyper* hp,
+                          const czc_draw* draw, uint32_t step, float* final_score, int32_t* best) {
+  DevPool pool;
+  const size_t bk = (size_t)B * K;
+  float* dt = (float*)pool.up(text_feat, bk * D * 4); T_PTR(dt);
+  float* di = (float*)pool.up(img_embeds, (size_t)B * D * 4); T_PTR(di);
+  float* din = (float*)pool.alloc((size_t)B * D * 4); T_PTR(din);
+  float* dp = (float*)pool.up(probs, bk * 4); T_PTR(dp);
+  float* ds = senti_raw ? (float*)pool.up(senti_raw, bk * 4) : nullptr;
+  float* dr = repeats ? (float*)pool.up(repeats, bk * 4) : nullptr;
+  int* dcand = (int*)pool.alloc(bk * 4); T_PTR(dcand);
+  T_HIP(hipMemset(dcand, 0, bk * 4));
+  float* o1 = (float*)pool.alloc(bk * 4); float* o2 = (float*)pool.alloc(bk * 4); float* o3 = (float*)pool.alloc(bk * 4);
+  int* ob = (int*)pool.alloc((size_t)B * 4); float* oc = (float*)pool.alloc((size_t)B * 4);
+  T_PTR(o1); T_PTR(o2); T_PTR(o3); T_PTR(ob); T_PTR(oc);
+  static_assert(sizeof(RowDraw) == sizeof(czc_draw), "RowDraw is czc_draw as the kernels read it");
+  RowDraw* dd = (RowDraw*)pool.up(draw, (size_t)B * sizeof(czc_draw)); T_PTR(dd);
+  int* dcol = (int*)pool.alloc((size_t)B * 4); T_PTR(dcol);  // the drawing instantiation is a per-row one; nothing is written back (inp null)
+  T_HIP(hipMemset(dcol, 0, (size_t)B * 4));
+  T_CHECK(launch_l2_normalize(di, B, D, din, nullptr));
+  CombineArgs a;
+  a.text_feat = dt; a.img_n = din; a.logit_scale_exp = expf(logit_scale); a.probs = dp; a.cand = dcand;
+  a.senti_raw = ds; a.repeats = dr; a.alpha = hp->alpha; a.beta = hp->beta; a.gamma = hp->gamma;
+  a.use_senti = (ds && (dr || hp->control == 2)) ? hp->control : 0; a.B = B; a.K = K; a.D = D; a.clip_score = o1; a.clip_ref = o2;
+  a.final_score = o3; a.best = ob; a.best_cos = oc; a.inp = nullptr; a.T = 0; a.gen_idx = 0;
+  a.gen_rows = dcol; a.draw_rows = dd; a.draw_step = step;
+  T_CHECK(launch_combine(a, nullptr));
+  T_HIP(hipDeviceSynchronize());
+  T_HIP(hipMemcpy(final_score, o3, bk * 4, hipMemcpyDeviceToHost));
+  T_HIP(hipMemcpy(best, ob, (size_t)B * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 }  // extern "C"

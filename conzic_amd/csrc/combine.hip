@@ -47,13 +47,36 @@ __global__ __launch_bounds__(256) void cosine_kernel(const float* text_feat, con
   }
 }
 
+// Philox4x32-10 (Salmon et al., SC'11): counter (c0, c1, 0, 0), key (k0, k1) -> four 32-bit words.  Counter-based, so the word
+// of (row seed, step, candidate) is a pure function of those three: no state, no order, no neighbour.
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned k0, unsigned k1, unsigned out[4]) {
+  unsigned c2 = 0u, c3 = 0u;
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
 // ROWS: the write-back column is the row's own (a.gen_rows[b], czc_generate_rows)
 // HP: so are alpha, beta, gamma and the control signal (a.hp_rows[b], czc_generate_rows_hp): one work-group serves one row, so
 // every branch on them is uniform over the work-group, as in the scalar form
-template <bool ROWS, bool HP>
+// DRAW (czc_generate_rows_draw): a row with a.draw_rows[b].tau > 0 draws its winner from softmax_K(final / tau) by the Gumbel-max
+// rule instead of taking the argmax.  For candidate k at step counter c = step0 + a.draw_step:
+//   x = word (k & 3) of Philox4x32-10(counter (c, k >> 2, 0, 0), key (seed_lo, seed_hi));   u = ((x >> 9) + 0.5) * 2^-23
+//   (exact in fp32 and strictly inside (0, 1));   g = -logf(-logf(u));   z_k = final_k / tau + g,  z_k = -inf where probs_k == 0
+//   (the candidates the token mask turned into id 0, or that BERT gives no mass);   winner = first index of max z.
+// No eligible candidate: the first argmax of final, as without the draw.  One thread per candidate in the strided loop the
+// other passes use; tau is the row's, so the branch is uniform over the work-group.  A tau == 0 row runs the argmax code below
+// on s_fin as the other instantiations do.
+template <bool ROWS, bool HP, bool DRAW>
 __global__ __launch_bounds__(CB_THREADS) void combine_kernel(CombineArgs a) {
   __shared__ float s_cos[CB_MAXK];
   __shared__ float s_fin[CB_MAXK];
+  __shared__ float s_z[DRAW ? CB_MAXK : 1];
   __shared__ float red[8];
   __shared__ int s_best;
   const int b = blockIdx.x;
@@ -141,14 +164,34 @@ __global__ __launch_bounds__(CB_THREADS) void combine_kernel(CombineArgs a) {
     s_cos[k] = ref;
   }
   __syncthreads();
+  const float* s_sel = s_fin;  // what the argmax below runs on: the fused scores, or a drawing row's perturbed scores
+  if (DRAW) {
+    const RowDraw dr = a.draw_rows[b];
+    if (dr.tau > 0.f) {
+      const unsigned ctr = dr.step0 + a.draw_step;
+      float zm = -INFINITY;
+      for (int k = tid; k < K; k += CB_THREADS) {
+        unsigned w[4];
+        philox4x32_10(ctr, (unsigned)k >> 2, dr.seed_lo, dr.seed_hi, w);
+        const unsigned x = (k & 3) == 0 ? w[0] : (k & 3) == 1 ? w[1] : (k & 3) == 2 ? w[2] : w[3];
+        const float u = ((float)(x >> 9) + 0.5f) * 1.1920928955078125e-07f;  // 2^-23
+        const float g = -logf(-logf(u));
+        const float z = a.probs[(long)b * K + k] == 0.f ? -INFINITY : s_fin[k] / dr.tau + g;
+        s_z[k] = z;
+        zm = fmaxf(zm, z);
+      }
+      zm = blk_reduce(zm, red, 1);  // (its barriers publish s_z)
+      if (zm > -INFINITY) s_sel = s_z;  // uniform: zm is the work-group's; no eligible candidate keeps the argmax of s_fin
+    }
+  }
   // first argmax (torch.argmax returns the first maximal index)
   float bm = -INFINITY;
-  for (int k = tid; k < K; k += CB_THREADS) bm = fmaxf(bm, s_fin[k]);
+  for (int k = tid; k < K; k += CB_THREADS) bm = fmaxf(bm, s_sel[k]);
   bm = blk_reduce(bm, red, 1);
   if (tid == 0) s_best = K;
   __syncthreads();
   for (int k = tid; k < K; k += CB_THREADS)
-    if (s_fin[k] == bm) atomicMin(&s_best, k);
+    if (s_sel[k] == bm) atomicMin(&s_best, k);
   __syncthreads();
   if (tid == 0) {
     const int bi = s_best < K ? s_best : 0;  // all-NaN scores: keep candidate 0
@@ -178,16 +221,20 @@ __global__ __launch_bounds__(CB_THREADS) void combine_kernel(CombineArgs a) {
 // image carries the same common error).  gated[0] counts those images, gated[1] all images.
 // HP (czc_generate_rows_hp): theta_ is the base threshold and beta_ the logit scale; the row's beta is hp_rows[b].beta and its
 // threshold theta_ / max(beta * scale, 1e-6), the expression the engine forms on the host for the scalar form
-template <bool HP>
+// DRAW (czc_generate_rows_draw): the gate proves an argmax, so a row that draws its winner (draw_rows[b].tau > 0) is never gated,
+// nor counted in gated[]: it takes the full selection below, and the final combine draws from the scores that leaves
+template <bool HP, bool DRAW>
 __global__ __launch_bounds__(CB_THREADS) void refine_select_kernel(const float* clip_score, const float* final_score, int K,
-                                                                   float theta_, int m_samples, float gate_h, float beta_, int need_cos,
-                                                                   const RowHyper* hp_rows, int* gated, int* kind, int* list, int* count) {
+                                                                   float theta_, int m_samples, float gate_h_, float beta_, int need_cos,
+                                                                   const RowHyper* hp_rows, const RowDraw* draw_rows, int* gated, int* kind,
+                                                                   int* list, int* count) {
   __shared__ float s_p[CB_MAXK];
   __shared__ float s_f[CB_MAXK];
   __shared__ int s_kind[CB_MAXK];
   __shared__ float red[8];
   __shared__ int s_arg;
   const int b = blockIdx.x, tid = threadIdx.x;
+  const float gate_h = (DRAW && draw_rows[b].tau > 0.f) ? 0.f : gate_h_;
   const float beta = HP ? hp_rows[b].beta : beta_;
   const float theta = HP ? theta_ / fmaxf(beta * beta_, 1e-6f) : theta_;
   for (int k = tid; k < K; k += CB_THREADS) {
@@ -277,8 +324,8 @@ int launch_refine_select(const float* clip_score, const float* final_score, int 
     snprintf(g_err, sizeof(g_err), "refine_select: K=%d > %d", K, CB_MAXK);
     return 1;
   }
-  hipLaunchKernelGGL(refine_select_kernel<false>, dim3(B), dim3(CB_THREADS), 0, st, clip_score, final_score, K, theta, m_samples, gate_h, beta,
-                     need_cos, nullptr, gated, kind, list, count);
+  hipLaunchKernelGGL((refine_select_kernel<false, false>), dim3(B), dim3(CB_THREADS), 0, st, clip_score, final_score, K, theta, m_samples, gate_h, beta,
+                     need_cos, nullptr, nullptr, gated, kind, list, count);
   CZC_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -290,8 +337,25 @@ int launch_refine_select_rows(const float* clip_score, const float* final_score,
     snprintf(g_err, sizeof(g_err), "refine_select: K=%d > %d or no hp_rows", K, CB_MAXK);
     return 1;
   }
-  hipLaunchKernelGGL(refine_select_kernel<true>, dim3(B), dim3(CB_THREADS), 0, st, clip_score, final_score, K, theta_base, m_samples, gate_h,
-                     scale, need_cos, hp_rows, gated, kind, list, count);
+  hipLaunchKernelGGL((refine_select_kernel<true, false>), dim3(B), dim3(CB_THREADS), 0, st, clip_score, final_score, K, theta_base, m_samples, gate_h,
+                     scale, need_cos, hp_rows, nullptr, gated, kind, list, count);
+  CZC_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int launch_refine_select_draw(const float* clip_score, const float* final_score, int B, int K, float theta, float theta_base, float scale,
+                              int m_samples, float gate_h, float beta, const RowHyper* hp_rows, const RowDraw* draw_rows, int need_cos,
+                              int* gated, int* kind, int* list, int* count, hipStream_t st) {
+  if (K > CB_MAXK || !draw_rows) {
+    snprintf(g_err, sizeof(g_err), "refine_select: K=%d > %d or no draw_rows", K, CB_MAXK);
+    return 1;
+  }
+  if (hp_rows)
+    hipLaunchKernelGGL((refine_select_kernel<true, true>), dim3(B), dim3(CB_THREADS), 0, st, clip_score, final_score, K, theta_base, m_samples,
+                       gate_h, scale, need_cos, hp_rows, draw_rows, gated, kind, list, count);
+  else
+    hipLaunchKernelGGL((refine_select_kernel<false, true>), dim3(B), dim3(CB_THREADS), 0, st, clip_score, final_score, K, theta, m_samples,
+                       gate_h, beta, need_cos, nullptr, draw_rows, gated, kind, list, count);
   CZC_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -335,9 +399,12 @@ int launch_combine(const CombineArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(cosine_kernel, dim3((unsigned)cdiv((long)a.B * a.K, 4)), dim3(256), 0, st, a.text_feat, a.img_n, a.B, a.K, a.D,
                        a.clip_ref, a.nonfinite);
   if (a.hp_rows && !a.gen_rows) { snprintf(g_err, sizeof(g_err), "combine: hp_rows needs gen_rows"); return 1; }
-  if (a.hp_rows) hipLaunchKernelGGL((combine_kernel<true, true>), dim3(a.B), dim3(CB_THREADS), 0, st, a);
-  else if (a.gen_rows) hipLaunchKernelGGL((combine_kernel<true, false>), dim3(a.B), dim3(CB_THREADS), 0, st, a);
-  else hipLaunchKernelGGL((combine_kernel<false, false>), dim3(a.B), dim3(CB_THREADS), 0, st, a);
+  if (a.draw_rows && !a.gen_rows) { snprintf(g_err, sizeof(g_err), "combine: draw_rows needs gen_rows"); return 1; }
+  if (a.draw_rows && a.hp_rows) hipLaunchKernelGGL((combine_kernel<true, true, true>), dim3(a.B), dim3(CB_THREADS), 0, st, a);
+  else if (a.draw_rows) hipLaunchKernelGGL((combine_kernel<true, false, true>), dim3(a.B), dim3(CB_THREADS), 0, st, a);
+  else if (a.hp_rows) hipLaunchKernelGGL((combine_kernel<true, true, false>), dim3(a.B), dim3(CB_THREADS), 0, st, a);
+  else if (a.gen_rows) hipLaunchKernelGGL((combine_kernel<true, false, false>), dim3(a.B), dim3(CB_THREADS), 0, st, a);
+  else hipLaunchKernelGGL((combine_kernel<false, false, false>), dim3(a.B), dim3(CB_THREADS), 0, st, a);
   CZC_HIP_CHECK(hipGetLastError());
   return 0;
 }

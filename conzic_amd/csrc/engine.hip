@@ -165,6 +165,10 @@ struct czc_engine {
   // czc_generate_rows_hp, during its steps: the hyper-parameters of the rows the step at hand runs on (device, one record per
   // row of that batch -- the call's upload, or a compact batch's gather of it); null everywhere else
   const RowHyper* hp_rows = nullptr;
+  // czc_generate_rows_draw, during its steps: the draw records of the rows the step at hand runs on (device, gathered like
+  // hp_rows) and the step's index in the call's schedule (the Philox counter is the record's step0 + draw_step); null elsewhere
+  const RowDraw* draw_rows = nullptr;
+  unsigned draw_step = 0;
   int memo_branch_floor = 0;  // compacted step: longest branch the HIT images had (the full batch's attention-kernel choice)
   int64_t stat_memo_hits = 0, stat_memo_images = 0;  // image-steps that took an entry / all image-steps of memo calls
   // option "memo_rows" (czc_generate_rows only; memo_rows.hip): the same rule keyed per row, with counters of its own
@@ -865,6 +869,8 @@ int step_phase_b(czc_engine* e, const StepArgs& a, int M, int max_len, int max_b
   ca.final_score = fin; ca.best = best; ca.best_cos = bcos; ca.inp = a.d_inp; ca.T = a.T; ca.gen_idx = a.gen_idx;
   ca.hp_rows = e->hp_rows;   // czc_generate_rows_hp: alpha / beta / gamma / control per row, in both passes of the refine engine too
   ca.gen_rows = a.gen_rows;  // both passes of the refine engine write back through the same per-row column
+  // czc_generate_rows_draw: the draw belongs to the combine that writes back -- the only one here, the final one of the refine engine
+  if (!e->refine) { ca.draw_rows = e->draw_rows; ca.draw_step = e->draw_step; }
   E_CHECK(ensure(e, "s_nonfinite", 32, (void**)&ca.nonfinite));
   if (!e->refine) {
     ProfScope ps(e, "combine", 0);
@@ -893,7 +899,9 @@ int step_phase_b(czc_engine* e, const StepArgs& a, int M, int max_len, int max_b
     ca.inp = nullptr;
     E_CHECK(launch_combine(ca, e->st));
     const float gate_h = e->gate_now ? e->refine_gate_delta * (refine_rows16_now(e) ? e->refine_rows16_factor : 1.f) * e->logit_scale_exp : 0.f;
-    if (e->hp_rows) E_CHECK(launch_refine_select_rows(cscore, fin, a.B, a.K, theta_base, e->logit_scale_exp, e->in_generate ? e->refine_samples : e->refine_samples_step,
+    if (e->draw_rows) E_CHECK(launch_refine_select_draw(cscore, fin, a.B, a.K, theta, theta_base, e->logit_scale_exp, e->in_generate ? e->refine_samples : e->refine_samples_step,
+                                                        gate_h, hp->beta, e->hp_rows, e->draw_rows, e->gate_need_cos ? 1 : 0, ca.nonfinite + 4, kind, list, count, e->st));
+    else if (e->hp_rows) E_CHECK(launch_refine_select_rows(cscore, fin, a.B, a.K, theta_base, e->logit_scale_exp, e->in_generate ? e->refine_samples : e->refine_samples_step,
                                                       gate_h, e->hp_rows, e->gate_need_cos ? 1 : 0, ca.nonfinite + 4, kind, list, count, e->st));
     else E_CHECK(launch_refine_select(cscore, fin, a.B, a.K, theta, e->in_generate ? e->refine_samples : e->refine_samples_step, gate_h, hp->beta, e->gate_need_cos ? 1 : 0,
                                  ca.nonfinite + 4, kind, list, count, e->st)); }
@@ -920,6 +928,7 @@ int step_phase_b(czc_engine* e, const StepArgs& a, int M, int max_len, int max_b
   }
   { ProfScope ps(e, "combine", 0);
     ca.text_feat = nullptr; ca.inp = a.d_inp; ca.refine_kind = kind; ca.refine_cos = rcos;
+    ca.draw_rows = e->draw_rows; ca.draw_step = e->draw_step;
     ca.refine_guard = e->refine_guard_dev * (refine_rows16_now(e) ? e->refine_rows16_factor : 1.f);
     E_CHECK(launch_combine(ca, e->st)); }
   e->stat_refine_rows += M2;
@@ -948,6 +957,7 @@ int step_device(czc_engine* e, int* d_inp, int B, int T, int gen_idx, int n_mask
   StepArgs a{d_inp, B, T, gen_idx, n_mask, dot_allowed, K, *hp};
   a.gen_rows = gen_rows; a.dot_rows = dot_rows; a.gen_rows_host = gen_rows_host; a.rag = rag; a.ctl_T = ctl_T;
   if (e->hp_rows && (!gen_rows || !dot_rows)) return fail(e, CZC_ERR_ARG, "step: per-row hyper-parameters need per-row columns%s");
+  if (e->draw_rows && !gen_rows) return fail(e, CZC_ERR_ARG, "step: per-row draws need per-row columns%s");
   if (rag && (!gen_rows || !dot_rows || rag->max_T > T || rag->M > B * T)) return fail(e, CZC_ERR_ARG, "step: ragged rows need per-row columns and lengths within T%s");
   E_CHECK(step_phase_a(e, a));
   if (n_mask > 0) { e->stat_bert_rows += rag ? rag->M : B * T; e->last_BT = B * T; e->last_B = B; e->last_T = T; }
@@ -1110,6 +1120,7 @@ struct MemoRowsPlan {
   int *hit = nullptr, *cnt = nullptr, *list = nullptr, *tot = nullptr, *inp_c = nullptr, *col_c = nullptr, *dot_c = nullptr;
   float *bcos = nullptr, *img_c = nullptr;
   RowHyper* hp_c = nullptr;      // czc_generate_rows_hp: the records of a compact batch's rows, gathered by its run list
+  RowDraw* draw_c = nullptr;     // czc_generate_rows_draw: their draw records, by the same list
   std::vector<std::vector<int32_t>> h_col_c;  // compact batch of the group in progress: the active rows' column at every step
   std::vector<int32_t> run_h;    // of the group in progress: the rows that run, ascending (host copy of list_d)
   const int* list_d = nullptr;   // of the group in progress: the device list of the rows that run (null: every row)
@@ -1133,7 +1144,8 @@ static inline int memo_rows_sig(int n_mask0, int n_sub, int col1) { return (n_ma
 // table = false (czc_generate_rows_from with idle steps, option off): no entries, nothing is recorded or checked; the plan
 // then only carries the compact-batch buffers and the full-batch cosines.  Idle rows (position CZC_POS_IDLE) visit no key.
 int memo_rows_begin(czc_engine* e, bool table, int R, int T, int L, int seed_len, int n_steps, const int32_t* positions,
-                    const int32_t* n_mask, int snapshot_every, bool want_cos, const std::vector<char>& audit, MemoRowsPlan* mp) {
+                    const int32_t* n_mask, int snapshot_every, bool want_cos, const std::vector<char>& audit, MemoRowsPlan* mp,
+                    const czc_draw* draw_host = nullptr) {
   static_assert(MEMO_ROWS_SUB == MEMO_SUB, "the rows memo keeps the step memo's group size");
   mp->first.assign(n_steps, 0); mp->sub.assign(n_steps, 0); mp->group_len.assign(n_steps, 0);
   mp->record.assign(n_steps, 0); mp->check.assign(n_steps, 0);
@@ -1154,6 +1166,7 @@ int memo_rows_begin(czc_engine* e, bool table, int R, int T, int L, int seed_len
       bool revisit = false;
       for (int r = 0; r < R; ++r) {
         if (positions[(size_t)s * R + r] < 0) continue;  // idle: not a visit
+        if (draw_host && draw_host[r].tau > 0.f) continue;  // a row that draws never hits (the check kernel refuses it too)
         const int sig = memo_rows_sig(nm0, g, g > 1 ? seed_len + positions[(size_t)(s + 1) * R + r] : 0);
         int& was = seen[(size_t)r * L + positions[(size_t)s * R + r]];
         revisit = revisit || was == sig;
@@ -1222,7 +1235,7 @@ int memo_rows_step(czc_engine* e, MemoRowsPlan& mp, int s, int* d_inp, int R, in
     mp.list_d = mp.n_run < R ? d_sched + 2 * n_pos + (size_t)s0 * R : nullptr;  // the schedule's own run list of this step
     mp.branch_max[0] = mp.branch_max[1] = 0;
     if (mp.check[s]) {
-      E_CHECK(launch_memo_rows_check(d_inp, mp.tab, col0, col1, n_mask0, g, mask_id, mp.hit, mp.cnt, mp.list, mp.tot, e->st));
+      E_CHECK(launch_memo_rows_check(d_inp, mp.tab, col0, col1, n_mask0, g, mask_id, mp.hit, mp.cnt, mp.list, mp.tot, e->st, e->draw_rows));
       int32_t* h = e->h_memo_list;
       E_HIP(hipMemcpyAsync(h, mp.tot, 16, hipMemcpyDeviceToHost, e->st));
       E_HIP(hipMemcpyAsync(h + 4, mp.list, (size_t)R * 4, hipMemcpyDeviceToHost, e->st));
@@ -1298,10 +1311,16 @@ int memo_rows_step(czc_engine* e, MemoRowsPlan& mp, int s, int* d_inp, int R, in
     E_CHECK(launch_gather_row_hyper(hp_full, mp.list_d, n_act, mp.hp_c, e->st));
     e->hp_rows = mp.hp_c;
   }
+  const RowDraw* draw_full = e->draw_rows;
+  if (draw_full) {
+    if (!mp.draw_c || !mp.list_d) return fail(e, CZC_ERR_STATE, "generate_rows_draw: a compact batch without room for its draw records%s");
+    E_CHECK(launch_gather_row_draw(draw_full, mp.list_d, n_act, mp.draw_c, e->st));
+    e->draw_rows = mp.draw_c;
+  }
   e->d_img_n = mp.img_c; e->img_B = n_act; e->memo_branch_floor = j < MEMO_ROWS_SUB ? mp.branch_max[j] : 0;
   const int rc = step_device(e, mp.inp_c, n_act, T, col_h[0], n_mask, col_h[0] - seed_len == L - 1 ? 1 : 0, K, hp, mp.col_c, mp.dot_c,
                              col_h, mp.rag(false), mp.ctl_T());
-  e->d_img_n = img_rows; e->img_B = img_B; e->memo_branch_floor = 0; e->hp_rows = hp_full;
+  e->d_img_n = img_rows; e->img_B = img_B; e->memo_branch_floor = 0; e->hp_rows = hp_full; e->draw_rows = draw_full;
   E_CHECK(rc);
   return launch_memo_rows_scatter(mp.inp_c, (const float*)e->ws["s_bcos"].p, (const int*)e->ws["p_img_max"].p, mp.list_d, n_act,
                                   mp.tab, col0, j, record, d_inp, mp.bcos, e->st) ? fail(e, CZC_ERR_HIP, "%s", g_err) : 0;
@@ -1312,7 +1331,7 @@ int memo_rows_step(czc_engine* e, MemoRowsPlan& mp, int s, int* d_inp, int R, in
 // =================================================================================================
 extern "C" {
 
-int czc_version(void) { return 103; }
+int czc_version(void) { return 104; }
 
 const char* czc_last_error(const czc_engine* e) { return e ? e->err : czc::g_err; }
 
@@ -1944,7 +1963,7 @@ int czc_step(czc_engine* e, int32_t* inp, int B, int T, int gen_idx, int n_mask,
 static int generate_impl(czc_engine* e, bool rows, bool from, int B, int T, int L, int seed_len, const int32_t* init_ids_host,
                          const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
                          const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp, int32_t* out_ids, float* out_cos,
-                         const int32_t* len_rows = nullptr, const czc_hyper* hp_rows_host = nullptr) {
+                         const int32_t* len_rows = nullptr, const czc_hyper* hp_rows_host = nullptr, const czc_draw* draw_host = nullptr) {
   if (!e || !init_ids_host || !positions_host || !hp || B <= 0 || n_steps < 0 || snapshot_every <= 0)
     return CZC_ERR_ARG;
   if (seed_len + L > T) return fail(e, CZC_ERR_ARG, "generate: seed_len + L > T%s");
@@ -2039,6 +2058,8 @@ static int generate_impl(czc_engine* e, bool rows, bool from, int B, int T, int 
   }
   int *d_inp, *d_row, *d_sched = nullptr;
   RowHyper* d_hp_rows = nullptr;
+  RowDraw* d_draw_rows = nullptr;
+  if (draw_host && !rows) return fail(e, CZC_ERR_ARG, "generate: draw records belong to a rows call%s");
   { int* flag; E_CHECK(ensure(e, "s_nonfinite", 32, (void**)&flag)); E_HIP(hipMemsetAsync(flag, 0, 32, e->st)); }
   E_CHECK(ensure(e, "g_inp", (size_t)B * T * 4, (void**)&d_inp));
   if (from) {  // every row brings its own start row: one upload, no broadcast
@@ -2068,6 +2089,13 @@ static int generate_impl(czc_engine* e, bool rows, bool from, int B, int T, int 
       E_CHECK(ensure(e, "g_hp_rows", (size_t)B * sizeof(RowHyper), (void**)&d_hp_rows));
       E_HIP(hipMemcpyAsync(d_hp_rows, hp_rows_host, (size_t)B * sizeof(RowHyper), hipMemcpyHostToDevice, e->st));
     }
+    if (draw_host) {  // likewise: seed, tau and step offset per row
+      static_assert(sizeof(RowDraw) == sizeof(czc_draw) && offsetof(RowDraw, seed_lo) == offsetof(czc_draw, seed) &&
+                    offsetof(RowDraw, tau) == offsetof(czc_draw, tau) && offsetof(RowDraw, step0) == offsetof(czc_draw, step0),
+                    "RowDraw is czc_draw as the kernels read it (little-endian seed halves)");
+      E_CHECK(ensure(e, "g_draw_rows", (size_t)B * sizeof(RowDraw), (void**)&d_draw_rows));
+      E_HIP(hipMemcpyAsync(d_draw_rows, draw_host, (size_t)B * sizeof(RowDraw), hipMemcpyHostToDevice, e->st));
+    }
     if (image_of_row_host) {
       E_HIP(hipMemcpyAsync(d_ior, image_of_row_host, (size_t)B * 4, hipMemcpyHostToDevice, e->st));
       E_CHECK(launch_gather_rows_f32(img_full, d_ior, B, D, img_r, e->st));
@@ -2096,7 +2124,7 @@ static int generate_impl(czc_engine* e, bool rows, bool from, int B, int T, int 
   MemoRowsPlan mrp;
   const bool memo_rows = rows && (e->memo_rows || any_idle) && n_steps > 0;  // the compact-batch path, with or without entries
   // (a failure here leaves through the exit below, which hands the resident image batch back)
-  if (memo_rows) rc = memo_rows_begin(e, e->memo_rows, B, T, L, seed_len, n_steps, positions_host, n_mask_host, snapshot_every, out_cos != nullptr, audit, &mrp);
+  if (memo_rows) rc = memo_rows_begin(e, e->memo_rows, B, T, L, seed_len, n_steps, positions_host, n_mask_host, snapshot_every, out_cos != nullptr, audit, &mrp, draw_host);
   Ragged rag_full{};
   if (len_rows && d_sched) {
     const size_t base = (any_idle ? 3 : 2) * n_pos;
@@ -2110,7 +2138,9 @@ static int generate_impl(czc_engine* e, bool rows, bool from, int B, int T, int 
   }
   // a row that has not run yet in this call reports cosine 0 (the reference's best_clip_score start value)
   if (memo_rows && d_hp_rows && !rc && ensure(e, "mr_hp_c", (size_t)B * sizeof(RowHyper), (void**)&mrp.hp_c)) rc = CZC_ERR_HIP;
+  if (memo_rows && d_draw_rows && !rc && ensure(e, "mr_draw_c", (size_t)B * sizeof(RowDraw), (void**)&mrp.draw_c)) rc = CZC_ERR_HIP;
   e->hp_rows = rc ? nullptr : d_hp_rows;  // (handed back with the image batch below)
+  e->draw_rows = rc ? nullptr : d_draw_rows;
   if (memo_rows && any_idle && !rc && hipMemsetAsync(mrp.bcos, 0, (size_t)B * 4, e->st) != hipSuccess) rc = fail(e, CZC_ERR_HIP, "generate_rows_from: clearing the cosines%s");
   for (int s = 0; s < n_steps && !rc; ++s) {
     const int pos = positions_host[rows ? (size_t)s * B : (size_t)s];
@@ -2119,6 +2149,7 @@ static int generate_impl(czc_engine* e, bool rows, bool from, int B, int T, int 
     e->gate_now = e->refine && e->refine_gate_delta > 0.f && e->refine_guard_dev > 0.f && !audit[s];
     e->gate_need_cos = snap_idx && out_cos != nullptr;
     e->in_generate = true;
+    e->draw_step = (unsigned)s;
     if (memo_rows) rc = memo_rows_step(e, mrp, s, d_inp, B, T, L, seed_len, nm, n_mask_host ? n_mask_host[mrp.first[s]] : 1, top_k, hp,
                                        sched.data(), d_sched, n_pos);
     else if (rows) rc = step_device(e, d_inp, B, T, seed_len + pos, nm, pos == L - 1 ? 1 : 0, top_k, hp, d_sched + (size_t)s * B,
@@ -2139,7 +2170,7 @@ static int generate_impl(czc_engine* e, bool rows, bool from, int B, int T, int 
     }
   }
   // rows: the resident image batch comes back whatever happened, and no later call may re-use a forward by this call's columns
-  e->d_img_n = img_full; e->img_B = img_B; e->hp_rows = nullptr;
+  e->d_img_n = img_full; e->img_B = img_B; e->hp_rows = nullptr; e->draw_rows = nullptr; e->draw_step = 0;
   if (rows) { e->bert_pruned_rows = nullptr; if (rc) (void)hipStreamSynchronize(e->st); }
   if (rc) return rc;
   E_HIP(hipMemcpyAsync(e->h_totals + 9, e->ws["s_nonfinite"].p, 24, hipMemcpyDeviceToHost, e->st));
@@ -2175,7 +2206,7 @@ int czc_generate_rows_from(czc_engine* e, int R, int T, int L, int seed_len, con
 static int rows_len_impl(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
                          const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
                          const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp, int32_t* out_ids, float* out_cos,
-                         const czc_hyper* hp_rows_host) {
+                         const czc_hyper* hp_rows_host, const czc_draw* draw_host = nullptr) {
   if (!e || !init_rows_host || !len_of_row_host || !positions_host || !hp || R <= 0 || n_steps < 0 || snapshot_every <= 0)
     return CZC_ERR_ARG;
   e->err[0] = 0;
@@ -2201,7 +2232,7 @@ static int rows_len_impl(czc_engine* e, int R, int T, int seed_len, const int32_
   }
   // rows of one length that fill the stride: czc_generate_rows_from itself, bit for bit
   return generate_impl(e, true, true, R, T, L_max, seed_len, init_rows_host, image_of_row_host, top_k, n_steps, positions_host, n_mask_host,
-                       snapshot_every, hp, out_ids, out_cos, uniform ? nullptr : len_of_row_host, hp_rows_host);
+                       snapshot_every, hp, out_ids, out_cos, uniform ? nullptr : len_of_row_host, hp_rows_host, draw_host);
 }
 
 int czc_generate_rows_len(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
@@ -2211,9 +2242,11 @@ int czc_generate_rows_len(czc_engine* e, int R, int T, int seed_len, const int32
                        snapshot_every, hp, out_ids, out_cos, nullptr);
 }
 
-int czc_generate_rows_hp(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
-                         const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
-                         const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp_of_row_host, int32_t* out_ids, float* out_cos) {
+// czc_generate_rows_hp, and czc_generate_rows_draw behind its own checks (draw_host [R], some tau > 0; null: no row draws)
+static int rows_hp_impl(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
+                        const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
+                        const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp_of_row_host, int32_t* out_ids, float* out_cos,
+                        const czc_draw* draw_host) {
   if (!e || !init_rows_host || !positions_host || !hp_of_row_host || R <= 0 || n_steps < 0 || snapshot_every <= 0) return CZC_ERR_ARG;
   e->err[0] = 0;
   if (R > CZC_MAX_ROWS) return fail(e, CZC_ERR_ARG, "generate_rows_hp: R > CZC_MAX_ROWS%s");
@@ -2241,9 +2274,36 @@ int czc_generate_rows_hp(czc_engine* e, int R, int T, int seed_len, const int32_
   const czc_hyper* rows_hp = uniform ? nullptr : hp_of_row_host;
   if (len_of_row_host)
     return rows_len_impl(e, R, T, seed_len, init_rows_host, len_of_row_host, image_of_row_host, top_k, n_steps, positions_host, n_mask_host,
-                         snapshot_every, &hp_of_row_host[0], out_ids, out_cos, rows_hp);
+                         snapshot_every, &hp_of_row_host[0], out_ids, out_cos, rows_hp, draw_host);
   return generate_impl(e, true, true, R, T, T - seed_len - 1, seed_len, init_rows_host, image_of_row_host, top_k, n_steps, positions_host,
-                       n_mask_host, snapshot_every, &hp_of_row_host[0], out_ids, out_cos, nullptr, rows_hp);
+                       n_mask_host, snapshot_every, &hp_of_row_host[0], out_ids, out_cos, nullptr, rows_hp, draw_host);
+}
+
+int czc_generate_rows_hp(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
+                         const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
+                         const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp_of_row_host, int32_t* out_ids, float* out_cos) {
+  return rows_hp_impl(e, R, T, seed_len, init_rows_host, len_of_row_host, image_of_row_host, top_k, n_steps, positions_host, n_mask_host,
+                      snapshot_every, hp_of_row_host, out_ids, out_cos, nullptr);
+}
+
+int czc_generate_rows_draw(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
+                           const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
+                           const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp_of_row_host,
+                           const czc_draw* draw_of_row_host, int32_t* out_ids, float* out_cos) {
+  if (!e || R <= 0 || n_steps < 0) return CZC_ERR_ARG;
+  e->err[0] = 0;
+  if (R > CZC_MAX_ROWS) return fail(e, CZC_ERR_ARG, "generate_rows_draw: R > CZC_MAX_ROWS%s");
+  bool any = false;
+  for (int r = 0; r < R && draw_of_row_host; ++r) {
+    const czc_draw& d = draw_of_row_host[r];
+    if (!std::isfinite(d.tau) || d.tau < 0.f) return fail(e, CZC_ERR_ARG, "generate_rows_draw: a tau must be finite and >= 0%s");
+    if ((uint64_t)d.step0 + (uint64_t)n_steps > 0xffffffffull)
+      return fail(e, CZC_ERR_ARG, "generate_rows_draw: step0 + n_steps does not fit the 32-bit step counter%s");
+    any = any || d.tau > 0.f;
+  }
+  // no row draws: czc_generate_rows_hp itself, bit for bit
+  return rows_hp_impl(e, R, T, seed_len, init_rows_host, len_of_row_host, image_of_row_host, top_k, n_steps, positions_host, n_mask_host,
+                      snapshot_every, hp_of_row_host, out_ids, out_cos, any ? draw_of_row_host : nullptr);
 }
 
 int czc_set_control_callback(czc_engine* e, czc_control_fn fn, void* user) {

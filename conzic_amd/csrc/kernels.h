@@ -166,8 +166,11 @@ struct MemoRowsTab {
 // check: hit[r] = 1 where slot (col0[r] - seed_len, r) is valid, has this group's signature and its key row equals the masked
 // row r, 2 where row r is idle, else 0; list = the rows with hit[r] == 0 in ascending order; tot[0] = their count, tot[1 + j] = max over the hit rows of the slot's imax at
 // sub-step j (j < n_sub <= MEMO_ROWS_SUB); cnt: scratch, (R + 255) / 256 ints
+// draw_rows (czc_generate_rows_draw; device, [R], may be null): a row with tau > 0 never hits -- its outcome is not a function
+// of its masked row alone
+struct RowDraw;
 int launch_memo_rows_check(const int* inp, const MemoRowsTab& m, const int* col0, const int* col1, int n_mask0, int n_sub,
-                           int mask_id, int* hit, int* cnt, int* list, int* tot, hipStream_t st);
+                           int mask_id, int* hit, int* cnt, int* list, int* tot, hipStream_t st, const RowDraw* draw_rows = nullptr);
 // for i < n, r = list ? list[i] : i: (record) key of r's slot = masked row r, valid, signature; (inp_c) inp_c[i] = row r,
 // img_c[i] = img_n[r], col_c[i] = col[r], dot_c[i] = dot[r] (col / dot: this step's schedule slice)
 int launch_memo_rows_gather(const int* inp, const int* list, int n, const MemoRowsTab& m, const int* col0, const int* col1,
@@ -213,6 +216,15 @@ int launch_attention_shared_split(const void* qkv, const SegTable& tab, int B, i
 struct RowHyper { float alpha, beta, gamma, temperature; int control, negative; };
 
 int launch_gather_row_hyper(const RowHyper* src, const int* idx, int n, RowHyper* dst, hipStream_t st);  // rowops.hip: dst[i] = src[idx[i]]
+
+// ---- per-row seeded draw of the winner (czc_generate_rows_draw) -----------------------------------------------------------
+// One record per row of a rows call, the layout of czc_draw on a little-endian host (engine.hip asserts it): the two halves of
+// the row's 64-bit seed (the Philox key), its tau (0: the row keeps the first argmax) and the call's step offset.  Uploaded once
+// with the schedule; read by the final combine (one work-group per row), the refine selection (a tau > 0 row is never
+// margin-gated) and the rows memo's check (a tau > 0 row never hits).
+struct RowDraw { unsigned seed_lo, seed_hi; float tau; unsigned step0; };
+
+int launch_gather_row_draw(const RowDraw* src, const int* idx, int n, RowDraw* dst, hipStream_t st);  // rowops.hip: dst[i] = src[idx[i]]
 
 // ---- topk.hip -----------------------------------------------------------------------------
 int launch_softmax_mask_topk(const float* logits, int B, int V, int K, const float* mask, float temperature, int dot_id,
@@ -315,6 +327,10 @@ struct CombineArgs {
   // czc_generate_rows_hp: alpha, beta, gamma and use_senti (= control) of row b come from hp_rows[b] (device, [B]; needs
   // gen_rows); null = the scalars above
   const RowHyper* hp_rows = nullptr;
+  // czc_generate_rows_draw: row b with draw_rows[b].tau > 0 draws its winner from softmax_K(final / tau) by the Gumbel-max rule
+  // of combine.hip at step counter draw_rows[b].step0 + draw_step (device, [B]; needs gen_rows); null = first argmax
+  const RowDraw* draw_rows = nullptr;
+  unsigned draw_step = 0;
 };
 // text_feat == null: clip_ref already holds the cosines
 int launch_combine(const CombineArgs& a, hipStream_t st);
@@ -326,6 +342,11 @@ int launch_refine_select(const float* clip_score, const float* final_score, int 
 int launch_refine_select_rows(const float* clip_score, const float* final_score, int B, int K, float theta_base, float scale,
                               int m_samples, float gate_h, const RowHyper* hp_rows, int need_cos, int* gated, int* kind, int* list,
                               int* count, hipStream_t st);
+// czc_generate_rows_draw: either form (hp_rows null: the scalar theta / beta) with the margin gate closed for the rows that
+// draw (draw_rows[b].tau > 0): the gate proves an argmax, so such a row takes the full selection
+int launch_refine_select_draw(const float* clip_score, const float* final_score, int B, int K, float theta, float theta_base, float scale,
+                              int m_samples, float gate_h, float beta, const RowHyper* hp_rows, const RowDraw* draw_rows, int need_cos,
+                              int* gated, int* kind, int* list, int* count, hipStream_t st);
 int launch_refine_cosine(const float* text_feat, const float* img_n, const int* rlist, const int* n_rows_dev, int n_rows_max, int K, int D,
                          float* cos_out, int* nonfinite, hipStream_t st);
 // segment plan of the refine pass (bridge.hip): B trunks (prefix lengths of the screening plan) + B x Kr branch slots
@@ -350,7 +371,7 @@ int launch_index_search(const split_t* index, int n, int D, const split_t* queri
 // ---- czc_internal_hooks (declared below, private to the build): what libconzic_hip_test.so may reach inside this library -----------
 // The product library has hidden visibility; the hook library (api_test.hip) gets the launchers it wraps and the
 // process-wide kernel-family switches it flips through this table instead of through exported C++ symbols.
-constexpr int HOOKS_ABI = 0x0603;
+constexpr int HOOKS_ABI = 0x0604;
 struct Hooks {
   char* (*err_buf)();  // the calling host thread's g_err [512]
   decltype(&launch_gemm) gemm;

@@ -36,7 +36,8 @@ __device__ __forceinline__ int mr_sig(int n_mask0, int n_sub, const int* col1, i
 // and every column agree, MR_IDLE where the row sits the group out.  cnt[work-group] = its rows that run (MR_MISS); tot[1 + j] (zeroed by the launcher) = longest branch
 // a hit row had at sub-step j on its last visit.
 __global__ __launch_bounds__(256) void memo_rows_flag_kernel(const int* inp, MemoRowsTab m, const int* col0, const int* col1,
-                                                             int n_mask0, int n_sub, int mask_id, int* hit, int* cnt, int* tot) {
+                                                             int n_mask0, int n_sub, int mask_id, const RowDraw* draw_rows, int* hit,
+                                                             int* cnt, int* tot) {
   __shared__ int wcount[4];
   __shared__ int hmax[MEMO_ROWS_SUB];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -51,6 +52,7 @@ __global__ __launch_bounds__(256) void memo_rows_flag_kernel(const int* inp, Mem
     if (p >= 0) {
       const size_t e = (size_t)p * m.R + r;
       same = m.valid[e] == 1 && m.sig[e] == mr_sig(n_mask0, n_sub, col1, r);
+      if (draw_rows && draw_rows[r].tau > 0.f) same = false;  // a row that draws its winner always runs (czc_generate_rows_draw)
       if (same) {
         const int* row = inp + (size_t)r * m.T;
         const int* k = m.key + e * m.T;
@@ -93,11 +95,11 @@ __global__ __launch_bounds__(256) void memo_rows_list_kernel(const int* hit, int
 }
 
 int launch_memo_rows_check(const int* inp, const MemoRowsTab& m, const int* col0, const int* col1, int n_mask0, int n_sub,
-                           int mask_id, int* hit, int* cnt, int* list, int* tot, hipStream_t st) {
+                           int mask_id, int* hit, int* cnt, int* list, int* tot, hipStream_t st, const RowDraw* draw_rows) {
   if (m.R <= 0 || m.R > CZC_MAX_ROWS) { snprintf(g_err, sizeof(g_err), "memo_rows check: bad row count %d", m.R); return 1; }
   const int nb = (m.R + 255) / 256;
   CZC_HIP_CHECK(hipMemsetAsync(tot, 0, 16, st));
-  hipLaunchKernelGGL(memo_rows_flag_kernel, dim3(nb), dim3(256), 0, st, inp, m, col0, col1, n_mask0, n_sub, mask_id, hit, cnt, tot);
+  hipLaunchKernelGGL(memo_rows_flag_kernel, dim3(nb), dim3(256), 0, st, inp, m, col0, col1, n_mask0, n_sub, mask_id, draw_rows, hit, cnt, tot);
   CZC_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(memo_rows_list_kernel, dim3(nb), dim3(256), 0, st, hit, m.R, cnt, list, tot);
   CZC_HIP_CHECK(hipGetLastError());

@@ -606,6 +606,19 @@ int launch_gather_row_hyper(const RowHyper* src, const int* idx, int n, RowHyper
   return 0;
 }
 
+// czc_generate_rows_draw: the draw records of a compact batch's rows, by the same run list
+__global__ void gather_row_draw_kernel(const RowDraw* src, const int* idx, int n, RowDraw* dst) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dst[i] = src[idx[i]];
+}
+
+int launch_gather_row_draw(const RowDraw* src, const int* idx, int n, RowDraw* dst, hipStream_t st) {
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(gather_row_draw_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, src, idx, n, dst);
+  CZC_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
 int launch_gather_rows_f32(const float* src, const int* idx, int M, int H, float* dst, hipStream_t st) {
   if (M <= 0) return 0;
   hipLaunchKernelGGL(gather_rows_kernel, dim3(cdiv(M, 4)), dim3(256), 0, st, src, idx, M, H, dst);

@@ -55,6 +55,11 @@ def get_args(argv=None):
     p.add_argument("--batch_samples", action="store_true",
                    help="polish the samples_num samples of a batch in ONE engine call (one row per image and sample, every "
                         "sample with the visiting order the sample loop would have drawn for it) instead of one call per sample")
+    p.add_argument("--sample_tau", type=float, default=0.0, metavar="T",
+                   help="draw every step's winner from softmax_K(fused score / T) instead of taking the argmax (0 = off, the "
+                        "reference's rule); every (image, sample) draws under its own seed derived from --seed, so samples_num "
+                        "samples differ under any --order and repeat from run to run; combines with --batch_samples, "
+                        "--sentence_lens, --signals and --run_type infill")
     p.add_argument("--sentence_lens", type=lambda v: [int(n) for n in v.split(",") if n.strip()], default=None, metavar="L1,L2,...",
                    help="several sentence lengths of every image in ONE engine call, e.g. 6,8,10,12 (each row at its own length; "
                         "--order sequential or shuffle): one call per sample, or with --batch_samples one call of samples_num x "
@@ -84,6 +89,10 @@ def get_args(argv=None):
                         "(num_iterations sweeps in --order sequential or shuffle, --candidate_k, alpha / beta / temperature), all "
                         "of them rows of one engine call")
     a = p.parse_args(argv)
+    if not (a.sample_tau >= 0.0) or a.sample_tau == float("inf"):
+        p.error("--sample_tau must be finite and >= 0")
+    if a.sample_tau and a.run_type == "retrieve":
+        p.error("--sample_tau does not apply to --run_type retrieve")
     if a.run_type == "retrieve":
         from conzic_amd import native
         files = a.index_matrix_path is not None or a.mapping_dict_path is not None
@@ -190,7 +199,8 @@ def main(argv=None):
         from conzic_amd.runtime import infill_captions
         infill_captions(args.caption, img_name, lm_model, clip, lm_tokenizer, image_instance, token_mask, logger, prompt=args.prompt,
                         top_k=args.candidate_k, temperature=args.lm_temperature, max_iter=args.num_iterations, alpha=args.alpha,
-                        beta=args.beta, generate_order=args.order, positions=args.infill_positions)
+                        beta=args.beta, generate_order=args.order, positions=args.infill_positions,
+                        sample_tau=args.sample_tau, sample_seed=args.seed)
         logger.info("total %.2fs" % (time.time() - t0))
         return
     if args.signals:
@@ -203,7 +213,8 @@ def main(argv=None):
                             img_name, lm_model, clip, lm_tokenizer, image_instance, token_mask, logger, prompt=args.prompt,
                             batch_size=args.batch_size, top_k=args.candidate_k, temperature=args.lm_temperature,
                             max_iter=args.num_iterations, alpha=args.alpha, beta=args.beta, generate_order=args.order,
-                            gamma=args.gamma, pos_type=args.pos_type)
+                            gamma=args.gamma, pos_type=args.pos_type, sample_tau=args.sample_tau, sample_seed=args.seed,
+                            sample0=sample_id or 0)
         logger.info("total %.2fs" % (time.time() - t0))
         return
     if args.sentence_lens:
@@ -211,35 +222,55 @@ def main(argv=None):
         from conzic_amd.runtime import caption_lengths
         kw = dict(prompt=args.prompt, batch_size=args.batch_size, top_k=args.candidate_k, temperature=args.lm_temperature,
                   max_iter=args.num_iterations, alpha=args.alpha, beta=args.beta, generate_order=args.order, gamma=args.gamma,
-                  ctl_type=args.control_type, style_type=args.sentiment_type, pos_type=args.pos_type)
+                  ctl_type=args.control_type, style_type=args.sentiment_type, pos_type=args.pos_type,
+                  sample_tau=args.sample_tau, sample_seed=args.seed)
         for sample_id in ([None] if args.batch_samples else range(args.samples_num)):
             if sample_id is not None:
                 logger.info(f"Sample {sample_id}: ")
             caption_lengths(args.sentence_lens, args.samples_num if args.batch_samples else 1, args.run_type, img_name, lm_model, clip,
-                            lm_tokenizer, image_instance, token_mask, logger, **kw)
+                            lm_tokenizer, image_instance, token_mask, logger, sample0=sample_id or 0, **kw)
         logger.info("total %.2fs" % (time.time() - t0))
         return
-    if args.batch_samples:
+    from conzic_amd.diversity import log_distinct
+    finals = [[] for _ in img_name]   # per image: the final caption of every sample
+
+    def keep(generate_texts):
+        last = generate_texts[-2] if len(generate_texts) > 1 else generate_texts[-1]   # (no snapshot recorded: the best entry)
+        for i in range(args.batch_size):
+            finals[i].append(last[i])
+
+    if args.batch_samples or args.sample_tau:
+        # one engine call for all samples, or -- the serial loop under --sample_tau -- one per sample with that sample's seeds
         from conzic_amd.runtime import caption_samples
-        caption_samples(args.samples_num, args.run_type, img_name, lm_model, clip, lm_tokenizer, image_instance, token_mask, logger,
-                        prompt=args.prompt, batch_size=args.batch_size, max_len=args.sentence_len, top_k=args.candidate_k,
-                        temperature=args.lm_temperature, max_iter=args.num_iterations, alpha=args.alpha, beta=args.beta,
-                        generate_order=args.order, gamma=args.gamma, ctl_type=args.control_type,
-                        style_type=args.sentiment_type, pos_type=args.pos_type)
+        kw = dict(prompt=args.prompt, batch_size=args.batch_size, max_len=args.sentence_len, top_k=args.candidate_k,
+                  temperature=args.lm_temperature, max_iter=args.num_iterations, alpha=args.alpha, beta=args.beta,
+                  generate_order=args.order, gamma=args.gamma, ctl_type=args.control_type,
+                  style_type=args.sentiment_type, pos_type=args.pos_type, sample_tau=args.sample_tau, sample_seed=args.seed)
+        for sample_id in ([None] if args.batch_samples else range(args.samples_num)):
+            outs = caption_samples(args.samples_num if sample_id is None else 1, args.run_type, img_name, lm_model, clip, lm_tokenizer,
+                                   image_instance, token_mask, logger, sample0=sample_id or 0, **kw)
+            for generate_texts, _ in outs:
+                keep(generate_texts)
+        if args.samples_num > 1:
+            log_distinct(logger, img_name, finals)
         logger.info("total %.2fs" % (time.time() - t0))
-        return
+        return finals
     for sample_id in range(args.samples_num):                                   # demo.py:83 (no reseeding)
         logger.info(f"Sample {sample_id}: ")
         kw = dict(prompt=args.prompt, batch_size=args.batch_size, max_len=args.sentence_len, top_k=args.candidate_k,
                   temperature=args.lm_temperature, max_iter=args.num_iterations, alpha=args.alpha, beta=args.beta,
                   generate_order=args.order)
         if args.run_type == 'caption':
-            generate_caption(img_name, lm_model, clip, lm_tokenizer, image_instance, token_mask, logger, **kw)
+            generate_texts, _ = generate_caption(img_name, lm_model, clip, lm_tokenizer, image_instance, token_mask, logger, **kw)
         else:
-            control_generate_caption(img_name, lm_model, clip, lm_tokenizer, image_instance, token_mask, logger,
-                                     gamma=args.gamma, ctl_type=args.control_type, style_type=args.sentiment_type,
-                                     pos_type=args.pos_type, **kw)
+            generate_texts, _ = control_generate_caption(img_name, lm_model, clip, lm_tokenizer, image_instance, token_mask, logger,
+                                                         gamma=args.gamma, ctl_type=args.control_type, style_type=args.sentiment_type,
+                                                         pos_type=args.pos_type, **kw)
+        keep(generate_texts)
+    if args.samples_num > 1:
+        log_distinct(logger, img_name, finals)
     logger.info("total %.2fs" % (time.time() - t0))
+    return finals
 
 
 if __name__ == "__main__":

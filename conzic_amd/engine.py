@@ -37,6 +37,17 @@ def hyper_array(hypers: Sequence[native.Hyper]):
     return arr if hs else arr[:0]
 
 
+def draw_array(draws: Sequence[native.Draw]):
+    """A contiguous ctypes array of native.Draw (czc_draw [R]) holding copies of `draws`."""
+    ds = list(draws)
+    arr = (native.Draw * max(len(ds), 1))()
+    for i, d in enumerate(ds):
+        if not isinstance(d, native.Draw):
+            raise TypeError(f"draws[{i}] is {type(d).__name__}, not native.Draw")
+        arr[i].seed, arr[i].tau, arr[i].step0 = d.seed, d.tau, d.step0
+    return arr if ds else arr[:0]
+
+
 def make_config(bert_cfg, clip_cfg, special: Dict[str, int], precision: int) -> native.Config:
     c = native.Config()
     if bert_cfg is not None:
@@ -496,6 +507,48 @@ class Engine:
         self._ck(rc, "czc_generate_rows_hp")
         return ids, cos
 
+    def generate_rows_draw(self, init_rows, lens, seed_len: int, top_k: int, positions, hypers: Sequence[native.Hyper],
+                           draws: Optional[Sequence[native.Draw]], image_of_row: Optional[Sequence[int]] = None,
+                           n_mask: Optional[Sequence[int]] = None, snapshot_every: Optional[int] = None, want_cos: bool = True):
+        """czc_generate_rows_draw: generate_rows_hp with a native.Draw per row (`draws`, R entries or None: row r's seed, tau and
+        step offset).  A row with tau > 0 draws its winner from softmax_K(final_score / tau) with a counter-based generator keyed
+        by its seed; tau == 0 keeps the first argmax.  Returns (ids int32 [S,R,T], cos fp32 [S,R]) per snapshot."""
+        init = np.ascontiguousarray(init_rows, dtype=np.int32)
+        pos = np.ascontiguousarray(positions, dtype=np.int32)
+        if pos.ndim != 2 or pos.shape[1] < 1:
+            raise ValueError("generate_rows_draw: positions must be [n_steps, R]")
+        n_steps, R = pos.shape
+        if init.ndim != 2 or init.shape[0] != R or init.shape[1] < 1:
+            raise ValueError(f"generate_rows_draw: init_rows must be [R, T] with R = {R}, got {init.shape}")
+        T = init.shape[1]
+        ln = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32).reshape(-1)
+        if ln is not None and ln.size != R:
+            raise ValueError(f"generate_rows_draw: lens has {ln.size} entries for {R} rows")
+        hp = hyper_array(hypers)
+        if len(hp) != R:
+            raise ValueError(f"generate_rows_draw: hypers has {len(hp)} entries for {R} rows")
+        dr = None if draws is None else draw_array(draws)
+        if dr is not None and len(dr) != R:
+            raise ValueError(f"generate_rows_draw: draws has {len(dr)} entries for {R} rows")
+        ior = None if image_of_row is None else np.ascontiguousarray(image_of_row, dtype=np.int32).reshape(-1)
+        if ior is not None and ior.size != R:
+            raise ValueError(f"generate_rows_draw: image_of_row has {ior.size} entries for {R} rows")
+        nm = None if n_mask is None else np.ascontiguousarray(n_mask, dtype=np.int32).reshape(-1)
+        if nm is not None and nm.size != n_steps:
+            raise ValueError(f"generate_rows_draw: n_mask has {nm.size} entries for {n_steps} steps")
+        every = snapshot_every or max(int(ln.max()) if ln is not None else T - seed_len - 1, 1)
+        S = n_steps // every
+        ids = np.empty((S, R, T), dtype=np.int32)
+        cos = np.empty((S, R), dtype=np.float32) if want_cos else None
+        rc = self.lib.czc_generate_rows_draw(self.h, R, T, seed_len, init.ctypes.data, None if ln is None else ln.ctypes.data,
+                                             None if ior is None else ior.ctypes.data, top_k, n_steps, pos.ctypes.data,
+                                             None if nm is None else nm.ctypes.data, every, hp, dr, ids.ctypes.data,
+                                             None if cos is None else cos.ctypes.data)
+        if rc:
+            self._raise_scorer_error()
+        self._ck(rc, "czc_generate_rows_draw")
+        return ids, cos
+
     def similarity(self, image_embeds, text_embeds, K: int):
         """clip/clip.py:86-98: (softmax_K(cos * exp(logit_scale)), cos), both [B, K], from un-normalised embeddings."""
         ie = np.ascontiguousarray(image_embeds, np.float32)
@@ -808,6 +861,44 @@ class EngineGroup:
         outs = self._run([(lambda e=e, lo=lo, hi=hi: e.generate_rows_hp(init[lo:hi], None if ln is None else ln[lo:hi], seed_len, top_k,
                                                                         pos[:, lo:hi], hps[lo:hi], n_mask=n_mask, snapshot_every=every,
                                                                         want_cos=want_cos))
+                          for e, (lo, hi) in zip(self.engines, parts)])
+        return np.concatenate([o[0] for o in outs], axis=1), (np.concatenate([o[1] for o in outs], axis=1) if want_cos else None)
+
+    def generate_rows_draw(self, init_rows, lens, seed_len: int, top_k: int, positions, hypers, draws, image_of_row=None,
+                           n_mask=None, snapshot_every=None, want_cos: bool = True):
+        """Engine.generate_rows_draw with the rows split contiguously over the streams, as generate_rows_hp splits them.  A row's
+        draw record travels with it and holds everything its draws depend on (seed, tau, step offset), so the result does not
+        depend on the split."""
+        pos = np.ascontiguousarray(positions, dtype=np.int32)
+        init = np.ascontiguousarray(init_rows, dtype=np.int32)
+        ln = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32).reshape(-1)
+        if pos.ndim != 2:
+            raise ValueError("generate_rows_draw: positions must be [n_steps, R]")
+        R = pos.shape[1]
+        if init.ndim != 2 or init.shape[0] != R:
+            raise ValueError(f"generate_rows_draw: init_rows must be [R, T] with R = {R}, got {init.shape}")
+        if ln is not None and ln.size != R:
+            raise ValueError(f"generate_rows_draw: lens has {ln.size} entries for {R} rows")
+        hps = list(hypers)
+        if len(hps) != R:
+            raise ValueError(f"generate_rows_draw: hypers has {len(hps)} entries for {R} rows")
+        drs = None if draws is None else list(draws)
+        if drs is not None and len(drs) != R:
+            raise ValueError(f"generate_rows_draw: draws has {len(drs)} entries for {R} rows")
+        embeds = self._full_embeds if self._full_embeds is not None else self._encoded
+        if embeds is None:
+            raise NativeError("EngineGroup.generate_rows_draw: encode_images / set_image_embeds first")
+        ior = np.arange(R) if image_of_row is None else np.asarray(image_of_row, dtype=np.int64).reshape(-1)
+        if ior.size != R or (R and (ior.min() < 0 or ior.max() >= embeds.shape[0])):
+            raise NativeError("EngineGroup.generate_rows_draw: image_of_row outside the resident image batch", code=native.ERR_ARG)
+        every = snapshot_every or max(int(ln.max()) if ln is not None else init.shape[1] - seed_len - 1, 1)
+        parts = self.parts(R)
+        for e, (lo, hi) in zip(self.engines, parts):
+            e.set_image_embeds(embeds[ior[lo:hi]])
+        self._full_embeds, self._resident = embeds, None
+        outs = self._run([(lambda e=e, lo=lo, hi=hi: e.generate_rows_draw(init[lo:hi], None if ln is None else ln[lo:hi], seed_len, top_k,
+                                                                          pos[:, lo:hi], hps[lo:hi], None if drs is None else drs[lo:hi],
+                                                                          n_mask=n_mask, snapshot_every=every, want_cos=want_cos))
                           for e, (lo, hi) in zip(self.engines, parts)])
         return np.concatenate([o[0] for o in outs], axis=1), (np.concatenate([o[1] for o in outs], axis=1) if want_cos else None)
 

@@ -74,6 +74,11 @@ class Hyper(C.Structure):
                 ("control", C.c_int32), ("negative", C.c_int32)]
 
 
+class Draw(C.Structure):
+    """czc_draw: a row's seed (the Philox key), its tau (0: first argmax) and the step counter of the call's first step."""
+    _fields_ = [("seed", C.c_uint64), ("tau", C.c_float), ("step0", C.c_uint32)]
+
+
 STEP_OUT_FIELDS = ["probs", "idxs", "cand_ids", "clip_ids", "clip_len", "clip_score", "clip_ref", "senti_raw",
                    "repeats", "final_score", "best", "best_cos", "logits"]
 
@@ -117,6 +122,7 @@ SIGNATURES = {
     "czc_generate_rows_from": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P, _I, C.POINTER(Hyper), _P, _P]),
     "czc_generate_rows_len": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _I, C.POINTER(Hyper), _P, _P]),
     "czc_generate_rows_hp": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _I, C.POINTER(Hyper), _P, _P]),
+    "czc_generate_rows_draw": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _I, C.POINTER(Hyper), C.POINTER(Draw), _P, _P]),
     "czc_set_option": (_I, [_P, C.c_char_p, _I]),
     "czc_get_option": (_I, [_P, C.c_char_p, C.POINTER(_I)]),
     "czc_profile_enable": (_I, [_P, _I]),
@@ -151,6 +157,7 @@ TEST_SIGNATURES = {
     "czc_test_topk": (_I, [_I, _I, _I, _P, _P, C.c_float, _I, _I, _P, _P, _P]),
     "czc_test_bridge": (_I, [C.POINTER(BridgeTables), C.POINTER(Config), _I, _I, _P, _P, _P]),
     "czc_test_combine": (_I, [_I, _I, _I, _P, _P, C.c_float, _P, _P, _P, C.POINTER(Hyper), _P, _P, _P, _P]),
+    "czc_test_combine_draw": (_I, [_I, _I, _I, _P, _P, C.c_float, _P, _P, _P, C.POINTER(Hyper), C.POINTER(Draw), C.c_uint32, _P, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

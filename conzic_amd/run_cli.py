@@ -74,7 +74,11 @@ def batched_samples(args, run_type, all_batches, own_lo, own_hi, rank, world, im
                                prompt=args.prompt, batch_size=args.batch_size, max_len=args.sentence_len, top_k=args.candidate_k,
                                temperature=args.lm_temperature, max_iter=args.num_iterations, alpha=args.alpha, beta=args.beta,
                                generate_order=args.order, gamma=args.gamma, ctl_type=args.control_type,
-                               style_type=args.sentiment_type, pos_type=args.pos_type, schedules=sched)
+                               style_type=args.sentiment_type, pos_type=args.pos_type, schedules=sched,
+                               sample_tau=args.sample_tau, sample_seed=args.seed)
+        if S > 1:
+            from conzic_amd.diversity import log_distinct
+            log_distinct(logger, name_batch, [[o[0][-2 if len(o[0]) > 1 else -1][i] for o in outs] for i in range(len(name_batch))])
         for s, (gen_texts, _) in enumerate(outs):
             results[s] = merge_results(results[s], gen_texts, name_batch)
     for sample_id in range(S):
@@ -126,7 +130,8 @@ def lengths_batches(args, run_type, all_batches, own_lo, own_hi, rank, world, im
                                    prompt=args.prompt, batch_size=args.batch_size, top_k=args.candidate_k,
                                    temperature=args.lm_temperature, max_iter=args.num_iterations, alpha=args.alpha, beta=args.beta,
                                    generate_order=args.order, gamma=args.gamma, ctl_type=args.control_type,
-                                   style_type=args.sentiment_type, pos_type=args.pos_type)
+                                   style_type=args.sentiment_type, pos_type=args.pos_type, sample_tau=args.sample_tau,
+                                   sample_seed=args.seed, sample0=sample_id or 0)
             if batch_idx not in embed_cache:
                 embed_cache[batch_idx] = clip.last_image_embeds()
             for l, per_sample in enumerate(outs):
@@ -187,7 +192,8 @@ def signals_batches(args, all_batches, own_lo, own_hi, rank, world, img_dir, lm_
             outs = caption_signals(sigs, lens, per_call, name_batch, lm_model, clip, lm_tokenizer, imgs, token_mask, logger,
                                    prompt=args.prompt, batch_size=args.batch_size, top_k=args.candidate_k,
                                    temperature=args.lm_temperature, max_iter=args.num_iterations, alpha=args.alpha, beta=args.beta,
-                                   generate_order=args.order, gamma=args.gamma, pos_type=args.pos_type)
+                                   generate_order=args.order, gamma=args.gamma, pos_type=args.pos_type, sample_tau=args.sample_tau,
+                                   sample_seed=args.seed, sample0=sample_id or 0)
             if batch_idx not in embed_cache:
                 embed_cache[batch_idx] = clip.last_image_embeds()
             for g, per_len in enumerate(outs):
@@ -233,7 +239,7 @@ def infill_batches(args, all_batches, own_lo, own_hi, rank, world, img_dir, lm_m
         outs = infill_captions(caps, name_batch, lm_model, clip, lm_tokenizer, imgs, token_mask, logger, prompt=args.prompt,
                                top_k=args.candidate_k, temperature=args.lm_temperature, max_iter=args.num_iterations,
                                alpha=args.alpha, beta=args.beta, generate_order=args.order, positions=args.infill_positions,
-                               image_of_caption=image_of_caption)
+                               image_of_caption=image_of_caption, sample_tau=args.sample_tau, sample_seed=args.seed)
         for i, (gen_texts, _) in enumerate(outs):
             key = name_batch[i // C] if C == 1 else f"{name_batch[i // C]}#{i % C}"
             # (a batch whose captions have no blank at all returns no snapshots: its files repeat the best entry)
@@ -377,6 +383,7 @@ def main(argv=None):
         batched_samples(args, run_type, all_batches, own_lo, own_hi, rank, world, img_dir, lm_model, clip, lm_tokenizer,
                         token_mask, logger)
         return
+    finals = {}   # image name -> the final caption of every sample
     for sample_id in range(args.samples_num):
         all_results = [None] * (args.num_iterations + 1)
         logger.info(f"Sample {sample_id + 1}: ")
@@ -392,7 +399,13 @@ def main(argv=None):
             kw = dict(prompt=args.prompt, batch_size=args.batch_size, max_len=args.sentence_len,
                       top_k=args.candidate_k, temperature=args.lm_temperature, max_iter=args.num_iterations,
                       alpha=args.alpha, beta=args.beta, generate_order=args.order)
-            if args.run_type == 'caption':
+            if args.sample_tau:   # the sample loop under --sample_tau: this sample's seeds, one engine call per sample
+                from conzic_amd.runtime import caption_samples
+                (gen_texts, _), = caption_samples(1, args.run_type, name_batch, lm_model, clip, lm_tokenizer, imgs, token_mask, logger,
+                                                  gamma=args.gamma, ctl_type=args.control_type, style_type=args.sentiment_type,
+                                                  pos_type=args.pos_type, sample_tau=args.sample_tau, sample_seed=args.seed,
+                                                  sample0=sample_id, **kw)
+            elif args.run_type == 'caption':
                 gen_texts, _ = generate_caption(name_batch, lm_model, clip, lm_tokenizer, imgs, token_mask, logger, **kw)
             else:
                 gen_texts, _ = control_generate_caption(name_batch, lm_model, clip, lm_tokenizer, imgs, token_mask,
@@ -401,6 +414,8 @@ def main(argv=None):
             if batch_idx not in embed_cache:
                 embed_cache[batch_idx] = clip.last_image_embeds()
             all_results = merge_results(all_results, gen_texts, name_batch)
+            for name, text in zip(name_batch, gen_texts[-2 if len(gen_texts) > 1 else -1]):
+                finals.setdefault(name, []).append(text)
         if world > 1:
             import torch.distributed as tdist
             parts = [None] * world
@@ -412,6 +427,9 @@ def main(argv=None):
                         all_results[it] = {**(all_results[it] or {}), **d}
         if rank == 0:
             write_results(result_dir(args, run_type, sample_id), all_results)
+    if args.samples_num > 1:   # (every rank logs the images of its own batches)
+        from conzic_amd.diversity import log_distinct
+        log_distinct(logger, list(finals), list(finals.values()))
 
 
 if __name__ == "__main__":

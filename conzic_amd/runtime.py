@@ -385,7 +385,8 @@ def run_generation(order: str, img_name, model, clip, tokenizer, image_instance,
 
 def run_generation_samples(order: str, samples_num: int, img_name, model, clip, tokenizer, image_instance, token_mask, prompt,
                            logger, max_len, top_k, temperature, alpha, beta, max_iters, batch_size, verbose=True, gamma=None,
-                           ctl_signal="positive", print_every: Optional[int] = None, pos_template=None, schedules=None):
+                           ctl_signal="positive", print_every: Optional[int] = None, pos_template=None, schedules=None,
+                           sample_tau: float = 0.0, sample_seed: int = 0, sample0: int = 0):
     """The sample loop around a *_generation call (demo.py:83, run.py) as ONE engine call: `samples_num` samples of a batch of
     `batch_size` images ride as batch_size * samples_num rows of czc_generate_rows, every sample with the visiting order the
     serial loop would have drawn for it (harness.sample_schedules); the images are encoded once.  Returns a list of
@@ -394,7 +395,11 @@ def run_generation_samples(order: str, samples_num: int, img_name, model, clip, 
     told one position per step, so with orders that differ between samples the engine is called once per sample, as the serial
     loop calls it (same orders, same results, the images still encoded once), and the log says why.
     `schedules`: what harness.sample_schedules returned for these samples when the caller drew the orders itself (run_cli draws
-    those of all batches first, in the serial loop's sample-major order); None: drawn here."""
+    those of all batches first, in the serial loop's sample-major order); None: drawn here.
+    `sample_tau` > 0: every row draws its winner from softmax_K(final_score / sample_tau) (czc_generate_rows_draw) under the
+    seed of its (image, sample): draws.row_seed(sample_seed, key of the image's name, sample0 + s).  A serial loop that calls
+    this function once per sample (samples_num = 1, sample0 = the sample's index) returns the ids of the one batched call."""
+    from . import draws as dw
     import utils as ref_utils
     S, B = int(samples_num), int(batch_size)
     eng = get_engine(model, clip, tokenizer)
@@ -414,6 +419,8 @@ def run_generation_samples(order: str, samples_num: int, img_name, model, clip, 
     orders_differ = bool((positions != positions[:, :1]).any())
     hp = Engine.hyper(alpha, beta, temperature, gamma, ctl_signal == "negative",
                       control="pos" if pos_template is not None else None)
+    row_draws = dw.sample_rows(sample_seed, [dw.image_key(n) for n in img_name], S, float(sample_tau or 0.0), sample0=sample0)
+    init_row = np.asarray(batch[0], dtype=np.int32)
 
     def polish(eng):
         eng.set_token_mask(_mask_to_numpy(token_mask))
@@ -440,10 +447,18 @@ def run_generation_samples(order: str, samples_num: int, img_name, model, clip, 
             runner.set_image_embeds(emb)
         if eng.precision == native.PREC_REFINE:
             runner.refine_guard(reset=True)
-        if one_by_one:
+        if one_by_one and row_draws is not None:
+            outs = [runner.generate_rows_draw(np.repeat(init_row[None, :], B, axis=0), None, seed_len, top_k,
+                                              np.repeat(positions[:, s:s + 1], B, axis=1), [hp] * B, row_draws[s * B:(s + 1) * B],
+                                              n_mask=n_mask, snapshot_every=every) for s in range(S)]
+            out = tuple(np.concatenate([o[j] for o in outs], axis=1) for j in (0, 1))
+        elif one_by_one:
             outs = [runner.generate(B, batch[0], max_len, seed_len, top_k, positions[:, s].tolist(), hp, n_mask=n_mask,
                                     snapshot_every=every) for s in range(S)]
             out = tuple(np.concatenate([o[j] for o in outs], axis=1) for j in (0, 1))
+        elif row_draws is not None:
+            out = runner.generate_rows_draw(np.repeat(init_row[None, :], B * S, axis=0), None, seed_len, top_k, rows_pos, [hp] * (B * S),
+                                            row_draws, image_of_row=image_of_row, n_mask=n_mask, snapshot_every=every)
         else:
             out = runner.generate_rows(batch[0], max_len, seed_len, top_k, rows_pos, hp, image_of_row=image_of_row,
                                        n_mask=n_mask, snapshot_every=every)
@@ -456,8 +471,11 @@ def run_generation_samples(order: str, samples_num: int, img_name, model, clip, 
         ref_utils.update_token_mask(tokenizer, token_mask, max_len, int(positions[-1, S - 1]))
     out = []
     for s in range(S):
+        said = dw.describe(row_draws[s * B:(s + 1) * B] if row_draws else None)
         if order_lists is not None:
-            logger.info(f"Order_list:{order_lists[s]}")
+            logger.info(f"Order_list:{order_lists[s]}" + said)
+        elif said:
+            logger.info(f"Order:{order}" + said)
         out.append(_bookkeeping(order, ids[:, s * B:(s + 1) * B], cos[:, s * B:(s + 1) * B], tokenizer, img_name, logger, B,
                                 verbose, print_every))
     return out
@@ -465,7 +483,8 @@ def run_generation_samples(order: str, samples_num: int, img_name, model, clip, 
 
 def run_generation_lengths(order: str, lens: Sequence[int], samples_num: int, img_name, model, clip, tokenizer, image_instance,
                            token_mask, prompt, logger, top_k, temperature, alpha, beta, max_iters, batch_size, verbose=True,
-                           gamma=None, ctl_signal="positive", pos_template=None):
+                           gamma=None, ctl_signal="positive", pos_template=None, sample_tau: float = 0.0, sample_seed: int = 0,
+                           sample0: int = 0, column0: int = 0):
     """The loop over sentence lengths around the sample loop (one CLI run per --sentence_len) as ONE engine call: `samples_num`
     samples at each length of `lens` of a batch of `batch_size` images ride as len(lens) * samples_num * batch_size rows of
     czc_generate_rows_len, row (l * samples_num + s) * batch_size + b = sample s at lens[l] of image b, at its own length
@@ -475,9 +494,11 @@ def run_generation_lengths(order: str, lens: Sequence[int], samples_num: int, im
     of `samples_num` (gen_texts_list, clip_score_sequence) pairs, each as the `run_generation` call at that length returns it, and
     logs every call's lines in the serial loop's order.  The reference's own sentence scorer (exact control mode) is told one
     position and one row length per step: with it the engine is called once per length and sample, as the serial loop calls it
-    (same orders, same results, the images still encoded once), and the log says why."""
+    (same orders, same results, the images still encoded once), and the log says why.
+    `sample_tau` > 0: every row draws its winner (czc_generate_rows_draw) under draws.row_seed(sample_seed, key of the image's
+    name, sample0 + s, column0 + l); a row's step counter is its step in the call at hand."""
     import utils as ref_utils
-    from . import lengths
+    from . import draws as dw, lengths
     lens = [int(n) for n in lens]
     S, B, NL = int(samples_num), int(batch_size), len(lens)
     if S < 1 or B < 1:
@@ -500,6 +521,8 @@ def run_generation_lengths(order: str, lens: Sequence[int], samples_num: int, im
     T = init_rows.shape[1]
     hp = Engine.hyper(alpha, beta, temperature, gamma, ctl_signal == "negative",
                       control="pos" if pos_template is not None else None)
+    row_draws = dw.sample_rows(sample_seed, [dw.image_key(n) for n in img_name], S, float(sample_tau or 0.0), columns=NL,
+                               sample0=sample0, column0=column0)
 
     def polish(eng):
         eng.set_token_mask(_mask_to_numpy(token_mask))
@@ -531,9 +554,17 @@ def run_generation_lengths(order: str, lens: Sequence[int], samples_num: int, im
             cos = np.zeros((max_iters, NL * S * B), dtype=np.float32)
             for c, n in enumerate(col_lens):
                 own = positions.reshape(max_iters, every, NL * S)[:, :n, c].reshape(-1).tolist()   # the column without its idle steps
-                i1, c1 = runner.generate(B, col_rows[c, :seed_len + n + 1].tolist(), n, seed_len, top_k, own, hp, snapshot_every=n)
+                if row_draws is not None:
+                    i1, c1 = runner.generate_rows_draw(np.repeat(col_rows[c:c + 1, :seed_len + n + 1], B, axis=0), None, seed_len, top_k,
+                                                       np.repeat(np.asarray(own, dtype=np.int32)[:, None], B, axis=1), [hp] * B,
+                                                       row_draws[c * B:(c + 1) * B], snapshot_every=n)
+                else:
+                    i1, c1 = runner.generate(B, col_rows[c, :seed_len + n + 1].tolist(), n, seed_len, top_k, own, hp, snapshot_every=n)
                 ids[:, c * B:(c + 1) * B, :seed_len + n + 1], cos[:, c * B:(c + 1) * B] = i1, c1
             out = (ids, cos)
+        elif row_draws is not None:
+            out = runner.generate_rows_draw(init_rows, row_lens, seed_len, top_k, rows_pos, [hp] * len(row_lens), row_draws,
+                                            image_of_row=image_of_row, n_mask=n_mask, snapshot_every=every)
         else:
             out = runner.generate_rows_len(init_rows, row_lens, seed_len, top_k, rows_pos, hp, image_of_row=image_of_row,
                                            n_mask=n_mask, snapshot_every=every)
@@ -550,8 +581,11 @@ def run_generation_lengths(order: str, lens: Sequence[int], samples_num: int, im
         per_sample = []
         for s in range(S):
             c = l * S + s
+            said = dw.describe(row_draws[c * B:(c + 1) * B] if row_draws else None)
             if order == "shuffle":
-                logger.info(f"Order_list:{[int(p) for p in positions[:n, c]]}")
+                logger.info(f"Order_list:{[int(p) for p in positions[:n, c]]}" + said)
+            elif said:
+                logger.info(f"Order:{order}" + said)
             per_sample.append(_bookkeeping(order, ids[:, c * B:(c + 1) * B, :seed_len + n + 1], cos[:, c * B:(c + 1) * B], tokenizer,
                                            img_name, logger, B, verbose, None))
         out.append(per_sample)
@@ -560,7 +594,8 @@ def run_generation_lengths(order: str, lens: Sequence[int], samples_num: int, im
 
 def run_infill(captions: Sequence[str], img_name, model, clip, tokenizer, image_instance, token_mask, prompt, logger, *,
                order: str = "sequential", max_iters: int = 10, top_k: int = 200, temperature=0.1, alpha=0.02, beta=2.0,
-               positions: str = "blanks", image_of_caption: Optional[Sequence[int]] = None, blank: str = "_", verbose=True):
+               positions: str = "blanks", image_of_caption: Optional[Sequence[int]] = None, blank: str = "_", verbose=True,
+               sample_tau: float = 0.0, sample_seed: int = 0):
     """Infilling, resume and draft polishing (beyond the reference's CLI; its loop body, gen_utils.py:64-81, unchanged): every
     caption of `captions` is a template whose `blank` words are polished while the given words stay as context
     (`positions="blanks"`), or a draft / earlier result of which every position is polished again (`positions="all"`: nothing is
@@ -571,9 +606,10 @@ def run_infill(captions: Sequence[str], img_name, model, clip, tokenizer, image_
     sweep.  Logs, results and the token mask keep the order of infill.group_by_length (captions of one token length together,
     lengths in order of first appearance).  `max_iters` sweeps; honours CZC_MEMO_ROWS.  Returns one (gen_texts_list, clip_score_sequence) pair per caption, in the
     structure a *_generation call returns for a batch of one.  The caller's token_mask is left as after the last visited
-    position (utils.py:53-59)."""
+    position (utils.py:53-59).  `sample_tau` > 0: caption i draws its winners (czc_generate_rows_draw) under
+    draws.row_seed(sample_seed, key of its image's name, 0, i)."""
     import utils as ref_utils
-    from . import infill
+    from . import draws as dw, infill
     captions = list(captions)
     if not captions:
         return []
@@ -599,9 +635,15 @@ def run_infill(captions: Sequence[str], img_name, model, clip, tokenizer, image_
     (T, members), = infill.group_for_call(parsed).items()   # every caption, in caption order: one call
     # one draw per caption from the process-global stream for `shuffle`, in caption order
     pos_all, n_mask, every = infill.infill_schedules(visits, order, max_iters)
-    if order == "shuffle":
-        for i, v in enumerate(visits):
-            logger.info(f"Order_list:{[int(p) for p in pos_all[:len(v), i]]}")
+    row_draws = None
+    if sample_tau:
+        row_draws = [dw.make_draw(dw.row_seed(sample_seed, dw.image_key(img_name[ioc[i]]), 0, i), sample_tau) for i in range(len(captions))]
+    for i, v in enumerate(visits):
+        said = dw.describe(row_draws[i:i + 1] if row_draws else None)
+        if order == "shuffle":
+            logger.info(f"Order_list:{[int(p) for p in pos_all[:len(v), i]]}" + said)
+        elif said:
+            logger.info(f"Order:{order}" + said)
     hp = Engine.hyper(alpha, beta, temperature)
     seed_len = parsed[0][3]
     init_rows = np.zeros((len(members), T), dtype=np.int32)   # id 0 ([PAD]) behind a shorter caption's [SEP]
@@ -618,7 +660,10 @@ def run_infill(captions: Sequence[str], img_name, model, clip, tokenizer, image_
             runner.set_image_embeds(emb)
         if eng.precision == native.PREC_REFINE:
             runner.refine_guard(reset=True)
-        if int(row_lens.min()) == int(row_lens.max()):   # one token length: czc_generate_rows_from, as before there were lengths
+        if row_draws is not None:
+            res = runner.generate_rows_draw(init_rows, row_lens, seed_len, top_k, pos_all, [hp] * len(members), row_draws,
+                                            image_of_row=image_of_row, n_mask=n_mask, snapshot_every=every)
+        elif int(row_lens.min()) == int(row_lens.max()):   # one token length: czc_generate_rows_from, as before there were lengths
             res = runner.generate_rows_from(init_rows, int(row_lens[0]), seed_len, top_k, pos_all, hp, image_of_row=image_of_row,
                                             n_mask=n_mask, snapshot_every=every)
         else:
@@ -645,14 +690,14 @@ def run_infill(captions: Sequence[str], img_name, model, clip, tokenizer, image_
 
 def infill_captions(captions, img_name, model, clip, tokenizer, image_instance, token_mask, logger, *, prompt="", top_k=100,
                     temperature=1.0, max_iter=10, alpha=0.7, beta=1, generate_order="sequential", positions="blanks",
-                    image_of_caption=None):
+                    image_of_caption=None, sample_tau=0.0, sample_seed=0):
     """`--run_type infill` of the two CLIs: one run_infill call over the `--caption` templates, logging every caption's final
     and best text as generate_caption does (gen_utils.py:325-331)."""
     start_time = time.time()
     order = "sequential" if generate_order == "sequential" else "shuffle"
     outs = run_infill(captions, img_name, model, clip, tokenizer, image_instance, token_mask, prompt, logger, order=order,
                       max_iters=max_iter, top_k=top_k, temperature=temperature, alpha=alpha, beta=beta, positions=positions,
-                      image_of_caption=image_of_caption)
+                      image_of_caption=image_of_caption, sample_tau=sample_tau, sample_seed=sample_seed)
     logger.info("Finished in %.3fs" % (time.time() - start_time))
     for i, (generate_texts, _) in enumerate(outs):
         logger.info(f"The {i + 1}-th caption: {captions[i]}")
@@ -673,7 +718,7 @@ def caption_order(run_type: str, generate_order: str, ctl_type: str, max_iter: i
 def caption_samples(samples_num: int, run_type: str, img_name, model, clip, tokenizer, image_instance, token_mask, logger, *,
                     prompt="", batch_size=1, max_len=15, top_k=100, temperature=1.0, max_iter=500, alpha=0.7, beta=1,
                     generate_order="sequential", gamma=5, ctl_type="sentiment", style_type="positive", pos_type=None,
-                    schedules=None):
+                    schedules=None, sample_tau=0.0, sample_seed=0, sample0=0):
     """`--batch_samples` of the two CLIs: what `samples_num` calls of generate_caption (run_type 'caption', gen_utils.py:289-333)
     or control_generate_caption (control_gen_utils.py:197-232) return, from one run_generation_samples call.  Returns the list
     of (generate_texts, clip_scores) pairs and logs every sample's final and best captions as those functions do."""
@@ -691,10 +736,11 @@ def caption_samples(samples_num: int, run_type: str, img_name, model, clip, toke
         logger.info(pos_type)
         kw.update(gamma=gamma, pos_template=pos_type)
     outs = run_generation_samples(order, samples_num, img_name, model, clip, tokenizer, image_instance, token_mask, prompt,
-                                  logger, max_len, top_k, temperature, alpha, beta, max_iters, batch_size, schedules=schedules, **kw)
+                                  logger, max_len, top_k, temperature, alpha, beta, max_iters, batch_size, schedules=schedules,
+                                  sample_tau=sample_tau, sample_seed=sample_seed, sample0=sample0, **kw)
     logger.info("Finished %d samples in %.3fs" % (samples_num, time.time() - start_time))
     for sample_id, (generate_texts, _) in enumerate(outs):
-        logger.info(f"Sample {sample_id}: ")
+        logger.info(f"Sample {sample0 + sample_id}: ")
         for i in range(batch_size):
             logger.info(f"The {i + 1}-th image: {img_name[i]}")
             logger.info(f"final caption: {generate_texts[-2][i]}")
@@ -704,7 +750,8 @@ def caption_samples(samples_num: int, run_type: str, img_name, model, clip, toke
 
 def caption_lengths(lens: Sequence[int], samples_num: int, run_type: str, img_name, model, clip, tokenizer, image_instance, token_mask,
                     logger, *, prompt="", batch_size=1, top_k=100, temperature=1.0, max_iter=500, alpha=0.7, beta=1,
-                    generate_order="sequential", gamma=5, ctl_type="sentiment", style_type="positive", pos_type=None):
+                    generate_order="sequential", gamma=5, ctl_type="sentiment", style_type="positive", pos_type=None,
+                    sample_tau=0.0, sample_seed=0, sample0=0):
     """`--sentence_lens` of the two CLIs: what `samples_num` calls of generate_caption (run_type 'caption') or
     control_generate_caption at max_len = n return for every n of `lens`, from one run_generation_lengths call.  Returns, per
     length, the list of `samples_num` (generate_texts, clip_scores) pairs and logs every length's and sample's final and best
@@ -724,7 +771,8 @@ def caption_lengths(lens: Sequence[int], samples_num: int, run_type: str, img_na
         logger.info(pos_type)
         kw.update(gamma=gamma, pos_template=pos_type)
     outs = run_generation_lengths(order, lens, samples_num, img_name, model, clip, tokenizer, image_instance, token_mask, prompt,
-                                  logger, top_k, temperature, alpha, beta, max_iters, batch_size, **kw)
+                                  logger, top_k, temperature, alpha, beta, max_iters, batch_size,
+                                  sample_tau=sample_tau, sample_seed=sample_seed, sample0=sample0, **kw)
     logger.info("Finished %d lengths x %d samples in %.3fs" % (len(lens), samples_num, time.time() - start_time))
     for n, per_sample in zip(lens, outs):
         for sample_id, (generate_texts, _) in enumerate(per_sample):
@@ -749,7 +797,8 @@ def _signal_kw(signal: str, gamma, pos_type) -> dict:
 
 def run_generation_signals(signals: Sequence[str], lens: Sequence[int], samples_num: int, generate_order: str, img_name, model, clip,
                            tokenizer, image_instance, token_mask, prompt, logger, top_k, temperature, alpha, beta, max_iter,
-                           batch_size, verbose=True, gamma=5, pos_template=None):
+                           batch_size, verbose=True, gamma=5, pos_template=None, sample_tau: float = 0.0, sample_seed: int = 0,
+                           sample0: int = 0):
     """The loop over control signals around the loops over lengths and samples (one CLI run per --run_type / --control_type /
     --sentiment_type) as ONE engine call: every signal x length x sample of a batch of `batch_size` images is a row of
     czc_generate_rows_hp with its own czc_hyper (signals.expand / signals.batch_rows), at its own length and with the visiting
@@ -757,9 +806,11 @@ def run_generation_signals(signals: Sequence[str], lens: Sequence[int], samples_
     and POS tags) are configured once and the images encoded once.  Returns, per signal, what run_generation_lengths returns
     for it (per length a list of `samples_num` (gen_texts_list, clip_score_sequence) pairs) and logs every call's lines in the
     serial loop's order.  The reference's own sentence scorer (exact control mode) is configured for one signal: with it the
-    signals run one call each, as the serial loop runs them, and the log says why."""
+    signals run one call each, as the serial loop runs them, and the log says why.
+    `sample_tau` > 0: every row draws its winner (czc_generate_rows_draw) under draws.row_seed(sample_seed, key of the image's
+    name, sample0 + s, g * len(lens) + l)."""
     import utils as ref_utils
-    from . import control, signals as sg
+    from . import control, draws as dw, signals as sg
     signals = sg.parse_signals(signals)
     lens = [int(n) for n in lens]
     S, B, NL = int(samples_num), int(batch_size), len(lens)
@@ -780,10 +831,11 @@ def run_generation_signals(signals: Sequence[str], lens: Sequence[int], samples_
                         f"{len(signals)} signals one call at a time (CZC_CONTROL=table batches them)")
             eng._one_by_one_signals_logged = True
         out = []
-        for sig in signals:
+        for g, sig in enumerate(signals):
             order, max_iters = sg.signal_order(sig, generate_order, max_iter, max(lens))
             out.append(run_generation_lengths(order, lens, S, img_name, model, clip, tokenizer, image_instance, token_mask, prompt, logger,
-                                              top_k, temperature, alpha, beta, max_iters, B, verbose=verbose,
+                                              top_k, temperature, alpha, beta, max_iters, B, verbose=verbose, sample_tau=sample_tau,
+                                              sample_seed=sample_seed, sample0=sample0, column0=g * NL,
                                               **_signal_kw(sig, gamma, pos_template)))
         return out
     seed_len = len(prompt.split()) + 1
@@ -795,6 +847,8 @@ def run_generation_signals(signals: Sequence[str], lens: Sequence[int], samples_
                     + (f" (exp(logit_scale) = {math.exp(scale):.1f})" if scale is not None else ""))
         eng._precision_logged = True
     init_rows, row_lens, rows_pos, hypers, image_of_row = sg.batch_rows(rows, tokenizer, prompt, B)
+    row_draws = dw.sample_rows(sample_seed, [dw.image_key(n) for n in img_name], S, float(sample_tau or 0.0),
+                               columns=len(signals) * NL, sample0=sample0)
 
     def polish(eng):
         eng.set_token_mask(_mask_to_numpy(token_mask))
@@ -812,8 +866,12 @@ def run_generation_signals(signals: Sequence[str], lens: Sequence[int], samples_
             runner.set_image_embeds(emb)
         if eng.precision == native.PREC_REFINE:
             runner.refine_guard(reset=True)
-        res = runner.generate_rows_hp(init_rows, row_lens, seed_len, top_k, rows_pos, hypers, image_of_row=image_of_row,
-                                      n_mask=rows.n_mask, snapshot_every=rows.every)
+        if row_draws is not None:
+            res = runner.generate_rows_draw(init_rows, row_lens, seed_len, top_k, rows_pos, hypers, row_draws, image_of_row=image_of_row,
+                                            n_mask=rows.n_mask, snapshot_every=rows.every)
+        else:
+            res = runner.generate_rows_hp(init_rows, row_lens, seed_len, top_k, rows_pos, hypers, image_of_row=image_of_row,
+                                          n_mask=rows.n_mask, snapshot_every=rows.every)
         if runner is not eng:
             eng.set_image_embeds(emb)
         return res, runner
@@ -831,8 +889,11 @@ def run_generation_signals(signals: Sequence[str], lens: Sequence[int], samples_
             per_sample = []
             for s in range(S):
                 c = rows.column(g, l, s)
+                said = dw.describe(row_draws[c * B:(c + 1) * B] if row_draws else None)
                 if rows.orders[g] == "shuffle":
-                    logger.info(f"Order_list:{[int(p) for p in rows.positions[:n, c]]}")
+                    logger.info(f"Order_list:{[int(p) for p in rows.positions[:n, c]]}" + said)
+                elif said:
+                    logger.info(f"Order:{rows.orders[g]}" + said)
                 per_sample.append(_bookkeeping(rows.orders[g], ids[:, c * B:(c + 1) * B, :seed_len + n + 1], cos[:, c * B:(c + 1) * B],
                                                tokenizer, img_name, logger, B, verbose, None))
             per_len.append(per_sample)
@@ -842,7 +903,7 @@ def run_generation_signals(signals: Sequence[str], lens: Sequence[int], samples_
 
 def caption_signals(signals: Sequence[str], lens: Sequence[int], samples_num: int, img_name, model, clip, tokenizer, image_instance,
                     token_mask, logger, *, prompt="", batch_size=1, top_k=100, temperature=1.0, max_iter=500, alpha=0.7, beta=1,
-                    generate_order="sequential", gamma=5, pos_type=None):
+                    generate_order="sequential", gamma=5, pos_type=None, sample_tau=0.0, sample_seed=0, sample0=0):
     """`--signals` of the two CLIs: what `samples_num` calls of generate_caption (signal `caption`) or control_generate_caption
     (`positive`, `negative`: ctl_type sentiment; `pos`: ctl_type pos) at max_len = n return for every signal and every n of
     `lens`, from one run_generation_signals call.  Returns, per signal, per length, the list of `samples_num` (generate_texts,
@@ -855,7 +916,7 @@ def caption_signals(signals: Sequence[str], lens: Sequence[int], samples_num: in
         raise ValueError("caption_signals: no sentence length given")
     outs = run_generation_signals(signals, lens, samples_num, generate_order, img_name, model, clip, tokenizer, image_instance,
                                   token_mask, prompt, logger, top_k, temperature, alpha, beta, max_iter, batch_size, gamma=gamma,
-                                  pos_template=pos_type)
+                                  pos_template=pos_type, sample_tau=sample_tau, sample_seed=sample_seed, sample0=sample0)
     logger.info("Finished %d signals x %d lengths x %d samples in %.3fs" % (len(signals), len(lens), samples_num, time.time() - start_time))
     for sig, per_len in zip(signals, outs):
         for n, per_sample in zip(lens, per_len):

@@ -382,6 +382,49 @@ int czc_generate_rows_hp(czc_engine* e, int R, int T, int seed_len, const int32_
                          const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp_of_row_host /* [R] */,
                          int32_t* out_ids, float* out_cos);
 
+/* czc_generate_rows_hp with a seeded DRAW of the winner per row: row r may take its winner from softmax_K(final_score / tau)
+ * instead of the first argmax (the reference's generate_step has such a branch; its caption path never reaches it).  Under the
+ * argmax rule two samples of an image differ only by their visiting order; with a tau and a seed per row, S rows of one image
+ * give S reproducible, different captions under any order.  Everything not named here is czc_generate_rows_hp's: ragged
+ * lengths, idle steps, image_of_row, per-row czc_hyper, snapshots, control callback and tables.
+ *   The draw of a row with 64-bit `seed`, at step s of the call's schedule (0-based), for candidate k in [0, K):
+ *     1. x = output word (k & 3) of Philox4x32 with 10 rounds (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9,
+ *        0xBB67AE85), key = (seed & 0xffffffff, seed >> 32), counter = (step0 + s, k >> 2, 0, 0).  Counter 0 under key 0
+ *        gives 6627e8d5 e169c58d bc57ac4c 9b00dbd8.
+ *     2. u = ((x >> 9) + 0.5) * 2^-23: exact in fp32 and strictly inside the unit interval.
+ *     3. g = -logf(-logf(u)).
+ *     4. z_k = final_k / tau + g in fp32; a candidate with probs_k == 0 (turned into id 0 by the token mask, or without mass
+ *        from BERT) takes z_k = -inf.
+ *     5. winner = the first index of the maximum z; with no eligible candidate, the first argmax of final as before.
+ *   Write-back into the row's own column, best and best_cos follow the winner unchanged.
+ *   - a row's result is a function of its content, its hyper-parameters, its seed and the step counter only: not of its index,
+ *     its companions in the batch, compaction, streams or engine replicas.
+ *   - draw_of_row == NULL, or every tau == 0: czc_generate_rows_hp itself, bit for bit.  In a mixed call a tau == 0 row returns
+ *     what czc_generate_rows_hp returns for it (the caveats are those stated for compact batches and the CZC_PREC_SPLIT /
+ *     CZC_PREC_REFINE cosines).
+ *   - step0 and resume: call A runs n steps; call B starts from A's last snapshot with the rest of the schedule and
+ *     step0 = n, and returns what one call over the whole schedule returns (the resume property of czc_generate_rows_from).
+ *   - the [R] array is uploaded once, with the schedule; a compact batch gathers the records through the run list it has.  No
+ *     device-to-host read beyond those of czc_generate_rows_hp.
+ *   - option "memo_rows": a row with tau > 0 never hits -- its outcome is not a function of its masked row alone -- and always
+ *     runs; tau == 0 rows hit as before.  Captions are those of memo_rows = 0.
+ *   - CZC_PREC_REFINE: the draw happens in the final combine, never in the screening one.  A tau > 0 row is never margin-gated
+ *     (the gate proves an argmax) and takes the full selection.  The cosine returned for a drawn winner that was not re-encoded
+ *     is its screening cosine minus the estimated mean error of the screening tower, i.e. within the guard's bound
+ *     (czc_refine_guard) of the exact one.  Guard and audit steps are unchanged.
+ * Checked before any GPU work, and the engine stays usable.  CZC_ERR_ARG: a tau that is not finite or < 0, step0 + n_steps
+ * beyond 32 bits, and everything czc_generate_rows_hp checks. */
+typedef struct czc_draw {
+  uint64_t seed;  /* the row's own: the Philox key */
+  float tau;      /* 0: the row keeps the first argmax */
+  uint32_t step0; /* step counter of the call's first step (resume: the steps already run) */
+} czc_draw;
+int czc_generate_rows_draw(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host,
+                           const int32_t* len_of_row_host /* NULL: every row has L = T - seed_len - 1 */,
+                           const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
+                           const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp_of_row_host /* [R] */,
+                           const czc_draw* draw_of_row_host /* [R], or NULL */, int32_t* out_ids, float* out_cos);
+
 /* Engine options (all are exact work reductions / kernel choices; results agree within the engine precision):
  *   "share_prefix"    (1) encode the causal prefix common to an image's K candidates once per step instead of K
  *                         times

@@ -83,6 +83,11 @@ int czc_test_bridge(const czc_bridge_tables* t, const czc_config* cfg, int n_row
 int czc_test_combine(int B, int K, int D, const float* text_feat, const float* img_embeds, float logit_scale,
                      const float* probs, const float* senti_raw, const float* repeats, const czc_hyper* hp,
                      float* clip_score, float* clip_ref, float* final_score, int32_t* best);
+/* czc_test_combine through the drawing instantiation of the combine kernel: draw [B] (a tau == 0 row keeps the first argmax),
+ * step = the step index added to every record's step0. */
+int czc_test_combine_draw(int B, int K, int D, const float* text_feat, const float* img_embeds, float logit_scale,
+                          const float* probs, const float* senti_raw, const float* repeats, const czc_hyper* hp,
+                          const czc_draw* draw, uint32_t step, float* final_score, int32_t* best);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -21,7 +21,15 @@ alone, e.g. on a library built from another commit (CZC_LIB_PATH) for an A/B of 
 One image at several sentence lengths: the serial loop (one czc_generate call at batch size 1 per length) against one
 czc_generate_rows_len call with one row per length, every row under its own shuffle order (lengths.length_schedules).  Full-size
 towers, both logit scales; per scale the wall times of --reps alternating serial / one-call repetitions after one warm-up of
-each, their spread, whether the one call was faster in every repetition and whether every sweep's ids agree row for row."""
+each, their spread, whether the one call was faster in every repetition and whether every sweep's ids agree row for row.
+
+    python tools/rows_probe.py --sample_tau 0.5 [--S 16] [--reps 5] [--out profiles/r11_draw_probe.json]
+
+The cost of sampled winners: one image x S rows under their own shuffle orders, one czc_generate_rows_draw call with every tau 0
+(the argmax path, i.e. czc_generate_rows_hp) against the same call with every tau = --sample_tau and a seed per row.  Full-size
+towers, both logit scales; per scale the wall times of --reps alternating repetitions after one warm-up of each, each arm's spread
+((max - min) / median), the median ratio, and the distinct final captions and Div-1 / Div-2 (over token ids) of each arm.
+`--describe_draw profiles/r11_draw_probe.json` prints the README's sentence about that file (no GPU needed)."""
 import argparse
 import json
 import os
@@ -50,13 +58,37 @@ ap.add_argument("--lengths", type=lambda v: [int(n) for n in v.split(",")], defa
                 help="the lengths leg: one call per length against one czc_generate_rows_len call")
 ap.add_argument("--signals", default=None, metavar="caption,positive,negative",
                 help="the signals leg: one call per control signal against one czc_generate_rows_hp call (table mode)")
+ap.add_argument("--sample_tau", type=float, default=None, metavar="T",
+                help="the draw leg: the rows call with every tau = 0 against the same call with every tau = T")
+ap.add_argument("--describe_draw", default=None, metavar="JSON", help="print the README sentence for a draw-leg result file and exit")
 args = ap.parse_args()
 if args.out is None:
-    args.out = os.path.join(ROOT, "profiles", "r10_signals_probe.json" if args.signals else "r09_lengths_probe.json" if args.lengths else
+    args.out = os.path.join(ROOT, "profiles", "r11_draw_probe.json" if args.sample_tau else "r10_signals_probe.json" if args.signals else "r09_lengths_probe.json" if args.lengths else
                             "r09_memo_rows_probe.json" if args.memo_rows else "r08_rows_probe.json")
 
 L, K, SEED_LEN = args.L, args.K, 4
 out = []
+
+
+def describe_draw(path):
+    """The README's sentence, from the file: a ratio inside the argmax arm's own spread is "no measurable cost"."""
+    parts = []
+    for r in json.load(open(path)):
+        inside = abs(r["ratio_median"] - 1.0) <= r["spread_argmax"]
+        verdict = "no measurable cost" if inside else (f"x{r['ratio_median']:.3f} the argmax arm" + (
+            "; its steps are never margin-gated, so it re-encodes %d candidate sequences against %d" % (r["refine_seqs_draw"], r["refine_seqs_argmax"])
+            if r["precision"] == "refine" else ""))
+        parts.append(f"on the {r['precision']} engine {r['wall_s_argmax_median']:.3f} s with every tau = 0 (spread {100 * r['spread_argmax']:.1f} %) and "
+                     f"{r['wall_s_draw_median']:.3f} s with tau = {r['tau']:g} (spread {100 * r['spread_draw']:.1f} %), ratio of the medians "
+                     f"{r['ratio_median']:.3f}: {verdict}; {r['distinct_captions_argmax']} -> {r['distinct_captions_draw']} distinct captions of "
+                     f"{r['S']}, Div-1 {r['div1_ids_argmax']:.2f} -> {r['div1_ids_draw']:.2f} and Div-2 {r['div2_ids_argmax']:.2f} -> "
+                     f"{r['div2_ids_draw']:.2f} over token ids")
+    return "; ".join(parts)
+
+
+if args.describe_draw:
+    print(describe_draw(args.describe_draw))
+    sys.exit(0)
 
 
 def spread(ts):
@@ -190,13 +222,61 @@ def signals_leg():
         eng.close()
 
 
-if args.memo_rows:
+def draw_leg():
+    from conzic_amd import draws as dw, lengths
+    tau = float(args.sample_tau)
+    for scale in args.scales:
+        prec = runtime.choose_precision(scale)
+        su = harness.build_synthetic(False, prec, logit_scale=scale, regular_only=True)
+        eng = su.engine
+        eng.set_image_embeds(np.random.default_rng(100).standard_normal((1, su.clip_cfg.proj)).astype(np.float32))
+        for S in (args.S if args.S != [1, 2, 4, 8, 16] else [16]):
+            init = lengths.length_rows(su.bert_tok, "Image of a", [L] * S)
+            hps = [Engine.hyper(0.02, 2.0, 0.1) for _ in range(S)]
+            random.seed(42)
+            positions, n_mask, every, _ = harness.sample_schedules("shuffle", L, args.sweeps, S)
+            seeds = [dw.row_seed(42, 0, s) for s in range(S)]
+            arms = {"argmax": dw.draw_rows(seeds, 0.0), "draw": dw.draw_rows(seeds, tau)}
+
+            def call(arm):
+                eng.profile_reset()
+                res = eng.generate_rows_draw(init, None, SEED_LEN, K, positions, hps, arms[arm], image_of_row=[0] * S, n_mask=n_mask,
+                                             snapshot_every=every)
+                return res, eng.stats()
+
+            warm = {arm: call(arm) for arm in arms}
+            times = {arm: [] for arm in arms}
+            for _ in range(args.reps):
+                for arm in arms:
+                    eng.sync()
+                    t0 = time.perf_counter()
+                    call(arm)
+                    times[arm].append(time.perf_counter() - t0)
+            rec = dict(logit_scale=scale, precision=runtime.PRECISION_NAMES[prec], S=S, L=L, K=K, sweeps=args.sweeps, order="shuffle",
+                       images=1, tau=tau)
+            for arm in arms:
+                finals = warm[arm][0][0][-1][:, SEED_LEN:SEED_LEN + L]
+                grams = {n: [tuple(r[i:i + n]) for r in finals.tolist() for i in range(L - n + 1)] for n in (1, 2)}
+                rec.update({f"wall_s_{arm}": times[arm], f"wall_s_{arm}_median": float(np.median(times[arm])),
+                            f"spread_{arm}": spread(times[arm]), f"distinct_captions_{arm}": len({r.tobytes() for r in finals}),
+                            f"div1_ids_{arm}": len(set(grams[1])) / len(grams[1]), f"div2_ids_{arm}": len(set(grams[2])) / len(grams[2]),
+                            f"refine_seqs_{arm}": warm[arm][1]["refine_seqs"], f"gated_image_steps_{arm}": warm[arm][1]["gated_image_steps"]})
+            rec["ratio_median"] = rec["wall_s_draw_median"] / rec["wall_s_argmax_median"]
+            rec["ratio_inside_argmax_spread"] = bool(abs(rec["ratio_median"] - 1.0) <= rec["spread_argmax"])
+            print(json.dumps(rec), flush=True)
+            out.append(rec)
+        eng.close()
+
+
+if args.sample_tau:
+    draw_leg()
+elif args.memo_rows:
     memo_rows_leg()
 elif args.signals:
     signals_leg()
 elif args.lengths:
     lengths_leg()
-for scale in ([] if args.memo_rows or args.lengths or args.signals else args.scales):
+for scale in ([] if args.memo_rows or args.lengths or args.signals or args.sample_tau else args.scales):
     prec = runtime.choose_precision(scale)
     su = harness.build_synthetic(False, prec, logit_scale=scale, regular_only=True)
     eng = su.engine

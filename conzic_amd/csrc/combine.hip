@@ -390,6 +390,14 @@ int launch_refine_cosine(const float* text_feat, const float* img_n, const int* 
   return 0;
 }
 
+// the cosines alone (czc_score_rows): text_feat [B * K, D] against img_n [B, D], the arithmetic of every step's cosines
+int launch_cosine(const float* text_feat, const float* img_n, int B, int K, int D, float* cos_out, int* nonfinite, hipStream_t st) {
+  if ((long)B * K <= 0) return 0;
+  hipLaunchKernelGGL(cosine_kernel, dim3((unsigned)cdiv((long)B * K, 4)), dim3(256), 0, st, text_feat, img_n, B, K, D, cos_out, nonfinite);
+  CZC_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
 int launch_combine(const CombineArgs& a, hipStream_t st) {
   if (a.K > CB_MAXK) {
     snprintf(g_err, sizeof(g_err), "combine: K=%d > %d", a.K, CB_MAXK);

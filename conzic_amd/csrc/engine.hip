@@ -1326,12 +1326,85 @@ int memo_rows_step(czc_engine* e, MemoRowsPlan& mp, int s, int* d_inp, int R, in
                                   mp.tab, col0, j, record, d_inp, mp.bcos, e->st) ? fail(e, CZC_ERR_HIP, "%s", g_err) : 0;
 }
 
+// czc_score_rows on the device: CLIP cosine of rows [n, T] (BERT ids; len: the rows' token counts or null = T) with
+// img_rows [n, D] (normalised, row-gathered) -> cos [n].  The text bridge on the row itself -- the per-row form with K = 1 and
+// a candidate that repeats the id column 0 holds -- then the tower as czc_encode_text runs it (independent sequences, the
+// exact tower of the engine precision) and the steps' cosine kernel.  Buffers of its own: a step's are left alone.
+int score_rows_device(czc_engine* e, const int* d_rows, int n, int T, const int* d_len, const float* img_rows, float* d_cos) {
+  if (!e->finalized) return fail(e, CZC_ERR_STATE, "weights not finalized%s");
+  if (!e->has_bridge) return fail(e, CZC_ERR_STATE, "bridge tables not set%s");
+  int *gen, *cand, *cids, *clen, *totals, *flag;
+  E_CHECK(ensure(e, "sc_gen", (size_t)n * 4, (void**)&gen));
+  E_CHECK(ensure(e, "sc_cand", (size_t)n * 4, (void**)&cand));
+  E_CHECK(ensure(e, "sc_cids", (size_t)n * CZC_CLIP_MAX_LEN * 4, (void**)&cids));
+  E_CHECK(ensure(e, "sc_clen", (size_t)n * 4, (void**)&clen));
+  E_CHECK(ensure(e, "sc_tot", 32, (void**)&totals));
+  E_CHECK(ensure(e, "s_nonfinite", 32, (void**)&flag));
+  E_HIP(hipMemsetAsync(gen, 0, (size_t)n * 4, e->st));
+  E_HIP(hipMemsetAsync(totals, 0, 32, e->st));
+  E_HIP(hipMemcpy2DAsync(cand, 4, d_rows, (size_t)T * 4, 4, n, hipMemcpyDeviceToDevice, e->st));  // column 0 of every row
+  { ProfScope ps(e, "bridge", 0);
+    E_CHECK(launch_bridge_rows(e->bd, d_rows, n, T, gen, cand, 1, nullptr, nullptr, e->d_lex_cls, 0, PosDev{nullptr, nullptr, 0}, cids, clen,
+                               nullptr, nullptr, totals + 2, e->st, d_len)); }
+  float* feat;
+  E_CHECK(clip_text_forward(e, cids, clen, n, 1, 0, totals, &feat, true));  // (reads the bridge's overflow flag with the sizes)
+  { ProfScope ps(e, "combine", 0);
+    E_CHECK(launch_cosine(feat, img_rows, n, 1, e->cfg.clip_proj, d_cos, flag, e->st)); }
+  return 0;
+}
+
+// czc_generate_rows_tied: the group table of a call.  Host: dense group of every row, members (CSR, ascending, so a group's
+// first member is its lowest-numbered row).  Device (one upload): [R] group of row | [G + 1] offsets | [R] members |
+// [G] leaders | [G] the leaders' token counts (len mode; else unused)
+struct TiePlan {
+  int G = 0;
+  std::vector<int32_t> host;
+  int *d_gor = nullptr, *d_off = nullptr, *d_rows = nullptr, *d_lead = nullptr, *d_lead_len = nullptr;
+  int* rows_c = nullptr; float *img_c = nullptr, *cos_c = nullptr, *cos = nullptr;
+};
+
+int tie_begin(czc_engine* e, int R, int T, int seed_len, const int32_t* group, const int32_t* len_rows, bool want_cos, TiePlan* tp) {
+  std::vector<int32_t> dense(R, -1), gor(R);
+  int G = 0;
+  for (int r = 0; r < R; ++r) { if (dense[group[r]] < 0) dense[group[r]] = G++; gor[r] = dense[group[r]]; }
+  tp->G = G;
+  std::vector<int32_t>& h = tp->host;
+  h.assign((size_t)2 * R + 3 * G + 1, 0);
+  int32_t *off = h.data() + R, *rows = off + G + 1, *lead = rows + R, *lead_len = lead + G;
+  for (int r = 0; r < R; ++r) { h[r] = gor[r]; ++off[gor[r] + 1]; }
+  for (int g = 0; g < G; ++g) off[g + 1] += off[g];
+  std::vector<int32_t> fill(off, off + G);
+  for (int r = 0; r < R; ++r) rows[fill[gor[r]]++] = r;
+  for (int g = 0; g < G; ++g) { lead[g] = rows[off[g]]; lead_len[g] = len_rows ? seed_len + len_rows[lead[g]] + 1 : T; }
+  int* d;
+  E_CHECK(ensure(e, "g_tie", h.size() * 4, (void**)&d));
+  E_HIP(hipMemcpyAsync(d, h.data(), h.size() * 4, hipMemcpyHostToDevice, e->st));
+  tp->d_gor = d; tp->d_off = d + R; tp->d_rows = tp->d_off + G + 1; tp->d_lead = tp->d_rows + R; tp->d_lead_len = tp->d_lead + G;
+  if (want_cos) {
+    E_CHECK(ensure(e, "t_rows_c", (size_t)G * T * 4, (void**)&tp->rows_c));
+    E_CHECK(ensure(e, "t_img_c", (size_t)G * e->cfg.clip_proj * 4, (void**)&tp->img_c));
+    E_CHECK(ensure(e, "t_cos_c", (size_t)G * 4, (void**)&tp->cos_c));
+    E_CHECK(ensure(e, "t_cos", (size_t)R * 4, (void**)&tp->cos));
+  }
+  return 0;
+}
+
+// the merged captions' cosines at a snapshot: one row per group (its leader) through score_rows_device, then to every member
+int tie_score(czc_engine* e, const TiePlan& tp, const int* d_inp, int R, int T, bool len_mode) {
+  const int D = e->cfg.clip_proj;
+  E_CHECK(launch_gather_rows_w32(d_inp, tp.d_lead, tp.G, T, tp.rows_c, e->st));
+  E_CHECK(launch_gather_rows_f32(e->d_img_n, tp.d_lead, tp.G, D, tp.img_c, e->st));
+  E_CHECK(score_rows_device(e, tp.rows_c, tp.G, T, len_mode ? tp.d_lead_len : nullptr, tp.img_c, tp.cos_c));
+  E_CHECK(launch_gather_rows_w32(tp.cos_c, tp.d_gor, R, 1, tp.cos, e->st));
+  return 0;
+}
+
 }  // namespace
 
 // =================================================================================================
 extern "C" {
 
-int czc_version(void) { return 104; }
+int czc_version(void) { return 105; }
 
 const char* czc_last_error(const czc_engine* e) { return e ? e->err : czc::g_err; }
 
@@ -1963,7 +2036,8 @@ int czc_step(czc_engine* e, int32_t* inp, int B, int T, int gen_idx, int n_mask,
 static int generate_impl(czc_engine* e, bool rows, bool from, int B, int T, int L, int seed_len, const int32_t* init_ids_host,
                          const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
                          const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp, int32_t* out_ids, float* out_cos,
-                         const int32_t* len_rows = nullptr, const czc_hyper* hp_rows_host = nullptr, const czc_draw* draw_host = nullptr) {
+                         const int32_t* len_rows = nullptr, const czc_hyper* hp_rows_host = nullptr, const czc_draw* draw_host = nullptr,
+                         const int32_t* group_host = nullptr) {
   if (!e || !init_ids_host || !positions_host || !hp || B <= 0 || n_steps < 0 || snapshot_every <= 0)
     return CZC_ERR_ARG;
   if (seed_len + L > T) return fail(e, CZC_ERR_ARG, "generate: seed_len + L > T%s");
@@ -2060,6 +2134,7 @@ static int generate_impl(czc_engine* e, bool rows, bool from, int B, int T, int 
   RowHyper* d_hp_rows = nullptr;
   RowDraw* d_draw_rows = nullptr;
   if (draw_host && !rows) return fail(e, CZC_ERR_ARG, "generate: draw records belong to a rows call%s");
+  if (group_host && !(rows && from)) return fail(e, CZC_ERR_ARG, "generate: a group table belongs to a rows call with start rows%s");
   { int* flag; E_CHECK(ensure(e, "s_nonfinite", 32, (void**)&flag)); E_HIP(hipMemsetAsync(flag, 0, 32, e->st)); }
   E_CHECK(ensure(e, "g_inp", (size_t)B * T * 4, (void**)&d_inp));
   if (from) {  // every row brings its own start row: one upload, no broadcast
@@ -2141,6 +2216,10 @@ static int generate_impl(czc_engine* e, bool rows, bool from, int B, int T, int 
   if (memo_rows && d_draw_rows && !rc && ensure(e, "mr_draw_c", (size_t)B * sizeof(RowDraw), (void**)&mrp.draw_c)) rc = CZC_ERR_HIP;
   e->hp_rows = rc ? nullptr : d_hp_rows;  // (handed back with the image batch below)
   e->draw_rows = rc ? nullptr : d_draw_rows;
+  // czc_generate_rows_tied (its checks have run): the group table goes up once, behind the schedule
+  TiePlan tie;
+  const bool tied = group_host != nullptr && n_steps > 0;
+  if (tied && !rc) rc = tie_begin(e, B, T, seed_len, group_host, len_rows, out_cos != nullptr, &tie);
   if (memo_rows && any_idle && !rc && hipMemsetAsync(mrp.bcos, 0, (size_t)B * 4, e->st) != hipSuccess) rc = fail(e, CZC_ERR_HIP, "generate_rows_from: clearing the cosines%s");
   for (int s = 0; s < n_steps && !rc; ++s) {
     const int pos = positions_host[rows ? (size_t)s * B : (size_t)s];
@@ -2158,12 +2237,18 @@ static int generate_impl(czc_engine* e, bool rows, bool from, int B, int T, int 
     else if (memo) rc = memo_step(e, mp, s, d_inp, B, T, seed_len + pos, nm, pos == L - 1 ? 1 : 0, top_k, hp);
     else rc = step_device(e, d_inp, B, T, seed_len + pos, nm, pos == L - 1 ? 1 : 0, top_k, hp);
     if (rc) break;
+    // the tie: one launch on the full batch, behind whatever the step did (in place, compact batch and scatter, memo fill)
+    if (tied && launch_tie_rows(d_inp, B, T, d_sched + (size_t)s * B, tie.d_gor, tie.d_off, tie.d_rows, e->st)) { rc = fail(e, CZC_ERR_HIP, "%s", g_err); break; }
+    if (tied && snap_idx && out_cos) {  // a tied call returns the cosine of the caption as it stands, one score per group
+      rc = tie_score(e, tie, d_inp, B, T, len_rows != nullptr);
+      if (rc) break;
+    }
     if (snap_idx) {
       hipError_t h = hipSuccess;
       if (out_ids)
         h = hipMemcpyAsync(out_ids + (size_t)snap * B * T, d_inp, (size_t)B * T * 4, hipMemcpyDefault, e->st);
       if (out_cos && h == hipSuccess)  // memo: the full-batch cosines (a compacted step leaves B_act of them in s_bcos)
-        h = hipMemcpyAsync(out_cos + (size_t)snap * B, memo ? mp.bcos : memo_rows ? mrp.bcos : e->ws["s_bcos"].p, (size_t)B * 4,
+        h = hipMemcpyAsync(out_cos + (size_t)snap * B, tied ? tie.cos : memo ? mp.bcos : memo_rows ? mrp.bcos : e->ws["s_bcos"].p, (size_t)B * 4,
                            hipMemcpyDefault, e->st);
       if (h != hipSuccess) { snprintf(e->err, sizeof(e->err), "generate: snapshot copy -> %s", hipGetErrorString(h)); rc = CZC_ERR_HIP; }
       ++snap;
@@ -2206,7 +2291,7 @@ int czc_generate_rows_from(czc_engine* e, int R, int T, int L, int seed_len, con
 static int rows_len_impl(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
                          const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
                          const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp, int32_t* out_ids, float* out_cos,
-                         const czc_hyper* hp_rows_host, const czc_draw* draw_host = nullptr) {
+                         const czc_hyper* hp_rows_host, const czc_draw* draw_host = nullptr, const int32_t* group_host = nullptr) {
   if (!e || !init_rows_host || !len_of_row_host || !positions_host || !hp || R <= 0 || n_steps < 0 || snapshot_every <= 0)
     return CZC_ERR_ARG;
   e->err[0] = 0;
@@ -2232,7 +2317,7 @@ static int rows_len_impl(czc_engine* e, int R, int T, int seed_len, const int32_
   }
   // rows of one length that fill the stride: czc_generate_rows_from itself, bit for bit
   return generate_impl(e, true, true, R, T, L_max, seed_len, init_rows_host, image_of_row_host, top_k, n_steps, positions_host, n_mask_host,
-                       snapshot_every, hp, out_ids, out_cos, uniform ? nullptr : len_of_row_host, hp_rows_host, draw_host);
+                       snapshot_every, hp, out_ids, out_cos, uniform ? nullptr : len_of_row_host, hp_rows_host, draw_host, group_host);
 }
 
 int czc_generate_rows_len(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
@@ -2246,7 +2331,7 @@ int czc_generate_rows_len(czc_engine* e, int R, int T, int seed_len, const int32
 static int rows_hp_impl(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
                         const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
                         const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp_of_row_host, int32_t* out_ids, float* out_cos,
-                        const czc_draw* draw_host) {
+                        const czc_draw* draw_host, const int32_t* group_host = nullptr) {
   if (!e || !init_rows_host || !positions_host || !hp_of_row_host || R <= 0 || n_steps < 0 || snapshot_every <= 0) return CZC_ERR_ARG;
   e->err[0] = 0;
   if (R > CZC_MAX_ROWS) return fail(e, CZC_ERR_ARG, "generate_rows_hp: R > CZC_MAX_ROWS%s");
@@ -2274,9 +2359,9 @@ static int rows_hp_impl(czc_engine* e, int R, int T, int seed_len, const int32_t
   const czc_hyper* rows_hp = uniform ? nullptr : hp_of_row_host;
   if (len_of_row_host)
     return rows_len_impl(e, R, T, seed_len, init_rows_host, len_of_row_host, image_of_row_host, top_k, n_steps, positions_host, n_mask_host,
-                         snapshot_every, &hp_of_row_host[0], out_ids, out_cos, rows_hp, draw_host);
+                         snapshot_every, &hp_of_row_host[0], out_ids, out_cos, rows_hp, draw_host, group_host);
   return generate_impl(e, true, true, R, T, T - seed_len - 1, seed_len, init_rows_host, image_of_row_host, top_k, n_steps, positions_host,
-                       n_mask_host, snapshot_every, &hp_of_row_host[0], out_ids, out_cos, nullptr, rows_hp, draw_host);
+                       n_mask_host, snapshot_every, &hp_of_row_host[0], out_ids, out_cos, nullptr, rows_hp, draw_host, group_host);
 }
 
 int czc_generate_rows_hp(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
@@ -2286,10 +2371,10 @@ int czc_generate_rows_hp(czc_engine* e, int R, int T, int seed_len, const int32_
                       snapshot_every, hp_of_row_host, out_ids, out_cos, nullptr);
 }
 
-int czc_generate_rows_draw(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
-                           const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
-                           const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp_of_row_host,
-                           const czc_draw* draw_of_row_host, int32_t* out_ids, float* out_cos) {
+static int rows_draw_impl(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
+                          const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
+                          const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp_of_row_host,
+                          const czc_draw* draw_of_row_host, int32_t* out_ids, float* out_cos, const int32_t* group_host) {
   if (!e || R <= 0 || n_steps < 0) return CZC_ERR_ARG;
   e->err[0] = 0;
   if (R > CZC_MAX_ROWS) return fail(e, CZC_ERR_ARG, "generate_rows_draw: R > CZC_MAX_ROWS%s");
@@ -2303,7 +2388,113 @@ int czc_generate_rows_draw(czc_engine* e, int R, int T, int seed_len, const int3
   }
   // no row draws: czc_generate_rows_hp itself, bit for bit
   return rows_hp_impl(e, R, T, seed_len, init_rows_host, len_of_row_host, image_of_row_host, top_k, n_steps, positions_host, n_mask_host,
-                      snapshot_every, hp_of_row_host, out_ids, out_cos, any ? draw_of_row_host : nullptr);
+                      snapshot_every, hp_of_row_host, out_ids, out_cos, any ? draw_of_row_host : nullptr, group_host);
+}
+
+int czc_generate_rows_draw(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
+                           const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
+                           const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp_of_row_host,
+                           const czc_draw* draw_of_row_host, int32_t* out_ids, float* out_cos) {
+  return rows_draw_impl(e, R, T, seed_len, init_rows_host, len_of_row_host, image_of_row_host, top_k, n_steps, positions_host, n_mask_host,
+                        snapshot_every, hp_of_row_host, draw_of_row_host, out_ids, out_cos, nullptr);
+}
+
+// czc_generate_rows_draw with rows tied into groups that hold one sentence: the group checks, then the draw call's own
+int czc_generate_rows_tied(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
+                           const int32_t* image_of_row_host, const int32_t* group_of_row_host, int top_k, int n_steps,
+                           const int32_t* positions_host, const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp_of_row_host,
+                           const czc_draw* draw_of_row_host, int32_t* out_ids, float* out_cos) {
+  if (!group_of_row_host)
+    return rows_draw_impl(e, R, T, seed_len, init_rows_host, len_of_row_host, image_of_row_host, top_k, n_steps, positions_host, n_mask_host,
+                          snapshot_every, hp_of_row_host, draw_of_row_host, out_ids, out_cos, nullptr);
+  if (!e || !init_rows_host || !positions_host || R <= 0 || n_steps < 0) return CZC_ERR_ARG;
+  e->err[0] = 0;
+  if (R > CZC_MAX_ROWS || seed_len < 0 || T <= 0 || T > CZC_MAX_BERT_LEN) return fail(e, CZC_ERR_ARG, "generate_rows_tied: R > CZC_MAX_ROWS, seed_len < 0 or T outside [1, CZC_MAX_BERT_LEN]%s");
+  for (int s = 0; s < n_steps && n_mask_host; ++s)
+    if (n_mask_host[s] != 1) return fail(e, CZC_ERR_ARG, "generate_rows_tied: every step needs n_mask = 1 (the n_mask = 0 re-use of a forward across a tie is not defined; span order is refused)%s");
+  std::vector<int32_t> lead(R, -1);  // by group id: its lowest-numbered row
+  for (int r = 0; r < R; ++r) {
+    const int g = group_of_row_host[r];
+    if (g < 0 || g >= R) return fail(e, CZC_ERR_ARG, "generate_rows_tied: a group id outside [0, R)%s");
+    if (lead[g] < 0) { lead[g] = r; continue; }
+    const int l = lead[g];
+    if (len_of_row_host && len_of_row_host[r] != len_of_row_host[l])
+      return fail(e, CZC_ERR_ARG, "generate_rows_tied: the rows of a group must share one length%s");
+    if (image_of_row_host ? image_of_row_host[r] != image_of_row_host[l] : true)  // (image_of_row = NULL: row r has image r)
+      return fail(e, CZC_ERR_ARG, "generate_rows_tied: the rows of a group must share one image%s");
+    if (memcmp(init_rows_host + (size_t)r * T, init_rows_host + (size_t)l * T, (size_t)T * 4) != 0)
+      return fail(e, CZC_ERR_ARG, "generate_rows_tied: the rows of a group must bring the same start row%s");
+  }
+  std::vector<int32_t> seen((size_t)R * T, -1);  // (group, position) -> the last step a member ran there
+  for (int s = 0; s < n_steps; ++s)
+    for (int r = 0; r < R; ++r) {
+      const int p = positions_host[(size_t)s * R + r];
+      if (p < 0 || p >= T) continue;  // idle; anything else out of range is refused by the call's own checks
+      int32_t& was = seen[(size_t)group_of_row_host[r] * T + p];
+      if (was == s) return fail(e, CZC_ERR_ARG, "generate_rows_tied: two rows of a group run at the same position in one step%s");
+      was = s;
+    }
+  return rows_draw_impl(e, R, T, seed_len, init_rows_host, len_of_row_host, image_of_row_host, top_k, n_steps, positions_host, n_mask_host,
+                        snapshot_every, hp_of_row_host, draw_of_row_host, out_ids, out_cos, group_of_row_host);
+}
+
+int czc_score_rows(czc_engine* e, const int32_t* rows, int R, int T, int seed_len, const int32_t* len_of_row_host,
+                   const int32_t* image_of_row_host, float* out_cos) {
+  if (!e || !rows || !out_cos || R <= 0) return CZC_ERR_ARG;
+  E_HIP(hipSetDevice(e->dev));
+  e->err[0] = 0;
+  if (R > CZC_MAX_ROWS || seed_len < 0 || T <= 0 || T > CZC_MAX_BERT_LEN) return fail(e, CZC_ERR_ARG, "score_rows: R > CZC_MAX_ROWS, seed_len < 0 or T outside [1, CZC_MAX_BERT_LEN]%s");
+  if (!e->finalized) return fail(e, CZC_ERR_STATE, "weights not finalized%s");
+  if (!e->has_bridge) return fail(e, CZC_ERR_STATE, "bridge tables not set%s");
+  if (!e->d_img_n || e->img_B <= 0) return fail(e, CZC_ERR_STATE, "image embeds not set%s");
+  if (!image_of_row_host && e->img_B != R) return fail(e, CZC_ERR_ARG, "score_rows: image_of_row = NULL needs R equal to the resident image batch%s");
+  for (int r = 0; r < R; ++r) {
+    if (image_of_row_host && (image_of_row_host[r] < 0 || image_of_row_host[r] >= e->img_B))
+      return fail(e, CZC_ERR_ARG, "score_rows: image_of_row outside the resident image batch%s");
+    if (len_of_row_host && (len_of_row_host[r] < 1 || len_of_row_host[r] > T - seed_len - 1))
+      return fail(e, CZC_ERR_ARG, "score_rows: len_of_row outside [1, T - seed_len - 1]%s");
+  }
+  const size_t n = (size_t)R * T;
+  std::vector<int32_t> host;
+  const int32_t* h = rows;
+  const bool on_device = is_device_ptr(rows);
+  if (on_device) {  // the ids are checked on the host either way: they index the bridge tables
+    host.resize(n);
+    E_HIP(hipMemcpyAsync(host.data(), rows, n * 4, hipMemcpyDeviceToHost, e->st));
+    E_HIP(hipStreamSynchronize(e->st));
+    h = host.data();
+  }
+  for (int r = 0; r < R; ++r) {
+    const int Tr = len_of_row_host ? seed_len + len_of_row_host[r] + 1 : T;
+    for (int t = 0; t < Tr; ++t)
+      if (h[(size_t)r * T + t] < 0 || h[(size_t)r * T + t] >= e->cfg.bert_vocab)
+        return fail(e, CZC_ERR_ARG, "score_rows: a row holds an id outside the BERT vocabulary%s");
+  }
+  const int D = e->cfg.clip_proj;
+  int *d_rows, *d_len = nullptr, *d_ior; float *img_r = e->d_img_n, *d_cos;
+  { int* flag; E_CHECK(ensure(e, "s_nonfinite", 32, (void**)&flag)); E_HIP(hipMemsetAsync(flag, 0, 32, e->st)); }
+  E_CHECK(ensure(e, "sc_rows", n * 4, (void**)&d_rows));
+  E_CHECK(ensure(e, "sc_cos", (size_t)R * 4, (void**)&d_cos));
+  E_HIP(hipMemcpyAsync(d_rows, rows, n * 4, hipMemcpyDefault, e->st));
+  std::vector<int32_t> len_t;
+  if (len_of_row_host) {
+    len_t.resize(R);
+    for (int r = 0; r < R; ++r) len_t[r] = seed_len + len_of_row_host[r] + 1;
+    E_CHECK(ensure(e, "sc_len", (size_t)R * 4, (void**)&d_len));
+    E_HIP(hipMemcpyAsync(d_len, len_t.data(), (size_t)R * 4, hipMemcpyHostToDevice, e->st));
+  }
+  if (image_of_row_host) {
+    E_CHECK(ensure(e, "sc_ior", (size_t)R * 4, (void**)&d_ior));
+    E_CHECK(ensure(e, "sc_img_r", (size_t)R * D * 4, (void**)&img_r));
+    E_HIP(hipMemcpyAsync(d_ior, image_of_row_host, (size_t)R * 4, hipMemcpyHostToDevice, e->st));
+    E_CHECK(launch_gather_rows_f32(e->d_img_n, d_ior, R, D, img_r, e->st));
+  }
+  E_CHECK(score_rows_device(e, d_rows, R, T, d_len, img_r, d_cos));  // (its size read waits for the pageable uploads above)
+  E_HIP(hipMemcpyAsync(out_cos, d_cos, (size_t)R * 4, hipMemcpyDefault, e->st));
+  E_HIP(hipMemcpyAsync(e->h_totals + 9, e->ws["s_nonfinite"].p, 4, hipMemcpyDeviceToHost, e->st));
+  E_HIP(hipStreamSynchronize(e->st));
+  if (e->h_totals[9]) return fail(e, CZC_ERR_OVERFLOW, "non-finite CLIP cosine: an fp16 quantity overflowed in a tower (fp16 residual rows: set option resid16 = 0 on the bf16 engine, refine_rows16 = 0 on the refine engine; fp16 operands: use CZC_PREC_SPLIT)%s");
+  return CZC_OK;
 }
 
 int czc_set_control_callback(czc_engine* e, czc_control_fn fn, void* user) {

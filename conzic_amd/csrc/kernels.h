@@ -125,6 +125,11 @@ int launch_mask_positions(int* inp, int B, int T, int gen_idx, int n_mask, int m
 // inp[b, gen[b] .. gen[b]+n_mask) = mask_id
 int launch_mask_positions_rows(int* inp, int B, int T, const int* gen, int n_mask, int mask_id, hipStream_t st);
 int launch_broadcast_rows_i32(const int* row, int T, int B, int* dst, hipStream_t st);
+// dst[m] = src[idx[m]] for rows of W 4-byte words, any W
+int launch_gather_rows_w32(const void* src, const int* idx, int M, int W, void* dst, hipStream_t st);
+// czc_generate_rows_tied: for every row r with col[r] >= 0, inp[m][col[r]] = inp[r][col[r]] for the other members m of r's group
+// (grp_of_row [R]; members of group g: grp_rows[grp_off[g] .. grp_off[g + 1]); all device)
+int launch_tie_rows(int* inp, int R, int T, const int* col, const int* grp_of_row, const int* grp_off, const int* grp_rows, hipStream_t st);
 
 // ---- ragged.hip (czc_generate_rows_len: BERT on packed ragged rows) -------------------------------------------------------
 // Sequence b: row_len[b] tokens, packed rows row_off[b] .. (row_off [n + 1], the exclusive scan of row_len [n]; device).
@@ -334,6 +339,8 @@ struct CombineArgs {
 };
 // text_feat == null: clip_ref already holds the cosines
 int launch_combine(const CombineArgs& a, hipStream_t st);
+// the cosine kernel of launch_combine on its own: cos_out[b * K + k] = normalised text_feat[b * K + k] . img_n[b]
+int launch_cosine(const float* text_feat, const float* img_n, int B, int K, int D, float* cos_out, int* nonfinite, hipStream_t st);
 // screen-then-refine engine (combine.hip): choose the candidates to re-encode / cosines of the re-encoded rows
 // gate_h > 0: margin gate of czc_generate (combine.hip); gated[0] += images that passed it, gated[1] += images
 int launch_refine_select(const float* clip_score, const float* final_score, int B, int K, float theta, int m_samples, float gate_h,

@@ -715,4 +715,44 @@ int launch_broadcast_rows_i32(const int* row, int T_, int B, int* dst, hipStream
   return 0;
 }
 
+// czc_generate_rows_tied: the rows of a group hold one sentence.  Behind a step, the thread of row r that ran at column c
+// (col[r], this step's slice of the schedule; CZC_POS_IDLE = sat out) copies the id it now holds there into the same column of
+// every other member of its group (CSR: members of group g at grp_rows[grp_off[g] .. grp_off[g + 1])).  The host has checked
+// that the members of a group that run at a step do so at distinct columns, so thread r reads inp[r][c_r] and the only writes
+// into row r go to other columns; two threads never write one word.  Plain loads and stores.
+__global__ void tie_rows_kernel(int* inp, int R, int T_, const int* col, const int* grp_of_row, const int* grp_off, const int* grp_rows) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= R) return;
+  const int c = col[r];
+  if (c < 0 || c >= T_) return;
+  const int g = grp_of_row[r];
+  const int v = inp[(long)r * T_ + c];
+  for (int i = grp_off[g]; i < grp_off[g + 1]; ++i) {
+    const int m = grp_rows[i];
+    if (m != r && m >= 0 && m < R) inp[(long)m * T_ + c] = v;
+  }
+}
+
+// rows of W 4-byte words, any W (the float4 / uint4 gathers above need whole vectors): dst[m] = src[idx[m]], one thread per word
+__global__ void gather_rows_w32_kernel(const unsigned* src, const int* idx, int M, int W, unsigned* dst) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)M * W) return;
+  const int m = (int)(i / W), c = (int)(i % W);
+  dst[i] = src[(long)idx[m] * W + c];
+}
+
+int launch_gather_rows_w32(const void* src, const int* idx, int M, int W, void* dst, hipStream_t st) {
+  if (M <= 0 || W <= 0) return 0;
+  hipLaunchKernelGGL(gather_rows_w32_kernel, dim3((unsigned)cdiv((long)M * W, 256)), dim3(256), 0, st, (const unsigned*)src, idx, M, W, (unsigned*)dst);
+  CZC_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int launch_tie_rows(int* inp, int R, int T_, const int* col, const int* grp_of_row, const int* grp_off, const int* grp_rows, hipStream_t st) {
+  if (R <= 0) return 0;
+  hipLaunchKernelGGL(tie_rows_kernel, dim3(cdiv(R, 256)), dim3(256), 0, st, inp, R, T_, col, grp_of_row, grp_off, grp_rows);
+  CZC_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
 }  // namespace czc

@@ -69,6 +69,14 @@ def get_args(argv=None):
                    help="one image under several control signals in ONE engine call (one row per signal, each with its own "
                         "hyper-parameters and the visiting order its own run would draw); combines with --sentence_lens and "
                         "--batch_samples; --run_type / --control_type / --sentiment_type are ignored while this is set")
+    p.add_argument("--block_width", type=int, default=1, metavar="W",
+                   help="block-synchronous sweeps: W tied rows per caption polish W positions of it per step, each from the same "
+                        "current sentence, and all winners are written back together -- ceil(sentence_len / W) serial steps per "
+                        "sweep instead of sentence_len (1 = off, the serial sweep; 0 = sentence_len, all positions at once); "
+                        "--order sequential or shuffle; combines with --batch_samples and --sample_tau")
+    p.add_argument("--block_layout", default="interleaved", choices=["interleaved", "contiguous"],
+                   help="--block_width under --order sequential: a block holds every nb-th position (interleaved: neighbouring "
+                        "words never update together) or W neighbouring positions (contiguous)")
     p.add_argument("--caption", action="append", default=None, metavar="TEMPLATE",
                    help="--run_type infill (repeatable): a caption with blanks, e.g. \"a _ dog on a _\"; only the blanks are "
                         "polished (num_iterations sweeps, --order sequential or shuffle over each caption's blanks), the given "
@@ -93,6 +101,18 @@ def get_args(argv=None):
         p.error("--sample_tau must be finite and >= 0")
     if a.sample_tau and a.run_type == "retrieve":
         p.error("--sample_tau does not apply to --run_type retrieve")
+    if a.block_width < 0:
+        p.error("--block_width must be >= 0 (0 = the sentence length, 1 = off)")
+    if a.block_width != 1:
+        if a.run_type in ("infill", "retrieve"):
+            p.error(f"--block_width does not combine with --run_type {a.run_type} (block-synchronous sweeps polish whole captions "
+                    "of one length from the prompt)")
+        if a.sentence_lens is not None:
+            p.error("--block_width does not combine with --sentence_lens")
+        if a.signals is not None:
+            p.error("--block_width does not combine with --signals")
+        if a.run_type == "caption" and a.order not in ("sequential", "shuffle"):
+            p.error("--block_width cuts a sweep's visiting order into blocks: --order sequential or shuffle")
     if a.run_type == "retrieve":
         from conzic_amd import native
         files = a.index_matrix_path is not None or a.mapping_dict_path is not None
@@ -239,6 +259,23 @@ def main(argv=None):
         for i in range(args.batch_size):
             finals[i].append(last[i])
 
+    if args.block_width != 1:
+        # block-synchronous sweeps: the block_width tied rows of every caption (with --batch_samples: of all samples) in one call
+        from conzic_amd.runtime import caption_blocks
+        kw = dict(prompt=args.prompt, batch_size=args.batch_size, max_len=args.sentence_len, top_k=args.candidate_k,
+                  temperature=args.lm_temperature, max_iter=args.num_iterations, alpha=args.alpha, beta=args.beta,
+                  generate_order=args.order, gamma=args.gamma, ctl_type=args.control_type,
+                  style_type=args.sentiment_type, pos_type=args.pos_type, sample_tau=args.sample_tau, sample_seed=args.seed)
+        for sample_id in ([None] if args.batch_samples else range(args.samples_num)):
+            outs = caption_blocks(args.block_width, args.block_layout, args.samples_num if sample_id is None else 1, args.run_type,
+                                  img_name, lm_model, clip, lm_tokenizer, image_instance, token_mask, logger,
+                                  sample0=sample_id or 0, **kw)
+            for generate_texts, _ in outs:
+                keep(generate_texts)
+        if args.samples_num > 1:
+            log_distinct(logger, img_name, finals)
+        logger.info("total %.2fs" % (time.time() - t0))
+        return finals
     if args.batch_samples or args.sample_tau:
         # one engine call for all samples, or -- the serial loop under --sample_tau -- one per sample with that sample's seeds
         from conzic_amd.runtime import caption_samples

@@ -549,6 +549,75 @@ class Engine:
         self._ck(rc, "czc_generate_rows_draw")
         return ids, cos
 
+    def generate_rows_tied(self, init_rows, lens, seed_len: int, top_k: int, positions, hypers: Sequence[native.Hyper],
+                           draws: Optional[Sequence[native.Draw]], groups: Optional[Sequence[int]],
+                           image_of_row: Optional[Sequence[int]] = None, snapshot_every: Optional[int] = None,
+                           want_cos: bool = True):
+        """czc_generate_rows_tied: generate_rows_draw with rows tied into groups (`groups` int [R], values in [0, R), or None:
+        generate_rows_draw itself).  The rows of a group hold one sentence: after every step each row's winner is written
+        into its siblings, so W rows polish W positions of one caption per step.  Every step masks one position.  Returns
+        (ids int32 [S,R,T], cos fp32 [S,R]) per snapshot; with groups, cos is the score_rows cosine of the merged caption."""
+        init = np.ascontiguousarray(init_rows, dtype=np.int32)
+        pos = np.ascontiguousarray(positions, dtype=np.int32)
+        if pos.ndim != 2 or pos.shape[1] < 1:
+            raise ValueError("generate_rows_tied: positions must be [n_steps, R]")
+        n_steps, R = pos.shape
+        if init.ndim != 2 or init.shape[0] != R or init.shape[1] < 1:
+            raise ValueError(f"generate_rows_tied: init_rows must be [R, T] with R = {R}, got {init.shape}")
+        T = init.shape[1]
+        ln = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32).reshape(-1)
+        if ln is not None and ln.size != R:
+            raise ValueError(f"generate_rows_tied: lens has {ln.size} entries for {R} rows")
+        hp = hyper_array(hypers)
+        if len(hp) != R:
+            raise ValueError(f"generate_rows_tied: hypers has {len(hp)} entries for {R} rows")
+        dr = None if draws is None else draw_array(draws)
+        if dr is not None and len(dr) != R:
+            raise ValueError(f"generate_rows_tied: draws has {len(dr)} entries for {R} rows")
+        gr = None if groups is None else np.ascontiguousarray(groups, dtype=np.int32).reshape(-1)
+        if gr is not None and gr.size != R:
+            raise ValueError(f"generate_rows_tied: groups has {gr.size} entries for {R} rows")
+        ior = None if image_of_row is None else np.ascontiguousarray(image_of_row, dtype=np.int32).reshape(-1)
+        if ior is not None and ior.size != R:
+            raise ValueError(f"generate_rows_tied: image_of_row has {ior.size} entries for {R} rows")
+        every = snapshot_every or max(int(ln.max()) if ln is not None else T - seed_len - 1, 1)
+        S = n_steps // every
+        ids = np.empty((S, R, T), dtype=np.int32)
+        cos = np.empty((S, R), dtype=np.float32) if want_cos else None
+        rc = self.lib.czc_generate_rows_tied(self.h, R, T, seed_len, init.ctypes.data, None if ln is None else ln.ctypes.data,
+                                             None if ior is None else ior.ctypes.data, None if gr is None else gr.ctypes.data,
+                                             top_k, n_steps, pos.ctypes.data, None, every, hp, dr, ids.ctypes.data,
+                                             None if cos is None else cos.ctypes.data)
+        if rc:
+            self._raise_scorer_error()
+        self._ck(rc, "czc_generate_rows_tied")
+        return ids, cos
+
+    def score_rows(self, rows, seed_len: int, lens: Optional[Sequence[int]] = None,
+                   image_of_row: Optional[Sequence[int]] = None) -> np.ndarray:
+        """czc_score_rows: the CLIP cosine fp32 [R] of BERT-id `rows` int [R, T] (decoded as the step decodes them; row r stops
+        at seed_len + lens[r] + 1 tokens) with resident image image_of_row[r] (None: row r = image r), all on the device."""
+        if hasattr(rows, "data_ptr"):   # a contiguous int32 torch tensor, on the device or the host: scored where it lies
+            if str(rows.dtype) != "torch.int32" or not rows.is_contiguous():
+                raise ValueError("score_rows: a tensor must be contiguous int32")
+            r, ptr = rows, rows.data_ptr()
+        else:
+            r = np.ascontiguousarray(rows, dtype=np.int32)
+            ptr = r.ctypes.data
+        if r.ndim != 2 or r.shape[0] < 1 or r.shape[1] < 1:
+            raise ValueError(f"score_rows: rows must be [R, T], got {tuple(r.shape)}")
+        R, T = int(r.shape[0]), int(r.shape[1])
+        ln = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32).reshape(-1)
+        if ln is not None and ln.size != R:
+            raise ValueError(f"score_rows: lens has {ln.size} entries for {R} rows")
+        ior = None if image_of_row is None else np.ascontiguousarray(image_of_row, dtype=np.int32).reshape(-1)
+        if ior is not None and ior.size != R:
+            raise ValueError(f"score_rows: image_of_row has {ior.size} entries for {R} rows")
+        out = np.empty((R,), dtype=np.float32)
+        self._ck(self.lib.czc_score_rows(self.h, ptr, R, T, seed_len, None if ln is None else ln.ctypes.data,
+                                         None if ior is None else ior.ctypes.data, out.ctypes.data), "czc_score_rows")
+        return out
+
     def similarity(self, image_embeds, text_embeds, K: int):
         """clip/clip.py:86-98: (softmax_K(cos * exp(logit_scale)), cos), both [B, K], from un-normalised embeddings."""
         ie = np.ascontiguousarray(image_embeds, np.float32)
@@ -901,6 +970,86 @@ class EngineGroup:
                                                                           n_mask=n_mask, snapshot_every=every, want_cos=want_cos))
                           for e, (lo, hi) in zip(self.engines, parts)])
         return np.concatenate([o[0] for o in outs], axis=1), (np.concatenate([o[1] for o in outs], axis=1) if want_cos else None)
+
+    def tied_parts(self, groups):
+        """Row index arrays, one per engine used: the rows dealt over the streams on group boundaries only.  Groups go, in
+        the order of their first rows, to the current part until it holds its share of the rows; a group is never cut."""
+        gr = np.asarray(groups, dtype=np.int64).reshape(-1)
+        R = gr.size
+        n = max(1, min(len(self.engines), R // max(self.min_images, 1)))
+        order, members = [], {}
+        for r, g in enumerate(gr.tolist()):
+            if g not in members:
+                members[g] = []
+                order.append(g)
+            members[g].append(r)
+        parts, cur, done = [], [], 0
+        for g in order:
+            cur += members[g]
+            if len(parts) < n - 1 and done + len(cur) >= (len(parts) + 1) * R / n:
+                parts.append(cur)
+                done += len(cur)
+                cur = []
+        if cur:
+            parts.append(cur)
+        return [np.array(sorted(p), dtype=np.int64) for p in parts]
+
+    def generate_rows_tied(self, init_rows, lens, seed_len: int, top_k: int, positions, hypers, draws, groups, image_of_row=None,
+                           snapshot_every=None, want_cos: bool = True):
+        """Engine.generate_rows_tied with the rows split over the streams ON GROUP BOUNDARIES ONLY (tied_parts; groups None:
+        generate_rows_draw's contiguous split).  A member gets the embeds of the images its rows name and its rows' image indices
+        into them, so the rows of a group still share one image."""
+        if groups is None:
+            return self.generate_rows_draw(init_rows, lens, seed_len, top_k, positions, hypers, draws, image_of_row=image_of_row,
+                                           snapshot_every=snapshot_every, want_cos=want_cos)
+        pos = np.ascontiguousarray(positions, dtype=np.int32)
+        init = np.ascontiguousarray(init_rows, dtype=np.int32)
+        ln = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32).reshape(-1)
+        if pos.ndim != 2:
+            raise ValueError("generate_rows_tied: positions must be [n_steps, R]")
+        R = pos.shape[1]
+        if init.ndim != 2 or init.shape[0] != R:
+            raise ValueError(f"generate_rows_tied: init_rows must be [R, T] with R = {R}, got {init.shape}")
+        if ln is not None and ln.size != R:
+            raise ValueError(f"generate_rows_tied: lens has {ln.size} entries for {R} rows")
+        hps = list(hypers)
+        if len(hps) != R:
+            raise ValueError(f"generate_rows_tied: hypers has {len(hps)} entries for {R} rows")
+        drs = None if draws is None else list(draws)
+        if drs is not None and len(drs) != R:
+            raise ValueError(f"generate_rows_tied: draws has {len(drs)} entries for {R} rows")
+        gr = np.asarray(groups, dtype=np.int64).reshape(-1)
+        if gr.size != R:
+            raise ValueError(f"generate_rows_tied: groups has {gr.size} entries for {R} rows")
+        if R and (gr.min() < 0 or gr.max() >= R):
+            raise NativeError("EngineGroup.generate_rows_tied: a group id outside [0, R)", code=native.ERR_ARG)
+        embeds = self._full_embeds if self._full_embeds is not None else self._encoded
+        if embeds is None:
+            raise NativeError("EngineGroup.generate_rows_tied: encode_images / set_image_embeds first")
+        ior = np.arange(R) if image_of_row is None else np.asarray(image_of_row, dtype=np.int64).reshape(-1)
+        if ior.size != R or (R and (ior.min() < 0 or ior.max() >= embeds.shape[0])):
+            raise NativeError("EngineGroup.generate_rows_tied: image_of_row outside the resident image batch", code=native.ERR_ARG)
+        every = snapshot_every or max(int(ln.max()) if ln is not None else init.shape[1] - seed_len - 1, 1)
+        parts = self.tied_parts(gr)
+        jobs = []
+        for e, rows in zip(self.engines, parts):
+            imgs, img_c = np.unique(ior[rows], return_inverse=True)
+            _, grp_c = np.unique(gr[rows], return_inverse=True)   # the part's own group ids, in [0, its row count)
+            e.set_image_embeds(embeds[imgs])
+            jobs.append(lambda e=e, rows=rows, img_c=img_c, grp_c=grp_c: e.generate_rows_tied(
+                init[rows], None if ln is None else ln[rows], seed_len, top_k, np.ascontiguousarray(pos[:, rows]),
+                [hps[r] for r in rows], None if drs is None else [drs[r] for r in rows], grp_c.astype(np.int32),
+                image_of_row=img_c.astype(np.int32), snapshot_every=every, want_cos=want_cos))
+        self._full_embeds, self._resident = embeds, None
+        outs = self._run(jobs)
+        S = outs[0][0].shape[0]
+        ids = np.empty((S, R, init.shape[1]), dtype=np.int32)
+        cos = np.empty((S, R), dtype=np.float32) if want_cos else None
+        for rows, (i, c) in zip(parts, outs):
+            ids[:, rows] = i
+            if want_cos:
+                cos[:, rows] = c
+        return ids, cos
 
     # ---- the engine calls that apply to every member ----
     def set_option(self, name, value):

@@ -123,6 +123,8 @@ SIGNATURES = {
     "czc_generate_rows_len": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _I, C.POINTER(Hyper), _P, _P]),
     "czc_generate_rows_hp": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _I, C.POINTER(Hyper), _P, _P]),
     "czc_generate_rows_draw": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _I, C.POINTER(Hyper), C.POINTER(Draw), _P, _P]),
+    "czc_generate_rows_tied": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _I, C.POINTER(Hyper), C.POINTER(Draw), _P, _P]),
+    "czc_score_rows": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
     "czc_set_option": (_I, [_P, C.c_char_p, _I]),
     "czc_get_option": (_I, [_P, C.c_char_p, C.POINTER(_I)]),
     "czc_profile_enable": (_I, [_P, _I]),

@@ -156,6 +156,60 @@ def lengths_batches(args, run_type, all_batches, own_lo, own_hi, rank, world, im
                 write_results(result_dir(at_len, run_type, sample_id), all_results)
 
 
+def blocks_batches(args, run_type, all_batches, own_lo, own_hi, rank, world, img_dir, lm_model, clip, lm_tokenizer, token_mask,
+                   logger):
+    """--block_width: every batch polishes a sample's captions in block-synchronous sweeps, block_width tied rows per caption in
+    one engine call (runtime.caption_blocks), or with --batch_samples those of all its samples; the images are encoded once per
+    batch.  The orders are drawn as that loop draws them -- samples outside and batches inside (with --batch_samples: batch by
+    batch) -- and a rank draws those of the batches it does not own as well.  The files are written sample for sample as
+    without the flag."""
+    from PIL import Image
+    from clip.clip import ImageEmbeds
+    from conzic_amd.runtime import advance_order_rng, caption_blocks, caption_order
+    S = args.samples_num
+    per_call = S if args.batch_samples else 1
+    order, _ = caption_order(args.run_type, args.order, args.control_type, args.num_iterations, args.sentence_len)
+    results = [[None] * (args.num_iterations + 1) for _ in range(S)]
+    embed_cache = {}
+    for sample_id in ([None] if args.batch_samples else range(S)):
+        if sample_id is not None:
+            logger.info(f"Sample {sample_id + 1}: ")
+        for batch_idx, name_batch in enumerate(all_batches):
+            if not (own_lo <= batch_idx < own_hi):
+                for _ in range(per_call):
+                    advance_order_rng(order, args.sentence_len, args.num_iterations)
+                continue
+            logger.info(f"The {batch_idx + 1}-th batch:")
+            if batch_idx in embed_cache:
+                imgs = ImageEmbeds(embed_cache[batch_idx])
+            else:
+                imgs = [Image.open(os.path.join(img_dir, n)).convert("RGB") for n in name_batch]
+            outs = caption_blocks(args.block_width, args.block_layout, per_call, args.run_type, name_batch, lm_model, clip,
+                                  lm_tokenizer, imgs, token_mask, logger, prompt=args.prompt, batch_size=args.batch_size,
+                                  max_len=args.sentence_len, top_k=args.candidate_k, temperature=args.lm_temperature,
+                                  max_iter=args.num_iterations, alpha=args.alpha, beta=args.beta, generate_order=args.order,
+                                  gamma=args.gamma, ctl_type=args.control_type, style_type=args.sentiment_type,
+                                  pos_type=args.pos_type, sample_tau=args.sample_tau, sample_seed=args.seed, sample0=sample_id or 0)
+            if batch_idx not in embed_cache:
+                embed_cache[batch_idx] = clip.last_image_embeds()
+            for s_, (gen_texts, _) in enumerate(outs):
+                sid = s_ if sample_id is None else sample_id
+                results[sid] = merge_results(results[sid], gen_texts, name_batch)
+    for sample_id in range(S):
+        all_results = results[sample_id]
+        if world > 1:
+            import torch.distributed as tdist
+            parts = [None] * world
+            tdist.all_gather_object(parts, all_results)
+            all_results = [None] * (args.num_iterations + 1)
+            for part in parts:  # rank order == batch order
+                for it, d in enumerate(part):
+                    if d is not None:
+                        all_results[it] = {**(all_results[it] or {}), **d}
+        if rank == 0:
+            write_results(result_dir(args, run_type, sample_id), all_results)
+
+
 def signals_batches(args, all_batches, own_lo, own_hi, rank, world, img_dir, lm_model, clip, lm_tokenizer, token_mask, logger):
     """--signals: every batch polishes all control signals (and with --sentence_lens all lengths) of a sample in one engine call
     (runtime.caption_signals), or with --batch_samples those of all its samples; the images are encoded once per batch.  The
@@ -378,6 +432,10 @@ def main(argv=None):
     if args.sentence_lens:
         lengths_batches(args, run_type, all_batches, own_lo, own_hi, rank, world, img_dir, lm_model, clip, lm_tokenizer, token_mask,
                         logger)
+        return
+    if args.block_width != 1:
+        blocks_batches(args, run_type, all_batches, own_lo, own_hi, rank, world, img_dir, lm_model, clip, lm_tokenizer, token_mask,
+                       logger)
         return
     if args.batch_samples:
         batched_samples(args, run_type, all_batches, own_lo, own_hi, rank, world, img_dir, lm_model, clip, lm_tokenizer,

@@ -748,6 +748,138 @@ def caption_samples(samples_num: int, run_type: str, img_name, model, clip, toke
     return outs
 
 
+def run_generation_blocks(order: str, width: int, layout: str, samples_num: int, img_name, model, clip, tokenizer, image_instance,
+                          token_mask, prompt, logger, max_len, top_k, temperature, alpha, beta, max_iters, batch_size,
+                          verbose=True, gamma=None, ctl_signal="positive", print_every: Optional[int] = None, pos_template=None,
+                          sample_tau: float = 0.0, sample_seed: int = 0, sample0: int = 0):
+    """Block-synchronous sweeps (czc_generate_rows_tied, conzic_amd/blocks.py): every caption is polished by `width` tied rows
+    that each mask, propose and score one position of the step's block from the same current sentence; all winners are written
+    back together.  A sweep costs ceil(max_len / width) serial steps instead of max_len, each on a batch `width` times larger.
+    Rows are images x samples x width: row ((s * B + b) * width + slot), one engine call for all of them.
+    `order` sequential: the blocks of blocks.sequential_order under `layout` (interleaved | contiguous).  shuffle: every
+    sample's permutation is drawn exactly as run_generation draws it (one `random.shuffle` per sample from the process-global
+    stream, the same list every sweep) and cut into consecutive blocks; `layout` does not apply.  span / random: ValueError.
+    width 0 means max_len; width 1 is run_generation_samples itself.  The exact host control scorer (a callback told one
+    position per step) cannot serve a block: such a run falls back to width 1 and the log says so.
+    `sample_tau` > 0: slot j of (image, sample) draws under draws.row_seed(sample_seed, key of the image's name, sample, j).
+    Returns a list of `samples_num` (gen_texts_list, clip_score_sequence) pairs in run_generation's structure -- texts per sweep
+    plus best, cosines per sweep plus best -- where the cosines are those of the merged captions (czc_score_rows) and "best"
+    is chosen by them."""
+    from . import blocks as bl, draws as dw
+    import utils as ref_utils
+    if order not in ("sequential", "shuffle"):
+        raise ValueError(f"block-synchronous sweeps visit the positions in order sequential|shuffle, got {order!r}")
+    if layout not in bl.LAYOUTS:
+        raise ValueError(f"block layout {layout!r}: expected one of {bl.LAYOUTS}")
+    S, B, L = int(samples_num), int(batch_size), int(max_len)
+    W = bl.resolve_width(int(width), L)
+    serial_kw = dict(verbose=verbose, gamma=gamma, ctl_signal=ctl_signal, print_every=print_every, pos_template=pos_template,
+                     sample_tau=sample_tau, sample_seed=sample_seed, sample0=sample0)
+    eng = get_engine(model, clip, tokenizer)
+    if W > 1 and gamma is not None:
+        from . import control
+        chosen = control.configure(eng, clip, tokenizer, pos_template=pos_template, ctl_signal=ctl_signal)
+        if chosen == "exact":
+            logger.info(f"block width {W}: the exact control scorer is called with one position per step; falling back to block "
+                        "width 1 (CZC_CONTROL=table polishes blocks)")
+            W = 1
+    if W <= 1:
+        return run_generation_samples(order, S, img_name, model, clip, tokenizer, image_instance, token_mask, prompt, logger, L,
+                                      top_k, temperature, alpha, beta, max_iters, B, **serial_kw)
+    seed_len = len(prompt.split()) + 1
+    batch = ref_utils.get_init_text(tokenizer, prompt, L, B)
+    clip.compute_image_representation_from_image_instance(image_instance)
+    if getattr(eng, "_precision_logged", None) is None:
+        scale = _logit_scale_of(clip)
+        logger.info(f"engine precision: {PRECISION_NAMES.get(eng.precision, eng.precision)}"
+                    + (f" (exp(logit_scale) = {math.exp(scale):.1f})" if scale is not None else ""))
+        eng._precision_logged = True
+    nb = bl.n_blocks(L, W)
+    order_lists, per_sample = [], []
+    for _ in range(S):
+        if order == "shuffle":
+            order_list, sweeps = bl.shuffle_sweeps(L, max_iters, random)     # gen_utils.py:110-111 (process-global stream)
+            order_lists.append(order_list)
+        else:
+            sweeps = [bl.sequential_order(L, W, layout)] * max_iters
+        per_sample.append(bl.tied_positions(sweeps, W)[0])
+    said = (f"block width {W}, " + (f"layout {layout}, " if order == "sequential" else "consecutive blocks of the permutation, ")
+            + f"{nb} steps per sweep instead of {L}")
+    groups, cap, image_of_row = bl.tied_rows(S * B, W, image_of_caption=np.tile(np.arange(B, dtype=np.int32), S))
+    rows_pos = bl.caption_positions([per_sample[c // B] for c in range(S * B)])
+    hp = Engine.hyper(alpha, beta, temperature, gamma, ctl_signal == "negative", control="pos" if pos_template is not None else None)
+    tau = float(sample_tau or 0.0)
+    keys = [dw.image_key(n) for n in img_name]
+    row_draws = None if not tau else [dw.make_draw(dw.row_seed(sample_seed, keys[c % B], sample0 + c // B, j), tau)
+                                      for c in range(S * B) for j in range(W)]
+    init_rows = np.repeat(np.asarray(batch[0], dtype=np.int32)[None, :], S * B * W, axis=0)
+
+    def polish(eng):
+        eng.set_token_mask(_mask_to_numpy(token_mask))
+        eng.set_option("memo_rows", memo_rows_setting())
+        if gamma is not None:
+            from . import control
+            chosen = control.configure(eng, clip, tokenizer, pos_template=pos_template, ctl_signal=ctl_signal)
+            if chosen != getattr(eng, "_control_logged", None):
+                logger.info(f"control scores: {chosen}")
+                eng._control_logged = chosen
+        runner = _group_for(eng, S * B * W)
+        emb = None
+        if runner is not eng:
+            from clip.clip import ImageEmbeds
+            emb = image_instance.embeds if isinstance(image_instance, ImageEmbeds) else clip.last_image_embeds()
+            runner.set_image_embeds(emb)
+        if eng.precision == native.PREC_REFINE:
+            runner.refine_guard(reset=True)
+        out = runner.generate_rows_tied(init_rows, None, seed_len, top_k, rows_pos, [hp] * (S * B * W), row_draws, groups,
+                                        image_of_row=image_of_row, snapshot_every=nb)
+        if runner is not eng:
+            eng.set_image_embeds(emb)
+        return out, runner
+
+    ids, cos = _polish_guarded(polish, eng, model, clip, tokenizer, image_instance, logger)
+    if rows_pos.shape[0]:   # the caller's mask as after the last position the serial loop would have visited (utils.py:53-59)
+        last = order_lists[-1][-1] if order == "shuffle" else L - 1
+        ref_utils.update_token_mask(tokenizer, token_mask, L, int(last))
+    lead = np.arange(S * B) * W   # a group's rows hold one sentence and one cosine: its first row speaks for the caption
+    out = []
+    for s in range(S):
+        rows = lead[s * B:(s + 1) * B]
+        drew = dw.describe(row_draws[s * B * W:(s + 1) * B * W] if row_draws else None)
+        logger.info((f"Order_list:{order_lists[s]}" if order == "shuffle" else f"Order:{order}") + f" ({said})" + drew)
+        out.append(_bookkeeping(order, ids[:, rows], cos[:, rows], tokenizer, img_name, logger, B, verbose, print_every))
+    return out
+
+
+def caption_blocks(width: int, layout: str, samples_num: int, run_type: str, img_name, model, clip, tokenizer, image_instance,
+                   token_mask, logger, *, prompt="", batch_size=1, max_len=15, top_k=100, temperature=1.0, max_iter=500, alpha=0.7,
+                   beta=1, generate_order="sequential", gamma=5, ctl_type="sentiment", style_type="positive", pos_type=None,
+                   sample_tau=0.0, sample_seed=0, sample0=0):
+    """`--block_width` of the two CLIs: what caption_samples returns, polished in block-synchronous sweeps by one
+    run_generation_blocks call.  The visiting order is sequential or shuffle (ValueError otherwise)."""
+    start_time = time.time()
+    kw = dict(verbose=True)
+    order, max_iters = caption_order(run_type, generate_order, ctl_type, max_iter, max_len)
+    if order not in ("sequential", "shuffle"):
+        raise ValueError(f"--block_width needs generate_order sequential|shuffle, got {generate_order!r}")
+    if run_type != "caption" and ctl_type == "sentiment":
+        kw.update(gamma=gamma, ctl_signal=style_type)
+    elif run_type != "caption":
+        logger.info(pos_type)
+        kw.update(gamma=gamma, pos_template=pos_type)
+    outs = run_generation_blocks(order, width, layout, samples_num, img_name, model, clip, tokenizer, image_instance, token_mask,
+                                 prompt, logger, max_len, top_k, temperature, alpha, beta, max_iters, batch_size,
+                                 sample_tau=sample_tau, sample_seed=sample_seed, sample0=sample0, **kw)
+    logger.info("Finished %d samples in %.3fs" % (samples_num, time.time() - start_time))
+    for sample_id, (generate_texts, _) in enumerate(outs):
+        logger.info(f"Sample {sample0 + sample_id}: ")
+        for i in range(batch_size):
+            logger.info(f"The {i + 1}-th image: {img_name[i]}")
+            logger.info(f"final caption: {generate_texts[-2][i]}")
+            logger.info(f"best caption: {generate_texts[-1][i]}")
+    return outs
+
+
 def caption_lengths(lens: Sequence[int], samples_num: int, run_type: str, img_name, model, clip, tokenizer, image_instance, token_mask,
                     logger, *, prompt="", batch_size=1, top_k=100, temperature=1.0, max_iter=500, alpha=0.7, beta=1,
                     generate_order="sequential", gamma=5, ctl_type="sentiment", style_type="positive", pos_type=None,

@@ -7,6 +7,9 @@ MI355X-native engine (libconzic_hip.so) instead of eager torch.
 
 `parallel_generation` is deliberately absent: it is unreachable from the reference's CLI
 (`--order` choices, demo.py:33) and indexes with the wrong variable (gen_utils.py:265).
+The engine's counterpart of the idea -- every position masked, proposed and scored from the same
+current sentence, all winners written back together -- is `--block_width 0` of the CLIs
+(conzic_amd.runtime.run_generation_blocks); no parity with the reference function is claimed.
 """
 import time
 

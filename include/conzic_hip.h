@@ -425,6 +425,52 @@ int czc_generate_rows_draw(czc_engine* e, int R, int T, int seed_len, const int3
                            const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp_of_row_host /* [R] */,
                            const czc_draw* draw_of_row_host /* [R], or NULL */, int32_t* out_ids, float* out_cos);
 
+/* The CLIP cosine of BERT-id rows with their images, without leaving the device: row r, decoded as the step decodes it
+ * (special tokens and [MASK] dropped; the row stops at T_r = seed_len + len_of_row[r] + 1 tokens), passes the text bridge, the
+ * text tower as czc_encode_text runs it (independent sequences, no prefix sharing, the exact tower of the engine precision:
+ * split-fp16 on CZC_PREC_REFINE) and the steps' cosine kernel against the normalised embedding of image image_of_row[r] of the
+ * resident batch (czc_encode_images / czc_set_image_embeds).  A row's cosine does not depend on its index or companions.
+ * `rows` may be host or device memory; out_cos is [R].  An overflow of the bridge's scratch or a non-finite cosine returns
+ * CZC_ERR_OVERFLOW as in czc_step.
+ * Checked before any GPU work, and the engine stays usable.  CZC_ERR_ARG: an id outside the vocabulary (within a row's T_r
+ * tokens), len_of_row[r] outside [1, T - seed_len - 1], image_of_row outside the resident batch (NULL: identity, R must equal
+ * the resident batch), R > CZC_MAX_ROWS, T > CZC_MAX_BERT_LEN.  CZC_ERR_STATE without bridge tables or image embeds. */
+int czc_score_rows(czc_engine* e, const int32_t* rows /* [R, T] BERT ids, host or device */, int R, int T, int seed_len,
+                   const int32_t* len_of_row_host /* NULL: every row has T tokens */,
+                   const int32_t* image_of_row_host /* NULL: identity, R == resident batch */, float* out_cos /* [R] */);
+
+/* czc_generate_rows_draw with rows TIED into groups that hold one sentence: W rows of a caption each polish a position of their
+ * own from the same current sentence, and all winners are written back together (a block-synchronous sweep: ceil(L / W) serial
+ * steps instead of L).  Everything not named here is czc_generate_rows_draw's.
+ *   - group_of_row == NULL: czc_generate_rows_draw itself, bit for bit.  Group ids are arbitrary values in [0, R); the rows of
+ *     a group need not be contiguous.
+ *   - the tie: after every step s, for every group g and every member r that ran at column c_r (not idle), every other member
+ *     r' of g gets inp[r'][c_r] = inp[r][c_r].  The rows of a group hold the same ids after every step; each row was computed
+ *     from the sentence the group held before the step with its own position masked (n_mask = 1): a Gibbs conditional on the
+ *     old values.  One launch per step on the full [R, T] batch, behind whatever the step did (in-place run, compact batch with
+ *     scatter, "memo_rows" fill); the group table (CSR of member rows) is uploaded once with the schedule.
+ *   - out_cos changes meaning: out_cos[snap][r] is the czc_score_rows cosine of the caption as it stands at the snapshot (a
+ *     row's winner cosine is that of "old sentence with one word replaced", which never exists once W winners are merged).  It
+ *     is computed once per group, on the group's lowest-numbered row, and written to every member; only at snapshot steps and
+ *     only when out_cos != NULL.  out_ids is unchanged.  Singleton groups: the ids of czc_generate_rows_draw and cosines that
+ *     agree with its within the precision's bound for one sentence in another packing.
+ *   - hyper-parameters and draw records may differ between members.  Give members different seeds: the Philox counter is
+ *     (step, candidate), so equal seeds would give equal noise at different positions.
+ *   - option "memo_rows" applies unchanged: the key is the whole masked row, so a sibling's write makes a miss exactly when it
+ *     must, and a row that hit still hands its restored winner to its siblings.  Captions equal those of memo_rows = 0.
+ *   - a control callback: the one-position rule of czc_generate_rows_from refuses blocks wider than one; the tables work.
+ *   - CZC_PREC_REFINE: gate, audit and guard are as for the rows that run; the snapshot score uses the split tower.
+ * Checked before any GPU work, CZC_ERR_ARG, and the engine stays usable: a group id outside [0, R); members of a group that
+ * differ in start row, in len_of_row or in image_of_row (NULL is the identity, so it only admits singleton groups); two members
+ * of a group that run at the same position in one step; any n_mask other than 1 (the n_mask = 0 re-use of a forward across a
+ * tie is not defined, so span order is refused); and everything czc_generate_rows_draw checks. */
+int czc_generate_rows_tied(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host,
+                           const int32_t* len_of_row_host /* NULL: every row has L = T - seed_len - 1 */,
+                           const int32_t* image_of_row_host, const int32_t* group_of_row_host /* [R], or NULL */, int top_k,
+                           int n_steps, const int32_t* positions_host, const int32_t* n_mask_host, int snapshot_every,
+                           const czc_hyper* hp_of_row_host /* [R] */, const czc_draw* draw_of_row_host /* [R], or NULL */,
+                           int32_t* out_ids, float* out_cos);
+
 /* Engine options (all are exact work reductions / kernel choices; results agree within the engine precision):
  *   "share_prefix"    (1) encode the causal prefix common to an image's K candidates once per step instead of K
  *                         times

@@ -38,6 +38,15 @@ static const Hooks& HK() {
 #define launch_ln_finalize HK().ln_finalize
 #define launch_fold_ln HK().fold_ln
 #define gemm_wreg_stats_in_kernel HK().wreg_stats_ok
+#define launch_scan HK().scan
+#define launch_prefix_plan HK().prefix_plan
+#define launch_prefix_finish HK().prefix_finish
+#define launch_refine_select HK().refine_select
+#define launch_refine_select_rows HK().refine_select_rows
+#define launch_refine_select_draw HK().refine_select_draw
+#define launch_refine_plan HK().refine_plan
+#define launch_refine_finish HK().refine_finish
+#define launch_refine_cosine HK().refine_cosine
 #define g_use_gemm256 (*HK().use_gemm256)
 #define g_use_skinny (*HK().use_skinny)
 #define g_use_splitk (*HK().use_splitk)
@@ -110,6 +119,33 @@ int down_act(DevPool& pool, int prec, const void* src, size_t n, float* host) {
   T_HIP(hipMemcpy(host, f, n * 4, hipMemcpyDeviceToHost));
   return 0;
 }
+
+// An output buffer of n 4-byte words inside a larger allocation (the selection / plan hooks): CZC_TEST_GUARD words in front of
+// it and behind it, everything pre-filled with bytes 0x5a, and all n + 2 * CZC_TEST_GUARD words go back to the caller -- a stray
+// store shows in the result instead of leaving the buffer, and a word a kernel does not write reads back as the pattern.
+struct Guarded {
+  unsigned char* base = nullptr;
+  size_t n = 0;
+  template <typename T> T* p() const { return (T*)(base + (size_t)CZC_TEST_GUARD * 4); }
+  int make(DevPool& pool, size_t words) {
+    n = words;
+    base = (unsigned char*)pool.alloc((n + 2 * CZC_TEST_GUARD) * 4); T_PTR(base);
+    T_HIP(hipMemset(base, 0x5a, (n + 2 * CZC_TEST_GUARD) * 4));
+    return 0;
+  }
+  int zero(size_t words) const {  // the engine's own memset of (part of) the buffer
+    T_HIP(hipMemset(base + (size_t)CZC_TEST_GUARD * 4, 0, words * 4));
+    return 0;
+  }
+  int fill(const void* src) const {
+    T_HIP(hipMemcpy(base + (size_t)CZC_TEST_GUARD * 4, src, n * 4, hipMemcpyHostToDevice));
+    return 0;
+  }
+  int down(void* host) const {
+    T_HIP(hipMemcpy(host, base, (n + 2 * CZC_TEST_GUARD) * 4, hipMemcpyDeviceToHost));
+    return 0;
+  }
+};
 
 }  // namespace
 
@@ -590,6 +626,174 @@ int czc_test_combine_draw(int B, int K, int D, const float* text_feat, const flo
   T_HIP(hipMemcpy(final_score, o3, bk * 4, hipMemcpyDeviceToHost));
   T_HIP(hipMemcpy(best, ob, (size_t)B * 4, hipMemcpyDeviceToHost));
   return 0;
+}
+
+// ---- the integer and selection side of the screen-then-refine engine, one launcher chain at a time ------------------------------
+// Every output is a Guarded buffer: the caller's arrays hold CZC_TEST_GUARD + n + CZC_TEST_GUARD words.
+
+int czc_test_scan(int n, const int32_t* len, int32_t* off, int32_t* totals) {
+  if (n < 1) { snprintf(TEST_ERR, 512, "scan: n = %d", n); return CZC_ERR_ARG; }
+  DevPool pool;
+  int* dlen = (int*)pool.up(len, (size_t)n * 4); T_PTR(dlen);
+  Guarded goff, gtot;
+  T_CHECK(goff.make(pool, (size_t)n + 1)); T_CHECK(gtot.make(pool, 2));
+  T_CHECK(launch_scan(dlen, n, goff.p<int>(), gtot.p<int>(), nullptr));
+  T_HIP(hipDeviceSynchronize());
+  T_CHECK(goff.down(off));
+  return gtot.down(totals);
+}
+
+// clip_plan of engine.hip: launch_prefix_plan -> launch_scan over the B + B*K segment slots -> launch_prefix_finish on the eight
+// pre-zeroed totals words ([0] rows, [1] longest segment, [3] longest sequence, [4] longest branch, [5] duplicates, [6] trunk
+// rows, [7] causal pairs).  dedup 0: the kernels get no rep table and `rep` keeps the pattern.
+int czc_test_prefix_plan(int B, int K, int share, int dedup, const int32_t* clip_ids, const int32_t* clip_len, int32_t* own_len,
+                         int32_t* pre_len, int32_t* seg_src, int32_t* seg_pos0, int32_t* own_off, int32_t* pre_off, int32_t* eos_idx,
+                         int32_t* rep, int32_t* img_max, int32_t* totals) {
+  if (B < 1 || K < 1 || (long)B * K > (1 << 22)) { snprintf(TEST_ERR, 512, "prefix_plan: B %d K %d", B, K); return CZC_ERR_ARG; }
+  const size_t bk = (size_t)B * K, S = B + bk;
+  DevPool pool;
+  int* dids = (int*)pool.up(clip_ids, bk * CZC_CLIP_MAX_LEN * 4); T_PTR(dids);
+  int* dlen = (int*)pool.up(clip_len, bk * 4); T_PTR(dlen);
+  Guarded own, pre, src, pos0, ooff, poff, eidx, grep, imax, tot;
+  T_CHECK(own.make(pool, S)); T_CHECK(pre.make(pool, S)); T_CHECK(src.make(pool, S)); T_CHECK(pos0.make(pool, S));
+  T_CHECK(ooff.make(pool, S + 1)); T_CHECK(poff.make(pool, S)); T_CHECK(eidx.make(pool, bk)); T_CHECK(grep.make(pool, bk));
+  T_CHECK(imax.make(pool, B)); T_CHECK(tot.make(pool, 8));
+  T_CHECK(tot.zero(8));
+  int* t = tot.p<int>();
+  int* r = dedup ? grep.p<int>() : nullptr;
+  T_CHECK(launch_prefix_plan(dids, dlen, B, K, share, own.p<int>(), pre.p<int>(), src.p<int>(), pos0.p<int>(), t + 3, imax.p<int>(), nullptr, r, t + 5));
+  T_CHECK(launch_scan(own.p<int>(), (int)S, ooff.p<int>(), t, nullptr));
+  T_CHECK(launch_prefix_finish(ooff.p<int>(), own.p<int>(), B, K, poff.p<int>(), eidx.p<int>(), t + 6, nullptr, r));
+  T_HIP(hipDeviceSynchronize());
+  T_CHECK(own.down(own_len)); T_CHECK(pre.down(pre_len)); T_CHECK(src.down(seg_src)); T_CHECK(pos0.down(seg_pos0));
+  T_CHECK(ooff.down(own_off)); T_CHECK(poff.down(pre_off)); T_CHECK(eidx.down(eos_idx)); T_CHECK(grep.down(rep));
+  T_CHECK(imax.down(img_max));
+  return tot.down(totals);
+}
+
+// form 0: launch_refine_select (theta, beta); 1: launch_refine_select_rows (theta_base, scale, hyper [B]); 2:
+// launch_refine_select_draw (draw [B]; hyper [B] or NULL: the scalar theta / beta).  gated: the two pre-zeroed counters.
+int czc_test_refine_select(int form, int B, int K, const float* clip_score, const float* final_score, float theta, float theta_base,
+                           float scale, int m_samples, float gate_h, float beta, int need_cos, const czc_hyper* hyper,
+                           const czc_draw* draw, int32_t* gated, int32_t* kind, int32_t* list, int32_t* count) {
+  static_assert(sizeof(RowHyper) == sizeof(czc_hyper), "RowHyper is czc_hyper as the kernels read it");
+  if (form < 0 || form > 2 || B < 1 || K < 1 || (form == 1 && !hyper) || (form == 2 && !draw) || (form == 0 && (hyper || draw))) {
+    snprintf(TEST_ERR, 512, "refine_select: form %d B %d K %d", form, B, K);
+    return CZC_ERR_ARG;
+  }
+  const size_t bk = (size_t)B * K;
+  DevPool pool;
+  float* dcs = (float*)pool.up(clip_score, bk * 4); T_PTR(dcs);
+  float* dfs = (float*)pool.up(final_score, bk * 4); T_PTR(dfs);
+  RowHyper* dh = nullptr;
+  RowDraw* dd = nullptr;
+  if (hyper) { dh = (RowHyper*)pool.up(hyper, (size_t)B * sizeof(czc_hyper)); T_PTR(dh); }
+  if (draw) { dd = (RowDraw*)pool.up(draw, (size_t)B * sizeof(czc_draw)); T_PTR(dd); }
+  Guarded gg, gk, gl, gc;
+  T_CHECK(gg.make(pool, 2)); T_CHECK(gk.make(pool, bk)); T_CHECK(gl.make(pool, bk)); T_CHECK(gc.make(pool, B));
+  T_CHECK(gg.zero(2));
+  if (form == 0)
+    T_CHECK(launch_refine_select(dcs, dfs, B, K, theta, m_samples, gate_h, beta, need_cos, gg.p<int>(), gk.p<int>(), gl.p<int>(), gc.p<int>(), nullptr));
+  else if (form == 1)
+    T_CHECK(launch_refine_select_rows(dcs, dfs, B, K, theta_base, scale, m_samples, gate_h, dh, need_cos, gg.p<int>(), gk.p<int>(), gl.p<int>(),
+                                      gc.p<int>(), nullptr));
+  else
+    T_CHECK(launch_refine_select_draw(dcs, dfs, B, K, theta, theta_base, scale, m_samples, gate_h, beta, dh, dd, need_cos, gg.p<int>(), gk.p<int>(),
+                                      gl.p<int>(), gc.p<int>(), nullptr));
+  T_HIP(hipDeviceSynchronize());
+  T_CHECK(gg.down(gated)); T_CHECK(gk.down(kind)); T_CHECK(gl.down(list));
+  return gc.down(count);
+}
+
+// the plan of the refine pass as step_phase_b queues it: 16 totals words and own_len [B + B*K] zeroed, launch_scan(count)
+// (totals[8] = R, [9] = Kr) -> launch_refine_plan -> launch_scan(own_len) (totals[0] = rows) -> launch_refine_finish.
+// trunk_len [B]: the prefix lengths of the screening plan.
+int czc_test_refine_plan(int B, int K, const int32_t* clip_len, const int32_t* trunk_len, const int32_t* list, const int32_t* count,
+                         int32_t* count_off, int32_t* own_len, int32_t* pre_len, int32_t* seg_src, int32_t* seg_pos0, int32_t* own_off,
+                         int32_t* pre_off, int32_t* rlist, int32_t* eos_idx, int32_t* img_max, int32_t* totals) {
+  if (B < 1 || K < 1 || (long)B * K > (1 << 22)) { snprintf(TEST_ERR, 512, "refine_plan: B %d K %d", B, K); return CZC_ERR_ARG; }
+  for (int b = 0; b < B; ++b)
+    if (count[b] < 0 || count[b] > K) { snprintf(TEST_ERR, 512, "refine_plan: count[%d] = %d", b, count[b]); return CZC_ERR_ARG; }
+  const size_t bk = (size_t)B * K, S = B + bk;
+  DevPool pool;
+  int* dlen = (int*)pool.up(clip_len, bk * 4); T_PTR(dlen);
+  int* dtl = (int*)pool.up(trunk_len, (size_t)B * 4); T_PTR(dtl);
+  int* dlist = (int*)pool.up(list, bk * 4); T_PTR(dlist);
+  int* dcnt = (int*)pool.up(count, (size_t)B * 4); T_PTR(dcnt);
+  Guarded coff, own, pre, src, pos0, ooff, poff, rl, eidx, imax, tot;
+  T_CHECK(coff.make(pool, (size_t)B + 1)); T_CHECK(own.make(pool, S)); T_CHECK(pre.make(pool, S)); T_CHECK(src.make(pool, S));
+  T_CHECK(pos0.make(pool, S)); T_CHECK(ooff.make(pool, S + 1)); T_CHECK(poff.make(pool, S)); T_CHECK(rl.make(pool, bk));
+  T_CHECK(eidx.make(pool, bk)); T_CHECK(imax.make(pool, B)); T_CHECK(tot.make(pool, 16));
+  T_CHECK(tot.zero(16));
+  T_CHECK(own.zero(S));
+  int* t = tot.p<int>();
+  T_CHECK(launch_scan(dcnt, B, coff.p<int>(), t + 8, nullptr));
+  T_CHECK(launch_refine_plan(dlen, dtl, dlist, dcnt, coff.p<int>(), t + 9, B, K, own.p<int>(), pre.p<int>(), src.p<int>(), pos0.p<int>(),
+                             rl.p<int>(), t + 3, imax.p<int>(), nullptr));
+  T_CHECK(launch_scan(own.p<int>(), (int)S, ooff.p<int>(), t, nullptr));
+  T_CHECK(launch_refine_finish(ooff.p<int>(), own.p<int>(), dcnt, coff.p<int>(), t + 9, B, K, poff.p<int>(), eidx.p<int>(), nullptr));
+  T_HIP(hipDeviceSynchronize());
+  T_CHECK(coff.down(count_off)); T_CHECK(own.down(own_len)); T_CHECK(pre.down(pre_len)); T_CHECK(src.down(seg_src));
+  T_CHECK(pos0.down(seg_pos0)); T_CHECK(ooff.down(own_off)); T_CHECK(poff.down(pre_off)); T_CHECK(rl.down(rlist));
+  T_CHECK(eidx.down(eos_idx)); T_CHECK(imax.down(img_max));
+  return tot.down(totals);
+}
+
+// launch_refine_cosine on n_rows_max compact feature rows of which the first n_rows count (the engine's R, read on the device):
+// text_feat [n_rows_max, D], img [B, D] (normalised here by launch_l2_normalize, as czc_test_combine does), rlist [n_rows_max]
+// (flat candidate b*K + k of each row) -> cos_out [B*K], nonfinite (8 pre-zeroed words; [0] is the cosine check's flag).
+int czc_test_refine_cosine(int n_rows_max, int n_rows, int B, int K, int D, const float* text_feat, const float* img_embeds,
+                           const int32_t* rlist, float* cos_out, int32_t* nonfinite) {
+  if (n_rows_max < 1 || n_rows < 0 || n_rows > n_rows_max || B < 1 || K < 1 || D < 1) {
+    snprintf(TEST_ERR, 512, "refine_cosine: rows %d of %d B %d K %d D %d", n_rows, n_rows_max, B, K, D);
+    return CZC_ERR_ARG;
+  }
+  for (int r = 0; r < n_rows; ++r)
+    if (rlist[r] < 0 || rlist[r] >= B * K) { snprintf(TEST_ERR, 512, "refine_cosine: rlist[%d] = %d", r, rlist[r]); return CZC_ERR_ARG; }
+  DevPool pool;
+  float* dt = (float*)pool.up(text_feat, (size_t)n_rows_max * D * 4); T_PTR(dt);
+  float* di = (float*)pool.up(img_embeds, (size_t)B * D * 4); T_PTR(di);
+  float* din = (float*)pool.alloc((size_t)B * D * 4); T_PTR(din);
+  int* drl = (int*)pool.up(rlist, (size_t)n_rows_max * 4); T_PTR(drl);
+  int* dn = (int*)pool.up(&n_rows, 4); T_PTR(dn);
+  Guarded gcos, gnf;
+  T_CHECK(gcos.make(pool, (size_t)B * K)); T_CHECK(gnf.make(pool, 8));
+  T_CHECK(gnf.zero(8));
+  T_CHECK(launch_l2_normalize(di, B, D, din, nullptr));
+  T_CHECK(launch_refine_cosine(dt, din, drl, dn, n_rows_max, K, D, gcos.p<float>(), gnf.p<int>(), nullptr));
+  T_HIP(hipDeviceSynchronize());
+  T_CHECK(gcos.down(cos_out));
+  return gnf.down(nonfinite);
+}
+
+// The final combine of the refine engine: the screening cosines cos_in [B*K] enter through clip_ref (text_feat null), candidates
+// marked in refine_kind take refine_cos.  nonfinite: 8 pre-zeroed words ([1] the float bits of the guard deviation, [2] trips).
+int czc_test_combine_refine(int B, int K, float logit_scale, const float* cos_in, const float* probs, const czc_hyper* hp,
+                            const int32_t* refine_kind, const float* refine_cos, float refine_guard, float* clip_score, float* clip_ref,
+                            float* final_score, int32_t* best, float* best_cos, int32_t* nonfinite) {
+  if (B < 1 || K < 1) { snprintf(TEST_ERR, 512, "combine_refine: B %d K %d", B, K); return CZC_ERR_ARG; }
+  DevPool pool;
+  const size_t bk = (size_t)B * K;
+  float* dp = (float*)pool.up(probs, bk * 4); T_PTR(dp);
+  int* dk = (int*)pool.up(refine_kind, bk * 4); T_PTR(dk);
+  float* drc = (float*)pool.up(refine_cos, bk * 4); T_PTR(drc);
+  int* dcand = (int*)pool.alloc(bk * 4); T_PTR(dcand);
+  T_HIP(hipMemset(dcand, 0, bk * 4));
+  Guarded o1, o2, o3, ob, oc, gnf;
+  T_CHECK(o1.make(pool, bk)); T_CHECK(o2.make(pool, bk)); T_CHECK(o3.make(pool, bk)); T_CHECK(ob.make(pool, B)); T_CHECK(oc.make(pool, B));
+  T_CHECK(gnf.make(pool, 8));
+  T_CHECK(gnf.zero(8));
+  T_CHECK(o2.fill(cos_in));
+  CombineArgs a;
+  a.text_feat = nullptr; a.img_n = nullptr; a.logit_scale_exp = expf(logit_scale); a.probs = dp; a.cand = dcand;
+  a.senti_raw = nullptr; a.repeats = nullptr; a.alpha = hp->alpha; a.beta = hp->beta; a.gamma = hp->gamma; a.use_senti = 0;
+  a.B = B; a.K = K; a.D = 0; a.clip_score = o1.p<float>(); a.clip_ref = o2.p<float>(); a.final_score = o3.p<float>();
+  a.best = ob.p<int>(); a.best_cos = oc.p<float>(); a.inp = nullptr; a.T = 0; a.gen_idx = 0; a.nonfinite = gnf.p<int>();
+  a.refine_kind = dk; a.refine_cos = drc; a.refine_guard = refine_guard;
+  T_CHECK(launch_combine(a, nullptr));
+  T_HIP(hipDeviceSynchronize());
+  T_CHECK(o1.down(clip_score)); T_CHECK(o2.down(clip_ref)); T_CHECK(o3.down(final_score)); T_CHECK(ob.down(best)); T_CHECK(oc.down(best_cos));
+  return gnf.down(nonfinite);
 }
 
 }  // extern "C"

@@ -2698,7 +2698,9 @@ const void* czc_internal_hooks(int abi) {
       &launch_layernorm_x16, &launch_ln_finalize, &launch_fold_ln, &gemm_wreg_stats_in_kernel,
       &g_use_gemm256, &g_use_skinny, &g_use_splitk, &g_gemm_deep, &g_gemm_small_tiles, &g_use_wreg, &g_use_gemm256s,
       &g_rowln_min_m, &g_wreg_min_m, &g_gemm256_min_m, &g_use_mfma_attention, &g_use_attention_image, &g_wreg_resid_min_m,
-      &g_wreg_stats_in_kernel, &g_gemm256s_min_m};
+      &g_wreg_stats_in_kernel, &g_gemm256s_min_m,
+      &launch_scan, &launch_prefix_plan, &launch_prefix_finish, &launch_refine_select, &launch_refine_select_rows,
+      &launch_refine_select_draw, &launch_refine_plan, &launch_refine_finish, &launch_refine_cosine};
   return abi == HOOKS_ABI ? &h : nullptr;
 }
 

@@ -378,7 +378,7 @@ int launch_index_search(const split_t* index, int n, int D, const split_t* queri
 // ---- czc_internal_hooks (declared below, private to the build): what libconzic_hip_test.so may reach inside this library -----------
 // The product library has hidden visibility; the hook library (api_test.hip) gets the launchers it wraps and the
 // process-wide kernel-family switches it flips through this table instead of through exported C++ symbols.
-constexpr int HOOKS_ABI = 0x0604;
+constexpr int HOOKS_ABI = 0x0605;
 struct Hooks {
   char* (*err_buf)();  // the calling host thread's g_err [512]
   decltype(&launch_gemm) gemm;
@@ -401,6 +401,16 @@ struct Hooks {
   int *use_gemm256, *use_skinny, *use_splitk, *gemm_deep, *gemm_small_tiles, *use_wreg, *use_gemm256s, *rowln_min_m,
       *wreg_min_m, *gemm256_min_m, *use_mfma_attention, *use_attention_image, *wreg_resid_min_m, *wreg_stats_in_kernel,
       *gemm256s_min_m;
+  // the integer and selection side of the screen-then-refine engine (tests/test_refine_kernels_gpu.py)
+  decltype(&launch_scan) scan;
+  decltype(&launch_prefix_plan) prefix_plan;
+  decltype(&launch_prefix_finish) prefix_finish;
+  decltype(&launch_refine_select) refine_select;
+  decltype(&launch_refine_select_rows) refine_select_rows;
+  decltype(&launch_refine_select_draw) refine_select_draw;
+  decltype(&launch_refine_plan) refine_plan;
+  decltype(&launch_refine_finish) refine_finish;
+  decltype(&launch_refine_cosine) refine_cosine;
 };
 
 }  // namespace czc

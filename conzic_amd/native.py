@@ -160,6 +160,13 @@ TEST_SIGNATURES = {
     "czc_test_bridge": (_I, [C.POINTER(BridgeTables), C.POINTER(Config), _I, _I, _P, _P, _P]),
     "czc_test_combine": (_I, [_I, _I, _I, _P, _P, C.c_float, _P, _P, _P, C.POINTER(Hyper), _P, _P, _P, _P]),
     "czc_test_combine_draw": (_I, [_I, _I, _I, _P, _P, C.c_float, _P, _P, _P, C.POINTER(Hyper), C.POINTER(Draw), C.c_uint32, _P, _P]),
+    "czc_test_scan": (_I, [_I, _P, _P, _P]),
+    "czc_test_prefix_plan": (_I, [_I, _I, _I, _I] + [_P] * 12),
+    "czc_test_refine_select": (_I, [_I, _I, _I, _P, _P, C.c_float, C.c_float, C.c_float, _I, C.c_float, C.c_float, _I, _P, _P,
+                                    _P, _P, _P, _P]),
+    "czc_test_refine_plan": (_I, [_I, _I] + [_P] * 15),
+    "czc_test_refine_cosine": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "czc_test_combine_refine": (_I, [_I, _I, C.c_float, _P, _P, C.POINTER(Hyper), _P, _P, C.c_float, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

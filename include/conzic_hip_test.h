@@ -89,6 +89,44 @@ int czc_test_combine_draw(int B, int K, int D, const float* text_feat, const flo
                           const float* probs, const float* senti_raw, const float* repeats, const czc_hyper* hp,
                           const czc_draw* draw, uint32_t step, float* final_score, int32_t* best);
 
+/* ---- the integer and selection side of the screen-then-refine engine (csrc/combine.hip, csrc/bridge.hip), one launcher chain
+ * at a time, with the buffer preparation of the engine (tests/refine_ref.py states each operation in numpy).
+ * EVERY OUTPUT ARRAY below holds CZC_TEST_GUARD + n + CZC_TEST_GUARD 4-byte words for the n the comment names: the device
+ * buffer sits inside a larger allocation pre-filled with bytes 0x5a and comes back whole, so a stray store shows in the guard
+ * words and a word the kernels do not write reads back as the pattern. */
+#define CZC_TEST_GUARD 64
+/* launch_scan: off [n + 1] = exclusive scan of len [n], totals [2] = (sum, max) */
+int czc_test_scan(int n, const int32_t* len, int32_t* off, int32_t* totals);
+/* launch_prefix_plan -> launch_scan -> launch_prefix_finish on clip_ids [B*K, 77] / clip_len [B*K], S = B + B*K segment slots:
+ * own_len, pre_len, seg_src, seg_pos0, pre_off [S]; own_off [S + 1]; eos_idx, rep [B*K] (rep only with dedup); img_max [B];
+ * totals [8], zeroed first: [0] rows, [1] longest segment, [3] longest sequence, [4] longest branch, [5] duplicates, [6] trunk
+ * rows, [7] causal (query, key) pairs. */
+int czc_test_prefix_plan(int B, int K, int share, int dedup, const int32_t* clip_ids, const int32_t* clip_len, int32_t* own_len,
+                         int32_t* pre_len, int32_t* seg_src, int32_t* seg_pos0, int32_t* own_off, int32_t* pre_off, int32_t* eos_idx,
+                         int32_t* rep, int32_t* img_max, int32_t* totals);
+/* form 0 launch_refine_select (theta, beta), 1 launch_refine_select_rows (theta_base, scale, hyper [B]), 2
+ * launch_refine_select_draw (draw [B]; hyper [B] or NULL = the scalar theta / beta) on clip_score / final_score [B, K]:
+ * gated [2] (zeroed first), kind, list [B*K], count [B]. */
+int czc_test_refine_select(int form, int B, int K, const float* clip_score, const float* final_score, float theta, float theta_base,
+                           float scale, int m_samples, float gate_h, float beta, int need_cos, const czc_hyper* hyper,
+                           const czc_draw* draw, int32_t* gated, int32_t* kind, int32_t* list, int32_t* count);
+/* the refine pass's plan: launch_scan(count) -> launch_refine_plan -> launch_scan(own_len) -> launch_refine_finish, own_len and
+ * the totals zeroed first.  clip_len, list [B*K], trunk_len, count [B] -> count_off [B + 1]; own_len, pre_len, seg_src, seg_pos0,
+ * pre_off [S]; own_off [S + 1]; rlist, eos_idx [B*K]; img_max [B]; totals [16]: [0] rows, [1] longest segment, [3] longest
+ * sequence, [4] longest branch, [7] pairs, [8] R, [9] Kr. */
+int czc_test_refine_plan(int B, int K, const int32_t* clip_len, const int32_t* trunk_len, const int32_t* list, const int32_t* count,
+                         int32_t* count_off, int32_t* own_len, int32_t* pre_len, int32_t* seg_src, int32_t* seg_pos0, int32_t* own_off,
+                         int32_t* pre_off, int32_t* rlist, int32_t* eos_idx, int32_t* img_max, int32_t* totals);
+/* launch_refine_cosine: text_feat [n_rows_max, D] of which the first n_rows count, img_embeds [B, D] (L2-normalised on the
+ * device), rlist [n_rows_max] -> cos_out [B*K], nonfinite [8] (zeroed first). */
+int czc_test_refine_cosine(int n_rows_max, int n_rows, int B, int K, int D, const float* text_feat, const float* img_embeds,
+                           const int32_t* rlist, float* cos_out, int32_t* nonfinite);
+/* launch_combine with refine_kind / refine_cos [B, K]: cos_in [B, K] enters through clip_ref (no text features) ->
+ * clip_score, clip_ref, final_score [B*K], best, best_cos [B], nonfinite [8] (zeroed first). */
+int czc_test_combine_refine(int B, int K, float logit_scale, const float* cos_in, const float* probs, const czc_hyper* hp,
+                            const int32_t* refine_kind, const float* refine_cos, float refine_guard, float* clip_score, float* clip_ref,
+                            float* final_score, int32_t* best, float* best_cos, int32_t* nonfinite);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

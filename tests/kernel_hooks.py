@@ -189,3 +189,128 @@ def combine(text_feat, img_embeds, logit_scale, probs, hyper, senti_raw=None, re
                                       _ptr(sr), _ptr(rp), C.byref(hyper), cs.ctypes.data, cr.ctypes.data,
                                       fs.ctypes.data, best.ctypes.data), None, "czc_test_combine")
     return cs, cr, fs, best
+
+
+# ---- the integer and selection side of the screen-then-refine engine (czc_test_scan .. czc_test_combine_refine) ----------------------
+GUARD = 64                  # include/conzic_hip_test.h CZC_TEST_GUARD: words in front of and behind every output of these hooks
+SENTINEL = 0x5A5A5A5A       # what a word no kernel wrote reads back as (compare through .view(np.uint32))
+
+
+class Guarded(dict):
+    """name -> the n words of an output; .guards: name -> its 2 * GUARD guard words"""
+
+    def __init__(self):
+        super().__init__()
+        self.guards = {}
+        self._full = {}
+
+    def buf(self, name, n, dtype=np.int32):
+        self._full[name] = np.zeros(int(n) + 2 * GUARD, dtype)
+        return self._full[name].ctypes.data
+
+    def done(self):
+        for name, full in self._full.items():
+            self[name] = full[GUARD:full.size - GUARD]
+            self.guards[name] = np.concatenate([full[:GUARD], full[full.size - GUARD:]])
+        return self
+
+    def assert_guards(self):
+        for name, g in self.guards.items():
+            bad = np.nonzero(g.view(np.uint32) != SENTINEL)[0]
+            assert bad.size == 0, f"{name}: stray store into guard words {bad[:8].tolist()} (front: < {GUARD})"
+
+
+def untouched(a):
+    """mask of the words that still hold the pre-fill pattern"""
+    return np.asarray(a).view(np.uint32) == SENTINEL
+
+
+def scan(length):
+    lib = native.load_test()
+    ln = np.ascontiguousarray(length, np.int32)
+    g = Guarded()
+    native.check(lib.czc_test_scan(ln.size, ln.ctypes.data, g.buf("off", ln.size + 1), g.buf("totals", 2)), None, "czc_test_scan")
+    return g.done()
+
+
+def prefix_plan(ids, length, share, dedup):
+    lib = native.load_test()
+    ids = np.ascontiguousarray(ids, np.int32)
+    ln = np.ascontiguousarray(length, np.int32)
+    B, K = ln.shape
+    assert ids.shape == (B, K, native.CLIP_MAX_LEN)
+    S = B + B * K
+    g = Guarded()
+    native.check(lib.czc_test_prefix_plan(B, K, int(share), int(dedup), ids.ctypes.data, ln.ctypes.data, g.buf("own_len", S),
+                                          g.buf("pre_len", S), g.buf("seg_src", S), g.buf("seg_pos0", S), g.buf("own_off", S + 1),
+                                          g.buf("pre_off", S), g.buf("eos_idx", B * K), g.buf("rep", B * K), g.buf("img_max", B),
+                                          g.buf("totals", 8)), None, "czc_test_prefix_plan")
+    return g.done()
+
+
+def refine_select(form, clip_score, final_score, m_samples, gate_h, need_cos, theta=0.0, beta=0.0, theta_base=0.0, scale=0.0,
+                  hyper=None, draws=None):
+    """form 0 scalar (theta, beta), 1 per-row hyper-parameters (theta_base, scale, hyper: list of native.Hyper), 2 drawing rows
+    (draws: list of native.Draw; hyper or the scalars) -> Guarded(gated [2], kind, list [B, K], count [B])"""
+    lib = native.load_test()
+    cs = np.ascontiguousarray(clip_score, np.float32)
+    fs = np.ascontiguousarray(final_score, np.float32)
+    B, K = cs.shape
+    hp = (native.Hyper * B)(*hyper) if hyper is not None else None
+    dr = (native.Draw * B)(*draws) if draws is not None else None
+    g = Guarded()
+    native.check(lib.czc_test_refine_select(int(form), B, K, cs.ctypes.data, fs.ctypes.data, float(theta), float(theta_base), float(scale),
+                                            int(m_samples), float(gate_h), float(beta), int(need_cos),
+                                            C.cast(hp, C.c_void_p) if hp is not None else None,
+                                            C.cast(dr, C.c_void_p) if dr is not None else None,
+                                            g.buf("gated", 2), g.buf("kind", B * K), g.buf("list", B * K), g.buf("count", B)),
+                 None, "czc_test_refine_select")
+    g.done()
+    g["kind"] = g["kind"].reshape(B, K)
+    g["list"] = g["list"].reshape(B, K)
+    return g
+
+
+def refine_plan(clip_len, trunk_len, lst, count):
+    lib = native.load_test()
+    cl = np.ascontiguousarray(clip_len, np.int32)
+    tl = np.ascontiguousarray(trunk_len, np.int32)
+    ls = np.ascontiguousarray(lst, np.int32)
+    ct = np.ascontiguousarray(count, np.int32)
+    B, K = cl.shape
+    S = B + B * K
+    g = Guarded()
+    native.check(lib.czc_test_refine_plan(B, K, cl.ctypes.data, tl.ctypes.data, ls.ctypes.data, ct.ctypes.data, g.buf("count_off", B + 1),
+                                          g.buf("own_len", S), g.buf("pre_len", S), g.buf("seg_src", S), g.buf("seg_pos0", S),
+                                          g.buf("own_off", S + 1), g.buf("pre_off", S), g.buf("rlist", B * K), g.buf("eos_idx", B * K),
+                                          g.buf("img_max", B), g.buf("totals", 16)), None, "czc_test_refine_plan")
+    return g.done()
+
+
+def refine_cosine(feat, img, rlist, n_rows, B, K):
+    lib = native.load_test()
+    tf = np.ascontiguousarray(feat, np.float32)
+    ie = np.ascontiguousarray(img, np.float32)
+    rl = np.ascontiguousarray(rlist, np.int32)
+    n_max, D = tf.shape
+    assert rl.shape == (n_max,) and ie.shape == (B, D)
+    g = Guarded()
+    native.check(lib.czc_test_refine_cosine(n_max, int(n_rows), B, K, D, tf.ctypes.data, ie.ctypes.data, rl.ctypes.data,
+                                            g.buf("cos_out", B * K, np.float32), g.buf("nonfinite", 8)), None, "czc_test_refine_cosine")
+    return g.done()
+
+
+def combine_refine(cos_in, probs, logit_scale, hyper, kind, rcos, guard):
+    lib = native.load_test()
+    ci = np.ascontiguousarray(cos_in, np.float32)
+    pr = np.ascontiguousarray(probs, np.float32)
+    kd = np.ascontiguousarray(kind, np.int32)
+    rc = np.ascontiguousarray(rcos, np.float32)
+    B, K = ci.shape
+    g = Guarded()
+    native.check(lib.czc_test_combine_refine(B, K, float(logit_scale), ci.ctypes.data, pr.ctypes.data, C.byref(hyper), kd.ctypes.data,
+                                             rc.ctypes.data, float(guard), g.buf("clip_score", B * K, np.float32),
+                                             g.buf("clip_ref", B * K, np.float32), g.buf("final_score", B * K, np.float32),
+                                             g.buf("best", B), g.buf("best_cos", B, np.float32), g.buf("nonfinite", 8)),
+                 None, "czc_test_combine_refine")
+    return g.done()

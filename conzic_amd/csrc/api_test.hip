@@ -796,4 +796,59 @@ int czc_test_combine_refine(int B, int K, float logit_scale, const float* cos_in
   return gnf.down(nonfinite);
 }
 
+// The rival instantiation of the combine: rows [B] with their own image image_of_row[b] of img_all [n_img, D] (normalised here by
+// launch_l2_normalize; the rows' own embeddings are the gathered copy, as in the rows calls) and rival_idx [B, M] into img_all.
+// draw NULL: no row draws.  Outputs are Guarded; nonfinite: 8 pre-zeroed words.
+int czc_test_combine_rivals(int B, int K, int D, const float* text_feat, const float* img_all, int n_img, const int32_t* image_of_row,
+                            const int32_t* rival_idx, int M, const float* delta, float logit_scale, const float* probs,
+                            const czc_hyper* hp, const czc_draw* draw, uint32_t step, float* clip_ref, float* disc, float* final_score,
+                            int32_t* best, int32_t* nonfinite) {
+  if (B < 1 || K < 1 || D < 1 || n_img < 1 || M < 1 || M > CZC_MAX_RIVALS || (long)D * CZC_MAX_RIVALS > CB_RIVAL_FLOATS) {
+    snprintf(TEST_ERR, 512, "combine_rivals: B %d K %d D %d n_img %d M %d", B, K, D, n_img, M);
+    return CZC_ERR_ARG;
+  }
+  for (int b = 0; b < B; ++b) {  // what the entry points refuse: nothing out of bounds reaches the kernel
+    if (image_of_row[b] < 0 || image_of_row[b] >= n_img) { snprintf(TEST_ERR, 512, "combine_rivals: image_of_row"); return CZC_ERR_ARG; }
+    if (hp[b].control != 0) { snprintf(TEST_ERR, 512, "combine_rivals: the hook carries no control scores"); return CZC_ERR_ARG; }
+    for (int j = 0; j < M; ++j)
+      if (rival_idx[(size_t)b * M + j] < -1 || rival_idx[(size_t)b * M + j] >= n_img) { snprintf(TEST_ERR, 512, "combine_rivals: rival index"); return CZC_ERR_ARG; }
+  }
+  DevPool pool;
+  const size_t bk = (size_t)B * K;
+  float* dt = (float*)pool.up(text_feat, bk * D * 4); T_PTR(dt);
+  float* di = (float*)pool.up(img_all, (size_t)n_img * D * 4); T_PTR(di);
+  float* dall = (float*)pool.alloc((size_t)n_img * D * 4); T_PTR(dall);
+  float* din = (float*)pool.alloc((size_t)B * D * 4); T_PTR(din);
+  float* dp = (float*)pool.up(probs, bk * 4); T_PTR(dp);
+  int* dcand = (int*)pool.alloc(bk * 4); T_PTR(dcand);
+  T_HIP(hipMemset(dcand, 0, bk * 4));
+  int* driv = (int*)pool.up(rival_idx, (size_t)B * M * 4); T_PTR(driv);
+  float* ddel = (float*)pool.up(delta, (size_t)B * 4); T_PTR(ddel);
+  static_assert(sizeof(RowHyper) == sizeof(czc_hyper), "RowHyper is czc_hyper as the kernels read it");
+  RowHyper* dh = (RowHyper*)pool.up(hp, (size_t)B * sizeof(czc_hyper)); T_PTR(dh);
+  std::vector<czc_draw> nodraw((size_t)B, czc_draw{0, 0.f, 0});
+  RowDraw* dd = (RowDraw*)pool.up(draw ? draw : nodraw.data(), (size_t)B * sizeof(czc_draw)); T_PTR(dd);
+  int* dcol = (int*)pool.alloc((size_t)B * 4); T_PTR(dcol);
+  T_HIP(hipMemset(dcol, 0, (size_t)B * 4));
+  Guarded o1, o2, o3, od, ob, oc, gnf;
+  T_CHECK(o1.make(pool, bk)); T_CHECK(o2.make(pool, bk)); T_CHECK(o3.make(pool, bk)); T_CHECK(od.make(pool, bk));
+  T_CHECK(ob.make(pool, B)); T_CHECK(oc.make(pool, B)); T_CHECK(gnf.make(pool, 8));
+  T_CHECK(gnf.zero(8));
+  T_CHECK(launch_l2_normalize(di, n_img, D, dall, nullptr));
+  T_HIP(hipDeviceSynchronize());
+  for (int b = 0; b < B; ++b)
+    T_HIP(hipMemcpy(din + (size_t)b * D, dall + (size_t)image_of_row[b] * D, (size_t)D * 4, hipMemcpyDeviceToDevice));
+  CombineArgs a;
+  a.text_feat = dt; a.img_n = din; a.logit_scale_exp = expf(logit_scale); a.probs = dp; a.cand = dcand;
+  a.senti_raw = nullptr; a.repeats = nullptr; a.alpha = hp->alpha; a.beta = hp->beta; a.gamma = hp->gamma; a.use_senti = 0;
+  a.B = B; a.K = K; a.D = D; a.clip_score = o1.p<float>(); a.clip_ref = o2.p<float>(); a.final_score = o3.p<float>();
+  a.best = ob.p<int>(); a.best_cos = oc.p<float>(); a.inp = nullptr; a.T = 0; a.gen_idx = 0; a.nonfinite = gnf.p<int>();
+  a.gen_rows = dcol; a.hp_rows = dh; a.draw_rows = dd; a.draw_step = step;
+  a.rival_idx = driv; a.M = M; a.rival_delta = ddel; a.img_all = dall; a.n_img = n_img; a.disc = od.p<float>();
+  T_CHECK(launch_combine(a, nullptr));
+  T_HIP(hipDeviceSynchronize());
+  T_CHECK(o2.down(clip_ref)); T_CHECK(od.down(disc)); T_CHECK(o3.down(final_score)); T_CHECK(ob.down(best));
+  return gnf.down(nonfinite);
+}
+
 }  // extern "C"

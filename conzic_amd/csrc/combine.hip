@@ -47,6 +47,85 @@ __global__ __launch_bounds__(256) void cosine_kernel(const float* text_feat, con
   }
 }
 
+// czc_generate_rows_vs: the cosines of a row's candidates against its own image AND against its rival images, and from them
+//   disc[b,k] = softmax over {own image} + rivals of exp(logit_scale) * cos(t, image), taken at the own image
+//             = 1 / (1 + sum_j exp(x_j)),   x_j = s * (c_j - c_0)
+// the probability that candidate k retrieves its own image among the set.  A work-group takes CR_CAND candidates of ONE row (a
+// wave walks CR_CAND / 4 of them), so the row's rival count m_b and everything that branches on it is uniform; the m_b rival
+// rows are staged once in LDS and shared by the four waves.  A wave reads its candidate's feature row from memory once, into
+// registers (lane l holds columns l, l + 64, ...: cosine_kernel's striding), and keeps the normalised slice across the rival
+// loop.  c_0 takes cosine_kernel's expressions in cosine_kernel's order: the same bits.  disc is evaluated in fp32 with
+// max(0, max_j x_j) subtracted before any expf, so no exponent is positive.
+constexpr int CR_CAND = 16;
+constexpr int CR_SLICE = CB_RIVAL_FLOATS / CB_MAX_RIVALS / 64;  // columns of a feature row one lane holds: 8 at D <= 512
+__global__ __launch_bounds__(256) void cosine_rival_kernel(const float* text_feat, const float* img_n, int B, int K, int D, const int* rival_idx,
+                                                           int M, const float* img_all, int n_img, float scale, float* cos_out, float* disc,
+                                                           int* nonfinite) {
+  __shared__ float s_riv[CB_RIVAL_FLOATS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int nchunk = (K + CR_CAND - 1) / CR_CAND;
+  const int b = blockIdx.x / nchunk, chunk = blockIdx.x % nchunk;
+  if (b >= B) return;
+  // filled slots come first; an index outside the resident batch ends the list like an empty slot (the host refuses both)
+  int m = 0;
+  while (m < M && m < CB_MAX_RIVALS && rival_idx[(long)b * M + m] >= 0 && rival_idx[(long)b * M + m] < n_img) ++m;
+  for (int i = threadIdx.x; i < m * D; i += 256) {
+    const int j = i / D, c = i - j * D;
+    s_riv[i] = img_all[(long)rival_idx[(long)b * M + j] * D + c];
+  }
+  __syncthreads();
+  const float* img = img_n + (long)b * D;
+  for (int q = 0; q < CR_CAND / 4; ++q) {
+    const int k = chunk * CR_CAND + q * 4 + wave;
+    if (k >= K) break;  // uniform over the wave
+    const long row = (long)b * K + k;
+    const float* t = text_feat + row * D;
+    float tv[CR_SLICE];
+#pragma unroll
+    for (int i = 0; i < CR_SLICE; ++i) { const int c = lane + 64 * i; tv[i] = c < D ? t[c] : 0.f; }
+    float nn = 0.f;
+#pragma unroll
+    for (int i = 0; i < CR_SLICE; ++i) if (lane + 64 * i < D) nn += tv[i] * tv[i];
+    const float nrm = sqrtf(wave_sum(nn));
+    float dot = 0.f;
+#pragma unroll
+    for (int i = 0; i < CR_SLICE; ++i) {
+      const int c = lane + 64 * i;
+      if (c < D) { tv[i] = tv[i] / nrm; dot += tv[i] * img[c]; }
+    }
+    dot = wave_sum(dot);
+    float x[CB_MAX_RIVALS];
+    float xm = 0.f;
+    bool bad = !(fabsf(dot) <= 2.0f);
+#pragma unroll
+    for (int j = 0; j < CB_MAX_RIVALS; ++j) {
+      x[j] = 0.f;
+      if (j < m) {
+        float dj = 0.f;
+#pragma unroll
+        for (int i = 0; i < CR_SLICE; ++i) {
+          const int c = lane + 64 * i;
+          if (c < D) dj += tv[i] * s_riv[j * D + c];
+        }
+        dj = wave_sum(dj);
+        bad = bad || !(fabsf(dj) <= 2.0f);
+        x[j] = scale * (dj - dot);
+        xm = fmaxf(xm, x[j]);
+      }
+    }
+    float den = expf(0.f - xm);
+    const float num = den;
+#pragma unroll
+    for (int j = 0; j < CB_MAX_RIVALS; ++j)
+      if (j < m) den += expf(x[j] - xm);
+    if (lane == 0) {
+      cos_out[row] = dot;
+      disc[row] = num / den;
+      if (nonfinite && bad) atomicOr(nonfinite, 1);
+    }
+  }
+}
+
 // Philox4x32-10 (Salmon et al., SC'11): counter (c0, c1, 0, 0), key (k0, k1) -> four 32-bit words.  Counter-based, so the word
 // of (row seed, step, candidate) is a pure function of those three: no state, no order, no neighbour.
 __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned k0, unsigned k1, unsigned out[4]) {
@@ -72,7 +151,10 @@ __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned
 // No eligible candidate: the first argmax of final, as without the draw.  One thread per candidate in the strided loop the
 // other passes use; tau is the row's, so the branch is uniform over the work-group.  A tau == 0 row runs the argmax code below
 // on s_fin as the other instantiations do.
-template <bool ROWS, bool HP, bool DRAW>
+// RIVAL (czc_generate_rows_vs): a row with rival_delta[b] != 0 and a filled rival slot adds rival_delta[b] * disc[b,k] (from
+// cosine_rival_kernel) to final_k, in fp32 and last, behind the control terms; any other row skips the term entirely -- it is not
+// added as a constant -- so its scores are those of the <ROWS, HP, DRAW> instantiation.  The branch is the row's: uniform.
+template <bool ROWS, bool HP, bool DRAW, bool RIVAL = false>
 __global__ __launch_bounds__(CB_THREADS) void combine_kernel(CombineArgs a) {
   __shared__ float s_cos[CB_MAXK];
   __shared__ float s_fin[CB_MAXK];
@@ -86,6 +168,8 @@ __global__ __launch_bounds__(CB_THREADS) void combine_kernel(CombineArgs a) {
     const RowHyper h = a.hp_rows[b];
     a.alpha = h.alpha; a.beta = h.beta; a.gamma = h.gamma; a.use_senti = h.control;
   }
+  float rdelta = 0.f;
+  if (RIVAL) rdelta = a.rival_idx[(long)b * a.M] >= 0 ? a.rival_delta[b] : 0.f;
 
   // cosines come from cosine_kernel through clip_ref (overwritten below with the reference's logits/scale form)
   for (int k = tid; k < K; k += CB_THREADS) s_cos[k] = a.clip_ref[(long)b * K + k];
@@ -156,6 +240,9 @@ __global__ __launch_bounds__(CB_THREADS) void combine_kernel(CombineArgs a) {
       const float sp = expf(a.senti_raw[o] / ctemp - smx) / ssm;
       f = f + a.gamma * sp;
       if (a.use_senti == 1) f = f + 0.1f * (1.0f - expf(a.repeats[o]));
+    }
+    if (RIVAL) {
+      if (rdelta != 0.f) f = f + rdelta * a.disc[o];
     }
     a.clip_score[o] = cs;
     a.clip_ref[o] = ref;
@@ -398,10 +485,37 @@ int launch_cosine(const float* text_feat, const float* img_n, int B, int K, int 
   return 0;
 }
 
+int launch_cosine_rival(const float* text_feat, const float* img_n, int B, int K, int D, const int* rival_idx, int M, const float* img_all,
+                        int n_img, float logit_scale_exp, float* cos_out, float* disc, int* nonfinite, hipStream_t st) {
+  if ((long)B * K <= 0) return 0;
+  if (M < 1 || M > CB_MAX_RIVALS || D < 1 || (long)D * CB_MAX_RIVALS > CB_RIVAL_FLOATS || n_img < 1) {
+    snprintf(g_err, sizeof(g_err), "cosine_rival: M=%d outside [1, %d], D=%d beyond %d or no image batch", M, CB_MAX_RIVALS, D,
+             CB_RIVAL_FLOATS / CB_MAX_RIVALS);
+    return 1;
+  }
+  const long blocks = (long)B * cdiv(K, CR_CAND);
+  if (blocks > 0x7fffffffL) { snprintf(g_err, sizeof(g_err), "cosine_rival: B * K too large"); return 1; }
+  hipLaunchKernelGGL(cosine_rival_kernel, dim3((unsigned)blocks), dim3(256), 0, st, text_feat, img_n, B, K, D, rival_idx, M, img_all, n_img,
+                     logit_scale_exp, cos_out, disc, nonfinite);
+  CZC_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
 int launch_combine(const CombineArgs& a, hipStream_t st) {
   if (a.K > CB_MAXK) {
     snprintf(g_err, sizeof(g_err), "combine: K=%d > %d", a.K, CB_MAXK);
     return 1;
+  }
+  if (a.rival_idx) {
+    if (!a.text_feat || !a.gen_rows || !a.hp_rows || !a.draw_rows || !a.rival_delta || !a.img_all || !a.disc || a.refine_kind) {
+      snprintf(g_err, sizeof(g_err), "combine: rivals need text features, gen_rows, hp_rows, draw_rows, deltas, the image batch and disc, and no refine pass");
+      return 1;
+    }
+    if (launch_cosine_rival(a.text_feat, a.img_n, a.B, a.K, a.D, a.rival_idx, a.M, a.img_all, a.n_img, a.logit_scale_exp, a.clip_ref, a.disc,
+                            a.nonfinite, st)) return 1;
+    hipLaunchKernelGGL((combine_kernel<true, true, true, true>), dim3(a.B), dim3(CB_THREADS), 0, st, a);
+    CZC_HIP_CHECK(hipGetLastError());
+    return 0;
   }
   if (a.text_feat)  // null: clip_ref already holds the cosines (second combine of the screen-then-refine engine)
     hipLaunchKernelGGL(cosine_kernel, dim3((unsigned)cdiv((long)a.B * a.K, 4)), dim3(256), 0, st, a.text_feat, a.img_n, a.B, a.K, a.D,

@@ -169,6 +169,12 @@ struct czc_engine {
   // hp_rows) and the step's index in the call's schedule (the Philox counter is the record's step0 + draw_step); null elsewhere
   const RowDraw* draw_rows = nullptr;
   unsigned draw_step = 0;
+  // czc_generate_rows_vs.  vs_*: what the entry point hands to the rows call underneath it (host arrays; vs_host null outside
+  // such a call).  rival_*: during the steps, the rival table [rows of the step at hand, rival_M] and the deltas of those rows
+  // (device, gathered like hp_rows) and the whole normalised resident batch the indices point into; null elsewhere
+  const int32_t* vs_host = nullptr; const float* vs_delta_host = nullptr; int vs_M = 0;
+  const int* rival_rows = nullptr; const float* rival_delta = nullptr; int rival_M = 0;
+  const float* rival_img_all = nullptr; int rival_n_img = 0;
   int memo_branch_floor = 0;  // compacted step: longest branch the HIT images had (the full batch's attention-kernel choice)
   int64_t stat_memo_hits = 0, stat_memo_images = 0;  // image-steps that took an entry / all image-steps of memo calls
   // option "memo_rows" (czc_generate_rows only; memo_rows.hip): the same rule keyed per row, with counters of its own
@@ -872,6 +878,11 @@ int step_phase_b(czc_engine* e, const StepArgs& a, int M, int max_len, int max_b
   // czc_generate_rows_draw: the draw belongs to the combine that writes back -- the only one here, the final one of the refine engine
   if (!e->refine) { ca.draw_rows = e->draw_rows; ca.draw_step = e->draw_step; }
   E_CHECK(ensure(e, "s_nonfinite", 32, (void**)&ca.nonfinite));
+  if (e->rival_rows) {  // czc_generate_rows_vs (never on the refine engine: refused by the entry point)
+    if (e->refine) return fail(e, CZC_ERR_STATE, "step: rivals on the screen-then-refine engine%s");
+    ca.rival_idx = e->rival_rows; ca.M = e->rival_M; ca.rival_delta = e->rival_delta; ca.img_all = e->rival_img_all; ca.n_img = e->rival_n_img;
+    E_CHECK(ensure(e, "s_disc", (size_t)n_seq * 4, (void**)&ca.disc));
+  }
   if (!e->refine) {
     ProfScope ps(e, "combine", 0);
     E_CHECK(launch_combine(ca, e->st));
@@ -1121,6 +1132,7 @@ struct MemoRowsPlan {
   float *bcos = nullptr, *img_c = nullptr;
   RowHyper* hp_c = nullptr;      // czc_generate_rows_hp: the records of a compact batch's rows, gathered by its run list
   RowDraw* draw_c = nullptr;     // czc_generate_rows_draw: their draw records, by the same list
+  int* riv_c = nullptr; float* rdelta_c = nullptr;  // czc_generate_rows_vs: their rival tables and deltas, by the same list
   std::vector<std::vector<int32_t>> h_col_c;  // compact batch of the group in progress: the active rows' column at every step
   std::vector<int32_t> run_h;    // of the group in progress: the rows that run, ascending (host copy of list_d)
   const int* list_d = nullptr;   // of the group in progress: the device list of the rows that run (null: every row)
@@ -1317,10 +1329,19 @@ int memo_rows_step(czc_engine* e, MemoRowsPlan& mp, int s, int* d_inp, int R, in
     E_CHECK(launch_gather_row_draw(draw_full, mp.list_d, n_act, mp.draw_c, e->st));
     e->draw_rows = mp.draw_c;
   }
+  const int* riv_full = e->rival_rows;
+  const float* rdelta_full = e->rival_delta;
+  if (riv_full) {  // the indices point into the whole resident batch (rival_img_all), which a compact batch leaves alone
+    if (!mp.riv_c || !mp.rdelta_c || !mp.list_d) return fail(e, CZC_ERR_STATE, "generate_rows_vs: a compact batch without room for its rival tables%s");
+    E_CHECK(launch_gather_rows_w32(riv_full, mp.list_d, n_act, e->rival_M, mp.riv_c, e->st));
+    E_CHECK(launch_gather_rows_w32(rdelta_full, mp.list_d, n_act, 1, mp.rdelta_c, e->st));
+    e->rival_rows = mp.riv_c; e->rival_delta = mp.rdelta_c;
+  }
   e->d_img_n = mp.img_c; e->img_B = n_act; e->memo_branch_floor = j < MEMO_ROWS_SUB ? mp.branch_max[j] : 0;
   const int rc = step_device(e, mp.inp_c, n_act, T, col_h[0], n_mask, col_h[0] - seed_len == L - 1 ? 1 : 0, K, hp, mp.col_c, mp.dot_c,
                              col_h, mp.rag(false), mp.ctl_T());
   e->d_img_n = img_rows; e->img_B = img_B; e->memo_branch_floor = 0; e->hp_rows = hp_full; e->draw_rows = draw_full;
+  e->rival_rows = riv_full; e->rival_delta = rdelta_full;
   E_CHECK(rc);
   return launch_memo_rows_scatter(mp.inp_c, (const float*)e->ws["s_bcos"].p, (const int*)e->ws["p_img_max"].p, mp.list_d, n_act,
                                   mp.tab, col0, j, record, d_inp, mp.bcos, e->st) ? fail(e, CZC_ERR_HIP, "%s", g_err) : 0;
@@ -1330,7 +1351,10 @@ int memo_rows_step(czc_engine* e, MemoRowsPlan& mp, int s, int* d_inp, int R, in
 // img_rows [n, D] (normalised, row-gathered) -> cos [n].  The text bridge on the row itself -- the per-row form with K = 1 and
 // a candidate that repeats the id column 0 holds -- then the tower as czc_encode_text runs it (independent sequences, the
 // exact tower of the engine precision) and the steps' cosine kernel.  Buffers of its own: a step's are left alone.
-int score_rows_device(czc_engine* e, const int* d_rows, int n, int T, const int* d_len, const float* img_rows, float* d_cos) {
+// d_rival [n, M] (czc_score_rows_vs; null otherwise): indices into the resident batch; the rival cosine kernel then leaves the same
+// cosines and d_disc [n] = P(own image | row) among the row's own image and its rivals
+int score_rows_device(czc_engine* e, const int* d_rows, int n, int T, const int* d_len, const float* img_rows, float* d_cos,
+                      const int* d_rival = nullptr, int M = 0, float* d_disc = nullptr) {
   if (!e->finalized) return fail(e, CZC_ERR_STATE, "weights not finalized%s");
   if (!e->has_bridge) return fail(e, CZC_ERR_STATE, "bridge tables not set%s");
   int *gen, *cand, *cids, *clen, *totals, *flag;
@@ -1349,7 +1373,9 @@ int score_rows_device(czc_engine* e, const int* d_rows, int n, int T, const int*
   float* feat;
   E_CHECK(clip_text_forward(e, cids, clen, n, 1, 0, totals, &feat, true));  // (reads the bridge's overflow flag with the sizes)
   { ProfScope ps(e, "combine", 0);
-    E_CHECK(launch_cosine(feat, img_rows, n, 1, e->cfg.clip_proj, d_cos, flag, e->st)); }
+    if (d_rival) E_CHECK(launch_cosine_rival(feat, img_rows, n, 1, e->cfg.clip_proj, d_rival, M, e->d_img_n, e->img_B, e->logit_scale_exp, d_cos,
+                                             d_disc, flag, e->st));
+    else E_CHECK(launch_cosine(feat, img_rows, n, 1, e->cfg.clip_proj, d_cos, flag, e->st)); }
   return 0;
 }
 
@@ -1404,7 +1430,7 @@ int tie_score(czc_engine* e, const TiePlan& tp, const int* d_inp, int R, int T, 
 // =================================================================================================
 extern "C" {
 
-int czc_version(void) { return 105; }
+int czc_version(void) { return 106; }
 
 const char* czc_last_error(const czc_engine* e) { return e ? e->err : czc::g_err; }
 
@@ -2133,6 +2159,8 @@ static int generate_impl(czc_engine* e, bool rows, bool from, int B, int T, int 
   int *d_inp, *d_row, *d_sched = nullptr;
   RowHyper* d_hp_rows = nullptr;
   RowDraw* d_draw_rows = nullptr;
+  int* d_rival = nullptr; float* d_rdelta = nullptr;
+  if (e->vs_host && !(rows && from && hp_rows_host && draw_host)) return fail(e, CZC_ERR_ARG, "generate: a rival table belongs to a rows call with per-row records%s");
   if (draw_host && !rows) return fail(e, CZC_ERR_ARG, "generate: draw records belong to a rows call%s");
   if (group_host && !(rows && from)) return fail(e, CZC_ERR_ARG, "generate: a group table belongs to a rows call with start rows%s");
   { int* flag; E_CHECK(ensure(e, "s_nonfinite", 32, (void**)&flag)); E_HIP(hipMemsetAsync(flag, 0, 32, e->st)); }
@@ -2170,6 +2198,12 @@ static int generate_impl(czc_engine* e, bool rows, bool from, int B, int T, int 
                     "RowDraw is czc_draw as the kernels read it (little-endian seed halves)");
       E_CHECK(ensure(e, "g_draw_rows", (size_t)B * sizeof(RowDraw), (void**)&d_draw_rows));
       E_HIP(hipMemcpyAsync(d_draw_rows, draw_host, (size_t)B * sizeof(RowDraw), hipMemcpyHostToDevice, e->st));
+    }
+    if (e->vs_host) {  // czc_generate_rows_vs (its checks have run): the [R, M] table and the [R] deltas, once, with the schedule
+      E_CHECK(ensure(e, "g_rival", (size_t)B * e->vs_M * 4, (void**)&d_rival));
+      E_CHECK(ensure(e, "g_rdelta", (size_t)B * 4, (void**)&d_rdelta));
+      E_HIP(hipMemcpyAsync(d_rival, e->vs_host, (size_t)B * e->vs_M * 4, hipMemcpyHostToDevice, e->st));
+      E_HIP(hipMemcpyAsync(d_rdelta, e->vs_delta_host, (size_t)B * 4, hipMemcpyHostToDevice, e->st));
     }
     if (image_of_row_host) {
       E_HIP(hipMemcpyAsync(d_ior, image_of_row_host, (size_t)B * 4, hipMemcpyHostToDevice, e->st));
@@ -2216,6 +2250,9 @@ static int generate_impl(czc_engine* e, bool rows, bool from, int B, int T, int 
   if (memo_rows && d_draw_rows && !rc && ensure(e, "mr_draw_c", (size_t)B * sizeof(RowDraw), (void**)&mrp.draw_c)) rc = CZC_ERR_HIP;
   e->hp_rows = rc ? nullptr : d_hp_rows;  // (handed back with the image batch below)
   e->draw_rows = rc ? nullptr : d_draw_rows;
+  if (memo_rows && d_rival && !rc && (ensure(e, "mr_riv_c", (size_t)B * e->vs_M * 4, (void**)&mrp.riv_c) ||
+                                      ensure(e, "mr_rdelta_c", (size_t)B * 4, (void**)&mrp.rdelta_c))) rc = CZC_ERR_HIP;
+  if (d_rival && !rc) { e->rival_rows = d_rival; e->rival_delta = d_rdelta; e->rival_M = e->vs_M; e->rival_img_all = img_full; e->rival_n_img = img_B; }
   // czc_generate_rows_tied (its checks have run): the group table goes up once, behind the schedule
   TiePlan tie;
   const bool tied = group_host != nullptr && n_steps > 0;
@@ -2256,6 +2293,7 @@ static int generate_impl(czc_engine* e, bool rows, bool from, int B, int T, int 
   }
   // rows: the resident image batch comes back whatever happened, and no later call may re-use a forward by this call's columns
   e->d_img_n = img_full; e->img_B = img_B; e->hp_rows = nullptr; e->draw_rows = nullptr; e->draw_step = 0;
+  e->rival_rows = nullptr; e->rival_delta = nullptr; e->rival_M = 0; e->rival_img_all = nullptr; e->rival_n_img = 0;
   if (rows) { e->bert_pruned_rows = nullptr; if (rc) (void)hipStreamSynchronize(e->st); }
   if (rc) return rc;
   E_HIP(hipMemcpyAsync(e->h_totals + 9, e->ws["s_nonfinite"].p, 24, hipMemcpyDeviceToHost, e->st));
@@ -2356,7 +2394,7 @@ static int rows_hp_impl(czc_engine* e, int R, int T, int seed_len, const int32_t
       return fail(e, CZC_ERR_STATE, "POS path needs czc_set_pos or czc_set_control_callback%s");
   }
   // equal entries: the existing call, bit for bit (its scalar kernels)
-  const czc_hyper* rows_hp = uniform ? nullptr : hp_of_row_host;
+  const czc_hyper* rows_hp = uniform && !e->vs_host ? nullptr : hp_of_row_host;  // (a rival call always carries its records)
   if (len_of_row_host)
     return rows_len_impl(e, R, T, seed_len, init_rows_host, len_of_row_host, image_of_row_host, top_k, n_steps, positions_host, n_mask_host,
                          snapshot_every, &hp_of_row_host[0], out_ids, out_cos, rows_hp, draw_host, group_host);
@@ -2388,7 +2426,7 @@ static int rows_draw_impl(czc_engine* e, int R, int T, int seed_len, const int32
   }
   // no row draws: czc_generate_rows_hp itself, bit for bit
   return rows_hp_impl(e, R, T, seed_len, init_rows_host, len_of_row_host, image_of_row_host, top_k, n_steps, positions_host, n_mask_host,
-                      snapshot_every, hp_of_row_host, out_ids, out_cos, any ? draw_of_row_host : nullptr, group_host);
+                      snapshot_every, hp_of_row_host, out_ids, out_cos, any || (e->vs_host && draw_of_row_host) ? draw_of_row_host : nullptr, group_host);
 }
 
 int czc_generate_rows_draw(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
@@ -2438,9 +2476,82 @@ int czc_generate_rows_tied(czc_engine* e, int R, int T, int seed_len, const int3
                         snapshot_every, hp_of_row_host, draw_of_row_host, out_ids, out_cos, group_of_row_host);
 }
 
+// the checks of a rival table, shared by czc_generate_rows_vs and czc_score_rows_vs (image_of_row and R are checked by then);
+// *active: some row has a filled slot (and, with deltas, a delta != 0)
+static int check_rivals(czc_engine* e, const char* who, int R, const int32_t* image_of_row_host, const int32_t* rival, int M,
+                        const float* delta, bool* active) {
+  static_assert(czc::CB_MAX_RIVALS == CZC_MAX_RIVALS, "the kernels' rival slots are the header's");
+  *active = false;
+  if (M < 1 || M > CZC_MAX_RIVALS) return fail(e, CZC_ERR_ARG, "%s: M outside [1, CZC_MAX_RIVALS]", who);
+  if ((size_t)e->cfg.clip_proj * CZC_MAX_RIVALS * 4 > (size_t)czc::CB_RIVAL_FLOATS * 4)
+    return fail(e, CZC_ERR_ARG, "%s: clip_proj * CZC_MAX_RIVALS * 4 exceeds the rival kernel's LDS array (32 KB)", who);
+  for (int r = 0; r < R; ++r) {
+    if (delta && !std::isfinite(delta[r])) return fail(e, CZC_ERR_ARG, "%s: a delta must be finite", who);
+    const int own = image_of_row_host ? image_of_row_host[r] : r;
+    bool empty = false;
+    for (int j = 0; j < M; ++j) {
+      const int v = rival[(size_t)r * M + j];
+      if (v < -1 || v >= e->img_B) return fail(e, CZC_ERR_ARG, "%s: a rival index outside [-1, resident image batch)", who);
+      if (v == -1) { empty = true; continue; }
+      if (empty) return fail(e, CZC_ERR_ARG, "%s: a filled rival slot behind an empty one (the filled slots come first)", who);
+      if (v == own) return fail(e, CZC_ERR_ARG, "%s: a rival equal to the row's own image", who);
+    }
+    if (rival[(size_t)r * M] >= 0 && (!delta || delta[r] != 0.f)) *active = true;
+  }
+  return 0;
+}
+
+int czc_generate_rows_vs(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
+                         const int32_t* image_of_row_host, const int32_t* group_of_row_host, int top_k, int n_steps,
+                         const int32_t* positions_host, const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp_of_row_host,
+                         const czc_draw* draw_of_row_host, const int32_t* rival_of_row_host, int M, const float* delta_of_row_host,
+                         int32_t* out_ids, float* out_cos) {
+  bool active = false;
+  if (rival_of_row_host) {
+    if (!e || R <= 0 || !delta_of_row_host) return CZC_ERR_ARG;
+    e->err[0] = 0;
+    if (R > CZC_MAX_ROWS) return fail(e, CZC_ERR_ARG, "generate_rows_vs: R > CZC_MAX_ROWS%s");
+    if (!e->d_img_n || e->img_B <= 0) return fail(e, CZC_ERR_STATE, "image embeds not set%s");
+    if (!image_of_row_host && e->img_B != R) return fail(e, CZC_ERR_ARG, "generate_rows_vs: image_of_row = NULL needs R equal to the resident image batch%s");
+    for (int r = 0; r < R && image_of_row_host; ++r)
+      if (image_of_row_host[r] < 0 || image_of_row_host[r] >= e->img_B)
+        return fail(e, CZC_ERR_ARG, "generate_rows_vs: image_of_row outside the resident image batch%s");
+    E_CHECK(check_rivals(e, "generate_rows_vs", R, image_of_row_host, rival_of_row_host, M, delta_of_row_host, &active));
+  }
+  // no row has both a rival and a delta: czc_generate_rows_tied itself, bit for bit
+  if (!active)
+    return czc_generate_rows_tied(e, R, T, seed_len, init_rows_host, len_of_row_host, image_of_row_host, group_of_row_host, top_k, n_steps,
+                                  positions_host, n_mask_host, snapshot_every, hp_of_row_host, draw_of_row_host, out_ids, out_cos);
+  if (e->refine)
+    return fail(e, CZC_ERR_STATE, "generate_rows_vs: the selection and guard bounds of CZC_PREC_REFINE were derived for the softmax-K term alone; "
+                                  "run rows with rivals on a CZC_PREC_SPLIT engine%s");
+  // the rival path always carries per-row records: rows without a draw record keep the first argmax (tau = 0)
+  std::vector<czc_draw> no_draw;
+  if (!draw_of_row_host) { no_draw.assign((size_t)R, czc_draw{0, 0.f, 0}); draw_of_row_host = no_draw.data(); }
+  e->vs_host = rival_of_row_host; e->vs_delta_host = delta_of_row_host; e->vs_M = M;
+  const int rc = czc_generate_rows_tied(e, R, T, seed_len, init_rows_host, len_of_row_host, image_of_row_host, group_of_row_host, top_k, n_steps,
+                                        positions_host, n_mask_host, snapshot_every, hp_of_row_host, draw_of_row_host, out_ids, out_cos);
+  e->vs_host = nullptr; e->vs_delta_host = nullptr; e->vs_M = 0;
+  return rc;
+}
+
+static int score_rows_impl(czc_engine* e, const char* who, const int32_t* rows, int R, int T, int seed_len, const int32_t* len_of_row_host,
+                           const int32_t* image_of_row_host, const int32_t* rival_of_row_host, int M, float* out_cos, float* out_disc);
+
 int czc_score_rows(czc_engine* e, const int32_t* rows, int R, int T, int seed_len, const int32_t* len_of_row_host,
                    const int32_t* image_of_row_host, float* out_cos) {
-  if (!e || !rows || !out_cos || R <= 0) return CZC_ERR_ARG;
+  if (!out_cos) return CZC_ERR_ARG;
+  return score_rows_impl(e, "score_rows", rows, R, T, seed_len, len_of_row_host, image_of_row_host, nullptr, 0, out_cos, nullptr);
+}
+
+int czc_score_rows_vs(czc_engine* e, const int32_t* rows, int R, int T, int seed_len, const int32_t* len_of_row_host,
+                      const int32_t* image_of_row_host, const int32_t* rival_of_row_host, int M, float* out_cos, float* out_disc) {
+  return score_rows_impl(e, "score_rows_vs", rows, R, T, seed_len, len_of_row_host, image_of_row_host, rival_of_row_host, M, out_cos, out_disc);
+}
+
+static int score_rows_impl(czc_engine* e, const char* who, const int32_t* rows, int R, int T, int seed_len, const int32_t* len_of_row_host,
+                           const int32_t* image_of_row_host, const int32_t* rival_of_row_host, int M, float* out_cos, float* out_disc) {
+  if (!e || !rows || R <= 0) return CZC_ERR_ARG;
   E_HIP(hipSetDevice(e->dev));
   e->err[0] = 0;
   if (R > CZC_MAX_ROWS || seed_len < 0 || T <= 0 || T > CZC_MAX_BERT_LEN) return fail(e, CZC_ERR_ARG, "score_rows: R > CZC_MAX_ROWS, seed_len < 0 or T outside [1, CZC_MAX_BERT_LEN]%s");
@@ -2454,6 +2565,8 @@ int czc_score_rows(czc_engine* e, const int32_t* rows, int R, int T, int seed_le
     if (len_of_row_host && (len_of_row_host[r] < 1 || len_of_row_host[r] > T - seed_len - 1))
       return fail(e, CZC_ERR_ARG, "score_rows: len_of_row outside [1, T - seed_len - 1]%s");
   }
+  bool any_rival = false;
+  if (rival_of_row_host) E_CHECK(check_rivals(e, who, R, image_of_row_host, rival_of_row_host, M, nullptr, &any_rival));
   const size_t n = (size_t)R * T;
   std::vector<int32_t> host;
   const int32_t* h = rows;
@@ -2489,8 +2602,17 @@ int czc_score_rows(czc_engine* e, const int32_t* rows, int R, int T, int seed_le
     E_HIP(hipMemcpyAsync(d_ior, image_of_row_host, (size_t)R * 4, hipMemcpyHostToDevice, e->st));
     E_CHECK(launch_gather_rows_f32(e->d_img_n, d_ior, R, D, img_r, e->st));
   }
-  E_CHECK(score_rows_device(e, d_rows, R, T, d_len, img_r, d_cos));  // (its size read waits for the pageable uploads above)
-  E_HIP(hipMemcpyAsync(out_cos, d_cos, (size_t)R * 4, hipMemcpyDefault, e->st));
+  int* d_rival = nullptr; float* d_disc = nullptr;
+  if (rival_of_row_host) {
+    E_CHECK(ensure(e, "sc_rival", (size_t)R * M * 4, (void**)&d_rival));
+    E_CHECK(ensure(e, "sc_disc", (size_t)R * 4, (void**)&d_disc));
+    E_HIP(hipMemcpyAsync(d_rival, rival_of_row_host, (size_t)R * M * 4, hipMemcpyHostToDevice, e->st));
+  }
+  E_CHECK(score_rows_device(e, d_rows, R, T, d_len, img_r, d_cos, d_rival, M, d_disc));  // (its size read waits for the pageable uploads above)
+  if (out_cos) E_HIP(hipMemcpyAsync(out_cos, d_cos, (size_t)R * 4, hipMemcpyDefault, e->st));
+  if (out_disc && d_disc) E_HIP(hipMemcpyAsync(out_disc, d_disc, (size_t)R * 4, hipMemcpyDefault, e->st));
+  if (out_disc && !d_disc)
+    for (int r = 0; r < R; ++r) out_disc[r] = 1.0f;  // no table: no row has a rival
   E_HIP(hipMemcpyAsync(e->h_totals + 9, e->ws["s_nonfinite"].p, 4, hipMemcpyDeviceToHost, e->st));
   E_HIP(hipStreamSynchronize(e->st));
   if (e->h_totals[9]) return fail(e, CZC_ERR_OVERFLOW, "non-finite CLIP cosine: an fp16 quantity overflowed in a tower (fp16 residual rows: set option resid16 = 0 on the bf16 engine, refine_rows16 = 0 on the refine engine; fp16 operands: use CZC_PREC_SPLIT)%s");

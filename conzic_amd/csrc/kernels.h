@@ -336,9 +336,25 @@ struct CombineArgs {
   // of combine.hip at step counter draw_rows[b].step0 + draw_step (device, [B]; needs gen_rows); null = first argmax
   const RowDraw* draw_rows = nullptr;
   unsigned draw_step = 0;
+  // czc_generate_rows_vs: row b is also scored against the rival images rival_idx[b * M + j] (device, [B, M]; indices into
+  // img_all, the whole normalised resident batch of n_img images [n_img, D]; -1 = empty slot, filled slots first).
+  // disc [B*K] (device) receives P(own image | candidate) over {own} + rivals, and a row with rival_delta[b] != 0 and a filled
+  // slot adds rival_delta[b] * disc to its fused score.  Needs gen_rows, hp_rows, draw_rows and text_feat; null = no rivals
+  const int* rival_idx = nullptr;
+  int M = 0;
+  const float* rival_delta = nullptr;  // [B]
+  const float* img_all = nullptr;
+  int n_img = 0;
+  float* disc = nullptr;
 };
+constexpr int CB_MAX_RIVALS = 16;       // CZC_MAX_RIVALS
+constexpr int CB_RIVAL_FLOATS = 8192;   // the rival kernel's LDS array: D * CB_MAX_RIVALS floats at D = 512
 // text_feat == null: clip_ref already holds the cosines
 int launch_combine(const CombineArgs& a, hipStream_t st);
+// the rival cosine kernel of launch_combine on its own (czc_score_rows_vs): cos_out as launch_cosine gives it, bit for bit, and
+// disc [B*K] (1 for a row without a filled slot).  D * CB_MAX_RIVALS <= CB_RIVAL_FLOATS, M in [1, CB_MAX_RIVALS]
+int launch_cosine_rival(const float* text_feat, const float* img_n, int B, int K, int D, const int* rival_idx, int M, const float* img_all,
+                        int n_img, float logit_scale_exp, float* cos_out, float* disc, int* nonfinite, hipStream_t st);
 // the cosine kernel of launch_combine on its own: cos_out[b * K + k] = normalised text_feat[b * K + k] . img_n[b]
 int launch_cosine(const float* text_feat, const float* img_n, int B, int K, int D, float* cos_out, int* nonfinite, hipStream_t st);
 // screen-then-refine engine (combine.hip): choose the candidates to re-encode / cosines of the re-encoded rows
@@ -378,7 +394,7 @@ int launch_index_search(const split_t* index, int n, int D, const split_t* queri
 // ---- czc_internal_hooks (declared below, private to the build): what libconzic_hip_test.so may reach inside this library -----------
 // The product library has hidden visibility; the hook library (api_test.hip) gets the launchers it wraps and the
 // process-wide kernel-family switches it flips through this table instead of through exported C++ symbols.
-constexpr int HOOKS_ABI = 0x0605;
+constexpr int HOOKS_ABI = 0x0606;
 struct Hooks {
   char* (*err_buf)();  // the calling host thread's g_err [512]
   decltype(&launch_gemm) gemm;

@@ -96,7 +96,34 @@ def get_args(argv=None):
                    help="--run_type retrieve: the retrieved captions are the drafts of a Gibbs polish of every position "
                         "(num_iterations sweeps in --order sequential or shuffle, --candidate_k, alpha / beta / temperature), all "
                         "of them rows of one engine call")
+    p.add_argument("--distinct", type=float, default=0.0, metavar="DELTA",
+                   help="discriminative captions: add DELTA x P(own image | candidate) -- the softmax over the image and its rival "
+                        "images of exp(logit_scale) x cos(candidate, image), taken at the own image -- to every candidate's fused "
+                        "score, so that the caption says what tells this image from its look-alikes (0 = off); combines with "
+                        "--batch_samples, --sample_tau and --run_type controllable")
+    p.add_argument("--distinct_rivals", type=int, default=4, metavar="M",
+                   help="--distinct: the rivals of an image are its M nearest others (image-image cosine) in its batch (1..16)")
+    p.add_argument("--rival_images", type=lambda v: [f.strip() for f in v.split(",") if f.strip()], default=None, metavar="a.jpg,b.jpg",
+                   help="demo_cli with --distinct: images that are rivals only (not captioned); every captioned image is scored "
+                        "against all of them instead of against its batch neighbours")
     a = p.parse_args(argv)
+    if not (a.distinct == a.distinct) or a.distinct in (float("inf"), float("-inf")):
+        p.error("--distinct must be finite")
+    if a.distinct:
+        if not 1 <= a.distinct_rivals <= 16:
+            p.error("--distinct_rivals must be between 1 and 16")
+        if a.rival_images is not None and not 1 <= len(a.rival_images) <= 16:
+            p.error("--rival_images takes between 1 and 16 files")
+        if a.run_type in ("infill", "retrieve"):
+            p.error(f"--distinct does not combine with --run_type {a.run_type} (the engine call supports rivals there; the "
+                    "command-line plumbing does not yet)")
+        for flag, on in (("--sentence_lens", a.sentence_lens is not None), ("--signals", a.signals is not None),
+                         ("--block_width", a.block_width != 1)):
+            if on:
+                p.error(f"--distinct does not combine with {flag} (the engine call supports rivals there; the command-line "
+                        "plumbing does not yet)")
+    elif a.rival_images is not None:
+        p.error("--rival_images belongs to --distinct")
     if not (a.sample_tau >= 0.0) or a.sample_tau == float("inf"):
         p.error("--sample_tau must be finite and >= 0")
     if a.sample_tau and a.run_type == "retrieve":
@@ -204,6 +231,14 @@ def main(argv=None):
         images = [Image.open(args.caption_img_path).convert("RGB")]
     image_instance = images if args.batch_size > 1 else images[0]
     img_name = [f"img{j}" for j in range(args.batch_size)]
+    rivals = args.distinct_rivals if args.distinct else None
+    if args.distinct and args.rival_images:
+        # the rival images ride behind the captioned ones in the resident batch; every captioned image is scored against all of them
+        B, E = args.batch_size, len(args.rival_images)
+        image_instance = list(images) + [Image.open(f).convert("RGB") for f in args.rival_images]
+        rivals = np.tile(np.arange(B, B + E, dtype=np.int32), (B, 1))
+    elif args.distinct and args.batch_size < 2:
+        raise SystemExit("--distinct needs rival images: --rival_images a.jpg,b.jpg, or a batch of at least two images")
     t0 = time.time()
     if args.run_type == "retrieve":
         from conzic_amd.retrieval import index_from_args
@@ -276,13 +311,14 @@ def main(argv=None):
             log_distinct(logger, img_name, finals)
         logger.info("total %.2fs" % (time.time() - t0))
         return finals
-    if args.batch_samples or args.sample_tau:
-        # one engine call for all samples, or -- the serial loop under --sample_tau -- one per sample with that sample's seeds
+    if args.batch_samples or args.sample_tau or args.distinct:
+        # one engine call for all samples, or -- the serial loop under --sample_tau / --distinct -- one per sample with that sample's seeds
         from conzic_amd.runtime import caption_samples
         kw = dict(prompt=args.prompt, batch_size=args.batch_size, max_len=args.sentence_len, top_k=args.candidate_k,
                   temperature=args.lm_temperature, max_iter=args.num_iterations, alpha=args.alpha, beta=args.beta,
                   generate_order=args.order, gamma=args.gamma, ctl_type=args.control_type,
-                  style_type=args.sentiment_type, pos_type=args.pos_type, sample_tau=args.sample_tau, sample_seed=args.seed)
+                  style_type=args.sentiment_type, pos_type=args.pos_type, sample_tau=args.sample_tau, sample_seed=args.seed,
+                  rivals=rivals, delta=args.distinct)
         for sample_id in ([None] if args.batch_samples else range(args.samples_num)):
             outs = caption_samples(args.samples_num if sample_id is None else 1, args.run_type, img_name, lm_model, clip, lm_tokenizer,
                                    image_instance, token_mask, logger, sample0=sample_id or 0, **kw)

@@ -618,10 +618,96 @@ class Engine:
                                          None if ior is None else ior.ctypes.data, out.ctypes.data), "czc_score_rows")
         return out
 
+    @staticmethod
+    def _rival_table(what: str, rivals, R: int):
+        """int32 [R, M] from `rivals` (None passes through)."""
+        if rivals is None:
+            return None
+        rv = np.ascontiguousarray(rivals, dtype=np.int32)
+        if rv.ndim != 2 or rv.shape[0] != R or rv.shape[1] < 1:
+            raise ValueError(f"{what}: rivals must be [R, M] with R = {R} and M >= 1, got {rv.shape}")
+        return rv
+
+    def generate_rows_vs(self, init_rows, lens, seed_len: int, top_k: int, positions, hypers: Sequence[native.Hyper],
+                         draws: Optional[Sequence[native.Draw]], groups: Optional[Sequence[int]], rivals, deltas,
+                         image_of_row: Optional[Sequence[int]] = None, n_mask: Optional[Sequence[int]] = None,
+                         snapshot_every: Optional[int] = None, want_cos: bool = True):
+        """czc_generate_rows_vs: generate_rows_tied with rival images per row.  `rivals` int [R, M] (indices into the resident
+        image batch, -1 = empty slot, filled slots first; None: generate_rows_tied itself) and `deltas` float [R]: row r adds
+        deltas[r] * P(own image | candidate, among own image and rivals) to every candidate's fused score.  `n_mask` (span
+        order) only without groups.  Returns (ids int32 [S,R,T], cos fp32 [S,R]) per snapshot."""
+        init = np.ascontiguousarray(init_rows, dtype=np.int32)
+        pos = np.ascontiguousarray(positions, dtype=np.int32)
+        if pos.ndim != 2 or pos.shape[1] < 1:
+            raise ValueError("generate_rows_vs: positions must be [n_steps, R]")
+        n_steps, R = pos.shape
+        if init.ndim != 2 or init.shape[0] != R or init.shape[1] < 1:
+            raise ValueError(f"generate_rows_vs: init_rows must be [R, T] with R = {R}, got {init.shape}")
+        T = init.shape[1]
+        ln = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32).reshape(-1)
+        if ln is not None and ln.size != R:
+            raise ValueError(f"generate_rows_vs: lens has {ln.size} entries for {R} rows")
+        hp = hyper_array(hypers)
+        if len(hp) != R:
+            raise ValueError(f"generate_rows_vs: hypers has {len(hp)} entries for {R} rows")
+        dr = None if draws is None else draw_array(draws)
+        if dr is not None and len(dr) != R:
+            raise ValueError(f"generate_rows_vs: draws has {len(dr)} entries for {R} rows")
+        gr = None if groups is None else np.ascontiguousarray(groups, dtype=np.int32).reshape(-1)
+        if gr is not None and gr.size != R:
+            raise ValueError(f"generate_rows_vs: groups has {gr.size} entries for {R} rows")
+        ior = None if image_of_row is None else np.ascontiguousarray(image_of_row, dtype=np.int32).reshape(-1)
+        if ior is not None and ior.size != R:
+            raise ValueError(f"generate_rows_vs: image_of_row has {ior.size} entries for {R} rows")
+        rv = self._rival_table("generate_rows_vs", rivals, R)
+        dl = np.zeros((R,), np.float32) if deltas is None else np.ascontiguousarray(deltas, dtype=np.float32).reshape(-1)
+        if dl.size != R:
+            raise ValueError(f"generate_rows_vs: deltas has {dl.size} entries for {R} rows")
+        nm = None if n_mask is None else np.ascontiguousarray(n_mask, dtype=np.int32).reshape(-1)
+        if nm is not None and nm.size != n_steps:
+            raise ValueError(f"generate_rows_vs: n_mask has {nm.size} entries for {n_steps} steps")
+        every = snapshot_every or max(int(ln.max()) if ln is not None else T - seed_len - 1, 1)
+        S = n_steps // every
+        ids = np.empty((S, R, T), dtype=np.int32)
+        cos = np.empty((S, R), dtype=np.float32) if want_cos else None
+        rc = self.lib.czc_generate_rows_vs(self.h, R, T, seed_len, init.ctypes.data, None if ln is None else ln.ctypes.data,
+                                           None if ior is None else ior.ctypes.data, None if gr is None else gr.ctypes.data,
+                                           top_k, n_steps, pos.ctypes.data, None if nm is None else nm.ctypes.data, every, hp, dr,
+                                           None if rv is None else rv.ctypes.data, 0 if rv is None else int(rv.shape[1]),
+                                           dl.ctypes.data, ids.ctypes.data, None if cos is None else cos.ctypes.data)
+        if rc:
+            self._raise_scorer_error()
+        self._ck(rc, "czc_generate_rows_vs")
+        return ids, cos
+
+    def score_rows_vs(self, rows, seed_len: int, rivals, lens: Optional[Sequence[int]] = None,
+                      image_of_row: Optional[Sequence[int]] = None):
+        """czc_score_rows_vs: (cos fp32 [R], disc fp32 [R]) of BERT-id `rows` int [R, T]: score_rows' cosine, bit for bit, and
+        P(own image | row) among the row's own image and its `rivals` (int [R, M], -1 = empty; None: disc is 1 everywhere)."""
+        r = np.ascontiguousarray(rows, dtype=np.int32)
+        if r.ndim != 2 or r.shape[0] < 1 or r.shape[1] < 1:
+            raise ValueError(f"score_rows_vs: rows must be [R, T], got {tuple(r.shape)}")
+        R, T = int(r.shape[0]), int(r.shape[1])
+        ln = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32).reshape(-1)
+        if ln is not None and ln.size != R:
+            raise ValueError(f"score_rows_vs: lens has {ln.size} entries for {R} rows")
+        ior = None if image_of_row is None else np.ascontiguousarray(image_of_row, dtype=np.int32).reshape(-1)
+        if ior is not None and ior.size != R:
+            raise ValueError(f"score_rows_vs: image_of_row has {ior.size} entries for {R} rows")
+        rv = self._rival_table("score_rows_vs", rivals, R)
+        cos, disc = np.empty((R,), dtype=np.float32), np.empty((R,), dtype=np.float32)
+        self._ck(self.lib.czc_score_rows_vs(self.h, r.ctypes.data, R, T, seed_len, None if ln is None else ln.ctypes.data,
+                                            None if ior is None else ior.ctypes.data, None if rv is None else rv.ctypes.data,
+                                            0 if rv is None else int(rv.shape[1]), cos.ctypes.data, disc.ctypes.data),
+                 "czc_score_rows_vs")
+        return cos, disc
+
     def similarity(self, image_embeds, text_embeds, K: int):
         """clip/clip.py:86-98: (softmax_K(cos * exp(logit_scale)), cos), both [B, K], from un-normalised embeddings."""
         ie = np.ascontiguousarray(image_embeds, np.float32)
         te = np.ascontiguousarray(text_embeds, np.float32)
+        if ie.ndim != 2 or te.ndim != 2 or ie.shape[1] != self.clip_cfg.proj or te.shape[1] != self.clip_cfg.proj:
+            raise ValueError(f"similarity: embeddings must be [*, {self.clip_cfg.proj}], got {ie.shape} and {te.shape}")
         B = ie.shape[0]
         assert te.shape == (B * K, ie.shape[1]), (te.shape, ie.shape, K)
         cs, cr = np.empty((B, K), np.float32), np.empty((B, K), np.float32)
@@ -1040,6 +1126,68 @@ class EngineGroup:
                 init[rows], None if ln is None else ln[rows], seed_len, top_k, np.ascontiguousarray(pos[:, rows]),
                 [hps[r] for r in rows], None if drs is None else [drs[r] for r in rows], grp_c.astype(np.int32),
                 image_of_row=img_c.astype(np.int32), snapshot_every=every, want_cos=want_cos))
+        self._full_embeds, self._resident = embeds, None
+        outs = self._run(jobs)
+        S = outs[0][0].shape[0]
+        ids = np.empty((S, R, init.shape[1]), dtype=np.int32)
+        cos = np.empty((S, R), dtype=np.float32) if want_cos else None
+        for rows, (i, c) in zip(parts, outs):
+            ids[:, rows] = i
+            if want_cos:
+                cos[:, rows] = c
+        return ids, cos
+
+    def generate_rows_vs(self, init_rows, lens, seed_len: int, top_k: int, positions, hypers, draws, groups, rivals, deltas,
+                         image_of_row=None, n_mask=None, snapshot_every=None, want_cos: bool = True):
+        """Engine.generate_rows_vs with the rows split over the streams (on group boundaries where `groups` is given).  A rival
+        may be any image of the batch, so every member holds the WHOLE resident batch and gets `image_of_row` and the rival
+        indices unchanged -- unlike generate_rows, which deals out per-row embeddings.  The normalisation is per row, so a
+        row's own embedding has the bits it has there."""
+        if rivals is None and groups is None:
+            return self.generate_rows_draw(init_rows, lens, seed_len, top_k, positions, hypers, draws, image_of_row=image_of_row,
+                                           n_mask=n_mask, snapshot_every=snapshot_every, want_cos=want_cos)
+        if rivals is None:
+            return self.generate_rows_tied(init_rows, lens, seed_len, top_k, positions, hypers, draws, groups, image_of_row=image_of_row,
+                                           snapshot_every=snapshot_every, want_cos=want_cos)
+        pos = np.ascontiguousarray(positions, dtype=np.int32)
+        init = np.ascontiguousarray(init_rows, dtype=np.int32)
+        ln = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32).reshape(-1)
+        if pos.ndim != 2:
+            raise ValueError("generate_rows_vs: positions must be [n_steps, R]")
+        R = pos.shape[1]
+        if init.ndim != 2 or init.shape[0] != R:
+            raise ValueError(f"generate_rows_vs: init_rows must be [R, T] with R = {R}, got {init.shape}")
+        if ln is not None and ln.size != R:
+            raise ValueError(f"generate_rows_vs: lens has {ln.size} entries for {R} rows")
+        hps = list(hypers)
+        if len(hps) != R:
+            raise ValueError(f"generate_rows_vs: hypers has {len(hps)} entries for {R} rows")
+        drs = None if draws is None else list(draws)
+        if drs is not None and len(drs) != R:
+            raise ValueError(f"generate_rows_vs: draws has {len(drs)} entries for {R} rows")
+        gr = None if groups is None else np.asarray(groups, dtype=np.int64).reshape(-1)
+        if gr is not None and (gr.size != R or (R and (gr.min() < 0 or gr.max() >= R))):
+            raise NativeError("EngineGroup.generate_rows_vs: groups must hold R ids in [0, R)", code=native.ERR_ARG)
+        rv = Engine._rival_table("generate_rows_vs", rivals, R)
+        dl = np.zeros((R,), np.float32) if deltas is None else np.ascontiguousarray(deltas, dtype=np.float32).reshape(-1)
+        if dl.size != R:
+            raise ValueError(f"generate_rows_vs: deltas has {dl.size} entries for {R} rows")
+        embeds = self._full_embeds if self._full_embeds is not None else self._encoded
+        if embeds is None:
+            raise NativeError("EngineGroup.generate_rows_vs: encode_images / set_image_embeds first")
+        ior = np.arange(R) if image_of_row is None else np.asarray(image_of_row, dtype=np.int64).reshape(-1)
+        if ior.size != R or (R and (ior.min() < 0 or ior.max() >= embeds.shape[0])):
+            raise NativeError("EngineGroup.generate_rows_vs: image_of_row outside the resident image batch", code=native.ERR_ARG)
+        every = snapshot_every or max(int(ln.max()) if ln is not None else init.shape[1] - seed_len - 1, 1)
+        parts = self.tied_parts(gr) if gr is not None else [np.arange(lo, hi) for lo, hi in self.parts(R)]
+        jobs = []
+        for e, rows in zip(self.engines, parts):
+            grp_c = None if gr is None else np.unique(gr[rows], return_inverse=True)[1].astype(np.int32)
+            e.set_image_embeds(embeds)   # the whole batch: the rival indices are the caller's
+            jobs.append(lambda e=e, rows=rows, grp_c=grp_c: e.generate_rows_vs(
+                init[rows], None if ln is None else ln[rows], seed_len, top_k, np.ascontiguousarray(pos[:, rows]),
+                [hps[r] for r in rows], None if drs is None else [drs[r] for r in rows], grp_c, rv[rows], dl[rows],
+                image_of_row=ior[rows].astype(np.int32), n_mask=n_mask, snapshot_every=every, want_cos=want_cos))
         self._full_embeds, self._resident = embeds, None
         outs = self._run(jobs)
         S = outs[0][0].shape[0]

@@ -27,6 +27,7 @@ PREC_FP16 = 4
 PREC_REFINE = 5
 CLIP_MAX_LEN = 77
 MAX_BERT_LEN = 64   # include/conzic_hip.h CZC_MAX_BERT_LEN: tokens of a BERT row, [CLS] and [SEP] included
+MAX_RIVALS = 16    # include/conzic_hip.h CZC_MAX_RIVALS: rival images of a row (czc_generate_rows_vs)
 INDEX_MAX_K = 64  # include/conzic_hip.h CZC_INDEX_MAX_K: the largest k of czc_index_search
 POS_IDLE = -1   # include/conzic_hip.h CZC_POS_IDLE: the row sits the step out (czc_generate_rows_from)
 
@@ -125,6 +126,9 @@ SIGNATURES = {
     "czc_generate_rows_draw": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _I, C.POINTER(Hyper), C.POINTER(Draw), _P, _P]),
     "czc_generate_rows_tied": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _I, C.POINTER(Hyper), C.POINTER(Draw), _P, _P]),
     "czc_score_rows": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
+    "czc_generate_rows_vs": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _I, C.POINTER(Hyper), C.POINTER(Draw), _P, _I, _P,
+                                  _P, _P]),
+    "czc_score_rows_vs": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P]),
     "czc_set_option": (_I, [_P, C.c_char_p, _I]),
     "czc_get_option": (_I, [_P, C.c_char_p, C.POINTER(_I)]),
     "czc_profile_enable": (_I, [_P, _I]),
@@ -167,6 +171,8 @@ TEST_SIGNATURES = {
     "czc_test_refine_plan": (_I, [_I, _I] + [_P] * 15),
     "czc_test_refine_cosine": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "czc_test_combine_refine": (_I, [_I, _I, C.c_float, _P, _P, C.POINTER(Hyper), _P, _P, C.c_float, _P, _P, _P, _P, _P, _P]),
+    "czc_test_combine_rivals": (_I, [_I, _I, _I, _P, _P, _I, _P, _P, _I, _P, C.c_float, _P, C.POINTER(Hyper), C.POINTER(Draw),
+                                     C.c_uint32, _P, _P, _P, _P, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -75,7 +75,8 @@ def batched_samples(args, run_type, all_batches, own_lo, own_hi, rank, world, im
                                temperature=args.lm_temperature, max_iter=args.num_iterations, alpha=args.alpha, beta=args.beta,
                                generate_order=args.order, gamma=args.gamma, ctl_type=args.control_type,
                                style_type=args.sentiment_type, pos_type=args.pos_type, schedules=sched,
-                               sample_tau=args.sample_tau, sample_seed=args.seed)
+                               sample_tau=args.sample_tau, sample_seed=args.seed,
+                               rivals=args.distinct_rivals if args.distinct else None, delta=args.distinct)
         if S > 1:
             from conzic_amd.diversity import log_distinct
             log_distinct(logger, name_batch, [[o[0][-2 if len(o[0]) > 1 else -1][i] for o in outs] for i in range(len(name_batch))])
@@ -359,6 +360,11 @@ def retrieve_batches(args, all_batches, own_lo, own_hi, rank, world, img_dir, lm
 
 def main(argv=None):
     args = get_args(argv)
+    if args.rival_images is not None:
+        raise SystemExit("--rival_images belongs to conzic_amd.demo_cli; here the rivals of an image are its --distinct_rivals "
+                         "nearest others in its batch")
+    if args.distinct and args.batch_size < 2:
+        raise SystemExit("--distinct needs rival images: a --batch_size of at least two")
     import logging
     import numpy as np
     from PIL import Image
@@ -457,12 +463,13 @@ def main(argv=None):
             kw = dict(prompt=args.prompt, batch_size=args.batch_size, max_len=args.sentence_len,
                       top_k=args.candidate_k, temperature=args.lm_temperature, max_iter=args.num_iterations,
                       alpha=args.alpha, beta=args.beta, generate_order=args.order)
-            if args.sample_tau:   # the sample loop under --sample_tau: this sample's seeds, one engine call per sample
+            if args.sample_tau or args.distinct:   # the sample loop under --sample_tau / --distinct: one rows call per sample
                 from conzic_amd.runtime import caption_samples
                 (gen_texts, _), = caption_samples(1, args.run_type, name_batch, lm_model, clip, lm_tokenizer, imgs, token_mask, logger,
                                                   gamma=args.gamma, ctl_type=args.control_type, style_type=args.sentiment_type,
                                                   pos_type=args.pos_type, sample_tau=args.sample_tau, sample_seed=args.seed,
-                                                  sample0=sample_id, **kw)
+                                                  sample0=sample_id, rivals=args.distinct_rivals if args.distinct else None,
+                                                  delta=args.distinct, **kw)
             elif args.run_type == 'caption':
                 gen_texts, _ = generate_caption(name_batch, lm_model, clip, lm_tokenizer, imgs, token_mask, logger, **kw)
             else:

@@ -289,6 +289,64 @@ def _polish_guarded(polish, eng, model, clip, tokenizer, image_instance, logger)
     return ids, cos
 
 
+def _rival_call(rivals, delta, clip, image_instance, batch_size: int):
+    """The rival table of a generation call, or None when the call has none (`rivals` None or `delta` 0).  `rivals`: an int M --
+    every captioned image against its M nearest others among the resident images (conzic_amd.rivals.rival_table) -- or an int
+    table [batch_size, M] of indices into the resident images (-1 = empty slot).  The resident images are those of
+    `image_instance`: the first `batch_size` are captioned, any behind them serve as rivals only.
+    Returns dict(table int32 [batch_size, M], delta, emb fp32 [n_images, proj])."""
+    if rivals is None or not delta:
+        return None
+    if not math.isfinite(float(delta)):
+        raise ValueError(f"delta = {delta!r} must be finite")
+    from . import rivals as rv
+    from clip.clip import ImageEmbeds
+    emb = image_instance.embeds if isinstance(image_instance, ImageEmbeds) else clip.last_image_embeds()
+    emb = np.ascontiguousarray(emb, dtype=np.float32)
+    if emb.shape[0] < batch_size:
+        raise ValueError(f"{emb.shape[0]} resident images for a batch of {batch_size}")
+    if isinstance(rivals, (int, np.integer)):
+        if emb.shape[0] < 2:
+            raise ValueError("rival images need at least two images in the batch")
+        table = rv.rival_table(emb, min(int(rivals), emb.shape[0] - 1))[:batch_size]
+    else:
+        table = np.ascontiguousarray(rivals, dtype=np.int32)
+    rv.check_table(table, np.arange(batch_size), emb.shape[0])
+    return dict(table=table, delta=float(delta), emb=emb)
+
+
+def _rival_engine(eng: Engine, vs, model, clip, tokenizer, logger) -> Engine:
+    """The engine a call with rivals runs on: `eng`, unless that is the screen-then-refine engine, whose selection and guard
+    bounds were derived for the softmax-K term alone (czc_generate_rows_vs refuses it) -- then the all-split engine, obtained the
+    way the guard's rerun obtains it, holding the same image embeddings."""
+    if vs is None or eng.precision != native.PREC_REFINE:
+        return eng
+    logger.info("rival images: the screen-then-refine engine's bounds do not cover the rival term; "
+                "this call runs on the split-fp16 engine")
+    grp = getattr(eng, "_group", None)
+    if grp is not None:   # the replicas' workspaces go before the second engine is built on the same GPU
+        grp.close(parent=False)
+        eng._group = None
+    eng2 = get_engine(model, clip, tokenizer, precision=native.PREC_SPLIT)
+    eng2.set_image_embeds(vs["emb"])
+    clip._engine = eng
+    return eng2
+
+
+def _log_own_probability(eng: Engine, vs, ids, seed_len: int, image_of_row, img_name, logger, what: str = "") -> None:
+    """After the last sweep: P(own image | caption) among every image's rival set (czc_score_rows_vs), one line per row."""
+    if vs is None or ids is None or not len(ids):
+        return
+    from . import rivals as rv
+    ior = np.asarray(image_of_row, dtype=np.int32)
+    eng.set_image_embeds(vs["emb"])
+    _, disc = eng.score_rows_vs(np.ascontiguousarray(ids[-1], dtype=np.int32), seed_len, rv.expand(vs["table"], ior), None, ior)
+    for r, b in enumerate(ior.tolist()):
+        n = int((vs["table"][b] >= 0).sum())
+        logger.info(f"{what}The {b + 1}-th image: {img_name[b]}, P(own image | caption) among {n + 1} images: {float(disc[r]):.3f}")
+
+
+
 def _bookkeeping(order, ids, cos, tokenizer, img_name, logger, batch_size, verbose, print_every):
     """gen_utils.py:82-96 on the snapshots of one *_generation call: (gen_texts_list, clip_score_sequence)."""
     best_score = [0] * batch_size
@@ -318,9 +376,12 @@ def _bookkeeping(order, ids, cos, tokenizer, img_name, logger, batch_size, verbo
 
 def run_generation(order: str, img_name, model, clip, tokenizer, image_instance, token_mask, prompt, logger, max_len,
                    top_k, temperature, alpha, beta, max_iters, batch_size, verbose=True, gamma=None,
-                   ctl_signal="positive", print_every: Optional[int] = None, pos_template=None):
+                   ctl_signal="positive", print_every: Optional[int] = None, pos_template=None, rivals=None, delta: float = 0.0):
     """Body shared by every *_generation function (gen_utils.py:51-242, control_gen_utils.py:30-134):
-    returns (gen_texts_list, clip_score_sequence) with the reference's list structure."""
+    returns (gen_texts_list, clip_score_sequence) with the reference's list structure.
+    `rivals` / `delta` (_rival_call): discriminative captions -- every candidate's fused score gets delta * P(own image |
+    candidate) among the image and its rivals added (czc_generate_rows_vs: the batch as rows with the identity image map and the
+    one shared order).  "best" is still chosen by cosine; after the last sweep P(own image | caption) is logged per image."""
     import utils as ref_utils  # the repo-root drop-in (same functions as the reference's utils.py)
     eng = get_engine(model, clip, tokenizer)
     seed_len = len(prompt.split()) + 1                                   # gen_utils.py:56
@@ -345,6 +406,8 @@ def run_generation(order: str, img_name, model, clip, tokenizer, image_instance,
         positions, n_mask, every = order_positions(order, max_len, iters, order_list=order_list)
     hp = Engine.hyper(alpha, beta, temperature, gamma, ctl_signal == "negative",
                       control="pos" if pos_template is not None else None)
+    vs = _rival_call(rivals, delta, clip, image_instance, batch_size)
+    eng = _rival_engine(eng, vs, model, clip, tokenizer, logger)
 
     def polish(eng):
         """One whole *_generation call on `eng` (which must hold the batch's image embeddings)."""
@@ -369,13 +432,20 @@ def run_generation(order: str, img_name, model, clip, tokenizer, image_instance,
             runner.set_image_embeds(emb)
         if eng.precision == native.PREC_REFINE:
             runner.refine_guard(reset=True)
-        out = runner.generate(batch_size, batch[0], max_len, seed_len, top_k, positions, hp, n_mask=n_mask,
-                              snapshot_every=every)
+        if vs is not None:
+            rows_pos = np.ascontiguousarray(np.repeat(np.asarray(positions, dtype=np.int32)[:, None], batch_size, axis=1))
+            out = runner.generate_rows_vs(np.repeat(np.asarray(batch[0], dtype=np.int32)[None, :], batch_size, axis=0), None, seed_len,
+                                          top_k, rows_pos, [hp] * batch_size, None, None, vs["table"], [vs["delta"]] * batch_size,
+                                          image_of_row=np.arange(batch_size, dtype=np.int32), n_mask=n_mask, snapshot_every=every)
+        else:
+            out = runner.generate(batch_size, batch[0], max_len, seed_len, top_k, positions, hp, n_mask=n_mask,
+                                  snapshot_every=every)
         if runner is not eng:
             eng.set_image_embeds(emb)  # the first engine holds the whole batch again, as after a single-stream call
         return out, runner
 
     ids, cos = _polish_guarded(polish, eng, model, clip, tokenizer, image_instance, logger)
+    _log_own_probability(eng, vs, ids, seed_len, np.arange(batch_size), img_name, logger)
     # utils.update_token_mask mutates the caller's mask in place (utils.py:53-59): leave it as the
     # reference would after the last visited position
     if positions:
@@ -386,7 +456,7 @@ def run_generation(order: str, img_name, model, clip, tokenizer, image_instance,
 def run_generation_samples(order: str, samples_num: int, img_name, model, clip, tokenizer, image_instance, token_mask, prompt,
                            logger, max_len, top_k, temperature, alpha, beta, max_iters, batch_size, verbose=True, gamma=None,
                            ctl_signal="positive", print_every: Optional[int] = None, pos_template=None, schedules=None,
-                           sample_tau: float = 0.0, sample_seed: int = 0, sample0: int = 0):
+                           sample_tau: float = 0.0, sample_seed: int = 0, sample0: int = 0, rivals=None, delta: float = 0.0):
     """The sample loop around a *_generation call (demo.py:83, run.py) as ONE engine call: `samples_num` samples of a batch of
     `batch_size` images ride as batch_size * samples_num rows of czc_generate_rows, every sample with the visiting order the
     serial loop would have drawn for it (harness.sample_schedules); the images are encoded once.  Returns a list of
@@ -398,7 +468,8 @@ def run_generation_samples(order: str, samples_num: int, img_name, model, clip, 
     those of all batches first, in the serial loop's sample-major order); None: drawn here.
     `sample_tau` > 0: every row draws its winner from softmax_K(final_score / sample_tau) (czc_generate_rows_draw) under the
     seed of its (image, sample): draws.row_seed(sample_seed, key of the image's name, sample0 + s).  A serial loop that calls
-    this function once per sample (samples_num = 1, sample0 = the sample's index) returns the ids of the one batched call."""
+    this function once per sample (samples_num = 1, sample0 = the sample's index) returns the ids of the one batched call.
+    `rivals` / `delta`: as for run_generation; every sample of an image carries the image's rivals (czc_generate_rows_vs)."""
     from . import draws as dw
     import utils as ref_utils
     S, B = int(samples_num), int(batch_size)
@@ -421,6 +492,16 @@ def run_generation_samples(order: str, samples_num: int, img_name, model, clip, 
                       control="pos" if pos_template is not None else None)
     row_draws = dw.sample_rows(sample_seed, [dw.image_key(n) for n in img_name], S, float(sample_tau or 0.0), sample0=sample0)
     init_row = np.asarray(batch[0], dtype=np.int32)
+    vs = _rival_call(rivals, delta, clip, image_instance, B)
+    eng = _rival_engine(eng, vs, model, clip, tokenizer, logger)
+
+    def vs_rows(runner, n_samples, pos_rows, draws_):
+        """`n_samples` samples of the batch as rows of one rivals call: sample-major, every row with its image's rivals."""
+        from . import rivals as rv
+        ior = np.tile(np.arange(B, dtype=np.int32), n_samples)
+        return runner.generate_rows_vs(np.repeat(init_row[None, :], B * n_samples, axis=0), None, seed_len, top_k, pos_rows,
+                                       [hp] * (B * n_samples), draws_, None, rv.expand(vs["table"], ior),
+                                       [vs["delta"]] * (B * n_samples), image_of_row=ior, n_mask=n_mask, snapshot_every=every)
 
     def polish(eng):
         eng.set_token_mask(_mask_to_numpy(token_mask))
@@ -447,7 +528,13 @@ def run_generation_samples(order: str, samples_num: int, img_name, model, clip, 
             runner.set_image_embeds(emb)
         if eng.precision == native.PREC_REFINE:
             runner.refine_guard(reset=True)
-        if one_by_one and row_draws is not None:
+        if vs is not None and one_by_one:
+            outs = [vs_rows(runner, 1, np.ascontiguousarray(np.repeat(positions[:, s:s + 1], B, axis=1)),
+                            None if row_draws is None else row_draws[s * B:(s + 1) * B]) for s in range(S)]
+            out = tuple(np.concatenate([o[j] for o in outs], axis=1) for j in (0, 1))
+        elif vs is not None:
+            out = vs_rows(runner, S, rows_pos, row_draws)
+        elif one_by_one and row_draws is not None:
             outs = [runner.generate_rows_draw(np.repeat(init_row[None, :], B, axis=0), None, seed_len, top_k,
                                               np.repeat(positions[:, s:s + 1], B, axis=1), [hp] * B, row_draws[s * B:(s + 1) * B],
                                               n_mask=n_mask, snapshot_every=every) for s in range(S)]
@@ -467,6 +554,7 @@ def run_generation_samples(order: str, samples_num: int, img_name, model, clip, 
         return out, runner
 
     ids, cos = _polish_guarded(polish, eng, model, clip, tokenizer, image_instance, logger)
+    _log_own_probability(eng, vs, ids, seed_len, image_of_row, img_name, logger)
     if positions.shape[0]:   # the caller's mask as after the LAST sample's last position (utils.py:53-59)
         ref_utils.update_token_mask(tokenizer, token_mask, max_len, int(positions[-1, S - 1]))
     out = []
@@ -718,7 +806,7 @@ def caption_order(run_type: str, generate_order: str, ctl_type: str, max_iter: i
 def caption_samples(samples_num: int, run_type: str, img_name, model, clip, tokenizer, image_instance, token_mask, logger, *,
                     prompt="", batch_size=1, max_len=15, top_k=100, temperature=1.0, max_iter=500, alpha=0.7, beta=1,
                     generate_order="sequential", gamma=5, ctl_type="sentiment", style_type="positive", pos_type=None,
-                    schedules=None, sample_tau=0.0, sample_seed=0, sample0=0):
+                    schedules=None, sample_tau=0.0, sample_seed=0, sample0=0, rivals=None, delta=0.0):
     """`--batch_samples` of the two CLIs: what `samples_num` calls of generate_caption (run_type 'caption', gen_utils.py:289-333)
     or control_generate_caption (control_gen_utils.py:197-232) return, from one run_generation_samples call.  Returns the list
     of (generate_texts, clip_scores) pairs and logs every sample's final and best captions as those functions do."""
@@ -737,7 +825,7 @@ def caption_samples(samples_num: int, run_type: str, img_name, model, clip, toke
         kw.update(gamma=gamma, pos_template=pos_type)
     outs = run_generation_samples(order, samples_num, img_name, model, clip, tokenizer, image_instance, token_mask, prompt,
                                   logger, max_len, top_k, temperature, alpha, beta, max_iters, batch_size, schedules=schedules,
-                                  sample_tau=sample_tau, sample_seed=sample_seed, sample0=sample0, **kw)
+                                  sample_tau=sample_tau, sample_seed=sample_seed, sample0=sample0, rivals=rivals, delta=delta, **kw)
     logger.info("Finished %d samples in %.3fs" % (samples_num, time.time() - start_time))
     for sample_id, (generate_texts, _) in enumerate(outs):
         logger.info(f"Sample {sample0 + sample_id}: ")

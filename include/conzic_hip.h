@@ -471,6 +471,48 @@ int czc_generate_rows_tied(czc_engine* e, int R, int T, int seed_len, const int3
                            const czc_hyper* hp_of_row_host /* [R] */, const czc_draw* draw_of_row_host /* [R], or NULL */,
                            int32_t* out_ids, float* out_cos);
 
+/* czc_generate_rows_tied with every row also scored against RIVAL images, for captions that tell an image from its look-alikes.
+ * Row r has its own image i0 = image_of_row[r] and up to M rivals i1..im of the resident batch.  For candidate sentence t the
+ * step forms, next to the one cosine it forms today,
+ *     disc = softmax over {i0, i1..im} of exp(logit_scale) * cos(t, ij), taken at i0  =  1 / (1 + sum_j exp(s * (cj - c0)))
+ * -- the probability that the caption retrieves its own image among the set -- in fp32, with max(0, max_j s (cj - c0))
+ * subtracted before any expf, and adds delta_of_row[r] * disc to the candidate's fused score, last, behind the control terms.
+ * The winner (argmax or draw), the write-back and the returned cosine follow as before; c0 has the bits of the step's cosine.
+ * Everything not named here is czc_generate_rows_tied's.
+ *   - no rivals: rival_of_row == NULL, or every delta 0, or no filled slot: czc_generate_rows_tied itself, bit for bit.  In a
+ *     mixed call a row with delta = 0 or without a rival skips the term entirely and returns what that call returns for it.
+ *   - rival_of_row is [R, M], indices into the resident image batch, -1 = empty slot, the filled slots first.  It and the
+ *     deltas are uploaded once, with the schedule; a compact batch (option "memo_rows", idle rows) gathers them through its run
+ *     list as it gathers the hyper-parameters.  The indices always point into the whole resident batch, while the rows' own
+ *     embeddings are the gathered per-row copy.
+ *   - a row's result depends on its content, hyper-parameters, draw record, own image and rival images only: not on its index,
+ *     its companions, the order of its rivals (beyond the rounding of the fp32 sum), compaction or streams.
+ *   - option "memo_rows" is exact and unchanged: the rivals of a row do not change during a call.
+ *   - tied groups: members may carry different rivals and deltas; out_cos keeps its tied meaning.
+ *   - control callbacks and tables behave as for czc_generate_rows_tied.
+ *   - CZC_PREC_REFINE: the selection and guard bounds were derived for the softmax-K term alone.  A call on that engine with
+ *     any row where delta != 0 and a slot is filled is refused with CZC_ERR_STATE and a message that names the CZC_PREC_SPLIT
+ *     engine (conzic_amd.runtime obtains one, as the guard's rerun does).  czc_score_rows_vs works on every precision: it uses
+ *     the exact tower, as czc_score_rows does.
+ * Checked before any GPU work, CZC_ERR_ARG, and the engine stays usable: M outside [1, CZC_MAX_RIVALS] when the array is
+ * given; an index outside [-1, resident batch); a rival equal to the row's own image; a filled slot behind an empty one; a
+ * delta that is not finite; clip_proj * CZC_MAX_RIVALS * 4 beyond the kernel's 32 KB LDS array (clip_proj > 512); and everything
+ * czc_generate_rows_tied checks. */
+#define CZC_MAX_RIVALS 16
+int czc_generate_rows_vs(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host,
+                         const int32_t* len_of_row_host /* NULL: every row has L = T - seed_len - 1 */,
+                         const int32_t* image_of_row_host, const int32_t* group_of_row_host /* [R], or NULL */, int top_k,
+                         int n_steps, const int32_t* positions_host, const int32_t* n_mask_host, int snapshot_every,
+                         const czc_hyper* hp_of_row_host /* [R] */, const czc_draw* draw_of_row_host /* [R], or NULL */,
+                         const int32_t* rival_of_row_host /* [R, M] indices into the resident image batch, -1 = none; or NULL */,
+                         int M, const float* delta_of_row_host /* [R] */, int32_t* out_ids, float* out_cos);
+/* czc_score_rows, then the rival kernel at K = 1: out_cos [R] has the bits czc_score_rows returns, out_disc [R] is the disc of
+ * czc_generate_rows_vs for the row as it stands (1 for a row without rivals, and everywhere with rival_of_row == NULL).
+ * Either output pointer may be NULL.  The checks of czc_score_rows and, for the table, those of czc_generate_rows_vs. */
+int czc_score_rows_vs(czc_engine* e, const int32_t* rows /* [R, T] BERT ids, host or device */, int R, int T, int seed_len,
+                      const int32_t* len_of_row_host, const int32_t* image_of_row_host, const int32_t* rival_of_row_host, int M,
+                      float* out_cos /* [R] */, float* out_disc /* [R] */);
+
 /* Engine options (all are exact work reductions / kernel choices; results agree within the engine precision):
  *   "share_prefix"    (1) encode the causal prefix common to an image's K candidates once per step instead of K
  *                         times

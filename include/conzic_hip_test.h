@@ -126,6 +126,14 @@ int czc_test_refine_cosine(int n_rows_max, int n_rows, int B, int K, int D, cons
 int czc_test_combine_refine(int B, int K, float logit_scale, const float* cos_in, const float* probs, const czc_hyper* hp,
                             const int32_t* refine_kind, const float* refine_cos, float refine_guard, float* clip_score, float* clip_ref,
                             float* final_score, int32_t* best, float* best_cos, int32_t* nonfinite);
+/* launch_combine through the rival instantiation (czc_generate_rows_vs): B rows with own image image_of_row[b] of img_all
+ * [n_img, D] (L2-normalised on the device; the rows' own embeddings are the gathered copy), rival_idx [B, M] into img_all (-1 =
+ * empty, filled slots first), delta [B], hp [B] (control 0), draw [B] or NULL = no row draws, step as in czc_test_combine_draw ->
+ * clip_ref, disc, final_score [B*K], best [B], nonfinite [8] (zeroed first); guarded outputs as above. */
+int czc_test_combine_rivals(int B, int K, int D, const float* text_feat, const float* img_all, int n_img, const int32_t* image_of_row,
+                            const int32_t* rival_idx, int M, const float* delta, float logit_scale, const float* probs,
+                            const czc_hyper* hp, const czc_draw* draw, uint32_t step, float* clip_ref, float* disc, float* final_score,
+                            int32_t* best, int32_t* nonfinite);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

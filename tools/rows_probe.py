@@ -29,7 +29,16 @@ The cost of sampled winners: one image x S rows under their own shuffle orders, 
 (the argmax path, i.e. czc_generate_rows_hp) against the same call with every tau = --sample_tau and a seed per row.  Full-size
 towers, both logit scales; per scale the wall times of --reps alternating repetitions after one warm-up of each, each arm's spread
 ((max - min) / median), the median ratio, and the distinct final captions and Div-1 / Div-2 (over token ids) of each arm.
-`--describe_draw profiles/r11_draw_probe.json` prints the README's sentence about that file (no GPU needed)."""
+`--describe_draw profiles/r11_draw_probe.json` prints the README's sentence about that file (no GPU needed).
+
+    python tools/rows_probe.py --distinct 1.0 [--S 16] [--reps 5] [--out profiles/r13_rival_probe.json]
+
+The cost of rival images: 8 resident images x S rows under their own shuffle orders, one czc_generate_rows_vs call with
+rival_of_row = NULL (czc_generate_rows_tied itself: the path without the feature) against the same call with the 4 nearest other
+images as every row's rivals and delta = --distinct.  Full-size towers, both logit scales (the screen-then-refine engine refuses
+rivals, so the published scale runs on the split-fp16 engine, where the runtime sends such a call); per scale the wall times of
+--reps alternating repetitions after one warm-up of each arm, each arm's spread, the ratio of the medians and the share of final
+captions the term changed.  `--describe_distinct profiles/r13_rival_probe.json` prints the README's sentence (no GPU needed)."""
 import argparse
 import json
 import os
@@ -60,10 +69,13 @@ ap.add_argument("--signals", default=None, metavar="caption,positive,negative",
                 help="the signals leg: one call per control signal against one czc_generate_rows_hp call (table mode)")
 ap.add_argument("--sample_tau", type=float, default=None, metavar="T",
                 help="the draw leg: the rows call with every tau = 0 against the same call with every tau = T")
+ap.add_argument("--distinct", type=float, default=None, metavar="DELTA",
+                help="the rivals leg: the rows call with rival_of_row = NULL against the same call with 4 rivals per row")
+ap.add_argument("--describe_distinct", default=None, metavar="JSON", help="print the README sentence for a rivals-leg result file and exit")
 ap.add_argument("--describe_draw", default=None, metavar="JSON", help="print the README sentence for a draw-leg result file and exit")
 args = ap.parse_args()
 if args.out is None:
-    args.out = os.path.join(ROOT, "profiles", "r11_draw_probe.json" if args.sample_tau else "r10_signals_probe.json" if args.signals else "r09_lengths_probe.json" if args.lengths else
+    args.out = os.path.join(ROOT, "profiles", "r13_rival_probe.json" if args.distinct else "r11_draw_probe.json" if args.sample_tau else "r10_signals_probe.json" if args.signals else "r09_lengths_probe.json" if args.lengths else
                             "r09_memo_rows_probe.json" if args.memo_rows else "r08_rows_probe.json")
 
 L, K, SEED_LEN = args.L, args.K, 4
@@ -88,6 +100,24 @@ def describe_draw(path):
 
 if args.describe_draw:
     print(describe_draw(args.describe_draw))
+    sys.exit(0)
+
+
+def describe_distinct(records):
+    """The README's sentence, from the records of a result file: a ratio inside the NULL arm's own spread is "no measurable cost"."""
+    parts = []
+    for r in records:
+        inside = abs(r["ratio_median"] - 1.0) <= r["spread_null"]
+        parts.append(f"on the {r['precision']} engine {r['wall_s_null_median']:.3f} s with rival_of_row = NULL (spread {100 * r['spread_null']:.1f} %) "
+                     f"and {r['wall_s_rivals_median']:.3f} s with {r['M']} rivals per row and delta = {r['delta']:g} (spread "
+                     f"{100 * r['spread_rivals']:.1f} %), ratio of the medians {r['ratio_median']:.3f}: "
+                     + ("no measurable cost" if inside else f"x{r['ratio_median']:.3f} the NULL arm")
+                     + f"; the term changed {r['captions_changed']} of {r['S']} final captions")
+    return "; ".join(parts)
+
+
+if args.describe_distinct:
+    print(describe_distinct(json.load(open(args.describe_distinct))))
     sys.exit(0)
 
 
@@ -268,7 +298,55 @@ def draw_leg():
         eng.close()
 
 
-if args.sample_tau:
+def distinct_leg():
+    from conzic_amd import lengths, native, rivals as rv
+    n_img, M = 8, 4
+    for scale in args.scales:
+        prec = runtime.choose_precision(scale)
+        if prec == native.PREC_REFINE:   # czc_generate_rows_vs refuses it; the runtime sends such a call to the split engine
+            prec = native.PREC_SPLIT
+        su = harness.build_synthetic(False, prec, logit_scale=scale, regular_only=True)
+        eng = su.engine
+        emb = np.random.default_rng(100).standard_normal((n_img, su.clip_cfg.proj)).astype(np.float32)
+        eng.set_image_embeds(emb)
+        for S in (args.S if args.S != [1, 2, 4, 8, 16] else [16]):
+            init = lengths.length_rows(su.bert_tok, "Image of a", [L] * S)
+            hps = [Engine.hyper(0.02, 2.0, 0.1) for _ in range(S)]
+            random.seed(42)
+            positions, n_mask, every, _ = harness.sample_schedules("shuffle", L, args.sweeps, S)
+            ior = np.arange(S, dtype=np.int32) % n_img
+            arms = {"null": None, "rivals": rv.expand(rv.rival_table(emb, M), ior)}
+            deltas = np.full(S, float(args.distinct), np.float32)
+
+            def call(arm):
+                return eng.generate_rows_vs(init, None, SEED_LEN, K, positions, hps, None, None, arms[arm], deltas, image_of_row=ior,
+                                            n_mask=n_mask, snapshot_every=every)
+
+            warm = {arm: call(arm) for arm in arms}
+            times = {arm: [] for arm in arms}
+            for _ in range(args.reps):
+                for arm in arms:
+                    eng.sync()
+                    t0 = time.perf_counter()
+                    call(arm)
+                    times[arm].append(time.perf_counter() - t0)
+            rec = dict(logit_scale=scale, precision=runtime.PRECISION_NAMES[prec], S=S, L=L, K=K, sweeps=args.sweeps, order="shuffle",
+                       images=n_img, M=M, delta=float(args.distinct))
+            for arm in arms:
+                rec.update({f"wall_s_{arm}": times[arm], f"wall_s_{arm}_median": float(np.median(times[arm])),
+                            f"spread_{arm}": spread(times[arm])})
+            rec["ratio_median"] = rec["wall_s_rivals_median"] / rec["wall_s_null_median"]
+            rec["ratio_inside_null_spread"] = bool(abs(rec["ratio_median"] - 1.0) <= rec["spread_null"])
+            rec["captions_changed"] = int((warm["null"][0][-1] != warm["rivals"][0][-1]).any(axis=1).sum())
+            print(json.dumps(rec), flush=True)
+            out.append(rec)
+        eng.close()
+    print(describe_distinct(out))
+
+
+if args.distinct:
+    distinct_leg()
+elif args.sample_tau:
     draw_leg()
 elif args.memo_rows:
     memo_rows_leg()
@@ -276,7 +354,7 @@ elif args.signals:
     signals_leg()
 elif args.lengths:
     lengths_leg()
-for scale in ([] if args.memo_rows or args.lengths or args.signals or args.sample_tau else args.scales):
+for scale in ([] if args.memo_rows or args.lengths or args.signals or args.sample_tau or args.distinct else args.scales):
     prec = runtime.choose_precision(scale)
     su = harness.build_synthetic(False, prec, logit_scale=scale, regular_only=True)
     eng = su.engine

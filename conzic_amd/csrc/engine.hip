@@ -54,6 +54,17 @@ struct ProfKind {
   int64_t launches = 0;
 };
 
+// The per-row device records of a step, one record per row of the batch the step runs on; all null outside a rows call.
+// hp: czc_generate_rows_hp's hyper-parameters.  draw + step: czc_generate_rows_draw's records and the step's index in the call's
+// schedule (the Philox counter is the record's step0 + step).  rival [rows, M] + delta [rows]: czc_generate_rows_vs' table and
+// deltas; the indices point into img_all, the whole normalised resident batch of n_img images, which a compact batch leaves alone.
+struct RowRecords {
+  const RowHyper* hp = nullptr;
+  const RowDraw* draw = nullptr; unsigned step = 0;
+  const int* rival = nullptr; const float* delta = nullptr; int M = 0;
+  const float* img_all = nullptr; int n_img = 0;
+};
+
 }  // namespace
 
 struct czc_engine {
@@ -162,19 +173,9 @@ struct czc_engine {
   // option "memo" (czc_generate only; memo.hip): a step runs only for the images whose masked row differs from the one they
   // had on their last visit of the same (position, n_mask) key in this call; the others take the entry's row and cosine back
   int memo = 0;
-  // czc_generate_rows_hp, during its steps: the hyper-parameters of the rows the step at hand runs on (device, one record per
-  // row of that batch -- the call's upload, or a compact batch's gather of it); null everywhere else
-  const RowHyper* hp_rows = nullptr;
-  // czc_generate_rows_draw, during its steps: the draw records of the rows the step at hand runs on (device, gathered like
-  // hp_rows) and the step's index in the call's schedule (the Philox counter is the record's step0 + draw_step); null elsewhere
-  const RowDraw* draw_rows = nullptr;
-  unsigned draw_step = 0;
-  // czc_generate_rows_vs.  vs_*: what the entry point hands to the rows call underneath it (host arrays; vs_host null outside
-  // such a call).  rival_*: during the steps, the rival table [rows of the step at hand, rival_M] and the deltas of those rows
-  // (device, gathered like hp_rows) and the whole normalised resident batch the indices point into; null elsewhere
-  const int32_t* vs_host = nullptr; const float* vs_delta_host = nullptr; int vs_M = 0;
-  const int* rival_rows = nullptr; const float* rival_delta = nullptr; int rival_M = 0;
-  const float* rival_img_all = nullptr; int rival_n_img = 0;
+  // a rows call, during its steps: the per-row records of the rows the step at hand runs on (the call's upload, or a compact
+  // batch's gather of it); empty everywhere else
+  RowRecords rec;
   int memo_branch_floor = 0;  // compacted step: longest branch the HIT images had (the full batch's attention-kernel choice)
   int64_t stat_memo_hits = 0, stat_memo_images = 0;  // image-steps that took an entry / all image-steps of memo calls
   // option "memo_rows" (czc_generate_rows only; memo_rows.hip): the same rule keyed per row, with counters of its own
@@ -784,7 +785,7 @@ int step_phase_a(czc_engine* e, const StepArgs& a) {
   StepBufs b;
   E_CHECK(step_bufs(e, a.B * a.K, &b));
   { ProfScope ps(e, "topk", 0);
-    if (e->hp_rows) E_CHECK(launch_softmax_mask_topk_rows_hp(logits, a.B, c.bert_vocab, a.K, e->d_mask, e->hp_rows, c.dot_id, a.dot_rows,
+    if (e->rec.hp) E_CHECK(launch_softmax_mask_topk_rows_hp(logits, a.B, c.bert_vocab, a.K, e->d_mask, e->rec.hp, c.dot_id, a.dot_rows,
                                                              b.probs, b.idxs, b.cand, e->st));
     else if (a.dot_rows) E_CHECK(launch_softmax_mask_topk_rows(logits, a.B, c.bert_vocab, a.K, e->d_mask, hp->temperature, c.dot_id, a.dot_rows,
                                                           b.probs, b.idxs, b.cand, e->st));
@@ -794,7 +795,7 @@ int step_phase_a(czc_engine* e, const StepArgs& a) {
   { ProfScope ps(e, "bridge", 0);
     PosDev pos{hp->control == 2 ? e->d_pos_tags : nullptr, e->d_pos_masks, e->pos_n};
     // per-row hyper-parameters: every table there is goes along and a candidate's thread scores by its row's control
-    if (e->hp_rows) E_CHECK(launch_bridge_rows_hp(e->bd, a.d_inp, a.B, a.T, a.gen_rows, b.cand, a.K, e->d_lex, e->d_lex_pos, e->d_lex_cls, e->hp_rows,
+    if (e->rec.hp) E_CHECK(launch_bridge_rows_hp(e->bd, a.d_inp, a.B, a.T, a.gen_rows, b.cand, a.K, e->d_lex, e->d_lex_pos, e->d_lex_cls, e->rec.hp,
                                                   PosDev{e->d_pos_tags, e->d_pos_masks, e->pos_n}, b.cids, b.clen, b.senti, b.reps,
                                                   b.totals + 2, e->st, a.rag ? a.rag->len : nullptr));
     else if (a.gen_rows) E_CHECK(launch_bridge_rows(e->bd, a.d_inp, a.B, a.T, a.gen_rows, b.cand, a.K, hp->control == 1 ? e->d_lex : nullptr,
@@ -873,14 +874,14 @@ int step_phase_b(czc_engine* e, const StepArgs& a, int M, int max_len, int max_b
   ca.senti_raw = b.senti; ca.repeats = b.reps; ca.alpha = hp->alpha; ca.beta = hp->beta; ca.gamma = hp->gamma;
   ca.use_senti = hp->control; ca.B = a.B; ca.K = a.K; ca.D = c.clip_proj; ca.clip_score = cscore; ca.clip_ref = cref;
   ca.final_score = fin; ca.best = best; ca.best_cos = bcos; ca.inp = a.d_inp; ca.T = a.T; ca.gen_idx = a.gen_idx;
-  ca.hp_rows = e->hp_rows;   // czc_generate_rows_hp: alpha / beta / gamma / control per row, in both passes of the refine engine too
+  ca.hp_rows = e->rec.hp;   // czc_generate_rows_hp: alpha / beta / gamma / control per row, in both passes of the refine engine too
   ca.gen_rows = a.gen_rows;  // both passes of the refine engine write back through the same per-row column
   // czc_generate_rows_draw: the draw belongs to the combine that writes back -- the only one here, the final one of the refine engine
-  if (!e->refine) { ca.draw_rows = e->draw_rows; ca.draw_step = e->draw_step; }
+  if (!e->refine) { ca.draw_rows = e->rec.draw; ca.draw_step = e->rec.step; }
   E_CHECK(ensure(e, "s_nonfinite", 32, (void**)&ca.nonfinite));
-  if (e->rival_rows) {  // czc_generate_rows_vs (never on the refine engine: refused by the entry point)
+  if (e->rec.rival) {  // czc_generate_rows_vs (never on the refine engine: refused by the entry point)
     if (e->refine) return fail(e, CZC_ERR_STATE, "step: rivals on the screen-then-refine engine%s");
-    ca.rival_idx = e->rival_rows; ca.M = e->rival_M; ca.rival_delta = e->rival_delta; ca.img_all = e->rival_img_all; ca.n_img = e->rival_n_img;
+    ca.rival_idx = e->rec.rival; ca.M = e->rec.M; ca.rival_delta = e->rec.delta; ca.img_all = e->rec.img_all; ca.n_img = e->rec.n_img;
     E_CHECK(ensure(e, "s_disc", (size_t)n_seq * 4, (void**)&ca.disc));
   }
   if (!e->refine) {
@@ -910,10 +911,10 @@ int step_phase_b(czc_engine* e, const StepArgs& a, int M, int max_len, int max_b
     ca.inp = nullptr;
     E_CHECK(launch_combine(ca, e->st));
     const float gate_h = e->gate_now ? e->refine_gate_delta * (refine_rows16_now(e) ? e->refine_rows16_factor : 1.f) * e->logit_scale_exp : 0.f;
-    if (e->draw_rows) E_CHECK(launch_refine_select_draw(cscore, fin, a.B, a.K, theta, theta_base, e->logit_scale_exp, e->in_generate ? e->refine_samples : e->refine_samples_step,
-                                                        gate_h, hp->beta, e->hp_rows, e->draw_rows, e->gate_need_cos ? 1 : 0, ca.nonfinite + 4, kind, list, count, e->st));
-    else if (e->hp_rows) E_CHECK(launch_refine_select_rows(cscore, fin, a.B, a.K, theta_base, e->logit_scale_exp, e->in_generate ? e->refine_samples : e->refine_samples_step,
-                                                      gate_h, e->hp_rows, e->gate_need_cos ? 1 : 0, ca.nonfinite + 4, kind, list, count, e->st));
+    if (e->rec.draw) E_CHECK(launch_refine_select_draw(cscore, fin, a.B, a.K, theta, theta_base, e->logit_scale_exp, e->in_generate ? e->refine_samples : e->refine_samples_step,
+                                                        gate_h, hp->beta, e->rec.hp, e->rec.draw, e->gate_need_cos ? 1 : 0, ca.nonfinite + 4, kind, list, count, e->st));
+    else if (e->rec.hp) E_CHECK(launch_refine_select_rows(cscore, fin, a.B, a.K, theta_base, e->logit_scale_exp, e->in_generate ? e->refine_samples : e->refine_samples_step,
+                                                      gate_h, e->rec.hp, e->gate_need_cos ? 1 : 0, ca.nonfinite + 4, kind, list, count, e->st));
     else E_CHECK(launch_refine_select(cscore, fin, a.B, a.K, theta, e->in_generate ? e->refine_samples : e->refine_samples_step, gate_h, hp->beta, e->gate_need_cos ? 1 : 0,
                                  ca.nonfinite + 4, kind, list, count, e->st)); }
   { ProfScope ps(e, "bridge", 0);
@@ -939,7 +940,7 @@ int step_phase_b(czc_engine* e, const StepArgs& a, int M, int max_len, int max_b
   }
   { ProfScope ps(e, "combine", 0);
     ca.text_feat = nullptr; ca.inp = a.d_inp; ca.refine_kind = kind; ca.refine_cos = rcos;
-    ca.draw_rows = e->draw_rows; ca.draw_step = e->draw_step;
+    ca.draw_rows = e->rec.draw; ca.draw_step = e->rec.step;
     ca.refine_guard = e->refine_guard_dev * (refine_rows16_now(e) ? e->refine_rows16_factor : 1.f);
     E_CHECK(launch_combine(ca, e->st)); }
   e->stat_refine_rows += M2;
@@ -967,8 +968,8 @@ int step_device(czc_engine* e, int* d_inp, int B, int T, int gen_idx, int n_mask
     return fail(e, CZC_ERR_STATE, "n_mask=0 needs a previous forward of the same [B,T] shape%s");
   StepArgs a{d_inp, B, T, gen_idx, n_mask, dot_allowed, K, *hp};
   a.gen_rows = gen_rows; a.dot_rows = dot_rows; a.gen_rows_host = gen_rows_host; a.rag = rag; a.ctl_T = ctl_T;
-  if (e->hp_rows && (!gen_rows || !dot_rows)) return fail(e, CZC_ERR_ARG, "step: per-row hyper-parameters need per-row columns%s");
-  if (e->draw_rows && !gen_rows) return fail(e, CZC_ERR_ARG, "step: per-row draws need per-row columns%s");
+  if (e->rec.hp && (!gen_rows || !dot_rows)) return fail(e, CZC_ERR_ARG, "step: per-row hyper-parameters need per-row columns%s");
+  if (e->rec.draw && !gen_rows) return fail(e, CZC_ERR_ARG, "step: per-row draws need per-row columns%s");
   if (rag && (!gen_rows || !dot_rows || rag->max_T > T || rag->M > B * T)) return fail(e, CZC_ERR_ARG, "step: ragged rows need per-row columns and lengths within T%s");
   E_CHECK(step_phase_a(e, a));
   if (n_mask > 0) { e->stat_bert_rows += rag ? rag->M : B * T; e->last_BT = B * T; e->last_B = B; e->last_T = T; }
@@ -1007,6 +1008,42 @@ void free_layer_set(std::vector<LayerW>& L) {
   L.clear();
 }
 
+// ---- a generate call as one value --------------------------------------------------------------------------------------
+// Every czc_generate* entry point fills a RowsCall and hands it to run_call.  `level` names the entry point and so which optional
+// arrays it has; a check_* function validates one array and drops it (null) where it carries nothing, so below them "the call has
+// per-row lengths / records / draws / groups / rivals" is a fact of the struct.  A new per-row argument: a field, a check_*
+// function, an upload in upload_call and, if kernels read it at every step, a RowRecords entry.
+enum CallLevel { CALL_GENERATE, CALL_ROWS, CALL_FROM, CALL_LEN, CALL_HP, CALL_DRAW, CALL_TIED, CALL_VS };
+struct RowsCall {
+  CallLevel level = CALL_GENERATE;
+  bool rows = false, from = false;  // per-row positions and images / a start row per row and idle positions
+  int R = 0, T = 0, L = 0, seed_len = 0, top_k = 0, n_steps = 0, snapshot_every = 0;  // (R: czc_generate's B)
+  const int32_t *init = nullptr, *len = nullptr, *image_of_row = nullptr, *group = nullptr, *positions = nullptr, *n_mask = nullptr;
+  const czc_hyper *hp = nullptr, *hp_rows = nullptr;  // the call's one record (with per-row records [R]: their entry 0)
+  const czc_draw* draw = nullptr;                     // [R]
+  const int32_t* rival = nullptr; int M = 0; const float* delta = nullptr;  // [R, M], [R]
+  int32_t* out_ids = nullptr; float* out_cos = nullptr;
+  std::vector<czc_draw> no_draw;  // check_rival_table: the tau = 0 records of a rival call that brought none
+  size_t n_pos() const { return rows ? (size_t)n_steps * R : (size_t)n_steps; }
+  int n_mask_at(int s) const { return n_mask ? n_mask[s] : 1; }
+};
+
+// The schedule upload of a rows call (int32 words; the kernels read this layout): [n_steps][R] columns (CZC_POS_IDLE where a row
+// sits the step out) | at dot: [n_steps][R] '.' rules | idle calls, at run: [n_steps][R] run lists (every step's rows that are not
+// idle, ascending) | len mode, at rag: [R] token counts + [R + 1] packed-row offsets of the full batch, then (idle calls, at
+// rag_steps, else 0) one such block per step for its run list
+struct SchedLayout {
+  int R = 0; bool idle = false;
+  size_t dot = 0, run = 0, rag = 0, rag_steps = 0;
+  int rag_M = 0, rag_max = 0;  // len mode: packed rows / longest row of the full batch
+  size_t rag_block() const { return 2 * (size_t)R + 1; }
+  size_t cols(int s) const { return (size_t)s * R; }
+  size_t dots(int s) const { return dot + (size_t)s * R; }
+  size_t runs(int s) const { return run + (size_t)s * R; }
+  size_t rag_step(int s) const { return rag_steps + (size_t)s * rag_block(); }
+};
+struct Sched { std::vector<int32_t> h; const int* d = nullptr; SchedLayout at; };  // on the host, its upload, where its blocks are
+
 // ---- option "memo" (czc_generate): the step memo of memo.hip ----------------------------------------------------------
 // A step group is one n_mask >= 1 step plus the n_mask = 0 steps that re-use its forward (span order: 2 then 0,
 // gen_utils.py:160-179).  Its key is the (position, n_mask) list of its steps; an image's entry at that key holds the masked
@@ -1023,8 +1060,10 @@ struct MemoPlan {
   int branch_max[MEMO_SUB] = {0, 0};
 };
 
-int memo_begin(czc_engine* e, int B, int T, int n_steps, const int32_t* positions, const int32_t* n_mask, int snapshot_every,
-               bool want_cos, const std::vector<char>& audit, MemoPlan* mp) {
+int memo_begin(czc_engine* e, const RowsCall& c, const std::vector<char>& audit, MemoPlan* mp) {
+  const int B = c.R, T = c.T, n_steps = c.n_steps, snapshot_every = c.snapshot_every;
+  const int32_t *positions = c.positions, *n_mask = c.n_mask;
+  const bool want_cos = c.out_cos != nullptr;
   mp->slot.assign(n_steps, -1); mp->sub.assign(n_steps, 0); mp->check.assign(n_steps, 0); mp->group_len.assign(n_steps, 0);
   std::map<std::vector<int>, int> slots;
   for (int s = 0; s < n_steps;) {
@@ -1070,8 +1109,10 @@ int memo_begin(czc_engine* e, int B, int T, int n_steps, const int32_t* position
 // 16-byte read (the second host round trip of such a step) give the active images; then all of them run as usual (and
 // record), none of them runs (BERT, the towers and the combine kernel are skipped), or the step runs on a compact batch of
 // them.  The group's other steps keep its active set: the n_mask = 0 step re-uses the forward of exactly those rows.
-int memo_step(czc_engine* e, MemoPlan& mp, int s, int* d_inp, int B, int T, int gen_idx, int n_mask, int dot_allowed, int K,
-              const czc_hyper* hp) {
+int memo_step(czc_engine* e, MemoPlan& mp, const RowsCall& c, int s, int* d_inp) {
+  const int B = c.R, T = c.T, K = c.top_k, pos = c.positions[s], gen_idx = c.seed_len + pos, n_mask = c.n_mask_at(s);
+  const int dot_allowed = pos == c.L - 1 ? 1 : 0;
+  const czc_hyper* hp = c.hp;
   const int slot = mp.slot[s], j = mp.sub[s], mask_id = e->cfg.mask_id, D = e->cfg.clip_proj;
   int* key = slot >= 0 ? mp.key + (size_t)slot * B * T : nullptr;
   int* rows = slot >= 0 ? mp.rows + ((size_t)slot * MEMO_SUB + j) * B * T : nullptr;
@@ -1130,9 +1171,8 @@ struct MemoRowsPlan {
   MemoRowsTab tab{};
   int *hit = nullptr, *cnt = nullptr, *list = nullptr, *tot = nullptr, *inp_c = nullptr, *col_c = nullptr, *dot_c = nullptr;
   float *bcos = nullptr, *img_c = nullptr;
-  RowHyper* hp_c = nullptr;      // czc_generate_rows_hp: the records of a compact batch's rows, gathered by its run list
-  RowDraw* draw_c = nullptr;     // czc_generate_rows_draw: their draw records, by the same list
-  int* riv_c = nullptr; float* rdelta_c = nullptr;  // czc_generate_rows_vs: their rival tables and deltas, by the same list
+  // room for the RowRecords of a compact batch's rows, gathered by its run list (a record the call does not carry has none)
+  struct { RowHyper* hp = nullptr; RowDraw* draw = nullptr; int* rival = nullptr; float* delta = nullptr; } rec_c;
   std::vector<std::vector<int32_t>> h_col_c;  // compact batch of the group in progress: the active rows' column at every step
   std::vector<int32_t> run_h;    // of the group in progress: the rows that run, ascending (host copy of list_d)
   const int* list_d = nullptr;   // of the group in progress: the device list of the rows that run (null: every row)
@@ -1141,10 +1181,10 @@ struct MemoRowsPlan {
   int n_act = 0;  // of the group in progress: rows that run (not idle and no hit)
   int branch_max[MEMO_ROWS_SUB] = {0, 0};
   // czc_generate_rows_len (len_h null otherwise): every row's token count T_r on the host; the full batch's offsets / lengths
-  // and those of every step's run list in the schedule upload (d_rag_steps: [n_steps][2 R + 1], lengths then offsets; null in
-  // a call without idle steps); d_rag_c [2 R + 1]: those of a checked step's compact batch, uploaded after the list read
+  // and those of every step's run list in the schedule upload (SchedLayout: rag, rag_steps); d_rag_c [2 R + 1]: those of a
+  // checked step's compact batch, uploaded after the list read
   const int32_t* len_h = nullptr;
-  Ragged rag_full{}; const int* d_rag_steps = nullptr; int* d_rag_c = nullptr;
+  Ragged rag_full{}; int* d_rag_c = nullptr;
   Ragged rag_c{};  // of the group in progress, where it runs on a compact batch
   const Ragged* rag(bool full) const { return len_h ? (full ? &rag_full : &rag_c) : nullptr; }
   int ctl_T() const { return len_h && !run_h.empty() ? len_h[run_h[0]] : 0; }
@@ -1155,9 +1195,11 @@ static inline int memo_rows_sig(int n_mask0, int n_sub, int col1) { return (n_ma
 
 // table = false (czc_generate_rows_from with idle steps, option off): no entries, nothing is recorded or checked; the plan
 // then only carries the compact-batch buffers and the full-batch cosines.  Idle rows (position CZC_POS_IDLE) visit no key.
-int memo_rows_begin(czc_engine* e, bool table, int R, int T, int L, int seed_len, int n_steps, const int32_t* positions,
-                    const int32_t* n_mask, int snapshot_every, bool want_cos, const std::vector<char>& audit, MemoRowsPlan* mp,
-                    const czc_draw* draw_host = nullptr) {
+int memo_rows_begin(czc_engine* e, const RowsCall& c, const std::vector<char>& audit, MemoRowsPlan* mp) {
+  const int R = c.R, T = c.T, L = c.L, seed_len = c.seed_len, n_steps = c.n_steps, snapshot_every = c.snapshot_every;
+  const int32_t *positions = c.positions, *n_mask = c.n_mask;
+  const czc_draw* draw_host = c.draw;
+  const bool table = e->memo_rows, want_cos = c.out_cos != nullptr;
   static_assert(MEMO_ROWS_SUB == MEMO_SUB, "the rows memo keeps the step memo's group size");
   mp->first.assign(n_steps, 0); mp->sub.assign(n_steps, 0); mp->group_len.assign(n_steps, 0);
   mp->record.assign(n_steps, 0); mp->check.assign(n_steps, 0);
@@ -1222,32 +1264,55 @@ int memo_rows_begin(czc_engine* e, bool table, int R, int T, int L, int seed_len
   return 0;
 }
 
+// The records of the rows a compact batch runs on: the call's own (e->rec), each gathered by the run list the batch is gathered
+// with into the plan's compact set
+int memo_rows_records(czc_engine* e, const MemoRowsPlan& mp, int n_act, RowRecords* out) {
+  const RowRecords& full = e->rec;
+  *out = full;
+  if (full.hp) {
+    if (!mp.rec_c.hp || !mp.list_d) return fail(e, CZC_ERR_STATE, "generate_rows_hp: a compact batch without room for its hyper-parameters%s");
+    E_CHECK(launch_gather_row_hyper(full.hp, mp.list_d, n_act, mp.rec_c.hp, e->st));
+    out->hp = mp.rec_c.hp;
+  }
+  if (full.draw) {
+    if (!mp.rec_c.draw || !mp.list_d) return fail(e, CZC_ERR_STATE, "generate_rows_draw: a compact batch without room for its draw records%s");
+    E_CHECK(launch_gather_row_draw(full.draw, mp.list_d, n_act, mp.rec_c.draw, e->st));
+    out->draw = mp.rec_c.draw;
+  }
+  if (full.rival) {
+    if (!mp.rec_c.rival || !mp.rec_c.delta || !mp.list_d) return fail(e, CZC_ERR_STATE, "generate_rows_vs: a compact batch without room for its rival tables%s");
+    E_CHECK(launch_gather_rows_w32(full.rival, mp.list_d, n_act, full.M, mp.rec_c.rival, e->st));
+    E_CHECK(launch_gather_rows_w32(full.delta, mp.list_d, n_act, 1, mp.rec_c.delta, e->st));
+    out->rival = mp.rec_c.rival; out->delta = mp.rec_c.delta;
+  }
+  return 0;
+}
+
 // One step of czc_generate_rows with the rows memo on, and of czc_generate_rows_from wherever a call has idle steps (with the
-// option or without: mp.table); sched / d_sched: the call's schedule ([n_steps][R] columns, CZC_POS_IDLE where a row sits the
-// step out, then [n_steps][R] '.' rules, n_pos = n_steps * R; a call with idle steps: then [n_steps][R] run lists, the rows of
-// every step that are not idle in ascending order) on the host and on the device.  A row is idle for a whole group or for none
-// of it (checked by the caller), so the group's first step decides who runs: the rows that are not idle and, where the check
-// ran, did not hit.  First step of a group in which some row
-// revisits a key: the check kernels and one read (totals and the ascending active list) give the active rows; then all of
+// option or without: mp.table); sc: the call's schedule (SchedLayout).  A row is idle for a whole group or for none of it
+// (checked by the caller), so the group's first step decides who runs: the rows that are not idle and, where the check ran, did
+// not hit.  First step of a group in which some row revisits a key: the check kernels and one read (totals and the ascending active list) give the active rows; then all of
 // them run as without the option (and record), none runs, or the step runs on a compact batch whose column / '.' arrays the
 // gather kernel builds.  The compact columns' host copy keeps the per-row n_mask = 0 re-use rule of mlm_head in force.
-int memo_rows_step(czc_engine* e, MemoRowsPlan& mp, int s, int* d_inp, int R, int T, int L, int seed_len, int n_mask, int n_mask0,
-                   int K, const czc_hyper* hp, const int32_t* sched, const int* d_sched, size_t n_pos) {
+int memo_rows_step(czc_engine* e, MemoRowsPlan& mp, const RowsCall& c, const Sched& sc, int s, int* d_inp) {
+  const int R = c.R, T = c.T, L = c.L, seed_len = c.seed_len, K = c.top_k;
   const int s0 = mp.first[s], j = mp.sub[s], g = mp.group_len[s0], mask_id = e->cfg.mask_id, D = e->cfg.clip_proj;
-  const int record = mp.record[s0];
-  const int* col0 = d_sched + (size_t)s0 * R;
-  const int* col1 = g > 1 ? d_sched + (size_t)(s0 + 1) * R : nullptr;
-  const int* col = d_sched + (size_t)s * R;
-  const int* dot = d_sched + n_pos + (size_t)s * R;
+  const int n_mask = c.n_mask_at(s), n_mask0 = c.n_mask_at(s0), record = mp.record[s0];
+  const czc_hyper* hp = c.hp;
+  const int32_t* sched = sc.h.data();
+  const int* col0 = sc.d + sc.at.cols(s0);
+  const int* col1 = g > 1 ? sc.d + sc.at.cols(s0 + 1) : nullptr;
+  const int* col = sc.d + sc.at.cols(s);
+  const int* dot = sc.d + sc.at.dots(s);
   if (j == 0) {
     mp.run_h.clear();
     for (int r = 0; r < R; ++r)
       if (sched[(size_t)s0 * R + r] >= 0) mp.run_h.push_back(r);
     mp.n_run = mp.n_act = (int)mp.run_h.size();
-    mp.list_d = mp.n_run < R ? d_sched + 2 * n_pos + (size_t)s0 * R : nullptr;  // the schedule's own run list of this step
+    mp.list_d = mp.n_run < R ? sc.d + sc.at.runs(s0) : nullptr;  // the schedule's own run list of this step
     mp.branch_max[0] = mp.branch_max[1] = 0;
     if (mp.check[s]) {
-      E_CHECK(launch_memo_rows_check(d_inp, mp.tab, col0, col1, n_mask0, g, mask_id, mp.hit, mp.cnt, mp.list, mp.tot, e->st, e->draw_rows));
+      E_CHECK(launch_memo_rows_check(d_inp, mp.tab, col0, col1, n_mask0, g, mask_id, mp.hit, mp.cnt, mp.list, mp.tot, e->st, e->rec.draw));
       int32_t* h = e->h_memo_list;
       E_HIP(hipMemcpyAsync(h, mp.tot, 16, hipMemcpyDeviceToHost, e->st));
       E_HIP(hipMemcpyAsync(h + 4, mp.list, (size_t)R * 4, hipMemcpyDeviceToHost, e->st));
@@ -1277,7 +1342,7 @@ int memo_rows_step(czc_engine* e, MemoRowsPlan& mp, int s, int* d_inp, int R, in
       }
       if (mp.len_h) {  // the compact batch's packed rows: the schedule's own for a run list, built here for a checked step's list
         const bool own = mp.list_d == mp.list;
-        if (!own && !mp.d_rag_steps) return fail(e, CZC_ERR_STATE, "generate_rows_len: a run list without its offsets%s");
+        if (!own && !sc.at.rag_steps) return fail(e, CZC_ERR_STATE, "generate_rows_len: a run list without its offsets%s");
         int32_t* h = own ? e->h_memo_list + 4 + R : nullptr;  // pinned; the previous upload from it was queued in front of this step's list read
         int M = 0, mx = 0;
         for (int i = 0; i < mp.n_act; ++i) {
@@ -1289,7 +1354,7 @@ int memo_rows_step(czc_engine* e, MemoRowsPlan& mp, int s, int* d_inp, int R, in
           h[R + mp.n_act] = M;
           E_HIP(hipMemcpyAsync(mp.d_rag_c, h, ((size_t)2 * R + 1) * 4, hipMemcpyHostToDevice, e->st));
         }
-        const int* base = own ? mp.d_rag_c : mp.d_rag_steps + (size_t)s0 * (2 * R + 1);
+        const int* base = own ? mp.d_rag_c : sc.d + sc.at.rag_step(s0);
         mp.rag_c = Ragged{base + R, base, M, mx};
       }
     }
@@ -1317,31 +1382,14 @@ int memo_rows_step(czc_engine* e, MemoRowsPlan& mp, int s, int* d_inp, int R, in
   const int32_t* col_h = mp.h_col_c[j].data();
   float* img_rows = e->d_img_n;
   const int img_B = e->img_B;
-  const RowHyper* hp_full = e->hp_rows;
-  if (hp_full) {  // the running rows' own records, by the run list the batch is gathered with
-    if (!mp.hp_c || !mp.list_d) return fail(e, CZC_ERR_STATE, "generate_rows_hp: a compact batch without room for its hyper-parameters%s");
-    E_CHECK(launch_gather_row_hyper(hp_full, mp.list_d, n_act, mp.hp_c, e->st));
-    e->hp_rows = mp.hp_c;
-  }
-  const RowDraw* draw_full = e->draw_rows;
-  if (draw_full) {
-    if (!mp.draw_c || !mp.list_d) return fail(e, CZC_ERR_STATE, "generate_rows_draw: a compact batch without room for its draw records%s");
-    E_CHECK(launch_gather_row_draw(draw_full, mp.list_d, n_act, mp.draw_c, e->st));
-    e->draw_rows = mp.draw_c;
-  }
-  const int* riv_full = e->rival_rows;
-  const float* rdelta_full = e->rival_delta;
-  if (riv_full) {  // the indices point into the whole resident batch (rival_img_all), which a compact batch leaves alone
-    if (!mp.riv_c || !mp.rdelta_c || !mp.list_d) return fail(e, CZC_ERR_STATE, "generate_rows_vs: a compact batch without room for its rival tables%s");
-    E_CHECK(launch_gather_rows_w32(riv_full, mp.list_d, n_act, e->rival_M, mp.riv_c, e->st));
-    E_CHECK(launch_gather_rows_w32(rdelta_full, mp.list_d, n_act, 1, mp.rdelta_c, e->st));
-    e->rival_rows = mp.riv_c; e->rival_delta = mp.rdelta_c;
-  }
+  const RowRecords rec_full = e->rec;
+  RowRecords rec_c;
+  E_CHECK(memo_rows_records(e, mp, n_act, &rec_c));
+  e->rec = rec_c;
   e->d_img_n = mp.img_c; e->img_B = n_act; e->memo_branch_floor = j < MEMO_ROWS_SUB ? mp.branch_max[j] : 0;
   const int rc = step_device(e, mp.inp_c, n_act, T, col_h[0], n_mask, col_h[0] - seed_len == L - 1 ? 1 : 0, K, hp, mp.col_c, mp.dot_c,
                              col_h, mp.rag(false), mp.ctl_T());
-  e->d_img_n = img_rows; e->img_B = img_B; e->memo_branch_floor = 0; e->hp_rows = hp_full; e->draw_rows = draw_full;
-  e->rival_rows = riv_full; e->rival_delta = rdelta_full;
+  e->d_img_n = img_rows; e->img_B = img_B; e->memo_branch_floor = 0; e->rec = rec_full;
   E_CHECK(rc);
   return launch_memo_rows_scatter(mp.inp_c, (const float*)e->ws["s_bcos"].p, (const int*)e->ws["p_img_max"].p, mp.list_d, n_act,
                                   mp.tab, col0, j, record, d_inp, mp.bcos, e->st) ? fail(e, CZC_ERR_HIP, "%s", g_err) : 0;
@@ -2048,68 +2096,62 @@ int czc_step(czc_engine* e, int32_t* inp, int B, int T, int gen_idx, int n_mask,
   return CZC_OK;
 }
 
-// czc_generate and czc_generate_rows.  rows = false: positions_host [n_steps], one column for the whole batch at every step (the
-// scalar kernels, the memo where the option is on).  rows = true: positions_host [n_steps, B], image_of_row_host [B] or null; the
-// schedule (column seed_len + position and the '.' rule of every row and step) is uploaded once and every step reads its slice.
-// from = true (czc_generate_rows_from, a rows call): init_ids_host is [B, T], one start row per row, and a position may be
-// CZC_POS_IDLE.  A call with idle steps appends the run list of every step to the schedule and takes the compact-batch path of
-// memo_rows_step (with the entries where option "memo_rows" is on, without them otherwise); a call without any runs as
-// czc_generate_rows does.
-// len_rows (czc_generate_rows_len, a from call whose rows differ in length; null otherwise): row r polishes len_rows[r]
-// positions and holds seed_len + len_rows[r] + 1 tokens, T is the stride of the rows and L the longest length (already checked
-// by the caller: lengths within T, tails [PAD]).  The schedule upload then also carries the packed-row offsets and lengths of
-// the full batch and of every step's run list; BERT, the MLM head's row index and the bridge run on them (Ragged).
-static int generate_impl(czc_engine* e, bool rows, bool from, int B, int T, int L, int seed_len, const int32_t* init_ids_host,
-                         const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
-                         const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp, int32_t* out_ids, float* out_cos,
-                         const int32_t* len_rows = nullptr, const czc_hyper* hp_rows_host = nullptr, const czc_draw* draw_host = nullptr,
-                         const int32_t* group_host = nullptr) {
-  if (!e || !init_ids_host || !positions_host || !hp || B <= 0 || n_steps < 0 || snapshot_every <= 0)
-    return CZC_ERR_ARG;
-  if (seed_len + L > T) return fail(e, CZC_ERR_ARG, "generate: seed_len + L > T%s");
+// ---- czc_generate and the czc_generate_rows* family --------------------------------------------------------------------
+// rows = false (czc_generate): positions [n_steps], one column for the whole batch at every step (the scalar kernels, the memo
+// where the option is on).  rows = true: positions [n_steps, R], image_of_row [R] or null; the schedule (SchedLayout) is uploaded
+// once and every step reads its slice.  from = true: init is [R, T], one start row per row, and a position may be CZC_POS_IDLE; a
+// call with idle steps takes the compact-batch path of memo_rows_step (with the entries where option "memo_rows" is on, without
+// them otherwise), a call without any runs as czc_generate_rows does.  len (rows that differ in length; null otherwise): row r
+// polishes len[r] positions and holds seed_len + len[r] + 1 tokens, T is the stride of the rows and L the longest length; BERT,
+// the MLM head's row index and the bridge then run on the packed rows (Ragged).
+
+// The checks every generate call passes, on the call as the check_* functions left it; *any_idle: some row sits a step out
+static int check_call(czc_engine* e, const RowsCall& c, bool* any_idle) {
+  const int B = c.R, T = c.T, L = c.L, n_steps = c.n_steps;
+  const int32_t *pos = c.positions, *len = c.len;
+  if (!e || !c.init || !pos || !c.hp || B <= 0 || n_steps < 0 || c.snapshot_every <= 0) return CZC_ERR_ARG;
+  if (c.seed_len + L > T) return fail(e, CZC_ERR_ARG, "generate: seed_len + L > T%s");
   E_HIP(hipSetDevice(e->dev));
   e->err[0] = 0;
-  const size_t n_pos = rows ? (size_t)n_steps * B : (size_t)n_steps;
+  const size_t n_pos = c.n_pos();
   for (size_t i = 0; i < n_pos; ++i)
-    if (positions_host[i] < (from ? CZC_POS_IDLE : 0) || positions_host[i] >= L)  // (len mode: checked per row by czc_generate_rows_len)
-      return fail(e, CZC_ERR_ARG, from ? "generate_rows_from: position outside {CZC_POS_IDLE} and [0, L)%s" : "generate: position out of range%s");
-  bool any_idle = false;
-  if (from) {
+    if (pos[i] < (c.from ? CZC_POS_IDLE : 0) || pos[i] >= L)  // (len mode: checked per row by check_lengths)
+      return fail(e, CZC_ERR_ARG, c.from ? "generate_rows_from: position outside {CZC_POS_IDLE} and [0, L)%s" : "generate: position out of range%s");
+  *any_idle = false;
+  if (c.from) {
     for (size_t i = 0; i < (size_t)B * T; ++i)
-      if (init_ids_host[i] < 0 || init_ids_host[i] >= e->cfg.bert_vocab)
+      if (c.init[i] < 0 || c.init[i] >= e->cfg.bert_vocab)
         return fail(e, CZC_ERR_ARG, "generate_rows_from: start row holds an id outside the BERT vocabulary%s");
     for (int s = 0; s < n_steps;) {  // a group: an n_mask >= 1 step plus the n_mask = 0 steps behind it
       int g = 1;
-      while (s + g < n_steps && n_mask_host && n_mask_host[s + g] <= 0) ++g;
+      while (s + g < n_steps && c.n_mask && c.n_mask[s + g] <= 0) ++g;
       for (int r = 0; r < B; ++r) {
-        const bool idle = positions_host[(size_t)s * B + r] == CZC_POS_IDLE;
-        any_idle = any_idle || idle;
+        const bool idle = pos[(size_t)s * B + r] == CZC_POS_IDLE;
+        *any_idle = *any_idle || idle;
         for (int j = 1; j < g; ++j)
-          if ((positions_host[(size_t)(s + j) * B + r] == CZC_POS_IDLE) != idle)
+          if ((pos[(size_t)(s + j) * B + r] == CZC_POS_IDLE) != idle)
             return fail(e, CZC_ERR_ARG, "generate_rows_from: a row must be idle for a whole step group (an n_mask >= 1 step and the n_mask = 0 steps behind it) or for none of it%s");
       }
       s += g;
     }
   }
-  int rag_M = 0, rag_max = 0;  // len mode: packed rows / longest row of the full batch
-  std::vector<int32_t> sched;  // rows: [n_steps][B] columns, then [n_steps][B] '.' rules (utils.py:53-59: position == L-1)
-  if (rows) {
-    if (B > CZC_MAX_ROWS || seed_len < 0 || T > CZC_MAX_BERT_LEN) return fail(e, CZC_ERR_ARG, "generate_rows: R > CZC_MAX_ROWS, seed_len < 0 or T > CZC_MAX_BERT_LEN%s");
+  if (c.rows) {
+    if (B > CZC_MAX_ROWS || c.seed_len < 0 || T > CZC_MAX_BERT_LEN) return fail(e, CZC_ERR_ARG, "generate_rows: R > CZC_MAX_ROWS, seed_len < 0 or T > CZC_MAX_BERT_LEN%s");
     if (!e->d_img_n || e->img_B <= 0) return fail(e, CZC_ERR_STATE, "image embeds not set%s");
-    if (!image_of_row_host && e->img_B != B)
+    if (!c.image_of_row && e->img_B != B)
       return fail(e, CZC_ERR_ARG, "generate_rows: image_of_row = NULL needs R equal to the resident image batch%s");
-    if (image_of_row_host)
+    if (c.image_of_row)
       for (int r = 0; r < B; ++r)
-        if (image_of_row_host[r] < 0 || image_of_row_host[r] >= e->img_B)
+        if (c.image_of_row[r] < 0 || c.image_of_row[r] >= e->img_B)
           return fail(e, CZC_ERR_ARG, "generate_rows: image_of_row outside the resident image batch%s");
-    if (e->ctl_fn && hp->control && from) {  // the callback sees the rows that run, compacted: those must share one position
+    if (e->ctl_fn && c.hp->control && c.from) {  // the callback sees the rows that run, compacted: those must share one position
       for (int s = 0; s < n_steps; ++s) {
         int shared = CZC_POS_IDLE, first_r = 0;
         for (int r = 0; r < B; ++r) {
-          const int p = positions_host[(size_t)s * B + r];
+          const int p = pos[(size_t)s * B + r];
           if (p == CZC_POS_IDLE) continue;
           // (the length is compared only between rows at one position: a row at another position is refused just below)
-          if (shared != CZC_POS_IDLE && p == shared && len_rows && len_rows[r] != len_rows[first_r])
+          if (shared != CZC_POS_IDLE && p == shared && len && len[r] != len[first_r])
             return fail(e, CZC_ERR_ARG, "generate_rows_len: a control callback is told one T, so the rows of a step that are not idle must share one length as well "
                                         "as one position; use the control tables (czc_set_lexicon / czc_set_lexicon_pos / czc_set_pos)%s");
           if (shared == CZC_POS_IDLE) first_r = r;
@@ -2119,98 +2161,122 @@ static int generate_impl(czc_engine* e, bool rows, bool from, int B, int T, int 
           shared = p;
         }
       }
-    } else if (e->ctl_fn && hp->control)  // the callback is only called on controlled steps
+    } else if (e->ctl_fn && c.hp->control)  // the callback is only called on controlled steps
       for (size_t i = 0; i < n_pos; ++i)
-        if (positions_host[i] != positions_host[i - i % B])
+        if (pos[i] != pos[i - i % B])
           return fail(e, CZC_ERR_ARG, "generate_rows: a control callback carries one gen_idx, so every row must visit the same position at a step; "
                                       "use the control tables (czc_set_lexicon / czc_set_lexicon_pos / czc_set_pos) or one czc_generate call per order%s");
-    const size_t n_rag = len_rows ? (size_t)(2 * B + 1) * (any_idle ? 1 + n_steps : 1) : 0;
-    sched.resize((any_idle ? 3 : 2) * n_pos + n_rag);
-    for (size_t i = 0; i < n_pos; ++i) {
-      sched[i] = positions_host[i] == CZC_POS_IDLE && from ? CZC_POS_IDLE : seed_len + positions_host[i];
-      sched[n_pos + i] = positions_host[i] == (len_rows ? len_rows[i % B] : L) - 1 ? 1 : 0;
+  }
+  return 0;
+}
+
+// The schedule of a rows call on the host, with its layout (czc_generate has none: its one column travels as an argument)
+static Sched build_schedule(const RowsCall& c, bool any_idle) {
+  Sched sc;
+  if (!c.rows) return sc;
+  const int B = c.R, n_steps = c.n_steps;
+  const int32_t* pos = c.positions;
+  const size_t n_pos = c.n_pos();
+  SchedLayout& at = sc.at;
+  at.R = B; at.idle = any_idle; at.dot = n_pos; at.run = 2 * n_pos; at.rag = (any_idle ? 3 : 2) * n_pos;
+  at.rag_steps = c.len && any_idle ? at.rag + at.rag_block() : 0;
+  sc.h.resize(at.rag + (c.len ? at.rag_block() * (any_idle ? 1 + n_steps : 1) : 0));
+  for (size_t i = 0; i < n_pos; ++i) {  // (utils.py:53-59: the '.' rule holds at position == L - 1)
+    sc.h[i] = pos[i] == CZC_POS_IDLE && c.from ? CZC_POS_IDLE : c.seed_len + pos[i];
+    sc.h[at.dot + i] = pos[i] == (c.len ? c.len[i % B] : c.L) - 1 ? 1 : 0;
+  }
+  if (any_idle)  // the host knows who runs: every step's rows that are not idle, ascending (the tail of a slice is not read)
+    for (int s = 0; s < n_steps; ++s) {
+      int32_t* list = sc.h.data() + at.runs(s);
+      int n = 0;
+      for (int r = 0; r < B; ++r)
+        if (pos[(size_t)s * B + r] != CZC_POS_IDLE) list[n++] = r;
+      for (; n < B; ++n) list[n] = 0;
     }
-    if (any_idle)  // the host knows who runs: every step's rows that are not idle, ascending (the tail of a slice is not read)
-      for (int s = 0; s < n_steps; ++s) {
-        int32_t* list = sched.data() + 2 * n_pos + (size_t)s * B;
-        int n = 0;
-        for (int r = 0; r < B; ++r)
-          if (positions_host[(size_t)s * B + r] != CZC_POS_IDLE) list[n++] = r;
-        for (; n < B; ++n) list[n] = 0;
-      }
-    if (len_rows) {  // [B] lengths then [B + 1] offsets: of the full batch, then (idle calls) of every step's run list
-      int32_t* blk = sched.data() + (any_idle ? 3 : 2) * n_pos;
-      for (int r = 0; r < B; ++r) {
-        blk[r] = seed_len + len_rows[r] + 1;
-        blk[B + r] = rag_M;
-        rag_M += blk[r]; rag_max = blk[r] > rag_max ? blk[r] : rag_max;
-      }
-      blk[2 * B] = rag_M;
-      for (int s = 0; s < n_steps && any_idle; ++s) {
-        int32_t* sb = blk + (size_t)(s + 1) * (2 * B + 1);
-        int n = 0, off = 0;
-        for (int r = 0; r < B; ++r)
-          if (positions_host[(size_t)s * B + r] != CZC_POS_IDLE) { sb[n] = blk[r]; sb[B + n] = off; off += blk[r]; ++n; }
-        sb[B + n] = off;
-        for (int i = n; i < B; ++i) { sb[i] = 0; sb[B + i + 1] = off; }
-      }
+  if (c.len) {  // [B] lengths then [B + 1] offsets: of the full batch, then (idle calls) of every step's run list
+    int32_t* blk = sc.h.data() + at.rag;
+    for (int r = 0; r < B; ++r) {
+      blk[r] = c.seed_len + c.len[r] + 1;
+      blk[B + r] = at.rag_M;
+      at.rag_M += blk[r]; at.rag_max = blk[r] > at.rag_max ? blk[r] : at.rag_max;
+    }
+    blk[2 * B] = at.rag_M;
+    for (int s = 0; s < n_steps && any_idle; ++s) {
+      int32_t* sb = sc.h.data() + at.rag_step(s);
+      int n = 0, off = 0;
+      for (int r = 0; r < B; ++r)
+        if (pos[(size_t)s * B + r] != CZC_POS_IDLE) { sb[n] = blk[r]; sb[B + n] = off; off += blk[r]; ++n; }
+      sb[B + n] = off;
+      for (int i = n; i < B; ++i) { sb[i] = 0; sb[B + i + 1] = off; }
     }
   }
-  int *d_inp, *d_row, *d_sched = nullptr;
-  RowHyper* d_hp_rows = nullptr;
-  RowDraw* d_draw_rows = nullptr;
-  int* d_rival = nullptr; float* d_rdelta = nullptr;
-  if (e->vs_host && !(rows && from && hp_rows_host && draw_host)) return fail(e, CZC_ERR_ARG, "generate: a rival table belongs to a rows call with per-row records%s");
-  if (draw_host && !rows) return fail(e, CZC_ERR_ARG, "generate: draw records belong to a rows call%s");
-  if (group_host && !(rows && from)) return fail(e, CZC_ERR_ARG, "generate: a group table belongs to a rows call with start rows%s");
+  return sc;
+}
+
+// What a call changes in the engine while its steps run comes back on every exit -- the resident image batch (swapped for the
+// rows' gather), the per-row records, and no later call may re-use a forward by this call's columns -- so the set-up and the steps
+// in its scope leave through E_CHECK / E_HIP.  A rows call that fails waits for the work it has queued.
+struct CallScope {
+  czc_engine* e; bool rows, ok = false;
+  float* img = e->d_img_n; int img_B = e->img_B;
+  ~CallScope() {
+    e->d_img_n = img; e->img_B = img_B; e->rec = RowRecords{};
+    if (rows) { e->bert_pruned_rows = nullptr; if (!ok) (void)hipStreamSynchronize(e->st); }
+  }
+};
+
+// The uploads of a call: the start rows and, for a rows call, the schedule, the per-row records (e->rec from here on) and the
+// gather of the rows' image embeddings, which then stand in for the resident batch (inside a CallScope)
+static int upload_call(czc_engine* e, const RowsCall& c, Sched& sc, int** d_inp) {
+  const int B = c.R, T = c.T, D = e->cfg.clip_proj;
+  auto put = [e](const char* name, const void* src, size_t bytes, void** out) -> int {
+    E_CHECK(ensure(e, name, bytes, out));
+    E_HIP(hipMemcpyAsync(*out, src, bytes, hipMemcpyHostToDevice, e->st));
+    return 0;
+  };
   { int* flag; E_CHECK(ensure(e, "s_nonfinite", 32, (void**)&flag)); E_HIP(hipMemsetAsync(flag, 0, 32, e->st)); }
-  E_CHECK(ensure(e, "g_inp", (size_t)B * T * 4, (void**)&d_inp));
-  if (from) {  // every row brings its own start row: one upload, no broadcast
-    E_HIP(hipMemcpyAsync(d_inp, init_ids_host, (size_t)B * T * 4, hipMemcpyHostToDevice, e->st));
+  if (c.from) {  // every row brings its own start row: one upload, no broadcast
+    E_CHECK(put("g_inp", c.init, (size_t)B * T * 4, (void**)d_inp));
   } else {
-    E_CHECK(ensure(e, "g_row", (size_t)T * 4, (void**)&d_row));
-    E_HIP(hipMemcpyAsync(d_row, init_ids_host, (size_t)T * 4, hipMemcpyHostToDevice, e->st));
-    E_CHECK(launch_broadcast_rows_i32(d_row, T, B, d_inp, e->st));
+    int* d_row;
+    E_CHECK(ensure(e, "g_inp", (size_t)B * T * 4, (void**)d_inp));
+    E_CHECK(put("g_row", c.init, (size_t)T * 4, (void**)&d_row));
+    E_CHECK(launch_broadcast_rows_i32(d_row, T, B, *d_inp, e->st));
   }
-  // rows: the embedding of row r is that of image image_of_row[r] -- one gather of the normalised embeds to [R, D] here, and the
-  // step sees a resident batch of R images (what the memo's compact batches do), so no tower or combine kernel changes
-  float* img_full = e->d_img_n;
-  const int img_B = e->img_B;
-  if (rows) {
-    const int D = e->cfg.clip_proj;
-    int* d_ior = nullptr; float* img_r = nullptr;
-    if (!sched.empty()) E_CHECK(ensure(e, "g_sched", sched.size() * 4, (void**)&d_sched));
-    if (image_of_row_host) {
-      E_CHECK(ensure(e, "g_ior", (size_t)B * 4, (void**)&d_ior));
-      E_CHECK(ensure(e, "g_img_r", (size_t)B * D * 4, (void**)&img_r));
-    }
-    if (!sched.empty()) E_HIP(hipMemcpyAsync(d_sched, sched.data(), sched.size() * 4, hipMemcpyHostToDevice, e->st));
-    if (hp_rows_host) {  // one record per row, uploaded once with the schedule
-      static_assert(sizeof(RowHyper) == sizeof(czc_hyper) && offsetof(RowHyper, temperature) == offsetof(czc_hyper, temperature) &&
-                    offsetof(RowHyper, control) == offsetof(czc_hyper, control) && offsetof(RowHyper, negative) == offsetof(czc_hyper, negative),
-                    "RowHyper is czc_hyper as the kernels read it");
-      E_CHECK(ensure(e, "g_hp_rows", (size_t)B * sizeof(RowHyper), (void**)&d_hp_rows));
-      E_HIP(hipMemcpyAsync(d_hp_rows, hp_rows_host, (size_t)B * sizeof(RowHyper), hipMemcpyHostToDevice, e->st));
-    }
-    if (draw_host) {  // likewise: seed, tau and step offset per row
-      static_assert(sizeof(RowDraw) == sizeof(czc_draw) && offsetof(RowDraw, seed_lo) == offsetof(czc_draw, seed) &&
-                    offsetof(RowDraw, tau) == offsetof(czc_draw, tau) && offsetof(RowDraw, step0) == offsetof(czc_draw, step0),
-                    "RowDraw is czc_draw as the kernels read it (little-endian seed halves)");
-      E_CHECK(ensure(e, "g_draw_rows", (size_t)B * sizeof(RowDraw), (void**)&d_draw_rows));
-      E_HIP(hipMemcpyAsync(d_draw_rows, draw_host, (size_t)B * sizeof(RowDraw), hipMemcpyHostToDevice, e->st));
-    }
-    if (e->vs_host) {  // czc_generate_rows_vs (its checks have run): the [R, M] table and the [R] deltas, once, with the schedule
-      E_CHECK(ensure(e, "g_rival", (size_t)B * e->vs_M * 4, (void**)&d_rival));
-      E_CHECK(ensure(e, "g_rdelta", (size_t)B * 4, (void**)&d_rdelta));
-      E_HIP(hipMemcpyAsync(d_rival, e->vs_host, (size_t)B * e->vs_M * 4, hipMemcpyHostToDevice, e->st));
-      E_HIP(hipMemcpyAsync(d_rdelta, e->vs_delta_host, (size_t)B * 4, hipMemcpyHostToDevice, e->st));
-    }
-    if (image_of_row_host) {
-      E_HIP(hipMemcpyAsync(d_ior, image_of_row_host, (size_t)B * 4, hipMemcpyHostToDevice, e->st));
-      E_CHECK(launch_gather_rows_f32(img_full, d_ior, B, D, img_r, e->st));
-      e->d_img_n = img_r; e->img_B = B;
-    }
+  if (!c.rows) return 0;
+  RowRecords rec;  // one record per row, uploaded once with the schedule
+  static_assert(sizeof(RowHyper) == sizeof(czc_hyper) && offsetof(RowHyper, temperature) == offsetof(czc_hyper, temperature) &&
+                offsetof(RowHyper, control) == offsetof(czc_hyper, control) && offsetof(RowHyper, negative) == offsetof(czc_hyper, negative),
+                "RowHyper is czc_hyper as the kernels read it");
+  static_assert(sizeof(RowDraw) == sizeof(czc_draw) && offsetof(RowDraw, seed_lo) == offsetof(czc_draw, seed) &&
+                offsetof(RowDraw, tau) == offsetof(czc_draw, tau) && offsetof(RowDraw, step0) == offsetof(czc_draw, step0),
+                "RowDraw is czc_draw as the kernels read it (little-endian seed halves)");
+  if (!sc.h.empty()) E_CHECK(put("g_sched", sc.h.data(), sc.h.size() * 4, (void**)&sc.d));
+  if (c.hp_rows) E_CHECK(put("g_hp_rows", c.hp_rows, (size_t)B * sizeof(RowHyper), (void**)&rec.hp));
+  if (c.draw) E_CHECK(put("g_draw_rows", c.draw, (size_t)B * sizeof(RowDraw), (void**)&rec.draw));
+  if (c.rival) {  // the indices point into the whole resident batch, not into the rows' gather below
+    E_CHECK(put("g_rival", c.rival, (size_t)B * c.M * 4, (void**)&rec.rival));
+    E_CHECK(put("g_rdelta", c.delta, (size_t)B * 4, (void**)&rec.delta));
+    rec.M = c.M; rec.img_all = e->d_img_n; rec.n_img = e->img_B;
   }
+  e->rec = rec;
+  // the embedding of row r is that of image image_of_row[r] -- one gather of the normalised embeds to [R, D] here, and the step
+  // sees a resident batch of R images (what the memo's compact batches do), so no tower or combine kernel changes
+  if (c.image_of_row) {
+    int* d_ior; float* img_r;
+    E_CHECK(ensure(e, "g_img_r", (size_t)B * D * 4, (void**)&img_r));
+    E_CHECK(put("g_ior", c.image_of_row, (size_t)B * 4, (void**)&d_ior));
+    E_CHECK(launch_gather_rows_f32(e->d_img_n, d_ior, B, D, img_r, e->st));
+    e->d_img_n = img_r; e->img_B = B;
+  }
+  return 0;
+}
+
+// The steps of a call and its snapshots (inside a CallScope, behind upload_call)
+static int run_steps(czc_engine* e, const RowsCall& c, const Sched& sc, int* d_inp) {
+  const int B = c.R, T = c.T, L = c.L, seed_len = c.seed_len, n_steps = c.n_steps, snapshot_every = c.snapshot_every;
+  const bool rows = c.rows;
+  float* out_cos = c.out_cos;
   // what this call returns of a step: the ids it leaves in d_inp and, at the snapshot steps, the winner's cosine
   // AUDIT steps -- the snapshot step of every fourth sweep, starting with the first -- take the full selection for every
   // image: there the guard (czc_refine_guard) measures the screening tower on all images although most other steps are
@@ -2228,74 +2294,72 @@ static int generate_impl(czc_engine* e, bool rows, bool from, int B, int T, int 
     } }
   MemoPlan mp;
   const bool memo = e->memo && !rows;  // the memo's keys are (image, position, n_mask); a rows call has option "memo_rows"
-  if (memo) E_CHECK(memo_begin(e, B, T, n_steps, positions_host, n_mask_host, snapshot_every, out_cos != nullptr, audit, &mp));
-  int snap = 0, rc = 0;
+  if (memo) E_CHECK(memo_begin(e, c, audit, &mp));
   MemoRowsPlan mrp;
-  const bool memo_rows = rows && (e->memo_rows || any_idle) && n_steps > 0;  // the compact-batch path, with or without entries
-  // (a failure here leaves through the exit below, which hands the resident image batch back)
-  if (memo_rows) rc = memo_rows_begin(e, e->memo_rows, B, T, L, seed_len, n_steps, positions_host, n_mask_host, snapshot_every, out_cos != nullptr, audit, &mrp, draw_host);
+  const bool memo_rows = rows && (e->memo_rows || sc.at.idle) && n_steps > 0;  // the compact-batch path, with or without entries
+  if (memo_rows) E_CHECK(memo_rows_begin(e, c, audit, &mrp));
   Ragged rag_full{};
-  if (len_rows && d_sched) {
-    const size_t base = (any_idle ? 3 : 2) * n_pos;
-    rag_full = Ragged{d_sched + base + B, d_sched + base, rag_M, rag_max};
-    if (memo_rows && !rc) {
-      mrp.len_h = sched.data() + base;
+  if (c.len && sc.d) {
+    rag_full = Ragged{sc.d + sc.at.rag + B, sc.d + sc.at.rag, sc.at.rag_M, sc.at.rag_max};
+    if (memo_rows) {
+      mrp.len_h = sc.h.data() + sc.at.rag;
       mrp.rag_full = rag_full;
-      mrp.d_rag_steps = any_idle ? d_sched + base + (2 * B + 1) : nullptr;
-      if (ensure(e, "mr_rag_c", ((size_t)2 * B + 1) * 4, (void**)&mrp.d_rag_c)) rc = CZC_ERR_HIP;
+      E_CHECK(ensure(e, "mr_rag_c", sc.at.rag_block() * 4, (void**)&mrp.d_rag_c));
     }
   }
-  // a row that has not run yet in this call reports cosine 0 (the reference's best_clip_score start value)
-  if (memo_rows && d_hp_rows && !rc && ensure(e, "mr_hp_c", (size_t)B * sizeof(RowHyper), (void**)&mrp.hp_c)) rc = CZC_ERR_HIP;
-  if (memo_rows && d_draw_rows && !rc && ensure(e, "mr_draw_c", (size_t)B * sizeof(RowDraw), (void**)&mrp.draw_c)) rc = CZC_ERR_HIP;
-  e->hp_rows = rc ? nullptr : d_hp_rows;  // (handed back with the image batch below)
-  e->draw_rows = rc ? nullptr : d_draw_rows;
-  if (memo_rows && d_rival && !rc && (ensure(e, "mr_riv_c", (size_t)B * e->vs_M * 4, (void**)&mrp.riv_c) ||
-                                      ensure(e, "mr_rdelta_c", (size_t)B * 4, (void**)&mrp.rdelta_c))) rc = CZC_ERR_HIP;
-  if (d_rival && !rc) { e->rival_rows = d_rival; e->rival_delta = d_rdelta; e->rival_M = e->vs_M; e->rival_img_all = img_full; e->rival_n_img = img_B; }
-  // czc_generate_rows_tied (its checks have run): the group table goes up once, behind the schedule
+  if (memo_rows && e->rec.hp) E_CHECK(ensure(e, "mr_hp_c", (size_t)B * sizeof(RowHyper), (void**)&mrp.rec_c.hp));
+  if (memo_rows && e->rec.draw) E_CHECK(ensure(e, "mr_draw_c", (size_t)B * sizeof(RowDraw), (void**)&mrp.rec_c.draw));
+  if (memo_rows && e->rec.rival) {
+    E_CHECK(ensure(e, "mr_riv_c", (size_t)B * c.M * 4, (void**)&mrp.rec_c.rival));
+    E_CHECK(ensure(e, "mr_rdelta_c", (size_t)B * 4, (void**)&mrp.rec_c.delta));
+  }
+  // czc_generate_rows_tied (check_groups has run): the group table goes up once, behind the schedule
   TiePlan tie;
-  const bool tied = group_host != nullptr && n_steps > 0;
-  if (tied && !rc) rc = tie_begin(e, B, T, seed_len, group_host, len_rows, out_cos != nullptr, &tie);
-  if (memo_rows && any_idle && !rc && hipMemsetAsync(mrp.bcos, 0, (size_t)B * 4, e->st) != hipSuccess) rc = fail(e, CZC_ERR_HIP, "generate_rows_from: clearing the cosines%s");
-  for (int s = 0; s < n_steps && !rc; ++s) {
-    const int pos = positions_host[rows ? (size_t)s * B : (size_t)s];
-    const int nm = n_mask_host ? n_mask_host[s] : 1;
+  const bool tied = c.group != nullptr && n_steps > 0;
+  if (tied) E_CHECK(tie_begin(e, B, T, seed_len, c.group, c.len, out_cos != nullptr, &tie));
+  // a row that has not run yet in this call reports cosine 0 (the reference's best_clip_score start value)
+  if (memo_rows && sc.at.idle && hipMemsetAsync(mrp.bcos, 0, (size_t)B * 4, e->st) != hipSuccess)
+    return fail(e, CZC_ERR_HIP, "generate_rows_from: clearing the cosines%s");
+  int snap = 0;
+  for (int s = 0; s < n_steps; ++s) {
+    const int pos = c.positions[rows ? (size_t)s * B : (size_t)s];
+    const int nm = c.n_mask_at(s), dot = pos == L - 1 ? 1 : 0;
     const bool snap_idx = (s + 1) % snapshot_every == 0;
     e->gate_now = e->refine && e->refine_gate_delta > 0.f && e->refine_guard_dev > 0.f && !audit[s];
     e->gate_need_cos = snap_idx && out_cos != nullptr;
     e->in_generate = true;
-    e->draw_step = (unsigned)s;
-    if (memo_rows) rc = memo_rows_step(e, mrp, s, d_inp, B, T, L, seed_len, nm, n_mask_host ? n_mask_host[mrp.first[s]] : 1, top_k, hp,
-                                       sched.data(), d_sched, n_pos);
-    else if (rows) rc = step_device(e, d_inp, B, T, seed_len + pos, nm, pos == L - 1 ? 1 : 0, top_k, hp, d_sched + (size_t)s * B,
-                               d_sched + n_pos + (size_t)s * B, sched.data() + (size_t)s * B, len_rows ? &rag_full : nullptr,
-                               len_rows ? seed_len + len_rows[0] + 1 : 0);  // (a callback call's rows share one length: checked above)
-    else if (memo) rc = memo_step(e, mp, s, d_inp, B, T, seed_len + pos, nm, pos == L - 1 ? 1 : 0, top_k, hp);
-    else rc = step_device(e, d_inp, B, T, seed_len + pos, nm, pos == L - 1 ? 1 : 0, top_k, hp);
-    if (rc) break;
+    e->rec.step = (unsigned)s;
+    if (memo_rows) E_CHECK(memo_rows_step(e, mrp, c, sc, s, d_inp));
+    else if (rows) E_CHECK(step_device(e, d_inp, B, T, seed_len + pos, nm, dot, c.top_k, c.hp, sc.d + sc.at.cols(s), sc.d + sc.at.dots(s),
+                                       sc.h.data() + sc.at.cols(s), c.len ? &rag_full : nullptr,
+                                       c.len ? seed_len + c.len[0] + 1 : 0));  // (a callback call's rows share one length: checked above)
+    else if (memo) E_CHECK(memo_step(e, mp, c, s, d_inp));
+    else E_CHECK(step_device(e, d_inp, B, T, seed_len + pos, nm, dot, c.top_k, c.hp));
     // the tie: one launch on the full batch, behind whatever the step did (in place, compact batch and scatter, memo fill)
-    if (tied && launch_tie_rows(d_inp, B, T, d_sched + (size_t)s * B, tie.d_gor, tie.d_off, tie.d_rows, e->st)) { rc = fail(e, CZC_ERR_HIP, "%s", g_err); break; }
-    if (tied && snap_idx && out_cos) {  // a tied call returns the cosine of the caption as it stands, one score per group
-      rc = tie_score(e, tie, d_inp, B, T, len_rows != nullptr);
-      if (rc) break;
-    }
+    if (tied && launch_tie_rows(d_inp, B, T, sc.d + sc.at.cols(s), tie.d_gor, tie.d_off, tie.d_rows, e->st)) return fail(e, CZC_ERR_HIP, "%s", g_err);
+    // a tied call returns the cosine of the caption as it stands, one score per group
+    if (tied && snap_idx && out_cos) E_CHECK(tie_score(e, tie, d_inp, B, T, c.len != nullptr));
     if (snap_idx) {
-      hipError_t h = hipSuccess;
-      if (out_ids)
-        h = hipMemcpyAsync(out_ids + (size_t)snap * B * T, d_inp, (size_t)B * T * 4, hipMemcpyDefault, e->st);
+      hipError_t h = c.out_ids ? hipMemcpyAsync(c.out_ids + (size_t)snap * B * T, d_inp, (size_t)B * T * 4, hipMemcpyDefault, e->st) : hipSuccess;
       if (out_cos && h == hipSuccess)  // memo: the full-batch cosines (a compacted step leaves B_act of them in s_bcos)
         h = hipMemcpyAsync(out_cos + (size_t)snap * B, tied ? tie.cos : memo ? mp.bcos : memo_rows ? mrp.bcos : e->ws["s_bcos"].p, (size_t)B * 4,
                            hipMemcpyDefault, e->st);
-      if (h != hipSuccess) { snprintf(e->err, sizeof(e->err), "generate: snapshot copy -> %s", hipGetErrorString(h)); rc = CZC_ERR_HIP; }
+      if (h != hipSuccess) { snprintf(e->err, sizeof(e->err), "generate: snapshot copy -> %s", hipGetErrorString(h)); return CZC_ERR_HIP; }
       ++snap;
     }
   }
-  // rows: the resident image batch comes back whatever happened, and no later call may re-use a forward by this call's columns
-  e->d_img_n = img_full; e->img_B = img_B; e->hp_rows = nullptr; e->draw_rows = nullptr; e->draw_step = 0;
-  e->rival_rows = nullptr; e->rival_delta = nullptr; e->rival_M = 0; e->rival_img_all = nullptr; e->rival_n_img = 0;
-  if (rows) { e->bert_pruned_rows = nullptr; if (rc) (void)hipStreamSynchronize(e->st); }
-  if (rc) return rc;
+  return 0;
+}
+
+static int generate_impl(czc_engine* e, const RowsCall& c) {
+  bool any_idle = false;
+  if (int rc = check_call(e, c, &any_idle)) return rc;
+  Sched sc = build_schedule(c, any_idle);
+  { CallScope scope{e, c.rows};
+    int* d_inp = nullptr;
+    E_CHECK(upload_call(e, c, sc, &d_inp));
+    E_CHECK(run_steps(e, c, sc, d_inp));
+    scope.ok = true; }
   E_HIP(hipMemcpyAsync(e->h_totals + 9, e->ws["s_nonfinite"].p, 24, hipMemcpyDeviceToHost, e->st));
   E_HIP(hipStreamSynchronize(e->st));
   if (e->h_totals[9]) return fail(e, CZC_ERR_OVERFLOW, "non-finite CLIP cosine: an fp16 quantity overflowed in a tower (fp16 residual rows: set option resid16 = 0 on the bf16 engine, refine_rows16 = 0 on the refine engine; fp16 operands: use CZC_PREC_SPLIT)%s");
@@ -2304,176 +2368,119 @@ static int generate_impl(czc_engine* e, bool rows, bool from, int B, int T, int 
   return CZC_OK;
 }
 
-int czc_generate(czc_engine* e, int B, int T, int L, int seed_len, const int32_t* init_ids_host, int top_k,
-                 int n_steps, const int32_t* positions_host, const int32_t* n_mask_host, int snapshot_every,
-                 const czc_hyper* hp, int32_t* out_ids, float* out_cos) {
-  return generate_impl(e, false, false, B, T, L, seed_len, init_ids_host, nullptr, top_k, n_steps, positions_host, n_mask_host,
-                       snapshot_every, hp, out_ids, out_cos);
-}
+// ---- the checks of the optional per-row arrays: each validates its array and, where the array carries nothing, drops it, so
+// that the call underneath is the simpler one, bit for bit
 
-int czc_generate_rows(czc_engine* e, int R, int T, int L, int seed_len, const int32_t* init_ids_host,
-                      const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
-                      const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp, int32_t* out_ids, float* out_cos) {
-  return generate_impl(e, true, false, R, T, L, seed_len, init_ids_host, image_of_row_host, top_k, n_steps, positions_host, n_mask_host,
-                       snapshot_every, hp, out_ids, out_cos);
-}
-
-int czc_generate_rows_from(czc_engine* e, int R, int T, int L, int seed_len, const int32_t* init_rows_host,
-                           const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
-                           const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp, int32_t* out_ids, float* out_cos) {
-  return generate_impl(e, true, true, R, T, L, seed_len, init_rows_host, image_of_row_host, top_k, n_steps, positions_host, n_mask_host,
-                       snapshot_every, hp, out_ids, out_cos);
-}
-
-// czc_generate_rows_len, and czc_generate_rows_hp behind its own checks (hp_rows_host [R]: hp is then its first entry)
-static int rows_len_impl(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
-                         const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
-                         const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp, int32_t* out_ids, float* out_cos,
-                         const czc_hyper* hp_rows_host, const czc_draw* draw_host = nullptr, const int32_t* group_host = nullptr) {
-  if (!e || !init_rows_host || !len_of_row_host || !positions_host || !hp || R <= 0 || n_steps < 0 || snapshot_every <= 0)
+// len (czc_generate_rows_len and above): rows of one length that fill the stride are czc_generate_rows_from itself
+static int check_lengths(czc_engine* e, RowsCall& c) {
+  const int R = c.R, T = c.T, seed_len = c.seed_len;
+  if (!e || !c.init || !c.len || !c.positions || !c.hp || R <= 0 || c.n_steps < 0 || c.snapshot_every <= 0)
     return CZC_ERR_ARG;
   e->err[0] = 0;
   if (R > CZC_MAX_ROWS || seed_len < 0 || T > CZC_MAX_BERT_LEN) return fail(e, CZC_ERR_ARG, "generate_rows_len: R > CZC_MAX_ROWS, seed_len < 0 or T > CZC_MAX_BERT_LEN%s");
   bool uniform = true;
   int L_max = 0;
   for (int r = 0; r < R; ++r) {
-    const int Lr = len_of_row_host[r];
+    const int Lr = c.len[r];
     if (Lr < 1 || Lr > T - seed_len - 1) return fail(e, CZC_ERR_ARG, "generate_rows_len: len_of_row outside [1, T - seed_len - 1]%s");
     uniform = uniform && seed_len + Lr + 1 == T;
     L_max = Lr > L_max ? Lr : L_max;
     for (int t = seed_len + Lr + 1; t < T; ++t)
-      if (init_rows_host[(size_t)r * T + t] != 0) return fail(e, CZC_ERR_ARG, "generate_rows_len: the columns behind a row's seed_len + len_of_row + 1 tokens must hold id 0 ([PAD])%s");
+      if (c.init[(size_t)r * T + t] != 0) return fail(e, CZC_ERR_ARG, "generate_rows_len: the columns behind a row's seed_len + len_of_row + 1 tokens must hold id 0 ([PAD])%s");
   }
-  for (int s = 0; s < n_steps; ++s) {
-    const int nm = n_mask_host ? n_mask_host[s] : 1;
+  for (int s = 0; s < c.n_steps; ++s) {
+    const int nm = c.n_mask_at(s);
     for (int r = 0; r < R; ++r) {
-      const int p = positions_host[(size_t)s * R + r];
-      if (p < CZC_POS_IDLE || p >= len_of_row_host[r]) return fail(e, CZC_ERR_ARG, "generate_rows_len: position outside {CZC_POS_IDLE} and [0, len_of_row[r])%s");
-      if (p >= 0 && nm > 1 && p + nm > len_of_row_host[r])
+      const int p = c.positions[(size_t)s * R + r];
+      if (p < CZC_POS_IDLE || p >= c.len[r]) return fail(e, CZC_ERR_ARG, "generate_rows_len: position outside {CZC_POS_IDLE} and [0, len_of_row[r])%s");
+      if (p >= 0 && nm > 1 && p + nm > c.len[r])
         return fail(e, CZC_ERR_ARG, "generate_rows_len: an n_mask >= 2 step masks past the row's last position (it needs position + n_mask <= len_of_row[r])%s");
     }
   }
-  // rows of one length that fill the stride: czc_generate_rows_from itself, bit for bit
-  return generate_impl(e, true, true, R, T, L_max, seed_len, init_rows_host, image_of_row_host, top_k, n_steps, positions_host, n_mask_host,
-                       snapshot_every, hp, out_ids, out_cos, uniform ? nullptr : len_of_row_host, hp_rows_host, draw_host, group_host);
+  c.L = L_max;
+  if (uniform) c.len = nullptr;
+  return 0;
 }
 
-int czc_generate_rows_len(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
-                          const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
-                          const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp, int32_t* out_ids, float* out_cos) {
-  return rows_len_impl(e, R, T, seed_len, init_rows_host, len_of_row_host, image_of_row_host, top_k, n_steps, positions_host, n_mask_host,
-                       snapshot_every, hp, out_ids, out_cos, nullptr);
-}
-
-// czc_generate_rows_hp, and czc_generate_rows_draw behind its own checks (draw_host [R], some tau > 0; null: no row draws)
-static int rows_hp_impl(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
-                        const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
-                        const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp_of_row_host, int32_t* out_ids, float* out_cos,
-                        const czc_draw* draw_host, const int32_t* group_host = nullptr) {
-  if (!e || !init_rows_host || !positions_host || !hp_of_row_host || R <= 0 || n_steps < 0 || snapshot_every <= 0) return CZC_ERR_ARG;
+// hp_rows (czc_generate_rows_hp and above): equal entries are the scalar call with entry 0 (its scalar kernels)
+static int check_hypers(czc_engine* e, RowsCall& c) {
+  const int R = c.R;
+  if (!e || !c.init || !c.positions || !c.hp_rows || R <= 0 || c.n_steps < 0 || c.snapshot_every <= 0) return CZC_ERR_ARG;
   e->err[0] = 0;
   if (R > CZC_MAX_ROWS) return fail(e, CZC_ERR_ARG, "generate_rows_hp: R > CZC_MAX_ROWS%s");
   bool uniform = true, any_ctl = false, one_signal = true;
   for (int r = 0; r < R; ++r) {
-    const czc_hyper& h = hp_of_row_host[r];
+    const czc_hyper& h = c.hp_rows[r];
     if (h.control < 0 || h.control > 2) return fail(e, CZC_ERR_ARG, "generate_rows_hp: control outside {0, 1, 2}%s");
     if (!std::isfinite(h.temperature) || !(h.temperature > 0.f)) return fail(e, CZC_ERR_ARG, "generate_rows_hp: a temperature must be finite and > 0%s");
     if (!std::isfinite(h.alpha) || !std::isfinite(h.beta) || !std::isfinite(h.gamma)) return fail(e, CZC_ERR_ARG, "generate_rows_hp: alpha, beta and gamma must be finite%s");
-    uniform = uniform && memcmp(&h, &hp_of_row_host[0], sizeof(czc_hyper)) == 0;
+    uniform = uniform && memcmp(&h, &c.hp_rows[0], sizeof(czc_hyper)) == 0;
     any_ctl = any_ctl || h.control != 0;
-    one_signal = one_signal && h.control == hp_of_row_host[0].control && (h.negative != 0) == (hp_of_row_host[0].negative != 0);
+    one_signal = one_signal && h.control == c.hp_rows[0].control && (h.negative != 0) == (c.hp_rows[0].negative != 0);
   }
   // the host scorer is configured for one signal, and it is called for every row of a controlled step
   if (e->ctl_fn && any_ctl && !one_signal)
     return fail(e, CZC_ERR_ARG, "generate_rows_hp: a control callback scores one signal, so every row must share control and negative; "
                                 "use the control tables (czc_set_lexicon / czc_set_lexicon_pos / czc_set_pos)%s");
   for (int r = 0; r < R; ++r) {  // step_device's messages, before any GPU work
-    if (hp_of_row_host[r].control == 1 && !e->ctl_fn && !e->d_lex && !e->d_lex_pos)
+    if (c.hp_rows[r].control == 1 && !e->ctl_fn && !e->d_lex && !e->d_lex_pos)
       return fail(e, CZC_ERR_STATE, "sentiment path needs a lexicon (czc_set_lexicon / czc_set_lexicon_pos) or czc_set_control_callback%s");
-    if (hp_of_row_host[r].control == 2 && !e->ctl_fn && !e->d_pos_tags)
+    if (c.hp_rows[r].control == 2 && !e->ctl_fn && !e->d_pos_tags)
       return fail(e, CZC_ERR_STATE, "POS path needs czc_set_pos or czc_set_control_callback%s");
   }
-  // equal entries: the existing call, bit for bit (its scalar kernels)
-  const czc_hyper* rows_hp = uniform && !e->vs_host ? nullptr : hp_of_row_host;  // (a rival call always carries its records)
-  if (len_of_row_host)
-    return rows_len_impl(e, R, T, seed_len, init_rows_host, len_of_row_host, image_of_row_host, top_k, n_steps, positions_host, n_mask_host,
-                         snapshot_every, &hp_of_row_host[0], out_ids, out_cos, rows_hp, draw_host, group_host);
-  return generate_impl(e, true, true, R, T, T - seed_len - 1, seed_len, init_rows_host, image_of_row_host, top_k, n_steps, positions_host,
-                       n_mask_host, snapshot_every, &hp_of_row_host[0], out_ids, out_cos, nullptr, rows_hp, draw_host, group_host);
+  c.hp = &c.hp_rows[0];
+  if (uniform && !c.rival) c.hp_rows = nullptr;  // (a rival call always carries its records)
+  return 0;
 }
 
-int czc_generate_rows_hp(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
-                         const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
-                         const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp_of_row_host, int32_t* out_ids, float* out_cos) {
-  return rows_hp_impl(e, R, T, seed_len, init_rows_host, len_of_row_host, image_of_row_host, top_k, n_steps, positions_host, n_mask_host,
-                      snapshot_every, hp_of_row_host, out_ids, out_cos, nullptr);
-}
-
-static int rows_draw_impl(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
-                          const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
-                          const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp_of_row_host,
-                          const czc_draw* draw_of_row_host, int32_t* out_ids, float* out_cos, const int32_t* group_host) {
-  if (!e || R <= 0 || n_steps < 0) return CZC_ERR_ARG;
+// draw (czc_generate_rows_draw and above; may be null): no row with tau > 0 is czc_generate_rows_hp itself
+static int check_draws(czc_engine* e, RowsCall& c) {
+  if (!e || c.R <= 0 || c.n_steps < 0) return CZC_ERR_ARG;
   e->err[0] = 0;
-  if (R > CZC_MAX_ROWS) return fail(e, CZC_ERR_ARG, "generate_rows_draw: R > CZC_MAX_ROWS%s");
+  if (c.R > CZC_MAX_ROWS) return fail(e, CZC_ERR_ARG, "generate_rows_draw: R > CZC_MAX_ROWS%s");
   bool any = false;
-  for (int r = 0; r < R && draw_of_row_host; ++r) {
-    const czc_draw& d = draw_of_row_host[r];
+  for (int r = 0; r < c.R && c.draw; ++r) {
+    const czc_draw& d = c.draw[r];
     if (!std::isfinite(d.tau) || d.tau < 0.f) return fail(e, CZC_ERR_ARG, "generate_rows_draw: a tau must be finite and >= 0%s");
-    if ((uint64_t)d.step0 + (uint64_t)n_steps > 0xffffffffull)
+    if ((uint64_t)d.step0 + (uint64_t)c.n_steps > 0xffffffffull)
       return fail(e, CZC_ERR_ARG, "generate_rows_draw: step0 + n_steps does not fit the 32-bit step counter%s");
     any = any || d.tau > 0.f;
   }
-  // no row draws: czc_generate_rows_hp itself, bit for bit
-  return rows_hp_impl(e, R, T, seed_len, init_rows_host, len_of_row_host, image_of_row_host, top_k, n_steps, positions_host, n_mask_host,
-                      snapshot_every, hp_of_row_host, out_ids, out_cos, any || (e->vs_host && draw_of_row_host) ? draw_of_row_host : nullptr, group_host);
+  if (!any && !c.rival) c.draw = nullptr;  // (a rival call always carries its records)
+  return 0;
 }
 
-int czc_generate_rows_draw(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
-                           const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
-                           const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp_of_row_host,
-                           const czc_draw* draw_of_row_host, int32_t* out_ids, float* out_cos) {
-  return rows_draw_impl(e, R, T, seed_len, init_rows_host, len_of_row_host, image_of_row_host, top_k, n_steps, positions_host, n_mask_host,
-                        snapshot_every, hp_of_row_host, draw_of_row_host, out_ids, out_cos, nullptr);
-}
-
-// czc_generate_rows_draw with rows tied into groups that hold one sentence: the group checks, then the draw call's own
-int czc_generate_rows_tied(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
-                           const int32_t* image_of_row_host, const int32_t* group_of_row_host, int top_k, int n_steps,
-                           const int32_t* positions_host, const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp_of_row_host,
-                           const czc_draw* draw_of_row_host, int32_t* out_ids, float* out_cos) {
-  if (!group_of_row_host)
-    return rows_draw_impl(e, R, T, seed_len, init_rows_host, len_of_row_host, image_of_row_host, top_k, n_steps, positions_host, n_mask_host,
-                          snapshot_every, hp_of_row_host, draw_of_row_host, out_ids, out_cos, nullptr);
-  if (!e || !init_rows_host || !positions_host || R <= 0 || n_steps < 0) return CZC_ERR_ARG;
+// group (czc_generate_rows_tied and above, not null): rows tied into groups that hold one sentence
+static int check_groups(czc_engine* e, const RowsCall& c) {
+  const int R = c.R, T = c.T;
+  if (!e || !c.init || !c.positions || R <= 0 || c.n_steps < 0) return CZC_ERR_ARG;
   e->err[0] = 0;
-  if (R > CZC_MAX_ROWS || seed_len < 0 || T <= 0 || T > CZC_MAX_BERT_LEN) return fail(e, CZC_ERR_ARG, "generate_rows_tied: R > CZC_MAX_ROWS, seed_len < 0 or T outside [1, CZC_MAX_BERT_LEN]%s");
-  for (int s = 0; s < n_steps && n_mask_host; ++s)
-    if (n_mask_host[s] != 1) return fail(e, CZC_ERR_ARG, "generate_rows_tied: every step needs n_mask = 1 (the n_mask = 0 re-use of a forward across a tie is not defined; span order is refused)%s");
+  if (R > CZC_MAX_ROWS || c.seed_len < 0 || T <= 0 || T > CZC_MAX_BERT_LEN) return fail(e, CZC_ERR_ARG, "generate_rows_tied: R > CZC_MAX_ROWS, seed_len < 0 or T outside [1, CZC_MAX_BERT_LEN]%s");
+  for (int s = 0; s < c.n_steps && c.n_mask; ++s)
+    if (c.n_mask[s] != 1) return fail(e, CZC_ERR_ARG, "generate_rows_tied: every step needs n_mask = 1 (the n_mask = 0 re-use of a forward across a tie is not defined; span order is refused)%s");
   std::vector<int32_t> lead(R, -1);  // by group id: its lowest-numbered row
   for (int r = 0; r < R; ++r) {
-    const int g = group_of_row_host[r];
+    const int g = c.group[r];
     if (g < 0 || g >= R) return fail(e, CZC_ERR_ARG, "generate_rows_tied: a group id outside [0, R)%s");
     if (lead[g] < 0) { lead[g] = r; continue; }
     const int l = lead[g];
-    if (len_of_row_host && len_of_row_host[r] != len_of_row_host[l])
+    if (c.len && c.len[r] != c.len[l])
       return fail(e, CZC_ERR_ARG, "generate_rows_tied: the rows of a group must share one length%s");
-    if (image_of_row_host ? image_of_row_host[r] != image_of_row_host[l] : true)  // (image_of_row = NULL: row r has image r)
+    if (c.image_of_row ? c.image_of_row[r] != c.image_of_row[l] : true)  // (image_of_row = NULL: row r has image r)
       return fail(e, CZC_ERR_ARG, "generate_rows_tied: the rows of a group must share one image%s");
-    if (memcmp(init_rows_host + (size_t)r * T, init_rows_host + (size_t)l * T, (size_t)T * 4) != 0)
+    if (memcmp(c.init + (size_t)r * T, c.init + (size_t)l * T, (size_t)T * 4) != 0)
       return fail(e, CZC_ERR_ARG, "generate_rows_tied: the rows of a group must bring the same start row%s");
   }
   std::vector<int32_t> seen((size_t)R * T, -1);  // (group, position) -> the last step a member ran there
-  for (int s = 0; s < n_steps; ++s)
+  for (int s = 0; s < c.n_steps; ++s)
     for (int r = 0; r < R; ++r) {
-      const int p = positions_host[(size_t)s * R + r];
+      const int p = c.positions[(size_t)s * R + r];
       if (p < 0 || p >= T) continue;  // idle; anything else out of range is refused by the call's own checks
-      int32_t& was = seen[(size_t)group_of_row_host[r] * T + p];
+      int32_t& was = seen[(size_t)c.group[r] * T + p];
       if (was == s) return fail(e, CZC_ERR_ARG, "generate_rows_tied: two rows of a group run at the same position in one step%s");
       was = s;
     }
-  return rows_draw_impl(e, R, T, seed_len, init_rows_host, len_of_row_host, image_of_row_host, top_k, n_steps, positions_host, n_mask_host,
-                        snapshot_every, hp_of_row_host, draw_of_row_host, out_ids, out_cos, group_of_row_host);
+  return 0;
 }
 
 // the checks of a rival table, shared by czc_generate_rows_vs and czc_score_rows_vs (image_of_row and R are checked by then);
@@ -2501,38 +2508,117 @@ static int check_rivals(czc_engine* e, const char* who, int R, const int32_t* im
   return 0;
 }
 
+// rival + delta (czc_generate_rows_vs, rival not null): no row with both a rival and a delta is czc_generate_rows_tied itself.
+// A call that keeps its table always carries per-row records: rows without a draw record keep the first argmax (tau = 0)
+static int check_rival_table(czc_engine* e, RowsCall& c) {
+  const int R = c.R;
+  if (!e || R <= 0 || !c.delta) return CZC_ERR_ARG;
+  e->err[0] = 0;
+  if (R > CZC_MAX_ROWS) return fail(e, CZC_ERR_ARG, "generate_rows_vs: R > CZC_MAX_ROWS%s");
+  if (!e->d_img_n || e->img_B <= 0) return fail(e, CZC_ERR_STATE, "image embeds not set%s");
+  if (!c.image_of_row && e->img_B != R) return fail(e, CZC_ERR_ARG, "generate_rows_vs: image_of_row = NULL needs R equal to the resident image batch%s");
+  for (int r = 0; r < R && c.image_of_row; ++r)
+    if (c.image_of_row[r] < 0 || c.image_of_row[r] >= e->img_B)
+      return fail(e, CZC_ERR_ARG, "generate_rows_vs: image_of_row outside the resident image batch%s");
+  bool active = false;
+  E_CHECK(check_rivals(e, "generate_rows_vs", R, c.image_of_row, c.rival, c.M, c.delta, &active));
+  if (!active) { c.rival = nullptr; return 0; }
+  if (e->refine)
+    return fail(e, CZC_ERR_STATE, "generate_rows_vs: the selection and guard bounds of CZC_PREC_REFINE were derived for the softmax-K term alone; "
+                                  "run rows with rivals on a CZC_PREC_SPLIT engine%s");
+  if (!c.draw) { c.no_draw.assign((size_t)R, czc_draw{0, 0.f, 0}); c.draw = c.no_draw.data(); }
+  return 0;
+}
+
+// The driver: the checks of the arrays the entry point has, outermost argument first, then the call itself
+static int run_call(czc_engine* e, RowsCall& c) {
+  int rc = 0;
+  if (c.level >= CALL_VS && c.rival && (rc = check_rival_table(e, c))) return rc;
+  if (c.level >= CALL_TIED && c.group && (rc = check_groups(e, c))) return rc;
+  if (c.level >= CALL_DRAW && (rc = check_draws(e, c))) return rc;
+  if (c.level >= CALL_HP && (rc = check_hypers(e, c))) return rc;
+  if (c.level >= CALL_LEN && (c.len || c.level == CALL_LEN)) { if ((rc = check_lengths(e, c))) return rc; }
+  else if (c.level >= CALL_HP) c.L = c.T - c.seed_len - 1;  // lens = NULL: the shape of czc_generate_rows_from
+  return generate_impl(e, c);
+}
+
+static RowsCall new_call(CallLevel level, int R, int T, int seed_len, int top_k, int n_steps, int snapshot_every, int32_t* out_ids, float* out_cos) {
+  RowsCall c;
+  c.level = level; c.rows = level >= CALL_ROWS; c.from = level >= CALL_FROM; c.out_ids = out_ids; c.out_cos = out_cos;
+  c.R = R; c.T = T; c.seed_len = seed_len; c.top_k = top_k; c.n_steps = n_steps; c.snapshot_every = snapshot_every;
+  return c;
+}
+
+int czc_generate(czc_engine* e, int B, int T, int L, int seed_len, const int32_t* init_ids_host, int top_k,
+                 int n_steps, const int32_t* positions_host, const int32_t* n_mask_host, int snapshot_every,
+                 const czc_hyper* hp, int32_t* out_ids, float* out_cos) {
+  RowsCall c = new_call(CALL_GENERATE, B, T, seed_len, top_k, n_steps, snapshot_every, out_ids, out_cos);
+  c.L = L; c.init = init_ids_host; c.positions = positions_host; c.n_mask = n_mask_host; c.hp = hp;
+  return run_call(e, c);
+}
+
+int czc_generate_rows(czc_engine* e, int R, int T, int L, int seed_len, const int32_t* init_ids_host,
+                      const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
+                      const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp, int32_t* out_ids, float* out_cos) {
+  RowsCall c = new_call(CALL_ROWS, R, T, seed_len, top_k, n_steps, snapshot_every, out_ids, out_cos);
+  c.L = L; c.init = init_ids_host; c.image_of_row = image_of_row_host; c.positions = positions_host; c.n_mask = n_mask_host; c.hp = hp;
+  return run_call(e, c);
+}
+
+int czc_generate_rows_from(czc_engine* e, int R, int T, int L, int seed_len, const int32_t* init_rows_host,
+                           const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
+                           const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp, int32_t* out_ids, float* out_cos) {
+  RowsCall c = new_call(CALL_FROM, R, T, seed_len, top_k, n_steps, snapshot_every, out_ids, out_cos);
+  c.L = L; c.init = init_rows_host; c.image_of_row = image_of_row_host; c.positions = positions_host; c.n_mask = n_mask_host; c.hp = hp;
+  return run_call(e, c);
+}
+
+int czc_generate_rows_len(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
+                          const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
+                          const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp, int32_t* out_ids, float* out_cos) {
+  RowsCall c = new_call(CALL_LEN, R, T, seed_len, top_k, n_steps, snapshot_every, out_ids, out_cos);
+  c.init = init_rows_host; c.len = len_of_row_host; c.image_of_row = image_of_row_host; c.positions = positions_host; c.n_mask = n_mask_host; c.hp = hp;
+  return run_call(e, c);
+}
+
+int czc_generate_rows_hp(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
+                         const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
+                         const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp_of_row_host, int32_t* out_ids, float* out_cos) {
+  RowsCall c = new_call(CALL_HP, R, T, seed_len, top_k, n_steps, snapshot_every, out_ids, out_cos);
+  c.init = init_rows_host; c.len = len_of_row_host; c.image_of_row = image_of_row_host; c.positions = positions_host; c.n_mask = n_mask_host;
+  c.hp_rows = hp_of_row_host;
+  return run_call(e, c);
+}
+
+int czc_generate_rows_draw(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
+                           const int32_t* image_of_row_host, int top_k, int n_steps, const int32_t* positions_host,
+                           const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp_of_row_host,
+                           const czc_draw* draw_of_row_host, int32_t* out_ids, float* out_cos) {
+  RowsCall c = new_call(CALL_DRAW, R, T, seed_len, top_k, n_steps, snapshot_every, out_ids, out_cos);
+  c.init = init_rows_host; c.len = len_of_row_host; c.image_of_row = image_of_row_host; c.positions = positions_host; c.n_mask = n_mask_host;
+  c.hp_rows = hp_of_row_host; c.draw = draw_of_row_host;
+  return run_call(e, c);
+}
+
+int czc_generate_rows_tied(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
+                           const int32_t* image_of_row_host, const int32_t* group_of_row_host, int top_k, int n_steps,
+                           const int32_t* positions_host, const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp_of_row_host,
+                           const czc_draw* draw_of_row_host, int32_t* out_ids, float* out_cos) {
+  RowsCall c = new_call(CALL_TIED, R, T, seed_len, top_k, n_steps, snapshot_every, out_ids, out_cos);
+  c.init = init_rows_host; c.len = len_of_row_host; c.image_of_row = image_of_row_host; c.positions = positions_host; c.n_mask = n_mask_host;
+  c.hp_rows = hp_of_row_host; c.draw = draw_of_row_host; c.group = group_of_row_host;
+  return run_call(e, c);
+}
+
 int czc_generate_rows_vs(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
                          const int32_t* image_of_row_host, const int32_t* group_of_row_host, int top_k, int n_steps,
                          const int32_t* positions_host, const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp_of_row_host,
                          const czc_draw* draw_of_row_host, const int32_t* rival_of_row_host, int M, const float* delta_of_row_host,
                          int32_t* out_ids, float* out_cos) {
-  bool active = false;
-  if (rival_of_row_host) {
-    if (!e || R <= 0 || !delta_of_row_host) return CZC_ERR_ARG;
-    e->err[0] = 0;
-    if (R > CZC_MAX_ROWS) return fail(e, CZC_ERR_ARG, "generate_rows_vs: R > CZC_MAX_ROWS%s");
-    if (!e->d_img_n || e->img_B <= 0) return fail(e, CZC_ERR_STATE, "image embeds not set%s");
-    if (!image_of_row_host && e->img_B != R) return fail(e, CZC_ERR_ARG, "generate_rows_vs: image_of_row = NULL needs R equal to the resident image batch%s");
-    for (int r = 0; r < R && image_of_row_host; ++r)
-      if (image_of_row_host[r] < 0 || image_of_row_host[r] >= e->img_B)
-        return fail(e, CZC_ERR_ARG, "generate_rows_vs: image_of_row outside the resident image batch%s");
-    E_CHECK(check_rivals(e, "generate_rows_vs", R, image_of_row_host, rival_of_row_host, M, delta_of_row_host, &active));
-  }
-  // no row has both a rival and a delta: czc_generate_rows_tied itself, bit for bit
-  if (!active)
-    return czc_generate_rows_tied(e, R, T, seed_len, init_rows_host, len_of_row_host, image_of_row_host, group_of_row_host, top_k, n_steps,
-                                  positions_host, n_mask_host, snapshot_every, hp_of_row_host, draw_of_row_host, out_ids, out_cos);
-  if (e->refine)
-    return fail(e, CZC_ERR_STATE, "generate_rows_vs: the selection and guard bounds of CZC_PREC_REFINE were derived for the softmax-K term alone; "
-                                  "run rows with rivals on a CZC_PREC_SPLIT engine%s");
-  // the rival path always carries per-row records: rows without a draw record keep the first argmax (tau = 0)
-  std::vector<czc_draw> no_draw;
-  if (!draw_of_row_host) { no_draw.assign((size_t)R, czc_draw{0, 0.f, 0}); draw_of_row_host = no_draw.data(); }
-  e->vs_host = rival_of_row_host; e->vs_delta_host = delta_of_row_host; e->vs_M = M;
-  const int rc = czc_generate_rows_tied(e, R, T, seed_len, init_rows_host, len_of_row_host, image_of_row_host, group_of_row_host, top_k, n_steps,
-                                        positions_host, n_mask_host, snapshot_every, hp_of_row_host, draw_of_row_host, out_ids, out_cos);
-  e->vs_host = nullptr; e->vs_delta_host = nullptr; e->vs_M = 0;
-  return rc;
+  RowsCall c = new_call(CALL_VS, R, T, seed_len, top_k, n_steps, snapshot_every, out_ids, out_cos);
+  c.init = init_rows_host; c.len = len_of_row_host; c.image_of_row = image_of_row_host; c.positions = positions_host; c.n_mask = n_mask_host;
+  c.hp_rows = hp_of_row_host; c.draw = draw_of_row_host; c.group = group_of_row_host; c.rival = rival_of_row_host; c.M = M; c.delta = delta_of_row_host;
+  return run_call(e, c);
 }
 
 static int score_rows_impl(czc_engine* e, const char* who, const int32_t* rows, int R, int T, int seed_len, const int32_t* len_of_row_host,

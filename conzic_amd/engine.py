@@ -6,6 +6,7 @@ device pointers of torch tensors) across the C ABI of include/conzic_hip.h.
 from __future__ import annotations
 
 import ctypes as C
+from types import SimpleNamespace
 from typing import Dict, Iterable, Optional, Sequence
 
 import numpy as np
@@ -46,6 +47,29 @@ def draw_array(draws: Sequence[native.Draw]):
             raise TypeError(f"draws[{i}] is {type(d).__name__}, not native.Draw")
         arr[i].seed, arr[i].tau, arr[i].step0 = d.seed, d.tau, d.step0
     return arr if ds else arr[:0]
+
+
+_ABSENT = object()   # an argument the method does not have (None is a value: NULL, or zeros for deltas)
+
+
+def _row_vector(name: str, what: str, x, n: int, unit: str = "rows", dtype=np.int32):
+    """contiguous 1-D `dtype` array of n entries from `x` (None passes through); `name`: the method, for the ValueError text"""
+    if x is None:
+        return None
+    v = np.ascontiguousarray(x, dtype=dtype).reshape(-1)
+    if v.size != n:
+        raise ValueError(f"{name}: {what} has {v.size} entries for {n} {unit}")
+    return v
+
+
+def _rival_table(name: str, rivals, R: int):
+    """int32 [R, M] from `rivals` (None passes through)."""
+    if rivals is None:
+        return None
+    rv = np.ascontiguousarray(rivals, dtype=np.int32)
+    if rv.ndim != 2 or rv.shape[0] != R or rv.shape[1] < 1:
+        raise ValueError(f"{name}: rivals must be [R, M] with R = {R} and M >= 1, got {rv.shape}")
+    return rv
 
 
 def make_config(bert_cfg, clip_cfg, special: Dict[str, int], precision: int) -> native.Config:
@@ -370,34 +394,60 @@ class Engine:
         self._ck(rc, "czc_generate")
         return ids, cos
 
+    def _rows_call(self, name: str, call, init, positions, seed_len: int, L: Optional[int] = None, lens=None, need_lens: bool = False,
+                   hypers=_ABSENT, draws=None, groups=None, rivals=None, deltas=_ABSENT, image_of_row=None, n_mask=None,
+                   snapshot_every: Optional[int] = None, want_cos: bool = True):
+        """The one path of every generate_rows* method: checked, contiguous arrays of whatever per-row arguments the method has
+        (`name` goes into the ValueError texts), the snapshot interval, the two outputs, then czc_<name>(handle, *call(a)), where
+        `a` holds the sizes and the pointers (None = NULL), and the error check.  A new per-row argument is normalised here."""
+        pos = np.ascontiguousarray(positions, dtype=np.int32)
+        init = np.ascontiguousarray(init, dtype=np.int32)
+        if pos.ndim != 2 or pos.shape[1] < 1:
+            raise ValueError(f"{name}: positions must be [n_steps, R]")
+        n_steps, R = pos.shape
+        if name == "generate_rows":   # one start row [T] for every row
+            T = init.size
+        elif init.ndim != 2 or init.shape[0] != R or init.shape[1] < 1:
+            raise ValueError(f"{name}: init_rows must be [R, T] with R = {R}, got {init.shape}")
+        else:
+            T = init.shape[1]
+        if need_lens and lens is None:
+            raise TypeError(f"{name}: lens is required")
+        ln = _row_vector(name, "lens", lens, R)
+        hp = None if hypers is _ABSENT else hyper_array(hypers)
+        if hp is not None and len(hp) != R:
+            raise ValueError(f"{name}: hypers has {len(hp)} entries for {R} rows")
+        dr = None if draws is None else draw_array(draws)
+        if dr is not None and len(dr) != R:
+            raise ValueError(f"{name}: draws has {len(dr)} entries for {R} rows")
+        gr = _row_vector(name, "groups", groups, R)
+        ior = _row_vector(name, "image_of_row", image_of_row, R)
+        rv = _rival_table(name, rivals, R)
+        dl = None if deltas is _ABSENT else _row_vector(name, "deltas", np.zeros((R,), np.float32) if deltas is None else deltas, R,
+                                                        dtype=np.float32)
+        nm = _row_vector(name, "n_mask", n_mask, n_steps, "steps")
+        every = snapshot_every or (L if L is not None else max(int(ln.max()) if ln is not None else T - seed_len - 1, 1))
+        S = n_steps // every
+        ids = np.empty((S, R, T), dtype=np.int32)
+        cos = np.empty((S, R), dtype=np.float32) if want_cos else None
+        a = SimpleNamespace(R=R, T=T, n_steps=n_steps, every=every, init=_ptr(init), pos=_ptr(pos), lens=_ptr(ln), hypers=hp, draws=dr,
+                            groups=_ptr(gr), ior=_ptr(ior), rivals=_ptr(rv), M=0 if rv is None else int(rv.shape[1]), deltas=_ptr(dl),
+                            n_mask=_ptr(nm), ids=_ptr(ids), cos=_ptr(cos))
+        rc = getattr(self.lib, "czc_" + name)(self.h, *call(a))
+        if rc:
+            self._raise_scorer_error()
+        self._ck(rc, "czc_" + name)
+        return ids, cos
+
     def generate_rows(self, init_ids: Sequence[int], L: int, seed_len: int, top_k: int, positions, hyper: native.Hyper,
                       image_of_row: Optional[Sequence[int]] = None, n_mask: Optional[Sequence[int]] = None,
                       snapshot_every: Optional[int] = None, want_cos: bool = True):
         """czc_generate_rows: `positions` int [n_steps, R], row r visits positions[s][r] at step s and polishes a caption for
         resident image image_of_row[r] (None: row r = image r).  Returns (ids int32 [S,R,T], cos fp32 [S,R]) per snapshot."""
-        init = np.ascontiguousarray(init_ids, dtype=np.int32)
-        T = init.size
-        pos = np.ascontiguousarray(positions, dtype=np.int32)
-        if pos.ndim != 2 or pos.shape[1] < 1:
-            raise ValueError("generate_rows: positions must be [n_steps, R]")
-        n_steps, R = pos.shape
-        ior = None if image_of_row is None else np.ascontiguousarray(image_of_row, dtype=np.int32).reshape(-1)
-        if ior is not None and ior.size != R:
-            raise ValueError(f"generate_rows: image_of_row has {ior.size} entries for {R} rows")
-        nm = None if n_mask is None else np.ascontiguousarray(n_mask, dtype=np.int32).reshape(-1)
-        if nm is not None and nm.size != n_steps:
-            raise ValueError(f"generate_rows: n_mask has {nm.size} entries for {n_steps} steps")
-        every = snapshot_every or L
-        S = n_steps // every
-        ids = np.empty((S, R, T), dtype=np.int32)
-        cos = np.empty((S, R), dtype=np.float32) if want_cos else None
-        rc = self.lib.czc_generate_rows(self.h, R, T, L, seed_len, init.ctypes.data, None if ior is None else ior.ctypes.data,
-                                        top_k, n_steps, pos.ctypes.data, None if nm is None else nm.ctypes.data, every,
-                                        C.byref(hyper), ids.ctypes.data, None if cos is None else cos.ctypes.data)
-        if rc:
-            self._raise_scorer_error()
-        self._ck(rc, "czc_generate_rows")
-        return ids, cos
+        return self._rows_call("generate_rows", lambda a: (a.R, a.T, L, seed_len, a.init, a.ior, top_k, a.n_steps, a.pos, a.n_mask, a.every,
+                                                           C.byref(hyper), a.ids, a.cos),
+                               init_ids, positions, seed_len, L=L, image_of_row=image_of_row, n_mask=n_mask,
+                               snapshot_every=snapshot_every, want_cos=want_cos)
 
     def generate_rows_from(self, init_rows, L: int, seed_len: int, top_k: int, positions, hyper: native.Hyper,
                            image_of_row: Optional[Sequence[int]] = None, n_mask: Optional[Sequence[int]] = None,
@@ -405,31 +455,10 @@ class Engine:
         """czc_generate_rows_from: generate_rows with a start row per row (`init_rows` int [R, T]: infilling, resume, polishing a
         draft) and positions that may be native.POS_IDLE (the row sits that step out).  Returns (ids int32 [S,R,T], cos fp32
         [S,R]) per snapshot; cos is 0 while a row has not run a step yet."""
-        init = np.ascontiguousarray(init_rows, dtype=np.int32)
-        pos = np.ascontiguousarray(positions, dtype=np.int32)
-        if pos.ndim != 2 or pos.shape[1] < 1:
-            raise ValueError("generate_rows_from: positions must be [n_steps, R]")
-        n_steps, R = pos.shape
-        if init.ndim != 2 or init.shape[0] != R or init.shape[1] < 1:
-            raise ValueError(f"generate_rows_from: init_rows must be [R, T] with R = {R}, got {init.shape}")
-        T = init.shape[1]
-        ior = None if image_of_row is None else np.ascontiguousarray(image_of_row, dtype=np.int32).reshape(-1)
-        if ior is not None and ior.size != R:
-            raise ValueError(f"generate_rows_from: image_of_row has {ior.size} entries for {R} rows")
-        nm = None if n_mask is None else np.ascontiguousarray(n_mask, dtype=np.int32).reshape(-1)
-        if nm is not None and nm.size != n_steps:
-            raise ValueError(f"generate_rows_from: n_mask has {nm.size} entries for {n_steps} steps")
-        every = snapshot_every or L
-        S = n_steps // every
-        ids = np.empty((S, R, T), dtype=np.int32)
-        cos = np.empty((S, R), dtype=np.float32) if want_cos else None
-        rc = self.lib.czc_generate_rows_from(self.h, R, T, L, seed_len, init.ctypes.data, None if ior is None else ior.ctypes.data,
-                                             top_k, n_steps, pos.ctypes.data, None if nm is None else nm.ctypes.data, every,
-                                             C.byref(hyper), ids.ctypes.data, None if cos is None else cos.ctypes.data)
-        if rc:
-            self._raise_scorer_error()
-        self._ck(rc, "czc_generate_rows_from")
-        return ids, cos
+        return self._rows_call("generate_rows_from", lambda a: (a.R, a.T, L, seed_len, a.init, a.ior, top_k, a.n_steps, a.pos, a.n_mask,
+                                                                a.every, C.byref(hyper), a.ids, a.cos),
+                               init_rows, positions, seed_len, L=L, image_of_row=image_of_row, n_mask=n_mask,
+                               snapshot_every=snapshot_every, want_cos=want_cos)
 
     def generate_rows_len(self, init_rows, lens, seed_len: int, top_k: int, positions, hyper: native.Hyper,
                           image_of_row: Optional[Sequence[int]] = None, n_mask: Optional[Sequence[int]] = None,
@@ -438,35 +467,10 @@ class Engine:
         holds seed_len + lens[r] + 1 tokens, then id 0), `lens` int [R], `positions` int [n_steps, R] with positions[s][r] in
         [0, lens[r]) or native.POS_IDLE.  Returns (ids int32 [S,R,T], cos fp32 [S,R]) per snapshot (snapshot_every defaults to
         the longest length); the padding tails stay 0."""
-        init = np.ascontiguousarray(init_rows, dtype=np.int32)
-        pos = np.ascontiguousarray(positions, dtype=np.int32)
-        if pos.ndim != 2 or pos.shape[1] < 1:
-            raise ValueError("generate_rows_len: positions must be [n_steps, R]")
-        n_steps, R = pos.shape
-        if init.ndim != 2 or init.shape[0] != R or init.shape[1] < 1:
-            raise ValueError(f"generate_rows_len: init_rows must be [R, T] with R = {R}, got {init.shape}")
-        T = init.shape[1]
-        ln = np.ascontiguousarray(lens, dtype=np.int32).reshape(-1)
-        if ln.size != R:
-            raise ValueError(f"generate_rows_len: lens has {ln.size} entries for {R} rows")
-        ior = None if image_of_row is None else np.ascontiguousarray(image_of_row, dtype=np.int32).reshape(-1)
-        if ior is not None and ior.size != R:
-            raise ValueError(f"generate_rows_len: image_of_row has {ior.size} entries for {R} rows")
-        nm = None if n_mask is None else np.ascontiguousarray(n_mask, dtype=np.int32).reshape(-1)
-        if nm is not None and nm.size != n_steps:
-            raise ValueError(f"generate_rows_len: n_mask has {nm.size} entries for {n_steps} steps")
-        every = snapshot_every or max(int(ln.max()), 1)
-        S = n_steps // every
-        ids = np.empty((S, R, T), dtype=np.int32)
-        cos = np.empty((S, R), dtype=np.float32) if want_cos else None
-        rc = self.lib.czc_generate_rows_len(self.h, R, T, seed_len, init.ctypes.data, ln.ctypes.data,
-                                            None if ior is None else ior.ctypes.data, top_k, n_steps, pos.ctypes.data,
-                                            None if nm is None else nm.ctypes.data, every, C.byref(hyper), ids.ctypes.data,
-                                            None if cos is None else cos.ctypes.data)
-        if rc:
-            self._raise_scorer_error()
-        self._ck(rc, "czc_generate_rows_len")
-        return ids, cos
+        return self._rows_call("generate_rows_len", lambda a: (a.R, a.T, seed_len, a.init, a.lens, a.ior, top_k, a.n_steps, a.pos, a.n_mask,
+                                                               a.every, C.byref(hyper), a.ids, a.cos),
+                               init_rows, positions, seed_len, lens=lens, need_lens=True, image_of_row=image_of_row, n_mask=n_mask,
+                               snapshot_every=snapshot_every, want_cos=want_cos)
 
     def generate_rows_hp(self, init_rows, lens, seed_len: int, top_k: int, positions, hypers: Sequence[native.Hyper],
                          image_of_row: Optional[Sequence[int]] = None, n_mask: Optional[Sequence[int]] = None,
@@ -474,38 +478,10 @@ class Engine:
         """czc_generate_rows_hp: generate_rows_len with a native.Hyper per row (`hypers`, R entries: row r's own temperature,
         alpha, beta, gamma, control and negative).  `lens` None: every row has T - seed_len - 1 positions (the shape of
         generate_rows_from).  Returns (ids int32 [S,R,T], cos fp32 [S,R]) per snapshot."""
-        init = np.ascontiguousarray(init_rows, dtype=np.int32)
-        pos = np.ascontiguousarray(positions, dtype=np.int32)
-        if pos.ndim != 2 or pos.shape[1] < 1:
-            raise ValueError("generate_rows_hp: positions must be [n_steps, R]")
-        n_steps, R = pos.shape
-        if init.ndim != 2 or init.shape[0] != R or init.shape[1] < 1:
-            raise ValueError(f"generate_rows_hp: init_rows must be [R, T] with R = {R}, got {init.shape}")
-        T = init.shape[1]
-        ln = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32).reshape(-1)
-        if ln is not None and ln.size != R:
-            raise ValueError(f"generate_rows_hp: lens has {ln.size} entries for {R} rows")
-        hp = hyper_array(hypers)
-        if len(hp) != R:
-            raise ValueError(f"generate_rows_hp: hypers has {len(hp)} entries for {R} rows")
-        ior = None if image_of_row is None else np.ascontiguousarray(image_of_row, dtype=np.int32).reshape(-1)
-        if ior is not None and ior.size != R:
-            raise ValueError(f"generate_rows_hp: image_of_row has {ior.size} entries for {R} rows")
-        nm = None if n_mask is None else np.ascontiguousarray(n_mask, dtype=np.int32).reshape(-1)
-        if nm is not None and nm.size != n_steps:
-            raise ValueError(f"generate_rows_hp: n_mask has {nm.size} entries for {n_steps} steps")
-        every = snapshot_every or max(int(ln.max()) if ln is not None else T - seed_len - 1, 1)
-        S = n_steps // every
-        ids = np.empty((S, R, T), dtype=np.int32)
-        cos = np.empty((S, R), dtype=np.float32) if want_cos else None
-        rc = self.lib.czc_generate_rows_hp(self.h, R, T, seed_len, init.ctypes.data, None if ln is None else ln.ctypes.data,
-                                           None if ior is None else ior.ctypes.data, top_k, n_steps, pos.ctypes.data,
-                                           None if nm is None else nm.ctypes.data, every, hp, ids.ctypes.data,
-                                           None if cos is None else cos.ctypes.data)
-        if rc:
-            self._raise_scorer_error()
-        self._ck(rc, "czc_generate_rows_hp")
-        return ids, cos
+        return self._rows_call("generate_rows_hp", lambda a: (a.R, a.T, seed_len, a.init, a.lens, a.ior, top_k, a.n_steps, a.pos, a.n_mask,
+                                                              a.every, a.hypers, a.ids, a.cos),
+                               init_rows, positions, seed_len, lens=lens, hypers=hypers, image_of_row=image_of_row, n_mask=n_mask,
+                               snapshot_every=snapshot_every, want_cos=want_cos)
 
     def generate_rows_draw(self, init_rows, lens, seed_len: int, top_k: int, positions, hypers: Sequence[native.Hyper],
                            draws: Optional[Sequence[native.Draw]], image_of_row: Optional[Sequence[int]] = None,
@@ -513,41 +489,10 @@ class Engine:
         """czc_generate_rows_draw: generate_rows_hp with a native.Draw per row (`draws`, R entries or None: row r's seed, tau and
         step offset).  A row with tau > 0 draws its winner from softmax_K(final_score / tau) with a counter-based generator keyed
         by its seed; tau == 0 keeps the first argmax.  Returns (ids int32 [S,R,T], cos fp32 [S,R]) per snapshot."""
-        init = np.ascontiguousarray(init_rows, dtype=np.int32)
-        pos = np.ascontiguousarray(positions, dtype=np.int32)
-        if pos.ndim != 2 or pos.shape[1] < 1:
-            raise ValueError("generate_rows_draw: positions must be [n_steps, R]")
-        n_steps, R = pos.shape
-        if init.ndim != 2 or init.shape[0] != R or init.shape[1] < 1:
-            raise ValueError(f"generate_rows_draw: init_rows must be [R, T] with R = {R}, got {init.shape}")
-        T = init.shape[1]
-        ln = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32).reshape(-1)
-        if ln is not None and ln.size != R:
-            raise ValueError(f"generate_rows_draw: lens has {ln.size} entries for {R} rows")
-        hp = hyper_array(hypers)
-        if len(hp) != R:
-            raise ValueError(f"generate_rows_draw: hypers has {len(hp)} entries for {R} rows")
-        dr = None if draws is None else draw_array(draws)
-        if dr is not None and len(dr) != R:
-            raise ValueError(f"generate_rows_draw: draws has {len(dr)} entries for {R} rows")
-        ior = None if image_of_row is None else np.ascontiguousarray(image_of_row, dtype=np.int32).reshape(-1)
-        if ior is not None and ior.size != R:
-            raise ValueError(f"generate_rows_draw: image_of_row has {ior.size} entries for {R} rows")
-        nm = None if n_mask is None else np.ascontiguousarray(n_mask, dtype=np.int32).reshape(-1)
-        if nm is not None and nm.size != n_steps:
-            raise ValueError(f"generate_rows_draw: n_mask has {nm.size} entries for {n_steps} steps")
-        every = snapshot_every or max(int(ln.max()) if ln is not None else T - seed_len - 1, 1)
-        S = n_steps // every
-        ids = np.empty((S, R, T), dtype=np.int32)
-        cos = np.empty((S, R), dtype=np.float32) if want_cos else None
-        rc = self.lib.czc_generate_rows_draw(self.h, R, T, seed_len, init.ctypes.data, None if ln is None else ln.ctypes.data,
-                                             None if ior is None else ior.ctypes.data, top_k, n_steps, pos.ctypes.data,
-                                             None if nm is None else nm.ctypes.data, every, hp, dr, ids.ctypes.data,
-                                             None if cos is None else cos.ctypes.data)
-        if rc:
-            self._raise_scorer_error()
-        self._ck(rc, "czc_generate_rows_draw")
-        return ids, cos
+        return self._rows_call("generate_rows_draw", lambda a: (a.R, a.T, seed_len, a.init, a.lens, a.ior, top_k, a.n_steps, a.pos, a.n_mask,
+                                                                a.every, a.hypers, a.draws, a.ids, a.cos),
+                               init_rows, positions, seed_len, lens=lens, hypers=hypers, draws=draws, image_of_row=image_of_row,
+                               n_mask=n_mask, snapshot_every=snapshot_every, want_cos=want_cos)
 
     def generate_rows_tied(self, init_rows, lens, seed_len: int, top_k: int, positions, hypers: Sequence[native.Hyper],
                            draws: Optional[Sequence[native.Draw]], groups: Optional[Sequence[int]],
@@ -557,41 +502,10 @@ class Engine:
         generate_rows_draw itself).  The rows of a group hold one sentence: after every step each row's winner is written
         into its siblings, so W rows polish W positions of one caption per step.  Every step masks one position.  Returns
         (ids int32 [S,R,T], cos fp32 [S,R]) per snapshot; with groups, cos is the score_rows cosine of the merged caption."""
-        init = np.ascontiguousarray(init_rows, dtype=np.int32)
-        pos = np.ascontiguousarray(positions, dtype=np.int32)
-        if pos.ndim != 2 or pos.shape[1] < 1:
-            raise ValueError("generate_rows_tied: positions must be [n_steps, R]")
-        n_steps, R = pos.shape
-        if init.ndim != 2 or init.shape[0] != R or init.shape[1] < 1:
-            raise ValueError(f"generate_rows_tied: init_rows must be [R, T] with R = {R}, got {init.shape}")
-        T = init.shape[1]
-        ln = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32).reshape(-1)
-        if ln is not None and ln.size != R:
-            raise ValueError(f"generate_rows_tied: lens has {ln.size} entries for {R} rows")
-        hp = hyper_array(hypers)
-        if len(hp) != R:
-            raise ValueError(f"generate_rows_tied: hypers has {len(hp)} entries for {R} rows")
-        dr = None if draws is None else draw_array(draws)
-        if dr is not None and len(dr) != R:
-            raise ValueError(f"generate_rows_tied: draws has {len(dr)} entries for {R} rows")
-        gr = None if groups is None else np.ascontiguousarray(groups, dtype=np.int32).reshape(-1)
-        if gr is not None and gr.size != R:
-            raise ValueError(f"generate_rows_tied: groups has {gr.size} entries for {R} rows")
-        ior = None if image_of_row is None else np.ascontiguousarray(image_of_row, dtype=np.int32).reshape(-1)
-        if ior is not None and ior.size != R:
-            raise ValueError(f"generate_rows_tied: image_of_row has {ior.size} entries for {R} rows")
-        every = snapshot_every or max(int(ln.max()) if ln is not None else T - seed_len - 1, 1)
-        S = n_steps // every
-        ids = np.empty((S, R, T), dtype=np.int32)
-        cos = np.empty((S, R), dtype=np.float32) if want_cos else None
-        rc = self.lib.czc_generate_rows_tied(self.h, R, T, seed_len, init.ctypes.data, None if ln is None else ln.ctypes.data,
-                                             None if ior is None else ior.ctypes.data, None if gr is None else gr.ctypes.data,
-                                             top_k, n_steps, pos.ctypes.data, None, every, hp, dr, ids.ctypes.data,
-                                             None if cos is None else cos.ctypes.data)
-        if rc:
-            self._raise_scorer_error()
-        self._ck(rc, "czc_generate_rows_tied")
-        return ids, cos
+        return self._rows_call("generate_rows_tied", lambda a: (a.R, a.T, seed_len, a.init, a.lens, a.ior, a.groups, top_k, a.n_steps, a.pos,
+                                                                None, a.every, a.hypers, a.draws, a.ids, a.cos),
+                               init_rows, positions, seed_len, lens=lens, hypers=hypers, draws=draws, groups=groups,
+                               image_of_row=image_of_row, snapshot_every=snapshot_every, want_cos=want_cos)
 
     def score_rows(self, rows, seed_len: int, lens: Optional[Sequence[int]] = None,
                    image_of_row: Optional[Sequence[int]] = None) -> np.ndarray:
@@ -600,33 +514,17 @@ class Engine:
         if hasattr(rows, "data_ptr"):   # a contiguous int32 torch tensor, on the device or the host: scored where it lies
             if str(rows.dtype) != "torch.int32" or not rows.is_contiguous():
                 raise ValueError("score_rows: a tensor must be contiguous int32")
-            r, ptr = rows, rows.data_ptr()
+            r = rows
         else:
             r = np.ascontiguousarray(rows, dtype=np.int32)
-            ptr = r.ctypes.data
         if r.ndim != 2 or r.shape[0] < 1 or r.shape[1] < 1:
             raise ValueError(f"score_rows: rows must be [R, T], got {tuple(r.shape)}")
         R, T = int(r.shape[0]), int(r.shape[1])
-        ln = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32).reshape(-1)
-        if ln is not None and ln.size != R:
-            raise ValueError(f"score_rows: lens has {ln.size} entries for {R} rows")
-        ior = None if image_of_row is None else np.ascontiguousarray(image_of_row, dtype=np.int32).reshape(-1)
-        if ior is not None and ior.size != R:
-            raise ValueError(f"score_rows: image_of_row has {ior.size} entries for {R} rows")
+        ln = _row_vector("score_rows", "lens", lens, R)
+        ior = _row_vector("score_rows", "image_of_row", image_of_row, R)
         out = np.empty((R,), dtype=np.float32)
-        self._ck(self.lib.czc_score_rows(self.h, ptr, R, T, seed_len, None if ln is None else ln.ctypes.data,
-                                         None if ior is None else ior.ctypes.data, out.ctypes.data), "czc_score_rows")
+        self._ck(self.lib.czc_score_rows(self.h, _ptr(r), R, T, seed_len, _ptr(ln), _ptr(ior), out.ctypes.data), "czc_score_rows")
         return out
-
-    @staticmethod
-    def _rival_table(what: str, rivals, R: int):
-        """int32 [R, M] from `rivals` (None passes through)."""
-        if rivals is None:
-            return None
-        rv = np.ascontiguousarray(rivals, dtype=np.int32)
-        if rv.ndim != 2 or rv.shape[0] != R or rv.shape[1] < 1:
-            raise ValueError(f"{what}: rivals must be [R, M] with R = {R} and M >= 1, got {rv.shape}")
-        return rv
 
     def generate_rows_vs(self, init_rows, lens, seed_len: int, top_k: int, positions, hypers: Sequence[native.Hyper],
                          draws: Optional[Sequence[native.Draw]], groups: Optional[Sequence[int]], rivals, deltas,
@@ -636,49 +534,10 @@ class Engine:
         image batch, -1 = empty slot, filled slots first; None: generate_rows_tied itself) and `deltas` float [R]: row r adds
         deltas[r] * P(own image | candidate, among own image and rivals) to every candidate's fused score.  `n_mask` (span
         order) only without groups.  Returns (ids int32 [S,R,T], cos fp32 [S,R]) per snapshot."""
-        init = np.ascontiguousarray(init_rows, dtype=np.int32)
-        pos = np.ascontiguousarray(positions, dtype=np.int32)
-        if pos.ndim != 2 or pos.shape[1] < 1:
-            raise ValueError("generate_rows_vs: positions must be [n_steps, R]")
-        n_steps, R = pos.shape
-        if init.ndim != 2 or init.shape[0] != R or init.shape[1] < 1:
-            raise ValueError(f"generate_rows_vs: init_rows must be [R, T] with R = {R}, got {init.shape}")
-        T = init.shape[1]
-        ln = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32).reshape(-1)
-        if ln is not None and ln.size != R:
-            raise ValueError(f"generate_rows_vs: lens has {ln.size} entries for {R} rows")
-        hp = hyper_array(hypers)
-        if len(hp) != R:
-            raise ValueError(f"generate_rows_vs: hypers has {len(hp)} entries for {R} rows")
-        dr = None if draws is None else draw_array(draws)
-        if dr is not None and len(dr) != R:
-            raise ValueError(f"generate_rows_vs: draws has {len(dr)} entries for {R} rows")
-        gr = None if groups is None else np.ascontiguousarray(groups, dtype=np.int32).reshape(-1)
-        if gr is not None and gr.size != R:
-            raise ValueError(f"generate_rows_vs: groups has {gr.size} entries for {R} rows")
-        ior = None if image_of_row is None else np.ascontiguousarray(image_of_row, dtype=np.int32).reshape(-1)
-        if ior is not None and ior.size != R:
-            raise ValueError(f"generate_rows_vs: image_of_row has {ior.size} entries for {R} rows")
-        rv = self._rival_table("generate_rows_vs", rivals, R)
-        dl = np.zeros((R,), np.float32) if deltas is None else np.ascontiguousarray(deltas, dtype=np.float32).reshape(-1)
-        if dl.size != R:
-            raise ValueError(f"generate_rows_vs: deltas has {dl.size} entries for {R} rows")
-        nm = None if n_mask is None else np.ascontiguousarray(n_mask, dtype=np.int32).reshape(-1)
-        if nm is not None and nm.size != n_steps:
-            raise ValueError(f"generate_rows_vs: n_mask has {nm.size} entries for {n_steps} steps")
-        every = snapshot_every or max(int(ln.max()) if ln is not None else T - seed_len - 1, 1)
-        S = n_steps // every
-        ids = np.empty((S, R, T), dtype=np.int32)
-        cos = np.empty((S, R), dtype=np.float32) if want_cos else None
-        rc = self.lib.czc_generate_rows_vs(self.h, R, T, seed_len, init.ctypes.data, None if ln is None else ln.ctypes.data,
-                                           None if ior is None else ior.ctypes.data, None if gr is None else gr.ctypes.data,
-                                           top_k, n_steps, pos.ctypes.data, None if nm is None else nm.ctypes.data, every, hp, dr,
-                                           None if rv is None else rv.ctypes.data, 0 if rv is None else int(rv.shape[1]),
-                                           dl.ctypes.data, ids.ctypes.data, None if cos is None else cos.ctypes.data)
-        if rc:
-            self._raise_scorer_error()
-        self._ck(rc, "czc_generate_rows_vs")
-        return ids, cos
+        return self._rows_call("generate_rows_vs", lambda a: (a.R, a.T, seed_len, a.init, a.lens, a.ior, a.groups, top_k, a.n_steps, a.pos,
+                                                              a.n_mask, a.every, a.hypers, a.draws, a.rivals, a.M, a.deltas, a.ids, a.cos),
+                               init_rows, positions, seed_len, lens=lens, hypers=hypers, draws=draws, groups=groups, rivals=rivals,
+                               deltas=deltas, image_of_row=image_of_row, n_mask=n_mask, snapshot_every=snapshot_every, want_cos=want_cos)
 
     def score_rows_vs(self, rows, seed_len: int, rivals, lens: Optional[Sequence[int]] = None,
                       image_of_row: Optional[Sequence[int]] = None):
@@ -688,16 +547,11 @@ class Engine:
         if r.ndim != 2 or r.shape[0] < 1 or r.shape[1] < 1:
             raise ValueError(f"score_rows_vs: rows must be [R, T], got {tuple(r.shape)}")
         R, T = int(r.shape[0]), int(r.shape[1])
-        ln = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32).reshape(-1)
-        if ln is not None and ln.size != R:
-            raise ValueError(f"score_rows_vs: lens has {ln.size} entries for {R} rows")
-        ior = None if image_of_row is None else np.ascontiguousarray(image_of_row, dtype=np.int32).reshape(-1)
-        if ior is not None and ior.size != R:
-            raise ValueError(f"score_rows_vs: image_of_row has {ior.size} entries for {R} rows")
-        rv = self._rival_table("score_rows_vs", rivals, R)
+        ln = _row_vector("score_rows_vs", "lens", lens, R)
+        ior = _row_vector("score_rows_vs", "image_of_row", image_of_row, R)
+        rv = _rival_table("score_rows_vs", rivals, R)
         cos, disc = np.empty((R,), dtype=np.float32), np.empty((R,), dtype=np.float32)
-        self._ck(self.lib.czc_score_rows_vs(self.h, r.ctypes.data, R, T, seed_len, None if ln is None else ln.ctypes.data,
-                                            None if ior is None else ior.ctypes.data, None if rv is None else rv.ctypes.data,
+        self._ck(self.lib.czc_score_rows_vs(self.h, r.ctypes.data, R, T, seed_len, _ptr(ln), _ptr(ior), _ptr(rv),
                                             0 if rv is None else int(rv.shape[1]), cos.ctypes.data, disc.ctypes.data),
                  "czc_score_rows_vs")
         return cos, disc
@@ -904,158 +758,122 @@ class EngineGroup:
                           for e, (lo, hi) in zip(self.engines, parts)])
         return np.concatenate([o[0] for o in outs], axis=1), np.concatenate([o[1] for o in outs], axis=1)
 
+    def _split_rows(self, name: str, run, init, positions, seed_len: int, L: Optional[int] = None, lens=None, hypers=None, draws=None,
+                    groups=None, rivals=None, deltas=None, image_of_row=None, snapshot_every=None, want_cos: bool = True,
+                    images: str = "rows"):
+        """The one path of every generate_rows* method of the group: check the per-row arguments the method has, work out the
+        snapshot interval of the whole call, deal the rows over the members (contiguously, or on group boundaries with `groups`),
+        hand every member its images, call run(member, p) -- p holds the member's slice of every per-row argument (rows, init,
+        lens, pos, hypers, draws, groups renumbered into [0, its row count), rivals, deltas, ior) and `every` -- and put the
+        results back by row index.  images: "rows" = the embeds of its own rows, p.ior None (the identity); "unique" = the embeds
+        of the images its rows name and p.ior into them; "whole" = the whole batch and the caller's indices (rivals may name any
+        image).  The normalisation is per row, so a row's embedding has the bits the whole batch had.  A new per-row argument is
+        checked and sliced here."""
+        pos = np.ascontiguousarray(positions, dtype=np.int32)
+        if pos.ndim != 2:
+            raise ValueError(f"{name}: positions must be [n_steps, R]")
+        R = pos.shape[1]
+        if name != "generate_rows":   # (its one start row goes to every member as it is)
+            init = np.ascontiguousarray(init, dtype=np.int32)
+            if init.ndim != 2 or init.shape[0] != R:
+                raise ValueError(f"{name}: init_rows must be [R, T] with R = {R}, got {init.shape}")
+        ln = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32).reshape(-1)
+        hps, drs = None if hypers is None else list(hypers), None if draws is None else list(draws)
+        for what, v in (("lens", ln), ("hypers", hps), ("draws", drs)):
+            if v is not None and len(v) != R:
+                raise ValueError(f"{name}: {what} has {len(v)} entries for {R} rows")
+        gr = None if groups is None else np.asarray(groups, dtype=np.int64).reshape(-1)
+        if gr is not None:
+            outside = gr.size == R and R and (gr.min() < 0 or gr.max() >= R)
+            if name == "generate_rows_vs" and (gr.size != R or outside):
+                raise NativeError("EngineGroup.generate_rows_vs: groups must hold R ids in [0, R)", code=native.ERR_ARG)
+            if gr.size != R:
+                raise ValueError(f"{name}: groups has {gr.size} entries for {R} rows")
+            if outside:
+                raise NativeError(f"EngineGroup.{name}: a group id outside [0, R)", code=native.ERR_ARG)
+        rv = _rival_table(name, rivals, R)
+        dl = None if rv is None else _row_vector(name, "deltas", np.zeros((R,), np.float32) if deltas is None else deltas, R, dtype=np.float32)
+        embeds = self._full_embeds if self._full_embeds is not None else self._encoded
+        if embeds is None:
+            raise NativeError(f"EngineGroup.{name}: encode_images / set_image_embeds first")
+        ior = np.arange(R) if image_of_row is None else np.asarray(image_of_row, dtype=np.int64).reshape(-1)
+        if ior.size != R or (R and (ior.min() < 0 or ior.max() >= embeds.shape[0])):
+            raise NativeError(f"EngineGroup.{name}: image_of_row outside the resident image batch", code=native.ERR_ARG)
+        every = snapshot_every or (L if L is not None else max(int(ln.max()) if ln is not None else init.shape[1] - seed_len - 1, 1))
+        parts = self.tied_parts(gr) if gr is not None else [np.arange(lo, hi) for lo, hi in self.parts(R)]
+        jobs = []
+        for e, rows in zip(self.engines, parts):
+            p = SimpleNamespace(rows=rows, every=every, init=init if name == "generate_rows" else init[rows],
+                                lens=None if ln is None else ln[rows], pos=np.ascontiguousarray(pos[:, rows]),
+                                hypers=None if hps is None else [hps[r] for r in rows], draws=None if drs is None else [drs[r] for r in rows],
+                                groups=None if gr is None else np.unique(gr[rows], return_inverse=True)[1].astype(np.int32),
+                                rivals=None if rv is None else rv[rows], deltas=None if dl is None else dl[rows], ior=None)
+            if images == "rows":
+                e.set_image_embeds(embeds[ior[rows]])
+            elif images == "unique":
+                imgs, img_c = np.unique(ior[rows], return_inverse=True)
+                e.set_image_embeds(embeds[imgs])
+                p.ior = img_c.astype(np.int32)
+            else:
+                e.set_image_embeds(embeds)
+                p.ior = ior[rows].astype(np.int32)
+            jobs.append(lambda e=e, p=p: run(e, p))
+        # the members now hold other embeds than their image slices: a later generate() hands the slices over again
+        self._full_embeds, self._resident = embeds, None
+        outs = self._run(jobs)
+        ids = np.empty((outs[0][0].shape[0], R, outs[0][0].shape[2]), dtype=np.int32)
+        cos = np.empty(ids.shape[:2], dtype=np.float32) if want_cos else None
+        for rows, (i, c) in zip(parts, outs):
+            ids[:, rows] = i
+            if want_cos:
+                cos[:, rows] = c
+        return ids, cos
+
     def generate_rows(self, init_ids, L: int, seed_len: int, top_k: int, positions, hyper, image_of_row=None, n_mask=None,
                       snapshot_every=None):
         """Engine.generate_rows with the rows split contiguously over the streams.  `image_of_row` is resolved here: every
         member gets the embeds of its own rows (the normalisation is per row, so they are the bits the whole batch had) and
         runs its rows with the identity."""
-        pos = np.ascontiguousarray(positions, dtype=np.int32)
-        if pos.ndim != 2:
-            raise ValueError("generate_rows: positions must be [n_steps, R]")
-        R = pos.shape[1]
-        embeds = self._full_embeds if self._full_embeds is not None else self._encoded
-        if embeds is None:
-            raise NativeError("EngineGroup.generate_rows: encode_images / set_image_embeds first")
-        ior = np.arange(R) if image_of_row is None else np.asarray(image_of_row, dtype=np.int64).reshape(-1)
-        if ior.size != R or (R and (ior.min() < 0 or ior.max() >= embeds.shape[0])):
-            raise NativeError("EngineGroup.generate_rows: image_of_row outside the resident image batch", code=native.ERR_ARG)
-        parts = self.parts(R)
-        for e, (lo, hi) in zip(self.engines, parts):
-            e.set_image_embeds(embeds[ior[lo:hi]])
-        # the members now hold their rows' embeds: a later generate() hands the image slices over again
-        self._full_embeds, self._resident = embeds, None
-        outs = self._run([(lambda e=e, lo=lo, hi=hi: e.generate_rows(init_ids, L, seed_len, top_k, pos[:, lo:hi], hyper,
-                                                                     n_mask=n_mask, snapshot_every=snapshot_every))
-                          for e, (lo, hi) in zip(self.engines, parts)])
-        return np.concatenate([o[0] for o in outs], axis=1), np.concatenate([o[1] for o in outs], axis=1)
+        return self._split_rows("generate_rows", lambda e, p: e.generate_rows(init_ids, L, seed_len, top_k, p.pos, hyper, n_mask=n_mask,
+                                                                              snapshot_every=snapshot_every),
+                                init_ids, positions, seed_len, L=L, image_of_row=image_of_row, snapshot_every=snapshot_every)
 
     def generate_rows_from(self, init_rows, L: int, seed_len: int, top_k: int, positions, hyper, image_of_row=None, n_mask=None,
                            snapshot_every=None):
         """Engine.generate_rows_from with the rows (start rows, positions, images) split contiguously over the streams, as
         generate_rows splits them."""
-        pos = np.ascontiguousarray(positions, dtype=np.int32)
-        init = np.ascontiguousarray(init_rows, dtype=np.int32)
-        if pos.ndim != 2:
-            raise ValueError("generate_rows_from: positions must be [n_steps, R]")
-        R = pos.shape[1]
-        if init.ndim != 2 or init.shape[0] != R:
-            raise ValueError(f"generate_rows_from: init_rows must be [R, T] with R = {R}, got {init.shape}")
-        embeds = self._full_embeds if self._full_embeds is not None else self._encoded
-        if embeds is None:
-            raise NativeError("EngineGroup.generate_rows_from: encode_images / set_image_embeds first")
-        ior = np.arange(R) if image_of_row is None else np.asarray(image_of_row, dtype=np.int64).reshape(-1)
-        if ior.size != R or (R and (ior.min() < 0 or ior.max() >= embeds.shape[0])):
-            raise NativeError("EngineGroup.generate_rows_from: image_of_row outside the resident image batch", code=native.ERR_ARG)
-        parts = self.parts(R)
-        for e, (lo, hi) in zip(self.engines, parts):
-            e.set_image_embeds(embeds[ior[lo:hi]])
-        self._full_embeds, self._resident = embeds, None
-        outs = self._run([(lambda e=e, lo=lo, hi=hi: e.generate_rows_from(init[lo:hi], L, seed_len, top_k, pos[:, lo:hi], hyper,
-                                                                          n_mask=n_mask, snapshot_every=snapshot_every))
-                          for e, (lo, hi) in zip(self.engines, parts)])
-        return np.concatenate([o[0] for o in outs], axis=1), np.concatenate([o[1] for o in outs], axis=1)
+        return self._split_rows("generate_rows_from", lambda e, p: e.generate_rows_from(p.init, L, seed_len, top_k, p.pos, hyper, n_mask=n_mask,
+                                                                                        snapshot_every=snapshot_every),
+                                init_rows, positions, seed_len, L=L, image_of_row=image_of_row, snapshot_every=snapshot_every)
 
     def generate_rows_len(self, init_rows, lens, seed_len: int, top_k: int, positions, hyper, image_of_row=None, n_mask=None,
                           snapshot_every=None, want_cos: bool = True):
         """Engine.generate_rows_len with the rows (start rows, lengths, positions, images) split contiguously over the streams,
         as generate_rows_from splits them.  Every member keeps the whole call's stride and snapshot interval."""
-        pos = np.ascontiguousarray(positions, dtype=np.int32)
-        init = np.ascontiguousarray(init_rows, dtype=np.int32)
-        ln = np.ascontiguousarray(lens, dtype=np.int32).reshape(-1)
-        if pos.ndim != 2:
-            raise ValueError("generate_rows_len: positions must be [n_steps, R]")
-        R = pos.shape[1]
-        if init.ndim != 2 or init.shape[0] != R:
-            raise ValueError(f"generate_rows_len: init_rows must be [R, T] with R = {R}, got {init.shape}")
-        if ln.size != R:
-            raise ValueError(f"generate_rows_len: lens has {ln.size} entries for {R} rows")
-        embeds = self._full_embeds if self._full_embeds is not None else self._encoded
-        if embeds is None:
-            raise NativeError("EngineGroup.generate_rows_len: encode_images / set_image_embeds first")
-        ior = np.arange(R) if image_of_row is None else np.asarray(image_of_row, dtype=np.int64).reshape(-1)
-        if ior.size != R or (R and (ior.min() < 0 or ior.max() >= embeds.shape[0])):
-            raise NativeError("EngineGroup.generate_rows_len: image_of_row outside the resident image batch", code=native.ERR_ARG)
-        every = snapshot_every or max(int(ln.max()), 1)
-        parts = self.parts(R)
-        for e, (lo, hi) in zip(self.engines, parts):
-            e.set_image_embeds(embeds[ior[lo:hi]])
-        self._full_embeds, self._resident = embeds, None
-        outs = self._run([(lambda e=e, lo=lo, hi=hi: e.generate_rows_len(init[lo:hi], ln[lo:hi], seed_len, top_k, pos[:, lo:hi], hyper,
-                                                                         n_mask=n_mask, snapshot_every=every, want_cos=want_cos))
-                          for e, (lo, hi) in zip(self.engines, parts)])
-        return np.concatenate([o[0] for o in outs], axis=1), (np.concatenate([o[1] for o in outs], axis=1) if want_cos else None)
+        lens = np.ascontiguousarray(lens, dtype=np.int32)   # (required here: None is refused as the engine refuses it)
+        return self._split_rows("generate_rows_len", lambda e, p: e.generate_rows_len(p.init, p.lens, seed_len, top_k, p.pos, hyper, n_mask=n_mask,
+                                                                                      snapshot_every=p.every, want_cos=want_cos),
+                                init_rows, positions, seed_len, lens=lens, image_of_row=image_of_row, snapshot_every=snapshot_every,
+                                want_cos=want_cos)
 
     def generate_rows_hp(self, init_rows, lens, seed_len: int, top_k: int, positions, hypers, image_of_row=None, n_mask=None,
                          snapshot_every=None, want_cos: bool = True):
         """Engine.generate_rows_hp with the rows (start rows, lengths, positions, images, hyper-parameters) split contiguously over
         the streams, as generate_rows_len splits them.  Every member keeps the whole call's stride and snapshot interval."""
-        pos = np.ascontiguousarray(positions, dtype=np.int32)
-        init = np.ascontiguousarray(init_rows, dtype=np.int32)
-        ln = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32).reshape(-1)
-        if pos.ndim != 2:
-            raise ValueError("generate_rows_hp: positions must be [n_steps, R]")
-        R = pos.shape[1]
-        if init.ndim != 2 or init.shape[0] != R:
-            raise ValueError(f"generate_rows_hp: init_rows must be [R, T] with R = {R}, got {init.shape}")
-        if ln is not None and ln.size != R:
-            raise ValueError(f"generate_rows_hp: lens has {ln.size} entries for {R} rows")
-        hps = list(hypers)
-        if len(hps) != R:
-            raise ValueError(f"generate_rows_hp: hypers has {len(hps)} entries for {R} rows")
-        embeds = self._full_embeds if self._full_embeds is not None else self._encoded
-        if embeds is None:
-            raise NativeError("EngineGroup.generate_rows_hp: encode_images / set_image_embeds first")
-        ior = np.arange(R) if image_of_row is None else np.asarray(image_of_row, dtype=np.int64).reshape(-1)
-        if ior.size != R or (R and (ior.min() < 0 or ior.max() >= embeds.shape[0])):
-            raise NativeError("EngineGroup.generate_rows_hp: image_of_row outside the resident image batch", code=native.ERR_ARG)
-        every = snapshot_every or max(int(ln.max()) if ln is not None else init.shape[1] - seed_len - 1, 1)
-        parts = self.parts(R)
-        for e, (lo, hi) in zip(self.engines, parts):
-            e.set_image_embeds(embeds[ior[lo:hi]])
-        self._full_embeds, self._resident = embeds, None
-        outs = self._run([(lambda e=e, lo=lo, hi=hi: e.generate_rows_hp(init[lo:hi], None if ln is None else ln[lo:hi], seed_len, top_k,
-                                                                        pos[:, lo:hi], hps[lo:hi], n_mask=n_mask, snapshot_every=every,
-                                                                        want_cos=want_cos))
-                          for e, (lo, hi) in zip(self.engines, parts)])
-        return np.concatenate([o[0] for o in outs], axis=1), (np.concatenate([o[1] for o in outs], axis=1) if want_cos else None)
+        return self._split_rows("generate_rows_hp", lambda e, p: e.generate_rows_hp(p.init, p.lens, seed_len, top_k, p.pos, p.hypers, n_mask=n_mask,
+                                                                                    snapshot_every=p.every, want_cos=want_cos),
+                                init_rows, positions, seed_len, lens=lens, hypers=list(hypers), image_of_row=image_of_row,
+                                snapshot_every=snapshot_every, want_cos=want_cos)
 
     def generate_rows_draw(self, init_rows, lens, seed_len: int, top_k: int, positions, hypers, draws, image_of_row=None,
                            n_mask=None, snapshot_every=None, want_cos: bool = True):
         """Engine.generate_rows_draw with the rows split contiguously over the streams, as generate_rows_hp splits them.  A row's
         draw record travels with it and holds everything its draws depend on (seed, tau, step offset), so the result does not
         depend on the split."""
-        pos = np.ascontiguousarray(positions, dtype=np.int32)
-        init = np.ascontiguousarray(init_rows, dtype=np.int32)
-        ln = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32).reshape(-1)
-        if pos.ndim != 2:
-            raise ValueError("generate_rows_draw: positions must be [n_steps, R]")
-        R = pos.shape[1]
-        if init.ndim != 2 or init.shape[0] != R:
-            raise ValueError(f"generate_rows_draw: init_rows must be [R, T] with R = {R}, got {init.shape}")
-        if ln is not None and ln.size != R:
-            raise ValueError(f"generate_rows_draw: lens has {ln.size} entries for {R} rows")
-        hps = list(hypers)
-        if len(hps) != R:
-            raise ValueError(f"generate_rows_draw: hypers has {len(hps)} entries for {R} rows")
-        drs = None if draws is None else list(draws)
-        if drs is not None and len(drs) != R:
-            raise ValueError(f"generate_rows_draw: draws has {len(drs)} entries for {R} rows")
-        embeds = self._full_embeds if self._full_embeds is not None else self._encoded
-        if embeds is None:
-            raise NativeError("EngineGroup.generate_rows_draw: encode_images / set_image_embeds first")
-        ior = np.arange(R) if image_of_row is None else np.asarray(image_of_row, dtype=np.int64).reshape(-1)
-        if ior.size != R or (R and (ior.min() < 0 or ior.max() >= embeds.shape[0])):
-            raise NativeError("EngineGroup.generate_rows_draw: image_of_row outside the resident image batch", code=native.ERR_ARG)
-        every = snapshot_every or max(int(ln.max()) if ln is not None else init.shape[1] - seed_len - 1, 1)
-        parts = self.parts(R)
-        for e, (lo, hi) in zip(self.engines, parts):
-            e.set_image_embeds(embeds[ior[lo:hi]])
-        self._full_embeds, self._resident = embeds, None
-        outs = self._run([(lambda e=e, lo=lo, hi=hi: e.generate_rows_draw(init[lo:hi], None if ln is None else ln[lo:hi], seed_len, top_k,
-                                                                          pos[:, lo:hi], hps[lo:hi], None if drs is None else drs[lo:hi],
-                                                                          n_mask=n_mask, snapshot_every=every, want_cos=want_cos))
-                          for e, (lo, hi) in zip(self.engines, parts)])
-        return np.concatenate([o[0] for o in outs], axis=1), (np.concatenate([o[1] for o in outs], axis=1) if want_cos else None)
+        return self._split_rows("generate_rows_draw", lambda e, p: e.generate_rows_draw(p.init, p.lens, seed_len, top_k, p.pos, p.hypers, p.draws,
+                                                                                        n_mask=n_mask, snapshot_every=p.every, want_cos=want_cos),
+                                init_rows, positions, seed_len, lens=lens, hypers=list(hypers), draws=draws, image_of_row=image_of_row,
+                                snapshot_every=snapshot_every, want_cos=want_cos)
 
     def tied_parts(self, groups):
         """Row index arrays, one per engine used: the rows dealt over the streams on group boundaries only.  Groups go, in
@@ -1088,54 +906,11 @@ class EngineGroup:
         if groups is None:
             return self.generate_rows_draw(init_rows, lens, seed_len, top_k, positions, hypers, draws, image_of_row=image_of_row,
                                            snapshot_every=snapshot_every, want_cos=want_cos)
-        pos = np.ascontiguousarray(positions, dtype=np.int32)
-        init = np.ascontiguousarray(init_rows, dtype=np.int32)
-        ln = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32).reshape(-1)
-        if pos.ndim != 2:
-            raise ValueError("generate_rows_tied: positions must be [n_steps, R]")
-        R = pos.shape[1]
-        if init.ndim != 2 or init.shape[0] != R:
-            raise ValueError(f"generate_rows_tied: init_rows must be [R, T] with R = {R}, got {init.shape}")
-        if ln is not None and ln.size != R:
-            raise ValueError(f"generate_rows_tied: lens has {ln.size} entries for {R} rows")
-        hps = list(hypers)
-        if len(hps) != R:
-            raise ValueError(f"generate_rows_tied: hypers has {len(hps)} entries for {R} rows")
-        drs = None if draws is None else list(draws)
-        if drs is not None and len(drs) != R:
-            raise ValueError(f"generate_rows_tied: draws has {len(drs)} entries for {R} rows")
-        gr = np.asarray(groups, dtype=np.int64).reshape(-1)
-        if gr.size != R:
-            raise ValueError(f"generate_rows_tied: groups has {gr.size} entries for {R} rows")
-        if R and (gr.min() < 0 or gr.max() >= R):
-            raise NativeError("EngineGroup.generate_rows_tied: a group id outside [0, R)", code=native.ERR_ARG)
-        embeds = self._full_embeds if self._full_embeds is not None else self._encoded
-        if embeds is None:
-            raise NativeError("EngineGroup.generate_rows_tied: encode_images / set_image_embeds first")
-        ior = np.arange(R) if image_of_row is None else np.asarray(image_of_row, dtype=np.int64).reshape(-1)
-        if ior.size != R or (R and (ior.min() < 0 or ior.max() >= embeds.shape[0])):
-            raise NativeError("EngineGroup.generate_rows_tied: image_of_row outside the resident image batch", code=native.ERR_ARG)
-        every = snapshot_every or max(int(ln.max()) if ln is not None else init.shape[1] - seed_len - 1, 1)
-        parts = self.tied_parts(gr)
-        jobs = []
-        for e, rows in zip(self.engines, parts):
-            imgs, img_c = np.unique(ior[rows], return_inverse=True)
-            _, grp_c = np.unique(gr[rows], return_inverse=True)   # the part's own group ids, in [0, its row count)
-            e.set_image_embeds(embeds[imgs])
-            jobs.append(lambda e=e, rows=rows, img_c=img_c, grp_c=grp_c: e.generate_rows_tied(
-                init[rows], None if ln is None else ln[rows], seed_len, top_k, np.ascontiguousarray(pos[:, rows]),
-                [hps[r] for r in rows], None if drs is None else [drs[r] for r in rows], grp_c.astype(np.int32),
-                image_of_row=img_c.astype(np.int32), snapshot_every=every, want_cos=want_cos))
-        self._full_embeds, self._resident = embeds, None
-        outs = self._run(jobs)
-        S = outs[0][0].shape[0]
-        ids = np.empty((S, R, init.shape[1]), dtype=np.int32)
-        cos = np.empty((S, R), dtype=np.float32) if want_cos else None
-        for rows, (i, c) in zip(parts, outs):
-            ids[:, rows] = i
-            if want_cos:
-                cos[:, rows] = c
-        return ids, cos
+        return self._split_rows("generate_rows_tied", lambda e, p: e.generate_rows_tied(p.init, p.lens, seed_len, top_k, p.pos, p.hypers, p.draws,
+                                                                                        p.groups, image_of_row=p.ior, snapshot_every=p.every,
+                                                                                        want_cos=want_cos),
+                                init_rows, positions, seed_len, lens=lens, hypers=list(hypers), draws=draws, groups=groups,
+                                image_of_row=image_of_row, snapshot_every=snapshot_every, want_cos=want_cos, images="unique")
 
     def generate_rows_vs(self, init_rows, lens, seed_len: int, top_k: int, positions, hypers, draws, groups, rivals, deltas,
                          image_of_row=None, n_mask=None, snapshot_every=None, want_cos: bool = True):
@@ -1149,55 +924,11 @@ class EngineGroup:
         if rivals is None:
             return self.generate_rows_tied(init_rows, lens, seed_len, top_k, positions, hypers, draws, groups, image_of_row=image_of_row,
                                            snapshot_every=snapshot_every, want_cos=want_cos)
-        pos = np.ascontiguousarray(positions, dtype=np.int32)
-        init = np.ascontiguousarray(init_rows, dtype=np.int32)
-        ln = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32).reshape(-1)
-        if pos.ndim != 2:
-            raise ValueError("generate_rows_vs: positions must be [n_steps, R]")
-        R = pos.shape[1]
-        if init.ndim != 2 or init.shape[0] != R:
-            raise ValueError(f"generate_rows_vs: init_rows must be [R, T] with R = {R}, got {init.shape}")
-        if ln is not None and ln.size != R:
-            raise ValueError(f"generate_rows_vs: lens has {ln.size} entries for {R} rows")
-        hps = list(hypers)
-        if len(hps) != R:
-            raise ValueError(f"generate_rows_vs: hypers has {len(hps)} entries for {R} rows")
-        drs = None if draws is None else list(draws)
-        if drs is not None and len(drs) != R:
-            raise ValueError(f"generate_rows_vs: draws has {len(drs)} entries for {R} rows")
-        gr = None if groups is None else np.asarray(groups, dtype=np.int64).reshape(-1)
-        if gr is not None and (gr.size != R or (R and (gr.min() < 0 or gr.max() >= R))):
-            raise NativeError("EngineGroup.generate_rows_vs: groups must hold R ids in [0, R)", code=native.ERR_ARG)
-        rv = Engine._rival_table("generate_rows_vs", rivals, R)
-        dl = np.zeros((R,), np.float32) if deltas is None else np.ascontiguousarray(deltas, dtype=np.float32).reshape(-1)
-        if dl.size != R:
-            raise ValueError(f"generate_rows_vs: deltas has {dl.size} entries for {R} rows")
-        embeds = self._full_embeds if self._full_embeds is not None else self._encoded
-        if embeds is None:
-            raise NativeError("EngineGroup.generate_rows_vs: encode_images / set_image_embeds first")
-        ior = np.arange(R) if image_of_row is None else np.asarray(image_of_row, dtype=np.int64).reshape(-1)
-        if ior.size != R or (R and (ior.min() < 0 or ior.max() >= embeds.shape[0])):
-            raise NativeError("EngineGroup.generate_rows_vs: image_of_row outside the resident image batch", code=native.ERR_ARG)
-        every = snapshot_every or max(int(ln.max()) if ln is not None else init.shape[1] - seed_len - 1, 1)
-        parts = self.tied_parts(gr) if gr is not None else [np.arange(lo, hi) for lo, hi in self.parts(R)]
-        jobs = []
-        for e, rows in zip(self.engines, parts):
-            grp_c = None if gr is None else np.unique(gr[rows], return_inverse=True)[1].astype(np.int32)
-            e.set_image_embeds(embeds)   # the whole batch: the rival indices are the caller's
-            jobs.append(lambda e=e, rows=rows, grp_c=grp_c: e.generate_rows_vs(
-                init[rows], None if ln is None else ln[rows], seed_len, top_k, np.ascontiguousarray(pos[:, rows]),
-                [hps[r] for r in rows], None if drs is None else [drs[r] for r in rows], grp_c, rv[rows], dl[rows],
-                image_of_row=ior[rows].astype(np.int32), n_mask=n_mask, snapshot_every=every, want_cos=want_cos))
-        self._full_embeds, self._resident = embeds, None
-        outs = self._run(jobs)
-        S = outs[0][0].shape[0]
-        ids = np.empty((S, R, init.shape[1]), dtype=np.int32)
-        cos = np.empty((S, R), dtype=np.float32) if want_cos else None
-        for rows, (i, c) in zip(parts, outs):
-            ids[:, rows] = i
-            if want_cos:
-                cos[:, rows] = c
-        return ids, cos
+        return self._split_rows("generate_rows_vs", lambda e, p: e.generate_rows_vs(p.init, p.lens, seed_len, top_k, p.pos, p.hypers, p.draws,
+                                                                                    p.groups, p.rivals, p.deltas, image_of_row=p.ior,
+                                                                                    n_mask=n_mask, snapshot_every=p.every, want_cos=want_cos),
+                                init_rows, positions, seed_len, lens=lens, hypers=list(hypers), draws=draws, groups=groups, rivals=rivals,
+                                deltas=deltas, image_of_row=image_of_row, snapshot_every=snapshot_every, want_cos=want_cos, images="whole")
 
     # ---- the engine calls that apply to every member ----
     def set_option(self, name, value):

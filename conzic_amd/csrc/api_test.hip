@@ -491,6 +491,152 @@ int czc_test_attention_plan(int precision, int kernel, int B, int K, int heads, 
   return rc < 0 ? CZC_TEST_REFUSED : 0;
 }
 
+namespace {
+// the host-given shared-prefix plan of czc_test_attention_plan, uploaded: tables, sizes, and the NaN pattern of the operand type
+struct HostPlan {
+  std::vector<int> len, off, poff, plen, imax;
+  int n_seg = 0, max_own = 0, max_keys = 0;
+  size_t rows = 0;
+  SegTable tab{};
+  int build(DevPool& pool, const char* who, int B, int K, const int32_t* trunk_len, const int32_t* own_len) {
+    n_seg = B + B * K;
+    len = std::vector<int>(n_seg); off = std::vector<int>(n_seg + 1, 0); poff = std::vector<int>(n_seg, 0); plen = std::vector<int>(n_seg, 0);
+    imax = std::vector<int>(B, 0);
+    for (int b = 0; b < B; ++b) len[b] = trunk_len[b];
+    for (int i = 0; i < B * K; ++i) len[B + i] = own_len[i];
+    for (int s = 0; s < n_seg; ++s) {
+      if (len[s] < 0 || len[s] > 4096) { snprintf(TEST_ERR, 512, "%s: segment %d has %d rows", who, s, len[s]); return CZC_ERR_ARG; }
+      off[s + 1] = off[s] + len[s];
+    }
+    for (int b = 0; b < B; ++b) {
+      for (int k = 0; k < K; ++k) {
+        const int s = B + b * K + k;
+        poff[s] = off[b]; plen[s] = len[b];
+        imax[b] = std::max(imax[b], len[s]);
+      }
+      max_own = std::max(max_own, imax[b]);
+      max_keys = std::max(max_keys, len[b] + imax[b]);
+    }
+    rows = off[n_seg];
+    int* doff = (int*)pool.up(off.data(), (size_t)(n_seg + 1) * 4); T_PTR(doff);
+    int* dlen = (int*)pool.up(len.data(), (size_t)n_seg * 4); T_PTR(dlen);
+    int* dpoff = (int*)pool.up(poff.data(), (size_t)n_seg * 4); T_PTR(dpoff);
+    int* dplen = (int*)pool.up(plen.data(), (size_t)n_seg * 4); T_PTR(dplen);
+    int* dimax = (int*)pool.up(imax.data(), (size_t)B * 4); T_PTR(dimax);
+    tab = SegTable{dpoff, dplen, doff, dlen, n_seg, 0};
+    tab.img_max = dimax;
+    return 0;
+  }
+};
+
+// n rows of `row` bytes (fp32 host data, rounded to `precision` on the device) with CZC_TEST_PLAN_GUARD rows of NaNs of the operand
+// type in front of and behind them; *rows0 = the first data row
+int guarded_operand(DevPool& pool, int precision, const float* src, size_t n, size_t row, unsigned char** rows0) {
+  const int GR = CZC_TEST_PLAN_GUARD;
+  unsigned char* d = (unsigned char*)pool.alloc((n + 2 * GR) * row); T_PTR(d);
+  std::vector<uint32_t> nan((size_t)GR * row / 4, precision == PREC_BF16 ? 0x7fc07fc0u : 0x7e007e00u);
+  T_HIP(hipMemcpy(d, nan.data(), (size_t)GR * row, hipMemcpyHostToDevice));
+  T_HIP(hipMemcpy(d + (GR + n) * row, nan.data(), (size_t)GR * row, hipMemcpyHostToDevice));
+  if (n) {
+    float* f = (float*)pool.up(src, n * (row / 2) * 4); T_PTR(f);
+    T_CHECK(launch_convert(precision, f, d + GR * row, (long)(n * (row / 2)), nullptr));
+  }
+  *rows0 = d + GR * row;
+  return 0;
+}
+}  // namespace
+
+int czc_test_attention_pooled(int precision, int B, int K, int heads, float scale, const int32_t* trunk_len, const int32_t* own_len,
+                              const int32_t* rep, const float* qkv, const float* qc, float* out) {
+  if (!(precision == PREC_BF16 || precision == PREC_F16) || B < 1 || K < 1 || heads < 1 || (long)B * K > (1 << 22)) {
+    snprintf(TEST_ERR, 512, "attention_pooled: precision %d B %d K %d heads %d", precision, B, K, heads);
+    return CZC_ERR_ARG;
+  }
+  const int GR = CZC_TEST_PLAN_GUARD;
+  DevPool pool;
+  HostPlan hp;
+  T_CHECK(hp.build(pool, "attention_pooled", B, K, trunk_len, own_len));
+  const size_t nc = (size_t)B * K, Hd = (size_t)heads * 64, orow = Hd * 2;
+  for (size_t i = 0; i < nc; ++i)
+    if (rep[i] < 0 || rep[i] >= K || rep[rep[i] + (i / K) * K] != rep[i]) { snprintf(TEST_ERR, 512, "attention_pooled: rep[%zu] = %d", i, rep[i]); return CZC_ERR_ARG; }
+  unsigned char *dq, *dqc;
+  T_CHECK(guarded_operand(pool, precision, qkv, hp.rows, 3 * orow, &dq));
+  T_CHECK(guarded_operand(pool, precision, qc, nc, orow, &dqc));
+  unsigned char* dout = (unsigned char*)pool.alloc((nc + 2 * GR) * orow); T_PTR(dout);
+  T_HIP(hipMemset(dout, 0x5a, (nc + 2 * GR) * orow));
+  int* dpidx = (int*)pool.up(rep, nc * 4); T_PTR(dpidx);
+  T_HIP(hipDeviceSynchronize());
+  const int saved = g_use_attention_image;
+  g_use_attention_image = 2;
+  const int rc = HK().attention_image_pooled(dq, dqc, hp.tab, dpidx, B, K, hp.max_own, hp.max_keys, heads, scale, dout + GR * orow, nullptr,
+                                             precision == PREC_F16);
+  g_use_attention_image = saved;
+  if (rc) return rc;
+  T_HIP(hipDeviceSynchronize());
+  T_CHECK(down_act(pool, precision, dout, (nc + 2 * GR) * Hd, out));
+  return 0;
+}
+
+int czc_test_attention_mapped(int precision, int B, int K, int heads, float scale, const int32_t* trunk_len, const int32_t* own_len,
+                              const int32_t* rowmap, int n_rows, const float* qkv, float* out) {
+  if (!(precision == PREC_BF16 || precision == PREC_F16) || B < 1 || K < 1 || heads < 1 || (long)B * K > (1 << 22) || n_rows < 1) {
+    snprintf(TEST_ERR, 512, "attention_mapped: precision %d B %d K %d heads %d rows %d", precision, B, K, heads, n_rows);
+    return CZC_ERR_ARG;
+  }
+  const int GR = CZC_TEST_PLAN_GUARD;
+  DevPool pool;
+  HostPlan hp;
+  T_CHECK(hp.build(pool, "attention_mapped", B, K, trunk_len, own_len));
+  const size_t Hd = (size_t)heads * 64, orow = Hd * 2, all = hp.rows + 2 * GR;
+  for (size_t r = 0; r < hp.rows; ++r)
+    if (rowmap[r] < 0 || rowmap[r] >= n_rows) { snprintf(TEST_ERR, 512, "attention_mapped: rowmap[%zu] = %d", r, rowmap[r]); return CZC_ERR_ARG; }
+  unsigned char* dq;
+  T_CHECK(guarded_operand(pool, precision, qkv, (size_t)n_rows, 3 * orow, &dq));
+  unsigned char* dout = (unsigned char*)pool.alloc(all * orow); T_PTR(dout);
+  T_HIP(hipMemset(dout, 0x5a, all * orow));
+  int* dmap = (int*)pool.up(rowmap, hp.rows * 4); T_PTR(dmap);
+  T_HIP(hipDeviceSynchronize());
+  const int saved = g_use_attention_image;
+  g_use_attention_image = 2;
+  const int rc = HK().attention_shared_mapped(dq, n_rows, dmap, hp.tab, B, K, hp.max_own, hp.max_keys, heads, scale, dout + GR * orow, nullptr,
+                                              precision == PREC_F16);
+  g_use_attention_image = saved;
+  if (rc) return rc;
+  T_HIP(hipDeviceSynchronize());
+  T_CHECK(down_act(pool, precision, dout, all * Hd, out));
+  return 0;
+}
+
+int czc_test_layer0_plan(int B, int K, const int32_t* clip_ids, const int32_t* clip_len, int dedup, int32_t* own_off, int32_t* own_len,
+                         int32_t* dcount, int32_t* totals, int M, int32_t* rowmap, int n_dist, int32_t* dist) {
+  const int S = B + B * K, bk = B * K;
+  DevPool pool;
+  int* dids = (int*)pool.up(clip_ids, (size_t)bk * CZC_CLIP_MAX_LEN * 4); T_PTR(dids);
+  int* dlen = (int*)pool.up(clip_len, (size_t)bk * 4); T_PTR(dlen);
+  Guarded own, pre, src, pos0, ooff, poff, eidx, grep, imax, tot, dcnt, gmap, gdist;
+  T_CHECK(own.make(pool, S)); T_CHECK(pre.make(pool, S)); T_CHECK(src.make(pool, S)); T_CHECK(pos0.make(pool, S));
+  T_CHECK(ooff.make(pool, S + 1)); T_CHECK(poff.make(pool, S)); T_CHECK(eidx.make(pool, bk)); T_CHECK(grep.make(pool, bk));
+  T_CHECK(imax.make(pool, B)); T_CHECK(tot.make(pool, 12)); T_CHECK(dcnt.make(pool, B));
+  T_CHECK(gmap.make(pool, M > 0 ? M : 1)); T_CHECK(gdist.make(pool, n_dist > 0 ? n_dist : 1));
+  int* t = tot.p<int>();
+  T_HIP(hipMemset(t, 0, 48));
+  int* r = dedup ? grep.p<int>() : nullptr;
+  T_CHECK(launch_prefix_plan(dids, dlen, B, K, 1, own.p<int>(), pre.p<int>(), src.p<int>(), pos0.p<int>(), t + 3, imax.p<int>(), nullptr, r, t + 5));
+  T_CHECK(HK().layer0_count(dids, own.p<int>(), pre.p<int>(), B, K, dcnt.p<int>(), t + 8, nullptr));
+  T_CHECK(launch_scan(own.p<int>(), S, ooff.p<int>(), t, nullptr));
+  T_CHECK(launch_prefix_finish(ooff.p<int>(), own.p<int>(), B, K, poff.p<int>(), eidx.p<int>(), t + 6, nullptr, r));
+  if (M > 0 && n_dist > 0)  // second call of the test, with the sizes the first one returned
+    T_CHECK(HK().layer0_map(dids, ooff.p<int>(), own.p<int>(), pre.p<int>(), dcnt.p<int>(), B, K, gmap.p<int>(), gdist.p<int>(), nullptr));
+  T_HIP(hipDeviceSynchronize());
+  T_CHECK(ooff.down(own_off)); T_CHECK(own.down(own_len)); T_CHECK(dcnt.down(dcount)); T_CHECK(tot.down(totals));
+  T_CHECK(gmap.down(rowmap)); T_CHECK(gdist.down(dist));
+  return 0;
+}
+
+int czc_test_text_tower(void* engine, int B, int K, const int32_t* clip_ids, const int32_t* clip_len, float* feat, int32_t* n_dup) {
+  return HK().text_tower(engine, clip_ids, clip_len, B, K, feat, n_dup);
+}
+
 int czc_test_topk(int B, int V, int K, const float* logits, const float* mask, float temperature, int dot_id,
                   int dot_allowed, float* probs, int32_t* idxs, int32_t* cand) {
   DevPool pool;

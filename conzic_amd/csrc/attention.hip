@@ -712,17 +712,40 @@ __global__ __launch_bounds__(256) void attention_branch_split_kernel(const split
 //   * rows past the group (the next group's) are zero-filled by the descriptor and dropped on store.
 // One wave = one head; math identical to attention_branch_kernel (S^T = K Q^T in-lane softmax, P V by MFMA).
 // Needs heads % 4 == 0, trunk <= 32 keys, K <= 1024.
+//
+// MODE A2_POOLED (the tower's last layer, whose rows are only read at the K EOS rows of an image): K and V of a group
+// are fetched as above, q comes from a compact [B*K, heads*64] buffer `qc` with ONE row per candidate (row b*K + k = q of
+// candidate k's last own row; tile row j = candidate k0 + j of the group), every query lane multiplies with the q row of
+// its own candidate, and only the lane on its candidate's last own row stores -- into the compact [B*K, heads*64] buffer
+// `out` at the candidate's index.  A query column of a tile depends on its own q and on the K/V tiles only, so those rows
+// are the bits the plain mode stores at the same packed rows; the other columns are not stored.  Candidates without rows
+// (own_len 0) store nothing.  Same tile composition, same number of VMEM instructions per group.
+//
+// MODE A2_MAPPED (the tower's layer 0, where a row's q / k / v depend on its (token, position) only and `qkv` holds every
+// distinct row once): packed branch row r lives at row rowmap[r] of qkv.  The LDS-DMA's per-lane source offset carries the
+// indirection (one descriptor over the whole buffer; lanes past the group's rows get an offset no descriptor admits and
+// read zeros as before), so the LDS image, the tiles, the MFMA order, the softmax and the stores -- to the PACKED context
+// rows -- are the plain mode's.  The 32 map entries of a group arrive by one more LDS-DMA (wave 0) two groups ahead, in a
+// two-slot area behind the segment offsets; the waits do not change (they count the stores younger than the DMA).  Trunk
+// keys and values are read as in the plain mode (trunk rows keep their indices).
 // ------------------------------------------------------------------------------------------------
+constexpr int A2_PLAIN = 0, A2_MAPPED = 1, A2_POOLED = 2;
 constexpr int A2_ROWB = 512;             // 4 heads x 64 dims x bf16
 constexpr int A2_TILE = 32 * A2_ROWB;    // 16 KiB
 constexpr int A2_STAGE = 3 * A2_TILE;    // q, k, v of one group
 constexpr int A2_RING = 2;               // the next group streams in while this one is computed
 constexpr int A2_META = 4224;            // K + 1 segment offsets (K <= 1024), padded
 constexpr int A2_LDS = A2_RING * A2_STAGE + 2 * A2_TILE + A2_META;
+constexpr int A2_MAPSLOT = 256;          // MAPPED: one group's map entries (a 64-lane dword DMA writes 256 bytes)
+constexpr int A2_LDS_MAPPED = A2_LDS + 2 * A2_MAPSLOT;
+static_assert(A2_LDS_MAPPED <= 160 * 1024, "LDS budget");
 
-template <typename HT>
+template <typename HT, int MODE>
 __global__ __launch_bounds__(256) void attention_image_kernel(const bf16_t* qkv, SegTable tab, int B, int K, int G, int heads,
-                                                              float scale, bf16_t* out) {
+                                                              float scale, bf16_t* out, const void* aux, int n_map) {
+  const bf16_t* qc = (const bf16_t*)aux;  // POOLED: the compact q rows
+  const int* rowmap = (const int*)aux;    // MAPPED: packed row -> row of qkv, which has n_map rows in all
+
   extern __shared__ __attribute__((aligned(16))) unsigned char at_lds[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -747,12 +770,14 @@ __global__ __launch_bounds__(256) void attention_image_kernel(const bf16_t* qkv,
   // ---- DMA plumbing: per-lane source offsets inside a 32-row block ----
   // row-major tiles: piece p (0..15) = rows 2p, 2p+1; lane -> row 2p + (lane>>5), physical chunk lane&31
   // sub-tile images: piece s (0..15) = sub-tile s; lane -> key lane>>1, 16-byte half lane&1
-  int vo_row[4], vo_sub[4];
+  const int opitch = Hd * 2;  // bytes per context row (and per row of the compact q buffer)
+  int vo_row[4], vo_sub[4], vo_rowc[4];
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
     const int r = 2 * (wave * 4 + u) + (lane >> 5);
     vo_row[u] = r * pitch + hq * A2_ROWB + (((lane & 31) ^ (r & 15)) << 4);
     vo_sub[u] = (lane >> 1) * pitch + hq * A2_ROWB + (wave * 4 + u) * 32 + (lane & 1) * 16;
+    vo_rowc[u] = r * opitch + hq * A2_ROWB + (((lane & 31) ^ (r & 15)) << 4);  // POOLED: the same tile from compact rows
   }
   auto dma4 = [&](unsigned dst, const int (&vo)[4], int part, u32x4_t rs) {  // this wave's quarter of one tile
     unsigned keep;
@@ -776,18 +801,78 @@ __global__ __launch_bounds__(256) void attention_image_kernel(const bf16_t* qkv,
     rs.w = 0x00020000u;
     return rs;
   };
+  auto cand_desc = [&](const void* base, int k0, int n) {  // descriptor over the compact rows of candidates k0 .. k0 + n - 1 of this image
+    const unsigned long long pa = (unsigned long long)base + (unsigned long long)(sb - B + k0) * opitch;
+    u32x4_t rs;
+    rs.x = __builtin_amdgcn_readfirstlane((unsigned)pa);
+    rs.y = __builtin_amdgcn_readfirstlane((unsigned)(pa >> 32) & 0xffffu);
+    rs.z = __builtin_amdgcn_readfirstlane((unsigned)(n * opitch));
+    rs.w = 0x00020000u;
+    return rs;
+  };
   const int Gb = tab.img_max ? 32 / max(1, __builtin_amdgcn_readfirstlane(tab.img_max[b])) : G;  // this image's own packing factor
   const int ngroups = (K + Gb - 1) / Gb;
+  const int* maps = (const int*)(at_lds + A2_LDS);  // MAPPED: two slots of map entries
+  u32x4_t rs_all;                                   // MAPPED: descriptor over all n_map rows of qkv
+  {
+    const unsigned long long pa = (unsigned long long)qkv;
+    rs_all.x = __builtin_amdgcn_readfirstlane((unsigned)pa);
+    rs_all.y = __builtin_amdgcn_readfirstlane((unsigned)(pa >> 32) & 0xffffu);
+    rs_all.z = __builtin_amdgcn_readfirstlane((unsigned)n_map * (unsigned)pitch);
+    rs_all.w = 0x00020000u;
+  }
   auto issue_group = [&](int gi) {
     const int k0 = gi * Gb, Gc = min(Gb, K - k0);
     const int r0 = __builtin_amdgcn_readfirstlane(meta[k0]);
     const int n_own = min(__builtin_amdgcn_readfirstlane(meta[k0 + Gc]) - r0, 32);
     const u32x4_t rs = rows_desc(r0, n_own);
     const unsigned st = lds0 + (gi & 1) * A2_STAGE;
-    dma4(st, vo_row, 0, rs);
+    if constexpr (MODE == A2_MAPPED) {
+      // this group's map entries (landed: prologue, or two iterations ago and published by the barrier) -> per-lane offsets
+      const int* slot = maps + (gi & 1) * (A2_MAPSLOT / 4);
+      int mo_row[4], mo_sub[4];
+      const int key = lane >> 1;
+      const unsigned kbase = key < n_own ? (unsigned)slot[key] * (unsigned)pitch : 0x7ffffff0u;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int r = 2 * (wave * 4 + u) + (lane >> 5);
+        mo_row[u] = r < n_own ? (int)((unsigned)slot[r] * (unsigned)pitch + (unsigned)(vo_row[u] - r * pitch)) : 0x7ffffff0;
+        mo_sub[u] = key < n_own ? (int)(kbase + (unsigned)(vo_sub[u] - key * pitch)) : 0x7ffffff0;
+      }
+      dma4(st, mo_row, 0, rs_all);
+      dma4(st + A2_TILE, mo_row, 1, rs_all);
+      dma4(st + 2 * A2_TILE, mo_sub, 2, rs_all);
+      return;
+    }
+    if constexpr (MODE == A2_POOLED) dma4(st, vo_rowc, 0, cand_desc(qc, k0, min(Gc, 32)));
+    else dma4(st, vo_row, 0, rs);
     dma4(st + A2_TILE, vo_row, 1, rs);
     dma4(st + 2 * A2_TILE, vo_sub, 2, rs);
   };
+  // MAPPED: the map entries of group gi -> slot gi & 1 (wave 0; lanes past the group's rows land zeros, which nobody reads)
+  auto issue_map = [&](int gi) {
+    if (wave != 0 || gi >= ngroups) return;
+    const int k0 = gi * Gb, Gc = min(Gb, K - k0);
+    const int r0 = __builtin_amdgcn_readfirstlane(meta[k0]);
+    const int n_own = min(__builtin_amdgcn_readfirstlane(meta[k0 + Gc]) - r0, 32);
+    const unsigned long long pa = (unsigned long long)rowmap + (unsigned long long)r0 * 4;
+    u32x4_t rm;
+    rm.x = __builtin_amdgcn_readfirstlane((unsigned)pa);
+    rm.y = __builtin_amdgcn_readfirstlane((unsigned)(pa >> 32) & 0xffffu);
+    rm.z = __builtin_amdgcn_readfirstlane((unsigned)(max(n_own, 0) * 4));
+    rm.w = 0x00020000u;
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dword %2, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "s"(lds0 + (unsigned)(A2_LDS + (gi & 1) * A2_MAPSLOT)), "v"(lane * 4), "s"(rm)
+                 : "memory");
+  };
+  if constexpr (MODE == A2_MAPPED) {  // the map entries of the first two groups, before anything reads them
+    issue_map(0);
+    issue_map(1);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
   // trunk (once), then the first group.  VMEM per wave: trunk 8, every group 12 DMA, 4 stores.
   {
     const u32x4_t rt = rows_desc(pre_off, min(pre_len, 32));
@@ -796,7 +881,6 @@ __global__ __launch_bounds__(256) void attention_image_kernel(const bf16_t* qkv,
   }
   issue_group(0);
 
-  const int opitch = Hd * 2;
   const int nkt_t = pre_len > 0 ? 1 : 0;
 
   typedef __attribute__((ext_vector_type(4))) short tr4_t;
@@ -810,6 +894,7 @@ __global__ __launch_bounds__(256) void attention_image_kernel(const bf16_t* qkv,
     __builtin_amdgcn_s_barrier();  // publishes group gi; every wave has left the other stage
     asm volatile("" ::: "memory");
     if (gi + 1 < ngroups) issue_group(gi + 1);
+    if constexpr (MODE == A2_MAPPED) issue_map(gi + 2);  // into the slot group gi's entries leave (read before this barrier)
 
     const int k0 = gi * Gb, Gc = min(Gb, K - k0);
     const int r0 = __builtin_amdgcn_readfirstlane(meta[k0]);
@@ -819,15 +904,17 @@ __global__ __launch_bounds__(256) void attention_image_kernel(const bf16_t* qkv,
     const unsigned char* Vs = Ks + A2_TILE;
     const int q = min(l31, n_own - 1);
     int ss = 0;  // first slot of this query's own candidate
+    int jq = 0;  // POOLED: that candidate's index inside the group
     for (int j = 1; j < Gc; ++j) {
       const int o = meta[k0 + j] - r0;
-      if (o <= q) ss = o;
+      if (o <= q) { ss = o; jq = j; }
     }
     // fragments: head `wave` owns chunks 8*wave .. 8*wave+7 of a row; step ks takes chunk 2ks + half
     const int cq = wave * 8 + half;
+    const int qr = MODE == A2_POOLED ? jq : q;  // this lane's row of the Q tile
     uint4 qf[4];
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) qf[ks] = *(const uint4*)(Qs + q * A2_ROWB + (((cq + 2 * ks) ^ (q & 15)) << 4));
+    for (int ks = 0; ks < 4; ++ks) qf[ks] = *(const uint4*)(Qs + qr * A2_ROWB + (((cq + 2 * ks) ^ (qr & 15)) << 4));
     f32x16_t st[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
@@ -876,7 +963,10 @@ __global__ __launch_bounds__(256) void attention_image_kernel(const bf16_t* qkv,
     sum += __shfl_xor(sum, 32, 64);
     const float inv = 1.0f / sum;
     u32x4_t rc;  // output descriptor: rows of this group only (the rest is dropped)
-    {
+    // POOLED: the compact rows of this group's candidates; a lane stores when it sits on its candidate's last own row
+    const bool pooled_store = MODE == A2_POOLED && l31 < n_own && l31 + 1 == meta[k0 + jq + 1] - r0;
+    if constexpr (MODE == A2_POOLED) rc = cand_desc(out, k0, min(Gc, 32));
+    else {
       const unsigned long long pc = (unsigned long long)out + (unsigned long long)r0 * opitch;
       rc.x = __builtin_amdgcn_readfirstlane((unsigned)pc);
       rc.y = __builtin_amdgcn_readfirstlane((unsigned)(pc >> 32) & 0xffffu);
@@ -918,7 +1008,9 @@ __global__ __launch_bounds__(256) void attention_image_kernel(const bf16_t* qkv,
         const u32x2_t sx = __builtin_amdgcn_permlane32_swap(w[qa].x, w[qa + 2].x, false, false);
         const u32x2_t sy = __builtin_amdgcn_permlane32_swap(w[qa].y, w[qa + 2].y, false, false);
         const u32x4_t d = {sx.x, sy.x, sx.y, sy.y};  // lower half-wave: quad qa, dims 0..7; upper: quad qa+2
-        const unsigned co = (unsigned)(l31 * opitch + (h * 64 + dt * 32 + 8 * (qa + 2 * half)) * 2);
+        const unsigned cc = (unsigned)((h * 64 + dt * 32 + 8 * (qa + 2 * half)) * 2);
+        // POOLED: the other lanes get an offset no descriptor admits (the store is issued all the same: vmcnt accounting)
+        const unsigned co = MODE == A2_POOLED ? (pooled_store ? (unsigned)(jq * opitch) + cc : 0x7ffffff0u) : (unsigned)(l31 * opitch) + cc;
         asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen\n\ts_nop 1" : : "v"(d), "v"(co), "s"(rc) : "memory");
       }
     }
@@ -926,6 +1018,96 @@ __global__ __launch_bounds__(256) void attention_image_kernel(const bf16_t* qkv,
 }
 
 int g_use_attention_image = 1;  // 0 off, 1 when the batch fills the chip, 2 always (tests)
+
+// launch_attention_shared serves this plan with attention_image_kernel
+bool attention_image_serves(int B, int K, int max_own, int max_keys, int heads) {
+  if (max_keys > 96 || max_own > 32 || max_own <= 0) return false;
+  return g_use_attention_image && heads % 4 == 0 && max_keys <= 32 && K <= 1024 &&
+         (B * (heads / 4) >= 128 || g_use_attention_image == 2);
+}
+
+// one-time set-up behind a function-local static (two engines launch from two host threads)
+static int attention_image_init() {
+  static PerDeviceInit per_dev;
+  const LaunchInit init = per_dev.get([](LaunchInit&) -> int {
+#define CZC_ATTR(K_) CZC_HIP_CHECK(hipFuncSetAttribute((const void*)K_, hipFuncAttributeMaxDynamicSharedMemorySize, A2_LDS))
+    CZC_ATTR((attention_image_kernel<bf16_t, A2_PLAIN>));
+    CZC_ATTR((attention_image_kernel<f16_t, A2_PLAIN>));
+    CZC_ATTR((attention_image_kernel<bf16_t, A2_POOLED>));
+    CZC_ATTR((attention_image_kernel<f16_t, A2_POOLED>));
+#undef CZC_ATTR
+    CZC_HIP_CHECK(hipFuncSetAttribute((const void*)attention_image_kernel<bf16_t, A2_MAPPED>, hipFuncAttributeMaxDynamicSharedMemorySize, A2_LDS_MAPPED));
+    CZC_HIP_CHECK(hipFuncSetAttribute((const void*)attention_image_kernel<f16_t, A2_MAPPED>, hipFuncAttributeMaxDynamicSharedMemorySize, A2_LDS_MAPPED));
+    return 0;
+  });
+  return init.rc;
+}
+
+// Candidates without rows of their own (de-duplicated: rep[s] names another candidate of the image) take their representative's
+// compact row.  One wave per candidate; representatives are their own (rep[r] == r), so no row is read while it is written.
+__global__ __launch_bounds__(256) void pooled_fill_kernel(const int* rep, int n, int K, int row16, uint4* rows) {
+  const int s = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (s >= n) return;
+  const int r = rep[s];
+  if (r == s % K) return;
+  const long src = (long)(s / K) * K + r;
+  for (int c = lane; c < row16; c += 64) rows[(long)s * row16 + c] = rows[src * row16 + c];
+}
+
+// Layer 0 on distinct rows: qkv holds n_rows rows, packed branch row r at row rowmap[r] (trunk rows at their own indices);
+// trunk attention as in launch_attention_shared (its context rows land at the trunk rows' packed indices), branch attention in
+// the per-image kernel's mapped mode, context rows packed.  Only for plans attention_image_serves() accepts.
+int launch_attention_shared_mapped(const void* qkv, int n_rows, const int* rowmap, const SegTable& tab, int B, int K, int max_own,
+                                   int max_keys, int heads, float scale, void* out, hipStream_t st, int f16) {
+  if (!attention_image_serves(B, K, max_own, max_keys, heads) || (long)n_rows * 3 * heads * 128 >= (1L << 31)) {
+    snprintf(g_err, sizeof(g_err), "attention_image (mapped): the plan is not the per-image kernel's (B %d K %d branch %d keys %d heads %d rows %d)",
+             B, K, max_own, max_keys, heads, n_rows);
+    return 1;
+  }
+  if (attention_image_init()) return launch_init_failed("attention_image");
+  const int G = 32 / max_own;
+  const int KPt = ((max_keys + 31) & ~31) + 4;
+  {
+    SegTable trunks = tab;
+    trunks.n_seg = B;
+    dim3 grid(B, heads / 4), block(256);
+    if (f16) hipLaunchKernelGGL(attention_mfma_kernel<f16_t>, grid, block, (size_t)4 * 64 * KPt * 2, st, (const bf16_t*)qkv, trunks, heads, 1,
+                                scale, KPt, (bf16_t*)out);
+    else hipLaunchKernelGGL(attention_mfma_kernel<bf16_t>, grid, block, (size_t)4 * 64 * KPt * 2, st, (const bf16_t*)qkv, trunks, heads, 1,
+                            scale, KPt, (bf16_t*)out);
+  }
+  if (f16) hipLaunchKernelGGL((attention_image_kernel<f16_t, A2_MAPPED>), dim3(B, heads / 4), dim3(256), A2_LDS_MAPPED, st,
+                              (const bf16_t*)qkv, tab, B, K, G, heads, scale, (bf16_t*)out, (const void*)rowmap, n_rows);
+  else hipLaunchKernelGGL((attention_image_kernel<bf16_t, A2_MAPPED>), dim3(B, heads / 4), dim3(256), A2_LDS_MAPPED, st,
+                          (const bf16_t*)qkv, tab, B, K, G, heads, scale, (bf16_t*)out, (const void*)rowmap, n_rows);
+  CZC_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// The last layer's branch attention on a plan attention_image_serves() accepts (no trunk launch: nobody reads trunk rows
+// there): q from the compact rows qc [B*K, heads*64], context of every candidate's last own row into the compact rows
+// ctx_c [B*K, heads*64]; qkv supplies k / v of all packed rows.  rep [B*K] (null: the plan has no de-duplicated candidates):
+// candidate i of image b rides on candidate rep[i] of that image (the plan's table) and receives its compact row.
+int launch_attention_image_pooled(const void* qkv, const void* qc, const SegTable& tab, const int* rep, int B, int K, int max_own,
+                                  int max_keys, int heads, float scale, void* ctx_c, hipStream_t st, int f16) {
+  if (!attention_image_serves(B, K, max_own, max_keys, heads)) {
+    snprintf(g_err, sizeof(g_err), "attention_image (pooled): the plan is not the per-image kernel's (B %d K %d branch %d keys %d heads %d)",
+             B, K, max_own, max_keys, heads);
+    return 1;
+  }
+  if (attention_image_init()) return launch_init_failed("attention_image");
+  const int G = 32 / max_own;
+  if (f16) hipLaunchKernelGGL((attention_image_kernel<f16_t, A2_POOLED>), dim3(B, heads / 4), dim3(256), A2_LDS, st, (const bf16_t*)qkv,
+                              tab, B, K, G, heads, scale, (bf16_t*)ctx_c, qc, 0);
+  else hipLaunchKernelGGL((attention_image_kernel<bf16_t, A2_POOLED>), dim3(B, heads / 4), dim3(256), A2_LDS, st, (const bf16_t*)qkv,
+                          tab, B, K, G, heads, scale, (bf16_t*)ctx_c, qc, 0);
+  CZC_HIP_CHECK(hipGetLastError());
+  if (rep) {
+    hipLaunchKernelGGL(pooled_fill_kernel, dim3(cdiv(B * K, 4)), dim3(256), 0, st, rep, B * K, K, heads * 8, (uint4*)ctx_c);
+    CZC_HIP_CHECK(hipGetLastError());
+  }
+  return 0;
+}
 
 // trunks through the generic kernel (n_seg = B), branches packed G per wave; f16: operands are IEEE fp16 (not bf16)
 int launch_attention_shared(const void* qkv, const SegTable& tab, int B, int K, int max_own, int max_keys, int heads,
@@ -945,20 +1127,12 @@ int launch_attention_shared(const void* qkv, const SegTable& tab, int B, int K, 
   }
   // one work-group per (image, 4 heads) walking the image's groups in sequence: needs enough images to fill the
   // chip (a single image would leave 2 work-groups doing 40 groups each; the per-group kernel spreads those)
-  if (g_use_attention_image && heads % 4 == 0 && max_keys <= 32 && K <= 1024 &&
-      (B * (heads / 4) >= 128 || g_use_attention_image == 2)) {
-    // one-time set-up behind a function-local static (two engines launch from two host threads)
-    static PerDeviceInit per_dev;
-  const LaunchInit init = per_dev.get([](LaunchInit&) -> int {
-      CZC_HIP_CHECK(hipFuncSetAttribute((const void*)attention_image_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, A2_LDS));
-      CZC_HIP_CHECK(hipFuncSetAttribute((const void*)attention_image_kernel<f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, A2_LDS));
-      return 0;
-    });
-    if (init.rc) return launch_init_failed("attention_image");
-    if (f16) hipLaunchKernelGGL(attention_image_kernel<f16_t>, dim3(B, heads / 4), dim3(256), A2_LDS, st, (const bf16_t*)qkv, tab, B,
-                                K, G, heads, scale, (bf16_t*)out);
-    else hipLaunchKernelGGL(attention_image_kernel<bf16_t>, dim3(B, heads / 4), dim3(256), A2_LDS, st, (const bf16_t*)qkv, tab, B, K,
-                            G, heads, scale, (bf16_t*)out);
+  if (attention_image_serves(B, K, max_own, max_keys, heads)) {
+    if (attention_image_init()) return launch_init_failed("attention_image");
+    if (f16) hipLaunchKernelGGL((attention_image_kernel<f16_t, A2_PLAIN>), dim3(B, heads / 4), dim3(256), A2_LDS, st, (const bf16_t*)qkv,
+                                tab, B, K, G, heads, scale, (bf16_t*)out, (const void*)nullptr, 0);
+    else hipLaunchKernelGGL((attention_image_kernel<bf16_t, A2_PLAIN>), dim3(B, heads / 4), dim3(256), A2_LDS, st, (const bf16_t*)qkv,
+                            tab, B, K, G, heads, scale, (bf16_t*)out, (const void*)nullptr, 0);
     CZC_HIP_CHECK(hipGetLastError());
     return 0;
   }

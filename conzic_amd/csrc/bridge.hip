@@ -420,6 +420,87 @@ int launch_prefix_finish(const int* own_off, const int* own_len, int B, int K, i
   return 0;
 }
 
+// ---- layer 0 on distinct rows (kernels.h) -------------------------------------------------------------------------
+// One work-group per image.  cid: the image's K id rows, own: its K branch lengths, pb: position of every branch's first row.
+// The lowest candidate j <= k with a row at offset i that holds candidate k's id there; (j, i) is then its own representative.
+__device__ __forceinline__ int layer0_rep(const int* cid, const int* own, int pb, int k, int i) {
+  const int id = cid[(long)k * BR_LEN + pb + i];
+  for (int j = 0; j < k; ++j)
+    if (own[j] > i && cid[(long)j * BR_LEN + pb + i] == id) return j;
+  return k;
+}
+
+__global__ __launch_bounds__(256) void layer0_count_kernel(const int* cids, const int* own_len, const int* pre_len, int B, int K,
+                                                           int* dcount, int* total) {
+  __shared__ int s_n;
+  const int b = blockIdx.x;
+  if (threadIdx.x == 0) s_n = 0;
+  __syncthreads();
+  const int* cid = cids + (long)b * K * BR_LEN;
+  const int* own = own_len + B + b * K;
+  const int pb = pre_len[B + b * K];
+  int n = 0;
+  for (int k = threadIdx.x; k < K; k += blockDim.x)
+    for (int i = 0; i < min(own[k], 32); ++i) n += layer0_rep(cid, own, pb, k, i) == k;
+  if (n) atomicAdd(&s_n, n);
+  __syncthreads();
+  if (threadIdx.x == 0) { dcount[b] = s_n; if (s_n) atomicAdd(total, s_n); }
+}
+
+int launch_layer0_count(const int* clip_ids, const int* own_len, const int* pre_len, int B, int K, int* dcount, int* total, hipStream_t st) {
+  hipLaunchKernelGGL(layer0_count_kernel, dim3(B), dim3(256), 0, st, clip_ids, own_len, pre_len, B, K, dcount, total);
+  CZC_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+__global__ __launch_bounds__(256) void layer0_map_kernel(const int* cids, const int* own_off, const int* own_len, const int* pre_len,
+                                                         const int* dcount, int B, int K, int* rowmap, int* dist) {
+  __shared__ unsigned s_mask[1024];  // K <= 1024: bit i = row (k, i) is its own representative
+  __shared__ int s_pref[1024];       // representative rows of the image in front of candidate k
+  __shared__ int s_base;
+  const int b = blockIdx.x;
+  if (threadIdx.x == 0) s_base = own_off[B];  // the B trunk segments come first and keep their indices
+  __syncthreads();
+  {
+    int n = 0;
+    for (int j = threadIdx.x; j < b; j += blockDim.x) n += dcount[j];
+    if (n) atomicAdd(&s_base, n);
+  }
+  for (int r = own_off[b] + threadIdx.x; r < own_off[b] + own_len[b]; r += blockDim.x) { rowmap[r] = r; dist[r] = r; }
+  const int* cid = cids + (long)b * K * BR_LEN;
+  const int* own = own_len + B + b * K;
+  const int* off = own_off + B + b * K;
+  const int pb = pre_len[B + b * K];
+  for (int k = threadIdx.x; k < K; k += blockDim.x) {
+    unsigned m = 0;
+    for (int i = 0; i < min(own[k], 32); ++i) m |= (unsigned)(layer0_rep(cid, own, pb, k, i) == k) << i;
+    s_mask[k] = m;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int run = 0;
+    for (int k = 0; k < K; ++k) { s_pref[k] = run; run += __popc(s_mask[k]); }
+  }
+  __syncthreads();
+  const int base = s_base;
+  for (int k = threadIdx.x; k < K; k += blockDim.x) {
+    for (int i = 0; i < min(own[k], 32); ++i) {
+      const int j = (s_mask[k] >> i) & 1 ? k : layer0_rep(cid, own, pb, k, i);
+      const int c = base + s_pref[j] + __popc(s_mask[j] & ((1u << i) - 1u));
+      rowmap[off[k] + i] = c;
+      if (j == k) dist[c] = off[k] + i;
+    }
+  }
+}
+
+int launch_layer0_map(const int* clip_ids, const int* own_off, const int* own_len, const int* pre_len, const int* dcount, int B, int K,
+                      int* rowmap, int* dist, hipStream_t st) {
+  if (K > 1024) { snprintf(g_err, sizeof(g_err), "layer-0 row map: K <= 1024"); return 1; }
+  hipLaunchKernelGGL(layer0_map_kernel, dim3(B), dim3(256), 0, st, clip_ids, own_off, own_len, pre_len, dcount, B, K, rowmap, dist);
+  CZC_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
 // ---- screen-then-refine: segment plan of the second (split-fp16) pass ---------------------------------
 // One work-group per image.  count_off = exclusive scan of count (count_off[B] = R), *kr = max_b count[b].  The plan
 // keeps the REGULAR shape of the screening plan -- B trunks, then B x Kr branch slots, image b's chosen candidates in

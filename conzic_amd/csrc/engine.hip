@@ -136,7 +136,7 @@ struct czc_engine {
   float* d_img_n = nullptr; int img_B = 0;
   float logit_scale_exp = 1.f;
   double plan_pairs = 0;    // causal (query, key) pairs of the text-tower plan about to run (totals[7]): attention FLOPs = 4 * H * pairs per layer
-  int* h_totals = nullptr;  // pinned, 64 ints: [0..7] plan totals, [8],[9] non-finite flags, [16..27] refine-plan totals
+  int* h_totals = nullptr;  // pinned, 64 ints: [8],[9] non-finite flags, [16..27] refine-plan totals, [32..35] memo check, [48..59] plan totals (HT_PLAN)
   int last_BT = 0, last_B = 0, last_T = 0;  // shape of the forward whose rows b_x / b_xg hold (n_mask = 0 re-use needs the same B AND T)
   int bert_prune = 1;       // last BERT layer behind the attention on the one row per sequence the MLM head reads (n_mask == 1 steps)
   int bert_pruned_idx = -1; // row the previous forward kept (-1: all rows of b_x are valid)
@@ -149,6 +149,8 @@ struct czc_engine {
   float* d_staged = nullptr; int staged_cap = 0, staged_n = 0;  // czc_preprocess_u8 output slots [cap][3][S][S]
   int pack_branches = 1; // pack several candidates' rows into one attention MFMA tile
   int pool_last_layer = 1; // last CLIP-text layer: out-proj + MLP on the EOS rows only
+  int share_layer0 = 1;    // CLIP-text layer 0 on the folded path under the per-image attention kernel: q/k/v of every distinct (token, position) row once
+  int pool_last_qkv = 1;   // ... and, on the folded path under the per-image attention kernel, q and the attention context too (k / v of all rows)
   int fuse_ln = 1;         // bf16 / fp16 CLIP-text tower: 1 = out-proj as a full-row kernel with LN2 in its epilogue
                            // (gemm_rowln_kernel; +1 % captions/s), 2 = fc2 -> next layer's LN1 as well (measured slower: the
                            // K = 2048 GEMM pays more for 128-row tiles than the LayerNorm pass costs), 0 = off
@@ -361,10 +363,13 @@ int gemm_ex(czc_engine* e, int prec, const char* kind, const GemmArgs& g) {
 // are still produced); the pooled residual rows are returned in *pooled (fp32 [n_pool, H]).
 // P = precision of the layer weights in L (the engine's CLIP precision, or PREC_F16X3 for the refine pass).
 // r16: x (and *pooled) are fp16 rows of a 2-byte residual stream (czc_engine::resid16; H = 512, half-precision P).
+// layer 0 of the text tower on its distinct rows (kernels.h launch_layer0_map): n > 0 rows, dist [n] their packed rows, rowmap [M]
+struct Layer0Rows { const int* rowmap = nullptr; const int* dist = nullptr; int n = 0; };
+
 int clip_stack(czc_engine* e, int P, const char* gk, std::vector<LayerW>& L, float* x, int M, int H, int I, int heads,
                float eps, const SegTable& tab, int max_keys, int causal, int plan_B = 0, int plan_K = 0,
                int plan_max_own = 0, const int* pool_idx = nullptr, int n_pool = 0, float** pooled = nullptr, bool r16 = false,
-               const float* ln_stat0 = nullptr) {  // ln_stat0: (mean, rstd) of the incoming rows (embedding kernel): enables the LayerNorm fold
+               const float* ln_stat0 = nullptr, const Layer0Rows& l0 = Layer0Rows(), const int* pool_rep = nullptr) {  // pool_rep: the plan's de-duplication table (null: none)  // ln_stat0: (mean, rstd) of the incoming rows (embedding kernel): enables the LayerNorm fold
   const size_t esz = prec_bytes(P);
   void *y, *qkv, *ctx, *hbuf;
   E_CHECK(ensure(e, "cs_y", (size_t)M * H * esz, &y));
@@ -399,9 +404,9 @@ int clip_stack(czc_engine* e, int P, const char* gk, std::vector<LayerW>& L, flo
   };
   // st_: the rows' statistics; nullptr = what finalize(rows, N) left (in `stat`, or still in `part` for the consumer to sum)
   auto folded_gemm = [&](const void* Ax, const void* Wf, const float* bf, const float* st_, void* out, int rows, int N,
-                         int act) -> int {
+                         int act, int ldc = 0) -> int {
     GemmArgs g;
-    g.A = Ax; g.lda = H; g.W = Wf; g.ldw = H; g.bias = bf; g.resid = nullptr; g.ldr = 0; g.out_act = out; g.out_f32 = nullptr; g.ldc = N;
+    g.A = Ax; g.lda = H; g.W = Wf; g.ldw = H; g.bias = bf; g.resid = nullptr; g.ldr = 0; g.out_act = out; g.out_f32 = nullptr; g.ldc = ldc ? ldc : N;
     g.M = rows; g.N = N; g.K = H; g.act = act;
     g.ln_stat = st_ ? st_ : stat;
     if (!st_ && gemm_wreg_stats_in_kernel(rows, N)) { g.ln_part = part; g.ln_part_ld = M; g.ln_eps = eps; }
@@ -429,10 +434,53 @@ int clip_stack(czc_engine* e, int P, const char* gk, std::vector<LayerW>& L, flo
     E_CHECK(launch_gemm_rowln(g, e->st));
     return 0;
   };
+  // Last layer, pooled rows only (pool_last_layer), on the folded path under the per-image attention kernel: k / v of all rows,
+  // but q and the attention context only of the pooled rows (every candidate's last own row) -- the q/k/v GEMM as a k/v launch
+  // on M rows and a q launch on the n_pool gathered rows, the branch attention in its pooled mode, no trunk attention.  Exact:
+  // a row of these GEMMs does not depend on the row count or the column split, a query column of the attention tile only on
+  // its own q and the K/V tiles.
+  const bool pool_qkv = pool_idx && e->pool_last_layer && e->pool_last_qkv && fold && plan_B > 0 && n_pool == plan_B * plan_K &&
+                        prec_is_half(P) && g_use_mfma_attention && e->pack_branches &&
+                        attention_image_serves(plan_B, plan_K, plan_max_own, max_keys, heads);
   bool have_y = false;  // y already holds this layer's LN1 output (left by the previous layer's fc2)
   for (size_t n = 0; n < L.size(); ++n) {
     LayerW& l = L[n];
-    if (fold) {
+    if (pool_qkv && n + 1 == L.size()) {
+      void *ctx_e, *q_e, *h_e; float *x_e, *stat_e;
+      E_CHECK(ensure(e, "cs_ctx_e", (size_t)n_pool * H * esz, &ctx_e));
+      E_CHECK(ensure(e, "cs_q_e", (size_t)n_pool * H * esz, &q_e));
+      E_CHECK(ensure(e, "cs_h_e", (size_t)n_pool * I * esz, &h_e));
+      E_CHECK(ensure(e, "cs_x_e", (size_t)n_pool * H * 4, (void**)&x_e));
+      E_CHECK(ensure(e, "cs_stat_e", (size_t)n_pool * 8 + 256, (void**)&stat_e));
+      const float* st_all = n == 0 ? ln_stat0 : stat;  // layer n - 1 left them finalized (below)
+      { ProfScope ps(e, rk, 0);
+        E_CHECK(launch_gather_rows_bytes(x, pool_idx, n_pool, H * 2, x_e, e->st));
+        E_CHECK(launch_gather_rows_w32(st_all, pool_idx, n_pool, 2, stat_e, e->st)); }
+      E_CHECK(folded_gemm(x, (const char*)l.qkv_wf + (size_t)H * H * 2, l.qkv_bf + H, st_all, (char*)qkv + (size_t)H * esz, M, 2 * H,
+                          ACT_NONE, 3 * H));
+      E_CHECK(folded_gemm(x_e, l.qkv_wf, l.qkv_bf, stat_e, q_e, n_pool, H, ACT_NONE));
+      { ProfScope ps(e, ak, attn_flops);
+        E_CHECK(launch_attention_image_pooled(qkv, q_e, tab, pool_rep, plan_B, plan_K, plan_max_own, max_keys, heads, scale, ctx_e,
+                                              e->st, P == PREC_F16)); }
+      E_CHECK(gemm_x16(e, P, gk, ctx_e, H, l.o_w, l.o_b, x_e, n_pool, H, H, part, M));
+      E_CHECK(finalize(n_pool, I));
+      E_CHECK(folded_gemm(x_e, l.fc1_wf, l.fc1_bf, nullptr, h_e, n_pool, I, ACT_QUICK_GELU));
+      E_CHECK(gemm_x16(e, P, gk, h_e, I, l.fc2_w, l.fc2_b, x_e, n_pool, H, I));
+      *pooled = x_e;
+      return 0;
+    }
+    const bool l0_rows = fold && n == 0 && l0.n > 0;
+    if (l0_rows) {
+      // a packed row's input here is token_embedding[id] + position_embedding[pos]: q/k/v of every distinct row once, into the
+      // first l0.n rows of qkv; the branch attention fetches row r at rowmap[r].  x stays packed (it is the residual).
+      void* xg; float* sg;
+      E_CHECK(ensure(e, "cs_xg", (size_t)l0.n * H * 2, &xg));
+      E_CHECK(ensure(e, "cs_sg", (size_t)l0.n * 8 + 256, (void**)&sg));
+      { ProfScope ps(e, rk, 0);
+        E_CHECK(launch_gather_rows_bytes(x, l0.dist, l0.n, H * 2, xg, e->st));
+        E_CHECK(launch_gather_rows_w32(ln_stat0, l0.dist, l0.n, 2, sg, e->st)); }
+      E_CHECK(folded_gemm(xg, l.qkv_wf, l.qkv_bf, sg, qkv, l0.n, 3 * H, ACT_NONE));
+    } else if (fold) {
       E_CHECK(folded_gemm(x, l.qkv_wf, l.qkv_bf, n == 0 ? ln_stat0 : nullptr, qkv, M, 3 * H, ACT_NONE));
     } else {
       if (!have_y) E_CHECK(ln(l.ln1_g, l.ln1_b, M, x, y));
@@ -440,7 +488,10 @@ int clip_stack(czc_engine* e, int P, const char* gk, std::vector<LayerW>& L, flo
     }
     { ProfScope ps(e, ak, attn_flops);
       int rc = -1;
-      if (plan_B > 0 && prec_is_half(P) && g_use_mfma_attention && e->pack_branches)
+      if (l0_rows)
+        rc = launch_attention_shared_mapped(qkv, l0.n, l0.rowmap, tab, plan_B, plan_K, plan_max_own, max_keys, heads, scale, ctx, e->st,
+                                            P == PREC_F16);
+      else if (plan_B > 0 && prec_is_half(P) && g_use_mfma_attention && e->pack_branches)
         rc = launch_attention_shared(qkv, tab, plan_B, plan_K, plan_max_own, max_keys, heads, scale, ctx, e->st, P == PREC_F16);
       else if (plan_B > 0 && P == PREC_F16X3 && g_use_mfma_attention && e->pack_branches)
         rc = launch_attention_shared_split(qkv, tab, plan_B, plan_K, plan_max_own, max_keys, heads, scale, ctx, e->st);
@@ -477,7 +528,10 @@ int clip_stack(czc_engine* e, int P, const char* gk, std::vector<LayerW>& L, flo
       E_CHECK(folded_gemm(x, l.fc1_wf, l.fc1_bf, nullptr, hbuf, M, I, ACT_QUICK_GELU));
       const bool more = n + 1 < L.size();  // the last layer's rows only feed the final LayerNorm (on the pooled rows)
       E_CHECK(gemm_x16(e, P, gk, hbuf, I, l.fc2_w, l.fc2_b, x, M, H, I, more ? part : nullptr, M));
-      if (more) E_CHECK(finalize(M, 3 * H));
+      if (more && pool_qkv && n + 2 == L.size()) {  // the pooled last layer gathers the statistics of its rows: always in `stat`
+        ProfScope ps(e, rk, 0);
+        E_CHECK(launch_ln_finalize(part, M, H / 32, M, eps, stat, e->st));
+      } else if (more) E_CHECK(finalize(M, 3 * H));
       continue;
     }
     if (rowln) E_CHECK(resid_ln_gemm(ctx, H, l.o_w, l.o_b, H, l.ln2_g, l.ln2_b));
@@ -626,6 +680,9 @@ int mlm_head(czc_engine* e, int B, int T, int gen_idx, float** logits_out, const
 // (trunk segment) and every candidate only carries the rows from its first differing token on.
 // Two halves around the step's single host round trip (32 bytes of totals: rows, longest sequence, overflow):
 // clip_plan builds the segment table on the device and starts the read, clip_tower runs on the sizes it returned.
+constexpr int HT_PLAN = 48;     // h_totals: where the plan's totals land
+constexpr int PLAN_TOTALS = 48; // bytes of a plan's device totals: [0] rows [1] longest segment [2] bridge overflow [3] longest sequence [4] longest
+                                // branch [5] de-duplicated candidates [6] trunk rows [7] attention pairs [8] distinct branch rows of layer 0
 struct PlanBufs { int *own_len, *pre_len, *src, *pos0, *own_off, *pre_off, *eidx, *img_max, *rep; };
 
 // the refine engine inside czc_generate: screening pass on fp16 rows (czc_engine::refine_rows16)
@@ -658,8 +715,13 @@ int clip_plan(czc_engine* e, const int* cids, const int* clen, int B, int K, int
     int* rep = e->dedup && share && K > 1 ? p.rep : nullptr;
     E_CHECK(launch_prefix_plan(cids, clen, B, K, share, p.own_len, p.pre_len, p.src, p.pos0, totals + 3, p.img_max, e->st, rep, totals + 5));
     E_CHECK(launch_scan(p.own_len, S, p.own_off, totals, e->st));
-    E_CHECK(launch_prefix_finish(p.own_off, p.own_len, B, K, p.pre_off, p.eidx, totals + 6, e->st, rep)); }
-  E_HIP(hipMemcpyAsync(e->h_totals, totals, 32, hipMemcpyDeviceToHost, e->st));
+    E_CHECK(launch_prefix_finish(p.own_off, p.own_len, B, K, p.pre_off, p.eidx, totals + 6, e->st, rep));
+    if (e->share_layer0 && share && K > 1 && K <= 1024 && e->fold_ln && e->pack_branches) {  // the tower decides on the sizes whether layer 0 uses it
+      int* dcount;
+      E_CHECK(ensure(e, "p_dcount", (size_t)B * 4, (void**)&dcount));
+      E_CHECK(launch_layer0_count(cids, p.own_len, p.pre_len, B, K, dcount, totals + 8, e->st));
+    } }
+  E_HIP(hipMemcpyAsync(e->h_totals + HT_PLAN, totals, PLAN_TOTALS, hipMemcpyDeviceToHost, e->st));
   int* flag;
   E_CHECK(ensure(e, "s_nonfinite", 32, (void**)&flag));
   E_HIP(hipMemcpyAsync(e->h_totals + 8, flag, 4, hipMemcpyDeviceToHost, e->st));  // the previous steps' cosine check
@@ -670,7 +732,7 @@ int clip_plan(czc_engine* e, const int* cids, const int* clen, int B, int K, int
 // P / L / tproj: the tower's precision and weights; plan_B > 0: regular B x K plan (packed-branch attention kernels).
 int clip_tower_on(czc_engine* e, int P, std::vector<LayerW>& L, const void* tproj, const char* gk, const int* cids,
                   const PlanBufs& p, int n_seg, int n_pool, int M, int max_len, int plan_B, int plan_K, int max_branch,
-                  const char* feat_name, float** feat_out) {
+                  const char* feat_name, float** feat_out, int n_dist = 0, const int* rep = nullptr) {  // n_dist: distinct rows of layer 0 (clip_plan; 0: not counted); rep: its de-duplication table
   const czc_config& c = e->cfg;
   const int H = c.clip_hidden;
   float *x, *feat, *tok, *pos, *fg, *fb; void* pa;
@@ -690,8 +752,22 @@ int clip_tower_on(czc_engine* e, int P, std::vector<LayerW>& L, const void* tpro
                               stat0, c.clip_eps)); }
   SegTable tab{p.pre_off, p.pre_len, p.own_off, p.own_len, n_seg, 0, plan_B > 0 ? p.img_max : nullptr};
   float* pooled = nullptr;
+  // layer 0 on distinct rows: where the folded path runs under the per-image attention kernel, with 32-bit byte offsets into the
+  // compact q/k/v buffer
+  Layer0Rows l0;
+  if (n_dist > 0 && n_dist <= M && e->share_layer0 && stat0 && L.size() > 1 && plan_B > 0 && prec_is_half(P) && g_use_mfma_attention &&
+      e->pack_branches && attention_image_serves(plan_B, plan_K, max_branch, max_len, c.clip_heads) &&
+      (long)n_dist * 3 * H * 2 < (1L << 31)) {
+    int *rowmap, *dist, *dcount;
+    E_CHECK(ensure(e, "c_l0map", (size_t)M * 4, (void**)&rowmap));
+    E_CHECK(ensure(e, "c_l0dist", (size_t)n_dist * 4, (void**)&dist));
+    E_CHECK(ensure(e, "p_dcount", (size_t)plan_B * 4, (void**)&dcount));  // left by clip_plan
+    { ProfScope ps(e, "bridge", 0);
+      E_CHECK(launch_layer0_map(cids, p.own_off, p.own_len, p.pre_len, dcount, plan_B, plan_K, rowmap, dist, e->st)); }
+    l0.rowmap = rowmap; l0.dist = dist; l0.n = n_dist;
+  }
   E_CHECK(clip_stack(e, P, gk, L, x, M, H, c.clip_inter, c.clip_heads, c.clip_eps, tab, max_len, 1, plan_B,
-                     plan_K, max_branch, p.eidx, n_pool, &pooled, r16, stat0));
+                     plan_K, max_branch, p.eidx, n_pool, &pooled, r16, stat0, l0, rep));
   { ProfScope ps(e, "rowops_clip_text", 0);
     if (r16) {
       if (pooled) E_CHECK(launch_layernorm_x16(P, pooled, nullptr, fg, fb, c.clip_eps, n_pool, H, pa, e->st));
@@ -704,26 +780,28 @@ int clip_tower_on(czc_engine* e, int P, std::vector<LayerW>& L, const void* tpro
 }
 
 // the engine's text tower on the regular B x K plan built by clip_plan; `exact`: the refine engine's split-fp16 weights
-int clip_tower(czc_engine* e, const int* cids, int B, int K, int share, int M, int max_len, int max_branch, int n_trunk,
-               float** feat_out, bool exact = false) {
-  (void)share; (void)n_trunk;
+int clip_tower(czc_engine* e, const int* cids, int B, int K, int share, int M, int max_len, int max_branch, int n_trunk, int n_dist,
+               float** feat_out, bool exact = false) {  // n_dist: distinct branch rows of layer 0 the plan counted (0: it did not)
   PlanBufs p;
   E_CHECK(plan_bufs(e, B, K, &p));
   const bool x = exact && e->refine;
   return clip_tower_on(e, x ? (int)PREC_F16X3 : e->pc, x ? e->ctext_x : e->ctext, x ? e->tproj_wx : e->tproj_w, "gemm_clip_text",
-                       cids, p, B + B * K, B * K, M, max_len, B, K, max_branch, "c_feat", feat_out);
+                       cids, p, B + B * K, B * K, M, max_len, B, K, max_branch, "c_feat", feat_out,
+                       n_dist > 0 ? n_trunk + n_dist : 0, e->dedup && share && K > 1 ? p.rep : nullptr);  // rep: as clip_plan filled it
 }
 
 // sizes of the tower from the totals the plan read back (after the stream has been synchronised)
-int read_totals(czc_engine* e, int* M, int* max_len, int* max_branch, int* n_trunk) {
+int read_totals(czc_engine* e, int* M, int* max_len, int* max_branch, int* n_trunk, int* n_dist) {
   const czc_config& c = e->cfg;
-  *M = e->h_totals[0]; *max_len = e->h_totals[3]; *max_branch = e->h_totals[4]; *n_trunk = e->h_totals[6];
+  const int* t = e->h_totals + HT_PLAN;
+  *M = t[0]; *max_len = t[3]; *max_branch = t[4]; *n_trunk = t[6];
+  *n_dist = t[8];
   // a compacted memo step: a branch longer than 32 rows among the images it skipped would have sent the full batch's launch
   // to the per-segment attention kernel, so it goes there too (round 3: the one batch coupling of the text tower)
   if (e->memo_branch_floor > 32 && *max_branch < e->memo_branch_floor) *max_branch = e->memo_branch_floor;
-  e->plan_pairs = (double)e->h_totals[7];
+  e->plan_pairs = (double)t[7];
   if (e->h_totals[8]) return fail(e, CZC_ERR_OVERFLOW, "non-finite CLIP cosine: an fp16 quantity overflowed in a tower (fp16 residual rows: set option resid16 = 0 on the bf16 engine, refine_rows16 = 0 on the refine engine; fp16 operands: use CZC_PREC_SPLIT)%s");
-  if (e->h_totals[2]) return fail(e, CZC_ERR_OVERFLOW, "text bridge overflow (row text > CZC_BRIDGE_MAX_BYTES)%s");
+  if (t[2]) return fail(e, CZC_ERR_OVERFLOW, "text bridge overflow (row text > CZC_BRIDGE_MAX_BYTES)%s");
   if (*max_len > c.clip_max_pos || *max_len > CZC_CLIP_MAX_LEN)
     return fail(e, CZC_ERR_ARG, "CLIP sequence longer than max_position_embeddings%s");
   return 0;
@@ -733,9 +811,9 @@ int clip_text_forward(czc_engine* e, const int* cids, const int* clen, int B, in
                       float** feat_out, bool exact = false) {
   E_CHECK(clip_plan(e, cids, clen, B, K, share, totals));
   E_HIP(hipStreamSynchronize(e->st));  // the one host round trip per step (the reference has one too, gen_utils.py:81)
-  int M, max_len, max_branch, n_trunk;
-  E_CHECK(read_totals(e, &M, &max_len, &max_branch, &n_trunk));
-  E_CHECK(clip_tower(e, cids, B, K, share, M, max_len, max_branch, n_trunk, feat_out, exact));
+  int M, max_len, max_branch, n_trunk, n_dist;
+  E_CHECK(read_totals(e, &M, &max_len, &max_branch, &n_trunk, &n_dist));
+  E_CHECK(clip_tower(e, cids, B, K, share, M, max_len, max_branch, n_trunk, n_dist, feat_out, exact));
   e->stat_clip_rows += M;
   e->stat_clip_seqs += B * K;
   return 0;
@@ -760,7 +838,7 @@ int step_bufs(czc_engine* e, int n_seq, StepBufs* b) {
   E_CHECK(ensure(e, "s_cand", (size_t)n_seq * 4, (void**)&b->cand));
   E_CHECK(ensure(e, "s_cids", (size_t)n_seq * CZC_CLIP_MAX_LEN * 4, (void**)&b->cids));
   E_CHECK(ensure(e, "s_clen", (size_t)n_seq * 4, (void**)&b->clen));
-  E_CHECK(ensure(e, "s_tot", 32, (void**)&b->totals));
+  E_CHECK(ensure(e, "s_tot", PLAN_TOTALS, (void**)&b->totals));
   E_CHECK(ensure(e, "s_senti", (size_t)n_seq * 4, (void**)&b->senti));
   E_CHECK(ensure(e, "s_reps", (size_t)n_seq * 4, (void**)&b->reps));
   return 0;
@@ -791,7 +869,7 @@ int step_phase_a(czc_engine* e, const StepArgs& a) {
                                                           b.probs, b.idxs, b.cand, e->st));
     else E_CHECK(launch_softmax_mask_topk(logits, a.B, c.bert_vocab, a.K, e->d_mask, hp->temperature, c.dot_id, a.dot_allowed,
                                           b.probs, b.idxs, b.cand, e->st)); }
-  E_HIP(hipMemsetAsync(b.totals, 0, 32, e->st));
+  E_HIP(hipMemsetAsync(b.totals, 0, PLAN_TOTALS, e->st));
   { ProfScope ps(e, "bridge", 0);
     PosDev pos{hp->control == 2 ? e->d_pos_tags : nullptr, e->d_pos_masks, e->pos_n};
     // per-row hyper-parameters: every table there is goes along and a candidate's thread scores by its row's control
@@ -854,14 +932,14 @@ int control_score(czc_engine* e, const StepArgs& a) {
 }
 
 // CLIP text tower on the planned rows -> cosine / softmax_K / fusion / argmax / write-back
-int step_phase_b(czc_engine* e, const StepArgs& a, int M, int max_len, int max_branch, int n_trunk) {
+int step_phase_b(czc_engine* e, const StepArgs& a, int M, int max_len, int max_branch, int n_trunk, int n_dist) {
   const czc_config& c = e->cfg;
   const czc_hyper* hp = &a.hp;
   const int n_seq = a.B * a.K;
   StepBufs b;
   E_CHECK(step_bufs(e, n_seq, &b));
   float* feat;
-  E_CHECK(clip_tower(e, b.cids, a.B, a.K, e->share_prefix, M, max_len, max_branch, n_trunk, &feat));
+  E_CHECK(clip_tower(e, b.cids, a.B, a.K, e->share_prefix, M, max_len, max_branch, n_trunk, n_dist, &feat));
   if (hp->control && e->ctl_fn) E_CHECK(control_score(e, a));  // host scorer under the tower that was just queued
   float *cscore, *cref, *fin, *bcos; int* best;
   E_CHECK(ensure(e, "s_cscore", (size_t)n_seq * 4, (void**)&cscore));
@@ -975,12 +1053,12 @@ int step_device(czc_engine* e, int* d_inp, int B, int T, int gen_idx, int n_mask
   if (n_mask > 0) { e->stat_bert_rows += rag ? rag->M : B * T; e->last_BT = B * T; e->last_B = B; e->last_T = T; }
   if (hp->control && e->ctl_fn) E_CHECK(control_fetch(e, a));  // ids for the host scorer ride on the same round trip
   E_HIP(hipStreamSynchronize(e->st));  // the one host round trip per step (the reference has one too, gen_utils.py:81)
-  int M, max_len, max_branch, n_trunk;
-  E_CHECK(read_totals(e, &M, &max_len, &max_branch, &n_trunk));
-  E_CHECK(step_phase_b(e, a, M, max_len, max_branch, n_trunk));
+  int M, max_len, max_branch, n_trunk, n_dist;
+  E_CHECK(read_totals(e, &M, &max_len, &max_branch, &n_trunk, &n_dist));
+  E_CHECK(step_phase_b(e, a, M, max_len, max_branch, n_trunk, n_dist));
   e->stat_clip_rows += M;
   e->stat_clip_seqs += B * K;
-  e->stat_dedup_seqs += e->h_totals[5];
+  e->stat_dedup_seqs += e->h_totals[HT_PLAN + 5];
   e->stat_steps += 1;
   return 0;
 }
@@ -1410,10 +1488,10 @@ int score_rows_device(czc_engine* e, const int* d_rows, int n, int T, const int*
   E_CHECK(ensure(e, "sc_cand", (size_t)n * 4, (void**)&cand));
   E_CHECK(ensure(e, "sc_cids", (size_t)n * CZC_CLIP_MAX_LEN * 4, (void**)&cids));
   E_CHECK(ensure(e, "sc_clen", (size_t)n * 4, (void**)&clen));
-  E_CHECK(ensure(e, "sc_tot", 32, (void**)&totals));
+  E_CHECK(ensure(e, "sc_tot", PLAN_TOTALS, (void**)&totals));
   E_CHECK(ensure(e, "s_nonfinite", 32, (void**)&flag));
   E_HIP(hipMemsetAsync(gen, 0, (size_t)n * 4, e->st));
-  E_HIP(hipMemsetAsync(totals, 0, 32, e->st));
+  E_HIP(hipMemsetAsync(totals, 0, PLAN_TOTALS, e->st));
   E_HIP(hipMemcpy2DAsync(cand, 4, d_rows, (size_t)T * 4, 4, n, hipMemcpyDeviceToDevice, e->st));  // column 0 of every row
   { ProfScope ps(e, "bridge", 0);
     E_CHECK(launch_bridge_rows(e->bd, d_rows, n, T, gen, cand, 1, nullptr, nullptr, e->d_lex_cls, 0, PosDev{nullptr, nullptr, 0}, cids, clen,
@@ -1574,7 +1652,7 @@ int czc_replicate(czc_engine* p, czc_engine** out) {
   e->mlm_dense_w = p->mlm_dense_w; e->decoder_w = p->decoder_w; e->tproj_w = p->tproj_w; e->vproj_w = p->vproj_w;
   e->patch_w = p->patch_w; e->tproj_wx = p->tproj_wx;
   e->logit_scale_exp = p->logit_scale_exp;
-  e->share_prefix = p->share_prefix; e->dedup = p->dedup; e->pack_branches = p->pack_branches; e->pool_last_layer = p->pool_last_layer;
+  e->share_prefix = p->share_prefix; e->dedup = p->dedup; e->pack_branches = p->pack_branches; e->pool_last_layer = p->pool_last_layer; e->pool_last_qkv = p->pool_last_qkv; e->share_layer0 = p->share_layer0;
   e->fuse_ln = p->fuse_ln; e->bert_prune = p->bert_prune; e->bert_fuse_splitk_ln = p->bert_fuse_splitk_ln; e->resid16 = p->resid16; e->fold_ln = p->fold_ln;
   memset(&e->bd, 0, sizeof(e->bd));
   if (hipSetDevice(e->dev) != hipSuccess || hipStreamCreate(&e->st) != hipSuccess ||
@@ -1901,10 +1979,10 @@ int czc_encode_text(czc_engine* e, const int32_t* clip_ids, const int32_t* clip_
   int *cids, *clen, *totals;
   E_CHECK(ensure(e, "s_cids", (size_t)n * CZC_CLIP_MAX_LEN * 4, (void**)&cids));
   E_CHECK(ensure(e, "s_clen", (size_t)n * 4, (void**)&clen));
-  E_CHECK(ensure(e, "s_tot", 32, (void**)&totals));
+  E_CHECK(ensure(e, "s_tot", PLAN_TOTALS, (void**)&totals));
   E_HIP(hipMemcpyAsync(cids, clip_ids, (size_t)n * CZC_CLIP_MAX_LEN * 4, hipMemcpyDefault, e->st));
   E_HIP(hipMemcpyAsync(clen, clip_len, (size_t)n * 4, hipMemcpyDefault, e->st));
-  E_HIP(hipMemsetAsync(totals, 0, 32, e->st));
+  E_HIP(hipMemsetAsync(totals, 0, PLAN_TOTALS, e->st));
   { int* flag; E_CHECK(ensure(e, "s_nonfinite", 32, (void**)&flag)); E_HIP(hipMemsetAsync(flag, 0, 32, e->st)); }
   float* feat;
   E_CHECK(clip_text_forward(e, cids, clen, n, 1, 0, totals, &feat, true));  // independent sequences: no sharing; exact tower
@@ -2720,6 +2798,8 @@ int czc_set_option(czc_engine* e, const char* name, int value) {
   if (!strcmp(name, "bert_fuse_splitk_ln")) { e->bert_fuse_splitk_ln = value ? 1 : 0; return CZC_OK; }
   if (!strcmp(name, "pack_branches")) { e->pack_branches = value ? 1 : 0; return CZC_OK; }
   if (!strcmp(name, "pool_last_layer")) { e->pool_last_layer = value ? 1 : 0; return CZC_OK; }
+  if (!strcmp(name, "share_layer0")) { e->share_layer0 = value ? 1 : 0; return CZC_OK; }
+  if (!strcmp(name, "pool_last_qkv")) { e->pool_last_qkv = value ? 1 : 0; return CZC_OK; }
   if (!strcmp(name, "fuse_ln")) { e->fuse_ln = value; return CZC_OK; }  // 0 off, 1 out-proj -> LN2, 2 also fc2 -> next LN1
   const auto fold_ready = [&]() -> int {  // an option that turns the folded form on after the weights were finalized without it
     if (e->finalized && wants_folded_ln(e) && (e->ctext.empty() || !e->ctext[0].qkv_wf))
@@ -2752,7 +2832,7 @@ int czc_get_option(czc_engine* e, const char* name, int* value) {
   const float f16x = r16 ? e->refine_rows16_factor : 1.f;
   struct { const char* n; int v; } tab[] = {
       {"share_prefix", e->share_prefix}, {"bert_prune", e->bert_prune}, {"pack_branches", e->pack_branches},
-      {"dedup", e->dedup}, {"pool_last_layer", e->pool_last_layer}, {"bert_fuse_splitk_ln", e->bert_fuse_splitk_ln}, {"fuse_ln", e->fuse_ln}, {"resid16", e->resid16}, {"fold_ln", e->fold_ln},
+      {"dedup", e->dedup}, {"pool_last_layer", e->pool_last_layer}, {"pool_last_qkv", e->pool_last_qkv}, {"share_layer0", e->share_layer0}, {"bert_fuse_splitk_ln", e->bert_fuse_splitk_ln}, {"fuse_ln", e->fuse_ln}, {"resid16", e->resid16}, {"fold_ln", e->fold_ln},
       {"refine_samples", e->refine_samples}, {"refine_samples_step", e->refine_samples_step}, {"refine_theta_x1000", (int)lrintf(e->refine_theta_x * 1000.f)},
       {"refine_theta_gen_x1000", (int)lrintf(e->refine_theta_gen * 1000.f)},
       {"refine_guard_x1e6", (int)lrintf(e->refine_guard_dev * 1e6f)}, {"refine_gate_x1e6", (int)lrintf(e->refine_gate_delta * 1e6f)},
@@ -2897,6 +2977,32 @@ int czc_refine_guard(czc_engine* e, int reset, float* max_dev, int64_t* tripped)
   return CZC_OK;
 }
 
+// czc_test_text_tower (api_test.hip): the engine's text tower on host-given CLIP id rows of B images x K candidates, through the
+// step's own plan (shared prefix and de-duplication as the engine's options say) -> features [B*K, proj]; *n_dup = candidates that
+// ride on an identical one
+static int test_text_tower(void* engine, const int32_t* clip_ids, const int32_t* clip_len, int B, int K, float* out, int32_t* n_dup) {
+  czc_engine* e = (czc_engine*)engine;
+  if (!e || !clip_ids || !clip_len || B <= 0 || K <= 0 || K > CZC_MAX_TOPK || !out) return CZC_ERR_ARG;
+  if (!e->finalized) return fail(e, CZC_ERR_STATE, "weights not finalized%s");
+  E_HIP(hipSetDevice(e->dev));
+  e->err[0] = 0;
+  const int n = B * K;
+  int *cids, *clen, *totals;
+  E_CHECK(ensure(e, "s_cids", (size_t)n * CZC_CLIP_MAX_LEN * 4, (void**)&cids));
+  E_CHECK(ensure(e, "s_clen", (size_t)n * 4, (void**)&clen));
+  E_CHECK(ensure(e, "s_tot", PLAN_TOTALS, (void**)&totals));
+  E_HIP(hipMemcpyAsync(cids, clip_ids, (size_t)n * CZC_CLIP_MAX_LEN * 4, hipMemcpyDefault, e->st));
+  E_HIP(hipMemcpyAsync(clen, clip_len, (size_t)n * 4, hipMemcpyDefault, e->st));
+  E_HIP(hipMemsetAsync(totals, 0, PLAN_TOTALS, e->st));
+  { int* flag; E_CHECK(ensure(e, "s_nonfinite", 32, (void**)&flag)); E_HIP(hipMemsetAsync(flag, 0, 32, e->st)); }
+  float* feat;
+  E_CHECK(clip_text_forward(e, cids, clen, B, K, e->share_prefix, totals, &feat));
+  if (n_dup) *n_dup = e->h_totals[HT_PLAN + 5];
+  E_HIP(hipMemcpyAsync(out, feat, (size_t)n * e->cfg.clip_proj * 4, hipMemcpyDefault, e->st));
+  E_HIP(hipStreamSynchronize(e->st));
+  return CZC_OK;
+}
+
 const void* czc_internal_hooks(int abi) {
   static const Hooks h = {
       []() -> char* { return czc::g_err; },
@@ -2908,7 +3014,9 @@ const void* czc_internal_hooks(int abi) {
       &g_rowln_min_m, &g_wreg_min_m, &g_gemm256_min_m, &g_use_mfma_attention, &g_use_attention_image, &g_wreg_resid_min_m,
       &g_wreg_stats_in_kernel, &g_gemm256s_min_m,
       &launch_scan, &launch_prefix_plan, &launch_prefix_finish, &launch_refine_select, &launch_refine_select_rows,
-      &launch_refine_select_draw, &launch_refine_plan, &launch_refine_finish, &launch_refine_cosine};
+      &launch_refine_select_draw, &launch_refine_plan, &launch_refine_finish, &launch_refine_cosine,
+      &launch_attention_image_pooled, &launch_attention_shared_mapped, &launch_layer0_count, &launch_layer0_map,
+      &test_text_tower};
   return abi == HOOKS_ABI ? &h : nullptr;
 }
 

@@ -209,6 +209,17 @@ extern int g_use_attention_image;
 // shapes do not fit the packed-branch kernel (caller then uses launch_attention)
 int launch_attention_shared(const void* qkv, const SegTable& tab, int B, int K, int max_own, int max_keys, int heads,
                             float scale, void* out, hipStream_t st, int f16 = 0);
+// launch_attention_shared serves this plan with the per-image kernel (attention_image_kernel)
+bool attention_image_serves(int B, int K, int max_own, int max_keys, int heads);
+// such a plan in the tower's layer 0 on distinct rows: qkv [n_rows, 3*heads*64] holds packed branch row r at row rowmap[r] (trunk
+// rows at their own indices); trunk and branch context rows are written at their packed indices
+int launch_attention_shared_mapped(const void* qkv, int n_rows, const int* rowmap, const SegTable& tab, int B, int K, int max_own,
+                                   int max_keys, int heads, float scale, void* out, hipStream_t st, int f16 = 0);
+// such a plan in the tower's last layer: q from compact rows qc [B*K, heads*64] (one per candidate: q of its last own row), the
+// context of those rows into compact rows ctx_c [B*K, heads*64]; k / v of all packed rows from qkv; no trunk rows are computed.
+// rep [B*K] or null (launch_prefix_plan's table): a de-duplicated candidate gets the compact row of candidate rep[i] of its image.
+int launch_attention_image_pooled(const void* qkv, const void* qc, const SegTable& tab, const int* rep, int B, int K, int max_own,
+                                  int max_keys, int heads, float scale, void* ctx_c, hipStream_t st, int f16 = 0);
 
 // the same for the split engine precision (qkv / out are split_t)
 int launch_attention_shared_split(const void* qkv, const SegTable& tab, int B, int K, int max_own, int max_keys, int heads,
@@ -302,6 +313,16 @@ int launch_prefix_plan(const int* clip_ids, const int* clip_len, int B, int K, i
 // first occurrence); the others get own_len 0 and pool their representative's EOS row; *n_dup_out += their number
 // after the scan of own_len: pre_off[trunk] = 0, pre_off[branch (b,k)] = own_off[b];
 // eos_idx[b*K+k] = own_off[B+b*K+k] + own_len[B+b*K+k] - 1
+// Layer 0 on distinct rows (exact: the input of a packed row in layer 0 is token_embedding[id] + position_embedding[pos]): the
+// representative of branch row (candidate k, offset i) of an image is the row at offset i of the lowest candidate of that image
+// that has a row there holding the same CLIP id (all branches of an image start at the same position).  Trunk rows are their own.
+// launch_layer0_count (plan phase, after launch_prefix_plan): distinct branch rows per image -> dcount [B], their sum added to
+// *total.  launch_layer0_map (after launch_scan / launch_prefix_finish, sizes known): rowmap [M] = packed row -> index among the
+// representative rows compacted in packed order (trunk rows first, indices kept), dist [n_trunk + sum] = the inverse list.
+// Branches of more than 32 rows are outside the plans this serves (counted up to 32, never mapped).
+int launch_layer0_count(const int* clip_ids, const int* own_len, const int* pre_len, int B, int K, int* dcount, int* total, hipStream_t st);
+int launch_layer0_map(const int* clip_ids, const int* own_off, const int* own_len, const int* pre_len, const int* dcount, int B, int K,
+                      int* rowmap, int* dist, hipStream_t st);
 int launch_prefix_finish(const int* own_off, const int* own_len, int B, int K, int* pre_off, int* eos_idx,
                          int* n_trunk_rows, hipStream_t st, const int* rep = nullptr);
 
@@ -394,7 +415,7 @@ int launch_index_search(const split_t* index, int n, int D, const split_t* queri
 // ---- czc_internal_hooks (declared below, private to the build): what libconzic_hip_test.so may reach inside this library -----------
 // The product library has hidden visibility; the hook library (api_test.hip) gets the launchers it wraps and the
 // process-wide kernel-family switches it flips through this table instead of through exported C++ symbols.
-constexpr int HOOKS_ABI = 0x0606;
+constexpr int HOOKS_ABI = 0x0608;
 struct Hooks {
   char* (*err_buf)();  // the calling host thread's g_err [512]
   decltype(&launch_gemm) gemm;
@@ -427,6 +448,12 @@ struct Hooks {
   decltype(&launch_refine_plan) refine_plan;
   decltype(&launch_refine_finish) refine_finish;
   decltype(&launch_refine_cosine) refine_cosine;
+  decltype(&launch_attention_image_pooled) attention_image_pooled;
+  decltype(&launch_attention_shared_mapped) attention_shared_mapped;
+  decltype(&launch_layer0_count) layer0_count;
+  decltype(&launch_layer0_map) layer0_map;
+  // the engine's text tower on host-given id rows (engine.hip test_text_tower; `engine` is a czc_engine*)
+  int (*text_tower)(void* engine, const int32_t* clip_ids, const int32_t* clip_len, int B, int K, float* out, int32_t* n_dup);
 };
 
 }  // namespace czc

@@ -160,6 +160,10 @@ TEST_SIGNATURES = {
     "czc_test_layernorm": (_I, [_I, _I, _I, _P, _P, _P, C.c_float, _P]),
     "czc_test_attention": (_I, [_I, _I, _P, _I, _I, C.c_float, _P, _P]),
     "czc_test_attention_plan": (_I, [_I, _I, _I, _I, _I, C.c_float, _P, _P, _I, _P, _P]),
+    "czc_test_attention_pooled": (_I, [_I, _I, _I, _I, C.c_float, _P, _P, _P, _P, _P, _P]),
+    "czc_test_attention_mapped": (_I, [_I, _I, _I, _I, C.c_float, _P, _P, _P, _I, _P, _P]),
+    "czc_test_layer0_plan": (_I, [_I, _I, _P, _P, _I, _P, _P, _P, _P, _I, _P, _I, _P]),
+    "czc_test_text_tower": (_I, [_P, _I, _I, _P, _P, _P, _P]),
     "czc_test_topk": (_I, [_I, _I, _I, _P, _P, C.c_float, _I, _I, _P, _P, _P]),
     "czc_test_bridge": (_I, [C.POINTER(BridgeTables), C.POINTER(Config), _I, _I, _P, _P, _P]),
     "czc_test_combine": (_I, [_I, _I, _I, _P, _P, C.c_float, _P, _P, _P, C.POINTER(Hyper), _P, _P, _P, _P]),

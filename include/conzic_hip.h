@@ -525,6 +525,13 @@ int czc_score_rows_vs(czc_engine* e, const int32_t* rows /* [R, T] BERT ids, hos
  *                         bias and residual itself instead of a reduce kernel followed by the LayerNorm kernel; bit-identical
  *   "pack_branches"   (1) attention of the branch rows with G candidates packed per 32-query MFMA tile
  *   "pool_last_layer" (1) last CLIP-text layer: out-projection + MLP on the EOS rows only
+ *   "share_layer0"    (1) CLIP-text layer 0, on the folded path ("resid16" + "fold_ln") wherever the per-image branch attention
+ *                         kernel serves the step: the input of a packed row there is token_embedding[id] + position_embedding[pos],
+ *                         so q / k / v are formed once per distinct (id, position) row of an image and the branch attention fetches
+ *                         its rows through an index table; bit-identical
+ *   "pool_last_qkv"   (1) with "pool_last_layer", on the folded path ("resid16" + "fold_ln") wherever the per-image branch attention
+ *                         kernel serves the step: the last layer also forms q and the attention context on the EOS rows only
+ *                         (k / v of all rows; no trunk attention); bit-identical
  *   "fold_ln"         (1) with "resid16": the LayerNorms inside the CLIP-text stack folded into the q/k/v and fc1 GEMMs (they
  *                         multiply x itself on the fp16 MFMA by weights whose rows carry the gain and are centred, and scale with
  *                         the row's rstd, which comes from partial sums the producer GEMMs leave): no LayerNorm kernel and no

@@ -76,6 +76,34 @@ int czc_test_attention(int precision, int n_seq, const int32_t* seq_len, int hea
 #define CZC_TEST_PLAN_GUARD 32
 int czc_test_attention_plan(int precision, int kernel, int B, int K, int heads, float scale, const int32_t* trunk_len,
                             const int32_t* own_len, int pass_img_max, const float* qkv, float* out);
+/* attention_image_kernel's POOLED mode (launch_attention_image_pooled: the tower's last layer) on the same kind of host-given
+ * plan, per-image kernel forced, precision 0 bf16 / 4 fp16:
+ *   qkv  fp32 [rows, 3*heads*64]: k / v of all packed rows (its q columns must not be read: the caller may poison them);
+ *   qc   fp32 [B*K, heads*64]: one q row per candidate;   rep [B*K]: the plan's de-duplication table (candidate i of image b
+ *        rides on candidate rep[i] of that image, its own index where it has rows) -- a candidate with own_len 0 receives the
+ *        compact row of its representative;
+ *   out  fp32 [CZC_TEST_PLAN_GUARD + B*K + CZC_TEST_PLAN_GUARD, heads*64]: the compact context rows with their guard rows.
+ * Guards and pre-fills as czc_test_attention_plan (NaN rows around qkv and qc, bytes 0x5a in out).  Returns 0 or a CZC_ERR_*
+ * status (a plan the per-image kernel does not serve is an error here). */
+int czc_test_attention_pooled(int precision, int B, int K, int heads, float scale, const int32_t* trunk_len, const int32_t* own_len,
+                              const int32_t* rep, const float* qkv, const float* qc, float* out);
+/* attention_image_kernel's MAPPED mode (launch_attention_shared_mapped: the tower's layer 0 on distinct rows) on such a plan,
+ * per-image kernel forced, precision 0 bf16 / 4 fp16: qkv fp32 [n_rows, 3*heads*64] holds packed row r of the plan at row
+ * rowmap[r] (rowmap [rows]; trunk rows must map to themselves), out as czc_test_attention_plan's (packed context rows with
+ * guard rows, pre-filled with bytes 0x5a); NaN rows around the n_rows rows of qkv. */
+int czc_test_attention_mapped(int precision, int B, int K, int heads, float scale, const int32_t* trunk_len, const int32_t* own_len,
+                              const int32_t* rowmap, int n_rows, const float* qkv, float* out);
+/* The engine's plan chain with the layer-0 distinct-row plan (launch_prefix_plan with sharing -> launch_layer0_count ->
+ * launch_scan -> launch_prefix_finish [-> launch_layer0_map when M > 0 and n_dist > 0: the sizes a first call returned]) on
+ * clip_ids [B*K, 77] / clip_len [B*K].  Outputs, each with CZC_TEST_GUARD words around it (see below): own_off [S + 1],
+ * own_len [S] (S = B + B*K), dcount [B], totals [12] ([0] rows, [6] trunk rows, [8] distinct branch rows), rowmap [max(M, 1)],
+ * dist [max(n_dist, 1)]. */
+int czc_test_layer0_plan(int B, int K, const int32_t* clip_ids, const int32_t* clip_len, int dedup, int32_t* own_off, int32_t* own_len,
+                         int32_t* dcount, int32_t* totals, int M, int32_t* rowmap, int n_dist, int32_t* dist);
+/* The text tower of `engine` (a czc_engine*) on host-given CLIP id rows clip_ids [B*K, 77] / clip_len [B*K] of B images x K
+ * candidates, through the step's own plan and tower (shared prefix, de-duplication and every other option as the engine holds
+ * them): feat fp32 [B*K, clip_proj], *n_dup = candidates that ride on an identical one of their image. */
+int czc_test_text_tower(void* engine, int B, int K, const int32_t* clip_ids, const int32_t* clip_len, float* feat, int32_t* n_dup);
 int czc_test_topk(int B, int V, int K, const float* logits, const float* mask, float temperature, int dot_id,
                   int dot_allowed, float* probs, int32_t* idxs, int32_t* cand);
 int czc_test_bridge(const czc_bridge_tables* t, const czc_config* cfg, int n_rows, int T, const int32_t* rows,

@@ -156,13 +156,19 @@ def block_status(f):
     return "\n".join(rows)
 
 
+# the newest kernel trace of the headline (profiles/README.md) and the caption batches its process ran
+KERNEL_STATS = ("r14_edge_layers_final_kernel_stats.csv", 2)
+
 # kernel-name pattern -> (what it is in the step, what bounds it, work model)
 #   work model: ("gemm", N, Kdim, which rows) FLOPs = 2 * rows * N * Kdim per pass;  ("bytes", bytes per row, which rows);  None
 KERNELS = [
     (r"gemm_wreg_kernel<1,", "fc1 512->2048 + quick-GELU, LayerNorm folded in (weights in registers, `gemm_wreg.hip`)", "MFMA", ("gemm", 2048, 512, "mlp")),
     (r"gemm256x_kernel<0, true, (false|true), (256|true)>", "fc2 2048->512 + residual on fp16 rows (256x256 ping-pong ring, `gemm256.hip`)", "MFMA", ("gemm", 512, 2048, "mlp")),
-    (r"gemm_wreg_kernel<0,", "q/k/v 512->1536, LayerNorm folded in (weights in registers)", "MFMA", ("gemm", 1536, 512, "all")),
-    (r"attention_image_kernel", "branch attention, one work-group per (image, 4 heads) (`attention.hip`)", "HBM: 4 KB per row (q, k, v in, context out)", ("bytes", 4096, "all")),
+    (r"gemm_wreg_kernel<0,", "q/k/v 512->1536, LayerNorm folded in (weights in registers); layer 0 on its distinct rows, last layer as k/v on all rows + q on the EOS rows", "MFMA", None),
+    (r"attention_image_kernel<unsigned short, 0>", "branch attention of layers 1..10, one work-group per (image, 4 heads) (`attention.hip`)", "HBM: 4 KB per row (q, k, v in, context out)", ("bytes", 4096, "mid")),
+    (r"attention_image_kernel<unsigned short, 1>", "layer 0: the same, q / k / v rows fetched through the distinct-row table", "VMEM issue; aliased rows hit L2", None),
+    (r"attention_image_kernel<unsigned short, 2>", "last layer: the same, one q row in and one context row out per candidate", "VMEM issue (the plain mode's instruction count)", None),
+    (r"layer0_(count|map)_kernel", "distinct (id, position) rows of layer 0: count before the size read, row table after it (`bridge.hip`)", "latency (one work-group per image)", None),
     (r"gemm_wreg_resid_kernel", "out-projection 512->512 + residual, x updated in place, LayerNorm partials out", "HBM: 3 KB per row (context, x in, x out; the second column group's context read hits L2)", ("gemmbytes", 512, 512, "mlp", 3072)),
     (r"gemm_kernel<czc::split_t, 0, true, false, 128>", "BERT q/k/v and fc2 slices (split-fp16, 3 MFMA passes, 128x128 tiles, `gemm.hip`)", "latency / tile count (180-540 tiles)", None),
     (r"gemm_kernel<czc::split_t, 2, true, false, 128>", "BERT fc1 + GELU", "latency / tile count", None),
@@ -186,18 +192,19 @@ KERNELS = [
 
 def block_kernels(f):
     """what runs in one caption batch of configs[2] on ONE stream, from the rocprofv3 kernel stats of
-    `bench.py --streams 1 --steps 2 --warmup 1 --full` (4 caption batches in the process) and the workload's row counts."""
+    `bench.py --streams 1 --steps 1 --warmup 1` (KERNEL_STATS: the file and the caption batches in its process) and the
+    workload's row counts."""
     import csv
-    path = os.path.join(P, f"{ROUND}_bench_bf16_kernel_stats.csv")
+    path = os.path.join(P, KERNEL_STATS[0])
     dflt = jload(f"{ROUND}_bench_default.json") or jload(f"{ROUND}_bench_driver_cmd.json")
     if not os.path.exists(path) or not dflt:
         return "(no kernel stats collected for this round yet)"
     rows = list(csv.DictReader(open(path)))
     total_ns = sum(float(r["TotalDurationNs"]) for r in rows)
-    batches = 4
+    batches = KERNEL_STATS[1]
     R = dflt["clip_rows_per_step"]                        # packed text-tower rows of one caption batch (sum over its 100 position-steps)
     S = dflt["config"]["images_per_gpu"] * dflt["config"]["candidate_k"] * dflt["config"]["sentence_len"] * dflt["config"]["num_iterations"]
-    which = {"all": 12 * R, "mlp": 11 * R + S, "all2": 23 * R}   # rows a kernel class sees per caption batch (last layer: EOS rows only)
+    which = {"all": 12 * R, "mid": 10 * R, "mlp": 11 * R + S, "all2": 23 * R}   # rows a kernel class sees per caption batch (last layer: EOS rows only)
     out = ["| kernel | role | launches per caption batch | mean us | share of GPU time | achieved | bound |", "|---|---|---|---|---|---|---|"]
     shown = 0.0
     for pat, role, bound, work in KERNELS:

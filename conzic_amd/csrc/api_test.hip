@@ -998,3 +998,429 @@ int czc_test_combine_rivals(int B, int K, int D, const float* text_feat, const f
 }
 
 }  // extern "C"
+
+// ---- the row, embedding, mover and memo kernels one by one (rowops.hip, ragged.hip, memo.hip, memo_rows.hip) ----------------------
+// Every output is a Guarded buffer of 4-byte words and comes back RAW (typed activations as the bytes the kernel stored:
+// tests/kernel_hooks.py decodes bf16 / fp16 / split hi + lo planes), so that results can be compared bit for bit.  Every index a
+// kernel would follow is checked on the host first: nothing out of bounds reaches a launch.  A launcher that refuses its shape
+// (status 1) launches nothing: the hook still returns every output (the untouched pattern) with CZC_TEST_REFUSED.
+namespace {
+size_t act_words(int prec, size_t n) { return (n * prec_bytes(prec) + 3) / 4; }
+int launch_status(int rc) { return rc == 0 ? 0 : rc == 1 ? CZC_TEST_REFUSED : CZC_ERR_HIP; }
+bool all_in(const int32_t* v, size_t n, long lo, long hi) {  // lo <= v[i] < hi
+  for (size_t i = 0; i < n; ++i) if (v[i] < lo || v[i] >= hi) return false;
+  return true;
+}
+bool prec_known(int p) { return p == PREC_BF16 || p == PREC_F32 || p == PREC_F16X3 || p == PREC_F16; }
+#define T_ARG(cond, who) do { if (!(cond)) { snprintf(TEST_ERR, 512, "%s: argument check failed: %s", who, #cond); return CZC_ERR_ARG; } } while (0)
+// a Guarded buffer of n words holding host data (null: the pattern)
+int guarded_in(DevPool& pool, Guarded& g, const void* src, size_t words) {
+  T_CHECK(g.make(pool, words));
+  if (src && words) T_CHECK(g.fill(src));
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int czc_test_layernorm_rows(int precision, int M, int H, int n_src, const float* x, const int32_t* row_idx, const float* gamma,
+                            const float* beta, float eps, int mode, int32_t* y_act, float* y_f32) {
+  const char* who = "layernorm_rows";
+  const bool want_act = mode & 1, want_f32 = mode & 2, alias = mode & 4;
+  T_ARG(prec_known(precision) && M >= 1 && H >= 1 && H <= 4096 && n_src >= 1 && (want_act || want_f32), who);
+  T_ARG(!alias || (want_f32 && !row_idx && n_src == M), who);  // in place: row m reads and writes row m only
+  T_ARG(row_idx ? all_in(row_idx, M, 0, n_src) : n_src >= M, who);
+  DevPool pool;
+  Guarded gx, ga, gf;
+  T_CHECK(guarded_in(pool, gx, x, (size_t)n_src * H));
+  float* dg = (float*)pool.up(gamma, (size_t)H * 4); T_PTR(dg);
+  float* db = (float*)pool.up(beta, (size_t)H * 4); T_PTR(db);
+  int* di = row_idx ? (int*)pool.up(row_idx, (size_t)M * 4) : nullptr;
+  if (row_idx) T_PTR(di);
+  T_CHECK(ga.make(pool, act_words(precision, (size_t)M * H)));
+  if (!alias) T_CHECK(gf.make(pool, (size_t)M * H));
+  float* yf = !want_f32 ? nullptr : alias ? gx.p<float>() : gf.p<float>();
+  const int rc = launch_layernorm(precision, gx.p<float>(), di, dg, db, eps, M, H, want_act ? ga.p<void>() : nullptr, yf, nullptr);
+  T_HIP(hipDeviceSynchronize());
+  T_CHECK(ga.down(y_act));
+  T_CHECK((alias ? gx : gf).down(y_f32));
+  return launch_status(rc);
+}
+
+int czc_test_layernorm_x16_rows(int precision, int M, int H, int n_src, const float* x, const int32_t* row_idx, const float* gamma,
+                                const float* beta, float eps, int32_t* y_act) {
+  const char* who = "layernorm_x16_rows";
+  T_ARG(prec_known(precision) && M >= 1 && H >= 8 && H <= 4096 && H % 8 == 0 && n_src >= 1, who);
+  T_ARG(row_idx ? all_in(row_idx, M, 0, n_src) : n_src >= M, who);
+  DevPool pool;
+  void* dx = up_act(pool, PREC_F16, x, (size_t)n_src * H); T_PTR(dx);
+  float* dg = (float*)pool.up(gamma, (size_t)H * 4); T_PTR(dg);
+  float* db = (float*)pool.up(beta, (size_t)H * 4); T_PTR(db);
+  int* di = row_idx ? (int*)pool.up(row_idx, (size_t)M * 4) : nullptr;
+  if (row_idx) T_PTR(di);
+  Guarded ga;
+  T_CHECK(ga.make(pool, (size_t)M * H / 2));
+  T_HIP(hipDeviceSynchronize());
+  const int rc = launch_layernorm_x16(precision, dx, di, dg, db, eps, M, H, ga.p<void>(), nullptr);
+  T_HIP(hipDeviceSynchronize());
+  T_CHECK(ga.down(y_act));
+  return launch_status(rc);
+}
+
+int czc_test_layernorm_splitk(int precision, int nslab, int M, int H, int ld, const float* slabs, const float* bias, const float* resid,
+                              int ldr, const float* gamma, const float* beta, float eps, int32_t* y_act, float* y_f32) {
+  const char* who = "layernorm_splitk";
+  T_ARG(prec_known(precision) && nslab >= 1 && nslab <= 64 && M >= 1 && H >= 1 && H <= 4096 && ld >= H && (!resid || ldr >= H), who);
+  DevPool pool;
+  float* ds = (float*)pool.up(slabs, (size_t)nslab * M * ld * 4); T_PTR(ds);
+  float* dbias = bias ? (float*)pool.up(bias, (size_t)H * 4) : nullptr;
+  float* dres = resid ? (float*)pool.up(resid, (size_t)M * ldr * 4) : nullptr;
+  if (bias) T_PTR(dbias);
+  if (resid) T_PTR(dres);
+  float* dg = (float*)pool.up(gamma, (size_t)H * 4); T_PTR(dg);
+  float* db = (float*)pool.up(beta, (size_t)H * 4); T_PTR(db);
+  Guarded ga, gf;
+  T_CHECK(ga.make(pool, act_words(precision, (size_t)M * H))); T_CHECK(gf.make(pool, (size_t)M * H));
+  SplitkPending sk;
+  sk.slabs = ds; sk.nslab = nslab; sk.slab_stride = (long)M * ld; sk.ld = ld;
+  const int rc = HK().layernorm_splitk(precision, sk, dbias, dres, ldr, dg, db, eps, M, H, ga.p<void>(), gf.p<float>(), nullptr);
+  T_HIP(hipDeviceSynchronize());
+  T_CHECK(ga.down(y_act));
+  T_CHECK(gf.down(y_f32));
+  return launch_status(rc);
+}
+
+int czc_test_ln_finalize(int nblk, int M, int ld, const float* part, float eps, float* stat) {
+  const char* who = "ln_finalize";
+  T_ARG(nblk >= 1 && nblk <= 64 && M >= 1 && ld >= M, who);
+  DevPool pool;
+  float* dp = (float*)pool.up(part, (size_t)nblk * ld * 8); T_PTR(dp);
+  Guarded gs;
+  T_CHECK(gs.make(pool, (size_t)M * 2));
+  const int rc = launch_ln_finalize(dp, ld, nblk, M, eps, gs.p<float>(), nullptr);
+  T_HIP(hipDeviceSynchronize());
+  T_CHECK(gs.down(stat));
+  return launch_status(rc);
+}
+
+int czc_test_bert_embed(int precision, int B, int T, int H, int V, int n_pos, const int32_t* ids, const float* word, const float* pos,
+                        const float* type0, const float* gamma, const float* beta, float eps, int32_t* y_act, float* y_f32) {
+  const char* who = "bert_embed";
+  T_ARG(prec_known(precision) && B >= 1 && T >= 1 && T <= n_pos && H >= 1 && H <= 4096 && V >= 1 && all_in(ids, (size_t)B * T, 0, V), who);
+  DevPool pool;
+  int* di = (int*)pool.up(ids, (size_t)B * T * 4); T_PTR(di);
+  float* dw = (float*)pool.up(word, (size_t)V * H * 4); T_PTR(dw);
+  float* dp = (float*)pool.up(pos, (size_t)n_pos * H * 4); T_PTR(dp);
+  float* dt = (float*)pool.up(type0, (size_t)H * 4); T_PTR(dt);
+  float* dg = (float*)pool.up(gamma, (size_t)H * 4); T_PTR(dg);
+  float* db = (float*)pool.up(beta, (size_t)H * 4); T_PTR(db);
+  Guarded ga, gf;
+  T_CHECK(ga.make(pool, act_words(precision, (size_t)B * T * H))); T_CHECK(gf.make(pool, (size_t)B * T * H));
+  const int rc = HK().bert_embed(precision, di, B, T, H, dw, dp, dt, dg, db, eps, ga.p<void>(), gf.p<float>(), nullptr);
+  T_HIP(hipDeviceSynchronize());
+  T_CHECK(ga.down(y_act));
+  T_CHECK(gf.down(y_f32));
+  return launch_status(rc);
+}
+
+int czc_test_bert_embed_ragged(int precision, int n, int n_id_rows, int ids_stride, int max_T, int H, int V, int n_pos, const int32_t* ids,
+                               const int32_t* run, const int32_t* row_off, const int32_t* row_len, int n_out_rows, const float* word,
+                               const float* pos, const float* type0, const float* gamma, const float* beta, float eps, int32_t* y_act,
+                               float* y_f32) {
+  const char* who = "bert_embed_ragged";
+  T_ARG(prec_known(precision) && n >= 1 && n_id_rows >= 1 && ids_stride >= 1 && max_T >= 1 && max_T <= n_pos && H >= 1 && H <= 4096 && V >= 1 &&
+        n_out_rows >= 1, who);
+  T_ARG(all_in(ids, (size_t)n_id_rows * ids_stride, 0, V), who);  // the padding columns too: a wrong read must show as a value
+  T_ARG(run ? all_in(run, n, 0, n_id_rows) : n <= n_id_rows, who);
+  T_ARG(all_in(row_len, n, 0, (max_T < ids_stride ? max_T : ids_stride) + 1), who);
+  for (int b = 0; b < n; ++b) T_ARG(row_off[b] >= 0 && row_off[b] + row_len[b] <= n_out_rows, who);
+  DevPool pool;
+  int* di = (int*)pool.up(ids, (size_t)n_id_rows * ids_stride * 4); T_PTR(di);
+  int* drun = run ? (int*)pool.up(run, (size_t)n * 4) : nullptr;
+  if (run) T_PTR(drun);
+  int* doff = (int*)pool.up(row_off, (size_t)(n + 1) * 4); T_PTR(doff);
+  int* dlen = (int*)pool.up(row_len, (size_t)n * 4); T_PTR(dlen);
+  float* dw = (float*)pool.up(word, (size_t)V * H * 4); T_PTR(dw);
+  float* dp = (float*)pool.up(pos, (size_t)n_pos * H * 4); T_PTR(dp);
+  float* dt = (float*)pool.up(type0, (size_t)H * 4); T_PTR(dt);
+  float* dg = (float*)pool.up(gamma, (size_t)H * 4); T_PTR(dg);
+  float* db = (float*)pool.up(beta, (size_t)H * 4); T_PTR(db);
+  Guarded ga, gf;
+  T_CHECK(ga.make(pool, act_words(precision, (size_t)n_out_rows * H))); T_CHECK(gf.make(pool, (size_t)n_out_rows * H));
+  const int rc = HK().bert_embed_ragged(precision, di, ids_stride, drun, doff, dlen, n, max_T, H, dw, dp, dt, dg, db, eps, ga.p<void>(),
+                                        gf.p<float>(), nullptr);
+  T_HIP(hipDeviceSynchronize());
+  T_CHECK(ga.down(y_act));
+  T_CHECK(gf.down(y_f32));
+  return launch_status(rc);
+}
+
+int czc_test_clip_embed(int mode, int n_seg, int max_len, int H, int n_id_rows, int ids_stride, const int32_t* ids, const int32_t* seg_src,
+                        const int32_t* seg_pos0, const int32_t* own_off, const int32_t* own_len, int V, int n_pos, const float* tok,
+                        const float* pos, int n_out_rows, float eps, int32_t* x_out, float* stat) {
+  const char* who = "clip_embed";
+  T_ARG(mode >= 0 && mode <= 2 && n_seg >= 1 && max_len >= 1 && H >= 1 && H <= 4096 && n_id_rows >= 1 && ids_stride >= 1 && V >= 1 && n_pos >= 1 &&
+        n_out_rows >= 1, who);
+  T_ARG(all_in(ids, (size_t)n_id_rows * ids_stride, 0, V) && all_in(seg_src, n_seg, 0, n_id_rows) && all_in(own_len, n_seg, 0, max_len + 1), who);
+  for (int s = 0; s < n_seg; ++s)
+    T_ARG(seg_pos0[s] >= 0 && seg_pos0[s] + own_len[s] <= ids_stride && seg_pos0[s] + own_len[s] <= n_pos && own_off[s] >= 0 &&
+          own_off[s] + own_len[s] <= n_out_rows, who);
+  DevPool pool;
+  int* di = (int*)pool.up(ids, (size_t)n_id_rows * ids_stride * 4); T_PTR(di);
+  int* dsrc = (int*)pool.up(seg_src, (size_t)n_seg * 4); T_PTR(dsrc);
+  int* dp0 = (int*)pool.up(seg_pos0, (size_t)n_seg * 4); T_PTR(dp0);
+  int* doff = (int*)pool.up(own_off, (size_t)n_seg * 4); T_PTR(doff);
+  int* dlen = (int*)pool.up(own_len, (size_t)n_seg * 4); T_PTR(dlen);
+  float* dtok = (float*)pool.up(tok, (size_t)V * H * 4); T_PTR(dtok);
+  float* dpos = (float*)pool.up(pos, (size_t)n_pos * H * 4); T_PTR(dpos);
+  Guarded gx, gs;
+  T_CHECK(gx.make(pool, act_words(mode ? PREC_F16 : PREC_F32, (size_t)n_out_rows * H))); T_CHECK(gs.make(pool, (size_t)n_out_rows * 2));
+  const int rc = HK().clip_embed(di, ids_stride, dsrc, dp0, doff, dlen, n_seg, max_len, H, dtok, dpos, gx.p<float>(), nullptr, mode ? 1 : 0,
+                                 mode == 2 ? gs.p<float>() : nullptr, eps);
+  T_HIP(hipDeviceSynchronize());
+  T_CHECK(gx.down(x_out));
+  T_CHECK(gs.down(stat));
+  return launch_status(rc);
+}
+
+int czc_test_im2col(int precision, int B, int S, int p, const float* pixels, int32_t* out) {
+  const char* who = "im2col";
+  T_ARG(prec_known(precision) && B >= 1 && S >= 1 && S <= 1024 && p >= 1 && p <= S, who);
+  DevPool pool;
+  float* dpix = (float*)pool.up(pixels, (size_t)B * 3 * S * S * 4); T_PTR(dpix);
+  Guarded go;
+  T_CHECK(go.make(pool, act_words(precision, (size_t)B * (S / p) * (S / p) * 3 * p * p)));
+  const int rc = HK().im2col(precision, dpix, B, S, p, go.p<void>(), nullptr);
+  T_HIP(hipDeviceSynchronize());
+  T_CHECK(go.down(out));
+  return launch_status(rc);
+}
+
+int czc_test_vision_assemble(int B, int P, int H, const float* patch_out, const float* cls, const float* pos, float* x) {
+  const char* who = "vision_assemble";
+  T_ARG(B >= 1 && P >= 1 && H >= 1, who);
+  DevPool pool;
+  float* dpo = (float*)pool.up(patch_out, (size_t)B * P * H * 4); T_PTR(dpo);
+  float* dcls = (float*)pool.up(cls, (size_t)H * 4); T_PTR(dcls);
+  float* dpos = (float*)pool.up(pos, (size_t)(P + 1) * H * 4); T_PTR(dpos);
+  Guarded gx;
+  T_CHECK(gx.make(pool, (size_t)B * (P + 1) * H));
+  const int rc = HK().vision_assemble(dpo, B, P, H, dcls, dpos, gx.p<float>(), nullptr);
+  T_HIP(hipDeviceSynchronize());
+  T_CHECK(gx.down(x));
+  return launch_status(rc);
+}
+
+int czc_test_l2_normalize(int M, int D, const float* x, float* y) {
+  const char* who = "l2_normalize";
+  T_ARG(M >= 1 && D >= 1, who);
+  DevPool pool;
+  float* dx = (float*)pool.up(x, (size_t)M * D * 4); T_PTR(dx);
+  Guarded gy;
+  T_CHECK(gy.make(pool, (size_t)M * D));
+  const int rc = launch_l2_normalize(dx, M, D, gy.p<float>(), nullptr);
+  T_HIP(hipDeviceSynchronize());
+  T_CHECK(gy.down(y));
+  return launch_status(rc);
+}
+
+// kind 0: launch_gather_rows_f32 (W floats per row), 1: launch_gather_rows_bytes (W bytes per row, W % 4 == 0 here), 2:
+// launch_gather_rows_w32 (W words per row); src: n_src rows, dst: M rows
+int czc_test_gather_rows(int kind, int M, int W, int n_src, const int32_t* src, const int32_t* idx, int32_t* dst) {
+  const char* who = "gather_rows";
+  T_ARG(kind >= 0 && kind <= 2 && M >= 1 && W >= 1 && n_src >= 1 && (kind != 1 || W % 4 == 0) && all_in(idx, M, 0, n_src), who);
+  const size_t rw = kind == 1 ? W / 4 : W;
+  DevPool pool;
+  int* ds = (int*)pool.up(src, (size_t)n_src * rw * 4); T_PTR(ds);
+  int* di = (int*)pool.up(idx, (size_t)M * 4); T_PTR(di);
+  Guarded gd;
+  T_CHECK(gd.make(pool, (size_t)M * rw));
+  const int rc = kind == 0   ? HK().gather_rows_f32((const float*)ds, di, M, W, gd.p<float>(), nullptr)
+                 : kind == 1 ? HK().gather_rows_bytes(ds, di, M, W, gd.p<void>(), nullptr)
+                             : HK().gather_rows_w32(ds, di, M, W, gd.p<void>(), nullptr);
+  T_HIP(hipDeviceSynchronize());
+  T_CHECK(gd.down(dst));
+  return launch_status(rc);
+}
+
+// gen_rows NULL: launch_mask_positions at gen_idx; else launch_mask_positions_rows (a row with gen_rows[b] < 0 is left alone)
+int czc_test_mask_positions(int B, int T, int gen_idx, const int32_t* gen_rows, int n_mask, int mask_id, const int32_t* inp, int32_t* inp_out) {
+  const char* who = "mask_positions";
+  T_ARG(B >= 1 && T >= 1 && n_mask >= 0 && (long)B * n_mask < (1 << 24) && (gen_rows ? all_in(gen_rows, B, -1, 1 << 20) : gen_idx >= 0), who);
+  DevPool pool;
+  Guarded gi;
+  T_CHECK(guarded_in(pool, gi, inp, (size_t)B * T));
+  int* dgen = gen_rows ? (int*)pool.up(gen_rows, (size_t)B * 4) : nullptr;
+  if (gen_rows) T_PTR(dgen);
+  const int rc = gen_rows ? HK().mask_positions_rows(gi.p<int>(), B, T, dgen, n_mask, mask_id, nullptr)
+                          : HK().mask_positions(gi.p<int>(), B, T, gen_idx, n_mask, mask_id, nullptr);
+  T_HIP(hipDeviceSynchronize());
+  T_CHECK(gi.down(inp_out));
+  return launch_status(rc);
+}
+
+int czc_test_tie_rows(int R, int T, int G, const int32_t* inp, const int32_t* col, const int32_t* grp_of_row, const int32_t* grp_off,
+                      const int32_t* grp_rows, int32_t* inp_out) {
+  const char* who = "tie_rows";
+  T_ARG(R >= 1 && T >= 1 && G >= 1 && all_in(grp_of_row, R, 0, G) && grp_off[0] == 0, who);
+  for (int g = 0; g < G; ++g) T_ARG(grp_off[g + 1] >= grp_off[g] && grp_off[g + 1] <= (1 << 24), who);
+  const int n_gr = grp_off[G];
+  DevPool pool;
+  Guarded gi;
+  T_CHECK(guarded_in(pool, gi, inp, (size_t)R * T));
+  int* dcol = (int*)pool.up(col, (size_t)R * 4); T_PTR(dcol);
+  int* dgor = (int*)pool.up(grp_of_row, (size_t)R * 4); T_PTR(dgor);
+  int* dgoff = (int*)pool.up(grp_off, (size_t)(G + 1) * 4); T_PTR(dgoff);
+  int* dgr = (int*)pool.up(grp_rows, (size_t)(n_gr ? n_gr : 1) * 4); T_PTR(dgr);
+  const int rc = HK().tie_rows(gi.p<int>(), R, T, dcol, dgor, dgoff, dgr, nullptr);
+  T_HIP(hipDeviceSynchronize());
+  T_CHECK(gi.down(inp_out));
+  return launch_status(rc);
+}
+
+// The image memo of czc_generate, as memo_step of engine.hip chains it for one sub-step: launch_memo_check; then (stages != 0), with n =
+// tot[0] read back: launch_memo_fill when n < B; nothing more when n == 0; else launch_memo_gather (use_list: the compact batch
+// of the listed images; else the whole batch in place, keys only), "the step" (compact row i takes new_rows / new_cos / new_max of
+// its image: what the host says the step leaves), launch_memo_scatter.  record 0: no key is written and the entry (ent_*) is not
+// passed to the scatter.  In: inp, key [B*T], img_max [2*B], img_n [B*D], new_rows [B*T], new_cos, new_max [B], ent_rows [B*T],
+// ent_cos, ent_max, bcos_in [B].  Out (guarded): hit, list [B], tot [4], key_out, inp_out [B*T], bcos_out [B], ent_rows_out [B*T],
+// ent_cos_out, ent_max_out [B], inp_c [B*T], img_c [B*D].
+int czc_test_memo_chain(int B, int T, int D, int gen_idx, int n_mask, int mask_id, int n_sub, int stages, int use_list, int record,
+                        const int32_t* inp, const int32_t* key, const int32_t* img_max, const float* img_n, const int32_t* new_rows,
+                        const float* new_cos, const int32_t* new_max, const int32_t* ent_rows, const float* ent_cos, const int32_t* ent_max,
+                        const float* bcos_in, int32_t* hit, int32_t* list, int32_t* tot, int32_t* key_out, int32_t* inp_out, float* bcos_out,
+                        int32_t* ent_rows_out, float* ent_cos_out, int32_t* ent_max_out, int32_t* inp_c, float* img_c) {
+  const char* who = "memo_chain";
+  T_ARG(B >= 1 && B <= (1 << 20) && T >= 1 && D >= 1 && gen_idx >= 0 && n_mask >= 0 && n_sub >= 1 && n_sub <= 2, who);
+  const size_t bt = (size_t)B * T;
+  DevPool pool;
+  Guarded ginp, gkey, ghit, glist, gtot, gbcos, grows, gcos, gmax, ginpc, gimgc;
+  T_CHECK(guarded_in(pool, ginp, inp, bt)); T_CHECK(guarded_in(pool, gkey, key, bt));
+  T_CHECK(ghit.make(pool, B)); T_CHECK(glist.make(pool, B)); T_CHECK(gtot.make(pool, 4));
+  T_CHECK(guarded_in(pool, gbcos, bcos_in, B)); T_CHECK(guarded_in(pool, grows, ent_rows, bt)); T_CHECK(guarded_in(pool, gcos, ent_cos, B));
+  T_CHECK(guarded_in(pool, gmax, ent_max, B)); T_CHECK(ginpc.make(pool, bt)); T_CHECK(gimgc.make(pool, (size_t)B * D));
+  int* dimax = (int*)pool.up(img_max, (size_t)2 * B * 4); T_PTR(dimax);
+  int rc = HK().memo_check(ginp.p<int>(), B, T, gen_idx, n_mask, mask_id, gkey.p<int>(), dimax, n_sub, ghit.p<int>(), glist.p<int>(),
+                           gtot.p<int>(), nullptr);
+  T_HIP(hipDeviceSynchronize());
+  if (rc == 0 && stages) {
+    int n = 0;
+    T_HIP(hipMemcpy(&n, gtot.p<int>(), 4, hipMemcpyDeviceToHost));
+    T_ARG(n >= 0 && n <= B, who);
+    std::vector<int> hl((size_t)B);
+    T_HIP(hipMemcpy(hl.data(), glist.p<int>(), (size_t)B * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; ++i) T_ARG(hl[i] >= 0 && hl[i] < B, who);  // a wrong list is reported, never followed
+    if (n < B) rc = HK().memo_fill(ghit.p<int>(), B, T, grows.p<int>(), gcos.p<float>(), ginp.p<int>(), gbcos.p<float>(), nullptr);
+    if (rc == 0 && n > 0) {
+      const bool compact = use_list != 0;
+      const int m = compact ? n : B;
+      float* dimg = (float*)pool.up(img_n, (size_t)B * D * 4); T_PTR(dimg);
+      rc = compact ? HK().memo_gather(ginp.p<int>(), glist.p<int>(), n, T, gen_idx, n_mask, mask_id, record ? gkey.p<int>() : nullptr,
+                                      ginpc.p<int>(), dimg, D, gimgc.p<float>(), nullptr)
+                   : HK().memo_gather(ginp.p<int>(), nullptr, B, T, gen_idx, n_mask, mask_id, record ? gkey.p<int>() : nullptr, nullptr, nullptr,
+                                      D, nullptr, nullptr);
+      std::vector<int> rows_c((size_t)m * T), max_c((size_t)m);
+      std::vector<float> cos_c((size_t)m);
+      for (int i = 0; i < m; ++i) {
+        const int b = compact ? hl[i] : i;
+        memcpy(&rows_c[(size_t)i * T], new_rows + (size_t)b * T, (size_t)T * 4);
+        cos_c[i] = new_cos[b]; max_c[i] = new_max[b];
+      }
+      int* drows = (int*)pool.up(rows_c.data(), rows_c.size() * 4); T_PTR(drows);
+      float* dcos = (float*)pool.up(cos_c.data(), cos_c.size() * 4); T_PTR(dcos);
+      int* dmax = (int*)pool.up(max_c.data(), max_c.size() * 4); T_PTR(dmax);
+      if (rc == 0)
+        rc = HK().memo_scatter(drows, dcos, dmax, compact ? glist.p<int>() : nullptr, m, T, ginp.p<int>(), gbcos.p<float>(),
+                               record ? grows.p<int>() : nullptr, record ? gcos.p<float>() : nullptr, record ? gmax.p<int>() : nullptr, nullptr);
+    }
+    T_HIP(hipDeviceSynchronize());
+  }
+  T_CHECK(ghit.down(hit)); T_CHECK(glist.down(list)); T_CHECK(gtot.down(tot)); T_CHECK(gkey.down(key_out)); T_CHECK(ginp.down(inp_out));
+  T_CHECK(gbcos.down(bcos_out)); T_CHECK(grows.down(ent_rows_out)); T_CHECK(gcos.down(ent_cos_out)); T_CHECK(gmax.down(ent_max_out));
+  T_CHECK(ginpc.down(inp_c)); T_CHECK(gimgc.down(img_c));
+  return launch_status(rc);
+}
+
+// The rows memo of czc_generate_rows, sub-step j of a group, as engine.hip chains it: launch_memo_rows_check; then (stages != 0), with n
+// = tot[0]: launch_memo_rows_fill when n < R; nothing more when n == 0; else launch_memo_rows_gather (use_list: compact batch of the
+// listed rows; else all R rows in place, recording only), "the step" (new_rows / new_cos / new_max of each row), launch_memo_rows_scatter.
+// Table in / out (guarded): valid, sig [L*R], key [L*R*T], rows [L*2*R*T], cos, imax [L*2*R].  tau NULL or [R]: czc_draw taus.
+// col / dot [R]: this step's schedule slice.  Out: hit [R], cnt [(R + 255) / 256], list [R], tot [4], inp_out [R*T], bcos_out [R], inp_c
+// [R*T], img_c [R*D], col_c, dot_c [R].
+int czc_test_memo_rows_chain(int R, int T, int L, int seed_len, int D, int n_mask0, int n_sub, int mask_id, int j, int stages, int use_list,
+                             int record, const int32_t* inp, const int32_t* col0, const int32_t* col1, const float* tau, const int32_t* col,
+                             const int32_t* dot, const float* img_n, const int32_t* new_rows, const float* new_cos, const int32_t* new_max,
+                             const float* bcos_in, const int32_t* valid, const int32_t* sig, const int32_t* key, const int32_t* rows,
+                             const float* cos, const int32_t* imax, int32_t* valid_out, int32_t* sig_out, int32_t* key_out, int32_t* rows_out,
+                             float* cos_out, int32_t* imax_out, int32_t* hit, int32_t* cnt, int32_t* list, int32_t* tot, int32_t* inp_out,
+                             float* bcos_out, int32_t* inp_c, float* img_c, int32_t* col_c, int32_t* dot_c) {
+  const char* who = "memo_rows_chain";
+  T_ARG(R >= 1 && R <= CZC_MAX_ROWS && T >= 1 && L >= 1 && L <= 64 && seed_len >= 0 && D >= 1 && n_mask0 >= 0 && n_sub >= 1 && n_sub <= MEMO_ROWS_SUB &&
+        j >= 0 && j < MEMO_ROWS_SUB, who);
+  const size_t rt = (size_t)R * T, lr = (size_t)L * R, nb = (size_t)(R + 255) / 256;
+  DevPool pool;
+  Guarded ginp, gvalid, gsig, gkey, grows, gcos, gimax, ghit, gcnt, glist, gtot, gbcos, ginpc, gimgc, gcolc, gdotc;
+  T_CHECK(guarded_in(pool, ginp, inp, rt)); T_CHECK(guarded_in(pool, gvalid, valid, lr)); T_CHECK(guarded_in(pool, gsig, sig, lr));
+  T_CHECK(guarded_in(pool, gkey, key, lr * T)); T_CHECK(guarded_in(pool, grows, rows, lr * MEMO_ROWS_SUB * T));
+  T_CHECK(guarded_in(pool, gcos, cos, lr * MEMO_ROWS_SUB)); T_CHECK(guarded_in(pool, gimax, imax, lr * MEMO_ROWS_SUB));
+  T_CHECK(ghit.make(pool, R)); T_CHECK(gcnt.make(pool, nb)); T_CHECK(glist.make(pool, R)); T_CHECK(gtot.make(pool, 4));
+  T_CHECK(guarded_in(pool, gbcos, bcos_in, R)); T_CHECK(ginpc.make(pool, rt)); T_CHECK(gimgc.make(pool, (size_t)R * D));
+  T_CHECK(gcolc.make(pool, R)); T_CHECK(gdotc.make(pool, R));
+  int* dcol0 = (int*)pool.up(col0, (size_t)R * 4); T_PTR(dcol0);
+  int* dcol1 = col1 ? (int*)pool.up(col1, (size_t)R * 4) : nullptr;
+  if (col1) T_PTR(dcol1);
+  RowDraw* ddraw = nullptr;
+  if (tau) {
+    std::vector<RowDraw> hd((size_t)R, RowDraw{0u, 0u, 0.f, 0u});
+    for (int r = 0; r < R; ++r) hd[r].tau = tau[r];
+    ddraw = (RowDraw*)pool.up(hd.data(), hd.size() * sizeof(RowDraw)); T_PTR(ddraw);
+  }
+  MemoRowsTab m;
+  m.valid = gvalid.p<int>(); m.sig = gsig.p<int>(); m.key = gkey.p<int>(); m.rows = grows.p<int>(); m.cos = gcos.p<float>();
+  m.imax = gimax.p<int>(); m.R = R; m.T = T; m.L = L; m.seed_len = seed_len;
+  int rc = HK().memo_rows_check(ginp.p<int>(), m, dcol0, dcol1, n_mask0, n_sub, mask_id, ghit.p<int>(), gcnt.p<int>(), glist.p<int>(),
+                                gtot.p<int>(), nullptr, ddraw);
+  T_HIP(hipDeviceSynchronize());
+  if (rc == 0 && stages) {
+    int n = 0;
+    T_HIP(hipMemcpy(&n, gtot.p<int>(), 4, hipMemcpyDeviceToHost));
+    T_ARG(n >= 0 && n <= R, who);
+    std::vector<int> hl((size_t)R);
+    T_HIP(hipMemcpy(hl.data(), glist.p<int>(), (size_t)R * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; ++i) T_ARG(hl[i] >= 0 && hl[i] < R, who);
+    if (n < R) rc = HK().memo_rows_fill(ghit.p<int>(), m, dcol0, j, ginp.p<int>(), gbcos.p<float>(), nullptr);
+    if (rc == 0 && n > 0) {
+      const bool compact = use_list != 0;
+      const int cnt_rows = compact ? n : R;
+      int* dcol = (int*)pool.up(col, (size_t)R * 4); T_PTR(dcol);
+      int* ddot = (int*)pool.up(dot, (size_t)R * 4); T_PTR(ddot);
+      float* dimg = (float*)pool.up(img_n, (size_t)R * D * 4); T_PTR(dimg);
+      rc = compact ? HK().memo_rows_gather(ginp.p<int>(), glist.p<int>(), n, m, dcol0, dcol1, n_mask0, n_sub, mask_id, record ? 1 : 0, dcol, ddot,
+                                           ginpc.p<int>(), dimg, D, gimgc.p<float>(), gcolc.p<int>(), gdotc.p<int>(), nullptr)
+                   : (record ? HK().memo_rows_gather(ginp.p<int>(), nullptr, R, m, dcol0, dcol1, n_mask0, n_sub, mask_id, 1, dcol, ddot, nullptr,
+                                                     nullptr, D, nullptr, nullptr, nullptr, nullptr)
+                             : 0);
+      std::vector<int> rows_c((size_t)cnt_rows * T), max_c((size_t)cnt_rows);
+      std::vector<float> cos_c((size_t)cnt_rows);
+      for (int i = 0; i < cnt_rows; ++i) {
+        const int r = compact ? hl[i] : i;
+        memcpy(&rows_c[(size_t)i * T], new_rows + (size_t)r * T, (size_t)T * 4);
+        cos_c[i] = new_cos[r]; max_c[i] = new_max[r];
+      }
+      int* drows = (int*)pool.up(rows_c.data(), rows_c.size() * 4); T_PTR(drows);
+      float* dcos = (float*)pool.up(cos_c.data(), cos_c.size() * 4); T_PTR(dcos);
+      int* dmax = (int*)pool.up(max_c.data(), max_c.size() * 4); T_PTR(dmax);
+      if (rc == 0)
+        rc = HK().memo_rows_scatter(drows, dcos, dmax, compact ? glist.p<int>() : nullptr, cnt_rows, m, dcol0, j, record ? 1 : 0, ginp.p<int>(),
+                                    gbcos.p<float>(), nullptr);
+    }
+    T_HIP(hipDeviceSynchronize());
+  }
+  T_CHECK(gvalid.down(valid_out)); T_CHECK(gsig.down(sig_out)); T_CHECK(gkey.down(key_out)); T_CHECK(grows.down(rows_out));
+  T_CHECK(gcos.down(cos_out)); T_CHECK(gimax.down(imax_out)); T_CHECK(ghit.down(hit)); T_CHECK(gcnt.down(cnt)); T_CHECK(glist.down(list));
+  T_CHECK(gtot.down(tot)); T_CHECK(ginp.down(inp_out)); T_CHECK(gbcos.down(bcos_out)); T_CHECK(ginpc.down(inp_c)); T_CHECK(gimgc.down(img_c));
+  T_CHECK(gcolc.down(col_c)); T_CHECK(gdotc.down(dot_c));
+  return launch_status(rc);
+}
+
+}  // extern "C"

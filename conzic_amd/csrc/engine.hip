@@ -3016,7 +3016,11 @@ const void* czc_internal_hooks(int abi) {
       &launch_scan, &launch_prefix_plan, &launch_prefix_finish, &launch_refine_select, &launch_refine_select_rows,
       &launch_refine_select_draw, &launch_refine_plan, &launch_refine_finish, &launch_refine_cosine,
       &launch_attention_image_pooled, &launch_attention_shared_mapped, &launch_layer0_count, &launch_layer0_map,
-      &test_text_tower};
+      &test_text_tower,
+      &launch_layernorm_splitk, &launch_bert_embed, &launch_bert_embed_ragged, &launch_clip_embed, &launch_im2col, &launch_vision_assemble,
+      &launch_gather_rows_f32, &launch_gather_rows_bytes, &launch_gather_rows_w32, &launch_mask_positions, &launch_mask_positions_rows,
+      &launch_tie_rows, &launch_memo_check, &launch_memo_gather, &launch_memo_scatter, &launch_memo_fill, &launch_memo_rows_check,
+      &launch_memo_rows_gather, &launch_memo_rows_scatter, &launch_memo_rows_fill};
   return abi == HOOKS_ABI ? &h : nullptr;
 }
 

@@ -415,7 +415,7 @@ int launch_index_search(const split_t* index, int n, int D, const split_t* queri
 // ---- czc_internal_hooks (declared below, private to the build): what libconzic_hip_test.so may reach inside this library -----------
 // The product library has hidden visibility; the hook library (api_test.hip) gets the launchers it wraps and the
 // process-wide kernel-family switches it flips through this table instead of through exported C++ symbols.
-constexpr int HOOKS_ABI = 0x0608;
+constexpr int HOOKS_ABI = 0x0609;
 struct Hooks {
   char* (*err_buf)();  // the calling host thread's g_err [512]
   decltype(&launch_gemm) gemm;
@@ -454,6 +454,27 @@ struct Hooks {
   decltype(&launch_layer0_map) layer0_map;
   // the engine's text tower on host-given id rows (engine.hip test_text_tower; `engine` is a czc_engine*)
   int (*text_tower)(void* engine, const int32_t* clip_ids, const int32_t* clip_len, int B, int K, float* out, int32_t* n_dup);
+  // the row, embedding, mover and memo kernels one by one (tests/test_row_kernels_gpu.py, tests/test_mover_memo_kernels_gpu.py)
+  decltype(&launch_layernorm_splitk) layernorm_splitk;
+  decltype(&launch_bert_embed) bert_embed;
+  decltype(&launch_bert_embed_ragged) bert_embed_ragged;
+  decltype(&launch_clip_embed) clip_embed;
+  decltype(&launch_im2col) im2col;
+  decltype(&launch_vision_assemble) vision_assemble;
+  decltype(&launch_gather_rows_f32) gather_rows_f32;
+  decltype(&launch_gather_rows_bytes) gather_rows_bytes;
+  decltype(&launch_gather_rows_w32) gather_rows_w32;
+  decltype(&launch_mask_positions) mask_positions;
+  decltype(&launch_mask_positions_rows) mask_positions_rows;
+  decltype(&launch_tie_rows) tie_rows;
+  decltype(&launch_memo_check) memo_check;
+  decltype(&launch_memo_gather) memo_gather;
+  decltype(&launch_memo_scatter) memo_scatter;
+  decltype(&launch_memo_fill) memo_fill;
+  decltype(&launch_memo_rows_check) memo_rows_check;
+  decltype(&launch_memo_rows_gather) memo_rows_gather;
+  decltype(&launch_memo_rows_scatter) memo_rows_scatter;
+  decltype(&launch_memo_rows_fill) memo_rows_fill;
 };
 
 }  // namespace czc

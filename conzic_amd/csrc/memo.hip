@@ -133,6 +133,7 @@ __global__ __launch_bounds__(64) void memo_fill_kernel(const int* hit, int T, co
 
 int launch_memo_fill(const int* hit, int B, int T, const int* out_rows, const float* out_cos, int* inp, float* bcos_full,
                      hipStream_t st) {
+  if (B <= 0) return 0;
   hipLaunchKernelGGL(memo_fill_kernel, dim3(B), dim3(64), 0, st, hit, T, out_rows, out_cos, inp, bcos_full);
   CZC_HIP_CHECK(hipGetLastError());
   return 0;

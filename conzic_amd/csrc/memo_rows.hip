@@ -192,6 +192,7 @@ __global__ __launch_bounds__(64) void memo_rows_fill_kernel(const int* hit, Memo
 
 int launch_memo_rows_fill(const int* hit, const MemoRowsTab& m, const int* col0, int j, int* inp, float* bcos_full, hipStream_t st) {
   if (j < 0 || j >= MEMO_ROWS_SUB) { snprintf(g_err, sizeof(g_err), "memo_rows fill: bad sub-step"); return 1; }
+  if (m.R <= 0) return 0;
   hipLaunchKernelGGL(memo_rows_fill_kernel, dim3(m.R), dim3(64), 0, st, hit, m, col0, j, inp, bcos_full);
   CZC_HIP_CHECK(hipGetLastError());
   return 0;

@@ -49,7 +49,7 @@ int launch_bert_embed_ragged(int prec, const int* ids, int ids_stride, const int
                              int max_T, int H, const float* word, const float* pos, const float* type0, const float* gamma,
                              const float* beta, float eps, void* y_act, float* y_f32, hipStream_t st) {
   if (n <= 0 || max_T <= 0) return 0;
-  if (H % 4 || H > LN_MAXV * 256 || max_T > ids_stride || !row_off || !row_len) {
+  if (H <= 0 || H % 4 || H > LN_MAXV * 256 || (prec == PREC_F16X3 && y_act && H % 8) || max_T > ids_stride || !row_off || !row_len) {
     snprintf(g_err, sizeof(g_err), "bert_embed_ragged: unsupported shape (H=%d, max_T=%d, stride=%d)", H, max_T, ids_stride);
     return 1;
   }

@@ -146,7 +146,9 @@ int launch_layernorm_x16(int prec, const void* x16, const int* row_idx, const fl
 // LayerNorm folded into the consumer GEMM (round 5): (mean, rstd) per row from the producers' partials -- row_part[b * ld + m] =
 // (sum, sum of squares) of row m's stored fp16 values over 32-column block b -- summed over the blocks in order.  One kernel
 // for every row count, so the statistics do not depend on the batch.  var = E[x^2] - mean^2 in fp32 (clamped at 0): the rows of
-// these towers have |mean| of the order of their spread, so the subtraction costs a few ulps, not digits.
+// these towers have |mean| of the order of their spread, so the subtraction costs a few ulps, not digits.  The relative error of
+// rstd grows as u (1 + mean^2 / var); measured against fp64 of the same partials (tests/test_row_kernels_gpu.py): 2e-7 up to
+// |mean| = spread, 1.5e-6 at 4 spreads, 2.3e-5 at 16 spreads -- still far below the fp16 operands' 5e-4, but digits, not ulps.
 __global__ __launch_bounds__(256) void ln_finalize_kernel(const float2* part, long ld, int nblk, int M, float eps, float2* stat) {
   const int m = blockIdx.x * 256 + threadIdx.x;
   if (m >= M) return;
@@ -270,7 +272,7 @@ int launch_fold_ln(const float* W, const float* gamma, const float* beta, const 
 int launch_layernorm(int prec, const float* x, const int* row_idx, const float* gamma, const float* beta, float eps,
                      int M, int H, void* y_act, float* y_f32, hipStream_t st) {
   if (M <= 0) return 0;
-  if (H % 4 || H > LN_MAXV * 256) {
+  if (H <= 0 || H % 4 || H > LN_MAXV * 256 || (prec == PREC_F16X3 && y_act && H % 8)) {  // split rows are whole 8-element groups (common.h)
     snprintf(g_err, sizeof(g_err), "layernorm: unsupported H=%d", H);
     return 1;
   }
@@ -336,7 +338,7 @@ __global__ __launch_bounds__(256) void layernorm_splitk_kernel(const float* slab
 int launch_layernorm_splitk(int prec, const SplitkPending& sk, const float* bias, const float* resid, int ldr, const float* gamma,
                             const float* beta, float eps, int M, int H, void* y_act, float* y_f32, hipStream_t st) {
   if (M <= 0) return 0;
-  if (H % 4 || H > LN_MAXV * 256 || sk.nslab <= 0 || !sk.slabs || sk.ld % 4 || (resid && ldr % 4) || (prec != PREC_F16X3 && prec != PREC_F32)) {
+  if (H <= 0 || H % 4 || H > LN_MAXV * 256 || (prec == PREC_F16X3 && y_act && H % 8) || sk.nslab <= 0 || !sk.slabs || sk.ld % 4 || (resid && ldr % 4) || (prec != PREC_F16X3 && prec != PREC_F32)) {
     snprintf(g_err, sizeof(g_err), "layernorm_splitk: unsupported shape / precision (H=%d, slabs=%d)", H, sk.nslab);
     return 1;
   }
@@ -391,6 +393,11 @@ int launch_bert_embed(int prec, const int* ids, int B, int T_, int H, const floa
                       hipStream_t st) {
   const int M = B * T_;
   if (M <= 0) return 0;
+  // a lane holds LN_MAXV float4: wider rows would keep their tail unwritten; split rows are whole 8-element groups
+  if (H <= 0 || H % 4 || H > LN_MAXV * 256 || (prec == PREC_F16X3 && y_act && H % 8)) {
+    snprintf(g_err, sizeof(g_err), "bert_embed: unsupported H=%d", H);
+    return 1;
+  }
   dim3 grid(cdiv(M, 4)), block(256);
   if (prec == PREC_BF16)
     hipLaunchKernelGGL(bert_embed_kernel<bf16_t>, grid, block, 0, st, ids, M, T_, H, word, pos, type0, gamma, beta, eps,
@@ -464,7 +471,11 @@ __global__ __launch_bounds__(256) void clip_embed_kernel(const int* ids, int ids
 int launch_clip_embed(const int* ids, int ids_stride, const int* seg_src, const int* seg_pos0, const int* own_off,
                       const int* own_len, int n_seg, int max_len, int H, const float* tok, const float* pos, float* x,
                       hipStream_t st, int x16, float* stat, float eps) {
-  if (n_seg <= 0) return 0;
+  if (n_seg <= 0 || max_len <= 0) return 0;
+  if (H <= 0 || H % 4 || (x16 && H > LN_MAXV * 256)) {  // float4 columns; the 2-byte path keeps LN_MAXV float4 per lane
+    snprintf(g_err, sizeof(g_err), "clip_embed: unsupported H=%d (x16=%d)", H, x16);
+    return 1;
+  }
   dim3 grid(cdiv((long)n_seg * max_len, 4)), block(256);
   hipLaunchKernelGGL(clip_embed_kernel, grid, block, 0, st, ids, ids_stride, seg_src, seg_pos0, own_off, own_len, n_seg,
                      max_len, H, tok, pos, x, x16, stat, eps);
@@ -491,6 +502,8 @@ __global__ void im2col_kernel(const float* pix, int B, int S, int p, T* out) {
 }
 
 int launch_im2col(int prec, const float* pixels, int B, int S, int p, void* out, hipStream_t st) {
+  if (B <= 0 || S <= 0) return 0;
+  if (p <= 0 || S % p) { snprintf(g_err, sizeof(g_err), "im2col: patch %d does not tile a %d-pixel side", p, S); return 1; }
   const long total = (long)B * (S / p) * (S / p) * 3 * p * p;
   dim3 grid((unsigned)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192)), block(256);
   if (prec == PREC_BF16)
@@ -521,6 +534,7 @@ __global__ void vision_assemble_kernel(const float* patch_out, int B, int P, int
 int launch_vision_assemble(const float* patch_out, int B, int P, int H, const float* cls, const float* pos, float* x,
                            hipStream_t st) {
   const long total = (long)B * (P + 1) * H;
+  if (B <= 0 || P < 0 || H <= 0) return 0;
   dim3 grid((unsigned)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192)), block(256);
   hipLaunchKernelGGL(vision_assemble_kernel, grid, block, 0, st, patch_out, B, P, H, cls, pos, x);
   CZC_HIP_CHECK(hipGetLastError());
@@ -586,7 +600,8 @@ __global__ void gather_rows_bytes_kernel(const unsigned char* src, const int* id
 }
 
 int launch_gather_rows_bytes(const void* src, const int* idx, int M, int row_bytes, void* dst, hipStream_t st) {
-  if (M <= 0) return 0;
+  if (M <= 0 || row_bytes <= 0) return 0;
+  if (row_bytes % 16) { snprintf(g_err, sizeof(g_err), "gather_rows_bytes: rows of %d bytes are not whole 16-byte vectors", row_bytes); return 1; }
   hipLaunchKernelGGL(gather_rows_bytes_kernel, dim3(cdiv(M, 4)), dim3(256), 0, st, (const unsigned char*)src, idx, M,
                      row_bytes, (unsigned char*)dst);
   CZC_HIP_CHECK(hipGetLastError());
@@ -620,7 +635,8 @@ int launch_gather_row_draw(const RowDraw* src, const int* idx, int n, RowDraw* d
 }
 
 int launch_gather_rows_f32(const float* src, const int* idx, int M, int H, float* dst, hipStream_t st) {
-  if (M <= 0) return 0;
+  if (M <= 0 || H <= 0) return 0;
+  if (H % 4) { snprintf(g_err, sizeof(g_err), "gather_rows_f32: H=%d is not a multiple of 4 (launch_gather_rows_w32 takes any width)", H); return 1; }
   hipLaunchKernelGGL(gather_rows_kernel, dim3(cdiv(M, 4)), dim3(256), 0, st, src, idx, M, H, dst);
   CZC_HIP_CHECK(hipGetLastError());
   return 0;
@@ -631,6 +647,7 @@ __global__ void make_row_index_kernel(int* idx, int B, int T_, int gen_idx) {
   if (b < B) idx[b] = b * T_ + gen_idx;
 }
 int launch_make_row_index(int* idx, int B, int T_, int gen_idx, hipStream_t st) {
+  if (B <= 0) return 0;
   hipLaunchKernelGGL(make_row_index_kernel, dim3(cdiv(B, 256)), dim3(256), 0, st, idx, B, T_, gen_idx);
   CZC_HIP_CHECK(hipGetLastError());
   return 0;
@@ -642,6 +659,7 @@ __global__ void make_row_index_rows_kernel(int* idx, int B, int T_, const int* g
   if (b < B) idx[b] = b * T_ + gen[b];
 }
 int launch_make_row_index_rows(int* idx, int B, int T_, const int* gen, hipStream_t st) {
+  if (B <= 0) return 0;
   hipLaunchKernelGGL(make_row_index_rows_kernel, dim3(cdiv(B, 256)), dim3(256), 0, st, idx, B, T_, gen);
   CZC_HIP_CHECK(hipGetLastError());
   return 0;
@@ -652,6 +670,7 @@ __global__ void eos_index_kernel(const int* off, const int* len, int n, int* idx
   if (i < n) idx[i] = off[i] + len[i] - 1;
 }
 int launch_eos_index(const int* off, const int* len, int n, int* idx, hipStream_t st) {
+  if (n <= 0) return 0;
   hipLaunchKernelGGL(eos_index_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, off, len, n, idx);
   CZC_HIP_CHECK(hipGetLastError());
   return 0;
@@ -668,6 +687,7 @@ __global__ void l2_normalize_kernel(const float* x, int M, int D, float* y) {
   for (int c = lane; c < D; c += 64) y[(long)m * D + c] = xr[c] / nrm;
 }
 int launch_l2_normalize(const float* x, int M, int D, float* y, hipStream_t st) {
+  if (M <= 0 || D <= 0) return 0;
   hipLaunchKernelGGL(l2_normalize_kernel, dim3(cdiv(M, 4)), dim3(256), 0, st, x, M, D, y);
   CZC_HIP_CHECK(hipGetLastError());
   return 0;
@@ -681,7 +701,7 @@ __global__ void mask_positions_kernel(int* inp, int B, int T_, int gen_idx, int 
   }
 }
 int launch_mask_positions(int* inp, int B, int T_, int gen_idx, int n_mask, int mask_id, hipStream_t st) {
-  if (n_mask <= 0) return 0;
+  if (n_mask <= 0 || B <= 0) return 0;
   hipLaunchKernelGGL(mask_positions_kernel, dim3(cdiv(B * n_mask, 256)), dim3(256), 0, st, inp, B, T_, gen_idx, n_mask,
                      mask_id);
   CZC_HIP_CHECK(hipGetLastError());
@@ -698,7 +718,7 @@ __global__ void mask_positions_rows_kernel(int* inp, int B, int T_, const int* g
   }
 }
 int launch_mask_positions_rows(int* inp, int B, int T_, const int* gen, int n_mask, int mask_id, hipStream_t st) {
-  if (n_mask <= 0) return 0;
+  if (n_mask <= 0 || B <= 0) return 0;
   hipLaunchKernelGGL(mask_positions_rows_kernel, dim3(cdiv(B * n_mask, 256)), dim3(256), 0, st, inp, B, T_, gen, n_mask,
                      mask_id);
   CZC_HIP_CHECK(hipGetLastError());
@@ -710,6 +730,7 @@ __global__ void broadcast_rows_kernel(const int* row, int T_, int B, int* dst) {
   if (i < B * T_) dst[i] = row[i % T_];
 }
 int launch_broadcast_rows_i32(const int* row, int T_, int B, int* dst, hipStream_t st) {
+  if (B <= 0 || T_ <= 0) return 0;
   hipLaunchKernelGGL(broadcast_rows_kernel, dim3(cdiv(B * T_, 256)), dim3(256), 0, st, row, T_, B, dst);
   CZC_HIP_CHECK(hipGetLastError());
   return 0;

@@ -177,6 +177,21 @@ TEST_SIGNATURES = {
     "czc_test_combine_refine": (_I, [_I, _I, C.c_float, _P, _P, C.POINTER(Hyper), _P, _P, C.c_float, _P, _P, _P, _P, _P, _P]),
     "czc_test_combine_rivals": (_I, [_I, _I, _I, _P, _P, _I, _P, _P, _I, _P, C.c_float, _P, C.POINTER(Hyper), C.POINTER(Draw),
                                      C.c_uint32, _P, _P, _P, _P, _P]),
+    "czc_test_layernorm_rows": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, C.c_float, _I, _P, _P]),
+    "czc_test_layernorm_x16_rows": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, C.c_float, _P]),
+    "czc_test_layernorm_splitk": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, C.c_float, _P, _P]),
+    "czc_test_ln_finalize": (_I, [_I, _I, _I, _P, C.c_float, _P]),
+    "czc_test_bert_embed": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, C.c_float, _P, _P]),
+    "czc_test_bert_embed_ragged": (_I, [_I] * 8 + [_P] * 4 + [_I] + [_P] * 5 + [C.c_float, _P, _P]),
+    "czc_test_clip_embed": (_I, [_I] * 6 + [_P] * 5 + [_I, _I, _P, _P, _I, C.c_float, _P, _P]),
+    "czc_test_im2col": (_I, [_I, _I, _I, _I, _P, _P]),
+    "czc_test_vision_assemble": (_I, [_I, _I, _I, _P, _P, _P, _P]),
+    "czc_test_l2_normalize": (_I, [_I, _I, _P, _P]),
+    "czc_test_gather_rows": (_I, [_I, _I, _I, _I, _P, _P, _P]),
+    "czc_test_mask_positions": (_I, [_I, _I, _I, _P, _I, _I, _P, _P]),
+    "czc_test_tie_rows": (_I, [_I, _I, _I] + [_P] * 6),
+    "czc_test_memo_chain": (_I, [_I] * 10 + [_P] * 22),
+    "czc_test_memo_rows_chain": (_I, [_I] * 12 + [_P] * 33),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -163,6 +163,74 @@ int czc_test_combine_rivals(int B, int K, int D, const float* text_feat, const f
                             const czc_hyper* hp, const czc_draw* draw, uint32_t step, float* clip_ref, float* disc, float* final_score,
                             int32_t* best, int32_t* nonfinite);
 
+/* ---- the row, embedding, mover and memo kernels one by one (csrc/rowops.hip, ragged.hip, memo.hip, memo_rows.hip; numpy models in
+ * tests/rowops_ref.py and tests/memo_ref.py).  EVERY OUTPUT ARRAY holds CZC_TEST_GUARD + n + CZC_TEST_GUARD 4-byte words as above and
+ * comes back RAW: an activation-typed output of n elements is the bytes the kernel stored, in (n * element size + 3) / 4 words (bf16 /
+ * fp16: 2-byte elements; split-fp16: groups of 8 elements as 16 bytes of hi parts, then 16 bytes of lo parts; f32: the floats), so
+ * results can be compared bit for bit.  Every index a kernel follows is checked on the host first (CZC_ERR_ARG).  A launcher that
+ * refuses its shape launches nothing: the call returns CZC_TEST_REFUSED and every output holds the untouched pattern. */
+/* launch_layernorm on x [n_src, H]: row m reads row row_idx[m] (NULL: m).  mode: 1 typed output y_act, 2 fp32 output y_f32, 4 the
+ * in-place form (y_f32 is x itself; needs 2, no row_idx, n_src == M; y_f32 then returns the x buffer). */
+int czc_test_layernorm_rows(int precision, int M, int H, int n_src, const float* x, const int32_t* row_idx, const float* gamma,
+                            const float* beta, float eps, int mode, int32_t* y_act, float* y_f32);
+/* launch_layernorm_x16 on fp16(x) [n_src, H] with row_idx (H = 512 is the only width it serves) -> y_act [M, H] 2-byte elements */
+int czc_test_layernorm_x16_rows(int precision, int M, int H, int n_src, const float* x, const int32_t* row_idx, const float* gamma,
+                                const float* beta, float eps, int32_t* y_act);
+/* launch_layernorm_splitk: slabs [nslab, M, ld], bias [H] or NULL, resid [M, ldr] or NULL -> y_act, y_f32 [M, H] */
+int czc_test_layernorm_splitk(int precision, int nslab, int M, int H, int ld, const float* slabs, const float* bias, const float* resid,
+                              int ldr, const float* gamma, const float* beta, float eps, int32_t* y_act, float* y_f32);
+/* launch_ln_finalize: part [nblk, ld, 2] (sum, sum of squares per 32-column block) -> stat [M, 2] (mean, rstd) */
+int czc_test_ln_finalize(int nblk, int M, int ld, const float* part, float eps, float* stat);
+/* launch_bert_embed: ids [B, T] < V, word [V, H], pos [n_pos, H], type0 [H] -> y_act, y_f32 [B*T, H] */
+int czc_test_bert_embed(int precision, int B, int T, int H, int V, int n_pos, const int32_t* ids, const float* word, const float* pos,
+                        const float* type0, const float* gamma, const float* beta, float eps, int32_t* y_act, float* y_f32);
+/* launch_bert_embed_ragged: ids [n_id_rows, ids_stride], run [n] or NULL, row_off [n + 1], row_len [n] -> y_act, y_f32 [n_out_rows, H] */
+int czc_test_bert_embed_ragged(int precision, int n, int n_id_rows, int ids_stride, int max_T, int H, int V, int n_pos, const int32_t* ids,
+                               const int32_t* run, const int32_t* row_off, const int32_t* row_len, int n_out_rows, const float* word,
+                               const float* pos, const float* type0, const float* gamma, const float* beta, float eps, int32_t* y_act,
+                               float* y_f32);
+/* launch_clip_embed on a host-given segment plan; mode 0 fp32 rows, 1 fp16 rows, 2 fp16 rows + stat [n_out_rows, 2] (mean, rstd of the
+ * stored row) -> x_out [n_out_rows, H] (4- or 2-byte elements) */
+int czc_test_clip_embed(int mode, int n_seg, int max_len, int H, int n_id_rows, int ids_stride, const int32_t* ids, const int32_t* seg_src,
+                        const int32_t* seg_pos0, const int32_t* own_off, const int32_t* own_len, int V, int n_pos, const float* tok,
+                        const float* pos, int n_out_rows, float eps, int32_t* x_out, float* stat);
+/* launch_im2col: pixels [B, 3, S, S] -> out [B * (S/p)^2, 3*p*p] typed */
+int czc_test_im2col(int precision, int B, int S, int p, const float* pixels, int32_t* out);
+/* launch_vision_assemble: patch_out [B*P, H], cls [H], pos [P + 1, H] -> x [B, P + 1, H] */
+int czc_test_vision_assemble(int B, int P, int H, const float* patch_out, const float* cls, const float* pos, float* x);
+/* launch_l2_normalize: x [M, D] -> y [M, D] */
+int czc_test_l2_normalize(int M, int D, const float* x, float* y);
+/* dst[m] = src[idx[m]]; kind 0 launch_gather_rows_f32 (W floats per row), 1 launch_gather_rows_bytes (W bytes per row, W % 4 == 0),
+ * 2 launch_gather_rows_w32 (W words per row); src n_src rows, dst M rows */
+int czc_test_gather_rows(int kind, int M, int W, int n_src, const int32_t* src, const int32_t* idx, int32_t* dst);
+/* gen_rows NULL: launch_mask_positions at gen_idx, else launch_mask_positions_rows; inp [B, T] -> inp_out */
+int czc_test_mask_positions(int B, int T, int gen_idx, const int32_t* gen_rows, int n_mask, int mask_id, const int32_t* inp, int32_t* inp_out);
+/* launch_tie_rows: inp [R, T], col, grp_of_row [R], grp_off [G + 1], grp_rows [grp_off[G]] -> inp_out */
+int czc_test_tie_rows(int R, int T, int G, const int32_t* inp, const int32_t* col, const int32_t* grp_of_row, const int32_t* grp_off,
+                      const int32_t* grp_rows, int32_t* inp_out);
+/* The image memo for one sub-step, chained as the engine chains it: launch_memo_check; with stages != 0 and n = tot[0] read back:
+ * launch_memo_fill when n < B; when n > 0 launch_memo_gather (use_list: the compact batch of the listed images, else the whole batch in
+ * place), the step (compact row i takes new_rows / new_cos / new_max of its image), launch_memo_scatter.  record 0: no key and no entry
+ * is written.  In: inp, key, new_rows, ent_rows [B, T]; img_max [2, B]; img_n [B, D]; new_cos, new_max, ent_cos, ent_max, bcos_in [B].
+ * Out: hit, list [B]; tot [4]; key_out, inp_out, ent_rows_out, inp_c [B, T]; bcos_out, ent_cos_out, ent_max_out [B]; img_c [B, D]. */
+int czc_test_memo_chain(int B, int T, int D, int gen_idx, int n_mask, int mask_id, int n_sub, int stages, int use_list, int record,
+                        const int32_t* inp, const int32_t* key, const int32_t* img_max, const float* img_n, const int32_t* new_rows,
+                        const float* new_cos, const int32_t* new_max, const int32_t* ent_rows, const float* ent_cos, const int32_t* ent_max,
+                        const float* bcos_in, int32_t* hit, int32_t* list, int32_t* tot, int32_t* key_out, int32_t* inp_out, float* bcos_out,
+                        int32_t* ent_rows_out, float* ent_cos_out, int32_t* ent_max_out, int32_t* inp_c, float* img_c);
+/* The rows memo for sub-step j of a group, chained likewise: launch_memo_rows_check; with stages != 0: launch_memo_rows_fill when n < R;
+ * when n > 0 launch_memo_rows_gather (use_list: compact batch, else all rows in place and recording only), the step,
+ * launch_memo_rows_scatter.  Table in / out: valid, sig [L, R]; key [L, R, T]; rows [L, 2, R, T]; cos, imax [L, 2, R].  col0, col1 (NULL:
+ * one-step group), col, dot [R]; tau NULL or [R].  Out: hit, list, col_c, dot_c, bcos_out [R]; cnt [(R + 255) / 256]; tot [4]; inp_out,
+ * inp_c [R, T]; img_c [R, D]. */
+int czc_test_memo_rows_chain(int R, int T, int L, int seed_len, int D, int n_mask0, int n_sub, int mask_id, int j, int stages, int use_list,
+                             int record, const int32_t* inp, const int32_t* col0, const int32_t* col1, const float* tau, const int32_t* col,
+                             const int32_t* dot, const float* img_n, const int32_t* new_rows, const float* new_cos, const int32_t* new_max,
+                             const float* bcos_in, const int32_t* valid, const int32_t* sig, const int32_t* key, const int32_t* rows,
+                             const float* cos, const int32_t* imax, int32_t* valid_out, int32_t* sig_out, int32_t* key_out, int32_t* rows_out,
+                             float* cos_out, int32_t* imax_out, int32_t* hit, int32_t* cnt, int32_t* list, int32_t* tot, int32_t* inp_out,
+                             float* bcos_out, int32_t* inp_c, float* img_c, int32_t* col_c, int32_t* dot_c);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

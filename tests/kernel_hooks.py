@@ -314,3 +314,231 @@ def combine_refine(cos_in, probs, logit_scale, hyper, kind, rcos, guard):
                                              g.buf("best", B), g.buf("best_cos", B, np.float32), g.buf("nonfinite", 8)),
                  None, "czc_test_combine_refine")
     return g.done()
+
+
+# ---- the row, embedding, mover and memo kernels one by one (czc_test_layernorm_rows .. czc_test_memo_rows_chain) --------------------
+# Outputs come back raw (include/conzic_hip_test.h): Stored decodes the bytes of an activation-typed buffer.
+REFUSED = PLAN_REFUSED
+
+
+def act_words(prec, n):
+    return (int(n) * (2 if prec in (0, 4) else 4) + 3) // 4
+
+
+class Stored:
+    """n elements of precision `prec` as the kernel stored them: .bits (bf16 / fp16: uint16 patterns; f32: uint32; split: (hi, lo)
+    uint16 patterns) and .f32 (their exact value in float32; split: float32(hi) + float32(lo), the kernels' own read)."""
+
+    def __init__(self, prec, words, n):
+        w = np.ascontiguousarray(words)
+        if prec == 1:
+            self.bits = w.view(np.uint32)[:n].copy()
+            self.f32 = self.bits.view(np.float32)
+        elif prec == 0:
+            self.bits = w.view(np.uint16)[:n].copy()
+            self.f32 = (self.bits.astype(np.uint32) << 16).view(np.float32)
+        elif prec == 4:
+            self.bits = w.view(np.uint16)[:n].copy()
+            self.f32 = self.bits.view(np.float16).astype(np.float32)
+        else:
+            assert n % 8 == 0, "split rows are whole groups of 8 elements"
+            g = w.view(np.uint16)[:2 * n].reshape(-1, 16)
+            hi, lo = g[:, :8].reshape(-1).copy(), g[:, 8:].reshape(-1).copy()
+            self.bits = (hi, lo)
+            self.f32 = hi.view(np.float16).astype(np.float32) + lo.view(np.float16).astype(np.float32)
+
+
+def _f32(a):
+    return np.ascontiguousarray(a, np.float32)
+
+
+def _i32(a):
+    return None if a is None else np.ascontiguousarray(a, np.int32)
+
+
+def _call(name, *args):
+    """-> refused (the launcher returned its refusal status and launched nothing); any other non-zero status raises"""
+    rc = getattr(native.load_test(), name)(*args)
+    if rc != REFUSED:
+        native.check(rc, None, name)
+    return rc == REFUSED
+
+
+def layernorm_rows(prec, x, gamma, beta, eps, row_idx=None, M=None, mode=3):
+    """-> (refused, Guarded(y_act raw words, y_f32 [M*H])); mode 1 typed, 2 fp32, 4 in place (y_f32 = the x buffer)"""
+    x = _f32(x)
+    n_src, H = x.shape
+    ri = _i32(row_idx)
+    M = (ri.size if ri is not None else n_src) if M is None else M
+    g = Guarded()
+    ref = _call("czc_test_layernorm_rows", prec, M, H, n_src, x.ctypes.data, _ptr(ri), _f32(gamma).ctypes.data, _f32(beta).ctypes.data,
+                float(eps), int(mode), g.buf("y_act", act_words(prec, M * H)), g.buf("y_f32", M * H, np.float32))
+    return ref, g.done()
+
+
+def layernorm_x16_rows(prec, x, gamma, beta, eps, row_idx=None):
+    x = _f32(x)
+    n_src, H = x.shape
+    ri = _i32(row_idx)
+    M = ri.size if ri is not None else n_src
+    g = Guarded()
+    ref = _call("czc_test_layernorm_x16_rows", prec, M, H, n_src, x.ctypes.data, _ptr(ri), _f32(gamma).ctypes.data, _f32(beta).ctypes.data,
+                float(eps), g.buf("y_act", M * H // 2))
+    return ref, g.done()
+
+
+def layernorm_splitk(prec, slabs, H, bias, resid, gamma, beta, eps):
+    """slabs [nslab, M, ld]; resid [M, ldr] or None"""
+    s = _f32(slabs)
+    nslab, M, ld = s.shape
+    b = None if bias is None else _f32(bias)
+    r = None if resid is None else _f32(resid)
+    g = Guarded()
+    ref = _call("czc_test_layernorm_splitk", prec, nslab, M, H, ld, s.ctypes.data, _ptr(b), _ptr(r), 0 if r is None else r.shape[1],
+                _f32(gamma).ctypes.data, _f32(beta).ctypes.data, float(eps), g.buf("y_act", act_words(prec, M * H)),
+                g.buf("y_f32", M * H, np.float32))
+    return ref, g.done()
+
+
+def ln_finalize(part, M, eps):
+    """part [nblk, ld, 2] -> Guarded(stat [2*M])"""
+    p = _f32(part)
+    nblk, ld, _ = p.shape
+    g = Guarded()
+    ref = _call("czc_test_ln_finalize", nblk, M, ld, p.ctypes.data, float(eps), g.buf("stat", 2 * M, np.float32))
+    return ref, g.done()
+
+
+def bert_embed(prec, ids, word, pos, type0, gamma, beta, eps):
+    ids = _i32(ids)
+    B, T = ids.shape
+    word, pos = _f32(word), _f32(pos)
+    V, H = word.shape
+    g = Guarded()
+    ref = _call("czc_test_bert_embed", prec, B, T, H, V, pos.shape[0], ids.ctypes.data, word.ctypes.data, pos.ctypes.data,
+                _f32(type0).ctypes.data, _f32(gamma).ctypes.data, _f32(beta).ctypes.data, float(eps),
+                g.buf("y_act", act_words(prec, B * T * H)), g.buf("y_f32", B * T * H, np.float32))
+    return ref, g.done()
+
+
+def bert_embed_ragged(prec, ids, run, row_off, row_len, max_T, n_out_rows, word, pos, type0, gamma, beta, eps):
+    ids = _i32(ids)
+    n_id_rows, stride = ids.shape
+    rn, ro, rl = _i32(run), _i32(row_off), _i32(row_len)
+    word, pos = _f32(word), _f32(pos)
+    V, H = word.shape
+    g = Guarded()
+    ref = _call("czc_test_bert_embed_ragged", prec, rl.size, n_id_rows, stride, int(max_T), H, V, pos.shape[0], ids.ctypes.data, _ptr(rn),
+                ro.ctypes.data, rl.ctypes.data, int(n_out_rows), word.ctypes.data, pos.ctypes.data, _f32(type0).ctypes.data,
+                _f32(gamma).ctypes.data, _f32(beta).ctypes.data, float(eps), g.buf("y_act", act_words(prec, n_out_rows * H)),
+                g.buf("y_f32", n_out_rows * H, np.float32))
+    return ref, g.done()
+
+
+def clip_embed(mode, ids, seg_src, seg_pos0, own_off, own_len, max_len, n_out_rows, tok, pos, eps=0.0):
+    ids = _i32(ids)
+    n_id_rows, stride = ids.shape
+    ss, sp, oo, ol = _i32(seg_src), _i32(seg_pos0), _i32(own_off), _i32(own_len)
+    tok, pos = _f32(tok), _f32(pos)
+    V, H = tok.shape
+    g = Guarded()
+    ref = _call("czc_test_clip_embed", int(mode), ol.size, int(max_len), H, n_id_rows, stride, ids.ctypes.data, ss.ctypes.data, sp.ctypes.data,
+                oo.ctypes.data, ol.ctypes.data, V, pos.shape[0], tok.ctypes.data, pos.ctypes.data, int(n_out_rows), float(eps),
+                g.buf("x", act_words(4 if mode else 1, n_out_rows * H)), g.buf("stat", 2 * n_out_rows, np.float32))
+    return ref, g.done()
+
+
+def im2col(prec, pix, p):
+    pix = _f32(pix)
+    B, _, S, _ = pix.shape
+    n = B * (S // p) ** 2 * 3 * p * p
+    g = Guarded()
+    ref = _call("czc_test_im2col", prec, B, S, int(p), pix.ctypes.data, g.buf("out", act_words(prec, n)))
+    return ref, g.done()
+
+
+def vision_assemble(patch_out, cls, pos):
+    po, pos = _f32(patch_out), _f32(pos)
+    B, P, H = po.shape
+    g = Guarded()
+    ref = _call("czc_test_vision_assemble", B, P, H, po.ctypes.data, _f32(cls).ctypes.data, pos.ctypes.data, g.buf("x", B * (P + 1) * H, np.float32))
+    return ref, g.done()
+
+
+def l2_normalize(x):
+    x = _f32(x)
+    M, D = x.shape
+    g = Guarded()
+    ref = _call("czc_test_l2_normalize", M, D, x.ctypes.data, g.buf("y", M * D, np.float32))
+    return ref, g.done()
+
+
+def gather_rows(kind, src, idx, W):
+    """kind 0 f32 rows of W floats, 1 rows of W bytes, 2 rows of W words; src [n_src, words per row] uint32"""
+    s = np.ascontiguousarray(src, np.uint32)
+    ix = _i32(idx)
+    rw = W // 4 if kind == 1 else W
+    assert s.shape[1] == rw
+    g = Guarded()
+    ref = _call("czc_test_gather_rows", int(kind), ix.size, int(W), s.shape[0], s.ctypes.data, ix.ctypes.data, g.buf("dst", ix.size * rw))
+    return ref, g.done()
+
+
+def mask_positions(inp, gen, n_mask, mask_id):
+    """gen: an int (launch_mask_positions) or an array [B] (launch_mask_positions_rows)"""
+    inp = _i32(inp)
+    B, T = inp.shape
+    rows = None if np.isscalar(gen) else _i32(gen)
+    g = Guarded()
+    ref = _call("czc_test_mask_positions", B, T, int(gen) if rows is None else 0, _ptr(rows), int(n_mask), int(mask_id), inp.ctypes.data,
+                g.buf("inp", B * T))
+    return ref, g.done()
+
+
+def tie_rows(inp, col, grp_of_row, grp_off, grp_rows):
+    inp = _i32(inp)
+    R, T = inp.shape
+    c, gr, go, rows = _i32(col), _i32(grp_of_row), _i32(grp_off), _i32(grp_rows)
+    g = Guarded()
+    ref = _call("czc_test_tie_rows", R, T, go.size - 1, inp.ctypes.data, c.ctypes.data, gr.ctypes.data, go.ctypes.data, rows.ctypes.data,
+                g.buf("inp", R * T))
+    return ref, g.done()
+
+
+def memo_chain(st, gen_idx, n_mask, mask_id, n_sub, stages=1, use_list=1, record=1):
+    """st: the arrays of tests/memo_ref.py MemoState (inp, key, img_max, img_n, new_rows, new_cos, new_max, ent_rows, ent_cos, ent_max,
+    bcos) -> Guarded of every buffer the chain may write"""
+    B, T = st["inp"].shape
+    D = st["img_n"].shape[1]
+    i = {k: _i32(st[k]) for k in ("inp", "key", "img_max", "new_rows", "new_max", "ent_rows", "ent_max")}
+    f = {k: _f32(st[k]) for k in ("img_n", "new_cos", "ent_cos", "bcos")}
+    g = Guarded()
+    ref = _call("czc_test_memo_chain", B, T, D, int(gen_idx), int(n_mask), int(mask_id), int(n_sub), int(stages), int(use_list), int(record),
+                i["inp"].ctypes.data, i["key"].ctypes.data, i["img_max"].ctypes.data, f["img_n"].ctypes.data, i["new_rows"].ctypes.data,
+                f["new_cos"].ctypes.data, i["new_max"].ctypes.data, i["ent_rows"].ctypes.data, f["ent_cos"].ctypes.data,
+                i["ent_max"].ctypes.data, f["bcos"].ctypes.data,
+                g.buf("hit", B), g.buf("list", B), g.buf("tot", 4), g.buf("key", B * T), g.buf("inp", B * T), g.buf("bcos", B, np.float32),
+                g.buf("ent_rows", B * T), g.buf("ent_cos", B, np.float32), g.buf("ent_max", B), g.buf("inp_c", B * T),
+                g.buf("img_c", B * D, np.float32))
+    return ref, g.done()
+
+
+def memo_rows_chain(st, L, seed_len, n_mask0, n_sub, mask_id, j=0, stages=1, use_list=1, record=1):
+    """st: the arrays of tests/memo_ref.py (inp, col0, col1 | None, tau | None, col, dot, img_n, new_rows, new_cos, new_max, bcos and the
+    table valid, sig, key, rows, cos, imax)"""
+    R, T = st["inp"].shape
+    D = st["img_n"].shape[1]
+    i = {k: _i32(st[k]) for k in ("inp", "col0", "col1", "col", "dot", "new_rows", "new_max", "valid", "sig", "key", "rows", "imax")}
+    f = {k: (None if st[k] is None else _f32(st[k])) for k in ("tau", "img_n", "new_cos", "bcos", "cos")}
+    nb = (R + 255) // 256
+    g = Guarded()
+    ref = _call("czc_test_memo_rows_chain", R, T, int(L), int(seed_len), D, int(n_mask0), int(n_sub), int(mask_id), int(j), int(stages),
+                int(use_list), int(record), i["inp"].ctypes.data, i["col0"].ctypes.data, _ptr(i["col1"]), _ptr(f["tau"]), i["col"].ctypes.data,
+                i["dot"].ctypes.data, f["img_n"].ctypes.data, i["new_rows"].ctypes.data, f["new_cos"].ctypes.data, i["new_max"].ctypes.data,
+                f["bcos"].ctypes.data, i["valid"].ctypes.data, i["sig"].ctypes.data, i["key"].ctypes.data, i["rows"].ctypes.data,
+                f["cos"].ctypes.data, i["imax"].ctypes.data,
+                g.buf("valid", L * R), g.buf("sig", L * R), g.buf("key", L * R * T), g.buf("rows", L * 2 * R * T),
+                g.buf("cos", L * 2 * R, np.float32), g.buf("imax", L * 2 * R), g.buf("hit", R), g.buf("cnt", nb), g.buf("list", R),
+                g.buf("tot", 4), g.buf("inp", R * T), g.buf("bcos", R, np.float32), g.buf("inp_c", R * T), g.buf("img_c", R * D, np.float32),
+                g.buf("col_c", R), g.buf("dot_c", R))
+    return ref, g.done()

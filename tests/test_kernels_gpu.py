@@ -13,6 +13,7 @@ from conzic_amd import harness, native, synth
 from conzic_amd.bridge import tables_from_tokenizers
 from conzic_amd.text import tokenizers_from_vocab
 from attn_ref import seq_ref
+import rowops_ref as RR
 from goldutil import GOLD
 
 pytestmark = pytest.mark.gpu
@@ -82,6 +83,9 @@ def test_layernorm(prec, H):
         ref = torch.nn.functional.layer_norm(torch.from_numpy(x), (H,), torch.from_numpy(g), torch.from_numpy(b), eps).numpy()
         tol = 3e-6 * 10 if prec == F32 else 2e-2
         assert np.abs(y - ref).max() < tol
+        # and inside the forward-error bound derived in tests/rowops_ref.py (fp64 reference, the row's own data, the storage rounding)
+        y64, bound = RR.layernorm_bound(x, g, b, eps, prec=prec)
+        assert (np.abs(y - y64) <= bound).all(), float((np.abs(y - y64) / bound).max())
 
 
 _attn_ref = seq_ref   # the per-sequence formula (fp32 here), tests/attn_ref.py

@@ -1423,4 +1423,54 @@ int czc_test_memo_rows_chain(int R, int T, int L, int seed_len, int D, int n_mas
   return launch_status(rc);
 }
 
+// ---- caption fluency (fluency.hip) ------------------------------------------------------------------------------------------
+int czc_test_logprob(int N, int V, const float* logits, const int32_t* target, float temperature, float* logp, int32_t* rank,
+                     int32_t* nonfinite) {
+  const char* who = "logprob";
+  T_ARG(N >= 1 && V >= 1 && (long)N * V < (1l << 28) && logits && target && logp && rank && nonfinite && all_in(target, N, 0, V), who);
+  DevPool pool;
+  float* dl = (float*)pool.up(logits, (size_t)N * V * 4); T_PTR(dl);
+  int* dt = (int*)pool.up(target, (size_t)N * 4); T_PTR(dt);
+  float* dp = (float*)pool.alloc((size_t)N * 4); T_PTR(dp);
+  int* dr = (int*)pool.alloc((size_t)N * 4); T_PTR(dr);
+  int* df = (int*)pool.alloc(4); T_PTR(df);
+  T_HIP(hipMemset(df, 0, 4));
+  const int rc = HK().logprob_target(dl, N, V, dt, temperature, nullptr, dp, dr, df, nullptr);
+  T_HIP(hipDeviceSynchronize());
+  if (rc) return launch_status(rc);
+  T_HIP(hipMemcpy(logp, dp, (size_t)N * 4, hipMemcpyDeviceToHost));
+  T_HIP(hipMemcpy(rank, dr, (size_t)N * 4, hipMemcpyDeviceToHost));
+  T_HIP(hipMemcpy(nonfinite, df, 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int czc_test_expand_mask(int R, int T, int seed_len, int mask_id, const int32_t* rows, const int32_t* len_of_row, int32_t* ids_out,
+                         int32_t* target, int32_t* gen_rows, int32_t* n_seq) {
+  const char* who = "expand_mask";
+  T_ARG(R >= 1 && R <= (1 << 14) && T >= 1 && T <= 4096 && seed_len >= 0 && T - seed_len - 1 >= 1 && rows && ids_out && target && gen_rows && n_seq, who);
+  const int Lmax = T - seed_len - 1;
+  T_ARG(!len_of_row || all_in(len_of_row, R, 1, Lmax + 1), who);
+  std::vector<int32_t> ros((size_t)R * Lmax), col((size_t)R * Lmax);
+  const int N = HK().fluency_expand_tables(R, seed_len, Lmax, len_of_row, ros.data(), col.data());
+  T_ARG(N >= 1 && N <= R * Lmax && all_in(ros.data(), N, 0, R) && all_in(col.data(), N, 0, T), who);  // what the kernel follows
+  DevPool pool;
+  int* drows = (int*)pool.up(rows, (size_t)R * T * 4); T_PTR(drows);
+  int* dros = (int*)pool.up(ros.data(), (size_t)N * 4); T_PTR(dros);
+  int* dcol = (int*)pool.up(col.data(), (size_t)N * 4); T_PTR(dcol);
+  int* dids = (int*)pool.alloc((size_t)N * T * 4); T_PTR(dids);
+  int* dtgt = (int*)pool.alloc((size_t)N * 4); T_PTR(dtgt);
+  int* dgen = (int*)pool.alloc((size_t)N * 4); T_PTR(dgen);
+  T_HIP(hipMemset(dids, 0x5a, (size_t)N * T * 4));
+  T_HIP(hipMemset(dtgt, 0x5a, (size_t)N * 4));
+  T_HIP(hipMemset(dgen, 0x5a, (size_t)N * 4));
+  const int rc = HK().expand_mask_rows(drows, T, dros, dcol, N, mask_id, dids, dtgt, dgen, nullptr);
+  T_HIP(hipDeviceSynchronize());
+  if (rc) return launch_status(rc);
+  T_HIP(hipMemcpy(ids_out, dids, (size_t)N * T * 4, hipMemcpyDeviceToHost));
+  T_HIP(hipMemcpy(target, dtgt, (size_t)N * 4, hipMemcpyDeviceToHost));
+  T_HIP(hipMemcpy(gen_rows, dgen, (size_t)N * 4, hipMemcpyDeviceToHost));
+  *n_seq = N;
+  return 0;
+}
+
 }  // extern "C"

@@ -188,6 +188,7 @@ struct czc_engine {
   // has none); option "index_groups": work-groups of the scan, 0 = the launcher's choice
   split_t* d_index = nullptr; int64_t index_n = 0;
   int index_groups = 0;
+  int fluency_chunk = 1024;  // czc_fluency_rows: expanded sequences per BERT forward (option "fluency_chunk", 1..16384)
 };
 
 namespace {
@@ -1556,7 +1557,7 @@ int tie_score(czc_engine* e, const TiePlan& tp, const int* d_inp, int R, int T, 
 // =================================================================================================
 extern "C" {
 
-int czc_version(void) { return 106; }
+int czc_version(void) { return 107; }
 
 const char* czc_last_error(const czc_engine* e) { return e ? e->err : czc::g_err; }
 
@@ -1647,7 +1648,7 @@ int czc_replicate(czc_engine* p, czc_engine** out) {
   e->refine = p->refine; e->refine_theta_x = p->refine_theta_x; e->refine_samples = p->refine_samples; e->refine_samples_step = p->refine_samples_step;
   e->refine_guard_dev = p->refine_guard_dev; e->refine_gate_delta = p->refine_gate_delta; e->refine_theta_gen = p->refine_theta_gen;
   e->refine_rows16 = p->refine_rows16; e->refine_rows16_factor = p->refine_rows16_factor;
-  e->memo = p->memo; e->memo_rows = p->memo_rows;
+  e->memo = p->memo; e->memo_rows = p->memo_rows; e->fluency_chunk = p->fluency_chunk;
   e->w = p->w; e->bert = p->bert; e->ctext = p->ctext; e->cvis = p->cvis; e->ctext_x = p->ctext_x;
   e->mlm_dense_w = p->mlm_dense_w; e->decoder_w = p->decoder_w; e->tproj_w = p->tproj_w; e->vproj_w = p->vproj_w;
   e->patch_w = p->patch_w; e->tproj_wx = p->tproj_wx;
@@ -2783,6 +2784,116 @@ static int score_rows_impl(czc_engine* e, const char* who, const int32_t* rows, 
   return CZC_OK;
 }
 
+// BERT's pseudo-log-likelihood of finished rows (fluency.hip).  The N = sum L_r masked sequences go through bert_forward and
+// mlm_head in chunks of at most fluency_chunk, as the sequences of a rows step do (one kept row each, ragged where the rows
+// differ in length); the tables of the whole call are uploaded once and nothing is read back before the end.
+int czc_fluency_rows(czc_engine* e, const int32_t* rows, int R, int T, int seed_len, const int32_t* len_of_row_host, float temperature,
+                     float* out_logp, int32_t* out_rank, float* out_pll) {
+  if (!e || !rows) return CZC_ERR_ARG;
+  E_HIP(hipSetDevice(e->dev));
+  e->err[0] = 0;
+  if (R < 1 || R > CZC_MAX_ROWS || T < 1 || T > CZC_MAX_BERT_LEN || seed_len < 0 || T - seed_len - 1 < 1)
+    return fail(e, CZC_ERR_ARG, "fluency_rows: R outside [1, CZC_MAX_ROWS], T outside [1, CZC_MAX_BERT_LEN], seed_len < 0 or T - seed_len - 1 < 1%s");
+  if (!out_logp && !out_rank && !out_pll) return fail(e, CZC_ERR_ARG, "fluency_rows: every output is NULL%s");
+  if (!std::isfinite(temperature) || !(temperature > 0.f)) return fail(e, CZC_ERR_ARG, "fluency_rows: temperature must be finite and > 0%s");
+  const czc_config& c = e->cfg;
+  const int Lmax = T - seed_len - 1, V = c.bert_vocab;
+  bool dense = true;
+  if (len_of_row_host)
+    for (int r = 0; r < R; ++r) {
+      if (len_of_row_host[r] < 1 || len_of_row_host[r] > Lmax) return fail(e, CZC_ERR_ARG, "fluency_rows: len_of_row outside [1, T - seed_len - 1]%s");
+      dense = dense && len_of_row_host[r] == Lmax;
+    }
+  if (!e->finalized) return fail(e, CZC_ERR_STATE, "weights not finalized%s");
+  if (c.bert_layers <= 0) return fail(e, CZC_ERR_STATE, "this engine was created without the BERT tower%s");
+  const size_t n_ids = (size_t)R * T;
+  std::vector<int32_t> host;
+  const int32_t* h = rows;
+  if (is_device_ptr(rows)) {  // the ids are checked on the host either way: they index the embedding table
+    host.resize(n_ids);
+    E_HIP(hipMemcpyAsync(host.data(), rows, n_ids * 4, hipMemcpyDeviceToHost, e->st));
+    E_HIP(hipStreamSynchronize(e->st));
+    h = host.data();
+  }
+  for (int r = 0; r < R; ++r) {
+    const int Tr = len_of_row_host ? seed_len + len_of_row_host[r] + 1 : T;
+    for (int t = 0; t < Tr; ++t)
+      if (h[(size_t)r * T + t] < 0 || h[(size_t)r * T + t] >= V) return fail(e, CZC_ERR_ARG, "fluency_rows: a row holds an id outside the BERT vocabulary%s");
+  }
+  // the tables of the call, one upload: [row_of_seq N][col_of_seq N][out_idx N][seq_len N][seq_off N + n_chunk][len_of_row R]
+  // (seq_off: the packed-row offsets of every chunk, each chunk's own exclusive scan starting at 0)
+  std::vector<int32_t> tab((size_t)R * Lmax * 2);
+  const int N = fluency_expand_tables(R, seed_len, Lmax, len_of_row_host, tab.data(), tab.data() + (size_t)R * Lmax);
+  const int chunk = e->fluency_chunk, n_chunk = (N + chunk - 1) / chunk;
+  {
+    std::vector<int32_t> t2((size_t)5 * N + n_chunk + R);
+    int32_t *ros = t2.data(), *cos_ = ros + N, *oidx = cos_ + N, *slen = oidx + N, *soff = slen + N, *lrow = soff + N + n_chunk;
+    memcpy(ros, tab.data(), (size_t)N * 4);
+    memcpy(cos_, tab.data() + (size_t)R * Lmax, (size_t)N * 4);
+    for (int n = 0; n < N; ++n) {
+      oidx[n] = ros[n] * Lmax + (cos_[n] - seed_len);
+      slen[n] = len_of_row_host ? seed_len + len_of_row_host[ros[n]] + 1 : T;
+    }
+    for (int k = 0; k < n_chunk; ++k) {
+      const int n0 = k * chunk, cn = std::min(chunk, N - n0);
+      int32_t* off = soff + n0 + k;
+      off[0] = 0;
+      for (int i = 0; i < cn; ++i) off[i + 1] = off[i] + slen[n0 + i];
+    }
+    for (int r = 0; r < R; ++r) lrow[r] = len_of_row_host ? len_of_row_host[r] : Lmax;
+    tab.swap(t2);
+  }
+  const int32_t *h_col = tab.data() + N, *h_slen = tab.data() + (size_t)3 * N, *h_soff = tab.data() + (size_t)4 * N;
+  int *d_tab, *d_rows, *d_ids, *d_target, *d_gen, *d_rank, *flag; float *d_logp, *d_pll;
+  E_CHECK(ensure(e, "s_nonfinite", 32, (void**)&flag));
+  E_CHECK(ensure(e, "fl_tab", tab.size() * 4, (void**)&d_tab));
+  E_CHECK(ensure(e, "fl_rows", n_ids * 4, (void**)&d_rows));
+  E_CHECK(ensure(e, "fl_ids", (size_t)std::min(chunk, N) * T * 4, (void**)&d_ids));
+  E_CHECK(ensure(e, "fl_target", (size_t)std::min(chunk, N) * 4, (void**)&d_target));
+  E_CHECK(ensure(e, "fl_gen", (size_t)std::min(chunk, N) * 4, (void**)&d_gen));
+  E_CHECK(ensure(e, "fl_logp", (size_t)R * Lmax * 4, (void**)&d_logp));
+  E_CHECK(ensure(e, "fl_rank", (size_t)R * Lmax * 4, (void**)&d_rank));
+  E_CHECK(ensure(e, "fl_pll", (size_t)R * 4, (void**)&d_pll));
+  const int *d_ros = d_tab, *d_col = d_tab + N, *d_oidx = d_tab + (size_t)2 * N, *d_slen = d_tab + (size_t)3 * N,
+            *d_soff = d_tab + (size_t)4 * N, *d_lrow = d_tab + (size_t)5 * N + n_chunk;
+  // from here on BERT's buffers are this call's: whatever the call returns, no later n_mask = 0 step re-uses a forward, and
+  // the host columns bert_forward is shown do not outlive the call
+  struct EndReuse {
+    czc_engine* e;
+    ~EndReuse() { (void)hipStreamSynchronize(e->st); e->bert_pruned_idx = PRUNED_ROWS; e->bert_pruned_rows = nullptr; }
+  } end_reuse{e};
+  E_HIP(hipMemsetAsync(flag, 0, 32, e->st));
+  E_HIP(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, e->st));
+  E_HIP(hipMemcpyAsync(d_rows, rows, n_ids * 4, hipMemcpyDefault, e->st));
+  E_HIP(hipMemsetAsync(d_logp, 0, (size_t)R * Lmax * 4, e->st));
+  E_HIP(hipMemsetAsync(d_rank, 0xff, (size_t)R * Lmax * 4, e->st));  // -1
+  const bool prune = e->bert_prune != 0;
+  for (int k = 0; k < n_chunk; ++k) {
+    const int n0 = k * chunk, cn = std::min(chunk, N - n0);
+    { ProfScope ps(e, "rowops", 0);
+      E_CHECK(launch_expand_mask_rows(d_rows, T, d_ros + n0, d_col + n0, cn, c.mask_id, d_ids, d_target, d_gen, e->st)); }
+    Ragged rag{d_soff + n0 + k, d_slen + n0, h_soff[n0 + k + cn], 0};
+    for (int i = 0; i < cn; ++i) rag.max_T = std::max(rag.max_T, h_slen[n0 + i]);
+    const Ragged* rg = dense ? nullptr : &rag;
+    E_CHECK(bert_forward(e, d_ids, cn, T, prune ? h_col[n0] : -1, prune ? d_gen : nullptr, h_col + n0, rg));
+    float* logits;
+    E_CHECK(mlm_head(e, cn, T, h_col[n0], &logits, d_gen, h_col + n0, rg));
+    { ProfScope ps(e, "topk", 0);
+      E_CHECK(launch_logprob_target(logits, cn, V, d_target, temperature, d_oidx + n0, d_logp, d_rank, flag, e->st)); }
+  }
+  if (out_pll) {
+    ProfScope ps(e, "rowops", 0);
+    E_CHECK(launch_pll_sum(d_logp, R, Lmax, d_lrow, d_pll, e->st));
+    E_HIP(hipMemcpyAsync(out_pll, d_pll, (size_t)R * 4, hipMemcpyDefault, e->st));
+  }
+  if (out_logp) E_HIP(hipMemcpyAsync(out_logp, d_logp, (size_t)R * Lmax * 4, hipMemcpyDefault, e->st));
+  if (out_rank) E_HIP(hipMemcpyAsync(out_rank, d_rank, (size_t)R * Lmax * 4, hipMemcpyDefault, e->st));
+  E_HIP(hipMemcpyAsync(e->h_totals + 9, flag, 4, hipMemcpyDeviceToHost, e->st));
+  E_HIP(hipStreamSynchronize(e->st));
+  if (e->h_totals[9]) return fail(e, CZC_ERR_OVERFLOW, "fluency_rows: non-finite log-probability (a non-finite BERT logit)%s");
+  return CZC_OK;
+}
+
 int czc_set_control_callback(czc_engine* e, czc_control_fn fn, void* user) {
   if (!e) return CZC_ERR_ARG;
   e->ctl_fn = fn;
@@ -2822,6 +2933,11 @@ int czc_set_option(czc_engine* e, const char* name, int value) {
     e->index_groups = value;
     return CZC_OK;
   }
+  if (!strcmp(name, "fluency_chunk")) {
+    if (value < 1 || value > 16384) return fail(e, CZC_ERR_ARG, "option %s: 1..16384", name);
+    e->fluency_chunk = value;
+    return CZC_OK;
+  }
   if (!strcmp(name, "refine_rows16_x1000")) { e->refine_rows16_factor = value < 1000 ? 1.f : (float)value / 1000.f; return CZC_OK; }
   return fail(e, CZC_ERR_ARG, "unknown option %s", name);
 }
@@ -2836,7 +2952,7 @@ int czc_get_option(czc_engine* e, const char* name, int* value) {
       {"refine_samples", e->refine_samples}, {"refine_samples_step", e->refine_samples_step}, {"refine_theta_x1000", (int)lrintf(e->refine_theta_x * 1000.f)},
       {"refine_theta_gen_x1000", (int)lrintf(e->refine_theta_gen * 1000.f)},
       {"refine_guard_x1e6", (int)lrintf(e->refine_guard_dev * 1e6f)}, {"refine_gate_x1e6", (int)lrintf(e->refine_gate_delta * 1e6f)},
-      {"refine_rows16", e->refine_rows16}, {"memo", e->memo}, {"memo_rows", e->memo_rows}, {"index_groups", e->index_groups}, {"refine_rows16_x1000", (int)lrintf(e->refine_rows16_factor * 1000.f)},
+      {"refine_rows16", e->refine_rows16}, {"memo", e->memo}, {"memo_rows", e->memo_rows}, {"index_groups", e->index_groups}, {"fluency_chunk", e->fluency_chunk}, {"refine_rows16_x1000", (int)lrintf(e->refine_rows16_factor * 1000.f)},
       // read-only, derived: the trip point / gate bound in force inside czc_generate (x refine_rows16_factor on fp16 rows)
       {"refine_guard_generate_x1e6", (int)lrintf(e->refine_guard_dev * f16x * 1e6f)},
       {"refine_gate_generate_x1e6", (int)lrintf(e->refine_gate_delta * f16x * 1e6f)},
@@ -3020,7 +3136,8 @@ const void* czc_internal_hooks(int abi) {
       &launch_layernorm_splitk, &launch_bert_embed, &launch_bert_embed_ragged, &launch_clip_embed, &launch_im2col, &launch_vision_assemble,
       &launch_gather_rows_f32, &launch_gather_rows_bytes, &launch_gather_rows_w32, &launch_mask_positions, &launch_mask_positions_rows,
       &launch_tie_rows, &launch_memo_check, &launch_memo_gather, &launch_memo_scatter, &launch_memo_fill, &launch_memo_rows_check,
-      &launch_memo_rows_gather, &launch_memo_rows_scatter, &launch_memo_rows_fill};
+      &launch_memo_rows_gather, &launch_memo_rows_scatter, &launch_memo_rows_fill,
+      &fluency_expand_tables, &launch_expand_mask_rows, &launch_logprob_target};
   return abi == HOOKS_ABI ? &h : nullptr;
 }
 

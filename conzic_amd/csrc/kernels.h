@@ -412,10 +412,27 @@ int index_scan_groups(int n, int D, int k, int groups);
 int launch_index_search(const split_t* index, int n, int D, const split_t* queries, int Q, int k, int G,
                         unsigned long long* part, int* out_ids, float* out_cos, hipStream_t st);
 
+// ---- caption fluency (fluency.hip; czc_fluency_rows) -------------------------------------------------------------------------
+// host: the expanded batch of R rows, one sequence per word -- sequence n masks column col_of_seq[n] = seed_len + j of row
+// row_of_seq[n], rows in order and j ascending within a row (len_of_row null: every row has Lmax words).  Returns N = sum L_r;
+// both arrays hold at least that many entries.
+int fluency_expand_tables(int R, int seed_len, int Lmax, const int32_t* len_of_row, int32_t* row_of_seq, int32_t* col_of_seq);
+// ids_out [N, T]: sequence n = row row_of_seq[n] of rows [*, T] with column col_of_seq[n] replaced by mask_id (every other
+// column as it stands); target[n] = the id that stood there; gen_rows[n] = col_of_seq[n].  All device.
+int launch_expand_mask_rows(const int* rows, int T, const int* row_of_seq, const int* col_of_seq, int N, int mask_id, int* ids_out,
+                            int* target, int* gen_rows, hipStream_t st);
+// logits [N, V] fp32, target [N] in [0, V), temperature > 0: logp[o] = log softmax(logits[n] / temperature)[target[n]] and
+// rank[o] = #{i : x_i > x_t} + #{i < target : x_i == x_t} (raw logits; the order of topk.hip), o = out_idx ? out_idx[n] : n.
+// One pass over the row.  A non-finite logp sets *nonfinite = 1.
+int launch_logprob_target(const float* logits, int N, int V, const int* target, float temperature, const int* out_idx, float* logp,
+                          int* rank, int* nonfinite, hipStream_t st);
+// pll[r] = logp[r][0] + ... + logp[r][L_r - 1] in that order (logp [R, Lmax]; len_of_row device [R] or null: L_r = Lmax)
+int launch_pll_sum(const float* logp, int R, int Lmax, const int* len_of_row, float* pll, hipStream_t st);
+
 // ---- czc_internal_hooks (declared below, private to the build): what libconzic_hip_test.so may reach inside this library -----------
 // The product library has hidden visibility; the hook library (api_test.hip) gets the launchers it wraps and the
 // process-wide kernel-family switches it flips through this table instead of through exported C++ symbols.
-constexpr int HOOKS_ABI = 0x0609;
+constexpr int HOOKS_ABI = 0x060a;
 struct Hooks {
   char* (*err_buf)();  // the calling host thread's g_err [512]
   decltype(&launch_gemm) gemm;
@@ -475,6 +492,10 @@ struct Hooks {
   decltype(&launch_memo_rows_gather) memo_rows_gather;
   decltype(&launch_memo_rows_scatter) memo_rows_scatter;
   decltype(&launch_memo_rows_fill) memo_rows_fill;
+  // caption fluency (tests/test_logprob_kernel_gpu.py, tests/test_expand_mask_gpu.py)
+  decltype(&fluency_expand_tables) fluency_expand_tables;
+  decltype(&launch_expand_mask_rows) expand_mask_rows;
+  decltype(&launch_logprob_target) logprob_target;
 };
 
 }  // namespace czc

@@ -106,7 +106,30 @@ def get_args(argv=None):
     p.add_argument("--rival_images", type=lambda v: [f.strip() for f in v.split(",") if f.strip()], default=None, metavar="a.jpg,b.jpg",
                    help="demo_cli with --distinct: images that are rivals only (not captioned); every captioned image is scored "
                         "against all of them instead of against its batch neighbours")
+    p.add_argument("--fluency", action="store_true",
+                   help="after the last sweep, log every final caption's BERT pseudo-log-likelihood (the sum over its words of "
+                        "log p(word | caption with that word masked)), mean log p, pseudo-perplexity and the word BERT ranks "
+                        "lowest; changes neither the captions nor the files; combines with --batch_samples, --sample_tau, "
+                        "--distinct and --run_type controllable")
+    p.add_argument("--pick_lambda", type=float, default=None, metavar="LAMBDA",
+                   help="implies --fluency; needs --samples_num > 1: log, per image, the \"picked caption\": the sample whose final "
+                        "caption has the largest cosine + LAMBDA x mean log p (the \"best caption\" lines stay as they are)")
     a = p.parse_args(argv)
+    if a.pick_lambda is not None:
+        if not (a.pick_lambda == a.pick_lambda) or a.pick_lambda in (float("inf"), float("-inf")):
+            p.error("--pick_lambda must be finite")
+        if a.samples_num <= 1:
+            p.error("--pick_lambda chooses among the samples of an image: it needs --samples_num > 1")
+        a.fluency = True
+    if a.fluency:
+        if a.run_type in ("infill", "retrieve"):
+            p.error(f"--fluency does not combine with --run_type {a.run_type} (the engine call scores rows of any length; the "
+                    "command-line plumbing does not yet)")
+        for flag, on in (("--sentence_lens", a.sentence_lens is not None), ("--signals", a.signals is not None),
+                         ("--block_width", a.block_width != 1)):
+            if on:
+                p.error(f"--fluency does not combine with {flag} (the engine call scores rows of any length; the command-line "
+                        "plumbing does not yet)")
     if not (a.distinct == a.distinct) or a.distinct in (float("inf"), float("-inf")):
         p.error("--distinct must be finite")
     if a.distinct:
@@ -288,6 +311,12 @@ def main(argv=None):
         return
     from conzic_amd.diversity import log_distinct
     finals = [[] for _ in img_name]   # per image: the final caption of every sample
+    fluency = [] if args.fluency else False   # --fluency: the records of every final caption (runtime._fluency_after)
+
+    def pick():
+        if args.pick_lambda is not None:
+            from conzic_amd.runtime import log_picked
+            log_picked(logger, img_name, fluency, args.pick_lambda, lm_tokenizer)
 
     def keep(generate_texts):
         last = generate_texts[-2] if len(generate_texts) > 1 else generate_texts[-1]   # (no snapshot recorded: the best entry)
@@ -318,7 +347,7 @@ def main(argv=None):
                   temperature=args.lm_temperature, max_iter=args.num_iterations, alpha=args.alpha, beta=args.beta,
                   generate_order=args.order, gamma=args.gamma, ctl_type=args.control_type,
                   style_type=args.sentiment_type, pos_type=args.pos_type, sample_tau=args.sample_tau, sample_seed=args.seed,
-                  rivals=rivals, delta=args.distinct)
+                  rivals=rivals, delta=args.distinct, fluency=fluency)
         for sample_id in ([None] if args.batch_samples else range(args.samples_num)):
             outs = caption_samples(args.samples_num if sample_id is None else 1, args.run_type, img_name, lm_model, clip, lm_tokenizer,
                                    image_instance, token_mask, logger, sample0=sample_id or 0, **kw)
@@ -326,6 +355,7 @@ def main(argv=None):
                 keep(generate_texts)
         if args.samples_num > 1:
             log_distinct(logger, img_name, finals)
+        pick()
         logger.info("total %.2fs" % (time.time() - t0))
         return finals
     for sample_id in range(args.samples_num):                                   # demo.py:83 (no reseeding)
@@ -333,6 +363,9 @@ def main(argv=None):
         kw = dict(prompt=args.prompt, batch_size=args.batch_size, max_len=args.sentence_len, top_k=args.candidate_k,
                   temperature=args.lm_temperature, max_iter=args.num_iterations, alpha=args.alpha, beta=args.beta,
                   generate_order=args.order)
+        n_rec = len(fluency) if args.fluency else 0
+        if args.fluency:
+            kw["fluency"] = fluency
         if args.run_type == 'caption':
             generate_texts, _ = generate_caption(img_name, lm_model, clip, lm_tokenizer, image_instance, token_mask, logger, **kw)
         else:
@@ -340,8 +373,11 @@ def main(argv=None):
                                                          gamma=args.gamma, ctl_type=args.control_type, style_type=args.sentiment_type,
                                                          pos_type=args.pos_type, **kw)
         keep(generate_texts)
+        for rec in (fluency[n_rec:] if args.fluency else ()):
+            rec["sample"] = sample_id   # (run_generation does not know which sample of the loop it serves)
     if args.samples_num > 1:
         log_distinct(logger, img_name, finals)
+    pick()
     logger.info("total %.2fs" % (time.time() - t0))
     return finals
 

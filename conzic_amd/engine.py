@@ -526,6 +526,29 @@ class Engine:
         self._ck(self.lib.czc_score_rows(self.h, _ptr(r), R, T, seed_len, _ptr(ln), _ptr(ior), out.ctypes.data), "czc_score_rows")
         return out
 
+    def fluency_rows(self, rows, seed_len: int, lens: Optional[Sequence[int]] = None, temperature: float = 1.0) -> dict:
+        """czc_fluency_rows: BERT's pseudo-log-likelihood of BERT-id `rows` int [R, T] (numpy, or a contiguous int32 torch tensor
+        on the host or the device; row r has lens[r] words behind seed_len prompt tokens, None: T - seed_len - 1).  Returns
+        dict(logp fp32 [R, Lmax], rank int32 [R, Lmax], pll fp32 [R]): log softmax(logits / temperature) at every word's own id
+        with that word masked, the id's rank among the vocabulary (0 = BERT's first choice), and the sum per row; the columns
+        behind a row's words hold 0.0 and -1."""
+        if hasattr(rows, "data_ptr"):
+            if str(rows.dtype) != "torch.int32" or not rows.is_contiguous():
+                raise ValueError("fluency_rows: a tensor must be contiguous int32")
+            r = rows
+        else:
+            r = np.ascontiguousarray(rows, dtype=np.int32)
+        if r.ndim != 2 or r.shape[0] < 1 or r.shape[1] < 1:
+            raise ValueError(f"fluency_rows: rows must be [R, T], got {tuple(r.shape)}")
+        R, T = int(r.shape[0]), int(r.shape[1])
+        ln = _row_vector("fluency_rows", "lens", lens, R)
+        lmax = max(T - int(seed_len) - 1, 0)   # (the C ABI refuses Lmax < 1: the buffers only have to exist)
+        logp, rank = np.empty((R, lmax), dtype=np.float32), np.empty((R, lmax), dtype=np.int32)
+        pll = np.empty((R,), dtype=np.float32)
+        self._ck(self.lib.czc_fluency_rows(self.h, _ptr(r), R, T, int(seed_len), _ptr(ln), float(temperature), logp.ctypes.data,
+                                           rank.ctypes.data, pll.ctypes.data), "czc_fluency_rows")
+        return dict(logp=logp, rank=rank, pll=pll)
+
     def generate_rows_vs(self, init_rows, lens, seed_len: int, top_k: int, positions, hypers: Sequence[native.Hyper],
                          draws: Optional[Sequence[native.Draw]], groups: Optional[Sequence[int]], rivals, deltas,
                          image_of_row: Optional[Sequence[int]] = None, n_mask: Optional[Sequence[int]] = None,
@@ -929,6 +952,12 @@ class EngineGroup:
                                                                                     n_mask=n_mask, snapshot_every=p.every, want_cos=want_cos),
                                 init_rows, positions, seed_len, lens=lens, hypers=list(hypers), draws=draws, groups=groups, rivals=rivals,
                                 deltas=deltas, image_of_row=image_of_row, snapshot_every=snapshot_every, want_cos=want_cos, images="whole")
+
+    def fluency_rows(self, rows, seed_len: int, lens=None, temperature: float = 1.0) -> dict:
+        """Engine.fluency_rows on the parent engine, WITHOUT a split over the streams: the call needs no image embeds, a
+        caption's result does not depend on its companions beyond the engine precision, and it is a scoring pass after the
+        chains have ended, not part of them."""
+        return self.engines[0].fluency_rows(rows, seed_len, lens=lens, temperature=temperature)
 
     # ---- the engine calls that apply to every member ----
     def set_option(self, name, value):

@@ -129,6 +129,7 @@ SIGNATURES = {
     "czc_generate_rows_vs": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _I, C.POINTER(Hyper), C.POINTER(Draw), _P, _I, _P,
                                   _P, _P]),
     "czc_score_rows_vs": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P]),
+    "czc_fluency_rows": (_I, [_P, _P, _I, _I, _I, _P, C.c_float, _P, _P, _P]),
     "czc_set_option": (_I, [_P, C.c_char_p, _I]),
     "czc_get_option": (_I, [_P, C.c_char_p, C.POINTER(_I)]),
     "czc_profile_enable": (_I, [_P, _I]),
@@ -192,6 +193,8 @@ TEST_SIGNATURES = {
     "czc_test_tie_rows": (_I, [_I, _I, _I] + [_P] * 6),
     "czc_test_memo_chain": (_I, [_I] * 10 + [_P] * 22),
     "czc_test_memo_rows_chain": (_I, [_I] * 12 + [_P] * 33),
+    "czc_test_logprob": (_I, [_I, _I, _P, _P, C.c_float, _P, _P, _P]),
+    "czc_test_expand_mask": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -70,16 +70,20 @@ def batched_samples(args, run_type, all_batches, own_lo, own_hi, rank, world, im
         cols = [s * nb + batch_idx for s in range(S)]   # the serial loop walks samples outside, batches inside
         sched = (positions[:, cols], n_mask, every, None if order_lists is None else [order_lists[c] for c in cols])
         imgs = [Image.open(os.path.join(img_dir, n)).convert("RGB") for n in name_batch]
+        fluency = [] if args.fluency else False   # --fluency: this batch's records (runtime._fluency_after)
         outs = caption_samples(S, args.run_type, name_batch, lm_model, clip, lm_tokenizer, imgs, token_mask, logger,
                                prompt=args.prompt, batch_size=args.batch_size, max_len=args.sentence_len, top_k=args.candidate_k,
                                temperature=args.lm_temperature, max_iter=args.num_iterations, alpha=args.alpha, beta=args.beta,
                                generate_order=args.order, gamma=args.gamma, ctl_type=args.control_type,
                                style_type=args.sentiment_type, pos_type=args.pos_type, schedules=sched,
                                sample_tau=args.sample_tau, sample_seed=args.seed,
-                               rivals=args.distinct_rivals if args.distinct else None, delta=args.distinct)
+                               rivals=args.distinct_rivals if args.distinct else None, delta=args.distinct, fluency=fluency)
         if S > 1:
             from conzic_amd.diversity import log_distinct
             log_distinct(logger, name_batch, [[o[0][-2 if len(o[0]) > 1 else -1][i] for o in outs] for i in range(len(name_batch))])
+        if args.pick_lambda is not None:
+            from conzic_amd.runtime import log_picked
+            log_picked(logger, name_batch, fluency, args.pick_lambda, lm_tokenizer)
         for s, (gen_texts, _) in enumerate(outs):
             results[s] = merge_results(results[s], gen_texts, name_batch)
     for sample_id in range(S):
@@ -448,6 +452,7 @@ def main(argv=None):
                         token_mask, logger)
         return
     finals = {}   # image name -> the final caption of every sample
+    fluency = {}  # --fluency: batch index -> the records of its final captions, every sample's (runtime._fluency_after)
     for sample_id in range(args.samples_num):
         all_results = [None] * (args.num_iterations + 1)
         logger.info(f"Sample {sample_id + 1}: ")
@@ -463,6 +468,9 @@ def main(argv=None):
             kw = dict(prompt=args.prompt, batch_size=args.batch_size, max_len=args.sentence_len,
                       top_k=args.candidate_k, temperature=args.lm_temperature, max_iter=args.num_iterations,
                       alpha=args.alpha, beta=args.beta, generate_order=args.order)
+            if args.fluency:
+                kw["fluency"] = fluency.setdefault(batch_idx, [])
+                n_rec = len(kw["fluency"])
             if args.sample_tau or args.distinct:   # the sample loop under --sample_tau / --distinct: one rows call per sample
                 from conzic_amd.runtime import caption_samples
                 (gen_texts, _), = caption_samples(1, args.run_type, name_batch, lm_model, clip, lm_tokenizer, imgs, token_mask, logger,
@@ -478,6 +486,9 @@ def main(argv=None):
                                                         style_type=args.sentiment_type, pos_type=args.pos_type, **kw)
             if batch_idx not in embed_cache:
                 embed_cache[batch_idx] = clip.last_image_embeds()
+            if args.fluency:
+                for rec in kw["fluency"][n_rec:]:
+                    rec["sample"] = sample_id
             all_results = merge_results(all_results, gen_texts, name_batch)
             for name, text in zip(name_batch, gen_texts[-2 if len(gen_texts) > 1 else -1]):
                 finals.setdefault(name, []).append(text)
@@ -495,6 +506,10 @@ def main(argv=None):
     if args.samples_num > 1:   # (every rank logs the images of its own batches)
         from conzic_amd.diversity import log_distinct
         log_distinct(logger, list(finals), list(finals.values()))
+    if args.pick_lambda is not None:
+        from conzic_amd.runtime import log_picked
+        for batch_idx, recs in sorted(fluency.items()):
+            log_picked(logger, all_batches[batch_idx], recs, args.pick_lambda, lm_tokenizer)
 
 
 if __name__ == "__main__":

@@ -346,6 +346,56 @@ def _log_own_probability(eng: Engine, vs, ids, seed_len: int, image_of_row, img_
         logger.info(f"{what}The {b + 1}-th image: {img_name[b]}, P(own image | caption) among {n + 1} images: {float(disc[r]):.3f}")
 
 
+def caption_fluency(eng: Engine, ids, seed_len: int, lens, tokenizer, img_name, logger, what: str = ""):
+    """After the last sweep: BERT's pseudo-log-likelihood of the final captions `ids` int [R, T] (czc_fluency_rows on `eng`; row r
+    belongs to image r % len(img_name), the sample-major layout of the rows calls), one line per caption: PLL, mean log p,
+    pseudo-perplexity and the word BERT ranks lowest.  Returns fluency.summarize's records, each with its `image` index added."""
+    from . import fluency as fl
+    rows = np.ascontiguousarray(ids, dtype=np.int32)
+    if rows.ndim != 2 or not len(rows):
+        return []
+    res = eng.fluency_rows(rows, seed_len, lens=lens)
+    recs = fl.summarize(res["logp"], res["rank"], lens)
+    for r, rec in enumerate(recs):
+        b = r % len(img_name)
+        word = tokenizer.convert_ids_to_tokens([int(rows[r, seed_len + rec["worst_pos"]])])[0]
+        rec["image"] = b
+        logger.info(f"{what}The {b + 1}-th image: {img_name[b]}, fluency: PLL {rec['pll']:.4f}, mean log p {rec['mean_logp']:.4f}, "
+                    f"pseudo-perplexity {rec['ppl']:.2f}, worst word '{word}' at position {rec['worst_pos']} (rank {rec['worst_rank']})")
+    return recs
+
+
+def _fluency_after(fluency, eng: Engine, ids, cos, seed_len: int, tokenizer, img_name, logger, sample0: int = 0) -> None:
+    """`fluency` of the run_generation* functions: falsy = nothing; True = log caption_fluency of the last snapshot; a list =
+    that, and every caption's record (with `sample`, `cos` = the final cosine and `ids` = the final row) is appended to it."""
+    if fluency is None or fluency is False or ids is None or not len(ids):   # (an empty list is a collector: on)
+        return
+    recs = caption_fluency(eng, ids[-1], seed_len, None, tokenizer, img_name, logger)
+    if isinstance(fluency, list):
+        for r, rec in enumerate(recs):
+            rec.update(sample=sample0 + r // len(img_name), cos=float(cos[-1][r]), ids=np.array(ids[-1][r], dtype=np.int32))
+            fluency.append(rec)
+
+
+
+def log_picked(logger, img_name, records, lam: float, tokenizer) -> list:
+    """`--pick_lambda` of the CLIs: per image, the sample whose final caption has the largest cos + lam * mean log p among the
+    records a `fluency` list collected (the first sample on ties); one "picked caption" line per image.  Returns, per image, the
+    picked record (None for an image without records)."""
+    from . import fluency as fl
+    picked = []
+    for b, name in enumerate(img_name):
+        recs = sorted((r for r in records if r["image"] == b), key=lambda r: r["sample"])
+        if not recs:
+            picked.append(None)
+            continue
+        rec = recs[fl.pick([r["cos"] for r in recs], [r["mean_logp"] for r in recs], lam)]
+        text = tokenizer.decode(rec["ids"].tolist(), skip_special_tokens=True)
+        logger.info(f"The {b + 1}-th image: {name}, picked caption (sample {rec['sample']}, clip score {rec['cos']:.3f}, "
+                    f"mean log p {rec['mean_logp']:.4f}, lambda {lam:g}): {text}")
+        picked.append(rec)
+    return picked
+
 
 def _bookkeeping(order, ids, cos, tokenizer, img_name, logger, batch_size, verbose, print_every):
     """gen_utils.py:82-96 on the snapshots of one *_generation call: (gen_texts_list, clip_score_sequence)."""
@@ -376,12 +426,15 @@ def _bookkeeping(order, ids, cos, tokenizer, img_name, logger, batch_size, verbo
 
 def run_generation(order: str, img_name, model, clip, tokenizer, image_instance, token_mask, prompt, logger, max_len,
                    top_k, temperature, alpha, beta, max_iters, batch_size, verbose=True, gamma=None,
-                   ctl_signal="positive", print_every: Optional[int] = None, pos_template=None, rivals=None, delta: float = 0.0):
+                   ctl_signal="positive", print_every: Optional[int] = None, pos_template=None, rivals=None, delta: float = 0.0,
+                   fluency=False):
     """Body shared by every *_generation function (gen_utils.py:51-242, control_gen_utils.py:30-134):
     returns (gen_texts_list, clip_score_sequence) with the reference's list structure.
     `rivals` / `delta` (_rival_call): discriminative captions -- every candidate's fused score gets delta * P(own image |
     candidate) among the image and its rivals added (czc_generate_rows_vs: the batch as rows with the identity image map and the
-    one shared order).  "best" is still chosen by cosine; after the last sweep P(own image | caption) is logged per image."""
+    one shared order).  "best" is still chosen by cosine; after the last sweep P(own image | caption) is logged per image.
+    `fluency` (_fluency_after): after the last sweep the final captions' BERT pseudo-log-likelihood is logged per image; it changes
+    neither the captions nor what is returned."""
     import utils as ref_utils  # the repo-root drop-in (same functions as the reference's utils.py)
     eng = get_engine(model, clip, tokenizer)
     seed_len = len(prompt.split()) + 1                                   # gen_utils.py:56
@@ -446,6 +499,7 @@ def run_generation(order: str, img_name, model, clip, tokenizer, image_instance,
 
     ids, cos = _polish_guarded(polish, eng, model, clip, tokenizer, image_instance, logger)
     _log_own_probability(eng, vs, ids, seed_len, np.arange(batch_size), img_name, logger)
+    _fluency_after(fluency, eng, ids, cos, seed_len, tokenizer, img_name, logger)
     # utils.update_token_mask mutates the caller's mask in place (utils.py:53-59): leave it as the
     # reference would after the last visited position
     if positions:
@@ -456,7 +510,8 @@ def run_generation(order: str, img_name, model, clip, tokenizer, image_instance,
 def run_generation_samples(order: str, samples_num: int, img_name, model, clip, tokenizer, image_instance, token_mask, prompt,
                            logger, max_len, top_k, temperature, alpha, beta, max_iters, batch_size, verbose=True, gamma=None,
                            ctl_signal="positive", print_every: Optional[int] = None, pos_template=None, schedules=None,
-                           sample_tau: float = 0.0, sample_seed: int = 0, sample0: int = 0, rivals=None, delta: float = 0.0):
+                           sample_tau: float = 0.0, sample_seed: int = 0, sample0: int = 0, rivals=None, delta: float = 0.0,
+                           fluency=False):
     """The sample loop around a *_generation call (demo.py:83, run.py) as ONE engine call: `samples_num` samples of a batch of
     `batch_size` images ride as batch_size * samples_num rows of czc_generate_rows, every sample with the visiting order the
     serial loop would have drawn for it (harness.sample_schedules); the images are encoded once.  Returns a list of
@@ -469,7 +524,8 @@ def run_generation_samples(order: str, samples_num: int, img_name, model, clip, 
     `sample_tau` > 0: every row draws its winner from softmax_K(final_score / sample_tau) (czc_generate_rows_draw) under the
     seed of its (image, sample): draws.row_seed(sample_seed, key of the image's name, sample0 + s).  A serial loop that calls
     this function once per sample (samples_num = 1, sample0 = the sample's index) returns the ids of the one batched call.
-    `rivals` / `delta`: as for run_generation; every sample of an image carries the image's rivals (czc_generate_rows_vs)."""
+    `rivals` / `delta`: as for run_generation; every sample of an image carries the image's rivals (czc_generate_rows_vs).
+    `fluency`: as for run_generation, one line per (sample, image) row."""
     from . import draws as dw
     import utils as ref_utils
     S, B = int(samples_num), int(batch_size)
@@ -555,6 +611,7 @@ def run_generation_samples(order: str, samples_num: int, img_name, model, clip, 
 
     ids, cos = _polish_guarded(polish, eng, model, clip, tokenizer, image_instance, logger)
     _log_own_probability(eng, vs, ids, seed_len, image_of_row, img_name, logger)
+    _fluency_after(fluency, eng, ids, cos, seed_len, tokenizer, img_name, logger, sample0=sample0)
     if positions.shape[0]:   # the caller's mask as after the LAST sample's last position (utils.py:53-59)
         ref_utils.update_token_mask(tokenizer, token_mask, max_len, int(positions[-1, S - 1]))
     out = []
@@ -806,7 +863,7 @@ def caption_order(run_type: str, generate_order: str, ctl_type: str, max_iter: i
 def caption_samples(samples_num: int, run_type: str, img_name, model, clip, tokenizer, image_instance, token_mask, logger, *,
                     prompt="", batch_size=1, max_len=15, top_k=100, temperature=1.0, max_iter=500, alpha=0.7, beta=1,
                     generate_order="sequential", gamma=5, ctl_type="sentiment", style_type="positive", pos_type=None,
-                    schedules=None, sample_tau=0.0, sample_seed=0, sample0=0, rivals=None, delta=0.0):
+                    schedules=None, sample_tau=0.0, sample_seed=0, sample0=0, rivals=None, delta=0.0, fluency=False):
     """`--batch_samples` of the two CLIs: what `samples_num` calls of generate_caption (run_type 'caption', gen_utils.py:289-333)
     or control_generate_caption (control_gen_utils.py:197-232) return, from one run_generation_samples call.  Returns the list
     of (generate_texts, clip_scores) pairs and logs every sample's final and best captions as those functions do."""
@@ -825,7 +882,8 @@ def caption_samples(samples_num: int, run_type: str, img_name, model, clip, toke
         kw.update(gamma=gamma, pos_template=pos_type)
     outs = run_generation_samples(order, samples_num, img_name, model, clip, tokenizer, image_instance, token_mask, prompt,
                                   logger, max_len, top_k, temperature, alpha, beta, max_iters, batch_size, schedules=schedules,
-                                  sample_tau=sample_tau, sample_seed=sample_seed, sample0=sample0, rivals=rivals, delta=delta, **kw)
+                                  sample_tau=sample_tau, sample_seed=sample_seed, sample0=sample0, rivals=rivals, delta=delta,
+                                  fluency=fluency, **kw)
     logger.info("Finished %d samples in %.3fs" % (samples_num, time.time() - start_time))
     for sample_id, (generate_texts, _) in enumerate(outs):
         logger.info(f"Sample {sample0 + sample_id}: ")

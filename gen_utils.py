@@ -18,44 +18,46 @@ from conzic_amd.runtime import run_generation
 
 def sequential_generation(img_name, model, clip, tokenizer, image_instance, token_mask, prompt, logger,
                           max_len=15, top_k=100, temperature=None, alpha=0.7, beta=1,
-                          max_iters=20, batch_size=1, verbose=True):
+                          max_iters=20, batch_size=1, verbose=True, fluency=False):
     """Generate one word at a time, in L->R order (gen_utils.py:51-96)."""
     return run_generation("sequential", img_name, model, clip, tokenizer, image_instance, token_mask, prompt, logger,
-                          max_len, top_k, temperature, alpha, beta, max_iters, batch_size, verbose)
+                          max_len, top_k, temperature, alpha, beta, max_iters, batch_size, verbose, fluency=fluency)
 
 
 def shuffle_generation(img_name, model, clip, tokenizer, image_instance, token_mask, prompt, logger,
                        max_len=15, top_k=0, temperature=None, alpha=0.7, beta=1,
-                       max_iters=20, batch_size=1, verbose=True):
+                       max_iters=20, batch_size=1, verbose=True, fluency=False):
     """Generate one word at a time, in random generation order (gen_utils.py:98-146)."""
     return run_generation("shuffle", img_name, model, clip, tokenizer, image_instance, token_mask, prompt, logger,
-                          max_len, top_k, temperature, alpha, beta, max_iters, batch_size, verbose)
+                          max_len, top_k, temperature, alpha, beta, max_iters, batch_size, verbose, fluency=fluency)
 
 
 def span_generation(img_name, model, clip, tokenizer, image_instance, token_mask, prompt, logger,
                     max_len=15, top_k=0, temperature=None, alpha=0.7, beta=1,
-                    max_iters=20, batch_size=1, verbose=True):
+                    max_iters=20, batch_size=1, verbose=True, fluency=False):
     """Generate span_len=2 words per BERT forward, in L->R order (gen_utils.py:148-195)."""
     return run_generation("span", img_name, model, clip, tokenizer, image_instance, token_mask, prompt, logger,
-                          max_len, top_k, temperature, alpha, beta, max_iters, batch_size, verbose)
+                          max_len, top_k, temperature, alpha, beta, max_iters, batch_size, verbose, fluency=fluency)
 
 
 def random_generation(img_name, model, clip, tokenizer, image_instance, token_mask, prompt, logger,
                       max_len=15, top_k=0, temperature=None, alpha=0.7, beta=2, max_iters=300, print_every=10,
-                      batch_size=1, verbose=True):
+                      batch_size=1, verbose=True, fluency=False):
     """Generate for one random position per step (gen_utils.py:197-242)."""
     return run_generation("random", img_name, model, clip, tokenizer, image_instance, token_mask, prompt, logger,
                           max_len, top_k, temperature, alpha, beta, max_iters, batch_size, verbose,
-                          print_every=print_every)
+                          print_every=print_every, fluency=fluency)
 
 
 def generate_caption(img_name, model, clip, tokenizer, image_instance, token_mask, logger,
                      prompt="", batch_size=1, max_len=15,
                      top_k=100, temperature=1.0, max_iter=500, alpha=0.7, beta=1,
-                     generate_order="sequential"):
-    """Main entry point (gen_utils.py:289-333)."""
+                     generate_order="sequential", fluency=False):
+    """Main entry point (gen_utils.py:289-333).  `fluency` (not in the reference; conzic_amd.runtime.run_generation): log the final
+    captions' BERT pseudo-log-likelihood after the last sweep."""
     start_time = time.time()
-    common = dict(batch_size=batch_size, max_len=max_len, top_k=top_k, alpha=alpha, beta=beta, temperature=temperature)
+    common = dict(batch_size=batch_size, max_len=max_len, top_k=top_k, alpha=alpha, beta=beta, temperature=temperature,
+                  fluency=fluency)
     if generate_order == "sequential":
         generate_texts, clip_scores = sequential_generation(img_name, model, clip, tokenizer, image_instance,
                                                             token_mask, prompt, logger, max_iters=max_iter, **common)

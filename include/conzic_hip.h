@@ -8,7 +8,9 @@
  *   gen_utils.py:64-81   (sequential_generation), :114-130 (shuffle_generation),
  *   gen_utils.py:160-179 (span_generation),       :209-226 (random_generation),
  *   control_gen_utils.py:43-65, :98-120           (sentiment_*_generation)
- * plus the once-per-image CLIP vision encode (clip/clip.py:48-62).
+ * plus the once-per-image CLIP vision encode (clip/clip.py:48-62).  Beyond the reference: whole chains on the device
+ * (czc_generate*), the scores of finished captions (czc_score_rows: CLIP cosine; czc_fluency_rows: BERT pseudo-log-likelihood)
+ * and caption retrieval.
  *
  * The reference is pure Python over torch/transformers, so it has no FFI of its own; the
  * Python modules gen_utils / control_gen_utils / clip.clip / utils at the repo root keep the
@@ -513,6 +515,33 @@ int czc_score_rows_vs(czc_engine* e, const int32_t* rows /* [R, T] BERT ids, hos
                       const int32_t* len_of_row_host, const int32_t* image_of_row_host, const int32_t* rival_of_row_host, int M,
                       float* out_cos /* [R] */, float* out_disc /* [R] */);
 
+/* Caption fluency: BERT's pseudo-log-likelihood of finished rows, on the device -- the BERT-side twin of czc_score_rows.
+ * Lmax = T - seed_len - 1.  Row r has L_r = len_of_row[r] words at columns seed_len .. seed_len + L_r - 1 and T_r = seed_len + L_r + 1
+ * tokens.  For every word j < L_r BERT reads the row's T_r tokens with word j masked, as a step reads them (position embeddings
+ * 0 .. T_r - 1, attention over its own T_r keys, no padding seen; the engine's BERT precision; option "bert_prune" applies), and
+ *   out_logp[r][j] = log softmax(logits / temperature) at the id the row holds at word j (natural log),
+ *   out_rank[r][j] = #{i : x_i > x_t} + #{i < t : x_i == x_t} on the raw logits x, t that id: its place in the step's sorted
+ *                    candidate list under an all-ones token mask (ties in ascending id, the top-K kernel's rule),
+ *   out_pll[r]     = out_logp[r][0] + ... + out_logp[r][L_r - 1], summed in that order in fp32.
+ * Columns j >= L_r hold 0.0f and -1.  Any output pointer may be NULL, but not all three.
+ * Prompt, [CLS] and [SEP] are context and are never scored; an id is scored as it stands (a [MASK] left in a row is scored as
+ * the id mask_id); the token mask plays no part -- this is BERT's distribution, not the step's masked one.
+ * The N = sum L_r masked sequences run in chunks of at most "fluency_chunk" (cut at any sequence boundary; ragged rows where the
+ * lengths differ, dense rows where every T_r == T).  One upload of the call's tables, one read of the results at the end.  A
+ * position's result is a function of its row's content, its length and the temperature; across companions, chunk sizes and row
+ * orders it agrees within the engine precision (the form of BERT's GEMMs depends on the packed row count, as for
+ * czc_generate_rows_len), and the same call repeated returns the same bits.
+ * Needs finalized weights only: no bridge tables, no image embeds, no token mask.  Leaves the resident image embeds, the text
+ * index, the options, the memo and the counters of czc_stats alone.  It ends any forward re-use: an n_mask = 0 czc_step right
+ * after it returns CZC_ERR_STATE.
+ * Checked before any GPU work, CZC_ERR_ARG, and the engine stays usable: R outside [1, CZC_MAX_ROWS], T outside
+ * [1, CZC_MAX_BERT_LEN], seed_len < 0, T - seed_len - 1 < 1, a length outside [1, Lmax], an id outside the vocabulary within a
+ * row's T_r tokens, a temperature that is not finite and > 0, all outputs NULL.  CZC_ERR_STATE without finalized weights.
+ * CZC_ERR_OVERFLOW when a log-probability is not finite. */
+int czc_fluency_rows(czc_engine* e, const int32_t* rows /* [R, T] BERT ids, host or device */, int R, int T, int seed_len,
+                     const int32_t* len_of_row_host /* NULL: every row has L = T - seed_len - 1 */, float temperature,
+                     float* out_logp /* [R, Lmax] */, int32_t* out_rank /* [R, Lmax] */, float* out_pll /* [R] */);
+
 /* Engine options (all are exact work reductions / kernel choices; results agree within the engine precision):
  *   "share_prefix"    (1) encode the causal prefix common to an image's K candidates once per step instead of K
  *                         times
@@ -601,7 +630,9 @@ int czc_score_rows_vs(czc_engine* e, const int32_t* rows /* [R, T] BERT ids, hos
  *                         per step).  Entry storage of a call: L x R x T x 12 bytes + L x R x 24 bytes on the device, i.e.
  *                         8 MB + 1 MB at R = 4096, L = 10, T = 16 and, at its largest (R = CZC_MAX_ROWS, L = 62, T = 64), 780 MB + 24 MB,
  *                         kept in the engine's workspace.  Replicas inherit the option and keep entries of their own.
- *                         czc_memo_rows_stats counts the hits */
+ *                         czc_memo_rows_stats counts the hits
+ *   "fluency_chunk"   (1024) czc_fluency_rows: masked sequences per BERT forward, 1 .. 16384 (CZC_ERR_ARG outside); the logits
+ *                         buffer of a call holds chunk x vocab x 4 bytes */
 int czc_set_option(czc_engine* e, const char* name, int value);
 /* Reads an option back (same names and units as czc_set_option), plus three read-only derived values:
  *   "refine_guard_generate_x1e6" / "refine_gate_generate_x1e6": the guard's trip point / the margin gate's bound in force inside

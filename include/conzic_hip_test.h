@@ -231,6 +231,17 @@ int czc_test_memo_rows_chain(int R, int T, int L, int seed_len, int D, int n_mas
                              float* cos_out, int32_t* imax_out, int32_t* hit, int32_t* cnt, int32_t* list, int32_t* tot, int32_t* inp_out,
                              float* bcos_out, int32_t* inp_c, float* img_c, int32_t* col_c, int32_t* dot_c);
 
+/* ---- caption fluency (csrc/fluency.hip; numpy models in tests/fluency_ref.py).  Plain output arrays of the sizes named. */
+/* launch_logprob_target on logits [N, V], target [N] (checked: inside [0, V)) -> logp, rank [N]; nonfinite [1] (zeroed first).  The
+ * device logits keep the row stride V, so odd V give rows that do not start on a 16-byte boundary. */
+int czc_test_logprob(int N, int V, const float* logits, const int32_t* target, float temperature, float* logp, int32_t* rank,
+                     int32_t* nonfinite);
+/* The expansion of czc_fluency_rows: the host tables (fluency_expand_tables) and launch_expand_mask_rows on rows [R, T] with
+ * len_of_row [R] (NULL: every row has T - seed_len - 1 words) -> *n_seq = N = sum L_r, ids_out [N, T], target, gen_rows [N]
+ * (the caller sizes them for N). */
+int czc_test_expand_mask(int R, int T, int seed_len, int mask_id, const int32_t* rows, const int32_t* len_of_row, int32_t* ids_out,
+                         int32_t* target, int32_t* gen_rows, int32_t* n_seq);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -36,6 +36,8 @@ ap.add_argument("--sweeps", type=int, default=10)
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--scales", type=float, nargs="+", default=[2.6592, 4.6052])
 ap.add_argument("--layout", default="interleaved", choices=["interleaved", "contiguous"])
+ap.add_argument("--fluency", action="store_true",
+                help="also record, per width, the merged caption's mean log p under BERT (Engine.fluency_rows) next to its cosine")
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r12_block_probe.json"))
 ap.add_argument("--describe", nargs="?", const=os.path.join(ROOT, "profiles", "r12_block_probe.json"), default=None, metavar="JSON",
                 help="print the README sentence for a result file and exit")
@@ -111,7 +113,7 @@ def timing_leg(scale):
 def converging_leg(prec):
     su, _, hp, init, seed_len = harness.converging_setup(B=1, L=args.L, precision=prec)
     eng = su.engine
-    out = {}
+    out, flu = {}, {}
     try:
         for w in args.widths:
             if w == 1:
@@ -125,16 +127,18 @@ def converging_leg(prec):
                                                 [hp] * w, None, groups, image_of_row=ior, snapshot_every=nb)
                 rows = ids[-1, :1]
             out[w] = float(eng.score_rows(rows, seed_len)[0])   # one yardstick for every width: the caption as it stands
+            if args.fluency:   # the other half of the objective: the same caption's mean log p under BERT
+                flu[w] = float(eng.fluency_rows(rows, seed_len)["pll"][0]) / args.L
     finally:
         eng.close()
-    return out
+    return out, flu
 
 
 def main():
     out = []
     for scale in args.scales:
         prec, times, finals = timing_leg(scale)
-        cos = converging_leg(prec)
+        cos, flu = converging_leg(prec)
         base = float(np.median(times[1])) if 1 in times else None
         rec = dict(logit_scale=scale, precision=runtime.PRECISION_NAMES[prec], L=args.L, K=args.K, sweeps=args.sweeps, order="sequential",
                    layout=args.layout, images=1, reps=args.reps, widths=[])
@@ -146,6 +150,8 @@ def main():
                 faster_in_every_rep=bool(1 in times and w != 1 and all(t < t1 for t, t1 in zip(times[w], times[1]))),
                 slower_in_every_rep=bool(1 in times and w != 1 and all(t > t1 for t, t1 in zip(times[w], times[1]))),
                 final_caption=finals[w], converging_final_cos=cos[w]))
+            if args.fluency:
+                rec["widths"][-1]["converging_final_mean_logp"] = flu[w]
         print(json.dumps(rec), flush=True)
         out.append(rec)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)

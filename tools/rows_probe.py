@@ -71,11 +71,15 @@ ap.add_argument("--sample_tau", type=float, default=None, metavar="T",
                 help="the draw leg: the rows call with every tau = 0 against the same call with every tau = T")
 ap.add_argument("--distinct", type=float, default=None, metavar="DELTA",
                 help="the rivals leg: the rows call with rival_of_row = NULL against the same call with 4 rivals per row")
+ap.add_argument("--fluency_probe", action="store_true",
+                help="the fluency leg: Engine.fluency_rows on R captions of L words against the path without it (L steps that return "
+                     "their logits row + a host log-softmax); R from --S")
+ap.add_argument("--describe_fluency", default=None, metavar="JSON", help="print the README sentence for a fluency-leg result file and exit")
 ap.add_argument("--describe_distinct", default=None, metavar="JSON", help="print the README sentence for a rivals-leg result file and exit")
 ap.add_argument("--describe_draw", default=None, metavar="JSON", help="print the README sentence for a draw-leg result file and exit")
 args = ap.parse_args()
 if args.out is None:
-    args.out = os.path.join(ROOT, "profiles", "r13_rival_probe.json" if args.distinct else "r11_draw_probe.json" if args.sample_tau else "r10_signals_probe.json" if args.signals else "r09_lengths_probe.json" if args.lengths else
+    args.out = os.path.join(ROOT, "profiles", "r14_fluency_probe.json" if args.fluency_probe else "r13_rival_probe.json" if args.distinct else "r11_draw_probe.json" if args.sample_tau else "r10_signals_probe.json" if args.signals else "r09_lengths_probe.json" if args.lengths else
                             "r09_memo_rows_probe.json" if args.memo_rows else "r08_rows_probe.json")
 
 L, K, SEED_LEN = args.L, args.K, 4
@@ -123,6 +127,64 @@ if args.describe_distinct:
 
 def spread(ts):
     return (max(ts) - min(ts)) / float(np.median(ts))
+
+
+def describe_fluency(records):
+    """The README's sentence, from the records of a result file."""
+    return "; ".join(f"on the {r['precision']} engine, R = {r['R']} captions of L = {r['L']}: {r['wall_s_fluency_median'] * 1e3:.1f} ms for "
+                     f"fluency_rows (spread {100 * r['spread_fluency']:.1f} %) against {r['wall_s_steps_median'] * 1e3:.1f} ms for {r['L']} steps "
+                     f"that return their logits row plus the host log-softmax (spread {100 * r['spread_steps']:.1f} %), ratio of the medians "
+                     f"{r['ratio_median']:.2f}; largest |log p| difference between the two {r['max_abs_diff']:.1e}" for r in records)
+
+
+if args.describe_fluency:
+    print(describe_fluency(json.load(open(args.describe_fluency))))
+    sys.exit(0)
+
+
+def fluency_leg():
+    """Full-size synthetic towers, arms alternated, median of 5: one fluency_rows call against what a user does without it."""
+    reps = max(args.reps, 5)
+    for scale in args.scales:
+        prec = runtime.choose_precision(scale)
+        su = harness.build_synthetic(False, prec, logit_scale=scale, regular_only=True)
+        eng = su.engine
+        regular = np.nonzero(su.token_mask[0] > 0)[0]
+        for R in (args.S if args.S != [1, 2, 4, 8, 16] else [16]):
+            rows = np.repeat(np.asarray(su.bert_tok.encode("Image of a" + su.bert_tok.mask_token * L), np.int32)[None, :], R, axis=0)
+            rows[:, SEED_LEN:SEED_LEN + L] = np.random.default_rng(5).choice(regular, size=(R, L))
+            eng.set_image_embeds(np.random.default_rng(100).standard_normal((R, su.clip_cfg.proj)).astype(np.float32))
+            hp = Engine.hyper(0.02, 2.0, 1.0)
+
+            def fluency():
+                return eng.fluency_rows(rows, SEED_LEN)["logp"]
+
+            def steps():   # every step also runs a CLIP tower nobody wants: that is the path as it stands
+                logp = np.empty((R, L), np.float32)
+                for j in range(L):
+                    x = eng.step(rows.copy(), SEED_LEN + j, K, hp, want=("logits",))["logits"].astype(np.float64)
+                    lse = x.max(axis=1) + np.log(np.exp(x - x.max(axis=1, keepdims=True)).sum(axis=1))
+                    logp[:, j] = x[np.arange(R), rows[:, SEED_LEN + j]] - lse
+                return logp
+
+            arms = {"fluency": fluency, "steps": steps}
+            warm = {arm: fn() for arm, fn in arms.items()}
+            times = {arm: [] for arm in arms}
+            for _ in range(reps):
+                for arm, fn in arms.items():
+                    eng.sync()
+                    t0 = time.perf_counter()
+                    fn()
+                    times[arm].append(time.perf_counter() - t0)
+            rec = dict(logit_scale=scale, precision=runtime.PRECISION_NAMES[prec], R=R, L=L, K=K, reps=reps,
+                       max_abs_diff=float(np.abs(warm["fluency"] - warm["steps"]).max()))
+            for arm in arms:
+                rec.update({f"wall_s_{arm}": times[arm], f"wall_s_{arm}_median": float(np.median(times[arm])), f"spread_{arm}": spread(times[arm])})
+            rec["ratio_median"] = rec["wall_s_steps_median"] / rec["wall_s_fluency_median"]
+            print(json.dumps(rec), flush=True)
+            out.append(rec)
+        eng.close()
+    print(describe_fluency(out))
 
 
 def memo_rows_leg():
@@ -344,7 +406,9 @@ def distinct_leg():
     print(describe_distinct(out))
 
 
-if args.distinct:
+if args.fluency_probe:
+    fluency_leg()
+elif args.distinct:
     distinct_leg()
 elif args.sample_tau:
     draw_leg()
@@ -354,7 +418,7 @@ elif args.signals:
     signals_leg()
 elif args.lengths:
     lengths_leg()
-for scale in ([] if args.memo_rows or args.lengths or args.signals or args.sample_tau or args.distinct else args.scales):
+for scale in ([] if args.fluency_probe or args.memo_rows or args.lengths or args.signals or args.sample_tau or args.distinct else args.scales):
     prec = runtime.choose_precision(scale)
     su = harness.build_synthetic(False, prec, logit_scale=scale, regular_only=True)
     eng = su.engine

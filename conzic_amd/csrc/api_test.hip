@@ -65,7 +65,7 @@ static const Hooks& HK() {
 #define TEST_ERR (HK().err_buf())
 
 static int g_bench_pad = 0;
-static int g_bridge_no_table = 0;  // czc_test_bridge: 1 = every chunk through the merge loop (option "bridge_no_table")  // czc_bench_gemm: extra elements per row of A and W (row pitch vs L2 channel experiments)
+static int g_bridge_no_table = 0;  // czc_test_bridge, czc_test_bridge_cand: 1 = every chunk through the merge loop (option "bridge_no_table")  // czc_bench_gemm: extra elements per row of A and W (row pitch vs L2 channel experiments)
 
 namespace {
 
@@ -146,6 +146,48 @@ struct Guarded {
     return 0;
   }
 };
+
+// The bridge tables on the device as the engine holds them (czc_set_bridge): the arrays uploaded, the merge list hashed and --
+// unless the option "bridge_no_table" is set -- the per-token CLIP ids tabulated by launch_bridge_precompute.  Shared by
+// czc_test_bridge and czc_test_bridge_cand.
+int bridge_tables_dev(DevPool& pool, const czc_bridge_tables* t, BridgeDev& bd) {
+  const size_t nbytes = t->piece_off[t->bert_vocab];
+  bd.bert_vocab = t->bert_vocab;
+  bd.piece_off = (const uint32_t*)pool.up(t->piece_off, (size_t)(t->bert_vocab + 1) * 4); T_PTR(bd.piece_off);
+  bd.piece_bytes = (const uint8_t*)pool.up(t->piece_bytes, nbytes ? nbytes : 1); T_PTR(bd.piece_bytes);
+  bd.piece_class = (const uint8_t*)pool.up(t->piece_class, nbytes ? nbytes : 1); T_PTR(bd.piece_class);
+  bd.piece_flags = (const uint8_t*)pool.up(t->piece_flags, (size_t)t->bert_vocab); T_PTR(bd.piece_flags);
+  bd.byte_sym = (const int*)pool.up(t->byte_sym, 256 * 4); T_PTR(bd.byte_sym);
+  bd.byte_sym_eow = (const int*)pool.up(t->byte_sym_eow, 256 * 4); T_PTR(bd.byte_sym_eow);
+  size_t cap = 1024;
+  while (cap < (size_t)t->n_merges * 2 + 2) cap <<= 1;
+  std::vector<unsigned long long> keys(cap, ~0ull), vals(cap, 0ull);
+  for (int r = 0; r < t->n_merges; ++r) {
+    const unsigned long long key = ((unsigned long long)(unsigned)t->merge_left[r] << 32) | (unsigned)t->merge_right[r];
+    unsigned h = bridge_hash(key) & (unsigned)(cap - 1);
+    bool dup = false;
+    while (keys[h] != ~0ull) {
+      if (keys[h] == key) { dup = true; break; }
+      h = (h + 1) & (unsigned)(cap - 1);
+    }
+    if (dup) continue;
+    keys[h] = key;
+    vals[h] = ((unsigned long long)(unsigned)r << 32) | (unsigned)t->merge_out[r];
+  }
+  bd.hkeys = (const unsigned long long*)pool.up(keys.data(), cap * 8); T_PTR(bd.hkeys);
+  bd.hvals = (const unsigned long long*)pool.up(vals.data(), cap * 8); T_PTR(bd.hvals);
+  bd.hmask = (unsigned)(cap - 1);
+  bd.bos_id = t->bos_id;
+  bd.eos_id = t->eos_id;
+  if (!g_bridge_no_table) {  // the product's fast path: per-token ids tabulated on the device
+    int* tok_ids = (int*)pool.alloc((size_t)t->bert_vocab * BR_TOKMAX * 4); T_PTR(tok_ids);
+    uint8_t* tok_len = (uint8_t*)pool.alloc((size_t)t->bert_vocab); T_PTR(tok_len);
+    T_CHECK(launch_bridge_precompute(bd, tok_ids, tok_len, nullptr));
+    T_HIP(hipDeviceSynchronize());
+    bd.tok_bpe = tok_ids; bd.tok_bpe_len = tok_len;
+  }
+  return 0;
+}
 
 }  // namespace
 
@@ -658,41 +700,7 @@ int czc_test_bridge(const czc_bridge_tables* t, const czc_config* cfg, int n_row
   (void)cfg;
   DevPool pool;
   BridgeDev bd;
-  const size_t nbytes = t->piece_off[t->bert_vocab];
-  bd.bert_vocab = t->bert_vocab;
-  bd.piece_off = (const uint32_t*)pool.up(t->piece_off, (size_t)(t->bert_vocab + 1) * 4); T_PTR(bd.piece_off);
-  bd.piece_bytes = (const uint8_t*)pool.up(t->piece_bytes, nbytes ? nbytes : 1); T_PTR(bd.piece_bytes);
-  bd.piece_class = (const uint8_t*)pool.up(t->piece_class, nbytes ? nbytes : 1); T_PTR(bd.piece_class);
-  bd.piece_flags = (const uint8_t*)pool.up(t->piece_flags, (size_t)t->bert_vocab); T_PTR(bd.piece_flags);
-  bd.byte_sym = (const int*)pool.up(t->byte_sym, 256 * 4); T_PTR(bd.byte_sym);
-  bd.byte_sym_eow = (const int*)pool.up(t->byte_sym_eow, 256 * 4); T_PTR(bd.byte_sym_eow);
-  size_t cap = 1024;
-  while (cap < (size_t)t->n_merges * 2 + 2) cap <<= 1;
-  std::vector<unsigned long long> keys(cap, ~0ull), vals(cap, 0ull);
-  for (int r = 0; r < t->n_merges; ++r) {
-    const unsigned long long key = ((unsigned long long)(unsigned)t->merge_left[r] << 32) | (unsigned)t->merge_right[r];
-    unsigned h = bridge_hash(key) & (unsigned)(cap - 1);
-    bool dup = false;
-    while (keys[h] != ~0ull) {
-      if (keys[h] == key) { dup = true; break; }
-      h = (h + 1) & (unsigned)(cap - 1);
-    }
-    if (dup) continue;
-    keys[h] = key;
-    vals[h] = ((unsigned long long)(unsigned)r << 32) | (unsigned)t->merge_out[r];
-  }
-  bd.hkeys = (const unsigned long long*)pool.up(keys.data(), cap * 8); T_PTR(bd.hkeys);
-  bd.hvals = (const unsigned long long*)pool.up(vals.data(), cap * 8); T_PTR(bd.hvals);
-  bd.hmask = (unsigned)(cap - 1);
-  bd.bos_id = t->bos_id;
-  bd.eos_id = t->eos_id;
-  if (!g_bridge_no_table) {  // the product's fast path: per-token ids tabulated on the device
-    int* tok_ids = (int*)pool.alloc((size_t)t->bert_vocab * BR_TOKMAX * 4); T_PTR(tok_ids);
-    uint8_t* tok_len = (uint8_t*)pool.alloc((size_t)t->bert_vocab); T_PTR(tok_len);
-    T_CHECK(launch_bridge_precompute(bd, tok_ids, tok_len, nullptr));
-    T_HIP(hipDeviceSynchronize());
-    bd.tok_bpe = tok_ids; bd.tok_bpe_len = tok_len;
-  }
+  T_CHECK(bridge_tables_dev(pool, t, bd));
   int* drows = (int*)pool.up(rows, (size_t)n_rows * T * 4); T_PTR(drows);
   int* dids = (int*)pool.alloc((size_t)n_rows * CZC_CLIP_MAX_LEN * 4); T_PTR(dids);
   int* dlen = (int*)pool.alloc((size_t)n_rows * 4); T_PTR(dlen);
@@ -1471,6 +1479,86 @@ int czc_test_expand_mask(int R, int T, int seed_len, int mask_id, const int32_t*
   T_HIP(hipMemcpy(gen_rows, dgen, (size_t)N * 4, hipMemcpyDeviceToHost));
   *n_seq = N;
   return 0;
+}
+
+// ---- the text bridge with candidates, the per-row forms of the top-K selection (bridge.hip, topk.hip) ---------------------------
+int czc_test_bridge_cand(const czc_bridge_tables* t, int form, int B, int T, int K, const int32_t* inp, int gen_idx, const int32_t* gen_rows,
+                         const int32_t* row_len, const int32_t* cand, const float* lexicon, const float* lex_pos, const uint8_t* lex_cls,
+                         const uint8_t* tag_of_token, const uint16_t* masks, int n_masks, int negative, const czc_hyper* hp_rows,
+                         int32_t* clip_ids, int32_t* clip_len, float* senti_raw, float* repeats, int32_t* overflow) {
+  const char* who = "bridge_cand";
+  T_ARG(t && form >= 0 && form <= 2 && B >= 1 && K >= 1 && (long)B * K <= (1 << 20) && T >= 1 && T <= CZC_MAX_BERT_LEN && inp, who);
+  T_ARG(clip_ids && clip_len && senti_raw && repeats && overflow, who);
+  const int V = t->bert_vocab;
+  // every index the kernel follows, checked here: nothing out of bounds reaches the launch
+  T_ARG(all_in(inp, (size_t)B * T, 0, V) && (!cand || all_in(cand, (size_t)B * K, 0, V)), who);
+  T_ARG(cand || form != 0 || K == 1, who);  // verbatim rows (launch_bridge without candidates); the per-row launchers refuse a null cand themselves
+  T_ARG(form == 0 ? (!cand || (gen_idx >= 0 && gen_idx < T)) : (!gen_rows || all_in(gen_rows, B, 0, T)), who);
+  T_ARG(!row_len || all_in(row_len, B, 1, T + 1), who);
+  T_ARG(!lex_pos == !lex_cls && (!lex_cls || [&] { for (int i = 0; i < V; ++i) if (lex_cls[i] >= 5) return false; return true; }()), who);
+  T_ARG(!tag_of_token == !masks && (!masks || n_masks >= 1), who);
+  T_ARG(!tag_of_token || [&] { for (int i = 0; i < V; ++i) if (tag_of_token[i] >= 15) return false; return true; }(), who);
+  static_assert(sizeof(RowHyper) == sizeof(czc_hyper), "RowHyper is czc_hyper as the kernels read it");
+  DevPool pool;
+  BridgeDev bd;
+  T_CHECK(bridge_tables_dev(pool, t, bd));
+  const size_t bk = (size_t)B * K;
+  int* dinp = (int*)pool.up(inp, (size_t)B * T * 4); T_PTR(dinp);
+  int *dgen = nullptr, *dlen = nullptr, *dcand = nullptr;
+  float *dlex = nullptr, *dlp = nullptr;
+  uint8_t *dlc = nullptr, *dtag = nullptr;
+  uint16_t* dmask = nullptr;
+  RowHyper* dhp = nullptr;
+  if (gen_rows) { dgen = (int*)pool.up(gen_rows, (size_t)B * 4); T_PTR(dgen); }
+  if (row_len) { dlen = (int*)pool.up(row_len, (size_t)B * 4); T_PTR(dlen); }
+  if (cand) { dcand = (int*)pool.up(cand, bk * 4); T_PTR(dcand); }
+  if (lexicon) { dlex = (float*)pool.up(lexicon, (size_t)V * 4); T_PTR(dlex); }
+  if (lex_pos) { dlp = (float*)pool.up(lex_pos, (size_t)V * 5 * 4); T_PTR(dlp); dlc = (uint8_t*)pool.up(lex_cls, (size_t)V); T_PTR(dlc); }
+  if (tag_of_token) {
+    dtag = (uint8_t*)pool.up(tag_of_token, (size_t)V); T_PTR(dtag);
+    dmask = (uint16_t*)pool.up(masks, (size_t)n_masks * 2); T_PTR(dmask);
+  }
+  if (hp_rows) { dhp = (RowHyper*)pool.up(hp_rows, (size_t)B * sizeof(czc_hyper)); T_PTR(dhp); }
+  Guarded gids, glen, gs, gr, govf;
+  T_CHECK(gids.make(pool, bk * CZC_CLIP_MAX_LEN)); T_CHECK(glen.make(pool, bk)); T_CHECK(gs.make(pool, bk)); T_CHECK(gr.make(pool, bk));
+  T_CHECK(govf.make(pool, 1)); T_CHECK(govf.zero(1));
+  const PosDev pos{dtag, dmask, dtag ? n_masks : 0};
+  int rc;
+  if (form == 0)
+    rc = launch_bridge(bd, dinp, B, T, cand ? gen_idx : -1, dcand, K, dlex, dlp, dlc, negative, pos, gids.p<int>(), glen.p<int>(), gs.p<float>(),
+                       gr.p<float>(), govf.p<int>(), nullptr);
+  else if (form == 1)
+    rc = HK().bridge_rows(bd, dinp, B, T, dgen, dcand, K, dlex, dlp, dlc, negative, pos, gids.p<int>(), glen.p<int>(), gs.p<float>(),
+                          gr.p<float>(), govf.p<int>(), nullptr, dlen);
+  else
+    rc = HK().bridge_rows_hp(bd, dinp, B, T, dgen, dcand, K, dlex, dlp, dlc, dhp, pos, gids.p<int>(), glen.p<int>(), gs.p<float>(),
+                             gr.p<float>(), govf.p<int>(), nullptr, dlen);
+  T_HIP(hipDeviceSynchronize());
+  T_CHECK(gids.down(clip_ids)); T_CHECK(glen.down(clip_len)); T_CHECK(gs.down(senti_raw)); T_CHECK(gr.down(repeats));
+  T_CHECK(govf.down(overflow));
+  return launch_status(rc);
+}
+
+int czc_test_topk_rows(int form, int B, int V, int K, const float* logits, const float* mask, float temperature, int dot_id,
+                       const int32_t* dot_rows, const czc_hyper* hp_rows, float* probs, int32_t* idxs, int32_t* cand) {
+  const char* who = "topk_rows";
+  T_ARG((form == 1 || form == 2) && B >= 1 && B <= (1 << 14) && V >= 1 && K >= 1 && logits && mask && probs && idxs && cand, who);
+  T_ARG(form == 2 || (dot_rows && temperature > 0.f), who);  // only the hyper-parameter form checks its own pointers
+  DevPool pool;
+  float* dl = (float*)pool.up(logits, (size_t)B * V * 4); T_PTR(dl);
+  float* dm = (float*)pool.up(mask, (size_t)V * 4); T_PTR(dm);
+  int* dd = nullptr;
+  RowHyper* dhp = nullptr;
+  if (dot_rows) { dd = (int*)pool.up(dot_rows, (size_t)B * 4); T_PTR(dd); }
+  if (hp_rows) { dhp = (RowHyper*)pool.up(hp_rows, (size_t)B * sizeof(czc_hyper)); T_PTR(dhp); }
+  Guarded gp, gi, gc;
+  const size_t bk = (size_t)B * K;
+  T_CHECK(gp.make(pool, bk)); T_CHECK(gi.make(pool, bk)); T_CHECK(gc.make(pool, bk));
+  const int rc = form == 1 ? HK().softmax_mask_topk_rows(dl, B, V, K, dm, temperature, dot_id, dd, gp.p<float>(), gi.p<int>(), gc.p<int>(), nullptr)
+                           : HK().softmax_mask_topk_rows_hp(dl, B, V, K, dm, dhp, dot_id, dd, gp.p<float>(), gi.p<int>(), gc.p<int>(), nullptr);
+  T_HIP(hipDeviceSynchronize());
+  T_CHECK(gp.down(probs)); T_CHECK(gi.down(idxs)); T_CHECK(gc.down(cand));
+  return launch_status(rc);
 }
 
 }  // extern "C"

@@ -3137,7 +3137,8 @@ const void* czc_internal_hooks(int abi) {
       &launch_gather_rows_f32, &launch_gather_rows_bytes, &launch_gather_rows_w32, &launch_mask_positions, &launch_mask_positions_rows,
       &launch_tie_rows, &launch_memo_check, &launch_memo_gather, &launch_memo_scatter, &launch_memo_fill, &launch_memo_rows_check,
       &launch_memo_rows_gather, &launch_memo_rows_scatter, &launch_memo_rows_fill,
-      &fluency_expand_tables, &launch_expand_mask_rows, &launch_logprob_target};
+      &fluency_expand_tables, &launch_expand_mask_rows, &launch_logprob_target,
+      &launch_bridge_rows, &launch_bridge_rows_hp, &launch_softmax_mask_topk_rows, &launch_softmax_mask_topk_rows_hp};
   return abi == HOOKS_ABI ? &h : nullptr;
 }
 

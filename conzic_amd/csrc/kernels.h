@@ -432,7 +432,7 @@ int launch_pll_sum(const float* logp, int R, int Lmax, const int* len_of_row, fl
 // ---- czc_internal_hooks (declared below, private to the build): what libconzic_hip_test.so may reach inside this library -----------
 // The product library has hidden visibility; the hook library (api_test.hip) gets the launchers it wraps and the
 // process-wide kernel-family switches it flips through this table instead of through exported C++ symbols.
-constexpr int HOOKS_ABI = 0x060a;
+constexpr int HOOKS_ABI = 0x060b;
 struct Hooks {
   char* (*err_buf)();  // the calling host thread's g_err [512]
   decltype(&launch_gemm) gemm;
@@ -496,6 +496,12 @@ struct Hooks {
   decltype(&fluency_expand_tables) fluency_expand_tables;
   decltype(&launch_expand_mask_rows) expand_mask_rows;
   decltype(&launch_logprob_target) logprob_target;
+  // the text bridge with candidates and the top-K selection in their per-row forms (tests/test_bridge_kernel_gpu.py against the
+  // string reference tests/bridge_ref.py, pinned by tests/test_bridge_ref_cpu.py; tests/test_topk_rows_gpu.py)
+  decltype(&launch_bridge_rows) bridge_rows;
+  decltype(&launch_bridge_rows_hp) bridge_rows_hp;
+  decltype(&launch_softmax_mask_topk_rows) softmax_mask_topk_rows;
+  decltype(&launch_softmax_mask_topk_rows_hp) softmax_mask_topk_rows_hp;
 };
 
 }  // namespace czc

@@ -195,6 +195,9 @@ TEST_SIGNATURES = {
     "czc_test_memo_rows_chain": (_I, [_I] * 12 + [_P] * 33),
     "czc_test_logprob": (_I, [_I, _I, _P, _P, C.c_float, _P, _P, _P]),
     "czc_test_expand_mask": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "czc_test_bridge_cand": (_I, [C.POINTER(BridgeTables), _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P,
+                                  _P, _P, _P, _P, _P]),
+    "czc_test_topk_rows": (_I, [_I, _I, _I, _I, _P, _P, C.c_float, _I, _P, _P, _P, _P, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

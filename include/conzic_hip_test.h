@@ -46,7 +46,7 @@ int czc_test_gemm_rowln(int precision, int M, int K, const float* A, const float
 int czc_bench_gemm(int precision, int M, int N, int K, int act, int out_mode, int iters, int use256, double* ms_out);
 /* Process-wide kernel-family switches for tests and tools: "gemm256" 0|1|3|5, "wreg" 0|1, "gemm256s" 0|1, "skinny",
  * "splitk", "gemm_deep" 0|1|2, "gemm_small_tiles", "mfma_attention", "attention_image" 0|1|2 (2 = force), the "*_min_m"
- * row-count thresholds, "wreg_stats_in_kernel", "bridge_no_table" (czc_test_bridge), "bench_pad" (row padding of
+ * row-count thresholds, "wreg_stats_in_kernel", "bridge_no_table" (czc_test_bridge, czc_test_bridge_cand), "bench_pad" (row padding of
  * czc_bench_gemm operands).  Any other name fails with CZC_ERR_ARG. */
 int czc_test_set_option(const char* name, int value);
 int czc_test_layernorm(int precision, int M, int H, const float* x, const float* gamma, const float* beta, float eps,
@@ -241,6 +241,27 @@ int czc_test_logprob(int N, int V, const float* logits, const int32_t* target, f
  * (the caller sizes them for N). */
 int czc_test_expand_mask(int R, int T, int seed_len, int mask_id, const int32_t* rows, const int32_t* len_of_row, int32_t* ids_out,
                          int32_t* target, int32_t* gen_rows, int32_t* n_seq);
+
+/* ---- the text bridge with candidates and the per-row forms of the top-K selection (csrc/bridge.hip, csrc/topk.hip; string-level
+ * reference in tests/bridge_ref.py).  EVERY OUTPUT ARRAY holds CZC_TEST_GUARD + n + CZC_TEST_GUARD 4-byte words, pre-filled with bytes
+ * 0x5a, and comes back raw.  A launcher's own refusal returns CZC_TEST_REFUSED with every output untouched. */
+/* bridge_kernel on inp [B, T] with column gen of row b replaced by cand [B, K] (one thread per candidate row):
+ *   form 0 launch_bridge (gen_idx; gen_rows, row_len, hp_rows are not passed on), 1 launch_bridge_rows (gen_rows [B], row_len [B] or
+ *   NULL, the scalar `negative`), 2 launch_bridge_rows_hp (hp_rows [B]: control / negative per row).
+ * Control tables, each may be NULL: lexicon [V]; lex_pos [V, 5] with lex_cls [V]; tag_of_token [V] with masks [n_masks].
+ * The bridge tables are uploaded, hashed and tabulated as czc_test_bridge does ("bridge_no_table" applies).  Checked on the host
+ * (CZC_ERR_ARG): every id of inp and cand inside the vocabulary, every gen inside the row, 1 <= row_len <= T <= CZC_MAX_BERT_LEN,
+ * lex_cls < 5, tags < 15.
+ * -> clip_ids [B*K, 77], clip_len, senti_raw, repeats [B*K], overflow [1] (zeroed first: the number of candidate rows that took the
+ * kernel's overflow path -- data, not an error status). */
+int czc_test_bridge_cand(const czc_bridge_tables* t, int form, int B, int T, int K, const int32_t* inp, int gen_idx, const int32_t* gen_rows,
+                         const int32_t* row_len, const int32_t* cand, const float* lexicon, const float* lex_pos, const uint8_t* lex_cls,
+                         const uint8_t* tag_of_token, const uint16_t* masks, int n_masks, int negative, const czc_hyper* hp_rows,
+                         int32_t* clip_ids, int32_t* clip_len, float* senti_raw, float* repeats, int32_t* overflow);
+/* softmax_mask_topk_kernel in its per-row forms on logits [B, V], mask [V]: form 1 launch_softmax_mask_topk_rows (temperature,
+ * dot_rows [B]), 2 launch_softmax_mask_topk_rows_hp (hp_rows [B]: the row's temperature; dot_rows [B]) -> probs, idxs, cand [B*K]. */
+int czc_test_topk_rows(int form, int B, int V, int K, const float* logits, const float* mask, float temperature, int dot_id,
+                       const int32_t* dot_rows, const czc_hyper* hp_rows, float* probs, int32_t* idxs, int32_t* cand);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

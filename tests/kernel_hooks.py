@@ -4,6 +4,12 @@ TEST INFRASTRUCTURE.  Each function runs ONE kernel family of the product librar
 compare it with the CPU oracle; nothing in conzic_amd/ imports this module and the product library exports none of the
 symbols behind it.  (Until round 5 these lived in conzic_amd/engine.py as test_*; the names lost the prefix here so that
 pytest does not collect them.)
+
+Families with a kernel-level test of their own: GEMM / LayerNorm / attention / top-K / bridge / combine (tests/test_kernels_gpu.py), the
+shared-prefix attention plans, the selection and plan kernels, the row / embedding / mover / memo kernels, the fluency kernels, and --
+at the end of this file -- the text bridge with candidates in its three forms (tests/test_bridge_kernel_gpu.py against the string
+reference tests/bridge_ref.py, pinned by tests/test_bridge_ref_cpu.py) and the per-row forms of the top-K selection
+(tests/test_topk_rows_gpu.py).
 """
 import ctypes as C
 
@@ -542,3 +548,54 @@ def memo_rows_chain(st, L, seed_len, n_mask0, n_sub, mask_id, j=0, stages=1, use
                 g.buf("tot", 4), g.buf("inp", R * T), g.buf("bcos", R, np.float32), g.buf("inp_c", R * T), g.buf("img_c", R * D, np.float32),
                 g.buf("col_c", R), g.buf("dot_c", R))
     return ref, g.done()
+
+
+# ---- the text bridge with candidates and the per-row forms of the top-K selection (czc_test_bridge_cand, czc_test_topk_rows) ---------
+# Compared with the string reference tests/bridge_ref.py (pinned by tests/test_bridge_ref_cpu.py) in tests/test_bridge_kernel_gpu.py,
+# and with an fp64 softmax in tests/test_topk_rows_gpu.py.
+def bridge_cand(tables: BridgeArrays, form, inp, gen, cand, row_len=None, lexicon=None, lex_pos=None, lex_cls=None, tag_of_token=None,
+                masks=None, negative=0, hyper=None, K=None):
+    """form 0 launch_bridge (gen: an int), 1 launch_bridge_rows, 2 launch_bridge_rows_hp (gen: [B] or None; hyper: list of native.Hyper
+    or None).  cand [B, K] or None (then K names the launch's K).  -> (refused, Guarded(clip_ids [B*K, 77], clip_len, senti_raw,
+    repeats [B*K], overflow [1]))"""
+    inp = _i32(inp)
+    B, T = inp.shape
+    cd = _i32(cand)
+    K = cd.shape[1] if cd is not None else int(K)
+    assert cd is None or cd.shape == (B, K)
+    rows = None if (form == 0 or gen is None) else _i32(gen)
+    rl = _i32(row_len)
+    lx = None if lexicon is None else _f32(lexicon)
+    lp = None if lex_pos is None else _f32(lex_pos)
+    lc = None if lex_cls is None else np.ascontiguousarray(lex_cls, np.uint8)
+    tg = None if tag_of_token is None else np.ascontiguousarray(tag_of_token, np.uint8)
+    mk = None if masks is None else np.ascontiguousarray(masks, np.uint16)
+    hp = (native.Hyper * B)(*hyper) if hyper is not None else None
+    st = tables.as_struct()
+    g = Guarded()
+    ref = _call("czc_test_bridge_cand", C.byref(st), int(form), B, T, K, inp.ctypes.data, int(gen) if form == 0 else 0, _ptr(rows), _ptr(rl),
+                _ptr(cd), _ptr(lx), _ptr(lp), _ptr(lc), _ptr(tg), _ptr(mk), 0 if mk is None else mk.size, int(negative),
+                C.cast(hp, C.c_void_p) if hp is not None else None,
+                g.buf("clip_ids", B * K * native.CLIP_MAX_LEN), g.buf("clip_len", B * K), g.buf("senti_raw", B * K, np.float32),
+                g.buf("repeats", B * K, np.float32), g.buf("overflow", 1))
+    g.done()
+    g["clip_ids"] = g["clip_ids"].reshape(B * K, native.CLIP_MAX_LEN)
+    return ref, g
+
+
+def topk_rows(form, logits, mask, K, dot_id, dot_rows, temperature=1.0, hyper=None):
+    """form 1 launch_softmax_mask_topk_rows (temperature, dot_rows [B]), 2 launch_softmax_mask_topk_rows_hp (hyper: list of
+    native.Hyper, dot_rows) -> (refused, Guarded(probs, idxs, cand [B, K]))"""
+    lg = _f32(logits)
+    mk = np.ascontiguousarray(np.asarray(mask, np.float32).reshape(-1))
+    B, V = lg.shape
+    dr = _i32(dot_rows)
+    hp = (native.Hyper * B)(*hyper) if hyper is not None else None
+    g = Guarded()
+    ref = _call("czc_test_topk_rows", int(form), B, V, int(K), lg.ctypes.data, mk.ctypes.data, float(temperature), int(dot_id), _ptr(dr),
+                C.cast(hp, C.c_void_p) if hp is not None else None, g.buf("probs", B * K, np.float32), g.buf("idxs", B * K),
+                g.buf("cand", B * K))
+    g.done()
+    for k in ("probs", "idxs", "cand"):
+        g[k] = g[k].reshape(B, K)
+    return ref, g

@@ -220,9 +220,9 @@ def test_device_bridge_overflow_fails_loudly():
     t = tables_from_tokenizers(bt, ct)
     longest = max(range(len(sv.bert_tokens)), key=lambda i: len(sv.bert_tokens[i].encode()))
     rows = np.full((1, 64), longest, np.int32)
-    if 64 * (len(sv.bert_tokens[longest].encode()) + 1) > 512:
-        with pytest.raises(native.NativeError, match="overflow"):
-            KH.bridge(t, rows)
+    assert 64 * (len(sv.bert_tokens[longest].encode()) + 1) - 1 > 512   # the construction: 64 words and their spaces pass the text buffer
+    with pytest.raises(native.NativeError, match="overflow"):
+        KH.bridge(t, rows)
 
 
 @pytest.mark.parametrize("senti", [False, True])

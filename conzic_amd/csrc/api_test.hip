@@ -1562,3 +1562,174 @@ int czc_test_topk_rows(int form, int B, int V, int K, const float* logits, const
 }
 
 }  // extern "C"
+
+// ---- czc_test_gemm_layout: one GEMM launch on strided, windowed and in-place buffers ----------------------------------------
+namespace {
+
+// A 2-D buffer of the layout hook: `rows` rows of `ld` elements of `es` bytes, CZC_TEST_LAYOUT_GUARD rows in front of them and
+// `back` rows behind them (to the end of the last 256-row tile and CZC_TEST_LAYOUT_GUARD more), every 32-bit word pre-filled.
+struct Padded {
+  unsigned char* base = nullptr;
+  size_t rows = 0, back = 0, ld = 0, es = 0;
+  size_t bytes() const { return (CZC_TEST_LAYOUT_GUARD + rows + back) * ld * es; }
+  unsigned char* at(size_t c0) const { return base + ((size_t)CZC_TEST_LAYOUT_GUARD * ld + c0) * es; }
+  int make(DevPool& pool, size_t rows_, size_t ld_, size_t es_, uint32_t fill) {
+    rows = rows_; ld = ld_; es = es_;
+    back = (256 - rows % 256) % 256 + CZC_TEST_LAYOUT_GUARD;
+    const size_t words = (bytes() + 3) / 4;
+    base = (unsigned char*)pool.alloc(words * 4); T_PTR(base);
+    T_HIP(hipMemsetD32((hipDeviceptr_t)base, (int)fill, words));
+    return 0;
+  }
+  // a dense [rows, width] device array of the same element type -> columns c0 .. c0 + width of the rows
+  int put(const void* dense, size_t width, size_t c0) const {
+    T_HIP(hipMemcpy2D(at(c0), ld * es, dense, width * es, width * es, rows, hipMemcpyDeviceToDevice));
+    return 0;
+  }
+  int down(void* host) const {
+    T_HIP(hipMemcpy(host, base, bytes(), hipMemcpyDeviceToHost));
+    return 0;
+  }
+};
+
+// quiet NaNs of an element type, as 32-bit words (fp16 planes for the split type)
+uint32_t nan_words(int prec) { return prec == PREC_F32 ? 0x7fc00000u : prec == PREC_BF16 ? 0x7fc07fc0u : 0x7e007e00u; }
+constexpr uint32_t SENTINEL_WORDS = 0x5a5a5a5au;
+
+// 0, CZC_TEST_REFUSED (the launcher refused: nothing ran) or a CZC_ERR_* status; *family = what the launcher recorded
+int gemm_layout_run(const czc_gemm_layout* c, int* family) {
+  const char* who = "gemm_layout";
+  const int P = c->precision, M = c->M, N = c->N, K = c->K, form = c->form;
+  const bool half = P == PREC_BF16 || P == PREC_F16;
+  const bool in_place = c->flags & CZC_GEMM_IN_PLACE, both = c->flags & CZC_GEMM_BOTH_OUTPUTS, typed = c->flags & CZC_GEMM_TYPED_OUT;
+  T_ARG(half || P == PREC_F32 || P == PREC_F16X3, who);
+  T_ARG(form >= CZC_GEMM_FORM_PLAIN && form <= CZC_GEMM_FORM_ROWLN && (form == CZC_GEMM_FORM_PLAIN || half), who);
+  T_ARG(M >= 1 && N >= 1 && K >= 1 && M <= (1 << 20) && N <= (1 << 16) && K <= (1 << 16) && c->A && c->W, who);
+  T_ARG(c->lda >= K && c->ldw >= K && c->c0 >= 0 && c->ldc >= c->c0 + N && c->lda <= 2 * K + 64 && c->ldw <= 2 * K + 64 && c->ldc <= 4 * N + 64, who);
+  T_ARG(!c->resid || (c->ldr >= c->c0 + N && c->ldr <= 4 * N + 64), who);
+  T_ARG(!in_place || (c->resid && c->ldr == c->ldc), who);
+  T_ARG(P != PREC_F16X3 || (K % 8 == 0 && c->lda % 8 == 0 && c->ldw % 8 == 0), who);  // whole hi / lo groups per row
+  const bool want_f32 = form == CZC_GEMM_FORM_X16 || form == CZC_GEMM_FORM_ROWLN || (form == CZC_GEMM_FORM_PLAIN && (!typed || both));
+  const bool want_act = form == CZC_GEMM_FORM_LNF || form == CZC_GEMM_FORM_ROWLN || (form == CZC_GEMM_FORM_PLAIN && (typed || both));
+  T_ARG((!want_f32 || c->out_f32) && (!want_act || c->out_act) && !(typed && both), who);
+  T_ARG(!in_place || want_f32, who);
+  T_ARG(P != PREC_F16X3 || !want_act || (c->ldc % 8 == 0 && c->c0 % 8 == 0), who);  // split_t rows: groups of 8 from the buffer's start
+  if (form == CZC_GEMM_FORM_X16) T_ARG(c->resid && K % 8 == 0 && (c->part_ld == 0 || (c->part_ld >= M && N % 32 == 0 && c->part_out)), who);
+  else T_ARG(c->part_ld == 0, who);
+  if (form == CZC_GEMM_FORM_LNF) T_ARG(K == 512 && c->bias && c->gamma && c->beta && c->ln_part && !c->resid, who);
+  if (form == CZC_GEMM_FORM_ROWLN) T_ARG(N == 512 && c->resid && c->gamma && c->beta, who);
+
+  DevPool pool;
+  const int a_prec = form == CZC_GEMM_FORM_LNF ? PREC_F16 : P;  // lnf: A is the raw fp16 residual stream
+  const size_t es = prec_bytes(P);
+  // operands: NaN pads and guards
+  Padded pA, pW, pR;
+  T_CHECK(pA.make(pool, M, c->lda, prec_bytes(a_prec), nan_words(a_prec)));
+  {
+    void* d = up_act(pool, a_prec, c->A, (size_t)M * K); T_PTR(d);
+    T_CHECK(pA.put(d, K, 0));
+  }
+  float* dB = nullptr;  // N entries, then a NaN tail the kernel must not read
+  auto up_bias = [&](const float* dev_or_host, hipMemcpyKind kind) -> int {
+    dB = (float*)pool.alloc((size_t)(N + 64) * 4); T_PTR(dB);
+    T_HIP(hipMemsetD32((hipDeviceptr_t)dB, (int)nan_words(PREC_F32), (size_t)N + 64));
+    T_HIP(hipMemcpy(dB, dev_or_host, (size_t)N * 4, kind));
+    return 0;
+  };
+  float* dstat = nullptr;
+  float* dpart_in = nullptr;
+  bool stats_in_kernel = false;
+  if (form == CZC_GEMM_FORM_LNF) {  // the preparation of czc_test_ln_fold_gemm, the folded weights then placed at ldw
+    T_CHECK(pW.make(pool, N, c->ldw, 2, nan_words(PREC_F16)));
+    float* dW = (float*)pool.up(c->W, (size_t)N * K * 4); T_PTR(dW);
+    float* dg = (float*)pool.up(c->gamma, (size_t)K * 4); T_PTR(dg);
+    float* dbt = (float*)pool.up(c->beta, (size_t)K * 4); T_PTR(dbt);
+    float* db = (float*)pool.up(c->bias, (size_t)N * 4); T_PTR(db);
+    dpart_in = (float*)pool.up(c->ln_part, (size_t)16 * M * 8); T_PTR(dpart_in);
+    dstat = (float*)pool.alloc((size_t)M * 8 + 256); T_PTR(dstat);
+    void* dWf = pool.alloc((size_t)N * K * 2); T_PTR(dWf);
+    float* dcs = (float*)pool.alloc((size_t)N * 4); T_PTR(dcs);
+    float* dbf = (float*)pool.alloc((size_t)N * 4); T_PTR(dbf);
+    stats_in_kernel = gemm_wreg_stats_in_kernel(M, N);
+    if (!stats_in_kernel) T_CHECK(launch_ln_finalize(dpart_in, M, 16, M, c->eps, dstat, nullptr));
+    T_CHECK(launch_fold_ln(dW, dg, dbt, db, N, K, dWf, dcs, dbf, nullptr));
+    T_HIP(hipDeviceSynchronize());
+    T_CHECK(pW.put(dWf, K, 0));
+    T_CHECK(up_bias(dbf, hipMemcpyDeviceToDevice));
+  } else {
+    T_CHECK(pW.make(pool, N, c->ldw, es, nan_words(P)));
+    void* d = up_act(pool, P, c->W, (size_t)N * K); T_PTR(d);
+    T_CHECK(pW.put(d, K, 0));
+    if (c->bias) T_CHECK(up_bias(c->bias, hipMemcpyHostToDevice));
+  }
+  // outputs: the 0x5a pattern everywhere; out_f32 holds fp16 rows in the x16 form
+  const size_t es_f = form == CZC_GEMM_FORM_X16 ? 2 : 4;
+  const int r_prec = form == CZC_GEMM_FORM_X16 ? PREC_F16 : PREC_F32;
+  Padded pF, pO;
+  if (want_f32) T_CHECK(pF.make(pool, M, c->ldc, es_f, SENTINEL_WORDS));
+  if (want_act) T_CHECK(pO.make(pool, M, c->ldc, es, SENTINEL_WORDS));
+  const void* resid_p = nullptr;
+  if (c->resid) {
+    void* d = up_act(pool, r_prec, c->resid, (size_t)M * N); T_PTR(d);
+    if (in_place) {
+      T_CHECK(pF.put(d, N, c->c0));
+      resid_p = pF.at(c->c0);
+    } else {
+      T_CHECK(pR.make(pool, M, c->ldr, es_f, nan_words(r_prec)));
+      T_CHECK(pR.put(d, N, c->c0));
+      resid_p = pR.at(c->c0);
+    }
+  }
+  Guarded gpart;
+  if (c->part_ld) T_CHECK(gpart.make(pool, (size_t)(N / 32) * c->part_ld * 2));
+  T_HIP(hipDeviceSynchronize());
+
+  GemmArgs g;
+  g.A = pA.at(0); g.lda = c->lda; g.W = pW.at(0); g.ldw = c->ldw; g.bias = dB;
+  g.resid = (const float*)resid_p; g.ldr = c->resid ? c->ldr : 0;
+  g.out_f32 = want_f32 ? (float*)pF.at(c->c0) : nullptr;
+  g.out_act = want_act ? (void*)pO.at(c->c0) : nullptr;
+  g.ldc = c->ldc; g.M = M; g.N = N; g.K = K; g.act = c->act;
+  int rc;
+  if (form == CZC_GEMM_FORM_ROWLN) {
+    float* dg = (float*)pool.up(c->gamma, (size_t)N * 4); T_PTR(dg);
+    float* dbt = (float*)pool.up(c->beta, (size_t)N * 4); T_PTR(dbt);
+    g.ln_gamma = dg; g.ln_beta = dbt; g.ln_eps = c->eps; g.f16 = P == PREC_F16;
+    rc = launch_gemm_rowln(g, nullptr);
+  } else {
+    if (form == CZC_GEMM_FORM_X16) {
+      g.x16 = 1;
+      if (c->part_ld) { g.row_part = gpart.p<float>(); g.part_ld = c->part_ld; }
+    }
+    if (form == CZC_GEMM_FORM_LNF) {
+      g.ln_stat = dstat;
+      if (stats_in_kernel) { g.ln_part = dpart_in; g.ln_part_ld = M; g.ln_eps = c->eps; }
+    }
+    rc = launch_gemm(P, g, nullptr);
+  }
+  *family = HK().gemm_family();
+  if (rc > 1) return CZC_ERR_HIP;
+  T_HIP(hipDeviceSynchronize());
+  if (want_f32) T_CHECK(pF.down(c->out_f32));
+  if (want_act) T_CHECK(pO.down(c->out_act));
+  if (c->part_ld) T_CHECK(gpart.down(c->part_out));
+  return rc == 1 ? CZC_TEST_REFUSED : 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int czc_test_gemm_family(void) { return HK().gemm_family(); }
+
+int czc_test_gemm_layout(const czc_gemm_layout* c) {
+  if (!c) { snprintf(TEST_ERR, 512, "gemm_layout: null argument"); return -CZC_ERR_ARG; }
+  int family = 0;
+  const int rc = gemm_layout_run(c, &family);
+  if (rc == CZC_TEST_REFUSED) return 0;
+  if (rc) return -rc;
+  if (family <= 0) { snprintf(TEST_ERR, 512, "gemm_layout: the launcher recorded no family"); return -CZC_ERR_STATE; }
+  return family;
+}
+
+}  // extern "C"

@@ -227,6 +227,9 @@ __host__ __device__ inline size_t prec_bytes(int p) { return prec_is_half(p) ? 2
   } while (0)
 
 extern thread_local char g_err[512];  // per host thread: two engines of an EngineGroup launch from two threads
+// the kernel family (kernels.h GemmFamily) that the calling thread's last launch_gemm / launch_gemm_rowln chose: one host store
+// per launch, read by the kernel-level tests only (a layout test must know which address code it exercised)
+extern thread_local int g_gemm_family;
 
 // One-time launch set-up of a kernel family (CU count, dynamic-LDS attributes), run by whichever host thread gets
 // there first behind a function-local static (C++11: initialised exactly once, other threads wait).

@@ -18,6 +18,7 @@
 
 namespace czc {
 thread_local char g_err[512] = {0};
+thread_local int g_gemm_family = 0;
 }
 using namespace czc;
 
@@ -3138,7 +3139,8 @@ const void* czc_internal_hooks(int abi) {
       &launch_tie_rows, &launch_memo_check, &launch_memo_gather, &launch_memo_scatter, &launch_memo_fill, &launch_memo_rows_check,
       &launch_memo_rows_gather, &launch_memo_rows_scatter, &launch_memo_rows_fill,
       &fluency_expand_tables, &launch_expand_mask_rows, &launch_logprob_target,
-      &launch_bridge_rows, &launch_bridge_rows_hp, &launch_softmax_mask_topk_rows, &launch_softmax_mask_topk_rows_hp};
+      &launch_bridge_rows, &launch_bridge_rows_hp, &launch_softmax_mask_topk_rows, &launch_softmax_mask_topk_rows_hp,
+      []() -> int { return czc::g_gemm_family; }};
   return abi == HOOKS_ABI ? &h : nullptr;
 }
 

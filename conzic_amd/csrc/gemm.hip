@@ -588,6 +588,7 @@ int launch_gemm(int prec, const GemmArgs& g_in, hipStream_t st) {
   GemmArgs g = g_in;
   g.f16 = prec == PREC_F16;
   if (g.splitk_pending) *g.splitk_pending = SplitkPending();
+  g_gemm_family = GF_NONE;
   if (g.M <= 0) return 0;
   const int kpt = prec_is_half(prec) ? Mma<bf16_t>::KPT : Mma<float>::KPT;  // split_t: 32 like float
   if (g.K % kpt != 0 || g.N <= 0) {
@@ -607,6 +608,7 @@ int launch_gemm(int prec, const GemmArgs& g_in, hipStream_t st) {
   if (prec_is_half(prec) && g_use_gemm256 && gemm256_eligible(g)) return launch_gemm256(g, st);
   if (prec == PREC_F16X3 && gemm256s_eligible(g)) return launch_gemm256s(g, st);
   if (prec == PREC_F16X3 && launch_skinny(g, st)) {
+    g_gemm_family = GF_SKINNY;
     CZC_HIP_CHECK(hipGetLastError());
     return 0;
   }
@@ -615,9 +617,11 @@ int launch_gemm(int prec, const GemmArgs& g_in, hipStream_t st) {
   int rc = 0;
   if (prec == PREC_F16X3 && try_splitk<split_t>(g, tiles_m, tiles_n, st, &rc)) {
     if (rc) return rc;
+    g_gemm_family = GF_SPLITK;
     CZC_HIP_CHECK(hipGetLastError());
     return 0;
   }
+  g_gemm_family = vec ? GF_TILED_VEC : GF_TILED_SCALAR;
   if (prec == PREC_BF16) launch_t<bf16_t>(g, tiles_m, tiles_n, vec, st);
   else if (prec == PREC_F16) launch_t<f16_t>(g, tiles_m, tiles_n, vec, st);
   else if (prec == PREC_F16X3) launch_t<split_t>(g, tiles_m, tiles_n, vec, st);

@@ -1248,6 +1248,7 @@ int launch_gemm_rowln(const GemmArgs& g, hipStream_t st) {
     return 0;
   });
   if (init.rc) return launch_init_failed("gemm_rowln");
+  g_gemm_family = GF_NONE;
   if (!gemm_rowln_eligible(g)) {
     snprintf(g_err, sizeof(g_err), "gemm_rowln: shape not eligible (M=%d N=%d K=%d)", g.M, g.N, g.K);
     return 1;
@@ -1259,6 +1260,7 @@ int launch_gemm_rowln(const GemmArgs& g, hipStream_t st) {
   const int stagger = tiles_m / (int)grid.x >= 4 ? (2 | 16 << 8) : 0;
   if (g.f16) hipLaunchKernelGGL(gemm_rowln_kernel<true>, grid, block, RL_LDS, st, g, g.ln_gamma, g.ln_beta, tiles_m, stagger);
   else hipLaunchKernelGGL(gemm_rowln_kernel<false>, grid, block, RL_LDS, st, g, g.ln_gamma, g.ln_beta, tiles_m, stagger);
+  g_gemm_family = GF_ROWLN;
   CZC_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -1295,6 +1297,7 @@ int launch_gemm256(const GemmArgs& g, hipStream_t st) {
   const bool f32 = g.out_f32 != nullptr || g.resid != nullptr;
   dim3 gq(tiles_m * tiles_n < n_cu ? tiles_m * tiles_n : n_cu);
   const bool pp = g_use_gemm256 == 5 || (g_use_gemm256 != 3 && f32);
+  g_gemm_family = (g.x16 || pp) ? GF_RING_PINGPONG : GF_RING_LOADER;
 #define CZC_GO(K_, A_, F_, H_, T_, ...) hipLaunchKernelGGL((K_<A_, F_, H_>), gq, dim3(T_), shp, st, g, tiles_m, tiles_n, ##__VA_ARGS__)
 #define CZC_DISPATCH(K_, T_, ...)                                                                                          \
   do {                                                                                                                     \
@@ -1347,6 +1350,7 @@ int launch_gemm256s(const GemmArgs& g, hipStream_t st) {
   const int tiles_m = cdiv(g.M, TM), tiles_n = cdiv(g.N, TN);
   dim3 grid(tiles_m * tiles_n < init.n_cu ? tiles_m * tiles_n : init.n_cu), block(768);
   const bool f32 = g.out_f32 != nullptr || g.resid != nullptr;
+  g_gemm_family = GF_RING_SPLIT;
 #define CZC_GOSQ(A_, F_) hipLaunchKernelGGL((gemm256sq_kernel<A_, F_>), grid, block, shp, st, g, tiles_m, tiles_n)
   if (g.act == ACT_QUICK_GELU) { if (f32) CZC_GOSQ(ACT_QUICK_GELU, true); else CZC_GOSQ(ACT_QUICK_GELU, false); }
   else { if (f32) CZC_GOSQ(ACT_NONE, true); else CZC_GOSQ(ACT_NONE, false); }

@@ -11,7 +11,8 @@
 //   * a work-group owns 256 output columns; each of its 8 waves keeps its 32 columns x 512 k of W
 //     in REGISTERS as 32 MFMA operand fragments (128 VGPRs) for the whole kernel.  The register
 //     file (512 KiB/CU) is the only on-CU memory that holds a 256 x 512 bf16 weight panel.
-//   * only activations stream: 32-row blocks (32 KiB, contiguous in HBM because lda == K) land in a
+//   * only activations stream: 32-row blocks (32 KiB; contiguous in HBM where lda == K, as in the tower, but each row is
+//     addressed by its own pitch `row * lda`, so any lda % 8 == 0 is served: tests/test_gemm_layout_gpu.py) land in a
 //     4-deep LDS ring by LDS-DMA, one full 1 KiB row per DMA instruction.  CU ingest is 1/256 byte
 //     per flop -- half of the tiled kernel -- and there is no weight traffic in steady state.
 //   * every wave multiplies every block against its own columns: one ds_read_b128 + one
@@ -669,6 +670,7 @@ int launch_gemm_wreg_resid(const GemmArgs& g, hipStream_t st) {
   int nsets = n_cu / ncg;
   if (nsets < 1) { snprintf(g_err, sizeof(g_err), "gemm_wreg_resid: N=%d needs more column groups than CUs", g.N); return 1; }
   if (nsets > nblk) nsets = nblk;
+  g_gemm_family = GF_WREG_RESID;
   dim3 grid(n_cu), block(512);
   if (g.f16) hipLaunchKernelGGL((gemm_wreg_resid_kernel<true>), grid, block, WRR_LDS, st, g, ncg, nsets, nblk);
   else hipLaunchKernelGGL((gemm_wreg_resid_kernel<false>), grid, block, WRR_LDS, st, g, ncg, nsets, nblk);
@@ -709,6 +711,7 @@ int launch_gemm_wreg(const GemmArgs& g, hipStream_t st) {
     snprintf(g_err, sizeof(g_err), "gemm_wreg: statistics in the kernel need at most %d row blocks per work-group (M=%d N=%d): gemm_wreg_stats_in_kernel()", WR_TS, g.M, g.N);
     return 1;
   }
+  g_gemm_family = g.ln_stat ? GF_WREG_LNF : GF_WREG;
   dim3 grid(n_cu), block(512);
 #define CZC_WR_GO(A_, H_) do { if (g.ln_stat) hipLaunchKernelGGL((gemm_wreg_kernel<A_, H_, true>), grid, block, WR_LDS_LNF, st, g, ncg, nsets, nblk); \
                                else hipLaunchKernelGGL((gemm_wreg_kernel<A_, H_>), grid, block, WR_LDS, st, g, ncg, nsets, nblk); } while (0)

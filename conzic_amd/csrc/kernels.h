@@ -49,6 +49,12 @@ struct GemmArgs {
   struct SplitkPending* splitk_pending = nullptr;
 };
 struct SplitkPending { const float* slabs = nullptr; int nslab = 0; long slab_stride = 0; int ld = 0; };
+// Which kernel family served the calling thread's last launch_gemm / launch_gemm_rowln (g_gemm_family, common.h); GF_NONE: the
+// launcher refused or M <= 0.  The values are part of include/conzic_hip_test.h (CZC_GEMM_FAMILY_*).
+enum GemmFamily {
+  GF_NONE = 0, GF_TILED_VEC = 1, GF_TILED_SCALAR = 2, GF_SPLITK = 3, GF_SKINNY = 4, GF_RING_LOADER = 5, GF_RING_PINGPONG = 6,
+  GF_RING_SPLIT = 7, GF_WREG = 8, GF_WREG_LNF = 9, GF_WREG_RESID = 10, GF_ROWLN = 11
+};
 int launch_gemm(int prec, const GemmArgs& g, hipStream_t st);
 bool gemm256_eligible(const GemmArgs& g);
 int launch_gemm256(const GemmArgs& g, hipStream_t st);  // gemm256.hip: 256x256 LDS-DMA ring kernels (bf16 / fp16 operands)
@@ -432,7 +438,7 @@ int launch_pll_sum(const float* logp, int R, int Lmax, const int* len_of_row, fl
 // ---- czc_internal_hooks (declared below, private to the build): what libconzic_hip_test.so may reach inside this library -----------
 // The product library has hidden visibility; the hook library (api_test.hip) gets the launchers it wraps and the
 // process-wide kernel-family switches it flips through this table instead of through exported C++ symbols.
-constexpr int HOOKS_ABI = 0x060b;
+constexpr int HOOKS_ABI = 0x060c;
 struct Hooks {
   char* (*err_buf)();  // the calling host thread's g_err [512]
   decltype(&launch_gemm) gemm;
@@ -502,6 +508,8 @@ struct Hooks {
   decltype(&launch_bridge_rows_hp) bridge_rows_hp;
   decltype(&launch_softmax_mask_topk_rows) softmax_mask_topk_rows;
   decltype(&launch_softmax_mask_topk_rows_hp) softmax_mask_topk_rows_hp;
+  // the family the calling thread's last GEMM launch chose (GemmFamily; tests/test_gemm_layout_gpu.py)
+  int (*gemm_family)();
 };
 
 }  // namespace czc

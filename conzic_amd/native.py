@@ -150,6 +150,15 @@ SIGNATURES = {
 # csrc/kernels.h; nothing in conzic_amd/ calls it)
 PRIVATE_SIGNATURES = {"czc_internal_hooks": (_P, [_I])}
 # every entry point include/conzic_hip_test.h declares (libconzic_hip_test.so)
+
+
+class GemmLayout(C.Structure):
+    """czc_gemm_layout (include/conzic_hip_test.h): one GEMM launch of czc_test_gemm_layout."""
+    _fields_ = ([(n, C.c_int32) for n in ("precision", "form", "M", "N", "K", "act", "lda", "ldw", "ldc", "ldr", "c0", "flags",
+                                          "part_ld")] + [("eps", C.c_float)] +
+                [(n, C.c_void_p) for n in ("A", "W", "bias", "resid", "gamma", "beta", "ln_part", "out_f32", "out_act", "part_out")])
+
+
 TEST_SIGNATURES = {
     "czc_test_gemm": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _I, _P]),
     "czc_test_gemm_x16": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
@@ -198,6 +207,8 @@ TEST_SIGNATURES = {
     "czc_test_bridge_cand": (_I, [C.POINTER(BridgeTables), _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P,
                                   _P, _P, _P, _P, _P]),
     "czc_test_topk_rows": (_I, [_I, _I, _I, _I, _P, _P, C.c_float, _I, _P, _P, _P, _P, _P]),
+    "czc_test_gemm_family": (_I, []),
+    "czc_test_gemm_layout": (_I, [C.POINTER(GemmLayout)]),
 }
 
 _lib: Optional[C.CDLL] = None

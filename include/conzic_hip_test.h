@@ -263,6 +263,61 @@ int czc_test_bridge_cand(const czc_bridge_tables* t, int form, int B, int T, int
 int czc_test_topk_rows(int form, int B, int V, int K, const float* logits, const float* mask, float temperature, int dot_id,
                        const int32_t* dot_rows, const czc_hyper* hp_rows, float* probs, int32_t* idxs, int32_t* cand);
 
+/* ---- every GEMM family on strided, windowed and in-place buffers (csrc/gemm.hip, gemm256.hip, gemm_wreg.hip; host reference and
+ * checker in tests/gemm_layout.py).  The kernel family a launch went to is recorded by the launcher (csrc/kernels.h GemmFamily): */
+#define CZC_GEMM_FAMILY_NONE 0 /* nothing launched */
+#define CZC_GEMM_FAMILY_TILED_VEC 1
+#define CZC_GEMM_FAMILY_TILED_SCALAR 2
+#define CZC_GEMM_FAMILY_SPLITK 3
+#define CZC_GEMM_FAMILY_SKINNY 4
+#define CZC_GEMM_FAMILY_RING_LOADER 5
+#define CZC_GEMM_FAMILY_RING_PINGPONG 6
+#define CZC_GEMM_FAMILY_RING_SPLIT 7
+#define CZC_GEMM_FAMILY_WREG 8
+#define CZC_GEMM_FAMILY_WREG_LNF 9
+#define CZC_GEMM_FAMILY_WREG_RESID 10
+#define CZC_GEMM_FAMILY_ROWLN 11
+/* the family of the calling thread's last czc_test_gemm* / czc_bench_gemm launch */
+int czc_test_gemm_family(void);
+
+#define CZC_GEMM_FORM_PLAIN 0 /* launch_gemm: out_f32 (default), out_act (TYPED_OUT) or both (BOTH_OUTPUTS) */
+#define CZC_GEMM_FORM_X16 1   /* launch_gemm on the 2-byte residual stream: resid / out_f32 are fp16 rows; optional row_part */
+#define CZC_GEMM_FORM_LNF 2   /* folded LayerNorm, prepared exactly as czc_test_ln_fold_gemm prepares it (K = 512, out_act) */
+#define CZC_GEMM_FORM_ROWLN 3 /* launch_gemm_rowln (N = ldc = 512): out_f32 = x and out_act = LayerNorm(x) */
+#define CZC_GEMM_IN_PLACE 1     /* resid and out_f32 are ONE buffer (ldr == ldc) */
+#define CZC_GEMM_BOTH_OUTPUTS 2 /* plain form: out_f32 and out_act from one launch */
+#define CZC_GEMM_TYPED_OUT 4    /* plain form: out_act only */
+#define CZC_TEST_LAYOUT_GUARD 8 /* guard rows in front of every 2-D buffer of the hook */
+/* One GEMM launch whose every leading dimension, output window and aliasing the caller chooses.  Host inputs are DENSE fp32
+ * arrays; the hook rounds them to the operand type on the device and places them in its own padded buffers:
+ *   rows r of a [rows, width] array sit at elements (CZC_TEST_LAYOUT_GUARD + r) * ld + c0 .. + width of a buffer of
+ *   CZC_TEST_LAYOUT_GUARD + rows + back(rows) rows of ld elements, back(rows) = (256 - rows % 256) % 256 + CZC_TEST_LAYOUT_GUARD
+ *   (the guard behind the rows reaches past the end of the last 256-row tile).
+ * A [M, K] at lda, W [N, K] at ldw and a residual that has a buffer of its own ([M, N] at ldr, c0 columns into its rows) are
+ * OPERANDS: every pad column and guard row holds the quiet-NaN pattern of the element type.  out_f32 and out_act are OUTPUTS
+ * ([M, N] at ldc, c0 columns into their rows): every byte pre-filled with 0x5a, and the WHOLE buffer (guards, pads, window) comes
+ * back raw in its element type (out_f32: fp32, or fp16 in the x16 form; out_act: the operand type of `precision`), bytes()
+ * = rows_total * ldc * element size.  IN_PLACE: the residual is written into the output buffer's owned elements instead (the
+ * rest of that buffer keeps the 0x5a pattern).  bias [N] is passed as it stands (the caller windows W and bias by choosing them).
+ *   x16: part_ld > 0 asks for row_part [N / 32][part_ld] float2; part_out receives CZC_TEST_GUARD + N / 32 * part_ld * 2 +
+ *        CZC_TEST_GUARD words, 0x5a-filled first.
+ *   lnf: A = x (fp16 rows), W / bias / gamma / beta fp32 folded by fold_ln_kernel, statistics from ln_part [16][M][2] through
+ *        ln_finalize_kernel, or inside the GEMM where gemm_wreg_stats_in_kernel(M, N) allows (option "wreg_stats_in_kernel").
+ *   rowln: gamma / beta [512]; the caller sets "rowln_min_m".
+ * Which kernel serves the launch follows the shape and the czc_test_set_option switches, as in the product.
+ * Returns the CZC_GEMM_FAMILY_* that served the launch (> 0), 0 when the launcher refused it (nothing ran, every output is the
+ * untouched pattern, the calling thread's last-error text says why), or -CZC_ERR_* for a failure of the hook itself. */
+typedef struct czc_gemm_layout {
+  int32_t precision, form, M, N, K, act;
+  int32_t lda, ldw, ldc, ldr;
+  int32_t c0, flags, part_ld;
+  float eps;
+  const float *A, *W, *bias, *resid, *gamma, *beta, *ln_part;
+  void *out_f32, *out_act;
+  float* part_out;
+} czc_gemm_layout;
+int czc_test_gemm_layout(const czc_gemm_layout* c);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -6,10 +6,15 @@ symbols behind it.  (Until round 5 these lived in conzic_amd/engine.py as test_*
 pytest does not collect them.)
 
 Families with a kernel-level test of their own: GEMM / LayerNorm / attention / top-K / bridge / combine (tests/test_kernels_gpu.py), the
-shared-prefix attention plans, the selection and plan kernels, the row / embedding / mover / memo kernels, the fluency kernels, and --
-at the end of this file -- the text bridge with candidates in its three forms (tests/test_bridge_kernel_gpu.py against the string
-reference tests/bridge_ref.py, pinned by tests/test_bridge_ref_cpu.py) and the per-row forms of the top-K selection
-(tests/test_topk_rows_gpu.py).
+shared-prefix attention plans, the selection and plan kernels, the row / embedding / mover / memo kernels, the fluency kernels, the
+text bridge with candidates in its three forms (tests/test_bridge_kernel_gpu.py against the string reference tests/bridge_ref.py,
+pinned by tests/test_bridge_ref_cpu.py), the per-row forms of the top-K selection (tests/test_topk_rows_gpu.py), and -- at the end
+of this file -- every GEMM family on strided, windowed and in-place buffers (gemm_layout: tests/test_gemm_layout_gpu.py, with the
+cases, the fp64 reference and the checker in tests/gemm_layout.py, pinned by tests/test_gemm_layout_cpu.py).
+
+Three kinds of guarded result: the attention-plan hooks return their guard rows beside the rows (PLAN_GUARD, PLAN_SENTINEL);
+the integer / row / bridge hooks return a Guarded (GUARD words around every 1-D output, untouched()); gemm_layout returns a
+gemm_layout.Launch (whole 2-D output buffers, guard rows and pad columns included) plus the kernel family the launcher chose.
 """
 import ctypes as C
 
@@ -599,3 +604,41 @@ def topk_rows(form, logits, mask, K, dot_id, dot_rows, temperature=1.0, hyper=No
     for k in ("probs", "idxs", "cand"):
         g[k] = g[k].reshape(B, K)
     return ref, g
+
+
+# ---- every GEMM family on strided, windowed and in-place buffers (czc_test_gemm_layout; host side in tests/gemm_layout.py) ---------
+
+def gemm_layout(case, data, eps=1e-5):
+    """One GEMM launch of a gemm_layout.Case on the dense fp32 inputs `data` (gemm_layout.make_data) -> (launch, family):
+    launch = gemm_layout.Launch, the Guarded of these hooks in two dimensions (name -> the WHOLE raw output buffer with its guard
+    rows and pad columns, .part / .part_guards for the x16 form's row_part); family = the CZC_GEMM_FAMILY_* the launcher reported,
+    0 when it refused the launch (nothing ran: every output is the untouched pattern)."""
+    import gemm_layout as GL
+    lib = native.load_test()
+    c = case.filled()
+    launch = GL.Launch(c)
+    keep = {}
+
+    def arr(name, need=True):
+        if not need:
+            return None
+        keep[name] = np.ascontiguousarray(data[name], np.float32)
+        return keep[name].ctypes.data
+
+    for name, kind in c.outputs().items():
+        launch[name] = np.zeros((launch.total_rows(), c.ldc * GL.ELEM_BYTES[kind]), np.uint8)
+    part = np.zeros(2 * GUARD + c.N // 32 * c.part_ld * 2, np.float32) if c.part_ld else None
+    s = native.GemmLayout(precision=c.prec, form=c.form, M=c.M, N=c.N, K=c.K, act=c.act, lda=c.lda, ldw=c.ldw, ldc=c.ldc, ldr=c.ldr,
+                          c0=c.c0, flags=c.flags, part_ld=c.part_ld, eps=float(eps), A=arr("A"), W=arr("W"), bias=arr("bias", c.bias),
+                          resid=arr("resid", c.has_resid), gamma=arr("gamma", c.form in (GL.LNF, GL.ROWLN)),
+                          beta=arr("beta", c.form in (GL.LNF, GL.ROWLN)), ln_part=arr("ln_part", c.form == GL.LNF),
+                          out_f32=launch["out_f32"].ctypes.data if "out_f32" in launch else None,
+                          out_act=launch["out_act"].ctypes.data if "out_act" in launch else None, part_out=_ptr(part))
+    rc = lib.czc_test_gemm_layout(C.byref(s))
+    if rc < 0:
+        native.check(-rc, None, "czc_test_gemm_layout")
+    launch.family = rc
+    if part is not None:
+        launch.part = part[GUARD:part.size - GUARD].reshape(c.N // 32, c.part_ld, 2)
+        launch.part_guards = np.concatenate([part[:GUARD], part[part.size - GUARD:]])
+    return launch, rc

@@ -1561,6 +1561,35 @@ int czc_test_topk_rows(int form, int B, int V, int K, const float* logits, const
   return launch_status(rc);
 }
 
+int czc_test_topk_rows_vocab(int B, int V, int K, const float* logits, const float* mask, int dot_id, const int32_t* dot_rows,
+                             const czc_hyper* hp_rows, const int32_t* set_rows, const uint32_t* bits, int n_sets, int W, float* probs,
+                             int32_t* idxs, int32_t* cand) {
+  const char* who = "topk_rows_vocab";
+  T_ARG(B >= 1 && B <= (1 << 14) && V >= 1 && K >= 1 && logits && mask && probs && idxs && cand, who);
+  T_ARG(n_sets >= 0 && n_sets <= (1 << 12) && W >= 0 && W <= (1 << 16), who);
+  // every index the kernel follows, checked here: nothing out of bounds reaches the launch (the launcher checks W against V, and
+  // refuses a null pointer before anything is read)
+  T_ARG(!set_rows || !bits || all_in(set_rows, B, -1, n_sets), who);
+  T_ARG(!bits || (n_sets >= 1 && W >= 1), who);
+  DevPool pool;
+  float* dl = (float*)pool.up(logits, (size_t)B * V * 4); T_PTR(dl);
+  float* dm = (float*)pool.up(mask, (size_t)V * 4); T_PTR(dm);
+  int *dd = nullptr, *ds = nullptr;
+  unsigned* db = nullptr;
+  RowHyper* dhp = nullptr;
+  if (dot_rows) { dd = (int*)pool.up(dot_rows, (size_t)B * 4); T_PTR(dd); }
+  if (hp_rows) { dhp = (RowHyper*)pool.up(hp_rows, (size_t)B * sizeof(czc_hyper)); T_PTR(dhp); }
+  if (set_rows) { ds = (int*)pool.up(set_rows, (size_t)B * 4); T_PTR(ds); }
+  if (bits) { db = (unsigned*)pool.up(bits, (size_t)n_sets * W * 4); T_PTR(db); }
+  Guarded gp, gi, gc;
+  const size_t bk = (size_t)B * K;
+  T_CHECK(gp.make(pool, bk)); T_CHECK(gi.make(pool, bk)); T_CHECK(gc.make(pool, bk));
+  const int rc = HK().softmax_mask_topk_rows_vocab(dl, B, V, K, dm, dhp, dot_id, dd, ds, db, W, gp.p<float>(), gi.p<int>(), gc.p<int>(), nullptr);
+  T_HIP(hipDeviceSynchronize());
+  T_CHECK(gp.down(probs)); T_CHECK(gi.down(idxs)); T_CHECK(gc.down(cand));
+  return launch_status(rc);
+}
+
 }  // extern "C"
 
 // ---- czc_test_gemm_layout: one GEMM launch on strided, windowed and in-place buffers ----------------------------------------

@@ -59,11 +59,15 @@ struct ProfKind {
 // hp: czc_generate_rows_hp's hyper-parameters.  draw + step: czc_generate_rows_draw's records and the step's index in the call's
 // schedule (the Philox counter is the record's step0 + step).  rival [rows, M] + delta [rows]: czc_generate_rows_vs' table and
 // deltas; the indices point into img_all, the whole normalised resident batch of n_img images, which a compact batch leaves alone.
+// vset [rows] + vbits [n_sets, vwords]: czc_generate_rows_vocab's set index of every row (-1: none) and the call's bitsets, which a
+// compact batch leaves alone too; vhp [rows]: the records the top-K kernel reads the temperature from where the call's entries were
+// all equal and hp is null (equal entries, so a compact batch takes its first rows as they are).
 struct RowRecords {
   const RowHyper* hp = nullptr;
   const RowDraw* draw = nullptr; unsigned step = 0;
   const int* rival = nullptr; const float* delta = nullptr; int M = 0;
   const float* img_all = nullptr; int n_img = 0;
+  const int* vset = nullptr; const unsigned* vbits = nullptr; int vwords = 0; const RowHyper* vhp = nullptr;
 };
 
 }  // namespace
@@ -865,7 +869,9 @@ int step_phase_a(czc_engine* e, const StepArgs& a) {
   StepBufs b;
   E_CHECK(step_bufs(e, a.B * a.K, &b));
   { ProfScope ps(e, "topk", 0);
-    if (e->rec.hp) E_CHECK(launch_softmax_mask_topk_rows_hp(logits, a.B, c.bert_vocab, a.K, e->d_mask, e->rec.hp, c.dot_id, a.dot_rows,
+    if (e->rec.vset) E_CHECK(launch_softmax_mask_topk_rows_vocab(logits, a.B, c.bert_vocab, a.K, e->d_mask, e->rec.hp ? e->rec.hp : e->rec.vhp, c.dot_id,
+                                                                 a.dot_rows, e->rec.vset, e->rec.vbits, e->rec.vwords, b.probs, b.idxs, b.cand, e->st));
+    else if (e->rec.hp) E_CHECK(launch_softmax_mask_topk_rows_hp(logits, a.B, c.bert_vocab, a.K, e->d_mask, e->rec.hp, c.dot_id, a.dot_rows,
                                                              b.probs, b.idxs, b.cand, e->st));
     else if (a.dot_rows) E_CHECK(launch_softmax_mask_topk_rows(logits, a.B, c.bert_vocab, a.K, e->d_mask, hp->temperature, c.dot_id, a.dot_rows,
                                                           b.probs, b.idxs, b.cand, e->st));
@@ -1093,7 +1099,7 @@ void free_layer_set(std::vector<LayerW>& L) {
 // arrays it has; a check_* function validates one array and drops it (null) where it carries nothing, so below them "the call has
 // per-row lengths / records / draws / groups / rivals" is a fact of the struct.  A new per-row argument: a field, a check_*
 // function, an upload in upload_call and, if kernels read it at every step, a RowRecords entry.
-enum CallLevel { CALL_GENERATE, CALL_ROWS, CALL_FROM, CALL_LEN, CALL_HP, CALL_DRAW, CALL_TIED, CALL_VS };
+enum CallLevel { CALL_GENERATE, CALL_ROWS, CALL_FROM, CALL_LEN, CALL_HP, CALL_DRAW, CALL_TIED, CALL_VS, CALL_VOCAB };
 struct RowsCall {
   CallLevel level = CALL_GENERATE;
   bool rows = false, from = false;  // per-row positions and images / a start row per row and idle positions
@@ -1102,7 +1108,9 @@ struct RowsCall {
   const czc_hyper *hp = nullptr, *hp_rows = nullptr;  // the call's one record (with per-row records [R]: their entry 0)
   const czc_draw* draw = nullptr;                     // [R]
   const int32_t* rival = nullptr; int M = 0; const float* delta = nullptr;  // [R, M], [R]
+  const uint32_t* sets = nullptr; int n_sets = 0; const int32_t* vset = nullptr;  // [n_sets, ceil(bert_vocab / 32)], [R]
   int32_t* out_ids = nullptr; float* out_cos = nullptr;
+  std::vector<czc_hyper> vocab_hp;  // upload_call: the R equal records of a vocabulary call whose own were dropped as uniform
   std::vector<czc_draw> no_draw;  // check_rival_table: the tau = 0 records of a rival call that brought none
   size_t n_pos() const { return rows ? (size_t)n_steps * R : (size_t)n_steps; }
   int n_mask_at(int s) const { return n_mask ? n_mask[s] : 1; }
@@ -1252,7 +1260,7 @@ struct MemoRowsPlan {
   int *hit = nullptr, *cnt = nullptr, *list = nullptr, *tot = nullptr, *inp_c = nullptr, *col_c = nullptr, *dot_c = nullptr;
   float *bcos = nullptr, *img_c = nullptr;
   // room for the RowRecords of a compact batch's rows, gathered by its run list (a record the call does not carry has none)
-  struct { RowHyper* hp = nullptr; RowDraw* draw = nullptr; int* rival = nullptr; float* delta = nullptr; } rec_c;
+  struct { RowHyper* hp = nullptr; RowDraw* draw = nullptr; int* rival = nullptr; float* delta = nullptr; int* vset = nullptr; } rec_c;
   std::vector<std::vector<int32_t>> h_col_c;  // compact batch of the group in progress: the active rows' column at every step
   std::vector<int32_t> run_h;    // of the group in progress: the rows that run, ascending (host copy of list_d)
   const int* list_d = nullptr;   // of the group in progress: the device list of the rows that run (null: every row)
@@ -1364,6 +1372,11 @@ int memo_rows_records(czc_engine* e, const MemoRowsPlan& mp, int n_act, RowRecor
     E_CHECK(launch_gather_rows_w32(full.rival, mp.list_d, n_act, full.M, mp.rec_c.rival, e->st));
     E_CHECK(launch_gather_rows_w32(full.delta, mp.list_d, n_act, 1, mp.rec_c.delta, e->st));
     out->rival = mp.rec_c.rival; out->delta = mp.rec_c.delta;
+  }
+  if (full.vset) {  // (the bitsets stay where they are, like img_all)
+    if (!mp.rec_c.vset || !mp.list_d) return fail(e, CZC_ERR_STATE, "generate_rows_vocab: a compact batch without room for its set indices%s");
+    E_CHECK(launch_gather_rows_w32(full.vset, mp.list_d, n_act, 1, mp.rec_c.vset, e->st));
+    out->vset = mp.rec_c.vset;
   }
   return 0;
 }
@@ -1558,7 +1571,7 @@ int tie_score(czc_engine* e, const TiePlan& tp, const int* d_inp, int R, int T, 
 // =================================================================================================
 extern "C" {
 
-int czc_version(void) { return 107; }
+int czc_version(void) { return 108; }
 
 const char* czc_last_error(const czc_engine* e) { return e ? e->err : czc::g_err; }
 
@@ -2307,7 +2320,7 @@ struct CallScope {
 
 // The uploads of a call: the start rows and, for a rows call, the schedule, the per-row records (e->rec from here on) and the
 // gather of the rows' image embeddings, which then stand in for the resident batch (inside a CallScope)
-static int upload_call(czc_engine* e, const RowsCall& c, Sched& sc, int** d_inp) {
+static int upload_call(czc_engine* e, RowsCall& c, Sched& sc, int** d_inp) {
   const int B = c.R, T = c.T, D = e->cfg.clip_proj;
   auto put = [e](const char* name, const void* src, size_t bytes, void** out) -> int {
     E_CHECK(ensure(e, name, bytes, out));
@@ -2338,6 +2351,15 @@ static int upload_call(czc_engine* e, const RowsCall& c, Sched& sc, int** d_inp)
     E_CHECK(put("g_rival", c.rival, (size_t)B * c.M * 4, (void**)&rec.rival));
     E_CHECK(put("g_rdelta", c.delta, (size_t)B * 4, (void**)&rec.delta));
     rec.M = c.M; rec.img_all = e->d_img_n; rec.n_img = e->img_B;
+  }
+  if (c.vset) {  // the whole table of bitsets and an index per row; the top-K kernel of a set call reads its temperature per row
+    rec.vwords = (e->cfg.bert_vocab + 31) / 32;
+    E_CHECK(put("g_vset", c.vset, (size_t)B * 4, (void**)&rec.vset));
+    E_CHECK(put("g_vbits", c.sets, (size_t)c.n_sets * rec.vwords * 4, (void**)&rec.vbits));
+    if (!c.hp_rows) {
+      c.vocab_hp.assign((size_t)B, *c.hp);
+      E_CHECK(put("g_vhp", c.vocab_hp.data(), (size_t)B * sizeof(RowHyper), (void**)&rec.vhp));
+    }
   }
   e->rec = rec;
   // the embedding of row r is that of image image_of_row[r] -- one gather of the normalised embeds to [R, D] here, and the step
@@ -2372,6 +2394,21 @@ static int run_steps(czc_engine* e, const RowsCall& c, const Sched& sc, int* d_i
       audit[s] = (snap_idx && (s / snapshot_every) % 4 == 0) || (s + 1 == n_steps && !audited);
       audited = audited || audit[s];
     } }
+  // The steps whose winner cosine this call returns: the snapshot steps and, in a call with idle steps, every step after which
+  // some row sits out the rest of its snapshot interval -- that row's cosine at the snapshot is the one this step leaves, so a
+  // gated row re-encodes its winner here as it does at a snapshot step (a row then returns the exact tower's cosine whether
+  // or not its companions run longer than it does)
+  std::vector<char> cos_step(n_steps, 0);
+  if (out_cos) {
+    std::vector<char> later(rows && sc.at.idle ? B : 0, 1);  // the row runs again before the coming snapshot (none comes: nothing is returned)
+    for (int s = n_steps - 1; s >= 0; --s) {
+      const bool snap_idx = (s + 1) % snapshot_every == 0;
+      cos_step[s] = snap_idx;
+      if (snap_idx) std::fill(later.begin(), later.end(), 0);
+      for (size_t r = 0; r < later.size(); ++r)
+        if (c.positions[(size_t)s * B + r] != CZC_POS_IDLE) { cos_step[s] = cos_step[s] || !later[r]; later[r] = 1; }
+    }
+  }
   MemoPlan mp;
   const bool memo = e->memo && !rows;  // the memo's keys are (image, position, n_mask); a rows call has option "memo_rows"
   if (memo) E_CHECK(memo_begin(e, c, audit, &mp));
@@ -2393,6 +2430,7 @@ static int run_steps(czc_engine* e, const RowsCall& c, const Sched& sc, int* d_i
     E_CHECK(ensure(e, "mr_riv_c", (size_t)B * c.M * 4, (void**)&mrp.rec_c.rival));
     E_CHECK(ensure(e, "mr_rdelta_c", (size_t)B * 4, (void**)&mrp.rec_c.delta));
   }
+  if (memo_rows && e->rec.vset) E_CHECK(ensure(e, "mr_vset_c", (size_t)B * 4, (void**)&mrp.rec_c.vset));
   // czc_generate_rows_tied (check_groups has run): the group table goes up once, behind the schedule
   TiePlan tie;
   const bool tied = c.group != nullptr && n_steps > 0;
@@ -2406,7 +2444,7 @@ static int run_steps(czc_engine* e, const RowsCall& c, const Sched& sc, int* d_i
     const int nm = c.n_mask_at(s), dot = pos == L - 1 ? 1 : 0;
     const bool snap_idx = (s + 1) % snapshot_every == 0;
     e->gate_now = e->refine && e->refine_gate_delta > 0.f && e->refine_guard_dev > 0.f && !audit[s];
-    e->gate_need_cos = snap_idx && out_cos != nullptr;
+    e->gate_need_cos = cos_step[s] != 0;
     e->in_generate = true;
     e->rec.step = (unsigned)s;
     if (memo_rows) E_CHECK(memo_rows_step(e, mrp, c, sc, s, d_inp));
@@ -2431,7 +2469,7 @@ static int run_steps(czc_engine* e, const RowsCall& c, const Sched& sc, int* d_i
   return 0;
 }
 
-static int generate_impl(czc_engine* e, const RowsCall& c) {
+static int generate_impl(czc_engine* e, RowsCall& c) {
   bool any_idle = false;
   if (int rc = check_call(e, c, &any_idle)) return rc;
   Sched sc = build_schedule(c, any_idle);
@@ -2610,9 +2648,27 @@ static int check_rival_table(czc_engine* e, RowsCall& c) {
   return 0;
 }
 
+// sets + vset (czc_generate_rows_vocab, vset not null): no row with a set is czc_generate_rows_vs itself
+static int check_vocab(czc_engine* e, RowsCall& c) {
+  if (!e || c.R <= 0) return CZC_ERR_ARG;
+  e->err[0] = 0;
+  if (c.R > CZC_MAX_ROWS) return fail(e, CZC_ERR_ARG, "generate_rows_vocab: R > CZC_MAX_ROWS%s");
+  if (c.n_sets < 1) return fail(e, CZC_ERR_ARG, "generate_rows_vocab: n_sets < 1 with a set_of_row array%s");
+  if (c.n_sets > CZC_MAX_VOCAB_SETS) return fail(e, CZC_ERR_ARG, "generate_rows_vocab: n_sets > CZC_MAX_VOCAB_SETS%s");
+  bool any = false;
+  for (int r = 0; r < c.R; ++r) {
+    if (c.vset[r] < -1 || c.vset[r] >= c.n_sets) return fail(e, CZC_ERR_ARG, "generate_rows_vocab: a set_of_row index outside [-1, n_sets)%s");
+    any = any || c.vset[r] >= 0;
+  }
+  if (any && !c.sets) return fail(e, CZC_ERR_ARG, "generate_rows_vocab: sets is NULL and a set_of_row index is >= 0%s");
+  if (!any) c.vset = nullptr;
+  return 0;
+}
+
 // The driver: the checks of the arrays the entry point has, outermost argument first, then the call itself
 static int run_call(czc_engine* e, RowsCall& c) {
   int rc = 0;
+  if (c.level >= CALL_VOCAB && c.vset && (rc = check_vocab(e, c))) return rc;
   if (c.level >= CALL_VS && c.rival && (rc = check_rival_table(e, c))) return rc;
   if (c.level >= CALL_TIED && c.group && (rc = check_groups(e, c))) return rc;
   if (c.level >= CALL_DRAW && (rc = check_draws(e, c))) return rc;
@@ -2698,6 +2754,18 @@ int czc_generate_rows_vs(czc_engine* e, int R, int T, int seed_len, const int32_
   RowsCall c = new_call(CALL_VS, R, T, seed_len, top_k, n_steps, snapshot_every, out_ids, out_cos);
   c.init = init_rows_host; c.len = len_of_row_host; c.image_of_row = image_of_row_host; c.positions = positions_host; c.n_mask = n_mask_host;
   c.hp_rows = hp_of_row_host; c.draw = draw_of_row_host; c.group = group_of_row_host; c.rival = rival_of_row_host; c.M = M; c.delta = delta_of_row_host;
+  return run_call(e, c);
+}
+
+int czc_generate_rows_vocab(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host, const int32_t* len_of_row_host,
+                            const int32_t* image_of_row_host, const int32_t* group_of_row_host, int top_k, int n_steps,
+                            const int32_t* positions_host, const int32_t* n_mask_host, int snapshot_every, const czc_hyper* hp_of_row_host,
+                            const czc_draw* draw_of_row_host, const int32_t* rival_of_row_host, int M, const float* delta_of_row_host,
+                            const uint32_t* sets_host, int n_sets, const int32_t* set_of_row_host, int32_t* out_ids, float* out_cos) {
+  RowsCall c = new_call(CALL_VOCAB, R, T, seed_len, top_k, n_steps, snapshot_every, out_ids, out_cos);
+  c.init = init_rows_host; c.len = len_of_row_host; c.image_of_row = image_of_row_host; c.positions = positions_host; c.n_mask = n_mask_host;
+  c.hp_rows = hp_of_row_host; c.draw = draw_of_row_host; c.group = group_of_row_host; c.rival = rival_of_row_host; c.M = M; c.delta = delta_of_row_host;
+  c.sets = sets_host; c.n_sets = n_sets; c.vset = set_of_row_host;
   return run_call(e, c);
 }
 
@@ -3140,6 +3208,7 @@ const void* czc_internal_hooks(int abi) {
       &launch_memo_rows_gather, &launch_memo_rows_scatter, &launch_memo_rows_fill,
       &fluency_expand_tables, &launch_expand_mask_rows, &launch_logprob_target,
       &launch_bridge_rows, &launch_bridge_rows_hp, &launch_softmax_mask_topk_rows, &launch_softmax_mask_topk_rows_hp,
+      &launch_softmax_mask_topk_rows_vocab,
       []() -> int { return czc::g_gemm_family; }};
   return abi == HOOKS_ABI ? &h : nullptr;
 }

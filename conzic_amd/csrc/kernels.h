@@ -257,6 +257,11 @@ int launch_softmax_mask_topk_rows(const float* logits, int B, int V, int K, cons
 // the per-row form with the row's own temperature: hp_rows[b].temperature (device, [B]) in place of temperature
 int launch_softmax_mask_topk_rows_hp(const float* logits, int B, int V, int K, const float* mask, const RowHyper* hp_rows, int dot_id,
                                      const int* dot_rows, float* probs, int* idxs, int* cand, hipStream_t st);
+// the hyper-parameter form with a vocabulary set per row (czc_generate_rows_vocab): set_rows[b] (device, [B]) in [-1, n_sets) picks
+// one of the bitsets bits [n_sets, W], W = ceil(V / 32); the mask factor of id i is mask[i] * bit(i), -1 = mask[i] alone
+int launch_softmax_mask_topk_rows_vocab(const float* logits, int B, int V, int K, const float* mask, const RowHyper* hp_rows, int dot_id,
+                                        const int* dot_rows, const int* set_rows, const unsigned* bits, int W, float* probs, int* idxs,
+                                        int* cand, hipStream_t st);
 
 // ---- bridge.hip ---------------------------------------------------------------------------
 struct BridgeDev {
@@ -438,7 +443,7 @@ int launch_pll_sum(const float* logp, int R, int Lmax, const int* len_of_row, fl
 // ---- czc_internal_hooks (declared below, private to the build): what libconzic_hip_test.so may reach inside this library -----------
 // The product library has hidden visibility; the hook library (api_test.hip) gets the launchers it wraps and the
 // process-wide kernel-family switches it flips through this table instead of through exported C++ symbols.
-constexpr int HOOKS_ABI = 0x060c;
+constexpr int HOOKS_ABI = 0x060d;
 struct Hooks {
   char* (*err_buf)();  // the calling host thread's g_err [512]
   decltype(&launch_gemm) gemm;
@@ -508,6 +513,8 @@ struct Hooks {
   decltype(&launch_bridge_rows_hp) bridge_rows_hp;
   decltype(&launch_softmax_mask_topk_rows) softmax_mask_topk_rows;
   decltype(&launch_softmax_mask_topk_rows_hp) softmax_mask_topk_rows_hp;
+  // the top-K selection with a vocabulary set per row (tests/test_topk_vocab_gpu.py)
+  decltype(&launch_softmax_mask_topk_rows_vocab) softmax_mask_topk_rows_vocab;
   // the family the calling thread's last GEMM launch chose (GemmFamily; tests/test_gemm_layout_gpu.py)
   int (*gemm_family)();
 };

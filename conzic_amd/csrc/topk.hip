@@ -26,12 +26,17 @@ __device__ __forceinline__ float block_reduce(float v, float* red, bool is_max) 
 }
 
 // ROWS: the '.' rule is the row's own (dot_rows[b], czc_generate_rows); one work-group serves one row, so the value is
-// uniform over the work-group either way.  HP: so is the temperature (hp_rows[b].temperature, czc_generate_rows_hp)
-template <bool ROWS, bool HP>
+// uniform over the work-group either way.  HP: so is the temperature (hp_rows[b].temperature, czc_generate_rows_hp).
+// VOCAB (czc_generate_rows_vocab; only with ROWS and HP): row b carries vocabulary set set_rows[b] of the bitsets bits [n_sets, W],
+// W = ceil(V / 32), bit (i & 31) of word (i >> 5) set = id i allowed; -1 = no set.  The mask factor of id i is then
+// mask[i] * bit(i) in both places that read it (step 3 and the cand tail), the '.' rule still on top.  The 32 lanes that share a
+// word read it from global memory (one 3.8 KB row of bits at V = 30 522, served by the cache): the LDS layout does not change.
+template <bool ROWS, bool HP, bool VOCAB>
 __global__ __launch_bounds__(TK_THREADS) void softmax_mask_topk_kernel(const float* logits, int V, int K,
                                                                         const float* mask, float temperature_, int dot_id,
                                                                         int dot_allowed_, const int* dot_rows, const RowHyper* hp_rows,
-                                                                        float* probs_out, int* idx_out, int* cand_out) {
+                                                                        float* probs_out, int* idx_out, int* cand_out,
+                                                                        const int* set_rows, const unsigned* bits, int W) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   float* p = (float*)smem_raw;                       // [V] probabilities (as float / uint bits)
   unsigned* hist = (unsigned*)(p + ((V + 3) & ~3));  // [256]
@@ -48,6 +53,11 @@ __global__ __launch_bounds__(TK_THREADS) void softmax_mask_topk_kernel(const flo
   const float* lr = logits + (long)b * V;
   const int dot_allowed = ROWS ? dot_rows[b] : dot_allowed_;
   const float temperature = HP ? hp_rows[b].temperature : temperature_;
+  const unsigned* bw = nullptr;  // VOCAB: the W words of the row's set, null where the row has none
+  if constexpr (VOCAB) {
+    const int set = set_rows[b];
+    if (set >= 0) bw = bits + (size_t)set * W;
+  }
 
   // 1. logits / temperature, row max
   float mx = -INFINITY;
@@ -68,6 +78,7 @@ __global__ __launch_bounds__(TK_THREADS) void softmax_mask_topk_kernel(const flo
   // 3. normalise and mask ('.' follows the per-position rule of utils.py:53-59)
   for (int i = tid; i < V; i += TK_THREADS) {
     float mk = mask[i];
+    if constexpr (VOCAB) { if (bw) mk *= (float)((bw[i >> 5] >> (i & 31)) & 1u); }
     if (i == dot_id) mk = dot_allowed ? 1.0f : 0.0f;
     p[i] = (p[i] / sm) * mk;
   }
@@ -161,14 +172,16 @@ __global__ __launch_bounds__(TK_THREADS) void softmax_mask_topk_kernel(const flo
     probs_out[(long)b * K + tid] = __uint_as_float(u);
     idx_out[(long)b * K + tid] = id;
     float mk = mask[id];
+    if constexpr (VOCAB) { if (bw) mk *= (float)((bw[id >> 5] >> (id & 31)) & 1u); }
     if (id == dot_id) mk = dot_allowed ? 1.0f : 0.0f;
     cand_out[(long)b * K + tid] = (int)((float)id * mk);
   }
 }
 
-template <bool ROWS, bool HP>
+template <bool ROWS, bool HP, bool VOCAB = false>
 static int launch_topk_t(const float* logits, int B, int V, int K, const float* mask, float temperature, int dot_id, int dot_allowed,
-                         const int* dot_rows, const RowHyper* hp_rows, float* probs, int* idxs, int* cand, hipStream_t st) {
+                         const int* dot_rows, const RowHyper* hp_rows, float* probs, int* idxs, int* cand, hipStream_t st,
+                         const int* set_rows = nullptr, const unsigned* bits = nullptr, int W = 0) {
   if (K > TK_MAXK || K <= 0 || K > V) {
     snprintf(g_err, sizeof(g_err), "topk: K=%d unsupported (1..%d, <= V)", K, TK_MAXK);
     return 1;
@@ -178,10 +191,10 @@ static int launch_topk_t(const float* logits, int B, int V, int K, const float* 
     snprintf(g_err, sizeof(g_err), "topk: V=%d does not fit the 160 KB LDS", V);
     return 1;
   }
-  CZC_HIP_CHECK(hipFuncSetAttribute((const void*)softmax_mask_topk_kernel<ROWS, HP>, hipFuncAttributeMaxDynamicSharedMemorySize,
+  CZC_HIP_CHECK(hipFuncSetAttribute((const void*)softmax_mask_topk_kernel<ROWS, HP, VOCAB>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)shmem));
-  hipLaunchKernelGGL((softmax_mask_topk_kernel<ROWS, HP>), dim3(B), dim3(TK_THREADS), shmem, st, logits, V, K, mask, temperature,
-                     dot_id, dot_allowed, dot_rows, hp_rows, probs, idxs, cand);
+  hipLaunchKernelGGL((softmax_mask_topk_kernel<ROWS, HP, VOCAB>), dim3(B), dim3(TK_THREADS), shmem, st, logits, V, K, mask, temperature,
+                     dot_id, dot_allowed, dot_rows, hp_rows, probs, idxs, cand, set_rows, bits, W);
   CZC_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -200,6 +213,15 @@ int launch_softmax_mask_topk_rows_hp(const float* logits, int B, int V, int K, c
                                      const int* dot_rows, float* probs, int* idxs, int* cand, hipStream_t st) {
   if (!hp_rows || !dot_rows) { snprintf(g_err, sizeof(g_err), "topk: the per-row hyper-parameter form needs hp_rows and dot_rows"); return 1; }
   return launch_topk_t<true, true>(logits, B, V, K, mask, 1.0f, dot_id, 0, dot_rows, hp_rows, probs, idxs, cand, st);
+}
+
+// set_rows [B]: every entry in [-1, n_sets) (the callers check them); bits [n_sets, W] with W = ceil(V / 32) words per set
+int launch_softmax_mask_topk_rows_vocab(const float* logits, int B, int V, int K, const float* mask, const RowHyper* hp_rows, int dot_id,
+                                        const int* dot_rows, const int* set_rows, const unsigned* bits, int W, float* probs, int* idxs,
+                                        int* cand, hipStream_t st) {
+  if (!hp_rows || !dot_rows || !set_rows || !bits) { snprintf(g_err, sizeof(g_err), "topk: the vocabulary-set form needs hp_rows, dot_rows, set_rows and bits"); return 1; }
+  if (W != (V + 31) / 32) { snprintf(g_err, sizeof(g_err), "topk: a vocabulary set has W=%d words, V=%d needs %d", W, V, (V + 31) / 32); return 1; }
+  return launch_topk_t<true, true, true>(logits, B, V, K, mask, 1.0f, dot_id, 0, dot_rows, hp_rows, probs, idxs, cand, st, set_rows, bits, W);
 }
 
 }  // namespace czc

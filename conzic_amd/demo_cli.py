@@ -114,7 +114,10 @@ def get_args(argv=None):
     p.add_argument("--pick_lambda", type=float, default=None, metavar="LAMBDA",
                    help="implies --fluency; needs --samples_num > 1: log, per image, the \"picked caption\": the sample whose final "
                         "caption has the largest cosine + LAMBDA x mean log p (the \"best caption\" lines stay as they are)")
+    from conzic_amd import vocab as vc
+    vc.add_arguments(p)
     a = p.parse_args(argv)
+    vc.check_arguments(p, a)
     if a.pick_lambda is not None:
         if not (a.pick_lambda == a.pick_lambda) or a.pick_lambda in (float("inf"), float("-inf")):
             p.error("--pick_lambda must be finite")
@@ -340,14 +343,16 @@ def main(argv=None):
             log_distinct(logger, img_name, finals)
         logger.info("total %.2fs" % (time.time() - t0))
         return finals
-    if args.batch_samples or args.sample_tau or args.distinct:
-        # one engine call for all samples, or -- the serial loop under --sample_tau / --distinct -- one per sample with that sample's seeds
+    from conzic_amd import vocab as vc
+    if args.batch_samples or args.sample_tau or args.distinct or vc.wanted(args):
+        # one engine call for all samples, or -- the serial loop under --sample_tau / --distinct / the word lists -- one per sample
+        # with that sample's seeds
         from conzic_amd.runtime import caption_samples
         kw = dict(prompt=args.prompt, batch_size=args.batch_size, max_len=args.sentence_len, top_k=args.candidate_k,
                   temperature=args.lm_temperature, max_iter=args.num_iterations, alpha=args.alpha, beta=args.beta,
                   generate_order=args.order, gamma=args.gamma, ctl_type=args.control_type,
                   style_type=args.sentiment_type, pos_type=args.pos_type, sample_tau=args.sample_tau, sample_seed=args.seed,
-                  rivals=rivals, delta=args.distinct, fluency=fluency)
+                  rivals=rivals, delta=args.distinct, fluency=fluency, vocab=vc.from_arguments(args, lm_tokenizer))
         for sample_id in ([None] if args.batch_samples else range(args.samples_num)):
             outs = caption_samples(args.samples_num if sample_id is None else 1, args.run_type, img_name, lm_model, clip, lm_tokenizer,
                                    image_instance, token_mask, logger, sample0=sample_id or 0, **kw)

@@ -72,6 +72,16 @@ def _rival_table(name: str, rivals, R: int):
     return rv
 
 
+def _vocab_sets(name: str, sets, V: int):
+    """uint32 [n_sets, W] bitsets from `sets` (one set [W] becomes [1, W]); W = ceil(V / 32), conzic_amd.vocab.pack builds such a table"""
+    bits = np.ascontiguousarray(sets, dtype=np.uint32)
+    if bits.ndim == 1:
+        bits = bits.reshape(1, -1)
+    if bits.ndim != 2 or bits.shape[1] != (V + 31) // 32:
+        raise ValueError(f"{name}: sets must be uint32 [n_sets, {(V + 31) // 32}] (one bit per id of the {V}-id vocabulary), got {bits.shape}")
+    return bits
+
+
 def make_config(bert_cfg, clip_cfg, special: Dict[str, int], precision: int) -> native.Config:
     c = native.Config()
     if bert_cfg is not None:
@@ -395,8 +405,8 @@ class Engine:
         return ids, cos
 
     def _rows_call(self, name: str, call, init, positions, seed_len: int, L: Optional[int] = None, lens=None, need_lens: bool = False,
-                   hypers=_ABSENT, draws=None, groups=None, rivals=None, deltas=_ABSENT, image_of_row=None, n_mask=None,
-                   snapshot_every: Optional[int] = None, want_cos: bool = True):
+                   hypers=_ABSENT, draws=None, groups=None, rivals=None, deltas=_ABSENT, sets=None, set_of_row=None,
+                   image_of_row=None, n_mask=None, snapshot_every: Optional[int] = None, want_cos: bool = True):
         """The one path of every generate_rows* method: checked, contiguous arrays of whatever per-row arguments the method has
         (`name` goes into the ValueError texts), the snapshot interval, the two outputs, then czc_<name>(handle, *call(a)), where
         `a` holds the sizes and the pointers (None = NULL), and the error check.  A new per-row argument is normalised here."""
@@ -426,12 +436,15 @@ class Engine:
         dl = None if deltas is _ABSENT else _row_vector(name, "deltas", np.zeros((R,), np.float32) if deltas is None else deltas, R,
                                                         dtype=np.float32)
         nm = _row_vector(name, "n_mask", n_mask, n_steps, "steps")
+        so = _row_vector(name, "set_of_row", set_of_row, R)
+        bits = None if sets is None else _vocab_sets(name, sets, int(self.cfg.bert_vocab))
         every = snapshot_every or (L if L is not None else max(int(ln.max()) if ln is not None else T - seed_len - 1, 1))
         S = n_steps // every
         ids = np.empty((S, R, T), dtype=np.int32)
         cos = np.empty((S, R), dtype=np.float32) if want_cos else None
         a = SimpleNamespace(R=R, T=T, n_steps=n_steps, every=every, init=_ptr(init), pos=_ptr(pos), lens=_ptr(ln), hypers=hp, draws=dr,
                             groups=_ptr(gr), ior=_ptr(ior), rivals=_ptr(rv), M=0 if rv is None else int(rv.shape[1]), deltas=_ptr(dl),
+                            sets=_ptr(bits), n_sets=0 if bits is None else int(bits.shape[0]), set_of_row=_ptr(so),
                             n_mask=_ptr(nm), ids=_ptr(ids), cos=_ptr(cos))
         rc = getattr(self.lib, "czc_" + name)(self.h, *call(a))
         if rc:
@@ -561,6 +574,22 @@ class Engine:
                                                               a.n_mask, a.every, a.hypers, a.draws, a.rivals, a.M, a.deltas, a.ids, a.cos),
                                init_rows, positions, seed_len, lens=lens, hypers=hypers, draws=draws, groups=groups, rivals=rivals,
                                deltas=deltas, image_of_row=image_of_row, n_mask=n_mask, snapshot_every=snapshot_every, want_cos=want_cos)
+
+    def generate_rows_vocab(self, init_rows, lens, seed_len: int, top_k: int, positions, hypers: Sequence[native.Hyper],
+                            draws: Optional[Sequence[native.Draw]] = None, groups: Optional[Sequence[int]] = None, rivals=None,
+                            deltas=None, sets=None, set_of_row: Optional[Sequence[int]] = None,
+                            image_of_row: Optional[Sequence[int]] = None, n_mask: Optional[Sequence[int]] = None,
+                            snapshot_every: Optional[int] = None, want_cos: bool = True):
+        """czc_generate_rows_vocab: generate_rows_vs with a vocabulary set per row.  `sets` uint32 [n_sets, ceil(V / 32)] bitsets
+        (bit i & 31 of word i >> 5 set = id i allowed; conzic_amd.vocab.pack / ban / allow build them) and `set_of_row` int [R],
+        -1 = no set (None: generate_rows_vs itself).  In row r's masked softmax the mask factor of id i is token_mask[i] * bit(i),
+        the '.' rule still on top.  Returns (ids int32 [S,R,T], cos fp32 [S,R]) per snapshot."""
+        return self._rows_call("generate_rows_vocab", lambda a: (a.R, a.T, seed_len, a.init, a.lens, a.ior, a.groups, top_k, a.n_steps, a.pos,
+                                                                 a.n_mask, a.every, a.hypers, a.draws, a.rivals, a.M, a.deltas, a.sets, a.n_sets,
+                                                                 a.set_of_row, a.ids, a.cos),
+                               init_rows, positions, seed_len, lens=lens, hypers=hypers, draws=draws, groups=groups, rivals=rivals,
+                               deltas=deltas, sets=sets, set_of_row=set_of_row, image_of_row=image_of_row, n_mask=n_mask,
+                               snapshot_every=snapshot_every, want_cos=want_cos)
 
     def score_rows_vs(self, rows, seed_len: int, rivals, lens: Optional[Sequence[int]] = None,
                       image_of_row: Optional[Sequence[int]] = None):
@@ -782,12 +811,12 @@ class EngineGroup:
         return np.concatenate([o[0] for o in outs], axis=1), np.concatenate([o[1] for o in outs], axis=1)
 
     def _split_rows(self, name: str, run, init, positions, seed_len: int, L: Optional[int] = None, lens=None, hypers=None, draws=None,
-                    groups=None, rivals=None, deltas=None, image_of_row=None, snapshot_every=None, want_cos: bool = True,
-                    images: str = "rows"):
+                    groups=None, rivals=None, deltas=None, set_of_row=None, image_of_row=None, snapshot_every=None,
+                    want_cos: bool = True, images: str = "rows"):
         """The one path of every generate_rows* method of the group: check the per-row arguments the method has, work out the
         snapshot interval of the whole call, deal the rows over the members (contiguously, or on group boundaries with `groups`),
         hand every member its images, call run(member, p) -- p holds the member's slice of every per-row argument (rows, init,
-        lens, pos, hypers, draws, groups renumbered into [0, its row count), rivals, deltas, ior) and `every` -- and put the
+        lens, pos, hypers, draws, groups renumbered into [0, its row count), rivals, deltas, set_of_row, ior) and `every` -- and put the
         results back by row index.  images: "rows" = the embeds of its own rows, p.ior None (the identity); "unique" = the embeds
         of the images its rows name and p.ior into them; "whole" = the whole batch and the caller's indices (rivals may name any
         image).  The normalisation is per row, so a row's embedding has the bits the whole batch had.  A new per-row argument is
@@ -816,6 +845,7 @@ class EngineGroup:
                 raise NativeError(f"EngineGroup.{name}: a group id outside [0, R)", code=native.ERR_ARG)
         rv = _rival_table(name, rivals, R)
         dl = None if rv is None else _row_vector(name, "deltas", np.zeros((R,), np.float32) if deltas is None else deltas, R, dtype=np.float32)
+        so = _row_vector(name, "set_of_row", set_of_row, R)
         embeds = self._full_embeds if self._full_embeds is not None else self._encoded
         if embeds is None:
             raise NativeError(f"EngineGroup.{name}: encode_images / set_image_embeds first")
@@ -830,7 +860,8 @@ class EngineGroup:
                                 lens=None if ln is None else ln[rows], pos=np.ascontiguousarray(pos[:, rows]),
                                 hypers=None if hps is None else [hps[r] for r in rows], draws=None if drs is None else [drs[r] for r in rows],
                                 groups=None if gr is None else np.unique(gr[rows], return_inverse=True)[1].astype(np.int32),
-                                rivals=None if rv is None else rv[rows], deltas=None if dl is None else dl[rows], ior=None)
+                                rivals=None if rv is None else rv[rows], deltas=None if dl is None else dl[rows],
+                                set_of_row=None if so is None else so[rows], ior=None)
             if images == "rows":
                 e.set_image_embeds(embeds[ior[rows]])
             elif images == "unique":
@@ -952,6 +983,20 @@ class EngineGroup:
                                                                                     n_mask=n_mask, snapshot_every=p.every, want_cos=want_cos),
                                 init_rows, positions, seed_len, lens=lens, hypers=list(hypers), draws=draws, groups=groups, rivals=rivals,
                                 deltas=deltas, image_of_row=image_of_row, snapshot_every=snapshot_every, want_cos=want_cos, images="whole")
+
+    def generate_rows_vocab(self, init_rows, lens, seed_len: int, top_k: int, positions, hypers, draws=None, groups=None, rivals=None,
+                            deltas=None, sets=None, set_of_row=None, image_of_row=None, n_mask=None, snapshot_every=None,
+                            want_cos: bool = True):
+        """Engine.generate_rows_vocab with the rows split over the streams as generate_rows_vs splits them (every member holds the
+        whole resident batch).  Every member gets the WHOLE table of bitsets and its own rows' indices into it, so an index means
+        the same set on every stream."""
+        return self._split_rows("generate_rows_vocab", lambda e, p: e.generate_rows_vocab(p.init, p.lens, seed_len, top_k, p.pos, p.hypers, p.draws,
+                                                                                          p.groups, p.rivals, p.deltas, sets=sets,
+                                                                                          set_of_row=p.set_of_row, image_of_row=p.ior,
+                                                                                          n_mask=n_mask, snapshot_every=p.every, want_cos=want_cos),
+                                init_rows, positions, seed_len, lens=lens, hypers=list(hypers), draws=draws, groups=groups, rivals=rivals,
+                                deltas=deltas, set_of_row=set_of_row, image_of_row=image_of_row, snapshot_every=snapshot_every,
+                                want_cos=want_cos, images="whole")
 
     def fluency_rows(self, rows, seed_len: int, lens=None, temperature: float = 1.0) -> dict:
         """Engine.fluency_rows on the parent engine, WITHOUT a split over the streams: the call needs no image embeds, a

@@ -27,6 +27,7 @@ PREC_FP16 = 4
 PREC_REFINE = 5
 CLIP_MAX_LEN = 77
 MAX_BERT_LEN = 64   # include/conzic_hip.h CZC_MAX_BERT_LEN: tokens of a BERT row, [CLS] and [SEP] included
+MAX_VOCAB_SETS = 4096  # include/conzic_hip.h CZC_MAX_VOCAB_SETS: vocabulary sets of a call (czc_generate_rows_vocab)
 MAX_RIVALS = 16    # include/conzic_hip.h CZC_MAX_RIVALS: rival images of a row (czc_generate_rows_vs)
 INDEX_MAX_K = 64  # include/conzic_hip.h CZC_INDEX_MAX_K: the largest k of czc_index_search
 POS_IDLE = -1   # include/conzic_hip.h CZC_POS_IDLE: the row sits the step out (czc_generate_rows_from)
@@ -128,6 +129,8 @@ SIGNATURES = {
     "czc_score_rows": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
     "czc_generate_rows_vs": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _I, C.POINTER(Hyper), C.POINTER(Draw), _P, _I, _P,
                                   _P, _P]),
+    "czc_generate_rows_vocab": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _I, C.POINTER(Hyper), C.POINTER(Draw), _P, _I, _P,
+                                     _P, _I, _P, _P, _P]),
     "czc_score_rows_vs": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P]),
     "czc_fluency_rows": (_I, [_P, _P, _I, _I, _I, _P, C.c_float, _P, _P, _P]),
     "czc_set_option": (_I, [_P, C.c_char_p, _I]),
@@ -207,6 +210,7 @@ TEST_SIGNATURES = {
     "czc_test_bridge_cand": (_I, [C.POINTER(BridgeTables), _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P,
                                   _P, _P, _P, _P, _P]),
     "czc_test_topk_rows": (_I, [_I, _I, _I, _I, _P, _P, C.c_float, _I, _P, _P, _P, _P, _P]),
+    "czc_test_topk_rows_vocab": (_I, [_I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P]),
     "czc_test_gemm_family": (_I, []),
     "czc_test_gemm_layout": (_I, [C.POINTER(GemmLayout)]),
 }

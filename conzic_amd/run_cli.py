@@ -59,6 +59,8 @@ def batched_samples(args, run_type, all_batches, own_lo, own_hi, rank, world, im
     from PIL import Image
     from conzic_amd.harness import sample_schedules
     from conzic_amd.runtime import caption_order, caption_samples
+    from conzic_amd import vocab as vc
+    vocab = vc.from_arguments(args, lm_tokenizer)   # --ban_words / --allow_words / --ban_per_sample: the same sets for every batch
     S, nb = args.samples_num, len(all_batches)
     order, max_iters = caption_order(args.run_type, args.order, args.control_type, args.num_iterations, args.sentence_len)
     positions, n_mask, every, order_lists = sample_schedules(order, args.sentence_len, max_iters, S * nb)
@@ -77,7 +79,8 @@ def batched_samples(args, run_type, all_batches, own_lo, own_hi, rank, world, im
                                generate_order=args.order, gamma=args.gamma, ctl_type=args.control_type,
                                style_type=args.sentiment_type, pos_type=args.pos_type, schedules=sched,
                                sample_tau=args.sample_tau, sample_seed=args.seed,
-                               rivals=args.distinct_rivals if args.distinct else None, delta=args.distinct, fluency=fluency)
+                               rivals=args.distinct_rivals if args.distinct else None, delta=args.distinct, fluency=fluency,
+                               vocab=vocab)
         if S > 1:
             from conzic_amd.diversity import log_distinct
             log_distinct(logger, name_batch, [[o[0][-2 if len(o[0]) > 1 else -1][i] for o in outs] for i in range(len(name_batch))])
@@ -451,6 +454,8 @@ def main(argv=None):
         batched_samples(args, run_type, all_batches, own_lo, own_hi, rank, world, img_dir, lm_model, clip, lm_tokenizer,
                         token_mask, logger)
         return
+    from conzic_amd import vocab as vc
+    vocab = vc.from_arguments(args, lm_tokenizer)   # --ban_words / --allow_words (serial loop: one set for every sample)
     finals = {}   # image name -> the final caption of every sample
     fluency = {}  # --fluency: batch index -> the records of its final captions, every sample's (runtime._fluency_after)
     for sample_id in range(args.samples_num):
@@ -471,13 +476,13 @@ def main(argv=None):
             if args.fluency:
                 kw["fluency"] = fluency.setdefault(batch_idx, [])
                 n_rec = len(kw["fluency"])
-            if args.sample_tau or args.distinct:   # the sample loop under --sample_tau / --distinct: one rows call per sample
+            if args.sample_tau or args.distinct or vocab is not None:   # the sample loop under --sample_tau / --distinct / word lists: one rows call per sample
                 from conzic_amd.runtime import caption_samples
                 (gen_texts, _), = caption_samples(1, args.run_type, name_batch, lm_model, clip, lm_tokenizer, imgs, token_mask, logger,
                                                   gamma=args.gamma, ctl_type=args.control_type, style_type=args.sentiment_type,
                                                   pos_type=args.pos_type, sample_tau=args.sample_tau, sample_seed=args.seed,
                                                   sample0=sample_id, rivals=args.distinct_rivals if args.distinct else None,
-                                                  delta=args.distinct, **kw)
+                                                  delta=args.distinct, vocab=vocab, **kw)
             elif args.run_type == 'caption':
                 gen_texts, _ = generate_caption(name_batch, lm_model, clip, lm_tokenizer, imgs, token_mask, logger, **kw)
             else:

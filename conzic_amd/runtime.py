@@ -511,7 +511,7 @@ def run_generation_samples(order: str, samples_num: int, img_name, model, clip, 
                            logger, max_len, top_k, temperature, alpha, beta, max_iters, batch_size, verbose=True, gamma=None,
                            ctl_signal="positive", print_every: Optional[int] = None, pos_template=None, schedules=None,
                            sample_tau: float = 0.0, sample_seed: int = 0, sample0: int = 0, rivals=None, delta: float = 0.0,
-                           fluency=False):
+                           fluency=False, vocab=None):
     """The sample loop around a *_generation call (demo.py:83, run.py) as ONE engine call: `samples_num` samples of a batch of
     `batch_size` images ride as batch_size * samples_num rows of czc_generate_rows, every sample with the visiting order the
     serial loop would have drawn for it (harness.sample_schedules); the images are encoded once.  Returns a list of
@@ -525,10 +525,20 @@ def run_generation_samples(order: str, samples_num: int, img_name, model, clip, 
     seed of its (image, sample): draws.row_seed(sample_seed, key of the image's name, sample0 + s).  A serial loop that calls
     this function once per sample (samples_num = 1, sample0 = the sample's index) returns the ids of the one batched call.
     `rivals` / `delta`: as for run_generation; every sample of an image carries the image's rivals (czc_generate_rows_vs).
-    `fluency`: as for run_generation, one line per (sample, image) row."""
+    `fluency`: as for run_generation, one line per (sample, image) row.
+    `vocab`: a vocab.Vocab, or bitsets uint32 [W] / [n, W] (vocab.pack): one vocabulary set for every row, or one per sample
+    (n = the samples of the whole loop; sample sample0 + s takes set sample0 + s), applied on top of the token mask
+    (czc_generate_rows_vocab).  An allow-list that leaves fewer than top_k ids after the token mask is refused (ValueError)."""
     from . import draws as dw
+    from . import vocab as vc
     import utils as ref_utils
     S, B = int(samples_num), int(batch_size)
+    if vocab is not None and not isinstance(vocab, vc.Vocab):
+        vocab = vc.Vocab(vocab)
+    if vocab is not None:   # before any engine work: the sets' sizes, and the refusal of an allow-list shorter than a step's K
+        vocab.check(_mask_to_numpy(token_mask), top_k)
+        set_of_sample = vocab.set_of_sample(S, sample0)
+        vocab_said = vocab.describe(_mask_to_numpy(token_mask))
     eng = get_engine(model, clip, tokenizer)
     seed_len = len(prompt.split()) + 1
     batch = ref_utils.get_init_text(tokenizer, prompt, max_len, B)
@@ -550,6 +560,17 @@ def run_generation_samples(order: str, samples_num: int, img_name, model, clip, 
     init_row = np.asarray(batch[0], dtype=np.int32)
     vs = _rival_call(rivals, delta, clip, image_instance, B)
     eng = _rival_engine(eng, vs, model, clip, tokenizer, logger)
+
+    def vocab_rows(runner, s0, n_samples, pos_rows, draws_):
+        """samples s0 .. s0 + n_samples - 1 of the batch as rows of one vocabulary call: sample-major, every row with its
+        sample's set and, with rivals, its image's rivals"""
+        from . import rivals as rv
+        n = B * n_samples
+        ior = np.tile(np.arange(B, dtype=np.int32), n_samples)
+        return runner.generate_rows_vocab(np.repeat(init_row[None, :], n, axis=0), None, seed_len, top_k, pos_rows, [hp] * n, draws_, None,
+                                          None if vs is None else rv.expand(vs["table"], ior), None if vs is None else [vs["delta"]] * n,
+                                          sets=vocab.bits, set_of_row=np.repeat(set_of_sample[s0:s0 + n_samples], B),
+                                          image_of_row=ior, n_mask=n_mask, snapshot_every=every)
 
     def vs_rows(runner, n_samples, pos_rows, draws_):
         """`n_samples` samples of the batch as rows of one rivals call: sample-major, every row with its image's rivals."""
@@ -584,7 +605,13 @@ def run_generation_samples(order: str, samples_num: int, img_name, model, clip, 
             runner.set_image_embeds(emb)
         if eng.precision == native.PREC_REFINE:
             runner.refine_guard(reset=True)
-        if vs is not None and one_by_one:
+        if vocab is not None and one_by_one:
+            outs = [vocab_rows(runner, s, 1, np.ascontiguousarray(np.repeat(positions[:, s:s + 1], B, axis=1)),
+                               None if row_draws is None else row_draws[s * B:(s + 1) * B]) for s in range(S)]
+            out = tuple(np.concatenate([o[j] for o in outs], axis=1) for j in (0, 1))
+        elif vocab is not None:
+            out = vocab_rows(runner, 0, S, rows_pos, row_draws)
+        elif vs is not None and one_by_one:
             outs = [vs_rows(runner, 1, np.ascontiguousarray(np.repeat(positions[:, s:s + 1], B, axis=1)),
                             None if row_draws is None else row_draws[s * B:(s + 1) * B]) for s in range(S)]
             out = tuple(np.concatenate([o[j] for o in outs], axis=1) for j in (0, 1))
@@ -617,6 +644,8 @@ def run_generation_samples(order: str, samples_num: int, img_name, model, clip, 
     out = []
     for s in range(S):
         said = dw.describe(row_draws[s * B:(s + 1) * B] if row_draws else None)
+        if vocab is not None:
+            said += vocab_said + f" (sample {sample0 + s}: set {int(set_of_sample[s])})"
         if order_lists is not None:
             logger.info(f"Order_list:{order_lists[s]}" + said)
         elif said:
@@ -863,7 +892,7 @@ def caption_order(run_type: str, generate_order: str, ctl_type: str, max_iter: i
 def caption_samples(samples_num: int, run_type: str, img_name, model, clip, tokenizer, image_instance, token_mask, logger, *,
                     prompt="", batch_size=1, max_len=15, top_k=100, temperature=1.0, max_iter=500, alpha=0.7, beta=1,
                     generate_order="sequential", gamma=5, ctl_type="sentiment", style_type="positive", pos_type=None,
-                    schedules=None, sample_tau=0.0, sample_seed=0, sample0=0, rivals=None, delta=0.0, fluency=False):
+                    schedules=None, sample_tau=0.0, sample_seed=0, sample0=0, rivals=None, delta=0.0, fluency=False, vocab=None):
     """`--batch_samples` of the two CLIs: what `samples_num` calls of generate_caption (run_type 'caption', gen_utils.py:289-333)
     or control_generate_caption (control_gen_utils.py:197-232) return, from one run_generation_samples call.  Returns the list
     of (generate_texts, clip_scores) pairs and logs every sample's final and best captions as those functions do."""
@@ -883,7 +912,7 @@ def caption_samples(samples_num: int, run_type: str, img_name, model, clip, toke
     outs = run_generation_samples(order, samples_num, img_name, model, clip, tokenizer, image_instance, token_mask, prompt,
                                   logger, max_len, top_k, temperature, alpha, beta, max_iters, batch_size, schedules=schedules,
                                   sample_tau=sample_tau, sample_seed=sample_seed, sample0=sample0, rivals=rivals, delta=delta,
-                                  fluency=fluency, **kw)
+                                  fluency=fluency, vocab=vocab, **kw)
     logger.info("Finished %d samples in %.3fs" % (samples_num, time.time() - start_time))
     for sample_id, (generate_texts, _) in enumerate(outs):
         logger.info(f"Sample {sample0 + sample_id}: ")

@@ -339,6 +339,8 @@ int czc_generate_rows_from(czc_engine* e, int R, int T, int L, int seed_len, con
  *     caveats stated there for compact batches -- the form of BERT's GEMMs depends on the packed row count and CZC_PREC_SPLIT's
  *     tower picks kernels by row count, so ids agree and winner cosines may differ in the last bits (1e-6).
  *   - a call whose rows all have T_r == T takes czc_generate_rows_from's path and returns its bits.
+ *   - CZC_PREC_REFINE: a row that is idle at a snapshot step returns the cosine its last step left; that step re-encodes a
+ *     margin-gated row's winner as a snapshot step does, so the 1e-6 above holds for rows shorter than their companions too.
  *   - option "memo_rows" applies unchanged (rows are compared over the stride T); idle steps, image_of_row and the control
  *     tables work as in czc_generate_rows_from.  The offsets of the full batch and of every step's run list travel with the
  *     one schedule upload; those of a "memo_rows" compact batch are derived on the host from the list it already reads and
@@ -514,6 +516,46 @@ int czc_generate_rows_vs(czc_engine* e, int R, int T, int seed_len, const int32_
 int czc_score_rows_vs(czc_engine* e, const int32_t* rows /* [R, T] BERT ids, host or device */, int R, int T, int seed_len,
                       const int32_t* len_of_row_host, const int32_t* image_of_row_host, const int32_t* rival_of_row_host, int M,
                       float* out_cos /* [R] */, float* out_disc /* [R] */);
+
+/* czc_generate_rows_vs with a VOCABULARY SET per row: "never say these words for this image", "describe it with words from this
+ * list only", "sample 3 may not re-use the nouns of samples 1 and 2", or one image under a plain and a restricted vocabulary side
+ * by side, in one batch instead of one czc_set_token_mask and one call per variant.  Everything not named here is
+ * czc_generate_rows_vs': ragged lengths, idle steps, image_of_row, hyper-parameters, draws, tied groups, rivals, snapshots.
+ *   - the sets are bitsets: sets is uint32 [n_sets, W], W = ceil(bert_vocab / 32); bit (i & 31) of word (i >> 5) is 1 when id i
+ *     is allowed.  Bits at or above bert_vocab in the last word are ignored.  set_of_row is [R]; -1 = the row has no set.
+ *   - the rule: in the masked softmax of a row r with set s (gen_utils.py:42-47) the mask factor of id i is
+ *         mk(i) = (i == dot_id) ? the '.' rule of the row : token_mask[i] * bit_s(i).
+ *     Nothing else changes: no renormalisation after masking, the ascending-id tie rule, cand = id * mk -- an id the set removed
+ *     becomes [PAD] with probability 0, exactly as a stop word does.  The '.' rule overrides the set as it overrides the token
+ *     mask (utils.py:53-59).  Only the top-K kernel knows about sets.
+ *   - E, the defining property: a call whose rows all carry set s returns, bit for bit (ids and cosines, every precision), what
+ *     the same call without sets returns after czc_set_token_mask(token_mask * bits_s).  Rows are independent: in a mixed call
+ *     row r returns what the call returns when every row carries row r's set (under the compact-batch caveats stated for
+ *     czc_generate_rows_len); a row with -1 returns what it returns today.
+ *   - set_of_row == NULL, or every entry -1: czc_generate_rows_vs itself, bit for bit.
+ *   - an all-zero set is legal: the row proposes [PAD] and possibly '.', which is what E says.  So is an allow-list shorter than
+ *     top_k (conzic_amd.runtime refuses that one, because [PAD] winners surprise users).
+ *   - the bitsets and the indices are uploaded once, with the schedule.  A compact batch (idle rows, ragged lengths, "memo_rows"
+ *     hits) gathers the indices of the rows that run through the run list it already has, as it gathers the hyper-parameters;
+ *     the table of bitsets stays where it is.  No device-to-host read beyond those of czc_generate_rows_vs.
+ *   - option "memo_rows" stays exact: a row's set is constant over the call, so its key still determines the outcome.
+ *   - CZC_PREC_REFINE: nothing changes; selection, gate and guard work on whatever candidates the top-K kernel produced.
+ *   - czc_step, czc_generate and option "memo" take no sets.
+ * Not built: sets per position; required ("must appear") words; a per-row top_k; any eligibility rule in the fusion -- a [PAD]
+ * candidate can still win, as today; the exact host scorer for mixed sets -- the control-callback rules of czc_generate_rows_vs
+ * apply unchanged.
+ * Checked before any GPU work, CZC_ERR_ARG, and the engine stays usable: n_sets < 1 with a set_of_row array; n_sets >
+ * CZC_MAX_VOCAB_SETS (4096 sets = 15 MB at bert_vocab = 30 522); an index outside [-1, n_sets); sets == NULL with an index >= 0;
+ * and everything czc_generate_rows_vs checks. */
+#define CZC_MAX_VOCAB_SETS 4096
+int czc_generate_rows_vocab(czc_engine* e, int R, int T, int seed_len, const int32_t* init_rows_host,
+                            const int32_t* len_of_row_host /* NULL: every row has L = T - seed_len - 1 */,
+                            const int32_t* image_of_row_host, const int32_t* group_of_row_host /* [R], or NULL */, int top_k,
+                            int n_steps, const int32_t* positions_host, const int32_t* n_mask_host, int snapshot_every,
+                            const czc_hyper* hp_of_row_host /* [R] */, const czc_draw* draw_of_row_host /* [R], or NULL */,
+                            const int32_t* rival_of_row_host /* [R, M], or NULL */, int M, const float* delta_of_row_host /* [R] */,
+                            const uint32_t* sets_host /* [n_sets, W] */, int n_sets, const int32_t* set_of_row_host /* [R] or NULL */,
+                            int32_t* out_ids, float* out_cos);
 
 /* Caption fluency: BERT's pseudo-log-likelihood of finished rows, on the device -- the BERT-side twin of czc_score_rows.
  * Lmax = T - seed_len - 1.  Row r has L_r = len_of_row[r] words at columns seed_len .. seed_len + L_r - 1 and T_r = seed_len + L_r + 1

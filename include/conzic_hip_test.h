@@ -262,6 +262,13 @@ int czc_test_bridge_cand(const czc_bridge_tables* t, int form, int B, int T, int
  * dot_rows [B]), 2 launch_softmax_mask_topk_rows_hp (hp_rows [B]: the row's temperature; dot_rows [B]) -> probs, idxs, cand [B*K]. */
 int czc_test_topk_rows(int form, int B, int V, int K, const float* logits, const float* mask, float temperature, int dot_id,
                        const int32_t* dot_rows, const czc_hyper* hp_rows, float* probs, int32_t* idxs, int32_t* cand);
+/* The same kernel with a vocabulary set per row (launch_softmax_mask_topk_rows_vocab, czc_generate_rows_vocab): set_rows [B] in
+ * [-1, n_sets) picks one of the bitsets bits [n_sets, W], W = ceil(V / 32); hp_rows [B] and dot_rows [B] as in form 2.  Checked on
+ * the host (CZC_ERR_ARG): every set index.  A null hp_rows, dot_rows, set_rows or bits, or a W other than ceil(V / 32), is the
+ * launcher's own refusal (CZC_TEST_REFUSED). */
+int czc_test_topk_rows_vocab(int B, int V, int K, const float* logits, const float* mask, int dot_id, const int32_t* dot_rows,
+                             const czc_hyper* hp_rows, const int32_t* set_rows, const uint32_t* bits, int n_sets, int W, float* probs,
+                             int32_t* idxs, int32_t* cand);
 
 /* ---- every GEMM family on strided, windowed and in-place buffers (csrc/gemm.hip, gemm256.hip, gemm_wreg.hip; host reference and
  * checker in tests/gemm_layout.py).  The kernel family a launch went to is recorded by the launcher (csrc/kernels.h GemmFamily): */

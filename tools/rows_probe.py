@@ -38,7 +38,16 @@ rival_of_row = NULL (czc_generate_rows_tied itself: the path without the feature
 images as every row's rivals and delta = --distinct.  Full-size towers, both logit scales (the screen-then-refine engine refuses
 rivals, so the published scale runs on the split-fp16 engine, where the runtime sends such a call); per scale the wall times of
 --reps alternating repetitions after one warm-up of each arm, each arm's spread, the ratio of the medians and the share of final
-captions the term changed.  `--describe_distinct profiles/r13_rival_probe.json` prints the README's sentence (no GPU needed)."""
+captions the term changed.  `--describe_distinct profiles/r13_rival_probe.json` prints the README's sentence (no GPU needed).
+
+    python tools/rows_probe.py --vocab [--S 16] [--reps 5] [--out profiles/r15_vocab_probe.json]
+
+The cost of vocabulary sets: S rows of one image under their own shuffle orders, one czc_generate_rows_vocab call with
+set_of_row = NULL (czc_generate_rows_vs itself, the path without the feature) against the same call in which every row carries a
+ban-list of 100 regular ids.  Full-size towers, both logit scales; arms alternated, one warm-up each.  Records per arm the wall
+times, their median and spread, the median ratio, and whether the set arm's ids are those of the NULL arm under a token mask with
+the 100 ids taken out by hand (property E).  `--describe_vocab profiles/r15_vocab_probe.json` prints the README's sentence (no GPU
+needed)."""
 import argparse
 import json
 import os
@@ -71,6 +80,8 @@ ap.add_argument("--sample_tau", type=float, default=None, metavar="T",
                 help="the draw leg: the rows call with every tau = 0 against the same call with every tau = T")
 ap.add_argument("--distinct", type=float, default=None, metavar="DELTA",
                 help="the rivals leg: the rows call with rival_of_row = NULL against the same call with 4 rivals per row")
+ap.add_argument("--vocab", action="store_true", help="the vocabulary-set leg: set_of_row = NULL against a ban-list of 100 ids in every row")
+ap.add_argument("--describe_vocab", default=None, metavar="JSON", help="print the README sentence for a vocabulary-leg result file and exit")
 ap.add_argument("--fluency_probe", action="store_true",
                 help="the fluency leg: Engine.fluency_rows on R captions of L words against the path without it (L steps that return "
                      "their logits row + a host log-softmax); R from --S")
@@ -79,7 +90,7 @@ ap.add_argument("--describe_distinct", default=None, metavar="JSON", help="print
 ap.add_argument("--describe_draw", default=None, metavar="JSON", help="print the README sentence for a draw-leg result file and exit")
 args = ap.parse_args()
 if args.out is None:
-    args.out = os.path.join(ROOT, "profiles", "r14_fluency_probe.json" if args.fluency_probe else "r13_rival_probe.json" if args.distinct else "r11_draw_probe.json" if args.sample_tau else "r10_signals_probe.json" if args.signals else "r09_lengths_probe.json" if args.lengths else
+    args.out = os.path.join(ROOT, "profiles", "r15_vocab_probe.json" if args.vocab else "r14_fluency_probe.json" if args.fluency_probe else "r13_rival_probe.json" if args.distinct else "r11_draw_probe.json" if args.sample_tau else "r10_signals_probe.json" if args.signals else "r09_lengths_probe.json" if args.lengths else
                             "r09_memo_rows_probe.json" if args.memo_rows else "r08_rows_probe.json")
 
 L, K, SEED_LEN = args.L, args.K, 4
@@ -122,6 +133,25 @@ def describe_distinct(records):
 
 if args.describe_distinct:
     print(describe_distinct(json.load(open(args.describe_distinct))))
+    sys.exit(0)
+
+
+def describe_vocab(records):
+    """The README's sentence, from the records of a result file: a ratio inside the NULL arm's own spread is "no measurable cost"."""
+    parts = []
+    for r in records:
+        inside = abs(r["ratio_median"] - 1.0) <= r["spread_null"]
+        parts.append(f"on the {r['precision']} engine {r['wall_s_null_median']:.3f} s with set_of_row = NULL (spread {100 * r['spread_null']:.1f} %) "
+                     f"and {r['wall_s_sets_median']:.3f} s with a ban-list of {r['banned']} ids in every row (spread "
+                     f"{100 * r['spread_sets']:.1f} %), ratio of the medians {r['ratio_median']:.3f}: "
+                     + ("no measurable cost" if inside else f"x{r['ratio_median']:.3f} the NULL arm")
+                     + f"; the ids are {'' if r['ids_identical_to_E'] else 'NOT '}those of the call without sets under the token mask with "
+                       f"the ids taken out by hand, and the list changed {r['captions_changed']} of {r['S']} final captions")
+    return "; ".join(parts)
+
+
+if args.describe_vocab:
+    print(describe_vocab(json.load(open(args.describe_vocab))))
     sys.exit(0)
 
 
@@ -406,7 +436,61 @@ def distinct_leg():
     print(describe_distinct(out))
 
 
-if args.fluency_probe:
+def vocab_leg():
+    from conzic_amd import lengths, vocab as vc
+    reps = max(args.reps, 5)
+    for scale in args.scales:
+        prec = runtime.choose_precision(scale)
+        su = harness.build_synthetic(False, prec, logit_scale=scale, regular_only=True)
+        eng = su.engine
+        eng.set_image_embeds(np.random.default_rng(100).standard_normal((1, su.clip_cfg.proj)).astype(np.float32))
+        mask = su.token_mask.reshape(-1).astype(np.float32)
+        banned = np.random.default_rng(7).choice(np.nonzero(mask > 0)[0], size=100, replace=False)
+        allowed = np.ones(mask.size, bool)
+        allowed[banned] = False
+        bits = vc.pack([allowed], mask.size)
+        for S in (args.S if args.S != [1, 2, 4, 8, 16] else [16]):
+            init = lengths.length_rows(su.bert_tok, "Image of a", [L] * S)
+            hps = [Engine.hyper(0.02, 2.0, 0.1) for _ in range(S)]
+            random.seed(42)
+            positions, n_mask, every, _ = harness.sample_schedules("shuffle", L, args.sweeps, S)
+            ior = np.zeros(S, dtype=np.int32)
+            arms = {"null": None, "sets": np.zeros(S, np.int32)}
+
+            def call(arm):
+                return eng.generate_rows_vocab(init, None, SEED_LEN, K, positions, hps, sets=bits, set_of_row=arms[arm], image_of_row=ior,
+                                               n_mask=n_mask, snapshot_every=every)
+
+            warm = {arm: call(arm) for arm in arms}
+            eng.set_token_mask(mask * allowed)   # property E: the NULL arm under the mask with the ids taken out by hand
+            by_hand = call("null")
+            eng.set_token_mask(mask)
+            times = {arm: [] for arm in arms}
+            for _ in range(reps):
+                for arm in arms:
+                    eng.sync()
+                    t0 = time.perf_counter()
+                    call(arm)
+                    times[arm].append(time.perf_counter() - t0)
+            rec = dict(logit_scale=scale, precision=runtime.PRECISION_NAMES[prec], S=S, L=L, K=K, sweeps=args.sweeps, order="shuffle",
+                       images=1, banned=int(banned.size), reps=reps)
+            for arm in arms:
+                rec.update({f"wall_s_{arm}": times[arm], f"wall_s_{arm}_median": float(np.median(times[arm])),
+                            f"spread_{arm}": spread(times[arm])})
+            rec["ratio_median"] = rec["wall_s_sets_median"] / rec["wall_s_null_median"]
+            rec["ratio_inside_null_spread"] = bool(abs(rec["ratio_median"] - 1.0) <= rec["spread_null"])
+            rec["ids_identical_to_E"] = bool(np.array_equal(warm["sets"][0], by_hand[0]))
+            rec["cos_bits_identical_to_E"] = bool(np.array_equal(warm["sets"][1].view(np.int32), by_hand[1].view(np.int32)))
+            rec["captions_changed"] = int((warm["null"][0][-1] != warm["sets"][0][-1]).any(axis=1).sum())
+            print(json.dumps(rec), flush=True)
+            out.append(rec)
+        eng.close()
+    print(describe_vocab(out))
+
+
+if args.vocab:
+    vocab_leg()
+elif args.fluency_probe:
     fluency_leg()
 elif args.distinct:
     distinct_leg()
@@ -418,7 +502,7 @@ elif args.signals:
     signals_leg()
 elif args.lengths:
     lengths_leg()
-for scale in ([] if args.fluency_probe or args.memo_rows or args.lengths or args.signals or args.sample_tau or args.distinct else args.scales):
+for scale in ([] if args.vocab or args.fluency_probe or args.memo_rows or args.lengths or args.signals or args.sample_tau or args.distinct else args.scales):
     prec = runtime.choose_precision(scale)
     su = harness.build_synthetic(False, prec, logit_scale=scale, regular_only=True)
     eng = su.engine

@@ -52,6 +52,26 @@ class ImageEmbeds:
         self.embeds = np.ascontiguousarray(np.asarray(embeds, dtype=np.float32))
 
 
+class ImageRegions:
+    """Boxes of one picture, handed over in place of an image (alone, or inside a list mixed with plain images): it expands
+    to len(boxes) rows, in order, row i being what `image.crop(boxes[i])` would give -- cropped, resized and staged on the
+    device in one call (czc_preprocess_regions_u8) where the device processor applies.  `image`: PIL image or uint8 [H, W, 3];
+    `boxes`: (x0, y0, x1, y1) in PIL's crop convention, inside the image (conzic_amd.regions.check_boxes)."""
+
+    def __init__(self, image, boxes):
+        self.image = image
+        self.boxes = [tuple(int(v) for v in b) for b in boxes]
+        if not self.boxes or any(len(b) != 4 for b in self.boxes):
+            raise ValueError("ImageRegions needs at least one box (x0, y0, x1, y1)")
+
+    def __len__(self):
+        return len(self.boxes)
+
+
+def _rgb_array(im) -> np.ndarray:
+    return im if isinstance(im, np.ndarray) else np.asarray(im.convert("RGB"))
+
+
 class CLIP:
     def __init__(self, model_name=None):
         self.model = None
@@ -135,8 +155,12 @@ class CLIP:
         # identity alone would serve stale embeddings to a caller that refills the same buffer / PIL object in place:
         # the key also carries a content fingerprint (size, mode / dtype and a hash of every pixel byte); objects that
         # cannot be fingerprinted are never cached
+        # (an ImageRegions is keyed by its picture and its boxes: the same picture under other boxes is another entry)
+        boxes = [tuple(im.boxes) if isinstance(im, ImageRegions) else None for im in imgs]
+        imgs = [im.image if isinstance(im, ImageRegions) else im for im in imgs]
         prints = [_fingerprint(im) for im in imgs]
-        key = None if any(fp is None for fp in prints) else tuple((id(im), fp) for im, fp in zip(imgs, prints))
+        key = None if any(fp is None for fp in prints) else tuple(
+            (id(im), fp) if bx is None else (id(im), fp, bx) for im, fp, bx in zip(imgs, prints, boxes))
         cached = getattr(self, "_img_cache", None)
         if key is None:
             self._img_cache = None
@@ -157,7 +181,48 @@ class CLIP:
         last = getattr(self, "_last_embeds", None)
         return None if last is None else last.copy()
 
+    def _encode_regions_uncached(self, items):
+        """A list that holds at least one ImageRegions: every plain image is one row, every ImageRegions len(boxes) rows, in
+        order.  On the device path the rows are staged slot by slot -- a run of consecutive ImageRegions of one picture through
+        ONE regions call -- and encoded as one batch; otherwise the boxes are cropped in PIL and the crops go the way whole
+        images go."""
+        from conzic_amd import regions as rg
+        std_cfg = self._device_processor_params() if self.processor is not None else None
+        if self.processor is not None and std_cfg is None:
+            from PIL import Image
+            crops = []
+            for it in items:
+                if isinstance(it, ImageRegions):
+                    pil = Image.fromarray(it.image) if isinstance(it.image, np.ndarray) else it.image
+                    rg.check_boxes(it.boxes, pil.size[0], pil.size[1])
+                    crops.extend(pil.crop(b) for b in it.boxes)
+                else:
+                    crops.append(it)
+            return self._encode_images_uncached(crops)
+        mean, std = (None, None) if std_cfg is None else std_cfg
+        eng, S, slot, i = self._eng(), self._image_size(), 0, 0
+        while i < len(items):
+            it = items[i]
+            if not isinstance(it, ImageRegions):
+                eng.preprocess_u8(_rgb_array(it), slot, mean=mean, std=std)
+                slot, i = slot + 1, i + 1
+                continue
+            boxes = list(it.boxes)
+            j = i + 1
+            while j < len(items) and isinstance(items[j], ImageRegions) and items[j].image is it.image:
+                boxes.extend(items[j].boxes)
+                j += 1
+            rgb = _rgb_array(it.image)
+            for lo in range(0, len(boxes), native.MAX_REGIONS):   # (a call takes up to CZC_MAX_REGIONS boxes)
+                part = rg.check_boxes(boxes[lo:lo + native.MAX_REGIONS], rgb.shape[1], rgb.shape[0], S)
+                eng.preprocess_regions_u8(rgb, part, slot + lo, mean=mean, std=std)
+            slot, i = slot + len(boxes), j
+        return _wrap(eng.encode_staged(slot))
+
     def _encode_images_uncached(self, image):
+        items = image if isinstance(image, (list, tuple)) else [image]
+        if any(isinstance(it, ImageRegions) for it in items):
+            return self._encode_regions_uncached(list(items))
         if self.processor is not None:
             std_cfg = self._device_processor_params()
             if std_cfg is not None:  # the checkpoint's processor is the standard CLIP one: run it on the device

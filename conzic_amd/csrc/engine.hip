@@ -194,6 +194,7 @@ struct czc_engine {
   split_t* d_index = nullptr; int64_t index_n = 0;
   int index_groups = 0;
   int fluency_chunk = 1024;  // czc_fluency_rows: expanded sequences per BERT forward (option "fluency_chunk", 1..16384)
+  int regions_chunk = 64;    // czc_preprocess_regions_u8: regions per upload and launch pair (option "regions_chunk", 1..1024)
 };
 
 namespace {
@@ -1662,7 +1663,7 @@ int czc_replicate(czc_engine* p, czc_engine** out) {
   e->refine = p->refine; e->refine_theta_x = p->refine_theta_x; e->refine_samples = p->refine_samples; e->refine_samples_step = p->refine_samples_step;
   e->refine_guard_dev = p->refine_guard_dev; e->refine_gate_delta = p->refine_gate_delta; e->refine_theta_gen = p->refine_theta_gen;
   e->refine_rows16 = p->refine_rows16; e->refine_rows16_factor = p->refine_rows16_factor;
-  e->memo = p->memo; e->memo_rows = p->memo_rows; e->fluency_chunk = p->fluency_chunk;
+  e->memo = p->memo; e->memo_rows = p->memo_rows; e->fluency_chunk = p->fluency_chunk; e->regions_chunk = p->regions_chunk;
   e->w = p->w; e->bert = p->bert; e->ctext = p->ctext; e->cvis = p->cvis; e->ctext_x = p->ctext_x;
   e->mlm_dense_w = p->mlm_dense_w; e->decoder_w = p->decoder_w; e->tproj_w = p->tproj_w; e->vproj_w = p->vproj_w;
   e->patch_w = p->patch_w; e->tproj_wx = p->tproj_wx;
@@ -1977,6 +1978,80 @@ int czc_preprocess_u8(czc_engine* e, const uint8_t* rgb, int height, int width, 
   if (pixels_out) E_HIP(hipMemcpyAsync(pixels_out, dst, img * 4, hipMemcpyDefault, e->st));
   E_HIP(hipStreamSynchronize(e->st));
   if (slot + 1 > e->staged_n) e->staged_n = slot + 1;
+  return CZC_OK;
+}
+
+// N boxes of one image into staged slots slot0 .. slot0 + n - 1: slot slot0 + i = czc_preprocess_u8 of the contiguous copy of
+// rgb[y0:y1, x0:x1], bit for bit.  One upload of the image; per chunk of "regions_chunk" boxes one upload of descriptors and
+// window tables, two launches and one synchronisation (the chunk's host staging must have left before it is rebuilt).
+int czc_preprocess_regions_u8(czc_engine* e, const uint8_t* rgb, int height, int width, const int32_t* boxes, int n, const float* mean,
+                              const float* stdv, int slot0, float* pixels_out) {
+  if (!e) return CZC_ERR_ARG;
+  if (!rgb || !boxes || !mean || !stdv) return fail(e, CZC_ERR_ARG, "preprocess_regions: null argument%s");
+  if (n < 1 || n > CZC_MAX_REGIONS) return fail(e, CZC_ERR_ARG, "preprocess_regions: the number of regions is outside [1, 1024]%s");
+  if (slot0 < 0) return fail(e, CZC_ERR_ARG, "preprocess_regions: slot0 is negative%s");
+  if (slot0 > (1 << 20)) return fail(e, CZC_ERR_ARG, "preprocess_regions: slot0 above 2^20%s");  // (slot0 + n stays an int)
+  if (height <= 0 || width <= 0 || (long)height * width > (1L << 28)) return fail(e, CZC_ERR_ARG, "preprocess_regions: bad image size%s");
+  const int S = e->cfg.vis_image;
+  for (int i = 0; i < n; ++i) {
+    const int x0 = boxes[4 * i], y0 = boxes[4 * i + 1], x1 = boxes[4 * i + 2], y1 = boxes[4 * i + 3];
+    if (x0 < 0 || y0 < 0 || x1 > width || y1 > height || x0 >= x1 || y0 >= y1) {
+      snprintf(e->err, sizeof(e->err), "preprocess_regions: box %d = (%d, %d, %d, %d) is empty or leaves the %dx%d image", i, x0, y0, x1,
+               y1, width, height);
+      return CZC_ERR_ARG;
+    }
+    const int bw = x1 - x0, bh = y1 - y0;
+    const double longest = bw <= bh ? (double)S * bh / bw : (double)S * bw / bh;
+    if (longest > (double)(1 << 24)) {
+      snprintf(e->err, sizeof(e->err), "preprocess_regions: box %d = (%d, %d, %d, %d) resizes to a long side above 2^24", i, x0, y0, x1, y1);
+      return CZC_ERR_ARG;
+    }
+  }
+  E_HIP(hipSetDevice(e->dev));
+  const size_t img = (size_t)3 * S * S;
+  // the plans first: a chunk that cannot be laid out refuses the call before the staged batch is touched
+  const int chunk = e->regions_chunk, n_chunk = (n + chunk - 1) / chunk;
+  std::vector<RegionsPlan> plans((size_t)n_chunk);
+  size_t scratch_bytes = 0;
+  for (int c = 0; c < n_chunk; ++c) {
+    const int lo = c * chunk, cnt = std::min(chunk, n - lo);
+    if (plan_clip_regions(S, boxes + 4 * (size_t)lo, cnt, plans[c])) return fail(e, CZC_ERR_ARG, "%s", g_err);
+    scratch_bytes = std::max(scratch_bytes, plans[c].scratch_bytes);
+  }
+  // staged batch grows by doubling and keeps its contents
+  if (slot0 + n > e->staged_cap) {
+    int cap = e->staged_cap ? e->staged_cap : 8;
+    while (cap < slot0 + n) cap *= 2;
+    float* nb = nullptr;
+    E_HIP(hipMalloc((void**)&nb, (size_t)cap * img * 4));
+    if (e->d_staged) {
+      E_HIP(hipMemcpyAsync(nb, e->d_staged, (size_t)e->staged_cap * img * 4, hipMemcpyDeviceToDevice, e->st));
+      E_HIP(hipStreamSynchronize(e->st));
+      E_HIP(hipFree(e->d_staged));
+    }
+    e->d_staged = nb;
+    e->staged_cap = cap;
+  }
+  unsigned char *d_rgb, *scratch;
+  E_CHECK(ensure(e, "pp_rgb", (size_t)height * width * 3, (void**)&d_rgb));
+  E_CHECK(ensure(e, "pp_scratch", scratch_bytes, (void**)&scratch));
+  E_HIP(hipMemcpyAsync(d_rgb, rgb, (size_t)height * width * 3, hipMemcpyDefault, e->st));
+  float* dst = e->d_staged + (size_t)slot0 * img;
+  for (int c = 0; c < n_chunk; ++c) {
+    {
+      ProfScope ps(e, "rowops", 0);
+      if (launch_clip_regions(d_rgb, width, S, plans[c], mean, stdv, scratch, dst + (size_t)c * chunk * img, e->st))
+        return fail(e, CZC_ERR_HIP, "%s", g_err);
+    }
+    // the next chunk overwrites the scratch in stream order; the host only waits where it frees a chunk's staging early
+    if (c + 1 < n_chunk) {
+      E_HIP(hipStreamSynchronize(e->st));
+      std::vector<unsigned char>().swap(plans[c].host);
+    }
+  }
+  if (pixels_out) E_HIP(hipMemcpyAsync(pixels_out, dst, (size_t)n * img * 4, hipMemcpyDefault, e->st));
+  E_HIP(hipStreamSynchronize(e->st));
+  if (slot0 + n > e->staged_n) e->staged_n = slot0 + n;
   return CZC_OK;
 }
 
@@ -3007,6 +3082,11 @@ int czc_set_option(czc_engine* e, const char* name, int value) {
     e->fluency_chunk = value;
     return CZC_OK;
   }
+  if (!strcmp(name, "regions_chunk")) {
+    if (value < 1 || value > CZC_MAX_REGIONS) return fail(e, CZC_ERR_ARG, "option %s: 1..1024", name);
+    e->regions_chunk = value;
+    return CZC_OK;
+  }
   if (!strcmp(name, "refine_rows16_x1000")) { e->refine_rows16_factor = value < 1000 ? 1.f : (float)value / 1000.f; return CZC_OK; }
   return fail(e, CZC_ERR_ARG, "unknown option %s", name);
 }
@@ -3021,7 +3101,7 @@ int czc_get_option(czc_engine* e, const char* name, int* value) {
       {"refine_samples", e->refine_samples}, {"refine_samples_step", e->refine_samples_step}, {"refine_theta_x1000", (int)lrintf(e->refine_theta_x * 1000.f)},
       {"refine_theta_gen_x1000", (int)lrintf(e->refine_theta_gen * 1000.f)},
       {"refine_guard_x1e6", (int)lrintf(e->refine_guard_dev * 1e6f)}, {"refine_gate_x1e6", (int)lrintf(e->refine_gate_delta * 1e6f)},
-      {"refine_rows16", e->refine_rows16}, {"memo", e->memo}, {"memo_rows", e->memo_rows}, {"index_groups", e->index_groups}, {"fluency_chunk", e->fluency_chunk}, {"refine_rows16_x1000", (int)lrintf(e->refine_rows16_factor * 1000.f)},
+      {"refine_rows16", e->refine_rows16}, {"memo", e->memo}, {"memo_rows", e->memo_rows}, {"index_groups", e->index_groups}, {"fluency_chunk", e->fluency_chunk}, {"regions_chunk", e->regions_chunk}, {"refine_rows16_x1000", (int)lrintf(e->refine_rows16_factor * 1000.f)},
       // read-only, derived: the trip point / gate bound in force inside czc_generate (x refine_rows16_factor on fp16 rows)
       {"refine_guard_generate_x1e6", (int)lrintf(e->refine_guard_dev * f16x * 1e6f)},
       {"refine_gate_generate_x1e6", (int)lrintf(e->refine_gate_delta * f16x * 1e6f)},

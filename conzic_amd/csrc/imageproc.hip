@@ -9,6 +9,7 @@
 // each through a uint8 intermediate, and a pass is skipped when that extent does not change -- all of which is
 // reproduced here so that the result is bit-identical to the host path (tests/test_imageproc_gpu.py).
 #include <cmath>
+#include <cstring>
 #include <vector>
 
 #include "kernels.h"
@@ -114,7 +115,206 @@ __global__ void resample_v_crop_norm_kernel(const unsigned char* in, int IH, int
   out[2 * plane + o] = __fdiv_rn(__fsub_rn(__fdiv_rn((float)v2, 255.0f), m2), d2);
 }
 
+// ---- regions: N boxes of one image per launch ---------------------------------------------------------------------------
+// A region is the contiguous copy of rgb[y0:y1, x0:x1] sent through the two kernels above (PIL: crop(box), then the processor).
+// Every output pixel of either pass is an independent integer sum, so the batched form computes only what the crop window
+// needs -- the S columns [left, left+S) of the horizontal pass on the source rows the window's vertical pass reads -- and
+// reads the box in place through the image's row stride.  The tables hold the window's S coordinates only, built by
+// precompute's per-coordinate arithmetic on the host (double precision; device code is compiled with contraction).
+struct RegionDesc {
+  int x0, y0;           // box origin in the source image
+  int left, top;        // crop window inside the resized box
+  int need_h, need_v;   // which passes run
+  int kh, kv;           // row length of the coefficient tables (precompute's ksize)
+  int row0, rows;       // box rows [row0, row0 + rows) the horizontal pass writes = those the window's vertical pass reads
+  int off_bh, off_ch, off_bv, off_cv;  // tables, in ints from the start of the chunk's table area
+  long long off_tmp;    // intermediate uint8 [rows][S][3], in bytes from the start of the chunk's intermediate area
+};
+
+// precompute for the output coordinates [first, first + count) only, appended to `bounds` / `coeff`: the same arithmetic per
+// coordinate, so the entries equal rows first.. of the full tables bit for bit
+int precompute_window(int in_size, int out_size, int first, int count, std::vector<int>& bounds, std::vector<int>& coeff) {
+  const double scale = (double)in_size / out_size;
+  double filterscale = scale;
+  if (filterscale < 1.0) filterscale = 1.0;
+  const double support = 2.0 * filterscale;
+  const int ksize = (int)std::ceil(support) * 2 + 1;
+  const size_t b0 = bounds.size(), c0 = coeff.size();
+  bounds.resize(b0 + (size_t)count * 2, 0);
+  coeff.resize(c0 + (size_t)count * ksize, 0);
+  std::vector<double> k(ksize);
+  for (int i = 0; i < count; ++i) {
+    const int xx = first + i;
+    const double center = 0.0 + (xx + 0.5) * scale;
+    double ww = 0.0;
+    const double ss = 1.0 / filterscale;
+    int xmin = (int)(center - support + 0.5);
+    if (xmin < 0) xmin = 0;
+    int xmax = (int)(center + support + 0.5);
+    if (xmax > in_size) xmax = in_size;
+    xmax -= xmin;
+    for (int x = 0; x < xmax; ++x) {
+      const double w = cubic((x + xmin - center + 0.5) * ss);
+      k[x] = w;
+      ww += w;
+    }
+    for (int x = 0; x < xmax; ++x) {
+      if (ww != 0.0) k[x] /= ww;
+      const double v = k[x];
+      coeff[c0 + (size_t)i * ksize + x] = v < 0 ? (int)(-0.5 + v * (1 << PREC_BITS)) : (int)(0.5 + v * (1 << PREC_BITS));
+    }
+    bounds[b0 + 2 * i] = xmin;
+    bounds[b0 + 2 * i + 1] = xmax;
+  }
+  return ksize;
+}
+
+// horizontal pass of the regions of a chunk that have one: blockIdx.y = region, one thread per pixel of its intermediate
+// tmp[r][c] = clip8(2^21 + sum_t box[row0 + r][xmin(left + c) + t] * k[left + c][t])
+__global__ void resample_h_regions_kernel(const unsigned char* rgb, int W, int S, const RegionDesc* desc, const int* tables,
+                                          unsigned char* tmp_base) {
+  const RegionDesc d = desc[blockIdx.y];
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (!d.need_h || i >= d.rows * S) return;
+  const int r = i / S, c = i - r * S;
+  const int xmin = tables[d.off_bh + 2 * c], n = tables[d.off_bh + 2 * c + 1];
+  const int* k = tables + d.off_ch + (size_t)c * d.kh;
+  int s0 = 1 << (PREC_BITS - 1), s1 = s0, s2 = s0;
+  const unsigned char* p = rgb + ((size_t)(d.y0 + d.row0 + r) * W + d.x0 + xmin) * 3;
+  for (int t = 0; t < n; ++t) {
+    const int w = k[t];
+    s0 += p[3 * t] * w; s1 += p[3 * t + 1] * w; s2 += p[3 * t + 2] * w;
+  }
+  unsigned char* o = tmp_base + d.off_tmp + (size_t)i * 3;
+  o[0] = (unsigned char)clip8(s0); o[1] = (unsigned char)clip8(s1); o[2] = (unsigned char)clip8(s2);
+}
+
+// vertical pass (or none) of the crop window, /255, normalise, HWC -> CHW, into the region's slot: blockIdx.y = region, one
+// thread per output pixel.  The source is the intermediate (row r = box row row0 + r, column c = resized column left + c) or,
+// where the horizontal pass is skipped, the box itself inside the image.
+__global__ void resample_v_crop_norm_regions_kernel(const unsigned char* rgb, int W, int S, const RegionDesc* desc,
+                                                    const int* tables, const unsigned char* tmp_base, float m0, float m1, float m2,
+                                                    float d0, float d1, float d2, float* out) {
+  const RegionDesc d = desc[blockIdx.y];
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= S * S) return;
+  const int y = i / S, x = i - y * S;
+  const unsigned char* src;   // pixel (box row row_base, the thread's column); consecutive box rows are `stride` bytes apart
+  size_t stride;
+  int row_base;               // box row of src
+  if (d.need_h) {
+    src = tmp_base + d.off_tmp + (size_t)x * 3;
+    stride = (size_t)S * 3;
+    row_base = d.row0;
+  } else {
+    src = rgb + ((size_t)d.y0 * W + d.x0 + d.left + x) * 3;
+    stride = (size_t)W * 3;
+    row_base = 0;
+  }
+  int v0, v1, v2;
+  if (d.need_v) {
+    const int ymin = tables[d.off_bv + 2 * y], n = tables[d.off_bv + 2 * y + 1];
+    const int* k = tables + d.off_cv + (size_t)y * d.kv;
+    int s0 = 1 << (PREC_BITS - 1), s1 = s0, s2 = s0;
+    const unsigned char* p = src + (size_t)(ymin - row_base) * stride;
+    for (int t = 0; t < n; ++t) {
+      const int w = k[t];
+      s0 += p[0] * w; s1 += p[1] * w; s2 += p[2] * w;
+      p += stride;
+    }
+    v0 = clip8(s0); v1 = clip8(s1); v2 = clip8(s2);
+  } else {
+    const unsigned char* p = src + (size_t)(d.top + y - row_base) * stride;
+    v0 = p[0]; v1 = p[1]; v2 = p[2];
+  }
+  // the three IEEE operations of resample_v_crop_norm_kernel
+  const size_t plane = (size_t)S * S;
+  float* o = out + (size_t)blockIdx.y * 3 * plane + i;
+  o[0] = __fdiv_rn(__fsub_rn(__fdiv_rn((float)v0, 255.0f), m0), d0);
+  o[plane] = __fdiv_rn(__fsub_rn(__fdiv_rn((float)v1, 255.0f), m1), d1);
+  o[2 * plane] = __fdiv_rn(__fsub_rn(__fdiv_rn((float)v2, 255.0f), m2), d2);
+}
+
 }  // namespace
+
+// The geometry of launch_clip_preprocess applied to boxes [n][4] (x0, y0, x1, y1; valid, checked by the caller): descriptors,
+// window tables and the layout of the intermediates of one chunk, all in plan.host (one upload).
+int plan_clip_regions(int S, const int* boxes, int n, RegionsPlan& plan) {
+  std::vector<RegionDesc> desc((size_t)n);
+  std::vector<int> bounds, coeff, tables;
+  long long tmp_bytes = 0;
+  int max_rows = 0, any_h = 0;
+  for (int r = 0; r < n; ++r) {
+    const int x0 = boxes[4 * r], y0 = boxes[4 * r + 1], W = boxes[4 * r + 2] - x0, H = boxes[4 * r + 3] - y0;
+    if (W <= 0 || H <= 0 || S <= 0) {
+      snprintf(g_err, sizeof(g_err), "preprocess_regions: bad box size %dx%d", W, H);
+      return 1;
+    }
+    int nw, nh;
+    if (W <= H) { nw = S; nh = (int)((double)S * H / W); }
+    else { nw = (int)((double)S * W / H); nh = S; }
+    if ((W == S && H == S)) { nw = W; nh = H; }
+    RegionDesc& d = desc[r];
+    memset(&d, 0, sizeof(d));
+    d.x0 = x0; d.y0 = y0;
+    d.need_h = nw != W; d.need_v = nh != H;
+    d.left = (nw - S) / 2; d.top = (nh - S) / 2;
+    if (d.need_v) {
+      bounds.clear(); coeff.clear();
+      d.kv = precompute_window(H, nh, d.top, S, bounds, coeff);
+      d.off_bv = (int)tables.size(); tables.insert(tables.end(), bounds.begin(), bounds.end());
+      d.off_cv = (int)tables.size(); tables.insert(tables.end(), coeff.begin(), coeff.end());
+      d.row0 = bounds[0];
+      d.rows = bounds[2 * (S - 1)] + bounds[2 * (S - 1) + 1] - d.row0;
+    } else {
+      d.row0 = d.top;
+      d.rows = S;
+    }
+    if (d.need_h) {
+      bounds.clear(); coeff.clear();
+      d.kh = precompute_window(W, nw, d.left, S, bounds, coeff);
+      d.off_bh = (int)tables.size(); tables.insert(tables.end(), bounds.begin(), bounds.end());
+      d.off_ch = (int)tables.size(); tables.insert(tables.end(), coeff.begin(), coeff.end());
+      d.off_tmp = tmp_bytes;
+      tmp_bytes += ((long long)d.rows * S * 3 + 15) & ~15LL;
+      if (d.rows > max_rows) max_rows = d.rows;
+      any_h = 1;
+    }
+    if (tables.size() > (size_t)1 << 30) {
+      snprintf(g_err, sizeof(g_err), "preprocess_regions: the tables of a chunk exceed 4 GiB (lower option regions_chunk)");
+      return 1;
+    }
+  }
+  const size_t desc_bytes = ((size_t)n * sizeof(RegionDesc) + 255) & ~(size_t)255;
+  const size_t table_bytes = (tables.size() * 4 + 255) & ~(size_t)255;
+  plan.host.assign(desc_bytes + table_bytes, 0);
+  memcpy(plan.host.data(), desc.data(), (size_t)n * sizeof(RegionDesc));
+  if (!tables.empty()) memcpy(plan.host.data() + desc_bytes, tables.data(), tables.size() * 4);
+  plan.n = n;
+  plan.tables_off = desc_bytes;
+  plan.tmp_off = desc_bytes + table_bytes;
+  plan.scratch_bytes = plan.tmp_off + (size_t)tmp_bytes + 256;
+  plan.max_rows = max_rows;
+  plan.any_h = any_h;
+  return 0;
+}
+
+// scratch: >= plan.scratch_bytes; out: slot of the chunk's first region.  plan.host must stay alive until the stream has
+// passed the copy (the caller synchronises once per chunk).
+int launch_clip_regions(const unsigned char* rgb_dev, int W, int S, const RegionsPlan& plan, const float* mean, const float* stdv,
+                        unsigned char* scratch, float* out, hipStream_t st) {
+  CZC_HIP_CHECK(hipMemcpyAsync(scratch, plan.host.data(), plan.host.size(), hipMemcpyHostToDevice, st));
+  const RegionDesc* desc = (const RegionDesc*)scratch;
+  const int* tables = (const int*)(scratch + plan.tables_off);
+  unsigned char* tmp = scratch + plan.tmp_off;
+  if (plan.any_h)
+    hipLaunchKernelGGL(resample_h_regions_kernel, dim3(cdiv((long)plan.max_rows * S, 256), plan.n), dim3(256), 0, st, rgb_dev, W, S,
+                       desc, tables, tmp);
+  hipLaunchKernelGGL(resample_v_crop_norm_regions_kernel, dim3(cdiv((long)S * S, 256), plan.n), dim3(256), 0, st, rgb_dev, W, S,
+                     desc, tables, tmp, mean[0], mean[1], mean[2], stdv[0], stdv[1], stdv[2], out);
+  CZC_HIP_CHECK(hipGetLastError());
+  return 0;
+}
 
 // rgb_dev: uint8 [H][W][3] on the device; scratch: >= H*NW*3 bytes + room for the tables (see imageproc_scratch_bytes)
 size_t imageproc_scratch_bytes(int H, int W, int S) {

@@ -1,5 +1,7 @@
 // Host-side launchers of the gfx950 kernels (one translation unit per kernel family).
 #pragma once
+#include <vector>
+
 #include "common.h"
 
 namespace czc {
@@ -85,6 +87,18 @@ extern int g_wreg_min_m, g_gemm256_min_m;  // row-count thresholds of the two bi
 size_t imageproc_scratch_bytes(int H, int W, int S);
 int launch_clip_preprocess(const unsigned char* rgb_dev, int H, int W, int S, const float* mean, const float* stdv,
                            unsigned char* scratch, float* out, hipStream_t st);
+// The same for N boxes of one resident image (a region = the contiguous copy of rgb[y0:y1, x0:x1] through the path above, bit
+// for bit), one chunk per call: plan_clip_regions lays out the descriptors, the crop windows' coefficient tables (host
+// arithmetic of the single-image path) and the intermediates; launch_clip_regions uploads plan.host in one copy and runs the
+// two batched kernels, region r of the chunk into out + r * 3 * S * S.
+struct RegionsPlan {
+  std::vector<unsigned char> host;  // descriptors, then tables: the upload
+  size_t tables_off = 0, tmp_off = 0, scratch_bytes = 0;
+  int n = 0, max_rows = 0, any_h = 0;
+};
+int plan_clip_regions(int S, const int* boxes, int n, RegionsPlan& plan);
+int launch_clip_regions(const unsigned char* rgb_dev, int W, int S, const RegionsPlan& plan, const float* mean, const float* stdv,
+                        unsigned char* scratch, float* out, hipStream_t st);
 
 // ---- rowops.hip -------------------------------------------------------------------------
 // y = LN(x[row_idx ? row_idx[m] : m]) ; x fp32 [*,H]; outputs optional

@@ -114,10 +114,43 @@ def get_args(argv=None):
     p.add_argument("--pick_lambda", type=float, default=None, metavar="LAMBDA",
                    help="implies --fluency; needs --samples_num > 1: log, per image, the \"picked caption\": the sample whose final "
                         "caption has the largest cosine + LAMBDA x mean log p (the \"best caption\" lines stay as they are)")
+    p.add_argument("--regions", type=str, default=None, metavar="\"x0,y0,x1,y1;...\"",
+                   help="demo_cli: caption these boxes of the picture instead of the whole picture (PIL's crop convention: pixel "
+                        "coordinates, x1 and y1 exclusive); all boxes are cropped, resized and staged on the device in one call and "
+                        "are the images of the batch from then on, so every other flag applies to them; with --distinct each box "
+                        "is described by what sets it apart from the other boxes")
+    p.add_argument("--region_grid", type=str, default=None, metavar="RxC",
+                   help="demo_cli: the R x C tiles of the picture as regions (before those of --regions)")
+    p.add_argument("--region_full", action="store_true",
+                   help="demo_cli: with --regions / --region_grid, the whole frame as the first region")
+    p.add_argument("--regions_file", type=str, default=None, metavar="FILE.json",
+                   help="run_cli: JSON {file name: [[x0,y0,x1,y1], ...]}; an image with an entry is captioned box by box (keys "
+                        "name#x0,y0,x1,y1 in the output files), one without is captioned whole; with --distinct the rivals of a "
+                        "region are the other regions of its picture")
     from conzic_amd import vocab as vc
     vc.add_arguments(p)
     a = p.parse_args(argv)
     vc.check_arguments(p, a)
+    if a.regions is not None or a.region_grid is not None:
+        from conzic_amd import regions as rg
+        try:
+            a.regions = rg.parse_boxes(a.regions) if a.regions is not None else []
+            a.region_grid = rg.parse_grid(a.region_grid) if a.region_grid is not None else None
+        except ValueError as exc:
+            p.error(f"--regions / --region_grid: {exc}")
+        if a.batch_size != 1:
+            p.error("--regions / --region_grid cut ONE picture into the images of the batch: --batch_size 1")
+        if a.regions_file is not None:
+            p.error("--regions / --region_grid belong to conzic_amd.demo_cli, --regions_file to conzic_amd.run_cli")
+    elif a.region_full:
+        p.error("--region_full adds the whole frame to --regions / --region_grid")
+    if a.regions is not None or a.regions_file is not None:
+        flag = "--regions_file" if a.regions_file is not None else "--regions / --region_grid"
+        if a.run_type in ("infill", "retrieve"):
+            p.error(f"{flag} does not combine with --run_type {a.run_type} (the engine call stages regions for any caller; the "
+                    "command-line plumbing does not yet)")
+        if a.rival_images is not None:
+            p.error(f"{flag} does not combine with --rival_images (the rivals of a region are the other regions of its picture)")
     if a.pick_lambda is not None:
         if not (a.pick_lambda == a.pick_lambda) or a.pick_lambda in (float("inf"), float("-inf")):
             p.error("--pick_lambda must be finite")
@@ -257,7 +290,28 @@ def main(argv=None):
         images = [Image.open(args.caption_img_path).convert("RGB")]
     image_instance = images if args.batch_size > 1 else images[0]
     img_name = [f"img{j}" for j in range(args.batch_size)]
+    if args.regions_file is not None:
+        raise SystemExit("--regions_file belongs to conzic_amd.run_cli; here: --regions \"x0,y0,x1,y1;...\" / --region_grid RxC")
+    if args.regions is not None:
+        # the boxes of the picture are the images of the batch from here on: one regions call stages them all
+        from clip.clip import ImageRegions
+        from conzic_amd import regions as rg
+        width, height = images[0].size
+        try:
+            boxes = ([(0, 0, width, height)] if args.region_full else []) \
+                + (rg.grid_boxes(width, height, *args.region_grid) if args.region_grid else []) + list(args.regions)
+            boxes = rg.check_boxes(boxes, width, height, clip._image_size())
+        except ValueError as exc:
+            raise SystemExit(f"--regions / --region_grid: {exc}")
+        image_instance = ImageRegions(images[0], boxes)
+        img_name = [rg.region_name(img_name[0], b) for b in boxes]   # (logs and the seeds of --sample_tau name the box)
+        args.batch_size = len(boxes)
     rivals = args.distinct_rivals if args.distinct else None
+    if args.distinct and args.regions is not None and args.batch_size >= 2:
+        # rivals scoped to the picture: a region against the nearest other regions of the same picture
+        from conzic_amd import rivals as rv
+        emb = np.asarray(clip.compute_image_representation_from_image_instance(image_instance), dtype=np.float32)
+        rivals = rv.rival_table(emb, min(args.distinct_rivals, args.batch_size - 1), group_of_image=[0] * args.batch_size)
     if args.distinct and args.rival_images:
         # the rival images ride behind the captioned ones in the resident batch; every captioned image is scored against all of them
         B, E = args.batch_size, len(args.rival_images)

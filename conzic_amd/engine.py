@@ -328,6 +328,36 @@ class Engine:
             self.preprocess_u8(im, i, mean=mean, std=std)
         return self.encode_staged(len(images))
 
+    def preprocess_regions_u8(self, rgb, boxes, slot0: int = 0, want_pixels: bool = False, mean=None, std=None):
+        """N boxes of one image in one call (czc_preprocess_regions_u8): rgb uint8 [H,W,3], boxes int [N,4] = x0, y0, x1, y1
+        (PIL's crop convention) -> staged slots slot0 .. slot0 + N - 1, each what preprocess_u8 gives for rgb[y0:y1, x0:x1];
+        returns the fp32 [N,3,S,S] pixels when want_pixels."""
+        from .synth import CLIP_MEAN, CLIP_STD
+        rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError("rgb must be uint8 [H, W, 3]")
+        bx = np.asarray(boxes, dtype=np.int64).reshape(-1, 4)
+        if bx.size and np.abs(bx).max() >= 2 ** 31:
+            raise ValueError("a box coordinate outside int32")
+        bx = np.ascontiguousarray(bx, dtype=np.int32)
+        m = np.ascontiguousarray(CLIP_MEAN if mean is None else mean, dtype=np.float32)
+        d = np.ascontiguousarray(CLIP_STD if std is None else std, dtype=np.float32)
+        S = self.clip_cfg.v_image
+        out = np.empty((bx.shape[0], 3, S, S), dtype=np.float32) if want_pixels else None
+        self._ck(self.lib.czc_preprocess_regions_u8(self.h, rgb.ctypes.data, rgb.shape[0], rgb.shape[1], bx.ctypes.data,
+                                                    bx.shape[0], m.ctypes.data, d.ctypes.data, int(slot0),
+                                                    out.ctypes.data if want_pixels else None), "czc_preprocess_regions_u8")
+        return out
+
+    def encode_regions(self, image, boxes, mean=None, std=None) -> np.ndarray:
+        """PIL image / uint8 array and N boxes -> image_embeds [N, proj]: the regions call at slot 0, then encode_staged(N);
+        equal to encode_pil of the N host crops bit for bit (same pixels, same batch shape)."""
+        if not isinstance(image, np.ndarray):
+            image = np.asarray(image.convert("RGB"))
+        n = int(np.size(boxes)) // 4
+        self.preprocess_regions_u8(image, boxes, 0, mean=mean, std=std)
+        return self.encode_staged(n)
+
     def set_image_embeds(self, embeds):
         e = np.ascontiguousarray(embeds, dtype=np.float32)
         self._ck(self.lib.czc_set_image_embeds(self.h, e.ctypes.data, e.shape[0]), "czc_set_image_embeds")

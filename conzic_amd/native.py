@@ -29,7 +29,8 @@ CLIP_MAX_LEN = 77
 MAX_BERT_LEN = 64   # include/conzic_hip.h CZC_MAX_BERT_LEN: tokens of a BERT row, [CLS] and [SEP] included
 MAX_VOCAB_SETS = 4096  # include/conzic_hip.h CZC_MAX_VOCAB_SETS: vocabulary sets of a call (czc_generate_rows_vocab)
 MAX_RIVALS = 16    # include/conzic_hip.h CZC_MAX_RIVALS: rival images of a row (czc_generate_rows_vs)
-INDEX_MAX_K = 64  # include/conzic_hip.h CZC_INDEX_MAX_K: the largest k of czc_index_search
+MAX_REGIONS = 1024  # include/conzic_hip.h CZC_MAX_REGIONS: boxes of a czc_preprocess_regions_u8 call
+INDEX_MAX_K = 64 # include/conzic_hip.h CZC_INDEX_MAX_K: the largest k of czc_index_search
 POS_IDLE = -1   # include/conzic_hip.h CZC_POS_IDLE: the row sits the step out (czc_generate_rows_from)
 
 
@@ -111,6 +112,7 @@ SIGNATURES = {
     "czc_set_control_callback": (_I, [_P, _P, _P]),
     "czc_encode_images": (_I, [_P, _P, _I, _P]),
     "czc_preprocess_u8": (_I, [_P, _P, _I, _I, _P, _P, _I, _P]),
+    "czc_preprocess_regions_u8": (_I, [_P, _P, _I, _I, _P, _I, _P, _P, _I, _P]),
     "czc_encode_staged": (_I, [_P, _I, _P]),
     "czc_set_image_embeds": (_I, [_P, _P, _I]),
     "czc_encode_text": (_I, [_P, _P, _P, _I, _P]),

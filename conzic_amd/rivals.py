@@ -18,10 +18,24 @@ import numpy as np
 MAX_RIVALS = 16  # include/conzic_hip.h CZC_MAX_RIVALS
 
 
-def rival_table(embeds, M: int, sets: Optional[Sequence[int]] = None) -> np.ndarray:
+def rival_table(embeds, M: int, sets: Optional[Sequence[int]] = None,
+                group_of_image: Optional[Sequence[int]] = None) -> np.ndarray:
     """int32 [B, M]: for image b the up to M OTHER images of its set with the highest image-image cosine (float64), best first,
     ties broken by the lowest index; -1 fills the tail of a set smaller than M + 1.  `sets` int [B]: the set id of every image
-    (None: the whole batch is one set).  `embeds` [B, D] need not be normalised."""
+    (None: the whole batch is one set).  `embeds` [B, D] need not be normalised.
+    `group_of_image` int [B]: the picture every image of the batch was cut from (conzic_amd.regions): an image's rivals are
+    chosen among the images of its own group only, so the regions of one picture become each other's rivals and a group of one
+    gets none.  With `sets` as well, a rival shares both.  None: the function is what it was."""
+    if group_of_image is not None:
+        grp = np.asarray(group_of_image, dtype=np.int64).reshape(-1)
+        if sets is None:
+            sets = grp
+        else:
+            st = np.asarray(sets, dtype=np.int64).reshape(-1)
+            if st.size != grp.size:
+                raise ValueError(f"rival_table: sets has {st.size} entries and group_of_image {grp.size}")
+            _, sets = np.unique(np.stack([st, grp], axis=1), axis=0, return_inverse=True)   # one id per (set, group) pair
+            sets = np.asarray(sets).reshape(-1)
     e = np.asarray(embeds, dtype=np.float64)
     if e.ndim != 2 or e.shape[0] < 1:
         raise ValueError(f"rival_table: embeds must be [B, D], got {e.shape}")

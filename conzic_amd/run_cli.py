@@ -51,6 +51,50 @@ def batches(names, batch_size):
         yield names[s:s + batch_size]
 
 
+def region_rows(name_batch, region_map):
+    """--regions_file: the rows of a batch of pictures -> (names, group_of_image).  A picture with an entry gives one row per box,
+    named regions.region_name(name, box); a picture without gives one row under its own name.  group_of_image[i] = the position
+    in `name_batch` of the picture row i was cut from.  Without a map: the batch itself."""
+    if not region_map:
+        return list(name_batch), list(range(len(name_batch)))
+    from conzic_amd.regions import region_name
+    names, groups = [], []
+    for g, name in enumerate(name_batch):
+        boxes = region_map.get(name)
+        names.extend([name] if boxes is None else [region_name(name, b) for b in boxes])
+        groups.extend([g] * (1 if boxes is None else len(boxes)))
+    return names, groups
+
+
+def load_batch(img_dir, name_batch, region_map):
+    """The images of a batch as the encoder takes them: a picture with an entry in the map as clip.ImageRegions (all its boxes
+    staged by one device call), the others whole, as without the map."""
+    from PIL import Image
+    from clip.clip import ImageRegions
+    imgs = [Image.open(os.path.join(img_dir, n)).convert("RGB") for n in name_batch]
+    if not region_map:
+        return imgs
+    return [ImageRegions(im, region_map[n]) if n in region_map else im for im, n in zip(imgs, name_batch)]
+
+
+def region_rivals(args, clip, imgs, groups):
+    """--distinct: the M nearest others of the batch, or under --regions_file the table scoped to the picture -- a region against
+    the other regions of its picture (rivals.rival_table's group_of_image; a picture captioned whole is a group of one and gets
+    no rivals)."""
+    if not args.distinct:
+        return None
+    if args.regions_file is None:
+        return args.distinct_rivals
+    import numpy as np
+    from clip.clip import ImageEmbeds
+    from conzic_amd import rivals as rv
+    emb = imgs.embeds if isinstance(imgs, ImageEmbeds) else np.asarray(clip.compute_image_representation_from_image_instance(imgs),
+                                                                       dtype=np.float32)
+    if len(groups) < 2:
+        raise SystemExit("--distinct needs rival images: at least two rows in a batch")
+    return rv.rival_table(emb, min(args.distinct_rivals, len(groups) - 1), group_of_image=groups)
+
+
 def batched_samples(args, run_type, all_batches, own_lo, own_hi, rank, world, img_dir, lm_model, clip, lm_tokenizer, token_mask,
                     logger):
     """--batch_samples: every batch polishes its samples_num samples in one engine call (runtime.run_generation_samples).  The
@@ -71,15 +115,16 @@ def batched_samples(args, run_type, all_batches, own_lo, own_hi, rank, world, im
         logger.info(f"The {batch_idx + 1}-th batch:")
         cols = [s * nb + batch_idx for s in range(S)]   # the serial loop walks samples outside, batches inside
         sched = (positions[:, cols], n_mask, every, None if order_lists is None else [order_lists[c] for c in cols])
-        imgs = [Image.open(os.path.join(img_dir, n)).convert("RGB") for n in name_batch]
+        imgs = load_batch(img_dir, name_batch, args.region_map)
+        name_batch, groups = region_rows(name_batch, args.region_map)   # (--regions_file: one row per box)
         fluency = [] if args.fluency else False   # --fluency: this batch's records (runtime._fluency_after)
         outs = caption_samples(S, args.run_type, name_batch, lm_model, clip, lm_tokenizer, imgs, token_mask, logger,
-                               prompt=args.prompt, batch_size=args.batch_size, max_len=args.sentence_len, top_k=args.candidate_k,
+                               prompt=args.prompt, batch_size=len(name_batch), max_len=args.sentence_len, top_k=args.candidate_k,
                                temperature=args.lm_temperature, max_iter=args.num_iterations, alpha=args.alpha, beta=args.beta,
                                generate_order=args.order, gamma=args.gamma, ctl_type=args.control_type,
                                style_type=args.sentiment_type, pos_type=args.pos_type, schedules=sched,
                                sample_tau=args.sample_tau, sample_seed=args.seed,
-                               rivals=args.distinct_rivals if args.distinct else None, delta=args.distinct, fluency=fluency,
+                               rivals=region_rivals(args, clip, imgs, groups), delta=args.distinct, fluency=fluency,
                                vocab=vocab)
         if S > 1:
             from conzic_amd.diversity import log_distinct
@@ -133,9 +178,10 @@ def lengths_batches(args, run_type, all_batches, own_lo, own_hi, rank, world, im
             if batch_idx in embed_cache:
                 imgs = ImageEmbeds(embed_cache[batch_idx])
             else:
-                imgs = [Image.open(os.path.join(img_dir, n)).convert("RGB") for n in name_batch]
+                imgs = load_batch(img_dir, name_batch, args.region_map)
+            name_batch, _ = region_rows(name_batch, args.region_map)   # (--regions_file: one row per box)
             outs = caption_lengths(lens, per_call, args.run_type, name_batch, lm_model, clip, lm_tokenizer, imgs, token_mask, logger,
-                                   prompt=args.prompt, batch_size=args.batch_size, top_k=args.candidate_k,
+                                   prompt=args.prompt, batch_size=len(name_batch), top_k=args.candidate_k,
                                    temperature=args.lm_temperature, max_iter=args.num_iterations, alpha=args.alpha, beta=args.beta,
                                    generate_order=args.order, gamma=args.gamma, ctl_type=args.control_type,
                                    style_type=args.sentiment_type, pos_type=args.pos_type, sample_tau=args.sample_tau,
@@ -191,9 +237,10 @@ def blocks_batches(args, run_type, all_batches, own_lo, own_hi, rank, world, img
             if batch_idx in embed_cache:
                 imgs = ImageEmbeds(embed_cache[batch_idx])
             else:
-                imgs = [Image.open(os.path.join(img_dir, n)).convert("RGB") for n in name_batch]
+                imgs = load_batch(img_dir, name_batch, args.region_map)
+            name_batch, _ = region_rows(name_batch, args.region_map)   # (--regions_file: one row per box)
             outs = caption_blocks(args.block_width, args.block_layout, per_call, args.run_type, name_batch, lm_model, clip,
-                                  lm_tokenizer, imgs, token_mask, logger, prompt=args.prompt, batch_size=args.batch_size,
+                                  lm_tokenizer, imgs, token_mask, logger, prompt=args.prompt, batch_size=len(name_batch),
                                   max_len=args.sentence_len, top_k=args.candidate_k, temperature=args.lm_temperature,
                                   max_iter=args.num_iterations, alpha=args.alpha, beta=args.beta, generate_order=args.order,
                                   gamma=args.gamma, ctl_type=args.control_type, style_type=args.sentiment_type,
@@ -250,9 +297,10 @@ def signals_batches(args, all_batches, own_lo, own_hi, rank, world, img_dir, lm_
             if batch_idx in embed_cache:
                 imgs = ImageEmbeds(embed_cache[batch_idx])
             else:
-                imgs = [Image.open(os.path.join(img_dir, n)).convert("RGB") for n in name_batch]
+                imgs = load_batch(img_dir, name_batch, args.region_map)
+            name_batch, _ = region_rows(name_batch, args.region_map)   # (--regions_file: one row per box)
             outs = caption_signals(sigs, lens, per_call, name_batch, lm_model, clip, lm_tokenizer, imgs, token_mask, logger,
-                                   prompt=args.prompt, batch_size=args.batch_size, top_k=args.candidate_k,
+                                   prompt=args.prompt, batch_size=len(name_batch), top_k=args.candidate_k,
                                    temperature=args.lm_temperature, max_iter=args.num_iterations, alpha=args.alpha, beta=args.beta,
                                    generate_order=args.order, gamma=args.gamma, pos_type=args.pos_type, sample_tau=args.sample_tau,
                                    sample_seed=args.seed, sample0=sample_id or 0)
@@ -370,7 +418,16 @@ def main(argv=None):
     if args.rival_images is not None:
         raise SystemExit("--rival_images belongs to conzic_amd.demo_cli; here the rivals of an image are its --distinct_rivals "
                          "nearest others in its batch")
-    if args.distinct and args.batch_size < 2:
+    if args.regions is not None:
+        raise SystemExit("--regions / --region_grid belong to conzic_amd.demo_cli; here: --regions_file FILE.json")
+    args.region_map = None
+    if args.regions_file is not None:
+        from conzic_amd.regions import load_regions_file
+        try:
+            args.region_map = load_regions_file(args.regions_file)
+        except (OSError, ValueError) as exc:
+            raise SystemExit(f"--regions_file: {exc}")
+    if args.distinct and args.batch_size < 2 and not args.region_map:
         raise SystemExit("--distinct needs rival images: a --batch_size of at least two")
     import logging
     import numpy as np
@@ -469,8 +526,9 @@ def main(argv=None):
             if batch_idx in embed_cache:
                 imgs = ImageEmbeds(embed_cache[batch_idx])
             else:
-                imgs = [Image.open(os.path.join(img_dir, n)).convert("RGB") for n in name_batch]
-            kw = dict(prompt=args.prompt, batch_size=args.batch_size, max_len=args.sentence_len,
+                imgs = load_batch(img_dir, name_batch, args.region_map)
+            name_batch, groups = region_rows(name_batch, args.region_map)   # (--regions_file: one row per box)
+            kw = dict(prompt=args.prompt, batch_size=len(name_batch), max_len=args.sentence_len,
                       top_k=args.candidate_k, temperature=args.lm_temperature, max_iter=args.num_iterations,
                       alpha=args.alpha, beta=args.beta, generate_order=args.order)
             if args.fluency:
@@ -481,7 +539,7 @@ def main(argv=None):
                 (gen_texts, _), = caption_samples(1, args.run_type, name_batch, lm_model, clip, lm_tokenizer, imgs, token_mask, logger,
                                                   gamma=args.gamma, ctl_type=args.control_type, style_type=args.sentiment_type,
                                                   pos_type=args.pos_type, sample_tau=args.sample_tau, sample_seed=args.seed,
-                                                  sample0=sample_id, rivals=args.distinct_rivals if args.distinct else None,
+                                                  sample0=sample_id, rivals=region_rivals(args, clip, imgs, groups),
                                                   delta=args.distinct, vocab=vocab, **kw)
             elif args.run_type == 'caption':
                 gen_texts, _ = generate_caption(name_batch, lm_model, clip, lm_tokenizer, imgs, token_mask, logger, **kw)
@@ -514,7 +572,7 @@ def main(argv=None):
     if args.pick_lambda is not None:
         from conzic_amd.runtime import log_picked
         for batch_idx, recs in sorted(fluency.items()):
-            log_picked(logger, all_batches[batch_idx], recs, args.pick_lambda, lm_tokenizer)
+            log_picked(logger, region_rows(all_batches[batch_idx], args.region_map)[0], recs, args.pick_lambda, lm_tokenizer)
 
 
 if __name__ == "__main__":

@@ -224,6 +224,20 @@ int czc_encode_images(czc_engine* e, const float* pixels, int B, float* out_embe
  * staged pixel batch on the device (and to pixels_out [3,S,S], host or device, when not NULL).  mean/std: 3 floats. */
 int czc_preprocess_u8(czc_engine* e, const uint8_t* rgb, int height, int width, const float* mean, const float* stdv,
                       int slot, float* pixels_out);
+/* Region captions: n boxes of ONE image into staged slots slot0 .. slot0 + n - 1 in one call.  boxes int32 [n][4] = x0, y0, x1,
+ * y1 (host memory) in PIL's crop convention: pixel coordinates, x1 and y1 exclusive.  Slot slot0 + i holds, bit for bit, what
+ * czc_preprocess_u8 writes for the contiguous copy of rgb[y0:y1, x0:x1] (PIL: crop(box), then the processor).  The image is
+ * uploaded once; the boxes are read in place through the image's row stride; per chunk of at most option "regions_chunk" boxes
+ * the descriptors and the crop windows' coefficient tables travel in one copy, two kernels run over all regions of the chunk
+ * and the host synchronises once.  Only what the crop window reads is computed, so a region's intermediate holds at most
+ * (source rows its window reads) x S x 3 bytes whatever the box's aspect.  pixels_out: [n,3,S,S], host or device, or NULL.
+ * The staged batch grows as in czc_preprocess_u8 and keeps the slots it held.  CZC_ERR_ARG, before any GPU work and with the
+ * staged slots untouched: n outside [1, CZC_MAX_REGIONS], slot0 outside [0, 2^20], a box that is empty or leaves the image
+ * (PIL would pad with black; the engine refuses), a box whose resized long side int(S * long / short) exceeds 2^24, the
+ * size limits of czc_preprocess_u8. */
+#define CZC_MAX_REGIONS 1024
+int czc_preprocess_regions_u8(czc_engine* e, const uint8_t* rgb, int height, int width, const int32_t* boxes, int n,
+                              const float* mean, const float* stdv, int slot0, float* pixels_out);
 /* czc_encode_images over staged slots 0..B-1 (no host round trip of the pixels). */
 int czc_encode_staged(czc_engine* e, int B, float* out_embeds);
 /* Alternative: hand over image_embeds computed elsewhere (fp32 [B,proj], un-normalised). */
@@ -674,7 +688,9 @@ int czc_fluency_rows(czc_engine* e, const int32_t* rows /* [R, T] BERT ids, host
  *                         kept in the engine's workspace.  Replicas inherit the option and keep entries of their own.
  *                         czc_memo_rows_stats counts the hits
  *   "fluency_chunk"   (1024) czc_fluency_rows: masked sequences per BERT forward, 1 .. 16384 (CZC_ERR_ARG outside); the logits
- *                         buffer of a call holds chunk x vocab x 4 bytes */
+ *                         buffer of a call holds chunk x vocab x 4 bytes
+ *   "regions_chunk"   (64) czc_preprocess_regions_u8: boxes per upload and launch pair, 1 .. 1024 (CZC_ERR_ARG outside); bounds
+ *                         the scratch of a call, changes no bit of the result */
 int czc_set_option(czc_engine* e, const char* name, int value);
 /* Reads an option back (same names and units as czc_set_option), plus three read-only derived values:
  *   "refine_guard_generate_x1e6" / "refine_gate_generate_x1e6": the guard's trip point / the margin gate's bound in force inside

@@ -55,7 +55,8 @@ struct ProfKind {
   int64_t launches = 0;
 };
 
-// The per-row device records of a step, one record per row of the batch the step runs on; all null outside a rows call.
+// The per-row device records of a step (StepArgs::rec), one record per row of the batch the step runs on: the call's upload, or a
+// compact batch's gather of it; all null outside a rows call.
 // hp: czc_generate_rows_hp's hyper-parameters.  draw + step: czc_generate_rows_draw's records and the step's index in the call's
 // schedule (the Philox counter is the record's step0 + step).  rival [rows, M] + delta [rows]: czc_generate_rows_vs' table and
 // deltas; the indices point into img_all, the whole normalised resident batch of n_img images, which a compact batch leaves alone.
@@ -95,7 +96,6 @@ struct czc_engine {
   // czc_generate returns ids and winner cosines, not the K scores: its selection keeps round 3's threshold (4.0: fewer mass
   // carriers to re-encode; winners identical to the all-split engine on every validated image-step), the bound above is czc_step's
   float refine_theta_gen = 4.0f;
-  bool in_generate = false;
   int refine_samples = 12;      // strata of the sample among the candidates below the threshold, inside czc_generate
   // czc_step (all K fused scores are its output): twice the strata.  The sample's job is the mass-weighted MEAN screening error of
   // the candidates that keep their screening cosine; what is left of it after the correction scales the softmax denominator, and
@@ -122,7 +122,6 @@ struct czc_engine {
   // czc_step keeps fp32 rows: all K fused scores are its output and fp16 rows would take its worst one from 6.3e-4 to 1.3e-3.
   int refine_rows16 = 1;
   float refine_rows16_factor = 1.75f;
-  bool gate_now = false, gate_need_cos = true;  // set per step by czc_generate; czc_step never gates (all K scores are its output)
   int64_t stat_gated = 0, stat_gate_images = 0;
 
   std::map<std::string, Tensor> w;
@@ -138,7 +137,7 @@ struct czc_engine {
   uint8_t* d_pos_tags = nullptr; uint16_t* d_pos_masks = nullptr; int pos_n = 0;
   BridgeDev bd; bool has_bridge = false;
   std::vector<void*> bridge_allocs;
-  float* d_img_n = nullptr; int img_B = 0;
+  float* d_img_n = nullptr; int img_B = 0;  // the resident image batch, L2-normalised [img_B, proj]: written only where it is set, encoded or freed
   float logit_scale_exp = 1.f;
   double plan_pairs = 0;    // causal (query, key) pairs of the text-tower plan about to run (totals[7]): attention FLOPs = 4 * H * pairs per layer
   int* h_totals = nullptr;  // pinned, 64 ints: [8],[9] non-finite flags, [16..27] refine-plan totals, [32..35] memo check, [48..59] plan totals (HT_PLAN)
@@ -180,10 +179,6 @@ struct czc_engine {
   // option "memo" (czc_generate only; memo.hip): a step runs only for the images whose masked row differs from the one they
   // had on their last visit of the same (position, n_mask) key in this call; the others take the entry's row and cosine back
   int memo = 0;
-  // a rows call, during its steps: the per-row records of the rows the step at hand runs on (the call's upload, or a compact
-  // batch's gather of it); empty everywhere else
-  RowRecords rec;
-  int memo_branch_floor = 0;  // compacted step: longest branch the HIT images had (the full batch's attention-kernel choice)
   int64_t stat_memo_hits = 0, stat_memo_images = 0;  // image-steps that took an entry / all image-steps of memo calls
   // option "memo_rows" (czc_generate_rows only; memo_rows.hip): the same rule keyed per row, with counters of its own
   int memo_rows = 0;
@@ -692,9 +687,9 @@ constexpr int PLAN_TOTALS = 48; // bytes of a plan's device totals: [0] rows [1]
                                 // branch [5] de-duplicated candidates [6] trunk rows [7] attention pairs [8] distinct branch rows of layer 0
 struct PlanBufs { int *own_len, *pre_len, *src, *pos0, *own_off, *pre_off, *eidx, *img_max, *rep; };
 
-// the refine engine inside czc_generate: screening pass on fp16 rows (czc_engine::refine_rows16)
-static inline bool refine_rows16_now(const czc_engine* e) {
-  return e->refine && e->in_generate && e->refine_rows16 && e->cfg.clip_hidden == 512;
+// the refine engine inside czc_generate (in_generate: StepMode): screening pass on fp16 rows (czc_engine::refine_rows16)
+static inline bool refine_rows16_now(const czc_engine* e, bool in_generate) {
+  return e->refine && in_generate && e->refine_rows16 && e->cfg.clip_hidden == 512;
 }
 
 // pfx "p": the plan of the screening / only pass; "r": the plan of the refine pass
@@ -737,9 +732,10 @@ int clip_plan(czc_engine* e, const int* cids, const int* clen, int B, int K, int
 
 // The text tower on a planned set of packed segments: n_seg segments (tab), M rows, n_pool sequences pooled at p.eidx.
 // P / L / tproj: the tower's precision and weights; plan_B > 0: regular B x K plan (packed-branch attention kernels).
+// in_generate: the pass belongs to a czc_generate* step (refine_rows16_now: the refine engine's screening pass on fp16 rows).
 int clip_tower_on(czc_engine* e, int P, std::vector<LayerW>& L, const void* tproj, const char* gk, const int* cids,
                   const PlanBufs& p, int n_seg, int n_pool, int M, int max_len, int plan_B, int plan_K, int max_branch,
-                  const char* feat_name, float** feat_out, int n_dist = 0, const int* rep = nullptr) {  // n_dist: distinct rows of layer 0 (clip_plan; 0: not counted); rep: its de-duplication table
+                  const char* feat_name, float** feat_out, bool in_generate, int n_dist = 0, const int* rep = nullptr) {  // n_dist: distinct rows of layer 0 (clip_plan; 0: not counted); rep: its de-duplication table
   const czc_config& c = e->cfg;
   const int H = c.clip_hidden;
   float *x, *feat, *tok, *pos, *fg, *fb; void* pa;
@@ -751,7 +747,7 @@ int clip_tower_on(czc_engine* e, int P, std::vector<LayerW>& L, const void* tpro
   E_CHECK(need(e, "text_model.final_layer_norm.weight", H, &fg));
   E_CHECK(need(e, "text_model.final_layer_norm.bias", H, &fb));
   const bool r16 = H == 512 && ((e->resid16 >= 1 && P == PREC_BF16) || (e->resid16 >= 2 && P == PREC_F16) ||
-                                (P == PREC_F16 && refine_rows16_now(e)));
+                                (P == PREC_F16 && refine_rows16_now(e, in_generate)));
   float* stat0 = nullptr;
   if (r16 && e->fold_ln && !L.empty() && L[0].qkv_wf) E_CHECK(ensure(e, "c_stat0", (size_t)M * 8 + 256, (void**)&stat0));
   { ProfScope ps(e, "rowops_clip_text", 0);
@@ -788,26 +784,29 @@ int clip_tower_on(czc_engine* e, int P, std::vector<LayerW>& L, const void* tpro
 
 // the engine's text tower on the regular B x K plan built by clip_plan; `exact`: the refine engine's split-fp16 weights
 int clip_tower(czc_engine* e, const int* cids, int B, int K, int share, int M, int max_len, int max_branch, int n_trunk, int n_dist,
-               float** feat_out, bool exact = false) {  // n_dist: distinct branch rows of layer 0 the plan counted (0: it did not)
+               float** feat_out, bool in_generate, bool exact = false) {  // n_dist: distinct branch rows of layer 0 the plan counted (0: it did not)
   PlanBufs p;
   E_CHECK(plan_bufs(e, B, K, &p));
   const bool x = exact && e->refine;
   return clip_tower_on(e, x ? (int)PREC_F16X3 : e->pc, x ? e->ctext_x : e->ctext, x ? e->tproj_wx : e->tproj_w, "gemm_clip_text",
-                       cids, p, B + B * K, B * K, M, max_len, B, K, max_branch, "c_feat", feat_out,
+                       cids, p, B + B * K, B * K, M, max_len, B, K, max_branch, "c_feat", feat_out, in_generate,
                        n_dist > 0 ? n_trunk + n_dist : 0, e->dedup && share && K > 1 ? p.rep : nullptr);  // rep: as clip_plan filled it
 }
 
+constexpr const char* MSG_NONFINITE = "non-finite CLIP cosine: an fp16 quantity overflowed in a tower (fp16 residual rows: set option resid16 = 0 on the bf16 engine, refine_rows16 = 0 on the refine engine; fp16 operands: use CZC_PREC_SPLIT)%s";
+
 // sizes of the tower from the totals the plan read back (after the stream has been synchronised)
-int read_totals(czc_engine* e, int* M, int* max_len, int* max_branch, int* n_trunk, int* n_dist) {
+// branch_floor: a compact memo step's (StepArgs::branch_floor); 0 everywhere else
+int read_totals(czc_engine* e, int branch_floor, int* M, int* max_len, int* max_branch, int* n_trunk, int* n_dist) {
   const czc_config& c = e->cfg;
   const int* t = e->h_totals + HT_PLAN;
   *M = t[0]; *max_len = t[3]; *max_branch = t[4]; *n_trunk = t[6];
   *n_dist = t[8];
   // a compacted memo step: a branch longer than 32 rows among the images it skipped would have sent the full batch's launch
   // to the per-segment attention kernel, so it goes there too (round 3: the one batch coupling of the text tower)
-  if (e->memo_branch_floor > 32 && *max_branch < e->memo_branch_floor) *max_branch = e->memo_branch_floor;
+  if (branch_floor > 32 && *max_branch < branch_floor) *max_branch = branch_floor;
   e->plan_pairs = (double)t[7];
-  if (e->h_totals[8]) return fail(e, CZC_ERR_OVERFLOW, "non-finite CLIP cosine: an fp16 quantity overflowed in a tower (fp16 residual rows: set option resid16 = 0 on the bf16 engine, refine_rows16 = 0 on the refine engine; fp16 operands: use CZC_PREC_SPLIT)%s");
+  if (e->h_totals[8]) return fail(e, CZC_ERR_OVERFLOW, MSG_NONFINITE);
   if (t[2]) return fail(e, CZC_ERR_OVERFLOW, "text bridge overflow (row text > CZC_BRIDGE_MAX_BYTES)%s");
   if (*max_len > c.clip_max_pos || *max_len > CZC_CLIP_MAX_LEN)
     return fail(e, CZC_ERR_ARG, "CLIP sequence longer than max_position_embeddings%s");
@@ -815,27 +814,37 @@ int read_totals(czc_engine* e, int* M, int* max_len, int* max_branch, int* n_tru
 }
 
 int clip_text_forward(czc_engine* e, const int* cids, const int* clen, int B, int K, int share, int* totals,
-                      float** feat_out, bool exact = false) {
+                      float** feat_out, bool in_generate, bool exact = false) {
   E_CHECK(clip_plan(e, cids, clen, B, K, share, totals));
   E_HIP(hipStreamSynchronize(e->st));  // the one host round trip per step (the reference has one too, gen_utils.py:81)
   int M, max_len, max_branch, n_trunk, n_dist;
-  E_CHECK(read_totals(e, &M, &max_len, &max_branch, &n_trunk, &n_dist));
-  E_CHECK(clip_tower(e, cids, B, K, share, M, max_len, max_branch, n_trunk, n_dist, feat_out, exact));
+  E_CHECK(read_totals(e, 0, &M, &max_len, &max_branch, &n_trunk, &n_dist));
+  E_CHECK(clip_tower(e, cids, B, K, share, M, max_len, max_branch, n_trunk, n_dist, feat_out, in_generate, exact));
   e->stat_clip_rows += M;
   e->stat_clip_seqs += B * K;
   return 0;
 }
 
 // ---- one position-step on the device-resident d_inp (gen_utils.py:66-81), in two halves around the size read ----
+// What a step is asked to do beyond its batch.  in_generate: it belongs to a czc_generate* call (czc_step, whose output is all K
+// scores, keeps the tighter selection and fp32 rows).  gate: the margin gate is open (czc_generate's steps that are not audited).
+// need_cos: the call returns this step's winner cosine, so a gated image re-encodes its winner (read on the gated path only).
+struct StepMode { bool in_generate = false, gate = false, need_cos = true; };
+
+// Everything a step reads about its batch and its mode: a caller fills one and a compact batch is a copy with its own rows.
 struct StepArgs {
   int* d_inp; int B, T, gen_idx, n_mask, dot_allowed, K;
   czc_hyper hp;
+  const float* img = nullptr;  // [B, D] normalised image rows the batch is scored against (the resident batch, a rows call's gather, a compact batch's)
   // czc_generate_rows: column / '.' rule of every row (device, [B]) and the columns' host copy; null = the scalars above
   // (gen_idx then still holds row 0's column: what a control callback is told when all rows share one)
   const int* gen_rows = nullptr; const int* dot_rows = nullptr; const int32_t* gen_rows_host = nullptr;
   // czc_generate_rows_len: the rows' own lengths (T is then the stride of d_inp only); ctl_T: the one length the rows of a step
   // share where a control callback is set -- what it is told as T, with the rows' first ctl_T columns
   const Ragged* rag = nullptr; int ctl_T = 0;
+  RowRecords rec;        // the per-row records of these B rows, with the step's index in the call's schedule
+  int branch_floor = 0;  // compact memo step: longest branch the images that HIT had (the full batch's attention-kernel choice)
+  StepMode mode;
 };
 struct StepBufs { float *probs, *senti, *reps; int *idxs, *cand, *cids, *clen, *totals; };
 
@@ -870,9 +879,9 @@ int step_phase_a(czc_engine* e, const StepArgs& a) {
   StepBufs b;
   E_CHECK(step_bufs(e, a.B * a.K, &b));
   { ProfScope ps(e, "topk", 0);
-    if (e->rec.vset) E_CHECK(launch_softmax_mask_topk_rows_vocab(logits, a.B, c.bert_vocab, a.K, e->d_mask, e->rec.hp ? e->rec.hp : e->rec.vhp, c.dot_id,
-                                                                 a.dot_rows, e->rec.vset, e->rec.vbits, e->rec.vwords, b.probs, b.idxs, b.cand, e->st));
-    else if (e->rec.hp) E_CHECK(launch_softmax_mask_topk_rows_hp(logits, a.B, c.bert_vocab, a.K, e->d_mask, e->rec.hp, c.dot_id, a.dot_rows,
+    if (a.rec.vset) E_CHECK(launch_softmax_mask_topk_rows_vocab(logits, a.B, c.bert_vocab, a.K, e->d_mask, a.rec.hp ? a.rec.hp : a.rec.vhp, c.dot_id,
+                                                                 a.dot_rows, a.rec.vset, a.rec.vbits, a.rec.vwords, b.probs, b.idxs, b.cand, e->st));
+    else if (a.rec.hp) E_CHECK(launch_softmax_mask_topk_rows_hp(logits, a.B, c.bert_vocab, a.K, e->d_mask, a.rec.hp, c.dot_id, a.dot_rows,
                                                              b.probs, b.idxs, b.cand, e->st));
     else if (a.dot_rows) E_CHECK(launch_softmax_mask_topk_rows(logits, a.B, c.bert_vocab, a.K, e->d_mask, hp->temperature, c.dot_id, a.dot_rows,
                                                           b.probs, b.idxs, b.cand, e->st));
@@ -882,7 +891,7 @@ int step_phase_a(czc_engine* e, const StepArgs& a) {
   { ProfScope ps(e, "bridge", 0);
     PosDev pos{hp->control == 2 ? e->d_pos_tags : nullptr, e->d_pos_masks, e->pos_n};
     // per-row hyper-parameters: every table there is goes along and a candidate's thread scores by its row's control
-    if (e->rec.hp) E_CHECK(launch_bridge_rows_hp(e->bd, a.d_inp, a.B, a.T, a.gen_rows, b.cand, a.K, e->d_lex, e->d_lex_pos, e->d_lex_cls, e->rec.hp,
+    if (a.rec.hp) E_CHECK(launch_bridge_rows_hp(e->bd, a.d_inp, a.B, a.T, a.gen_rows, b.cand, a.K, e->d_lex, e->d_lex_pos, e->d_lex_cls, a.rec.hp,
                                                   PosDev{e->d_pos_tags, e->d_pos_masks, e->pos_n}, b.cids, b.clen, b.senti, b.reps,
                                                   b.totals + 2, e->st, a.rag ? a.rag->len : nullptr));
     else if (a.gen_rows) E_CHECK(launch_bridge_rows(e->bd, a.d_inp, a.B, a.T, a.gen_rows, b.cand, a.K, hp->control == 1 ? e->d_lex : nullptr,
@@ -901,16 +910,15 @@ int step_phase_a(czc_engine* e, const StepArgs& a) {
 // in front of the step's one host round trip), launches the CLIP tower, and calls the host WHILE the tower runs
 // (control_score): the reference's Python scorer (control_gen_utils.py:56-57) disappears under the tower's GPU time wherever
 // it is the shorter of the two.
-int control_pinned(czc_engine* e, size_t n_inp, size_t n_seq) {
-  const size_t want = (n_inp + n_seq) * 4 + n_seq * 4;
-  if (e->h_ctl_cap < want) {
-    E_HIP(hipStreamSynchronize(e->st));
-    if (e->h_ctl_ids) (void)hipHostFree(e->h_ctl_ids);
-    e->h_ctl_ids = nullptr; e->h_ctl_cap = 0;
-    E_HIP(hipHostMalloc((void**)&e->h_ctl_ids, want + want / 4));
-    e->h_ctl_cap = want + want / 4;
-  }
-  e->h_ctl_scores = (float*)(e->h_ctl_ids + n_inp + n_seq);
+// a grow-only pinned host buffer: at least `want` bytes behind *p (*cap: what it holds), a quarter more where it has to grow --
+// after the stream has drained, since a queued copy may still read the old one
+int ensure_pinned(czc_engine* e, int32_t** p, size_t* cap, size_t want) {
+  if (*cap >= want) return 0;
+  E_HIP(hipStreamSynchronize(e->st));
+  if (*p) (void)hipHostFree(*p);
+  *p = nullptr; *cap = 0;
+  E_HIP(hipHostMalloc((void**)p, want + want / 4));
+  *cap = want + want / 4;
   return 0;
 }
 
@@ -919,7 +927,8 @@ int control_fetch(czc_engine* e, const StepArgs& a) {
   const int Tc = a.ctl_T > 0 ? a.ctl_T : a.T;
   const size_t n_seq = (size_t)a.B * a.K, n_inp = (size_t)a.B * Tc;
   E_CHECK(step_bufs(e, (int)n_seq, &b));
-  E_CHECK(control_pinned(e, n_inp, n_seq));
+  E_CHECK(ensure_pinned(e, &e->h_ctl_ids, &e->h_ctl_cap, (n_inp + n_seq) * 4 + n_seq * 4));  // [B*T + B*K] ids, [B*K] scores
+  e->h_ctl_scores = (float*)(e->h_ctl_ids + n_inp + n_seq);
   if (Tc == a.T) E_HIP(hipMemcpyAsync(e->h_ctl_ids, a.d_inp, n_inp * 4, hipMemcpyDeviceToHost, e->st));
   else E_HIP(hipMemcpy2DAsync(e->h_ctl_ids, (size_t)Tc * 4, a.d_inp, (size_t)a.T * 4, (size_t)Tc * 4, a.B, hipMemcpyDeviceToHost, e->st));
   E_HIP(hipMemcpyAsync(e->h_ctl_ids + n_inp, b.cand, n_seq * 4, hipMemcpyDeviceToHost, e->st));
@@ -948,7 +957,7 @@ int step_phase_b(czc_engine* e, const StepArgs& a, int M, int max_len, int max_b
   StepBufs b;
   E_CHECK(step_bufs(e, n_seq, &b));
   float* feat;
-  E_CHECK(clip_tower(e, b.cids, a.B, a.K, e->share_prefix, M, max_len, max_branch, n_trunk, n_dist, &feat));
+  E_CHECK(clip_tower(e, b.cids, a.B, a.K, e->share_prefix, M, max_len, max_branch, n_trunk, n_dist, &feat, a.mode.in_generate));
   if (hp->control && e->ctl_fn) E_CHECK(control_score(e, a));  // host scorer under the tower that was just queued
   float *cscore, *cref, *fin, *bcos; int* best;
   E_CHECK(ensure(e, "s_cscore", (size_t)n_seq * 4, (void**)&cscore));
@@ -957,18 +966,18 @@ int step_phase_b(czc_engine* e, const StepArgs& a, int M, int max_len, int max_b
   E_CHECK(ensure(e, "s_best", (size_t)a.B * 4, (void**)&best));
   E_CHECK(ensure(e, "s_bcos", (size_t)a.B * 4, (void**)&bcos));
   CombineArgs ca;
-  ca.text_feat = feat; ca.img_n = e->d_img_n; ca.logit_scale_exp = e->logit_scale_exp; ca.probs = b.probs; ca.cand = b.cand;
+  ca.text_feat = feat; ca.img_n = a.img; ca.logit_scale_exp = e->logit_scale_exp; ca.probs = b.probs; ca.cand = b.cand;
   ca.senti_raw = b.senti; ca.repeats = b.reps; ca.alpha = hp->alpha; ca.beta = hp->beta; ca.gamma = hp->gamma;
   ca.use_senti = hp->control; ca.B = a.B; ca.K = a.K; ca.D = c.clip_proj; ca.clip_score = cscore; ca.clip_ref = cref;
   ca.final_score = fin; ca.best = best; ca.best_cos = bcos; ca.inp = a.d_inp; ca.T = a.T; ca.gen_idx = a.gen_idx;
-  ca.hp_rows = e->rec.hp;   // czc_generate_rows_hp: alpha / beta / gamma / control per row, in both passes of the refine engine too
+  ca.hp_rows = a.rec.hp;   // czc_generate_rows_hp: alpha / beta / gamma / control per row, in both passes of the refine engine too
   ca.gen_rows = a.gen_rows;  // both passes of the refine engine write back through the same per-row column
   // czc_generate_rows_draw: the draw belongs to the combine that writes back -- the only one here, the final one of the refine engine
-  if (!e->refine) { ca.draw_rows = e->rec.draw; ca.draw_step = e->rec.step; }
+  if (!e->refine) { ca.draw_rows = a.rec.draw; ca.draw_step = a.rec.step; }
   E_CHECK(ensure(e, "s_nonfinite", 32, (void**)&ca.nonfinite));
-  if (e->rec.rival) {  // czc_generate_rows_vs (never on the refine engine: refused by the entry point)
+  if (a.rec.rival) {  // czc_generate_rows_vs (never on the refine engine: refused by the entry point)
     if (e->refine) return fail(e, CZC_ERR_STATE, "step: rivals on the screen-then-refine engine%s");
-    ca.rival_idx = e->rec.rival; ca.M = e->rec.M; ca.rival_delta = e->rec.delta; ca.img_all = e->rec.img_all; ca.n_img = e->rec.n_img;
+    ca.rival_idx = a.rec.rival; ca.M = a.rec.M; ca.rival_delta = a.rec.delta; ca.img_all = a.rec.img_all; ca.n_img = a.rec.n_img;
     E_CHECK(ensure(e, "s_disc", (size_t)n_seq * 4, (void**)&ca.disc));
   }
   if (!e->refine) {
@@ -990,20 +999,22 @@ int step_phase_b(czc_engine* e, const StepArgs& a, int M, int max_len, int max_b
   E_CHECK(plan_bufs(e, a.B, a.K, &sp));
   E_CHECK(plan_bufs(e, a.B, a.K, &rp, "r"));
   const int S = a.B + n_seq;
+  const bool gen = a.mode.in_generate;
+  const float rows16_x = refine_rows16_now(e, gen) ? e->refine_rows16_factor : 1.f;  // what the bounds on the screening deviation grow by on fp16 rows
+  const int strata = gen ? e->refine_samples : e->refine_samples_step, need_cos = a.mode.need_cos ? 1 : 0;
   // (on fp16 rows the deviation a kept screening cosine carries is refine_rows16_factor times larger: the mass threshold
   // shrinks by the same factor, so theta * deviation -- what such a candidate can move its score by -- stays what it was)
-  const float theta_base = e->in_generate ? e->refine_theta_gen / (refine_rows16_now(e) ? e->refine_rows16_factor : 1.f) : e->refine_theta_x;
+  const float theta_base = gen ? e->refine_theta_gen / rows16_x : e->refine_theta_x;
   const float theta = theta_base / fmaxf(hp->beta * e->logit_scale_exp, 1e-6f);  // (per-row hyper-parameters: formed per row in the kernel)
   { ProfScope ps(e, "combine", 0);
     ca.inp = nullptr;
     E_CHECK(launch_combine(ca, e->st));
-    const float gate_h = e->gate_now ? e->refine_gate_delta * (refine_rows16_now(e) ? e->refine_rows16_factor : 1.f) * e->logit_scale_exp : 0.f;
-    if (e->rec.draw) E_CHECK(launch_refine_select_draw(cscore, fin, a.B, a.K, theta, theta_base, e->logit_scale_exp, e->in_generate ? e->refine_samples : e->refine_samples_step,
-                                                        gate_h, hp->beta, e->rec.hp, e->rec.draw, e->gate_need_cos ? 1 : 0, ca.nonfinite + 4, kind, list, count, e->st));
-    else if (e->rec.hp) E_CHECK(launch_refine_select_rows(cscore, fin, a.B, a.K, theta_base, e->logit_scale_exp, e->in_generate ? e->refine_samples : e->refine_samples_step,
-                                                      gate_h, e->rec.hp, e->gate_need_cos ? 1 : 0, ca.nonfinite + 4, kind, list, count, e->st));
-    else E_CHECK(launch_refine_select(cscore, fin, a.B, a.K, theta, e->in_generate ? e->refine_samples : e->refine_samples_step, gate_h, hp->beta, e->gate_need_cos ? 1 : 0,
-                                 ca.nonfinite + 4, kind, list, count, e->st)); }
+    const float gate_h = a.mode.gate ? e->refine_gate_delta * rows16_x * e->logit_scale_exp : 0.f;
+    if (a.rec.draw) E_CHECK(launch_refine_select_draw(cscore, fin, a.B, a.K, theta, theta_base, e->logit_scale_exp, strata, gate_h, hp->beta, a.rec.hp,
+                                                      a.rec.draw, need_cos, ca.nonfinite + 4, kind, list, count, e->st));
+    else if (a.rec.hp) E_CHECK(launch_refine_select_rows(cscore, fin, a.B, a.K, theta_base, e->logit_scale_exp, strata, gate_h, a.rec.hp, need_cos,
+                                                         ca.nonfinite + 4, kind, list, count, e->st));
+    else E_CHECK(launch_refine_select(cscore, fin, a.B, a.K, theta, strata, gate_h, hp->beta, need_cos, ca.nonfinite + 4, kind, list, count, e->st)); }
   { ProfScope ps(e, "bridge", 0);
     E_HIP(hipMemsetAsync(rtot, 0, 64, e->st));
     E_HIP(hipMemsetAsync(rp.own_len, 0, (size_t)S * 4, e->st));
@@ -1021,30 +1032,32 @@ int step_phase_b(czc_engine* e, const StepArgs& a, int M, int max_len, int max_b
     e->plan_pairs = (double)e->h_totals[16 + 7];
     // regular B x Kr plan (empty slots have no rows): the packed-branch split attention serves it like the screening plan
     E_CHECK(clip_tower_on(e, PREC_F16X3, e->ctext_x, e->tproj_wx, "gemm_clip_refine", b.cids, rp, a.B + a.B * Kr, R, M2, max_len2,
-                          a.B, Kr, max_branch2, "c_feat2", &feat2));
+                          a.B, Kr, max_branch2, "c_feat2", &feat2, gen));
     ProfScope ps(e, "combine", 0);
-    E_CHECK(launch_refine_cosine(feat2, e->d_img_n, rlist, count_off + a.B, R, a.K, c.clip_proj, rcos, ca.nonfinite, e->st));
+    E_CHECK(launch_refine_cosine(feat2, a.img, rlist, count_off + a.B, R, a.K, c.clip_proj, rcos, ca.nonfinite, e->st));
   }
   { ProfScope ps(e, "combine", 0);
     ca.text_feat = nullptr; ca.inp = a.d_inp; ca.refine_kind = kind; ca.refine_cos = rcos;
-    ca.draw_rows = e->rec.draw; ca.draw_step = e->rec.step;
-    ca.refine_guard = e->refine_guard_dev * (refine_rows16_now(e) ? e->refine_rows16_factor : 1.f);
+    ca.draw_rows = a.rec.draw; ca.draw_step = a.rec.step;
+    ca.refine_guard = e->refine_guard_dev * rows16_x;
     E_CHECK(launch_combine(ca, e->st)); }
   e->stat_refine_rows += M2;
   e->stat_refine_seqs += R;
   return 0;
 }
 
-// gen_rows / dot_rows (device, [B]) + gen_rows_host: czc_generate_rows' per-row column and '.' rule (gen_idx = row 0's then)
-int step_device(czc_engine* e, int* d_inp, int B, int T, int gen_idx, int n_mask, int dot_allowed, int K,
-                const czc_hyper* hp, const int* gen_rows = nullptr, const int* dot_rows = nullptr,
-                const int32_t* gen_rows_host = nullptr, const Ragged* rag = nullptr, int ctl_T = 0) {
+// The resident image batch as a step's image rows: null (step_device refuses the step) unless it holds exactly B images
+const float* resident_images(const czc_engine* e, int B) { return B == e->img_B ? e->d_img_n : nullptr; }
+
+int step_device(czc_engine* e, const StepArgs& a) {
   const czc_config& c = e->cfg;
+  const int B = a.B, T = a.T, gen_idx = a.gen_idx, n_mask = a.n_mask, K = a.K;
+  const czc_hyper* hp = &a.hp; const Ragged* rag = a.rag;
   if (!e->finalized) return fail(e, CZC_ERR_STATE, "weights not finalized%s");
   if (c.bert_layers <= 0) return fail(e, CZC_ERR_STATE, "this engine was created without the BERT tower%s");
   if (!e->d_mask) return fail(e, CZC_ERR_STATE, "token mask not set%s");
   if (!e->has_bridge) return fail(e, CZC_ERR_STATE, "bridge tables not set%s");
-  if (!e->d_img_n || e->img_B != B) return fail(e, CZC_ERR_STATE, "image embeds not set for this batch size%s");
+  if (!a.img) return fail(e, CZC_ERR_STATE, "image embeds not set for this batch size%s");
   if (T > CZC_MAX_BERT_LEN || gen_idx < 0 || gen_idx >= T || K > CZC_MAX_TOPK)
     return fail(e, CZC_ERR_ARG, "step: bad T/gen_idx/K%s");
   if (hp->control == 1 && !e->ctl_fn && !e->d_lex && !e->d_lex_pos)
@@ -1053,23 +1066,31 @@ int step_device(czc_engine* e, int* d_inp, int B, int T, int gen_idx, int n_mask
     return fail(e, CZC_ERR_STATE, "POS path needs czc_set_pos or czc_set_control_callback%s");
   if (n_mask <= 0 && (e->last_B != B || e->last_T != T))
     return fail(e, CZC_ERR_STATE, "n_mask=0 needs a previous forward of the same [B,T] shape%s");
-  StepArgs a{d_inp, B, T, gen_idx, n_mask, dot_allowed, K, *hp};
-  a.gen_rows = gen_rows; a.dot_rows = dot_rows; a.gen_rows_host = gen_rows_host; a.rag = rag; a.ctl_T = ctl_T;
-  if (e->rec.hp && (!gen_rows || !dot_rows)) return fail(e, CZC_ERR_ARG, "step: per-row hyper-parameters need per-row columns%s");
-  if (e->rec.draw && !gen_rows) return fail(e, CZC_ERR_ARG, "step: per-row draws need per-row columns%s");
-  if (rag && (!gen_rows || !dot_rows || rag->max_T > T || rag->M > B * T)) return fail(e, CZC_ERR_ARG, "step: ragged rows need per-row columns and lengths within T%s");
+  if (a.rec.hp && (!a.gen_rows || !a.dot_rows)) return fail(e, CZC_ERR_ARG, "step: per-row hyper-parameters need per-row columns%s");
+  if (a.rec.draw && !a.gen_rows) return fail(e, CZC_ERR_ARG, "step: per-row draws need per-row columns%s");
+  if (rag && (!a.gen_rows || !a.dot_rows || rag->max_T > T || rag->M > B * T)) return fail(e, CZC_ERR_ARG, "step: ragged rows need per-row columns and lengths within T%s");
   E_CHECK(step_phase_a(e, a));
   if (n_mask > 0) { e->stat_bert_rows += rag ? rag->M : B * T; e->last_BT = B * T; e->last_B = B; e->last_T = T; }
   if (hp->control && e->ctl_fn) E_CHECK(control_fetch(e, a));  // ids for the host scorer ride on the same round trip
   E_HIP(hipStreamSynchronize(e->st));  // the one host round trip per step (the reference has one too, gen_utils.py:81)
   int M, max_len, max_branch, n_trunk, n_dist;
-  E_CHECK(read_totals(e, &M, &max_len, &max_branch, &n_trunk, &n_dist));
+  E_CHECK(read_totals(e, a.branch_floor, &M, &max_len, &max_branch, &n_trunk, &n_dist));
   E_CHECK(step_phase_b(e, a, M, max_len, max_branch, n_trunk, n_dist));
   e->stat_clip_rows += M;
   e->stat_clip_seqs += B * K;
   e->stat_dedup_seqs += e->h_totals[HT_PLAN + 5];
   e->stat_steps += 1;
   return 0;
+}
+
+// the end of a call that ran steps, one read: the steps' cosine check, then their guard and gate statistics
+int finish_steps(czc_engine* e) {
+  E_HIP(hipMemcpyAsync(e->h_totals + 9, e->ws["s_nonfinite"].p, 24, hipMemcpyDeviceToHost, e->st));
+  E_HIP(hipStreamSynchronize(e->st));
+  if (e->h_totals[9]) return fail(e, CZC_ERR_OVERFLOW, MSG_NONFINITE);
+  { float dev; memcpy(&dev, e->h_totals + 10, 4); e->guard_max_dev = fmaxf(e->guard_max_dev, dev); e->guard_trips += e->h_totals[11];
+    e->stat_gated += e->h_totals[13]; e->stat_gate_images += e->h_totals[14]; }
+  return CZC_OK;
 }
 
 int copy_out(czc_engine* e, void* dst, const char* ws_name, size_t bytes) {
@@ -1139,10 +1160,37 @@ struct Sched { std::vector<int32_t> h; const int* d = nullptr; SchedLayout at; }
 // row of the group's first step (which fixes the outcome of every step of the group), the row and winner cosine each step
 // left, and each step's longest CLIP branch.  Entries live for one call.
 constexpr int MEMO_SUB = 2;  // steps per group the entry has room for (a longer group runs without the memo)
+
+// The step groups of a call's schedule, shared by the step memo and the rows memo (n_mask is one value per step for all rows)
+struct StepGroups {
+  std::vector<int> first, sub, len;  // per step: first step of its group, index inside the group; per group-start step: its steps
+  // per group-start step: the group may take an entry back.  CZC_PREC_REFINE: not where a step is audited (the guard stays on every
+  // image) or returns its winner cosine (a split re-encode whose last bits can depend on which other candidates went with the winner)
+  std::vector<char> hittable;
+};
+
+StepGroups step_groups(const czc_engine* e, const RowsCall& c, const std::vector<char>& audit) {
+  const int n_steps = c.n_steps;
+  StepGroups G;
+  G.first.assign(n_steps, 0); G.sub.assign(n_steps, 0); G.len.assign(n_steps, 0); G.hittable.assign(n_steps, 0);
+  for (int s = 0; s < n_steps; s += G.len[s]) {
+    int g = 1;
+    while (s + g < n_steps && c.n_mask && c.n_mask[s + g] <= 0) ++g;
+    G.len[s] = g;
+    G.hittable[s] = 1;
+    for (int j = 0; j < g; ++j) {
+      G.first[s + j] = s; G.sub[s + j] = j;
+      const bool cos_out = c.out_cos && (s + j + 1) % c.snapshot_every == 0;
+      if (e->refine && (audit[s + j] || cos_out)) G.hittable[s] = 0;
+    }
+  }
+  return G;
+}
+
 struct MemoPlan {
-  std::vector<int> slot, sub;  // per step: entry slot of its group (-1: never memoised), index inside the group
+  StepGroups grp;
+  std::vector<int> slot;       // per step: entry slot of its group (-1: never memoised)
   std::vector<char> check;     // per group-start step: the host knows the key was visited before and the step may hit
-  std::vector<int> group_len;  // per group-start step
   int *key = nullptr, *rows = nullptr, *imax = nullptr, *hit = nullptr, *list = nullptr, *tot = nullptr, *inp_c = nullptr;
   float *cos = nullptr, *bcos = nullptr, *img_c = nullptr;
   int n_act = 0;  // of the group in progress
@@ -1150,35 +1198,21 @@ struct MemoPlan {
 };
 
 int memo_begin(czc_engine* e, const RowsCall& c, const std::vector<char>& audit, MemoPlan* mp) {
-  const int B = c.R, T = c.T, n_steps = c.n_steps, snapshot_every = c.snapshot_every;
-  const int32_t *positions = c.positions, *n_mask = c.n_mask;
-  const bool want_cos = c.out_cos != nullptr;
-  mp->slot.assign(n_steps, -1); mp->sub.assign(n_steps, 0); mp->check.assign(n_steps, 0); mp->group_len.assign(n_steps, 0);
+  const int B = c.R, T = c.T, n_steps = c.n_steps;
+  mp->grp = step_groups(e, c, audit);
+  mp->slot.assign(n_steps, -1); mp->check.assign(n_steps, 0);
   std::map<std::vector<int>, int> slots;
-  for (int s = 0; s < n_steps;) {
-    int g = 1;
-    while (s + g < n_steps && n_mask && n_mask[s + g] <= 0) ++g;
-    const int nm0 = n_mask ? n_mask[s] : 1;
-    mp->group_len[s] = g;
-    for (int j = 0; j < g; ++j) mp->sub[s + j] = j;
-    if (nm0 >= 1 && g <= MEMO_SUB) {
-      std::vector<int> key;
-      bool hittable = true;
-      for (int j = 0; j < g; ++j) {
-        key.push_back(positions[s + j]); key.push_back(n_mask ? n_mask[s + j] : 1);
-        // CZC_PREC_REFINE: audit steps keep the guard on every image, and a step whose winner cosine the call returns takes
-        // it from a split re-encode whose last bits can depend on which other candidates were re-encoded with the winner
-        const bool cos_out = want_cos && (s + j + 1) % snapshot_every == 0;
-        if (e->refine && (audit[s + j] || cos_out)) hittable = false;
-      }
-      auto it = slots.find(key);
-      const bool seen = it != slots.end();
-      const int sl = seen ? it->second : (int)slots.size();
-      if (!seen) slots[key] = sl;
-      for (int j = 0; j < g; ++j) mp->slot[s + j] = sl;
-      mp->check[s] = seen && hittable;
-    }
-    s += g;
+  for (int s = 0; s < n_steps; s += mp->grp.len[s]) {
+    const int g = mp->grp.len[s];
+    if (c.n_mask_at(s) < 1 || g > MEMO_SUB) continue;
+    std::vector<int> key;
+    for (int j = 0; j < g; ++j) { key.push_back(c.positions[s + j]); key.push_back(c.n_mask_at(s + j)); }
+    auto it = slots.find(key);
+    const bool seen = it != slots.end();
+    const int sl = seen ? it->second : (int)slots.size();
+    if (!seen) slots[key] = sl;
+    for (int j = 0; j < g; ++j) mp->slot[s + j] = sl;
+    mp->check[s] = seen && mp->grp.hittable[s];
   }
   const size_t n_slots = slots.size() ? slots.size() : 1, D = (size_t)e->cfg.clip_proj;
   E_CHECK(ensure(e, "m_key", n_slots * B * T * 4, (void**)&mp->key));
@@ -1194,15 +1228,15 @@ int memo_begin(czc_engine* e, const RowsCall& c, const std::vector<char>& audit,
   return 0;
 }
 
-// One step of czc_generate with the memo on.  First step of a group whose key this call has seen: the check kernel and one
-// 16-byte read (the second host round trip of such a step) give the active images; then all of them run as usual (and
-// record), none of them runs (BERT, the towers and the combine kernel are skipped), or the step runs on a compact batch of
-// them.  The group's other steps keep its active set: the n_mask = 0 step re-uses the forward of exactly those rows.
-int memo_step(czc_engine* e, MemoPlan& mp, const RowsCall& c, int s, int* d_inp) {
-  const int B = c.R, T = c.T, K = c.top_k, pos = c.positions[s], gen_idx = c.seed_len + pos, n_mask = c.n_mask_at(s);
-  const int dot_allowed = pos == c.L - 1 ? 1 : 0;
-  const czc_hyper* hp = c.hp;
-  const int slot = mp.slot[s], j = mp.sub[s], mask_id = e->cfg.mask_id, D = e->cfg.clip_proj;
+// One step of czc_generate with the memo on (full: the step on the whole batch, as it runs without the memo).  First step of a
+// group whose key this call has seen: the check kernel and one 16-byte read (the second host round trip of such a step) give the
+// active images; then all of them run as usual (and record), none of them runs (BERT, the towers and the combine kernel are
+// skipped), or the step runs on a compact batch of them: a copy of `full` with its own rows and image rows.  The group's other
+// steps keep its active set: the n_mask = 0 step re-uses the forward of exactly those rows.
+int memo_step(czc_engine* e, MemoPlan& mp, int s, const StepArgs& full) {
+  int* const d_inp = full.d_inp;
+  const int B = full.B, T = full.T, gen_idx = full.gen_idx, n_mask = full.n_mask;
+  const int slot = mp.slot[s], j = mp.grp.sub[s], mask_id = e->cfg.mask_id, D = e->cfg.clip_proj;
   int* key = slot >= 0 ? mp.key + (size_t)slot * B * T : nullptr;
   int* rows = slot >= 0 ? mp.rows + ((size_t)slot * MEMO_SUB + j) * B * T : nullptr;
   float* cos = slot >= 0 ? mp.cos + ((size_t)slot * MEMO_SUB + j) * B : nullptr;
@@ -1211,7 +1245,7 @@ int memo_step(czc_engine* e, MemoPlan& mp, const RowsCall& c, int s, int* d_inp)
     mp.n_act = B;
     mp.branch_max[0] = mp.branch_max[1] = 0;
     if (mp.check[s]) {
-      E_CHECK(launch_memo_check(d_inp, B, T, gen_idx, n_mask, mask_id, key, mp.imax + (size_t)slot * MEMO_SUB * B, mp.group_len[s],
+      E_CHECK(launch_memo_check(d_inp, B, T, gen_idx, n_mask, mask_id, key, mp.imax + (size_t)slot * MEMO_SUB * B, mp.grp.len[s],
                                 mp.hit, mp.list, mp.tot, e->st));
       E_HIP(hipMemcpyAsync(e->h_totals + 32, mp.tot, 16, hipMemcpyDeviceToHost, e->st));
       E_HIP(hipStreamSynchronize(e->st));
@@ -1228,33 +1262,27 @@ int memo_step(czc_engine* e, MemoPlan& mp, const RowsCall& c, int s, int* d_inp)
   e->stat_memo_hits += B - n_act;
   if (n_act < B) E_CHECK(launch_memo_fill(mp.hit, B, T, rows, cos, d_inp, mp.bcos, e->st));
   if (n_act == 0) return 0;
-  if (n_act == B) {  // the whole batch, in place, as without the memo; then the entry is recorded
+  const bool whole = n_act == B;
+  StepArgs a = full;
+  if (whole) {  // the whole batch, in place, as without the memo; then the entry is recorded
     if (key && j == 0) E_CHECK(launch_memo_gather(d_inp, nullptr, B, T, gen_idx, n_mask, mask_id, key, nullptr, nullptr, D, nullptr, e->st));
-    E_CHECK(step_device(e, d_inp, B, T, gen_idx, n_mask, dot_allowed, K, hp));
-    return launch_memo_scatter(d_inp, (const float*)e->ws["s_bcos"].p, (const int*)e->ws["p_img_max"].p, nullptr, B, T, d_inp,
-                               mp.bcos, rows, cos, imax, e->st) ? fail(e, CZC_ERR_HIP, "%s", g_err) : 0;
+  } else {  // compact batch: rows and normalised image embeds of the active images, the step on them, then their rows and cosines
+            // back into the full batch and into the entry
+    E_CHECK(launch_memo_gather(d_inp, mp.list, n_act, T, gen_idx, n_mask, mask_id, j == 0 ? key : nullptr, mp.inp_c, full.img, D,
+                               mp.img_c, e->st));
+    a.d_inp = mp.inp_c; a.B = n_act; a.img = mp.img_c; a.branch_floor = mp.branch_max[j];
   }
-  // compact batch: rows and normalised image embeds of the active images, the step on them (step_device needs image embeds
-  // of its own batch size), then their rows and cosines back into the full batch and into the entry
-  E_CHECK(launch_memo_gather(d_inp, mp.list, n_act, T, gen_idx, n_mask, mask_id, j == 0 ? key : nullptr, mp.inp_c, e->d_img_n, D,
-                             mp.img_c, e->st));
-  float* img_full = e->d_img_n;
-  const int img_B = e->img_B;
-  e->d_img_n = mp.img_c; e->img_B = n_act; e->memo_branch_floor = mp.branch_max[j];
-  const int rc = step_device(e, mp.inp_c, n_act, T, gen_idx, n_mask, dot_allowed, K, hp);
-  e->d_img_n = img_full; e->img_B = img_B; e->memo_branch_floor = 0;
-  E_CHECK(rc);
-  return launch_memo_scatter(mp.inp_c, (const float*)e->ws["s_bcos"].p, (const int*)e->ws["p_img_max"].p, mp.list, n_act, T, d_inp,
-                             mp.bcos, rows, cos, imax, e->st) ? fail(e, CZC_ERR_HIP, "%s", g_err) : 0;
+  E_CHECK(step_device(e, a));
+  return launch_memo_scatter(a.d_inp, (const float*)e->ws["s_bcos"].p, (const int*)e->ws["p_img_max"].p, whole ? nullptr : mp.list, n_act, T,
+                             d_inp, mp.bcos, rows, cos, imax, e->st) ? fail(e, CZC_ERR_HIP, "%s", g_err) : 0;
 }
 
 // ---- option "memo_rows" (czc_generate_rows): the per-row step memo of memo_rows.hip -----------------------------------
-// n_mask is one value per step for all rows, so the step groups are those of memo_begin and shared by the rows; the positions
+// n_mask is one value per step for all rows, so the step groups are the step memo's (StepGroups) and shared by the rows; the positions
 // are per row.  Row r's entry for a group sits in slot (first position of the group, r) under the group's signature (n_mask,
 // length, column of the second step): the same first position under another shape replaces it.
 struct MemoRowsPlan {
-  std::vector<int> first, sub;   // per step: first step of its group, index inside the group
-  std::vector<int> group_len;    // per group-start step
+  StepGroups grp;
   std::vector<char> record;      // per group-start step: the group has an entry (starts with n_mask >= 1, fits MEMO_ROWS_SUB)
   std::vector<char> check;       // per group-start step: the host knows some row revisits a key and the step may hit
   MemoRowsTab tab{};
@@ -1269,13 +1297,12 @@ struct MemoRowsPlan {
   int n_run = 0;  // of the group in progress: rows that are not idle
   int n_act = 0;  // of the group in progress: rows that run (not idle and no hit)
   int branch_max[MEMO_ROWS_SUB] = {0, 0};
-  // czc_generate_rows_len (len_h null otherwise): every row's token count T_r on the host; the full batch's offsets / lengths
-  // and those of every step's run list in the schedule upload (SchedLayout: rag, rag_steps); d_rag_c [2 R + 1]: those of a
-  // checked step's compact batch, uploaded after the list read
+  // czc_generate_rows_len (len_h null otherwise): every row's token count T_r on the host; the offsets / lengths of every step's
+  // run list are in the schedule upload (SchedLayout: rag_steps); d_rag_c [2 R + 1]: those of a checked step's compact batch,
+  // uploaded after the list read
   const int32_t* len_h = nullptr;
-  Ragged rag_full{}; int* d_rag_c = nullptr;
+  int* d_rag_c = nullptr;
   Ragged rag_c{};  // of the group in progress, where it runs on a compact batch
-  const Ragged* rag(bool full) const { return len_h ? (full ? &rag_full : &rag_c) : nullptr; }
   int ctl_T() const { return len_h && !run_h.empty() ? len_h[run_h[0]] : 0; }
 };
 
@@ -1285,40 +1312,29 @@ static inline int memo_rows_sig(int n_mask0, int n_sub, int col1) { return (n_ma
 // table = false (czc_generate_rows_from with idle steps, option off): no entries, nothing is recorded or checked; the plan
 // then only carries the compact-batch buffers and the full-batch cosines.  Idle rows (position CZC_POS_IDLE) visit no key.
 int memo_rows_begin(czc_engine* e, const RowsCall& c, const std::vector<char>& audit, MemoRowsPlan* mp) {
-  const int R = c.R, T = c.T, L = c.L, seed_len = c.seed_len, n_steps = c.n_steps, snapshot_every = c.snapshot_every;
-  const int32_t *positions = c.positions, *n_mask = c.n_mask;
+  const int R = c.R, T = c.T, L = c.L, seed_len = c.seed_len, n_steps = c.n_steps;
+  const int32_t* positions = c.positions;
   const czc_draw* draw_host = c.draw;
-  const bool table = e->memo_rows, want_cos = c.out_cos != nullptr;
+  const bool table = e->memo_rows;
   static_assert(MEMO_ROWS_SUB == MEMO_SUB, "the rows memo keeps the step memo's group size");
-  mp->first.assign(n_steps, 0); mp->sub.assign(n_steps, 0); mp->group_len.assign(n_steps, 0);
+  mp->grp = step_groups(e, c, audit);
   mp->record.assign(n_steps, 0); mp->check.assign(n_steps, 0);
   mp->table = table;
   std::vector<int> seen(table ? (size_t)R * L : 0, -1);  // per slot: the signature it was last recorded under in this call
-  for (int s = 0; s < n_steps;) {
-    int g = 1;
-    while (s + g < n_steps && n_mask && n_mask[s + g] <= 0) ++g;
-    const int nm0 = n_mask ? n_mask[s] : 1;
-    mp->group_len[s] = g;
-    for (int j = 0; j < g; ++j) { mp->first[s + j] = s; mp->sub[s + j] = j; }
-    if (table && nm0 >= 1 && nm0 <= T && g <= MEMO_ROWS_SUB) {
-      bool hittable = true;  // CZC_PREC_REFINE: the step-level rule of memo_begin
-      for (int j = 0; j < g; ++j) {
-        const bool cos_out = want_cos && (s + j + 1) % snapshot_every == 0;
-        if (e->refine && (audit[s + j] || cos_out)) hittable = false;
-      }
-      bool revisit = false;
-      for (int r = 0; r < R; ++r) {
-        if (positions[(size_t)s * R + r] < 0) continue;  // idle: not a visit
-        if (draw_host && draw_host[r].tau > 0.f) continue;  // a row that draws never hits (the check kernel refuses it too)
-        const int sig = memo_rows_sig(nm0, g, g > 1 ? seed_len + positions[(size_t)(s + 1) * R + r] : 0);
-        int& was = seen[(size_t)r * L + positions[(size_t)s * R + r]];
-        revisit = revisit || was == sig;
-        was = sig;
-      }
-      mp->record[s] = 1;
-      mp->check[s] = revisit && hittable;
+  for (int s = 0; table && s < n_steps; s += mp->grp.len[s]) {
+    const int g = mp->grp.len[s], nm0 = c.n_mask_at(s);
+    if (nm0 < 1 || nm0 > T || g > MEMO_ROWS_SUB) continue;
+    bool revisit = false;
+    for (int r = 0; r < R; ++r) {
+      if (positions[(size_t)s * R + r] < 0) continue;  // idle: not a visit
+      if (draw_host && draw_host[r].tau > 0.f) continue;  // a row that draws never hits (the check kernel refuses it too)
+      const int sig = memo_rows_sig(nm0, g, g > 1 ? seed_len + positions[(size_t)(s + 1) * R + r] : 0);
+      int& was = seen[(size_t)r * L + positions[(size_t)s * R + r]];
+      revisit = revisit || was == sig;
+      was = sig;
     }
-    s += g;
+    mp->record[s] = 1;
+    mp->check[s] = revisit && mp->grp.hittable[s];
   }
   MemoRowsTab& m = mp->tab;
   m.R = R; m.T = T; m.L = L; m.seed_len = seed_len;
@@ -1342,21 +1358,13 @@ int memo_rows_begin(czc_engine* e, const RowsCall& c, const std::vector<char>& a
   E_CHECK(ensure(e, "mr_dot_c", (size_t)R * 4, (void**)&mp->dot_c));
   if (!table) return 0;
   E_HIP(hipMemsetAsync(m.valid, 0, n_slot * 4, e->st));  // entries live for one call
-  const size_t want = ((size_t)R + 4 + 2 * (size_t)R + 1) * 4;  // the check's totals (16 bytes), then its list; then (len mode) the compact batch's lengths and offsets
-  if (e->h_memo_list_cap < want) {
-    E_HIP(hipStreamSynchronize(e->st));
-    if (e->h_memo_list) (void)hipHostFree(e->h_memo_list);
-    e->h_memo_list = nullptr; e->h_memo_list_cap = 0;
-    E_HIP(hipHostMalloc((void**)&e->h_memo_list, want + want / 4));
-    e->h_memo_list_cap = want + want / 4;
-  }
-  return 0;
+  // the check's totals (16 bytes), then its list; then (len mode) the compact batch's lengths and offsets
+  return ensure_pinned(e, &e->h_memo_list, &e->h_memo_list_cap, ((size_t)R + 4 + 2 * (size_t)R + 1) * 4);
 }
 
-// The records of the rows a compact batch runs on: the call's own (e->rec), each gathered by the run list the batch is gathered
-// with into the plan's compact set
-int memo_rows_records(czc_engine* e, const MemoRowsPlan& mp, int n_act, RowRecords* out) {
-  const RowRecords& full = e->rec;
+// The records of the rows a compact batch runs on: the full batch's, each gathered by the run list the batch is gathered with into
+// the plan's compact set
+int memo_rows_records(czc_engine* e, const MemoRowsPlan& mp, const RowRecords& full, int n_act, RowRecords* out) {
   *out = full;
   if (full.hp) {
     if (!mp.rec_c.hp || !mp.list_d) return fail(e, CZC_ERR_STATE, "generate_rows_hp: a compact batch without room for its hyper-parameters%s");
@@ -1383,16 +1391,17 @@ int memo_rows_records(czc_engine* e, const MemoRowsPlan& mp, int n_act, RowRecor
 }
 
 // One step of czc_generate_rows with the rows memo on, and of czc_generate_rows_from wherever a call has idle steps (with the
-// option or without: mp.table); sc: the call's schedule (SchedLayout).  A row is idle for a whole group or for none of it
-// (checked by the caller), so the group's first step decides who runs: the rows that are not idle and, where the check ran, did
-// not hit.  First step of a group in which some row revisits a key: the check kernels and one read (totals and the ascending active list) give the active rows; then all of
-// them run as without the option (and record), none runs, or the step runs on a compact batch whose column / '.' arrays the
-// gather kernel builds.  The compact columns' host copy keeps the per-row n_mask = 0 re-use rule of mlm_head in force.
-int memo_rows_step(czc_engine* e, MemoRowsPlan& mp, const RowsCall& c, const Sched& sc, int s, int* d_inp) {
-  const int R = c.R, T = c.T, L = c.L, seed_len = c.seed_len, K = c.top_k;
-  const int s0 = mp.first[s], j = mp.sub[s], g = mp.group_len[s0], mask_id = e->cfg.mask_id, D = e->cfg.clip_proj;
-  const int n_mask = c.n_mask_at(s), n_mask0 = c.n_mask_at(s0), record = mp.record[s0];
-  const czc_hyper* hp = c.hp;
+// option or without: mp.table); sc: the call's schedule (SchedLayout), full: the step on all R rows.  A row is idle for a whole
+// group or for none of it (checked by the caller), so the group's first step decides who runs: the rows that are not idle and,
+// where the check ran, did not hit.  First step of a group in which some row revisits a key: the check kernels and one read (totals
+// and the ascending active list) give the active rows; then all of them run as without the option (and record), none runs, or the
+// step runs on a compact batch whose column / '.' arrays the gather kernel builds.  The compact columns' host copy keeps the
+// per-row n_mask = 0 re-use rule of mlm_head in force.
+int memo_rows_step(czc_engine* e, MemoRowsPlan& mp, const RowsCall& c, const Sched& sc, int s, const StepArgs& full) {
+  int* const d_inp = full.d_inp;
+  const int R = c.R, L = c.L, seed_len = c.seed_len;
+  const int s0 = mp.grp.first[s], j = mp.grp.sub[s], g = mp.grp.len[s0], mask_id = e->cfg.mask_id, D = e->cfg.clip_proj;
+  const int n_mask0 = c.n_mask_at(s0), record = mp.record[s0];
   const int32_t* sched = sc.h.data();
   const int* col0 = sc.d + sc.at.cols(s0);
   const int* col1 = g > 1 ? sc.d + sc.at.cols(s0 + 1) : nullptr;
@@ -1406,7 +1415,7 @@ int memo_rows_step(czc_engine* e, MemoRowsPlan& mp, const RowsCall& c, const Sch
     mp.list_d = mp.n_run < R ? sc.d + sc.at.runs(s0) : nullptr;  // the schedule's own run list of this step
     mp.branch_max[0] = mp.branch_max[1] = 0;
     if (mp.check[s]) {
-      E_CHECK(launch_memo_rows_check(d_inp, mp.tab, col0, col1, n_mask0, g, mask_id, mp.hit, mp.cnt, mp.list, mp.tot, e->st, e->rec.draw));
+      E_CHECK(launch_memo_rows_check(d_inp, mp.tab, col0, col1, n_mask0, g, mask_id, mp.hit, mp.cnt, mp.list, mp.tot, e->st, full.rec.draw));
       int32_t* h = e->h_memo_list;
       E_HIP(hipMemcpyAsync(h, mp.tot, 16, hipMemcpyDeviceToHost, e->st));
       E_HIP(hipMemcpyAsync(h + 4, mp.list, (size_t)R * 4, hipMemcpyDeviceToHost, e->st));
@@ -1460,40 +1469,33 @@ int memo_rows_step(czc_engine* e, MemoRowsPlan& mp, const RowsCall& c, const Sch
   }
   if (n_act < mp.n_run) E_CHECK(launch_memo_rows_fill(mp.hit, mp.tab, col0, j, d_inp, mp.bcos, e->st));  // only after a check
   if (n_act == 0) return 0;  // every row idle or hit: nothing runs
-  if (n_act == R) {  // every row, in place, as without the option; then the entries are recorded
-    const int32_t* col_h = sched + (size_t)s * R;
+  const bool whole = n_act == R;
+  StepArgs a = full;
+  if (whole) {  // every row, in place, as without the option; then the entries are recorded
     if (record && j == 0)
       E_CHECK(launch_memo_rows_gather(d_inp, nullptr, R, mp.tab, col0, col1, n_mask0, g, mask_id, 1, col, dot, nullptr, nullptr, D,
                                       nullptr, nullptr, nullptr, e->st));
-    E_CHECK(step_device(e, d_inp, R, T, col_h[0], n_mask, col_h[0] - seed_len == L - 1 ? 1 : 0, K, hp, col, dot, col_h, mp.rag(true), mp.ctl_T()));
-    return launch_memo_rows_scatter(d_inp, (const float*)e->ws["s_bcos"].p, (const int*)e->ws["p_img_max"].p, nullptr, R, mp.tab,
-                                    col0, j, record, d_inp, mp.bcos, e->st) ? fail(e, CZC_ERR_HIP, "%s", g_err) : 0;
+  } else {  // compact batch: rows, row-gathered image embeds, columns, '.' rules and records of the active rows, the step on them,
+            // then their rows and cosines back into the batch and into their own slots
+    E_CHECK(launch_memo_rows_gather(d_inp, mp.list_d, n_act, mp.tab, col0, col1, n_mask0, g, mask_id, record && j == 0 ? 1 : 0, col, dot,
+                                    mp.inp_c, full.img, D, mp.img_c, mp.col_c, mp.dot_c, e->st));
+    const int32_t* col_h = mp.h_col_c[j].data();
+    a.d_inp = mp.inp_c; a.B = n_act; a.img = mp.img_c;
+    a.gen_idx = col_h[0]; a.dot_allowed = col_h[0] - seed_len == L - 1 ? 1 : 0;
+    a.gen_rows = mp.col_c; a.dot_rows = mp.dot_c; a.gen_rows_host = col_h; a.rag = mp.len_h ? &mp.rag_c : nullptr; a.ctl_T = mp.ctl_T();
+    a.branch_floor = j < MEMO_ROWS_SUB ? mp.branch_max[j] : 0;
+    E_CHECK(memo_rows_records(e, mp, full.rec, n_act, &a.rec));
   }
-  // compact batch: rows, row-gathered image embeds, columns and '.' rules of the active rows, the step on them, then their
-  // rows and cosines back into the batch and into their own slots
-  E_CHECK(launch_memo_rows_gather(d_inp, mp.list_d, n_act, mp.tab, col0, col1, n_mask0, g, mask_id, record && j == 0 ? 1 : 0, col, dot,
-                                  mp.inp_c, e->d_img_n, D, mp.img_c, mp.col_c, mp.dot_c, e->st));
-  const int32_t* col_h = mp.h_col_c[j].data();
-  float* img_rows = e->d_img_n;
-  const int img_B = e->img_B;
-  const RowRecords rec_full = e->rec;
-  RowRecords rec_c;
-  E_CHECK(memo_rows_records(e, mp, n_act, &rec_c));
-  e->rec = rec_c;
-  e->d_img_n = mp.img_c; e->img_B = n_act; e->memo_branch_floor = j < MEMO_ROWS_SUB ? mp.branch_max[j] : 0;
-  const int rc = step_device(e, mp.inp_c, n_act, T, col_h[0], n_mask, col_h[0] - seed_len == L - 1 ? 1 : 0, K, hp, mp.col_c, mp.dot_c,
-                             col_h, mp.rag(false), mp.ctl_T());
-  e->d_img_n = img_rows; e->img_B = img_B; e->memo_branch_floor = 0; e->rec = rec_full;
-  E_CHECK(rc);
-  return launch_memo_rows_scatter(mp.inp_c, (const float*)e->ws["s_bcos"].p, (const int*)e->ws["p_img_max"].p, mp.list_d, n_act,
-                                  mp.tab, col0, j, record, d_inp, mp.bcos, e->st) ? fail(e, CZC_ERR_HIP, "%s", g_err) : 0;
+  E_CHECK(step_device(e, a));
+  return launch_memo_rows_scatter(a.d_inp, (const float*)e->ws["s_bcos"].p, (const int*)e->ws["p_img_max"].p, whole ? nullptr : mp.list_d,
+                                  n_act, mp.tab, col0, j, record, d_inp, mp.bcos, e->st) ? fail(e, CZC_ERR_HIP, "%s", g_err) : 0;
 }
 
 // czc_score_rows on the device: CLIP cosine of rows [n, T] (BERT ids; len: the rows' token counts or null = T) with
 // img_rows [n, D] (normalised, row-gathered) -> cos [n].  The text bridge on the row itself -- the per-row form with K = 1 and
 // a candidate that repeats the id column 0 holds -- then the tower as czc_encode_text runs it (independent sequences, the
 // exact tower of the engine precision) and the steps' cosine kernel.  Buffers of its own: a step's are left alone.
-// d_rival [n, M] (czc_score_rows_vs; null otherwise): indices into the resident batch; the rival cosine kernel then leaves the same
+// d_rival [n, M] (czc_score_rows_vs; null otherwise): indices into the resident batch (e->d_img_n); the rival cosine kernel then leaves the same
 // cosines and d_disc [n] = P(own image | row) among the row's own image and its rivals
 int score_rows_device(czc_engine* e, const int* d_rows, int n, int T, const int* d_len, const float* img_rows, float* d_cos,
                       const int* d_rival = nullptr, int M = 0, float* d_disc = nullptr) {
@@ -1513,7 +1515,7 @@ int score_rows_device(czc_engine* e, const int* d_rows, int n, int T, const int*
     E_CHECK(launch_bridge_rows(e->bd, d_rows, n, T, gen, cand, 1, nullptr, nullptr, e->d_lex_cls, 0, PosDev{nullptr, nullptr, 0}, cids, clen,
                                nullptr, nullptr, totals + 2, e->st, d_len)); }
   float* feat;
-  E_CHECK(clip_text_forward(e, cids, clen, n, 1, 0, totals, &feat, true));  // (reads the bridge's overflow flag with the sizes)
+  E_CHECK(clip_text_forward(e, cids, clen, n, 1, 0, totals, &feat, false, true));  // exact tower; (reads the bridge's overflow flag with the sizes)
   { ProfScope ps(e, "combine", 0);
     if (d_rival) E_CHECK(launch_cosine_rival(feat, img_rows, n, 1, e->cfg.clip_proj, d_rival, M, e->d_img_n, e->img_B, e->logit_scale_exp, d_cos,
                                              d_disc, flag, e->st));
@@ -1558,10 +1560,11 @@ int tie_begin(czc_engine* e, int R, int T, int seed_len, const int32_t* group, c
 }
 
 // the merged captions' cosines at a snapshot: one row per group (its leader) through score_rows_device, then to every member
-int tie_score(czc_engine* e, const TiePlan& tp, const int* d_inp, int R, int T, bool len_mode) {
+// img_rows [R, D]: the call's image rows (CallBatch::img)
+int tie_score(czc_engine* e, const TiePlan& tp, const int* d_inp, const float* img_rows, int R, int T, bool len_mode) {
   const int D = e->cfg.clip_proj;
   E_CHECK(launch_gather_rows_w32(d_inp, tp.d_lead, tp.G, T, tp.rows_c, e->st));
-  E_CHECK(launch_gather_rows_f32(e->d_img_n, tp.d_lead, tp.G, D, tp.img_c, e->st));
+  E_CHECK(launch_gather_rows_f32(img_rows, tp.d_lead, tp.G, D, tp.img_c, e->st));
   E_CHECK(score_rows_device(e, tp.rows_c, tp.G, T, len_mode ? tp.d_lead_len : nullptr, tp.img_c, tp.cos_c));
   E_CHECK(launch_gather_rows_w32(tp.cos_c, tp.d_gor, R, 1, tp.cos, e->st));
   return 0;
@@ -2075,7 +2078,7 @@ int czc_encode_text(czc_engine* e, const int32_t* clip_ids, const int32_t* clip_
   E_HIP(hipMemsetAsync(totals, 0, PLAN_TOTALS, e->st));
   { int* flag; E_CHECK(ensure(e, "s_nonfinite", 32, (void**)&flag)); E_HIP(hipMemsetAsync(flag, 0, 32, e->st)); }
   float* feat;
-  E_CHECK(clip_text_forward(e, cids, clen, n, 1, 0, totals, &feat, true));  // independent sequences: no sharing; exact tower
+  E_CHECK(clip_text_forward(e, cids, clen, n, 1, 0, totals, &feat, false, true));  // independent sequences: no sharing; exact tower
   E_HIP(hipMemcpyAsync(out_embeds, feat, (size_t)n * e->cfg.clip_proj * 4, hipMemcpyDefault, e->st));
   E_HIP(hipStreamSynchronize(e->st));
   return CZC_OK;
@@ -2236,9 +2239,11 @@ int czc_step(czc_engine* e, int32_t* inp, int B, int T, int gen_idx, int n_mask,
   { int* flag; E_CHECK(ensure(e, "s_nonfinite", 32, (void**)&flag)); E_HIP(hipMemsetAsync(flag, 0, 32, e->st)); }
   E_CHECK(ensure(e, "g_inp", (size_t)B * T * 4, (void**)&d_inp));
   E_HIP(hipMemcpyAsync(d_inp, inp, (size_t)B * T * 4, hipMemcpyDefault, e->st));
-  e->gate_now = false;  // parity granularity: every one of the K fused scores is an output, all of them are refined
-  e->in_generate = false;
-  E_CHECK(step_device(e, d_inp, B, T, gen_idx, n_mask, dot_allowed, top_k, hp));
+  StepArgs a{d_inp, B, T, gen_idx, n_mask, dot_allowed, top_k, *hp};
+  // parity granularity: every one of the K fused scores is an output, all of them are refined -- no gate (need_cos is read on the
+  // gated path only: its default)
+  a.img = resident_images(e, B); a.mode = StepMode{false, false, true};
+  E_CHECK(step_device(e, a));
   const size_t bk = (size_t)B * top_k;
   if (out) {
     E_CHECK(copy_out(e, out->probs, "s_probs", bk * 4));
@@ -2256,12 +2261,7 @@ int czc_step(czc_engine* e, int32_t* inp, int B, int T, int gen_idx, int n_mask,
     E_CHECK(copy_out(e, out->logits, "b_logits", (size_t)B * e->cfg.bert_vocab * 4));
   }
   E_HIP(hipMemcpyAsync(inp, d_inp, (size_t)B * T * 4, hipMemcpyDefault, e->st));
-  E_HIP(hipMemcpyAsync(e->h_totals + 9, e->ws["s_nonfinite"].p, 24, hipMemcpyDeviceToHost, e->st));
-  E_HIP(hipStreamSynchronize(e->st));
-  if (e->h_totals[9]) return fail(e, CZC_ERR_OVERFLOW, "non-finite CLIP cosine: an fp16 quantity overflowed in a tower (fp16 residual rows: set option resid16 = 0 on the bf16 engine, refine_rows16 = 0 on the refine engine; fp16 operands: use CZC_PREC_SPLIT)%s");
-  { float dev; memcpy(&dev, e->h_totals + 10, 4); e->guard_max_dev = fmaxf(e->guard_max_dev, dev); e->guard_trips += e->h_totals[11];
-    e->stat_gated += e->h_totals[13]; e->stat_gate_images += e->h_totals[14]; }
-  return CZC_OK;
+  return finish_steps(e);
 }
 
 // ---- czc_generate and the czc_generate_rows* family --------------------------------------------------------------------
@@ -2381,22 +2381,24 @@ static Sched build_schedule(const RowsCall& c, bool any_idle) {
   return sc;
 }
 
-// What a call changes in the engine while its steps run comes back on every exit -- the resident image batch (swapped for the
-// rows' gather), the per-row records, and no later call may re-use a forward by this call's columns -- so the set-up and the steps
-// in its scope leave through E_CHECK / E_HIP.  A rows call that fails waits for the work it has queued.
+// What a rows call leaves in the engine comes back on every exit: no later call may re-use a forward by this call's columns (they
+// are the caller's memory), so the set-up and the steps in its scope leave through E_CHECK / E_HIP.  A rows call that fails waits
+// for the work it has queued.
 struct CallScope {
   czc_engine* e; bool rows, ok = false;
-  float* img = e->d_img_n; int img_B = e->img_B;
   ~CallScope() {
-    e->d_img_n = img; e->img_B = img_B; e->rec = RowRecords{};
     if (rows) { e->bert_pruned_rows = nullptr; if (!ok) (void)hipStreamSynchronize(e->st); }
   }
 };
 
-// The uploads of a call: the start rows and, for a rows call, the schedule, the per-row records (e->rec from here on) and the
-// gather of the rows' image embeddings, which then stand in for the resident batch (inside a CallScope)
-static int upload_call(czc_engine* e, RowsCall& c, Sched& sc, int** d_inp) {
+// What upload_call leaves for the steps of a call: the start rows, the image rows [R, D] they are scored against (the resident
+// batch, or its gather by image_of_row) and the per-row records
+struct CallBatch { int* d_inp = nullptr; const float* img = nullptr; RowRecords rec; };
+
+// The uploads of a call: the start rows and, for a rows call, the schedule, the per-row records and the gather of its image rows
+static int upload_call(czc_engine* e, RowsCall& c, Sched& sc, CallBatch* cb) {
   const int B = c.R, T = c.T, D = e->cfg.clip_proj;
+  cb->img = resident_images(e, B);
   auto put = [e](const char* name, const void* src, size_t bytes, void** out) -> int {
     E_CHECK(ensure(e, name, bytes, out));
     E_HIP(hipMemcpyAsync(*out, src, bytes, hipMemcpyHostToDevice, e->st));
@@ -2404,15 +2406,15 @@ static int upload_call(czc_engine* e, RowsCall& c, Sched& sc, int** d_inp) {
   };
   { int* flag; E_CHECK(ensure(e, "s_nonfinite", 32, (void**)&flag)); E_HIP(hipMemsetAsync(flag, 0, 32, e->st)); }
   if (c.from) {  // every row brings its own start row: one upload, no broadcast
-    E_CHECK(put("g_inp", c.init, (size_t)B * T * 4, (void**)d_inp));
+    E_CHECK(put("g_inp", c.init, (size_t)B * T * 4, (void**)&cb->d_inp));
   } else {
     int* d_row;
-    E_CHECK(ensure(e, "g_inp", (size_t)B * T * 4, (void**)d_inp));
+    E_CHECK(ensure(e, "g_inp", (size_t)B * T * 4, (void**)&cb->d_inp));
     E_CHECK(put("g_row", c.init, (size_t)T * 4, (void**)&d_row));
-    E_CHECK(launch_broadcast_rows_i32(d_row, T, B, *d_inp, e->st));
+    E_CHECK(launch_broadcast_rows_i32(d_row, T, B, cb->d_inp, e->st));
   }
   if (!c.rows) return 0;
-  RowRecords rec;  // one record per row, uploaded once with the schedule
+  RowRecords& rec = cb->rec;  // one record per row, uploaded once with the schedule
   static_assert(sizeof(RowHyper) == sizeof(czc_hyper) && offsetof(RowHyper, temperature) == offsetof(czc_hyper, temperature) &&
                 offsetof(RowHyper, control) == offsetof(czc_hyper, control) && offsetof(RowHyper, negative) == offsetof(czc_hyper, negative),
                 "RowHyper is czc_hyper as the kernels read it");
@@ -2436,21 +2438,21 @@ static int upload_call(czc_engine* e, RowsCall& c, Sched& sc, int** d_inp) {
       E_CHECK(put("g_vhp", c.vocab_hp.data(), (size_t)B * sizeof(RowHyper), (void**)&rec.vhp));
     }
   }
-  e->rec = rec;
   // the embedding of row r is that of image image_of_row[r] -- one gather of the normalised embeds to [R, D] here, and the step
-  // sees a resident batch of R images (what the memo's compact batches do), so no tower or combine kernel changes
+  // sees a batch of R images (what the memo's compact batches do), so no tower or combine kernel changes
   if (c.image_of_row) {
     int* d_ior; float* img_r;
     E_CHECK(ensure(e, "g_img_r", (size_t)B * D * 4, (void**)&img_r));
     E_CHECK(put("g_ior", c.image_of_row, (size_t)B * 4, (void**)&d_ior));
     E_CHECK(launch_gather_rows_f32(e->d_img_n, d_ior, B, D, img_r, e->st));
-    e->d_img_n = img_r; e->img_B = B;
+    cb->img = img_r;
   }
   return 0;
 }
 
 // The steps of a call and its snapshots (inside a CallScope, behind upload_call)
-static int run_steps(czc_engine* e, const RowsCall& c, const Sched& sc, int* d_inp) {
+static int run_steps(czc_engine* e, const RowsCall& c, const Sched& sc, const CallBatch& cb) {
+  int* const d_inp = cb.d_inp;
   const int B = c.R, T = c.T, L = c.L, seed_len = c.seed_len, n_steps = c.n_steps, snapshot_every = c.snapshot_every;
   const bool rows = c.rows;
   float* out_cos = c.out_cos;
@@ -2495,17 +2497,16 @@ static int run_steps(czc_engine* e, const RowsCall& c, const Sched& sc, int* d_i
     rag_full = Ragged{sc.d + sc.at.rag + B, sc.d + sc.at.rag, sc.at.rag_M, sc.at.rag_max};
     if (memo_rows) {
       mrp.len_h = sc.h.data() + sc.at.rag;
-      mrp.rag_full = rag_full;
       E_CHECK(ensure(e, "mr_rag_c", sc.at.rag_block() * 4, (void**)&mrp.d_rag_c));
     }
   }
-  if (memo_rows && e->rec.hp) E_CHECK(ensure(e, "mr_hp_c", (size_t)B * sizeof(RowHyper), (void**)&mrp.rec_c.hp));
-  if (memo_rows && e->rec.draw) E_CHECK(ensure(e, "mr_draw_c", (size_t)B * sizeof(RowDraw), (void**)&mrp.rec_c.draw));
-  if (memo_rows && e->rec.rival) {
+  if (memo_rows && cb.rec.hp) E_CHECK(ensure(e, "mr_hp_c", (size_t)B * sizeof(RowHyper), (void**)&mrp.rec_c.hp));
+  if (memo_rows && cb.rec.draw) E_CHECK(ensure(e, "mr_draw_c", (size_t)B * sizeof(RowDraw), (void**)&mrp.rec_c.draw));
+  if (memo_rows && cb.rec.rival) {
     E_CHECK(ensure(e, "mr_riv_c", (size_t)B * c.M * 4, (void**)&mrp.rec_c.rival));
     E_CHECK(ensure(e, "mr_rdelta_c", (size_t)B * 4, (void**)&mrp.rec_c.delta));
   }
-  if (memo_rows && e->rec.vset) E_CHECK(ensure(e, "mr_vset_c", (size_t)B * 4, (void**)&mrp.rec_c.vset));
+  if (memo_rows && cb.rec.vset) E_CHECK(ensure(e, "mr_vset_c", (size_t)B * 4, (void**)&mrp.rec_c.vset));
   // czc_generate_rows_tied (check_groups has run): the group table goes up once, behind the schedule
   TiePlan tie;
   const bool tied = c.group != nullptr && n_steps > 0;
@@ -2518,20 +2519,21 @@ static int run_steps(czc_engine* e, const RowsCall& c, const Sched& sc, int* d_i
     const int pos = c.positions[rows ? (size_t)s * B : (size_t)s];
     const int nm = c.n_mask_at(s), dot = pos == L - 1 ? 1 : 0;
     const bool snap_idx = (s + 1) % snapshot_every == 0;
-    e->gate_now = e->refine && e->refine_gate_delta > 0.f && e->refine_guard_dev > 0.f && !audit[s];
-    e->gate_need_cos = cos_step[s] != 0;
-    e->in_generate = true;
-    e->rec.step = (unsigned)s;
-    if (memo_rows) E_CHECK(memo_rows_step(e, mrp, c, sc, s, d_inp));
-    else if (rows) E_CHECK(step_device(e, d_inp, B, T, seed_len + pos, nm, dot, c.top_k, c.hp, sc.d + sc.at.cols(s), sc.d + sc.at.dots(s),
-                                       sc.h.data() + sc.at.cols(s), c.len ? &rag_full : nullptr,
-                                       c.len ? seed_len + c.len[0] + 1 : 0));  // (a callback call's rows share one length: checked above)
-    else if (memo) E_CHECK(memo_step(e, mp, c, s, d_inp));
-    else E_CHECK(step_device(e, d_inp, B, T, seed_len + pos, nm, dot, c.top_k, c.hp));
+    StepArgs a{d_inp, B, T, seed_len + pos, nm, dot, c.top_k, *c.hp};  // (rows: row 0's column and '.' rule)
+    a.img = cb.img; a.rec = cb.rec; a.rec.step = (unsigned)s;
+    a.mode = StepMode{true, e->refine && e->refine_gate_delta > 0.f && e->refine_guard_dev > 0.f && !audit[s], cos_step[s] != 0};
+    if (rows) {
+      a.gen_rows = sc.d + sc.at.cols(s); a.dot_rows = sc.d + sc.at.dots(s); a.gen_rows_host = sc.h.data() + sc.at.cols(s);
+      a.rag = c.len ? &rag_full : nullptr;
+      a.ctl_T = c.len ? seed_len + c.len[0] + 1 : 0;  // (a callback call's rows share one length: checked above)
+    }
+    if (memo_rows) E_CHECK(memo_rows_step(e, mrp, c, sc, s, a));
+    else if (memo) E_CHECK(memo_step(e, mp, s, a));
+    else E_CHECK(step_device(e, a));
     // the tie: one launch on the full batch, behind whatever the step did (in place, compact batch and scatter, memo fill)
     if (tied && launch_tie_rows(d_inp, B, T, sc.d + sc.at.cols(s), tie.d_gor, tie.d_off, tie.d_rows, e->st)) return fail(e, CZC_ERR_HIP, "%s", g_err);
     // a tied call returns the cosine of the caption as it stands, one score per group
-    if (tied && snap_idx && out_cos) E_CHECK(tie_score(e, tie, d_inp, B, T, c.len != nullptr));
+    if (tied && snap_idx && out_cos) E_CHECK(tie_score(e, tie, d_inp, cb.img, B, T, c.len != nullptr));
     if (snap_idx) {
       hipError_t h = c.out_ids ? hipMemcpyAsync(c.out_ids + (size_t)snap * B * T, d_inp, (size_t)B * T * 4, hipMemcpyDefault, e->st) : hipSuccess;
       if (out_cos && h == hipSuccess)  // memo: the full-batch cosines (a compacted step leaves B_act of them in s_bcos)
@@ -2549,16 +2551,11 @@ static int generate_impl(czc_engine* e, RowsCall& c) {
   if (int rc = check_call(e, c, &any_idle)) return rc;
   Sched sc = build_schedule(c, any_idle);
   { CallScope scope{e, c.rows};
-    int* d_inp = nullptr;
-    E_CHECK(upload_call(e, c, sc, &d_inp));
-    E_CHECK(run_steps(e, c, sc, d_inp));
+    CallBatch cb;
+    E_CHECK(upload_call(e, c, sc, &cb));
+    E_CHECK(run_steps(e, c, sc, cb));
     scope.ok = true; }
-  E_HIP(hipMemcpyAsync(e->h_totals + 9, e->ws["s_nonfinite"].p, 24, hipMemcpyDeviceToHost, e->st));
-  E_HIP(hipStreamSynchronize(e->st));
-  if (e->h_totals[9]) return fail(e, CZC_ERR_OVERFLOW, "non-finite CLIP cosine: an fp16 quantity overflowed in a tower (fp16 residual rows: set option resid16 = 0 on the bf16 engine, refine_rows16 = 0 on the refine engine; fp16 operands: use CZC_PREC_SPLIT)%s");
-  { float dev; memcpy(&dev, e->h_totals + 10, 4); e->guard_max_dev = fmaxf(e->guard_max_dev, dev); e->guard_trips += e->h_totals[11];
-    e->stat_gated += e->h_totals[13]; e->stat_gate_images += e->h_totals[14]; }
-  return CZC_OK;
+  return finish_steps(e);
 }
 
 // ---- the checks of the optional per-row arrays: each validates its array and, where the array carries nothing, drops it, so
@@ -2924,7 +2921,7 @@ static int score_rows_impl(czc_engine* e, const char* who, const int32_t* rows, 
     for (int r = 0; r < R; ++r) out_disc[r] = 1.0f;  // no table: no row has a rival
   E_HIP(hipMemcpyAsync(e->h_totals + 9, e->ws["s_nonfinite"].p, 4, hipMemcpyDeviceToHost, e->st));
   E_HIP(hipStreamSynchronize(e->st));
-  if (e->h_totals[9]) return fail(e, CZC_ERR_OVERFLOW, "non-finite CLIP cosine: an fp16 quantity overflowed in a tower (fp16 residual rows: set option resid16 = 0 on the bf16 engine, refine_rows16 = 0 on the refine engine; fp16 operands: use CZC_PREC_SPLIT)%s");
+  if (e->h_totals[9]) return fail(e, CZC_ERR_OVERFLOW, MSG_NONFINITE);
   return CZC_OK;
 }
 
@@ -3261,7 +3258,7 @@ static int test_text_tower(void* engine, const int32_t* clip_ids, const int32_t*
   E_HIP(hipMemsetAsync(totals, 0, PLAN_TOTALS, e->st));
   { int* flag; E_CHECK(ensure(e, "s_nonfinite", 32, (void**)&flag)); E_HIP(hipMemsetAsync(flag, 0, 32, e->st)); }
   float* feat;
-  E_CHECK(clip_text_forward(e, cids, clen, B, K, e->share_prefix, totals, &feat));
+  E_CHECK(clip_text_forward(e, cids, clen, B, K, e->share_prefix, totals, &feat, false));  // outside czc_generate: the engine's own rows
   if (n_dup) *n_dup = e->h_totals[HT_PLAN + 5];
   E_HIP(hipMemcpyAsync(out, feat, (size_t)n * e->cfg.clip_proj * 4, hipMemcpyDefault, e->st));
   E_HIP(hipStreamSynchronize(e->st));

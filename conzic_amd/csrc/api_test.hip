@@ -575,18 +575,65 @@ struct HostPlan {
 // type in front of and behind them; *rows0 = the first data row
 int guarded_operand(DevPool& pool, int precision, const float* src, size_t n, size_t row, unsigned char** rows0) {
   const int GR = CZC_TEST_PLAN_GUARD;
+  const size_t per_row = row / prec_bytes(precision);  // elements (fp16 planes for the split type: 0x7e00 twice per element)
   unsigned char* d = (unsigned char*)pool.alloc((n + 2 * GR) * row); T_PTR(d);
-  std::vector<uint32_t> nan((size_t)GR * row / 4, precision == PREC_BF16 ? 0x7fc07fc0u : 0x7e007e00u);
+  std::vector<uint32_t> nan((size_t)GR * row / 4,
+                            precision == PREC_F32 ? 0x7fc00000u : precision == PREC_BF16 ? 0x7fc07fc0u : 0x7e007e00u);
   T_HIP(hipMemcpy(d, nan.data(), (size_t)GR * row, hipMemcpyHostToDevice));
   T_HIP(hipMemcpy(d + (GR + n) * row, nan.data(), (size_t)GR * row, hipMemcpyHostToDevice));
   if (n) {
-    float* f = (float*)pool.up(src, n * (row / 2) * 4); T_PTR(f);
-    T_CHECK(launch_convert(precision, f, d + GR * row, (long)(n * (row / 2)), nullptr));
+    float* f = (float*)pool.up(src, n * per_row * 4); T_PTR(f);
+    if (precision == PREC_F32) T_HIP(hipMemcpy(d + GR * row, f, n * row, hipMemcpyDeviceToDevice));
+    else T_CHECK(launch_convert(precision, f, d + GR * row, (long)(n * per_row), nullptr));
   }
   *rows0 = d + GR * row;
   return 0;
 }
 }  // namespace
+
+// One launch_attention call on plain segments (no prefix), in the two forms of SegTable the towers use: seq_len given -> own_off /
+// own_len tables (BERT ragged; zero-length segments allowed), seq_len null -> the fixed_T form (BERT padded, vision).  max_keys 0:
+// the longest segment, else what the caller sizes the kernels' LDS with (must cover the longest segment: the kernels trust it).
+// Guards and pre-fills as czc_test_attention_plan.
+int czc_test_attention_seq(int precision, int n_seg, const int32_t* seq_len, int fixed_T, int max_keys, int heads, int causal,
+                           float scale, const float* qkv, float* out) {
+  const bool known = precision == PREC_BF16 || precision == PREC_F16 || precision == PREC_F32 || precision == PREC_F16X3;
+  if (!known || n_seg < 0 || n_seg > (1 << 20) || heads < 1 || heads > 64 || (causal != 0 && causal != 1) || max_keys < 0 ||
+      (!seq_len && (fixed_T < 0 || fixed_T > 4096))) {
+    snprintf(TEST_ERR, 512, "attention_seq: precision %d n_seg %d fixed_T %d max_keys %d heads %d causal %d", precision, n_seg, fixed_T,
+             max_keys, heads, causal);
+    return CZC_ERR_ARG;
+  }
+  const int GR = CZC_TEST_PLAN_GUARD;
+  std::vector<int> off((size_t)n_seg + 1, 0);
+  int longest = 0;
+  for (int s = 0; s < n_seg; ++s) {
+    const int len = seq_len ? seq_len[s] : fixed_T;
+    if (len < 0 || len > 4096) { snprintf(TEST_ERR, 512, "attention_seq: segment %d has %d rows", s, len); return CZC_ERR_ARG; }
+    off[s + 1] = off[s] + len;
+    longest = std::max(longest, len);
+  }
+  if (max_keys && max_keys < longest) {
+    snprintf(TEST_ERR, 512, "attention_seq: max_keys %d below the longest segment (%d rows)", max_keys, longest);
+    return CZC_ERR_ARG;
+  }
+  const size_t rows = off[n_seg], Hd = (size_t)heads * 64, orow = Hd * prec_bytes(precision), all = rows + 2 * GR;
+  DevPool pool;
+  unsigned char* dq;
+  T_CHECK(guarded_operand(pool, precision, qkv, rows, 3 * orow, &dq));
+  unsigned char* dout = (unsigned char*)pool.alloc(all * orow); T_PTR(dout);
+  T_HIP(hipMemset(dout, 0x5a, all * orow));
+  SegTable tab{nullptr, nullptr, nullptr, nullptr, n_seg, fixed_T};
+  if (seq_len) {
+    int* doff = (int*)pool.up(off.data(), ((size_t)n_seg + 1) * 4); T_PTR(doff);
+    int* dlen = (int*)pool.up(seq_len, (size_t)n_seg * 4); T_PTR(dlen);
+    tab = SegTable{nullptr, nullptr, doff, dlen, n_seg, 0};
+  }
+  T_HIP(hipDeviceSynchronize());
+  T_CHECK(launch_attention(precision, dq, tab, max_keys ? max_keys : longest, heads, causal, scale, dout + GR * orow, nullptr));
+  T_HIP(hipDeviceSynchronize());
+  return down_act(pool, precision, dout, all * Hd, out);
+}
 
 int czc_test_attention_pooled(int precision, int B, int K, int heads, float scale, const int32_t* trunk_len, const int32_t* own_len,
                               const int32_t* rep, const float* qkv, const float* qc, float* out) {

@@ -176,6 +176,7 @@ TEST_SIGNATURES = {
     "czc_test_attention": (_I, [_I, _I, _P, _I, _I, C.c_float, _P, _P]),
     "czc_test_attention_plan": (_I, [_I, _I, _I, _I, _I, C.c_float, _P, _P, _I, _P, _P]),
     "czc_test_attention_pooled": (_I, [_I, _I, _I, _I, C.c_float, _P, _P, _P, _P, _P, _P]),
+    "czc_test_attention_seq": (_I, [_I, _I, _P, _I, _I, _I, _I, C.c_float, _P, _P]),
     "czc_test_attention_mapped": (_I, [_I, _I, _I, _I, C.c_float, _P, _P, _P, _I, _P, _P]),
     "czc_test_layer0_plan": (_I, [_I, _I, _P, _P, _I, _P, _P, _P, _P, _I, _P, _I, _P]),
     "czc_test_text_tower": (_I, [_P, _I, _I, _P, _P, _P, _P]),

@@ -76,6 +76,20 @@ int czc_test_attention(int precision, int n_seq, const int32_t* seq_len, int hea
 #define CZC_TEST_PLAN_GUARD 32
 int czc_test_attention_plan(int precision, int kernel, int B, int K, int heads, float scale, const int32_t* trunk_len,
                             const int32_t* own_len, int pass_img_max, const float* qkv, float* out);
+/* One launch_attention call on PLAIN segments (no prefix) in the forms the BERT and vision towers pass them, through
+ * attention_mfma_kernel / attention_mfma_split_kernel / attention_valu_kernel, whichever `precision` (1 f32, 0 bf16, 4 fp16,
+ * 3 split-fp16) and the "mfma_attention" switch select:
+ *   seq_len [n_seg]: own_off / own_len tables, rows back to back (own_off = exclusive scan), prefix tables null; a segment may
+ *     have 0 rows.  seq_len NULL: the fixed_T form, SegTable{NULL, NULL, NULL, NULL, n_seg, fixed_T} (fixed_T is ignored otherwise).
+ *   max_keys: what the launcher sizes the kernels' shared memory with; 0 = the longest segment.  A value below the longest
+ *     segment is refused here with CZC_ERR_ARG (the kernels trust it); one the launcher does not serve (outside 1..96) comes back
+ *     as the launcher's error.  n_seg 0 is an empty launch: it succeeds and writes nothing.
+ *   causal 0 | 1.  qkv: fp32 [rows, 3*heads*64] (rows = sum of the lengths), rounded to the operand type on the device.
+ *   out: fp32 [CZC_TEST_PLAN_GUARD + rows + CZC_TEST_PLAN_GUARD, heads*64], guarded and pre-filled as czc_test_attention_plan's
+ *     (NaN rows of the operand type around qkv, bytes 0x5a in every byte of the device output before the launch).
+ * Returns 0 or a CZC_ERR_* status. */
+int czc_test_attention_seq(int precision, int n_seg, const int32_t* seq_len, int fixed_T, int max_keys, int heads, int causal,
+                           float scale, const float* qkv, float* out);
 /* attention_image_kernel's POOLED mode (launch_attention_image_pooled: the tower's last layer) on the same kind of host-given
  * plan, per-image kernel forced, precision 0 bf16 / 4 fp16:
  *   qkv  fp32 [rows, 3*heads*64]: k / v of all packed rows (its q columns must not be read: the caller may poison them);

@@ -7,6 +7,10 @@ that directly (one masked einsum per image over candidates padded to the image's
 it to seq_ref() on the materialised sequences.  It also carries what the plan tests need around the reference: the three
 mask-widening mutants (a reference that is wrong by exactly one key), the rounding model that sets the tolerance where the
 inputs are not standard normal, and the constructions of those inputs (bait keys, spotlight queries).
+
+The same for plain segments in both mask modes (seg_ref and the seg_* constructions at the end: what launch_attention serves
+for the BERT and vision towers, tests/test_attention_seq_gpu.py): mutants "next" / "prev" / "dup_last", bait by segment parity,
+spotlights on either side of the 32-key tile edges, and the twin input on which a last key counted twice shows.
 """
 import numpy as np
 import torch
@@ -286,6 +290,17 @@ def spotlight(x, trunk_len, own_len, kind):
     return x, tgt, trow
 
 
+def _tol_from_model(prec, model, ref, xr, heads):
+    """the rule of rounding_tol / seg_rounding_tol: 4 * max |model - ref| + 2 ulp * max |v|, floored for f32 / split-fp16"""
+    xr = np.asarray(xr).reshape(-1, 3, heads, 64)
+    merr = float(np.abs(model - ref).max()) if ref.size else 0.0
+    vmax = float(np.abs(xr[:, 2]).max()) if xr.size else 0.0
+    tol = 4.0 * merr + 2.0 * ULP[prec] * vmax
+    if prec in (F32, SPLIT):
+        tol = max(tol, NORMAL_TOL[prec])
+    return tol, merr
+
+
 def rounding_tol(prec, xr, trunk_len, own_len, heads, scale, ref):
     """Tolerance where the inputs are not standard normal, as a margin over a ROUNDING MODEL OF THE REFERENCE (never over a
     kernel): tol = 4 * max |model - ref| + 2 ulp(output type) * max |v|, floored for f32 / split-fp16 (whose model lies below
@@ -300,9 +315,146 @@ def rounding_tol(prec, xr, trunk_len, own_len, heads, scale, ref):
     -> tol, model error"""
     xr = np.asarray(xr).reshape(-1, 3, heads, 64)
     model = plan_ref(xr.reshape(xr.shape[0], -1), trunk_len, own_len, heads, scale, model=prec)
-    merr = float(np.abs(model - ref).max()) if ref.size else 0.0
-    vmax = float(np.abs(xr[:, 2]).max()) if xr.size else 0.0
-    tol = 4.0 * merr + 2.0 * ULP[prec] * vmax
-    if prec in (F32, SPLIT):
-        tol = max(tol, NORMAL_TOL[prec])
-    return tol, merr
+    return _tol_from_model(prec, model, ref, xr, heads)
+
+
+# ---- plain segments (no prefix), both mask modes: what launch_attention serves for the BERT and vision towers ------------------
+def seg_rows(lens):
+    """per packed row of plain segments: segment, position inside it, the segment's length"""
+    lens = np.asarray(lens, np.int64).reshape(-1)
+    seg = np.repeat(np.arange(lens.size), lens)
+    pos = np.arange(int(lens.sum())) - np.repeat(np.cumsum(lens) - lens, lens)
+    return seg, pos, lens[seg]
+
+
+def seg_ref(qkv, lens, heads, causal, scale, mutant=None, model=None, want_weight=None):
+    """fp64 context rows [rows, heads*64] of plain segments packed back to back, from operands already rounded to the operand
+    type: query i of a segment sees its keys 0..i (causal) or all of them.
+
+    mutant: None, or a reference that is wrong by exactly ONE key: "next" -- every query also sees the row that follows its
+    segment (key 0 of the following segment; the last segment has none); "prev" -- every query also sees the row in front of
+    its segment (the last key of the preceding segment); "dup_last" -- the last visible key of every query is counted twice
+    (what an unmasked padding lane does: those lanes re-read the clamped last key).
+    model: None, or a precision code: the rounding model of plan_ref.
+    want_weight: None, or [rows] / [rows, 2] key indices inside the query's segment: also returns the softmax weight
+    [rows, heads] each query puts on that key, or on the pair (a pair of equal indices counts once)."""
+    lens = np.asarray(lens, np.int64).reshape(-1)
+    rows = int(lens.sum())
+    x = np.ascontiguousarray(qkv, np.float64).reshape(rows, 3, heads, 64)
+    out = np.zeros((rows, heads, 64), np.float64)
+    wout = np.zeros((rows, heads), np.float64) if want_weight is not None else None
+    if want_weight is not None:
+        want_weight = np.asarray(want_weight, np.int64).reshape(rows, -1)
+    start = np.cumsum(lens) - lens
+    for L in np.unique(lens[lens > 0]):   # the segments of one length in one batch
+        L = int(L)
+        o = start[lens == L]                                     # [S]
+        idx = o[:, None] + np.arange(L)[None]                    # [S, L] packed rows
+        q, k, v = (x[idx][:, :, c].transpose(0, 2, 1, 3) for c in range(3))   # [S, h, L, d]
+        mask = np.tril(np.ones((L, L), bool)) if causal else np.ones((L, L), bool)
+        mask = np.broadcast_to(mask, (o.size, 1, L, L))
+        if mutant in ("next", "prev"):
+            er = o + L if mutant == "next" else o - 1
+            has = (er >= 0) & (er < rows)
+            er = np.clip(er, 0, rows - 1)
+            k = np.concatenate([k, x[er, 1][:, :, None]], 2)
+            v = np.concatenate([v, x[er, 2][:, :, None]], 2)
+            mask = np.concatenate([mask, np.broadcast_to(has[:, None, None, None], (o.size, 1, L, 1))], 3)
+        s = np.matmul(q, k.transpose(0, 1, 3, 2)) * scale       # [S, h, L, M]
+        s = np.where(mask, s, -np.inf)
+        e = np.exp(s - s.max(-1, keepdims=True))
+        if mutant == "dup_last":
+            last = np.arange(L) if causal else np.full(L, L - 1)
+            e[:, :, np.arange(L), last] *= 2.0
+        den = e.sum(-1, keepdims=True)
+        if wout is not None:
+            t = want_weight[idx]                                 # [S, L, 1 or 2]
+            hit = (np.arange(k.shape[2])[None, None, None] == t[..., None]).any(2)   # [S, L, M]
+            wout[idx] = ((e / den) * hit[:, None]).sum(-1).transpose(0, 2, 1)
+        if model is not None:
+            e = _round64(model, e)
+        ctx = (np.matmul(e, v) / den).transpose(0, 2, 1, 3)      # [S, L, h, d]
+        out[idx] = _round64(model, ctx) if model is not None else ctx
+    out = out.reshape(rows, heads * 64)
+    return (out, wout) if want_weight is not None else out
+
+
+def seg_rounding_tol(prec, xr, lens, heads, causal, scale, ref):
+    """rounding_tol for plain segments: the same rule over seg_ref's rounding model.  -> tol, model error"""
+    xr = np.asarray(xr).reshape(-1, 3, heads, 64)
+    model = seg_ref(xr.reshape(xr.shape[0], -1), lens, heads, causal, scale, model=prec)
+    return _tol_from_model(prec, model, ref, xr, heads)
+
+
+def seg_bait(x, lens, parity):
+    """x [rows, 3, heads, 64] (modified in place) -> same.  The segments that have rows are numbered in memory order; the keys
+    of those of `parity` (0 / 1) get + C_BAIT along U, the queries of the others D_BAIT along it, every other query 0 along it:
+    the rows on either side of a victim segment are bait, and no row is both.  Run both parities: every segment with a
+    neighbour is a victim once.  v is clipped to 3.5 V_SIGMA: a context row is a convex combination of v rows (and row 0 of a
+    causal segment IS a v row), so the true reference stays under 4 V_SIGMA by construction, not by the luck of a seed."""
+    seg, _, _ = seg_rows(lens)
+    np.clip(x[:, 2], -3.5 * V_SIGMA, 3.5 * V_SIGMA, out=x[:, 2])
+    lens = np.asarray(lens, np.int64).reshape(-1)
+    ordinal = np.cumsum(lens > 0) - 1          # number of the segment among those that have rows
+    baits = ordinal[seg] % 2 == parity
+    x[:, 0, :, 0] = 0.0
+    x[baits, 1, :, 0] += C_BAIT
+    x[~baits, 0, :, 0] = D_BAIT
+    return x
+
+
+def seg_victims(lens, parity, mutant):
+    """rows of seg_bait(parity) whose output a "next" / "prev" mutant must move: victim queries with such a neighbour"""
+    seg, _, ln = seg_rows(lens)
+    lens = np.asarray(lens, np.int64).reshape(-1)
+    ordinal = np.cumsum(lens > 0) - 1
+    start = np.repeat(np.cumsum(lens) - lens, lens)
+    has = start + ln < int(lens.sum()) if mutant == "next" else start > 0
+    return (ordinal[seg] % 2 != parity) & has
+
+
+SEG_SPOT_KINDS = ("key0", "last", "key31", "key32", "key63", "key64", "diag")
+
+
+def _seg_last_visible(lens, causal):
+    _, pos, ln = seg_rows(lens)
+    return pos if causal else ln - 1
+
+
+def seg_spotlight(x, lens, kind, causal):
+    """spotlight() for plain segments: every key scaled to |k| = 8 and q = 5 k_target (logit SPOT_LOGIT at scale 0.125), the
+    target being key 0, the last visible key (the diagonal under the causal mask, the segment's last key otherwise), the key
+    at 31 / 32 / 63 / 64 -- either side of a 32-key tile edge -- clamped to the last visible key, or the diagonal.
+    -> x, target [rows] (key index inside the segment), target_row [rows] (packed row of that key)"""
+    seg, pos, ln = seg_rows(lens)
+    lastv = _seg_last_visible(lens, causal)
+    if kind == "key0":
+        tgt = np.zeros_like(pos)
+    elif kind == "last":
+        tgt = lastv
+    elif kind == "diag":
+        tgt = pos
+    elif kind in SEG_SPOT_KINDS:
+        tgt = np.minimum(int(kind[3:]), lastv)
+    else:
+        raise ValueError(kind)
+    trow = np.arange(pos.size) - pos + tgt
+    x[:, 1] *= 8.0 / np.linalg.norm(x[:, 1], axis=-1, keepdims=True)
+    x[:, 0] = (SPOT_LOGIT / 8.0) * x[trow, 1]
+    return x, tgt, trow
+
+
+def seg_twin(x, lens, causal):
+    """every key scaled to |k| = 8 and q = 5 (k_0 + k_last) / (1 + cos(k_0, k_last)), k_last the last visible key: key 0 and the
+    last visible key carry logit SPOT_LOGIT each and share the weight, so a last key counted twice moves the row by a sixth of
+    v_last - v_0.  Where the two are one key (a segment of one row, query 0 under the causal mask) this is a spotlight.
+    -> x, pair [rows, 2] (key indices inside the segment)"""
+    seg, pos, ln = seg_rows(lens)
+    lastv = _seg_last_visible(lens, causal)
+    me = np.arange(pos.size)
+    r0, r1 = me - pos, me - pos + lastv
+    x[:, 1] *= 8.0 / np.linalg.norm(x[:, 1], axis=-1, keepdims=True)
+    k0, k1 = x[r0, 1], x[r1, 1]
+    cos = (k0 * k1).sum(-1, keepdims=True) / 64.0
+    x[:, 0] = (SPOT_LOGIT / 8.0) * (k0 + k1) / (1.0 + cos)
+    return x, np.stack([np.zeros_like(pos), lastv], 1)

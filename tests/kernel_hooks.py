@@ -6,7 +6,8 @@ symbols behind it.  (Until round 5 these lived in conzic_amd/engine.py as test_*
 pytest does not collect them.)
 
 Families with a kernel-level test of their own: GEMM / LayerNorm / attention / top-K / bridge / combine (tests/test_kernels_gpu.py), the
-shared-prefix attention plans, the selection and plan kernels, the row / embedding / mover / memo kernels, the fluency kernels, the
+shared-prefix attention plans, the per-sequence attention launches (attention_seq: tests/test_attention_seq_gpu.py), the
+selection and plan kernels, the row / embedding / mover / memo kernels, the fluency kernels, the
 text bridge with candidates in its three forms (tests/test_bridge_kernel_gpu.py against the string reference tests/bridge_ref.py,
 pinned by tests/test_bridge_ref_cpu.py), the per-row forms of the top-K selection (tests/test_topk_rows_gpu.py), and -- at the end
 of this file -- every GEMM family on strided, windowed and in-place buffers (gemm_layout: tests/test_gemm_layout_gpu.py, with the
@@ -157,6 +158,24 @@ def attention_plan(prec, kernel, trunk_len, own_len, heads, scale, qkv, img_max=
     if rc != PLAN_REFUSED:
         native.check(rc, None, "czc_test_attention_plan")
     return rc == PLAN_REFUSED, full[PLAN_GUARD:PLAN_GUARD + rows], np.concatenate([full[:PLAN_GUARD], full[PLAN_GUARD + rows:]])
+
+
+def attention_seq(prec, qkv, heads, causal, scale, seq_len=None, n_seg=None, fixed_T=0, max_keys=0):
+    """One launch_attention call on plain segments (czc_test_attention_seq): seq_len given -> own_off / own_len tables (zero-length
+    segments allowed); seq_len None -> the fixed_T form, n_seg segments of fixed_T rows.  max_keys 0: the longest segment.
+    qkv fp32 [rows, 3*heads*64].  -> (out [rows, heads*64], guard [2*PLAN_GUARD, heads*64]); the launcher's refusal raises
+    native.NativeError with the launcher's message."""
+    lib = native.load_test()
+    if seq_len is not None:
+        sl = np.ascontiguousarray(seq_len, np.int32).reshape(-1)
+        n_seg, rows, slp = sl.size, int(sl.sum()), sl.ctypes.data
+    else:
+        n_seg, rows, slp = int(n_seg), int(n_seg) * int(fixed_T), None
+    qkv = np.ascontiguousarray(qkv, np.float32).reshape(rows, 3 * heads * 64)
+    full = np.empty((rows + 2 * PLAN_GUARD, heads * 64), np.float32)
+    native.check(lib.czc_test_attention_seq(int(prec), n_seg, slp, int(fixed_T), int(max_keys), int(heads), 1 if causal else 0,
+                                            C.c_float(scale), qkv.ctypes.data, full.ctypes.data), None, "czc_test_attention_seq")
+    return full[PLAN_GUARD:PLAN_GUARD + rows], np.concatenate([full[:PLAN_GUARD], full[PLAN_GUARD + rows:]])
 
 
 def topk(logits, mask, K, temperature, dot_id, dot_allowed):

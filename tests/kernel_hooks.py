@@ -17,6 +17,7 @@ Three kinds of guarded result: the attention-plan hooks return their guard rows 
 the integer / row / bridge hooks return a Guarded (GUARD words around every 1-D output, untouched()); gemm_layout returns a
 gemm_layout.Launch (whole 2-D output buffers, guard rows and pad columns included) plus the kernel family the launcher chose.
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -661,3 +662,21 @@ def gemm_layout(case, data, eps=1e-5):
         launch.part = part[GUARD:part.size - GUARD].reshape(c.N // 32, c.part_ld, 2)
         launch.part_guards = np.concatenate([part[:GUARD], part[part.size - GUARD:]])
     return launch, rc
+
+
+# czc_test_set_option defaults of the GEMM launchers (csrc/gemm.hip, gemm256.hip, gemm_wreg.hip)
+GEMM_OPTION_DEFAULTS = {"gemm256": 1, "skinny": 1, "splitk": 1, "gemm_deep": 1, "gemm_small_tiles": 4, "wreg": 1, "gemm256s": 1, "rowln_min_m": 8192,
+                        "wreg_min_m": 1, "gemm256_min_m": 8192, "gemm256s_min_m": 16384, "wreg_resid_min_m": 6144, "wreg_stats_in_kernel": 1}
+
+
+@contextlib.contextmanager
+def gemm_options(**kw):
+    """pins kernel switches and thresholds for the launches inside, and puts the defaults back whatever happens"""
+    lib = native.load_test()
+    try:
+        for k, v in kw.items():
+            assert lib.czc_test_set_option(k.encode(), int(v)) == 0, k
+        yield
+    finally:
+        for k in kw:
+            lib.czc_test_set_option(k.encode(), GEMM_OPTION_DEFAULTS[k])

@@ -11,7 +11,6 @@ a ragged edge in each -- the layouts run on the same numbers and, in this order 
   5. LayerNorm partials at part_ld > M equal those at part_ld == M, pad entries untouched.
 tests/test_gemm_layout_cpu.py proves that the checker behind 2-5 (gemm_layout.check) can fail.  Each launch prints one line
 `gemm-layout | row | layout | family` (pytest -s)."""
-import contextlib
 import functools
 from dataclasses import replace
 
@@ -22,26 +21,12 @@ import gemm_layout as GL
 import kernel_hooks as KH
 from conzic_amd import native
 from gemm_layout import BF16, F32, FP16, SPLIT, Case
+from kernel_hooks import GEMM_OPTION_DEFAULTS as DEFAULTS, gemm_options as options  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-# czc_test_set_option defaults (csrc/gemm.hip, gemm256.hip, gemm_wreg.hip)
-DEFAULTS = {"gemm256": 1, "skinny": 1, "splitk": 1, "gemm_deep": 1, "gemm_small_tiles": 4, "wreg": 1, "gemm256s": 1, "rowln_min_m": 8192,
-            "wreg_min_m": 1, "gemm256_min_m": 8192, "gemm256s_min_m": 16384, "wreg_resid_min_m": 6144, "wreg_stats_in_kernel": 1}
 HALF = [BF16, FP16]
 NAME = {BF16: "bf16", F32: "f32", SPLIT: "split", FP16: "fp16"}
-
-
-@contextlib.contextmanager
-def options(**kw):
-    lib = native.load_test()
-    try:
-        for k, v in kw.items():
-            assert lib.czc_test_set_option(k.encode(), int(v)) == 0, k
-        yield
-    finally:
-        for k in kw:
-            lib.czc_test_set_option(k.encode(), DEFAULTS[k])
 
 
 @functools.lru_cache(maxsize=None)

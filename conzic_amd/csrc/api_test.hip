@@ -47,6 +47,8 @@ static const Hooks& HK() {
 #define launch_refine_plan HK().refine_plan
 #define launch_refine_finish HK().refine_finish
 #define launch_refine_cosine HK().refine_cosine
+#define launch_gather_row_hyper HK().gather_row_hyper
+#define launch_gather_row_draw HK().gather_row_draw
 #define g_use_gemm256 (*HK().use_gemm256)
 #define g_use_skinny (*HK().use_skinny)
 #define g_use_splitk (*HK().use_splitk)
@@ -1806,6 +1808,106 @@ int czc_test_gemm_layout(const czc_gemm_layout* c) {
   if (rc) return -rc;
   if (family <= 0) { snprintf(TEST_ERR, 512, "gemm_layout: the launcher recorded no family"); return -CZC_ERR_STATE; }
   return family;
+}
+
+// ---- the combine kernel in every instantiation without rivals (tests/test_combine_kernel_gpu.py against tests/combine_ref.py) ------
+// form 0 <false,false,false> (gen_idx), 1 <true,false,false> (gen_rows), 2 <true,true,false> (+ hp_rows), 3 <true,true,true>
+// (+ draw_rows).  The cosines come from text_feat / img_embeds (normalised by launch_l2_normalize) or, with text_feat null, from
+// cos_in placed in clip_ref before the launch.  run [B] given: hp / draw hold R full records and the B compact rows' records are
+// gathered on the device by launch_gather_row_hyper / launch_gather_row_draw (and returned in hp_out / draw_out).  Every output is
+// Guarded; every index the kernels follow is checked here first.
+int czc_test_combine_rows(int B, int K, int D, int T, const float* text_feat, const float* img_embeds, const float* cos_in,
+                          float logit_scale, const float* probs, const int32_t* cand, const float* senti_raw, const float* repeats,
+                          int form, const czc_hyper* hp, const czc_draw* draw, uint32_t draw_step, int gen_idx, const int32_t* gen_rows,
+                          const int32_t* run, int R, const int32_t* inp_in, int32_t* inp_out, float* clip_score, float* clip_ref,
+                          float* final_score, int32_t* best, float* best_cos, int32_t* nonfinite, int32_t* hp_out, int32_t* draw_out,
+                          float* scale_out) {
+  const char* who = "combine_rows";
+  static_assert(sizeof(RowHyper) == sizeof(czc_hyper) && sizeof(RowHyper) == 24, "RowHyper is czc_hyper as the kernels read it");
+  static_assert(sizeof(RowDraw) == sizeof(czc_draw) && sizeof(RowDraw) == 16, "RowDraw is czc_draw as the kernels read it");
+  T_ARG(B >= 1 && K >= 1 && form >= 0 && form <= 3 && (long)B * K <= (1 << 22), who);
+  T_ARG((text_feat != nullptr) != (cos_in != nullptr), who);
+  T_ARG(!text_feat || (img_embeds && D >= 1), who);
+  T_ARG(probs && cand && hp && clip_score && clip_ref && final_score && best && best_cos && nonfinite, who);
+  T_ARG((form == 3) == (draw != nullptr), who);
+  T_ARG((inp_in != nullptr) == (inp_out != nullptr), who);
+  T_ARG(!run || (form >= 2 && R >= 1 && all_in(run, B, 0, R) && hp_out && (form < 3 || draw_out)), who);
+  if (inp_in) {  // the write-back column of every row
+    T_ARG(T >= 1, who);
+    if (form == 0) T_ARG(gen_idx >= 0 && gen_idx < T, who);
+    else T_ARG(gen_rows && all_in(gen_rows, B, 0, T), who);
+  }
+  for (int b = 0; b < (form >= 2 ? B : 1); ++b) {  // what a row's control signal makes the kernel read
+    const czc_hyper& h = hp[run ? run[b] : b];
+    T_ARG(h.control >= 0 && h.control <= 2, who);
+    T_ARG(h.control != 1 || (senti_raw && repeats), who);
+    T_ARG(h.control != 2 || senti_raw, who);
+  }
+  DevPool pool;
+  const size_t bk = (size_t)B * K;
+  float *dt = nullptr, *din = nullptr;
+  if (text_feat) {
+    dt = (float*)pool.up(text_feat, bk * D * 4); T_PTR(dt);
+    float* di = (float*)pool.up(img_embeds, (size_t)B * D * 4); T_PTR(di);
+    din = (float*)pool.alloc((size_t)B * D * 4); T_PTR(din);
+    T_CHECK(launch_l2_normalize(di, B, D, din, nullptr));
+  }
+  float* dp = (float*)pool.up(probs, bk * 4); T_PTR(dp);
+  int* dcand = (int*)pool.up(cand, bk * 4); T_PTR(dcand);
+  float* ds = nullptr; float* dr = nullptr;
+  if (senti_raw) { ds = (float*)pool.up(senti_raw, bk * 4); T_PTR(ds); }
+  if (repeats) { dr = (float*)pool.up(repeats, bk * 4); T_PTR(dr); }
+  int* dcol = nullptr;
+  if (form >= 1) {
+    dcol = (int*)pool.alloc((size_t)B * 4); T_PTR(dcol);
+    if (gen_rows) T_HIP(hipMemcpy(dcol, gen_rows, (size_t)B * 4, hipMemcpyHostToDevice));
+    else T_HIP(hipMemset(dcol, 0, (size_t)B * 4));  // nothing is written back
+  }
+  Guarded o1, o2, o3, ob, oc, gnf, ginp, ghp, gdr;
+  T_CHECK(o1.make(pool, bk)); T_CHECK(o2.make(pool, bk)); T_CHECK(o3.make(pool, bk)); T_CHECK(ob.make(pool, B)); T_CHECK(oc.make(pool, B));
+  T_CHECK(gnf.make(pool, 8));
+  T_CHECK(gnf.zero(8));
+  if (cos_in) T_CHECK(o2.fill(cos_in));
+  if (inp_in) T_CHECK(guarded_in(pool, ginp, inp_in, (size_t)B * T));
+  const RowHyper* dh = nullptr;
+  const RowDraw* dd = nullptr;
+  if (form >= 2) {
+    const int n_rec = run ? R : B;
+    RowHyper* full = (RowHyper*)pool.up(hp, (size_t)n_rec * sizeof(czc_hyper)); T_PTR(full);
+    dh = full;
+    RowDraw* dfull = nullptr;
+    if (form == 3) { dfull = (RowDraw*)pool.up(draw, (size_t)n_rec * sizeof(czc_draw)); T_PTR(dfull); dd = dfull; }
+    if (run) {
+      int* drun = (int*)pool.up(run, (size_t)B * 4); T_PTR(drun);
+      T_CHECK(ghp.make(pool, (size_t)B * 6));
+      T_CHECK(launch_status(launch_gather_row_hyper(full, drun, B, ghp.p<RowHyper>(), nullptr)));
+      dh = ghp.p<RowHyper>();
+      if (form == 3) {
+        T_CHECK(gdr.make(pool, (size_t)B * 4));
+        T_CHECK(launch_status(launch_gather_row_draw(dfull, drun, B, gdr.p<RowDraw>(), nullptr)));
+        dd = gdr.p<RowDraw>();
+      }
+    }
+  }
+  CombineArgs a;
+  a.text_feat = dt; a.img_n = din; a.logit_scale_exp = expf(logit_scale); a.probs = dp; a.cand = dcand;
+  a.senti_raw = ds; a.repeats = dr; a.alpha = hp->alpha; a.beta = hp->beta; a.gamma = hp->gamma; a.use_senti = hp->control;
+  a.B = B; a.K = K; a.D = D; a.clip_score = o1.p<float>(); a.clip_ref = o2.p<float>(); a.final_score = o3.p<float>();
+  a.best = ob.p<int>(); a.best_cos = oc.p<float>(); a.inp = inp_in ? ginp.p<int>() : nullptr; a.T = T; a.gen_idx = gen_idx;
+  a.nonfinite = gnf.p<int>();
+  a.gen_rows = dcol; a.hp_rows = dh; a.draw_rows = dd; a.draw_step = draw_step;
+  if (scale_out) *scale_out = a.logit_scale_exp;  // the fp32 scale the kernel is given: an input of the kernel, exact to the reference
+  const int rc = launch_combine(a, nullptr);
+  T_HIP(hipDeviceSynchronize());
+  if (rc > 1) return CZC_ERR_HIP;
+  T_CHECK(o1.down(clip_score)); T_CHECK(o2.down(clip_ref)); T_CHECK(o3.down(final_score)); T_CHECK(ob.down(best)); T_CHECK(oc.down(best_cos));
+  T_CHECK(gnf.down(nonfinite));
+  if (inp_in) T_CHECK(ginp.down(inp_out));
+  if (run) {
+    T_CHECK(ghp.down(hp_out));
+    if (form == 3) T_CHECK(gdr.down(draw_out));
+  }
+  return rc == 1 ? CZC_TEST_REFUSED : 0;
 }
 
 }  // extern "C"

@@ -3286,7 +3286,8 @@ const void* czc_internal_hooks(int abi) {
       &fluency_expand_tables, &launch_expand_mask_rows, &launch_logprob_target,
       &launch_bridge_rows, &launch_bridge_rows_hp, &launch_softmax_mask_topk_rows, &launch_softmax_mask_topk_rows_hp,
       &launch_softmax_mask_topk_rows_vocab,
-      []() -> int { return czc::g_gemm_family; }};
+      []() -> int { return czc::g_gemm_family; },
+      &launch_gather_row_hyper, &launch_gather_row_draw};
   return abi == HOOKS_ABI ? &h : nullptr;
 }
 

@@ -457,7 +457,7 @@ int launch_pll_sum(const float* logp, int R, int Lmax, const int* len_of_row, fl
 // ---- czc_internal_hooks (declared below, private to the build): what libconzic_hip_test.so may reach inside this library -----------
 // The product library has hidden visibility; the hook library (api_test.hip) gets the launchers it wraps and the
 // process-wide kernel-family switches it flips through this table instead of through exported C++ symbols.
-constexpr int HOOKS_ABI = 0x060d;
+constexpr int HOOKS_ABI = 0x060e;
 struct Hooks {
   char* (*err_buf)();  // the calling host thread's g_err [512]
   decltype(&launch_gemm) gemm;
@@ -531,6 +531,9 @@ struct Hooks {
   decltype(&launch_softmax_mask_topk_rows_vocab) softmax_mask_topk_rows_vocab;
   // the family the calling thread's last GEMM launch chose (GemmFamily; tests/test_gemm_layout_gpu.py)
   int (*gemm_family)();
+  // the records a compact batch's combine reads (tests/test_combine_kernel_gpu.py)
+  decltype(&launch_gather_row_hyper) gather_row_hyper;
+  decltype(&launch_gather_row_draw) gather_row_draw;
 };
 
 }  // namespace czc

@@ -28,6 +28,7 @@ PREC_REFINE = 5
 CLIP_MAX_LEN = 77
 MAX_BERT_LEN = 64   # include/conzic_hip.h CZC_MAX_BERT_LEN: tokens of a BERT row, [CLS] and [SEP] included
 MAX_VOCAB_SETS = 4096  # include/conzic_hip.h CZC_MAX_VOCAB_SETS: vocabulary sets of a call (czc_generate_rows_vocab)
+MAX_TOPK = 1024   # include/conzic_hip.h CZC_MAX_TOPK: the largest K of a step, a generation call or czc_similarity
 MAX_RIVALS = 16    # include/conzic_hip.h CZC_MAX_RIVALS: rival images of a row (czc_generate_rows_vs)
 MAX_REGIONS = 1024  # include/conzic_hip.h CZC_MAX_REGIONS: boxes of a czc_preprocess_regions_u8 call
 INDEX_MAX_K = 64 # include/conzic_hip.h CZC_INDEX_MAX_K: the largest k of czc_index_search
@@ -193,6 +194,8 @@ TEST_SIGNATURES = {
     "czc_test_combine_refine": (_I, [_I, _I, C.c_float, _P, _P, C.POINTER(Hyper), _P, _P, C.c_float, _P, _P, _P, _P, _P, _P]),
     "czc_test_combine_rivals": (_I, [_I, _I, _I, _P, _P, _I, _P, _P, _I, _P, C.c_float, _P, C.POINTER(Hyper), C.POINTER(Draw),
                                      C.c_uint32, _P, _P, _P, _P, _P]),
+    "czc_test_combine_rows": (_I, [_I, _I, _I, _I, _P, _P, _P, C.c_float, _P, _P, _P, _P, _I, C.POINTER(Hyper), C.POINTER(Draw),
+                                   C.c_uint32, _I, _P, _P, _I] + [_P] * 11),
     "czc_test_layernorm_rows": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, C.c_float, _I, _P, _P]),
     "czc_test_layernorm_x16_rows": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, C.c_float, _P]),
     "czc_test_layernorm_splitk": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, C.c_float, _P, _P]),

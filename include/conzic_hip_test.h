@@ -176,6 +176,29 @@ int czc_test_combine_rivals(int B, int K, int D, const float* text_feat, const f
                             const int32_t* rival_idx, int M, const float* delta, float logit_scale, const float* probs,
                             const czc_hyper* hp, const czc_draw* draw, uint32_t step, float* clip_ref, float* disc, float* final_score,
                             int32_t* best, int32_t* nonfinite);
+/* launch_combine in every instantiation without rivals, on B rows of K candidates (tests/combine_ref.py states the operation):
+ *   form 0 the scalar form (write-back column gen_idx), 1 per-row columns (gen_rows [B]), 2 per-row columns and hyper-parameters
+ *   (hp [B]), 3 those and the draw (draw [B], draw_step as in czc_test_combine_draw).  Forms 0 and 1 read ONE record of hp; draw is
+ *   NULL unless form 3; gen_rows NULL (forms 1-3, inp NULL) = zeros.
+ *   Cosines: text_feat [B*K, D] and img_embeds [B, D] (L2-normalised on the device), cos_in NULL -- or text_feat NULL and cos_in
+ *   [B*K], which is placed in clip_ref before the launch (the form the refine engine's second combine uses).
+ *   probs [B*K], cand [B*K] (the ids written back), senti_raw / repeats [B*K] or NULL.
+ *   inp_in [B*T] or NULL = nothing is written back; inp_out [B*T] receives the rows after the launch (both or neither).
+ *   run [B] or NULL (forms 2, 3): hp / draw hold R full records, the B rows' records are gathered on the device by
+ *   launch_gather_row_hyper / launch_gather_row_draw (record of row i = record run[i]) and come back as stored in hp_out [B*6 words]
+ *   / draw_out [B*4 words].
+ * Outputs (guarded as above): clip_score, clip_ref, final_score [B*K]; best, best_cos [B]; nonfinite [8] (zeroed first); inp_out.
+ * scale_out (one plain float, or NULL): expf(logit_scale) as the kernel is handed it.
+ * Checked here first (CZC_ERR_ARG): every write-back column in [0, T), every run entry in [0, R), a control-1 row has senti_raw
+ * and repeats, a control-2 row has senti_raw.  K beyond the launcher's limit: CZC_TEST_REFUSED -- launch_combine launched neither
+ * the cosine kernel nor the combine kernel (the hook's own preparation, launch_l2_normalize and the record gathers into its scratch,
+ * has run) and every output is the untouched pattern (clip_ref: cos_in where that was given, inp_out: inp_in). */
+int czc_test_combine_rows(int B, int K, int D, int T, const float* text_feat, const float* img_embeds, const float* cos_in,
+                          float logit_scale, const float* probs, const int32_t* cand, const float* senti_raw, const float* repeats,
+                          int form, const czc_hyper* hp, const czc_draw* draw, uint32_t draw_step, int gen_idx, const int32_t* gen_rows,
+                          const int32_t* run, int R, const int32_t* inp_in, int32_t* inp_out, float* clip_score, float* clip_ref,
+                          float* final_score, int32_t* best, float* best_cos, int32_t* nonfinite, int32_t* hp_out, int32_t* draw_out,
+                          float* scale_out);
 
 /* ---- the row, embedding, mover and memo kernels one by one (csrc/rowops.hip, ragged.hip, memo.hip, memo_rows.hip; numpy models in
  * tests/rowops_ref.py and tests/memo_ref.py).  EVERY OUTPUT ARRAY holds CZC_TEST_GUARD + n + CZC_TEST_GUARD 4-byte words as above and

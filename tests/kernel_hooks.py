@@ -9,7 +9,9 @@ Families with a kernel-level test of their own: GEMM / LayerNorm / attention / t
 shared-prefix attention plans, the per-sequence attention launches (attention_seq: tests/test_attention_seq_gpu.py), the
 selection and plan kernels, the row / embedding / mover / memo kernels, the fluency kernels, the
 text bridge with candidates in its three forms (tests/test_bridge_kernel_gpu.py against the string reference tests/bridge_ref.py,
-pinned by tests/test_bridge_ref_cpu.py), the per-row forms of the top-K selection (tests/test_topk_rows_gpu.py), and -- at the end
+pinned by tests/test_bridge_ref_cpu.py), the per-row forms of the top-K selection (tests/test_topk_rows_gpu.py), the combine kernel in
+its scalar, per-row and drawing forms (tests/combine_hooks.py: tests/test_combine_kernel_gpu.py against the fp64 reference and the
+derived bars of tests/combine_ref.py, pinned by tests/test_combine_ref_cpu.py), and -- at the end
 of this file -- every GEMM family on strided, windowed and in-place buffers (gemm_layout: tests/test_gemm_layout_gpu.py, with the
 cases, the fp64 reference and the checker in tests/gemm_layout.py, pinned by tests/test_gemm_layout_cpu.py).
 

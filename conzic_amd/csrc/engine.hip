@@ -139,8 +139,7 @@ struct czc_engine {
   std::vector<void*> bridge_allocs;
   float* d_img_n = nullptr; int img_B = 0;  // the resident image batch, L2-normalised [img_B, proj]: written only where it is set, encoded or freed
   float logit_scale_exp = 1.f;
-  double plan_pairs = 0;    // causal (query, key) pairs of the text-tower plan about to run (totals[7]): attention FLOPs = 4 * H * pairs per layer
-  int* h_totals = nullptr;  // pinned, 64 ints: [8],[9] non-finite flags, [16..27] refine-plan totals, [32..35] memo check, [48..59] plan totals (HT_PLAN)
+  int* h_totals = nullptr;  // pinned, 64 ints: the blocks of the HT_* layout below
   int last_BT = 0, last_B = 0, last_T = 0;  // shape of the forward whose rows b_x / b_xg hold (n_mask = 0 re-use needs the same B AND T)
   int bert_prune = 1;       // last BERT layer behind the attention on the one row per sequence the MLM head reads (n_mask == 1 steps)
   int bert_pruned_idx = -1; // row the previous forward kept (-1: all rows of b_x are valid)
@@ -329,14 +328,18 @@ int build_layers(czc_engine* e, std::vector<LayerW>& L, int n_layers, int H, int
   return 0;
 }
 
+int gemm_ex(czc_engine* e, int prec, const char* kind, const GemmArgs& g) {
+  ProfScope ps(e, kind, 2.0 * g.M * (double)g.N * g.K);
+  E_CHECK(launch_gemm(prec, g, e->st));
+  return 0;
+}
+
 int gemm(czc_engine* e, int prec, const char* kind, const void* A, int lda, const void* W, int ldw, const float* bias,
          const float* resid, int ldr, void* out_act, float* out_f32, int ldc, int M, int N, int K, int act) {
   GemmArgs g;
   g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.resid = resid; g.ldr = ldr;
   g.out_act = out_act; g.out_f32 = out_f32; g.ldc = ldc; g.M = M; g.N = N; g.K = K; g.act = act;
-  ProfScope ps(e, kind, 2.0 * M * (double)N * K);
-  E_CHECK(launch_gemm(prec, g, e->st));
-  return 0;
+  return gemm_ex(e, prec, kind, g);
 }
 
 // x <- fp16(x + A.W^T + b) on a 2-byte residual stream (GemmArgs::x16): x16 [M,N] fp16 rows, updated in place
@@ -347,32 +350,63 @@ int gemm_x16(czc_engine* e, int prec, const char* kind, const void* A, int lda, 
   g.A = A; g.lda = lda; g.W = W; g.ldw = K; g.bias = bias; g.resid = (const float*)x16; g.ldr = N;
   g.out_act = nullptr; g.out_f32 = (float*)x16; g.ldc = N; g.M = M; g.N = N; g.K = K; g.act = ACT_NONE; g.x16 = 1;
   g.row_part = part; g.part_ld = part_ld;
-  ProfScope ps(e, kind, 2.0 * M * (double)N * K);
-  E_CHECK(launch_gemm(prec, g, e->st));
-  return 0;
+  return gemm_ex(e, prec, kind, g);
 }
 
-int gemm_ex(czc_engine* e, int prec, const char* kind, const GemmArgs& g) {
-  ProfScope ps(e, kind, 2.0 * g.M * (double)g.N * g.K);
-  E_CHECK(launch_gemm(prec, g, e->st));
-  return 0;
+// ---- layout of the pinned czc_engine::h_totals (64 ints) and of the device blocks that are copied into it ----
+// HT_FLAG_PLAN: s_nonfinite[0] as read with a plan's totals (the previous steps' cosine check); HT_FLAGS: s_nonfinite as read at the end
+// of a call (NF_*); HT_REFINE: the refine plan's totals (PT_*, RT_*); HT_MEMO: the step memo's check (MC_*); HT_PLAN: clip_plan's totals (PT_*)
+enum : int { HT_FLAG_PLAN = 8, HT_FLAGS = 9, HT_REFINE = 16, HT_MEMO = 32, HT_PLAN = 48 };
+// s_nonfinite: the cosine check, the refine guard's largest deviation (float bits) and trips, the margin gate's counts; NF_READ ints are read
+enum : int { NF_NONFINITE = 0, NF_GUARD_DEV = 1, NF_GUARD_TRIPS = 2, NF_GATED = 4, NF_GATE_IMAGES = 5, NF_READ = 6 };
+// a plan's device totals: rows, longest segment, text-bridge overflow, longest sequence, longest branch, de-duplicated candidates,
+// trunk rows, causal (query, key) pairs, distinct branch rows of layer 0.  The refine plan has [0] [3] [4] [7] of them and RT_R =
+// candidates to re-encode, RT_KR = the largest count of one image
+enum : int { PT_ROWS = 0, PT_MAX_SEG = 1, PT_OVERFLOW = 2, PT_MAX_LEN = 3, PT_MAX_BRANCH = 4, PT_DUP = 5, PT_TRUNK = 6, PT_PAIRS = 7,
+             PT_DIST = 8, RT_R = 8, RT_KR = 9 };
+constexpr int PLAN_TOTALS = 48;  // bytes of a plan's device totals
+enum : int { MC_ACTIVE = 0, MC_BRANCH0 = 1, MC_BRANCH1 = 2 };  // memo check: active images, longest branch of the HIT images at sub-step 0 / 1
+
+// a plan's segment table and pooling indices on the device; rep: de-duplication table (null: none); dcount: layer 0's distinct rows per image (null: not counted)
+struct PlanBufs { int *own_len, *pre_len, *src, *pos0, *own_off, *pre_off, *eidx, *img_max, *rep, *dcount; };
+
+// Everything the text tower reads about a planned pass once its sizes have been read back: made by read_totals from clip_plan's
+// totals and by the refine pass of step_phase_b from its own; the vision tower's stack runs on an empty one.
+struct TowerPlan {
+  PlanBufs buf{};
+  int n_seg = 0, n_pool = 0, M = 0, max_len = 0, max_branch = 0;  // segments, sequences pooled at buf.eidx, packed rows, longest sequence / branch
+  int B = 0, K = 0;          // regular B x K plan (B trunk segments, then B * K branches); 0: none
+  int n_l0 = 0;              // layer 0 on distinct rows: trunk + distinct branch rows (0: not counted)
+  int n_dup = 0;             // candidates that ride on an identical one's rows (the table: buf.rep)
+  double pairs = 0;          // causal (query, key) pairs: attention FLOPs = 4 * H * pairs per layer
+};
+
+// a regular plan's branches go to the packed-branch attention kernels; a half-precision tower's to the per-image kernel where it
+// serves the plan: the kernel whose mapped mode layer 0 and whose pooled mode the last layer may use
+bool packed_branches(const czc_engine* e, const TowerPlan& tp) { return tp.B > 0 && g_use_mfma_attention && e->pack_branches; }
+bool per_image_attention(const czc_engine* e, int P, const TowerPlan& tp) {
+  return prec_is_half(P) && packed_branches(e, tp) && attention_image_serves(tp.B, tp.K, tp.max_branch, tp.max_len, e->cfg.clip_heads);
 }
 
 // ---- pre-LN transformer stack shared by the CLIP text and vision towers -----------------------
-// x_f32 [M,H] residual stream (updated in place); packed sequences described by off/len or fixed_T
-// `pool_idx` (optional): only these n_pool rows are needed after the stack (EOS rows of the CLIP text
-// tower).  The last layer then runs its out-projection and MLP on those rows only (K/V of every row
-// are still produced); the pooled residual rows are returned in *pooled (fp32 [n_pool, H]).
-// P = precision of the layer weights in L (the engine's CLIP precision, or PREC_F16X3 for the refine pass).
-// r16: x (and *pooled) are fp16 rows of a 2-byte residual stream (czc_engine::resid16; H = 512, half-precision P).
 // layer 0 of the text tower on its distinct rows (kernels.h launch_layer0_map): n > 0 rows, dist [n] their packed rows, rowmap [M]
 struct Layer0Rows { const int* rowmap = nullptr; const int* dist = nullptr; int n = 0; };
+// P: precision of the layer weights L (an engine's CLIP precision, or PREC_F16X3 for the refine pass); gk: profile kind of the GEMMs.
+// The residual stream x [M, H] is updated in place; tab describes its packed sequences (off / len, or fixed_T).
+// Text tower only -- tp: its plan.  pool_idx: only these n_pool rows are needed after the stack (the EOS rows): the last layer runs
+// its out-projection and MLP on them alone (K/V of every row are still produced) and returns the pooled residual rows in *pooled
+// [n_pool, H].  r16: x (and *pooled) are fp16 rows of a 2-byte residual stream (czc_engine::resid16; H = 512, half-precision P).
+// ln_stat0: (mean, rstd) of the incoming rows (embedding kernel): enables the LayerNorm fold.
+struct StackDesc {
+  int P; std::vector<LayerW>* L; const char* gk; int M, H, I, heads; float eps;
+  SegTable tab; int max_keys, causal;
+  TowerPlan tp; const int* pool_idx = nullptr; int n_pool = 0; bool r16 = false; const float* ln_stat0 = nullptr; Layer0Rows l0;
+};
 
-int clip_stack(czc_engine* e, int P, const char* gk, std::vector<LayerW>& L, float* x, int M, int H, int I, int heads,
-               float eps, const SegTable& tab, int max_keys, int causal, int plan_B = 0, int plan_K = 0,
-               int plan_max_own = 0, const int* pool_idx = nullptr, int n_pool = 0, float** pooled = nullptr, bool r16 = false,
-               const float* ln_stat0 = nullptr, const Layer0Rows& l0 = Layer0Rows(), const int* pool_rep = nullptr) {  // pool_rep: the plan's de-duplication table (null: none)  // ln_stat0: (mean, rstd) of the incoming rows (embedding kernel): enables the LayerNorm fold
-  const size_t esz = prec_bytes(P);
+int clip_stack(czc_engine* e, const StackDesc& d, float* x, float** pooled = nullptr) {
+  const int P = d.P, M = d.M, H = d.H, I = d.I, heads = d.heads, max_keys = d.max_keys, n_pool = d.n_pool;
+  const float eps = d.eps; const bool r16 = d.r16; const char* gk = d.gk; const size_t esz = prec_bytes(P);
+  const SegTable& tab = d.tab; const TowerPlan& tp = d.tp; const Layer0Rows& l0 = d.l0; std::vector<LayerW>& L = *d.L;
   void *y, *qkv, *ctx, *hbuf;
   E_CHECK(ensure(e, "cs_y", (size_t)M * H * esz, &y));
   E_CHECK(ensure(e, "cs_qkv", (size_t)M * 3 * H * esz, &qkv));
@@ -382,96 +416,83 @@ int clip_stack(czc_engine* e, int P, const char* gk, std::vector<LayerW>& L, flo
   // the text tower's attention / row kernels are timed under their own classes (bench.py: MFMA utilisation of the whole
   // CLIP-text K-candidate batch, not only of its linear layers)
   const bool text = !strcmp(gk, "gemm_clip_text") || !strcmp(gk, "gemm_clip_refine");
-  const char* ak = text ? "attention_clip_text" : "attention";
-  const char* rk = text ? "rowops_clip_text" : "rowops";
-  const double attn_flops = text ? 4.0 * H * e->plan_pairs : 0.0;
+  const char *ak = text ? "attention_clip_text" : "attention", *rk = text ? "rowops_clip_text" : "rowops";
+  const double attn_flops = 4.0 * H * tp.pairs;  // (the vision tower has no plan: 0)
   // LayerNorm fused into the producer: out-proj (fuse_ln >= 1) and fc2 (fuse_ln >= 2) run on full 512-wide rows and
   // leave y = LN(x) beside the new fp32 x; the LayerNorm kernel then only runs where no such producer exists.
   const bool rowln = !r16 && prec_is_half(P) && e->fuse_ln && H == 512 && M >= g_rowln_min_m && I % 32 == 0;
   // LayerNorm folded into the q/k/v and fc1 GEMMs: they multiply x itself and correct with the row statistics `stat`, which
   // come from the producer's partials `part` (out-projection -> LN2, fc2 -> the next layer's LN1, the embedding kernel -> layer 0)
-  const bool fold = r16 && e->fold_ln && !L.empty() && L[0].qkv_wf && ln_stat0;
+  const bool fold = r16 && e->fold_ln && !L.empty() && L[0].qkv_wf && d.ln_stat0;
   float *part = nullptr, *stat = nullptr;
-  if (fold) {
-    E_CHECK(ensure(e, "cs_part", (size_t)(H / 32) * M * 8, (void**)&part));
-    E_CHECK(ensure(e, "cs_stat", (size_t)M * 8 + 256, (void**)&stat));
-  }
+  if (fold) E_CHECK(ensure(e, "cs_part", (size_t)(H / 32) * M * 8, (void**)&part));
+  if (fold) E_CHECK(ensure(e, "cs_stat", (size_t)M * 8 + 256, (void**)&stat));
   // the statistics of `rows` rows for a folded consumer with N columns: stat <- (mean, rstd) from part -- unless the consumer is
-  // small enough to form them itself (gemm_wreg_stats_in_kernel: one or two images), which saves this launch
-  auto finalize = [&](int rows, int N) -> int {
-    if (gemm_wreg_stats_in_kernel(rows, N)) return 0;
+  // small enough to form them itself (gemm_wreg_stats_in_kernel: one or two images), which saves this launch.  always: launch it
+  // even then, for a reader of `stat` other than that consumer
+  auto finalize = [&](int rows, int N, bool always = false) -> int {
+    if (!always && gemm_wreg_stats_in_kernel(rows, N)) return 0;
     ProfScope ps(e, rk, 0);
-    E_CHECK(launch_ln_finalize(part, M, H / 32, rows, eps, stat, e->st));
-    return 0;
+    return launch_ln_finalize(part, M, H / 32, rows, eps, stat, e->st);
   };
   // st_: the rows' statistics; nullptr = what finalize(rows, N) left (in `stat`, or still in `part` for the consumer to sum)
-  auto folded_gemm = [&](const void* Ax, const void* Wf, const float* bf, const float* st_, void* out, int rows, int N,
-                         int act, int ldc = 0) -> int {
+  auto folded_gemm = [&](const void* Ax, const void* Wf, const float* bf, const float* st_, void* out, int rows, int N, int act, int ldc = 0) -> int {
     GemmArgs g;
     g.A = Ax; g.lda = H; g.W = Wf; g.ldw = H; g.bias = bf; g.resid = nullptr; g.ldr = 0; g.out_act = out; g.out_f32 = nullptr; g.ldc = ldc ? ldc : N;
     g.M = rows; g.N = N; g.K = H; g.act = act;
     g.ln_stat = st_ ? st_ : stat;
     if (!st_ && gemm_wreg_stats_in_kernel(rows, N)) { g.ln_part = part; g.ln_part_ld = M; g.ln_eps = eps; }
-    ProfScope ps(e, gk, 2.0 * rows * (double)N * H);
-    E_CHECK(launch_gemm(P, g, e->st));
-    return 0;
+    return gemm_ex(e, P, gk, g);
   };
   auto ln = [&](const float* gm, const float* bt, int rows, const void* src, void* dst) -> int {  // dst <- LN(src rows)
     ProfScope ps(e, rk, 0);
-    if (r16) E_CHECK(launch_layernorm_x16(P, src, nullptr, gm, bt, eps, rows, H, dst, e->st));
-    else E_CHECK(launch_layernorm(P, (const float*)src, nullptr, gm, bt, eps, rows, H, dst, nullptr, e->st));
-    return 0;
+    if (r16) return launch_layernorm_x16(P, src, nullptr, gm, bt, eps, rows, H, dst, e->st);
+    return launch_layernorm(P, (const float*)src, nullptr, gm, bt, eps, rows, H, dst, nullptr, e->st);
   };
-  auto resid_gemm = [&](const void* A, int lda, const void* W, const float* b, int K) -> int {  // x += A.W^T + b
-    if (r16) return gemm_x16(e, P, gk, A, lda, W, b, x, M, H, K);
-    return gemm(e, P, gk, A, lda, W, K, b, x, H, nullptr, x, H, M, H, K, ACT_NONE);
+  auto resid_gemm = [&](const void* A, const void* W, const float* b, int K, float* xr, int rows) -> int {  // xr += A.W^T + b
+    if (r16) return gemm_x16(e, P, gk, A, K, W, b, xr, rows, H, K);
+    return gemm(e, P, gk, A, K, W, K, b, xr, H, nullptr, xr, H, rows, H, K, ACT_NONE);
   };
-  auto resid_ln_gemm = [&](const void* A, int lda, const void* W, const float* b, int K, const float* gm,
-                           const float* bt) -> int {  // x += A.W^T + b; y = LN(x; gm, bt)
+  auto resid_ln_gemm = [&](const void* A, const void* W, const float* b, int K, const float* gm, const float* bt) -> int {  // x += A.W^T + b; y = LN(x; gm, bt)
     GemmArgs g;
-    g.A = A; g.lda = lda; g.W = W; g.ldw = K; g.bias = b; g.resid = x; g.ldr = H; g.out_act = y; g.out_f32 = x;
+    g.A = A; g.lda = K; g.W = W; g.ldw = K; g.bias = b; g.resid = x; g.ldr = H; g.out_act = y; g.out_f32 = x;
     g.ldc = H; g.M = M; g.N = H; g.K = K; g.act = ACT_NONE; g.f16 = P == PREC_F16;
     g.ln_gamma = gm; g.ln_beta = bt; g.ln_eps = eps;
     ProfScope ps(e, gk, 2.0 * M * (double)H * K);
-    E_CHECK(launch_gemm_rowln(g, e->st));
-    return 0;
+    return launch_gemm_rowln(g, e->st);
   };
-  // Last layer, pooled rows only (pool_last_layer), on the folded path under the per-image attention kernel: k / v of all rows,
-  // but q and the attention context only of the pooled rows (every candidate's last own row) -- the q/k/v GEMM as a k/v launch
-  // on M rows and a q launch on the n_pool gathered rows, the branch attention in its pooled mode, no trunk attention.  Exact:
-  // a row of these GEMMs does not depend on the row count or the column split, a query column of the attention tile only on
-  // its own q and the K/V tiles.
-  const bool pool_qkv = pool_idx && e->pool_last_layer && e->pool_last_qkv && fold && plan_B > 0 && n_pool == plan_B * plan_K &&
-                        prec_is_half(P) && g_use_mfma_attention && e->pack_branches &&
-                        attention_image_serves(plan_B, plan_K, plan_max_own, max_keys, heads);
-  bool have_y = false;  // y already holds this layer's LN1 output (left by the previous layer's fc2)
+  bool have_y = false;  // y already holds the next layer's LN1 output (left by this layer's fc2)
+  // What follows a layer's attention, on `rows` rows (all M of x, or the pooled ones): xr += cx.Wo^T + b; xr += fc2(quick_gelu(fc1(LN2(xr))))
+  // through yb / hb.  next: the layer that follows on these rows (null: none); it finds the partials of the new rows (folded path) or y (fuse_ln >= 2)
+  // whole: the rows are the stream x itself (rows = M, yb = y), whose partials are M apart and which alone has the full-row kernels
+  auto tail = [&](LayerW& l, bool whole, int rows, const void* cx, float* xr, void* yb, void* hb, const LayerW* next) -> int {
+    if (fold) {
+      E_CHECK(gemm_x16(e, P, gk, cx, H, l.o_w, l.o_b, xr, rows, H, H, part, M));
+      E_CHECK(finalize(rows, I));
+      E_CHECK(folded_gemm(xr, l.fc1_wf, l.fc1_bf, nullptr, hb, rows, I, ACT_QUICK_GELU));
+      return gemm_x16(e, P, gk, hb, I, l.fc2_w, l.fc2_b, xr, rows, H, I, next ? part : nullptr, whole ? M : 0);
+    }
+    if (rowln && whole) E_CHECK(resid_ln_gemm(cx, l.o_w, l.o_b, H, l.ln2_g, l.ln2_b));  // (the full-row kernel is the whole stream's)
+    else {
+      E_CHECK(resid_gemm(cx, l.o_w, l.o_b, H, xr, rows));
+      E_CHECK(ln(l.ln2_g, l.ln2_b, rows, xr, yb));
+    }
+    E_CHECK(gemm(e, P, gk, yb, H, l.fc1_w, H, l.fc1_b, nullptr, 0, hb, nullptr, I, rows, I, H, ACT_QUICK_GELU));
+    have_y = rowln && whole && e->fuse_ln >= 2 && next;
+    if (have_y) return resid_ln_gemm(hb, l.fc2_w, l.fc2_b, I, next->ln1_g, next->ln1_b);
+    return resid_gemm(hb, l.fc2_w, l.fc2_b, I, xr, rows);
+  };
+  // Last layer, pooled rows only (pool_last_layer): out-projection and MLP on the n_pool gathered rows.  pool_qkv, on the folded path
+  // under the per-image attention kernel: k / v of all rows, but q and the attention context too only of the pooled rows (every candidate's
+  // last own row) -- the q/k/v GEMM as a k/v launch on M rows and a q launch on the gathered rows, the branch attention in its pooled mode,
+  // no trunk attention.  Exact: a row of these GEMMs does not depend on the row count or the column split, a query column of the
+  // attention tile only on its own q and the K/V tiles.
+  const bool pool_last = d.pool_idx && e->pool_last_layer;
+  const bool pool_qkv = pool_last && e->pool_last_qkv && fold && n_pool == tp.B * tp.K && per_image_attention(e, P, tp);
   for (size_t n = 0; n < L.size(); ++n) {
     LayerW& l = L[n];
-    if (pool_qkv && n + 1 == L.size()) {
-      void *ctx_e, *q_e, *h_e; float *x_e, *stat_e;
-      E_CHECK(ensure(e, "cs_ctx_e", (size_t)n_pool * H * esz, &ctx_e));
-      E_CHECK(ensure(e, "cs_q_e", (size_t)n_pool * H * esz, &q_e));
-      E_CHECK(ensure(e, "cs_h_e", (size_t)n_pool * I * esz, &h_e));
-      E_CHECK(ensure(e, "cs_x_e", (size_t)n_pool * H * 4, (void**)&x_e));
-      E_CHECK(ensure(e, "cs_stat_e", (size_t)n_pool * 8 + 256, (void**)&stat_e));
-      const float* st_all = n == 0 ? ln_stat0 : stat;  // layer n - 1 left them finalized (below)
-      { ProfScope ps(e, rk, 0);
-        E_CHECK(launch_gather_rows_bytes(x, pool_idx, n_pool, H * 2, x_e, e->st));
-        E_CHECK(launch_gather_rows_w32(st_all, pool_idx, n_pool, 2, stat_e, e->st)); }
-      E_CHECK(folded_gemm(x, (const char*)l.qkv_wf + (size_t)H * H * 2, l.qkv_bf + H, st_all, (char*)qkv + (size_t)H * esz, M, 2 * H,
-                          ACT_NONE, 3 * H));
-      E_CHECK(folded_gemm(x_e, l.qkv_wf, l.qkv_bf, stat_e, q_e, n_pool, H, ACT_NONE));
-      { ProfScope ps(e, ak, attn_flops);
-        E_CHECK(launch_attention_image_pooled(qkv, q_e, tab, pool_rep, plan_B, plan_K, plan_max_own, max_keys, heads, scale, ctx_e,
-                                              e->st, P == PREC_F16)); }
-      E_CHECK(gemm_x16(e, P, gk, ctx_e, H, l.o_w, l.o_b, x_e, n_pool, H, H, part, M));
-      E_CHECK(finalize(n_pool, I));
-      E_CHECK(folded_gemm(x_e, l.fc1_wf, l.fc1_bf, nullptr, h_e, n_pool, I, ACT_QUICK_GELU));
-      E_CHECK(gemm_x16(e, P, gk, h_e, I, l.fc2_w, l.fc2_b, x_e, n_pool, H, I));
-      *pooled = x_e;
-      return 0;
-    }
-    const bool l0_rows = fold && n == 0 && l0.n > 0;
+    const bool last = n + 1 == L.size(), l0_rows = fold && n == 0 && l0.n > 0;
+    const bool own_front = pool_qkv && last;  // q/k/v and the attention are the pooled layer's own (below)
     if (l0_rows) {
       // a packed row's input here is token_embedding[id] + position_embedding[pos]: q/k/v of every distinct row once, into the
       // first l0.n rows of qkv; the branch attention fetches row r at rowmap[r].  x stays packed (it is the residual).
@@ -480,71 +501,58 @@ int clip_stack(czc_engine* e, int P, const char* gk, std::vector<LayerW>& L, flo
       E_CHECK(ensure(e, "cs_sg", (size_t)l0.n * 8 + 256, (void**)&sg));
       { ProfScope ps(e, rk, 0);
         E_CHECK(launch_gather_rows_bytes(x, l0.dist, l0.n, H * 2, xg, e->st));
-        E_CHECK(launch_gather_rows_w32(ln_stat0, l0.dist, l0.n, 2, sg, e->st)); }
+        E_CHECK(launch_gather_rows_w32(d.ln_stat0, l0.dist, l0.n, 2, sg, e->st)); }
       E_CHECK(folded_gemm(xg, l.qkv_wf, l.qkv_bf, sg, qkv, l0.n, 3 * H, ACT_NONE));
-    } else if (fold) {
-      E_CHECK(folded_gemm(x, l.qkv_wf, l.qkv_bf, n == 0 ? ln_stat0 : nullptr, qkv, M, 3 * H, ACT_NONE));
-    } else {
+    } else if (fold && !own_front) {
+      E_CHECK(folded_gemm(x, l.qkv_wf, l.qkv_bf, n == 0 ? d.ln_stat0 : nullptr, qkv, M, 3 * H, ACT_NONE));
+    } else if (!fold) {
       if (!have_y) E_CHECK(ln(l.ln1_g, l.ln1_b, M, x, y));
       E_CHECK(gemm(e, P, gk, y, H, l.qkv_w, H, l.qkv_b, nullptr, 0, qkv, nullptr, 3 * H, M, 3 * H, H, ACT_NONE));
     }
-    { ProfScope ps(e, ak, attn_flops);
+    if (!own_front) {
+      ProfScope ps(e, ak, attn_flops);
       int rc = -1;
       if (l0_rows)
-        rc = launch_attention_shared_mapped(qkv, l0.n, l0.rowmap, tab, plan_B, plan_K, plan_max_own, max_keys, heads, scale, ctx, e->st,
-                                            P == PREC_F16);
-      else if (plan_B > 0 && prec_is_half(P) && g_use_mfma_attention && e->pack_branches)
-        rc = launch_attention_shared(qkv, tab, plan_B, plan_K, plan_max_own, max_keys, heads, scale, ctx, e->st, P == PREC_F16);
-      else if (plan_B > 0 && P == PREC_F16X3 && g_use_mfma_attention && e->pack_branches)
-        rc = launch_attention_shared_split(qkv, tab, plan_B, plan_K, plan_max_own, max_keys, heads, scale, ctx, e->st);
+        rc = launch_attention_shared_mapped(qkv, l0.n, l0.rowmap, tab, tp.B, tp.K, tp.max_branch, max_keys, heads, scale, ctx, e->st, P == PREC_F16);
+      else if (prec_is_half(P) && packed_branches(e, tp))
+        rc = launch_attention_shared(qkv, tab, tp.B, tp.K, tp.max_branch, max_keys, heads, scale, ctx, e->st, P == PREC_F16);
+      else if (P == PREC_F16X3 && packed_branches(e, tp))
+        rc = launch_attention_shared_split(qkv, tab, tp.B, tp.K, tp.max_branch, max_keys, heads, scale, ctx, e->st);
       if (rc > 0) E_CHECK(rc);
-      if (rc < 0) E_CHECK(launch_attention(P, qkv, tab, max_keys, heads, causal, scale, ctx, e->st)); }
-    if (pool_idx && n + 1 == L.size() && e->pool_last_layer) {
-      void *ctx_e, *y_e, *h_e; float* x_e;
+      if (rc < 0) E_CHECK(launch_attention(P, qkv, tab, max_keys, heads, d.causal, scale, ctx, e->st));
+    }
+    if (pool_last && last) {
+      // the pooled rows' context, q (pool_qkv) or LN2 output, hidden and residual rows, and their gathered statistics (pool_qkv)
+      void *ctx_e, *qy_e, *h_e; float *x_e, *stat_e = nullptr;
       E_CHECK(ensure(e, "cs_ctx_e", (size_t)n_pool * H * esz, &ctx_e));
-      E_CHECK(ensure(e, "cs_y_e", (size_t)n_pool * H * esz, &y_e));
+      E_CHECK(ensure(e, pool_qkv ? "cs_q_e" : "cs_y_e", (size_t)n_pool * H * esz, &qy_e));
       E_CHECK(ensure(e, "cs_h_e", (size_t)n_pool * I * esz, &h_e));
       E_CHECK(ensure(e, "cs_x_e", (size_t)n_pool * H * 4, (void**)&x_e));
-      { ProfScope ps(e, rk, 0);
-        E_CHECK(launch_gather_rows_bytes(ctx, pool_idx, n_pool, H * (int)esz, ctx_e, e->st));
-        if (r16) E_CHECK(launch_gather_rows_bytes(x, pool_idx, n_pool, H * 2, x_e, e->st));
-        else E_CHECK(launch_gather_rows_f32(x, pool_idx, n_pool, H, x_e, e->st)); }
-      if (fold) {
-        E_CHECK(gemm_x16(e, P, gk, ctx_e, H, l.o_w, l.o_b, x_e, n_pool, H, H, part, M));
-        E_CHECK(finalize(n_pool, I));
-        E_CHECK(folded_gemm(x_e, l.fc1_wf, l.fc1_bf, nullptr, h_e, n_pool, I, ACT_QUICK_GELU));
+      if (pool_qkv) {
+        E_CHECK(ensure(e, "cs_stat_e", (size_t)n_pool * 8 + 256, (void**)&stat_e));
+        const float* st_all = n == 0 ? d.ln_stat0 : stat;  // layer n - 1 left them finalized (below)
+        { ProfScope ps(e, rk, 0);
+          E_CHECK(launch_gather_rows_bytes(x, d.pool_idx, n_pool, H * 2, x_e, e->st));
+          E_CHECK(launch_gather_rows_w32(st_all, d.pool_idx, n_pool, 2, stat_e, e->st)); }
+        E_CHECK(folded_gemm(x, (const char*)l.qkv_wf + (size_t)H * H * 2, l.qkv_bf + H, st_all, (char*)qkv + (size_t)H * esz, M, 2 * H,
+                            ACT_NONE, 3 * H));
+        E_CHECK(folded_gemm(x_e, l.qkv_wf, l.qkv_bf, stat_e, qy_e, n_pool, H, ACT_NONE));
+        ProfScope ps(e, ak, attn_flops);
+        E_CHECK(launch_attention_image_pooled(qkv, qy_e, tab, tp.buf.rep, tp.B, tp.K, tp.max_branch, max_keys, heads, scale, ctx_e, e->st,
+                                              P == PREC_F16));
       } else {
-        if (r16) E_CHECK(gemm_x16(e, P, gk, ctx_e, H, l.o_w, l.o_b, x_e, n_pool, H, H));
-        else E_CHECK(gemm(e, P, gk, ctx_e, H, l.o_w, H, l.o_b, x_e, H, nullptr, x_e, H, n_pool, H, H, ACT_NONE));
-        E_CHECK(ln(l.ln2_g, l.ln2_b, n_pool, x_e, y_e));
-        E_CHECK(gemm(e, P, gk, y_e, H, l.fc1_w, H, l.fc1_b, nullptr, 0, h_e, nullptr, I, n_pool, I, H, ACT_QUICK_GELU));
+        ProfScope ps(e, rk, 0);
+        E_CHECK(launch_gather_rows_bytes(ctx, d.pool_idx, n_pool, H * (int)esz, ctx_e, e->st));
+        if (r16) E_CHECK(launch_gather_rows_bytes(x, d.pool_idx, n_pool, H * 2, x_e, e->st));
+        else E_CHECK(launch_gather_rows_f32(x, d.pool_idx, n_pool, H, x_e, e->st));
       }
-      if (r16) E_CHECK(gemm_x16(e, P, gk, h_e, I, l.fc2_w, l.fc2_b, x_e, n_pool, H, I));
-      else E_CHECK(gemm(e, P, gk, h_e, I, l.fc2_w, I, l.fc2_b, x_e, H, nullptr, x_e, H, n_pool, H, I, ACT_NONE));
+      E_CHECK(tail(l, false, n_pool, ctx_e, x_e, qy_e, h_e, nullptr));
       *pooled = x_e;
       return 0;
     }
-    if (fold) {
-      E_CHECK(gemm_x16(e, P, gk, ctx, H, l.o_w, l.o_b, x, M, H, H, part, M));
-      E_CHECK(finalize(M, I));
-      E_CHECK(folded_gemm(x, l.fc1_wf, l.fc1_bf, nullptr, hbuf, M, I, ACT_QUICK_GELU));
-      const bool more = n + 1 < L.size();  // the last layer's rows only feed the final LayerNorm (on the pooled rows)
-      E_CHECK(gemm_x16(e, P, gk, hbuf, I, l.fc2_w, l.fc2_b, x, M, H, I, more ? part : nullptr, M));
-      if (more && pool_qkv && n + 2 == L.size()) {  // the pooled last layer gathers the statistics of its rows: always in `stat`
-        ProfScope ps(e, rk, 0);
-        E_CHECK(launch_ln_finalize(part, M, H / 32, M, eps, stat, e->st));
-      } else if (more) E_CHECK(finalize(M, 3 * H));
-      continue;
-    }
-    if (rowln) E_CHECK(resid_ln_gemm(ctx, H, l.o_w, l.o_b, H, l.ln2_g, l.ln2_b));
-    else {
-      E_CHECK(resid_gemm(ctx, H, l.o_w, l.o_b, H));
-      E_CHECK(ln(l.ln2_g, l.ln2_b, M, x, y));
-    }
-    E_CHECK(gemm(e, P, gk, y, H, l.fc1_w, H, l.fc1_b, nullptr, 0, hbuf, nullptr, I, M, I, H, ACT_QUICK_GELU));
-    have_y = rowln && e->fuse_ln >= 2 && n + 1 < L.size();
-    if (have_y) E_CHECK(resid_ln_gemm(hbuf, I, l.fc2_w, l.fc2_b, I, L[n + 1].ln1_g, L[n + 1].ln1_b));
-    else E_CHECK(resid_gemm(hbuf, I, l.fc2_w, l.fc2_b, I));
+    E_CHECK(tail(l, true, M, ctx, x, y, hbuf, last ? nullptr : &L[n + 1]));  // (the last layer's rows only feed the final LayerNorm)
+    // a pooled last layer (pool_qkv) gathers the statistics of its rows: always in `stat`, not left in `part` for a consumer to sum
+    if (fold && !last) E_CHECK(finalize(M, 3 * H, pool_qkv && n + 2 == L.size()));
   }
   return 0;
 }
@@ -682,11 +690,6 @@ int mlm_head(czc_engine* e, int B, int T, int gen_idx, float** logits_out, const
 // (trunk segment) and every candidate only carries the rows from its first differing token on.
 // Two halves around the step's single host round trip (32 bytes of totals: rows, longest sequence, overflow):
 // clip_plan builds the segment table on the device and starts the read, clip_tower runs on the sizes it returned.
-constexpr int HT_PLAN = 48;     // h_totals: where the plan's totals land
-constexpr int PLAN_TOTALS = 48; // bytes of a plan's device totals: [0] rows [1] longest segment [2] bridge overflow [3] longest sequence [4] longest
-                                // branch [5] de-duplicated candidates [6] trunk rows [7] attention pairs [8] distinct branch rows of layer 0
-struct PlanBufs { int *own_len, *pre_len, *src, *pos0, *own_off, *pre_off, *eidx, *img_max, *rep; };
-
 // the refine engine inside czc_generate (in_generate: StepMode): screening pass on fp16 rows (czc_engine::refine_rows16)
 static inline bool refine_rows16_now(const czc_engine* e, bool in_generate) {
   return e->refine && in_generate && e->refine_rows16 && e->cfg.clip_hidden == 512;
@@ -705,43 +708,46 @@ int plan_bufs(czc_engine* e, int B, int K, PlanBufs* p, const char* pfx = "p") {
   E_CHECK(ensure(e, (q + "_eidx").c_str(), (size_t)n_seq * 4, (void**)&p->eidx));
   E_CHECK(ensure(e, (q + "_img_max").c_str(), (size_t)B * 4, (void**)&p->img_max));
   E_CHECK(ensure(e, (q + "_rep").c_str(), (size_t)n_seq * 4, (void**)&p->rep));
+  p->dcount = nullptr;
   return 0;
 }
 
-int clip_plan(czc_engine* e, const int* cids, const int* clen, int B, int K, int share, int* totals) {
-  PlanBufs p;
+// *bufs: what the plan filled (rep / dcount: null without de-duplication / where layer 0's distinct rows were not counted)
+int clip_plan(czc_engine* e, const int* cids, const int* clen, int B, int K, int share, int* totals, PlanBufs* bufs) {
+  PlanBufs& p = *bufs;
   E_CHECK(plan_bufs(e, B, K, &p));
   const int S = B + B * K;
+  // de-duplication rides on the shared-prefix plan (K > 1 candidates per image; czc_encode_text's independent sequences have none)
+  if (!(e->dedup && share && K > 1)) p.rep = nullptr;
   { ProfScope ps(e, "bridge", 0);
-    // de-duplication rides on the shared-prefix plan (K > 1 candidates per image; czc_encode_text's independent sequences have none)
-    int* rep = e->dedup && share && K > 1 ? p.rep : nullptr;
-    E_CHECK(launch_prefix_plan(cids, clen, B, K, share, p.own_len, p.pre_len, p.src, p.pos0, totals + 3, p.img_max, e->st, rep, totals + 5));
+    E_CHECK(launch_prefix_plan(cids, clen, B, K, share, p.own_len, p.pre_len, p.src, p.pos0, totals + PT_MAX_LEN, p.img_max, e->st, p.rep,
+                               totals + PT_DUP));
     E_CHECK(launch_scan(p.own_len, S, p.own_off, totals, e->st));
-    E_CHECK(launch_prefix_finish(p.own_off, p.own_len, B, K, p.pre_off, p.eidx, totals + 6, e->st, rep));
+    E_CHECK(launch_prefix_finish(p.own_off, p.own_len, B, K, p.pre_off, p.eidx, totals + PT_TRUNK, e->st, p.rep));
     if (e->share_layer0 && share && K > 1 && K <= 1024 && e->fold_ln && e->pack_branches) {  // the tower decides on the sizes whether layer 0 uses it
-      int* dcount;
-      E_CHECK(ensure(e, "p_dcount", (size_t)B * 4, (void**)&dcount));
-      E_CHECK(launch_layer0_count(cids, p.own_len, p.pre_len, B, K, dcount, totals + 8, e->st));
+      E_CHECK(ensure(e, "p_dcount", (size_t)B * 4, (void**)&p.dcount));
+      E_CHECK(launch_layer0_count(cids, p.own_len, p.pre_len, B, K, p.dcount, totals + PT_DIST, e->st));
     } }
   E_HIP(hipMemcpyAsync(e->h_totals + HT_PLAN, totals, PLAN_TOTALS, hipMemcpyDeviceToHost, e->st));
   int* flag;
   E_CHECK(ensure(e, "s_nonfinite", 32, (void**)&flag));
-  E_HIP(hipMemcpyAsync(e->h_totals + 8, flag, 4, hipMemcpyDeviceToHost, e->st));  // the previous steps' cosine check
+  E_HIP(hipMemcpyAsync(e->h_totals + HT_FLAG_PLAN, flag, 4, hipMemcpyDeviceToHost, e->st));  // the previous steps' cosine check
   return 0;
 }
 
-// The text tower on a planned set of packed segments: n_seg segments (tab), M rows, n_pool sequences pooled at p.eidx.
-// P / L / tproj: the tower's precision and weights; plan_B > 0: regular B x K plan (packed-branch attention kernels).
+// a text tower: its precision and weights, the profile kind of its GEMMs, the workspace name of its features
+struct TextTower { int P; std::vector<LayerW>* L; const void* tproj; const char* gk; const char* feat_name; };
+
+// The text tower on a planned set of packed segments: tp.n_seg segments, tp.M rows, tp.n_pool sequences pooled at tp.buf.eidx.
 // in_generate: the pass belongs to a czc_generate* step (refine_rows16_now: the refine engine's screening pass on fp16 rows).
-int clip_tower_on(czc_engine* e, int P, std::vector<LayerW>& L, const void* tproj, const char* gk, const int* cids,
-                  const PlanBufs& p, int n_seg, int n_pool, int M, int max_len, int plan_B, int plan_K, int max_branch,
-                  const char* feat_name, float** feat_out, bool in_generate, int n_dist = 0, const int* rep = nullptr) {  // n_dist: distinct rows of layer 0 (clip_plan; 0: not counted); rep: its de-duplication table
+int clip_tower_on(czc_engine* e, const TextTower& w, const int* cids, const TowerPlan& tp, float** feat_out, bool in_generate) {
   const czc_config& c = e->cfg;
-  const int H = c.clip_hidden;
-  float *x, *feat, *tok, *pos, *fg, *fb; void* pa;
+  const PlanBufs& p = tp.buf;
+  const int H = c.clip_hidden, P = w.P, M = tp.M, n_pool = tp.n_pool;
+  float *x, *feat, *tok, *pos, *fg, *fb, *pooled = nullptr; void* pa;
   E_CHECK(ensure(e, "c_x", (size_t)M * H * 4, (void**)&x));
   E_CHECK(ensure(e, "c_pa", (size_t)n_pool * H * prec_bytes(P), &pa));
-  E_CHECK(ensure(e, feat_name, (size_t)n_pool * c.clip_proj * 4, (void**)&feat));
+  E_CHECK(ensure(e, w.feat_name, (size_t)n_pool * c.clip_proj * 4, (void**)&feat));
   E_CHECK(need(e, "text_model.embeddings.token_embedding.weight", (size_t)c.clip_vocab * H, &tok));
   E_CHECK(need(e, "text_model.embeddings.position_embedding.weight", (size_t)c.clip_max_pos * H, &pos));
   E_CHECK(need(e, "text_model.final_layer_norm.weight", H, &fg));
@@ -749,79 +755,73 @@ int clip_tower_on(czc_engine* e, int P, std::vector<LayerW>& L, const void* tpro
   const bool r16 = H == 512 && ((e->resid16 >= 1 && P == PREC_BF16) || (e->resid16 >= 2 && P == PREC_F16) ||
                                 (P == PREC_F16 && refine_rows16_now(e, in_generate)));
   float* stat0 = nullptr;
-  if (r16 && e->fold_ln && !L.empty() && L[0].qkv_wf) E_CHECK(ensure(e, "c_stat0", (size_t)M * 8 + 256, (void**)&stat0));
+  if (r16 && e->fold_ln && !w.L->empty() && (*w.L)[0].qkv_wf) E_CHECK(ensure(e, "c_stat0", (size_t)M * 8 + 256, (void**)&stat0));
   { ProfScope ps(e, "rowops_clip_text", 0);
-    E_CHECK(launch_clip_embed(cids, CZC_CLIP_MAX_LEN, p.src, p.pos0, p.own_off, p.own_len, n_seg, max_len, H, tok, pos, x, e->st, r16 ? 1 : 0,
-                              stat0, c.clip_eps)); }
-  SegTable tab{p.pre_off, p.pre_len, p.own_off, p.own_len, n_seg, 0, plan_B > 0 ? p.img_max : nullptr};
-  float* pooled = nullptr;
+    E_CHECK(launch_clip_embed(cids, CZC_CLIP_MAX_LEN, p.src, p.pos0, p.own_off, p.own_len, tp.n_seg, tp.max_len, H, tok, pos, x, e->st,
+                              r16 ? 1 : 0, stat0, c.clip_eps)); }
+  StackDesc d{P, w.L, w.gk, M, H, c.clip_inter, c.clip_heads, c.clip_eps,
+              SegTable{p.pre_off, p.pre_len, p.own_off, p.own_len, tp.n_seg, 0, tp.B > 0 ? p.img_max : nullptr}, tp.max_len, 1};
+  d.tp = tp; d.pool_idx = p.eidx; d.n_pool = n_pool; d.r16 = r16; d.ln_stat0 = stat0;
   // layer 0 on distinct rows: where the folded path runs under the per-image attention kernel, with 32-bit byte offsets into the
   // compact q/k/v buffer
-  Layer0Rows l0;
-  if (n_dist > 0 && n_dist <= M && e->share_layer0 && stat0 && L.size() > 1 && plan_B > 0 && prec_is_half(P) && g_use_mfma_attention &&
-      e->pack_branches && attention_image_serves(plan_B, plan_K, max_branch, max_len, c.clip_heads) &&
-      (long)n_dist * 3 * H * 2 < (1L << 31)) {
-    int *rowmap, *dist, *dcount;
+  if (tp.n_l0 > 0 && tp.n_l0 <= M && e->share_layer0 && stat0 && w.L->size() > 1 && per_image_attention(e, P, tp) &&
+      (long)tp.n_l0 * 3 * H * 2 < (1L << 31)) {
+    int *rowmap, *dist;
     E_CHECK(ensure(e, "c_l0map", (size_t)M * 4, (void**)&rowmap));
-    E_CHECK(ensure(e, "c_l0dist", (size_t)n_dist * 4, (void**)&dist));
-    E_CHECK(ensure(e, "p_dcount", (size_t)plan_B * 4, (void**)&dcount));  // left by clip_plan
+    E_CHECK(ensure(e, "c_l0dist", (size_t)tp.n_l0 * 4, (void**)&dist));
     { ProfScope ps(e, "bridge", 0);
-      E_CHECK(launch_layer0_map(cids, p.own_off, p.own_len, p.pre_len, dcount, plan_B, plan_K, rowmap, dist, e->st)); }
-    l0.rowmap = rowmap; l0.dist = dist; l0.n = n_dist;
+      E_CHECK(launch_layer0_map(cids, p.own_off, p.own_len, p.pre_len, p.dcount, tp.B, tp.K, rowmap, dist, e->st)); }
+    d.l0 = Layer0Rows{rowmap, dist, tp.n_l0};
   }
-  E_CHECK(clip_stack(e, P, gk, L, x, M, H, c.clip_inter, c.clip_heads, c.clip_eps, tab, max_len, 1, plan_B,
-                     plan_K, max_branch, p.eidx, n_pool, &pooled, r16, stat0, l0, rep));
+  E_CHECK(clip_stack(e, d, x, &pooled));
   { ProfScope ps(e, "rowops_clip_text", 0);
-    if (r16) {
-      if (pooled) E_CHECK(launch_layernorm_x16(P, pooled, nullptr, fg, fb, c.clip_eps, n_pool, H, pa, e->st));
-      else E_CHECK(launch_layernorm_x16(P, x, p.eidx, fg, fb, c.clip_eps, n_pool, H, pa, e->st));
-    } else if (pooled) E_CHECK(launch_layernorm(P, pooled, nullptr, fg, fb, c.clip_eps, n_pool, H, pa, nullptr, e->st));
-    else E_CHECK(launch_layernorm(P, x, p.eidx, fg, fb, c.clip_eps, n_pool, H, pa, nullptr, e->st)); }
-  E_CHECK(gemm(e, P, gk, pa, H, tproj, H, nullptr, nullptr, 0, nullptr, feat, c.clip_proj, n_pool, c.clip_proj, H, ACT_NONE));
+    const float* src = pooled ? pooled : x; const int* idx = pooled ? nullptr : p.eidx;
+    if (r16) E_CHECK(launch_layernorm_x16(P, src, idx, fg, fb, c.clip_eps, n_pool, H, pa, e->st));
+    else E_CHECK(launch_layernorm(P, src, idx, fg, fb, c.clip_eps, n_pool, H, pa, nullptr, e->st)); }
+  E_CHECK(gemm(e, P, w.gk, pa, H, w.tproj, H, nullptr, nullptr, 0, nullptr, feat, c.clip_proj, n_pool, c.clip_proj, H, ACT_NONE));
   *feat_out = feat;
   return 0;
 }
 
 // the engine's text tower on the regular B x K plan built by clip_plan; `exact`: the refine engine's split-fp16 weights
-int clip_tower(czc_engine* e, const int* cids, int B, int K, int share, int M, int max_len, int max_branch, int n_trunk, int n_dist,
-               float** feat_out, bool in_generate, bool exact = false) {  // n_dist: distinct branch rows of layer 0 the plan counted (0: it did not)
-  PlanBufs p;
-  E_CHECK(plan_bufs(e, B, K, &p));
+int clip_tower(czc_engine* e, const int* cids, const TowerPlan& tp, float** feat_out, bool in_generate, bool exact = false) {
   const bool x = exact && e->refine;
-  return clip_tower_on(e, x ? (int)PREC_F16X3 : e->pc, x ? e->ctext_x : e->ctext, x ? e->tproj_wx : e->tproj_w, "gemm_clip_text",
-                       cids, p, B + B * K, B * K, M, max_len, B, K, max_branch, "c_feat", feat_out, in_generate,
-                       n_dist > 0 ? n_trunk + n_dist : 0, e->dedup && share && K > 1 ? p.rep : nullptr);  // rep: as clip_plan filled it
+  return clip_tower_on(e, TextTower{x ? (int)PREC_F16X3 : e->pc, x ? &e->ctext_x : &e->ctext, x ? e->tproj_wx : e->tproj_w,
+                                    "gemm_clip_text", "c_feat"}, cids, tp, feat_out, in_generate);
 }
 
 constexpr const char* MSG_NONFINITE = "non-finite CLIP cosine: an fp16 quantity overflowed in a tower (fp16 residual rows: set option resid16 = 0 on the bf16 engine, refine_rows16 = 0 on the refine engine; fp16 operands: use CZC_PREC_SPLIT)%s";
 
-// sizes of the tower from the totals the plan read back (after the stream has been synchronised)
+// the regular B x K plan clip_plan left in `bufs`, from the totals it read back (after the stream has been synchronised)
 // branch_floor: a compact memo step's (StepArgs::branch_floor); 0 everywhere else
-int read_totals(czc_engine* e, int branch_floor, int* M, int* max_len, int* max_branch, int* n_trunk, int* n_dist) {
-  const czc_config& c = e->cfg;
+int read_totals(czc_engine* e, const PlanBufs& bufs, int B, int K, int branch_floor, TowerPlan* tp) {
   const int* t = e->h_totals + HT_PLAN;
-  *M = t[0]; *max_len = t[3]; *max_branch = t[4]; *n_trunk = t[6];
-  *n_dist = t[8];
+  *tp = TowerPlan{};
+  tp->buf = bufs; tp->n_seg = B + B * K; tp->n_pool = B * K; tp->B = B; tp->K = K;
+  tp->M = t[PT_ROWS]; tp->max_len = t[PT_MAX_LEN]; tp->max_branch = t[PT_MAX_BRANCH];
+  tp->n_l0 = t[PT_DIST] > 0 ? t[PT_TRUNK] + t[PT_DIST] : 0;
+  tp->n_dup = t[PT_DUP]; tp->pairs = (double)t[PT_PAIRS];
   // a compacted memo step: a branch longer than 32 rows among the images it skipped would have sent the full batch's launch
   // to the per-segment attention kernel, so it goes there too (round 3: the one batch coupling of the text tower)
-  if (branch_floor > 32 && *max_branch < branch_floor) *max_branch = branch_floor;
-  e->plan_pairs = (double)t[7];
-  if (e->h_totals[8]) return fail(e, CZC_ERR_OVERFLOW, MSG_NONFINITE);
-  if (t[2]) return fail(e, CZC_ERR_OVERFLOW, "text bridge overflow (row text > CZC_BRIDGE_MAX_BYTES)%s");
-  if (*max_len > c.clip_max_pos || *max_len > CZC_CLIP_MAX_LEN)
-    return fail(e, CZC_ERR_ARG, "CLIP sequence longer than max_position_embeddings%s");
+  if (branch_floor > 32 && tp->max_branch < branch_floor) tp->max_branch = branch_floor;
+  if (e->h_totals[HT_FLAG_PLAN]) return fail(e, CZC_ERR_OVERFLOW, MSG_NONFINITE);
+  if (t[PT_OVERFLOW]) return fail(e, CZC_ERR_OVERFLOW, "text bridge overflow (row text > CZC_BRIDGE_MAX_BYTES)%s");
+  if (tp->max_len > e->cfg.clip_max_pos || tp->max_len > CZC_CLIP_MAX_LEN) return fail(e, CZC_ERR_ARG, "CLIP sequence longer than max_position_embeddings%s");
   return 0;
 }
 
+// plan, size read and tower outside a czc_generate* step (the engine's own rows); *plan (optional): the plan that ran
 int clip_text_forward(czc_engine* e, const int* cids, const int* clen, int B, int K, int share, int* totals,
-                      float** feat_out, bool in_generate, bool exact = false) {
-  E_CHECK(clip_plan(e, cids, clen, B, K, share, totals));
+                      float** feat_out, bool exact = false, TowerPlan* plan = nullptr) {
+  PlanBufs bufs;
+  E_CHECK(clip_plan(e, cids, clen, B, K, share, totals, &bufs));
   E_HIP(hipStreamSynchronize(e->st));  // the one host round trip per step (the reference has one too, gen_utils.py:81)
-  int M, max_len, max_branch, n_trunk, n_dist;
-  E_CHECK(read_totals(e, 0, &M, &max_len, &max_branch, &n_trunk, &n_dist));
-  E_CHECK(clip_tower(e, cids, B, K, share, M, max_len, max_branch, n_trunk, n_dist, feat_out, in_generate, exact));
-  e->stat_clip_rows += M;
+  TowerPlan tp;
+  E_CHECK(read_totals(e, bufs, B, K, 0, &tp));
+  E_CHECK(clip_tower(e, cids, tp, feat_out, false, exact));
+  e->stat_clip_rows += tp.M;
   e->stat_clip_seqs += B * K;
+  if (plan) *plan = tp;
   return 0;
 }
 
@@ -860,8 +860,8 @@ int step_bufs(czc_engine* e, int n_seq, StepBufs* b) {
   return 0;
 }
 
-// mask -> BERT -> MLM head -> softmax/top-K -> text bridge -> segment plan -> start of the 32-byte size read
-int step_phase_a(czc_engine* e, const StepArgs& a) {
+// mask -> BERT -> MLM head -> softmax/top-K -> text bridge -> segment plan (*bufs: what it filled) -> start of the size read
+int step_phase_a(czc_engine* e, const StepArgs& a, const StepBufs& b, PlanBufs* bufs) {
   const czc_config& c = e->cfg;
   const czc_hyper* hp = &a.hp;
   if (a.n_mask > 0) {
@@ -876,8 +876,6 @@ int step_phase_a(czc_engine* e, const StepArgs& a) {
   }
   float* logits;
   E_CHECK(mlm_head(e, a.B, a.T, a.gen_idx, &logits, a.gen_rows, a.gen_rows_host, a.rag));
-  StepBufs b;
-  E_CHECK(step_bufs(e, a.B * a.K, &b));
   { ProfScope ps(e, "topk", 0);
     if (a.rec.vset) E_CHECK(launch_softmax_mask_topk_rows_vocab(logits, a.B, c.bert_vocab, a.K, e->d_mask, a.rec.hp ? a.rec.hp : a.rec.vhp, c.dot_id,
                                                                  a.dot_rows, a.rec.vset, a.rec.vbits, a.rec.vwords, b.probs, b.idxs, b.cand, e->st));
@@ -893,14 +891,14 @@ int step_phase_a(czc_engine* e, const StepArgs& a) {
     // per-row hyper-parameters: every table there is goes along and a candidate's thread scores by its row's control
     if (a.rec.hp) E_CHECK(launch_bridge_rows_hp(e->bd, a.d_inp, a.B, a.T, a.gen_rows, b.cand, a.K, e->d_lex, e->d_lex_pos, e->d_lex_cls, a.rec.hp,
                                                   PosDev{e->d_pos_tags, e->d_pos_masks, e->pos_n}, b.cids, b.clen, b.senti, b.reps,
-                                                  b.totals + 2, e->st, a.rag ? a.rag->len : nullptr));
+                                                  b.totals + PT_OVERFLOW, e->st, a.rag ? a.rag->len : nullptr));
     else if (a.gen_rows) E_CHECK(launch_bridge_rows(e->bd, a.d_inp, a.B, a.T, a.gen_rows, b.cand, a.K, hp->control == 1 ? e->d_lex : nullptr,
                                                hp->control == 1 ? e->d_lex_pos : nullptr, e->d_lex_cls, hp->negative,
-                                               pos, b.cids, b.clen, b.senti, b.reps, b.totals + 2, e->st, a.rag ? a.rag->len : nullptr));
+                                               pos, b.cids, b.clen, b.senti, b.reps, b.totals + PT_OVERFLOW, e->st, a.rag ? a.rag->len : nullptr));
     else E_CHECK(launch_bridge(e->bd, a.d_inp, a.B, a.T, a.gen_idx, b.cand, a.K, hp->control == 1 ? e->d_lex : nullptr,
                                hp->control == 1 ? e->d_lex_pos : nullptr, e->d_lex_cls, hp->negative,
-                               pos, b.cids, b.clen, b.senti, b.reps, b.totals + 2, e->st)); }
-  E_CHECK(clip_plan(e, b.cids, b.clen, a.B, a.K, e->share_prefix, b.totals));
+                               pos, b.cids, b.clen, b.senti, b.reps, b.totals + PT_OVERFLOW, e->st)); }
+  E_CHECK(clip_plan(e, b.cids, b.clen, a.B, a.K, e->share_prefix, b.totals, bufs));
   return 0;
 }
 
@@ -922,11 +920,9 @@ int ensure_pinned(czc_engine* e, int32_t** p, size_t* cap, size_t want) {
   return 0;
 }
 
-int control_fetch(czc_engine* e, const StepArgs& a) {
-  StepBufs b;
+int control_fetch(czc_engine* e, const StepArgs& a, const StepBufs& b) {
   const int Tc = a.ctl_T > 0 ? a.ctl_T : a.T;
   const size_t n_seq = (size_t)a.B * a.K, n_inp = (size_t)a.B * Tc;
-  E_CHECK(step_bufs(e, (int)n_seq, &b));
   E_CHECK(ensure_pinned(e, &e->h_ctl_ids, &e->h_ctl_cap, (n_inp + n_seq) * 4 + n_seq * 4));  // [B*T + B*K] ids, [B*K] scores
   e->h_ctl_scores = (float*)(e->h_ctl_ids + n_inp + n_seq);
   if (Tc == a.T) E_HIP(hipMemcpyAsync(e->h_ctl_ids, a.d_inp, n_inp * 4, hipMemcpyDeviceToHost, e->st));
@@ -936,11 +932,9 @@ int control_fetch(czc_engine* e, const StepArgs& a) {
 }
 
 // after the step's host round trip (the ids have landed) and after the tower's launches have been queued
-int control_score(czc_engine* e, const StepArgs& a) {
-  StepBufs b;
+int control_score(czc_engine* e, const StepArgs& a, const StepBufs& b) {
   const int Tc = a.ctl_T > 0 ? a.ctl_T : a.T;
   const size_t n_seq = (size_t)a.B * a.K, n_inp = (size_t)a.B * Tc;
-  E_CHECK(step_bufs(e, (int)n_seq, &b));
   memset(e->h_ctl_scores, 0, n_seq * 4);
   const int rc = e->ctl_fn(e->ctl_user, e->h_ctl_ids, e->h_ctl_ids + n_inp, a.B, Tc, a.K, a.gen_idx, e->h_ctl_scores);
   if (rc) return fail(e, CZC_ERR_STATE, "the control callback reported an error%s");
@@ -949,22 +943,21 @@ int control_score(czc_engine* e, const StepArgs& a) {
   return 0;
 }
 
-// CLIP text tower on the planned rows -> cosine / softmax_K / fusion / argmax / write-back
-int step_phase_b(czc_engine* e, const StepArgs& a, int M, int max_len, int max_branch, int n_trunk, int n_dist) {
+// CLIP text tower on the planned rows -> cosine / softmax_K / fusion / argmax / write-back; *bcos_out: the winners' cosines [B]
+int step_phase_b(czc_engine* e, const StepArgs& a, const StepBufs& b, const TowerPlan& tp, float** bcos_out) {
   const czc_config& c = e->cfg;
   const czc_hyper* hp = &a.hp;
   const int n_seq = a.B * a.K;
-  StepBufs b;
-  E_CHECK(step_bufs(e, n_seq, &b));
   float* feat;
-  E_CHECK(clip_tower(e, b.cids, a.B, a.K, e->share_prefix, M, max_len, max_branch, n_trunk, n_dist, &feat, a.mode.in_generate));
-  if (hp->control && e->ctl_fn) E_CHECK(control_score(e, a));  // host scorer under the tower that was just queued
+  E_CHECK(clip_tower(e, b.cids, tp, &feat, a.mode.in_generate));
+  if (hp->control && e->ctl_fn) E_CHECK(control_score(e, a, b));  // host scorer under the tower that was just queued
   float *cscore, *cref, *fin, *bcos; int* best;
   E_CHECK(ensure(e, "s_cscore", (size_t)n_seq * 4, (void**)&cscore));
   E_CHECK(ensure(e, "s_cref", (size_t)n_seq * 4, (void**)&cref));
   E_CHECK(ensure(e, "s_fin", (size_t)n_seq * 4, (void**)&fin));
   E_CHECK(ensure(e, "s_best", (size_t)a.B * 4, (void**)&best));
   E_CHECK(ensure(e, "s_bcos", (size_t)a.B * 4, (void**)&bcos));
+  *bcos_out = bcos;
   CombineArgs ca;
   ca.text_feat = feat; ca.img_n = a.img; ca.logit_scale_exp = e->logit_scale_exp; ca.probs = b.probs; ca.cand = b.cand;
   ca.senti_raw = b.senti; ca.repeats = b.reps; ca.alpha = hp->alpha; ca.beta = hp->beta; ca.gamma = hp->gamma;
@@ -995,8 +988,8 @@ int step_phase_b(czc_engine* e, const StepArgs& a, int M, int max_len, int max_b
   E_CHECK(ensure(e, "r_tot", 64, (void**)&rtot));
   E_CHECK(ensure(e, "r_rlist", (size_t)n_seq * 4, (void**)&rlist));
   E_CHECK(ensure(e, "r_cos", (size_t)n_seq * 4, (void**)&rcos));
-  PlanBufs sp, rp;
-  E_CHECK(plan_bufs(e, a.B, a.K, &sp));
+  const PlanBufs& sp = tp.buf;  // the screening plan
+  PlanBufs rp;
   E_CHECK(plan_bufs(e, a.B, a.K, &rp, "r"));
   const int S = a.B + n_seq;
   const bool gen = a.mode.in_generate;
@@ -1011,28 +1004,30 @@ int step_phase_b(czc_engine* e, const StepArgs& a, int M, int max_len, int max_b
     E_CHECK(launch_combine(ca, e->st));
     const float gate_h = a.mode.gate ? e->refine_gate_delta * rows16_x * e->logit_scale_exp : 0.f;
     if (a.rec.draw) E_CHECK(launch_refine_select_draw(cscore, fin, a.B, a.K, theta, theta_base, e->logit_scale_exp, strata, gate_h, hp->beta, a.rec.hp,
-                                                      a.rec.draw, need_cos, ca.nonfinite + 4, kind, list, count, e->st));
+                                                      a.rec.draw, need_cos, ca.nonfinite + NF_GATED, kind, list, count, e->st));
     else if (a.rec.hp) E_CHECK(launch_refine_select_rows(cscore, fin, a.B, a.K, theta_base, e->logit_scale_exp, strata, gate_h, a.rec.hp, need_cos,
-                                                         ca.nonfinite + 4, kind, list, count, e->st));
-    else E_CHECK(launch_refine_select(cscore, fin, a.B, a.K, theta, strata, gate_h, hp->beta, need_cos, ca.nonfinite + 4, kind, list, count, e->st)); }
+                                                         ca.nonfinite + NF_GATED, kind, list, count, e->st));
+    else E_CHECK(launch_refine_select(cscore, fin, a.B, a.K, theta, strata, gate_h, hp->beta, need_cos, ca.nonfinite + NF_GATED, kind, list, count, e->st)); }
   { ProfScope ps(e, "bridge", 0);
-    E_HIP(hipMemsetAsync(rtot, 0, 64, e->st));
+    E_HIP(hipMemsetAsync(rtot, 0, 64, e->st));  // (the buffer's 64 bytes; PLAN_TOTALS of them are read back)
     E_HIP(hipMemsetAsync(rp.own_len, 0, (size_t)S * 4, e->st));
-    E_CHECK(launch_scan(count, a.B, count_off, rtot + 8, e->st));  // rtot[8] = R, rtot[9] = Kr = largest per-image count
-    E_CHECK(launch_refine_plan(b.clen, sp.own_len, list, count, count_off, rtot + 9, a.B, a.K, rp.own_len, rp.pre_len, rp.src, rp.pos0,
-                               rlist, rtot + 3, rp.img_max, e->st));
-    E_CHECK(launch_scan(rp.own_len, S, rp.own_off, rtot, e->st));   // rtot[0] = rows of the refine pass
-    E_CHECK(launch_refine_finish(rp.own_off, rp.own_len, count, count_off, rtot + 9, a.B, a.K, rp.pre_off, rp.eidx, e->st)); }
-  E_HIP(hipMemcpyAsync(e->h_totals + 16, rtot, 48, hipMemcpyDeviceToHost, e->st));
+    E_CHECK(launch_scan(count, a.B, count_off, rtot + RT_R, e->st));  // R, then Kr = largest per-image count
+    E_CHECK(launch_refine_plan(b.clen, sp.own_len, list, count, count_off, rtot + RT_KR, a.B, a.K, rp.own_len, rp.pre_len, rp.src, rp.pos0,
+                               rlist, rtot + PT_MAX_LEN, rp.img_max, e->st));
+    E_CHECK(launch_scan(rp.own_len, S, rp.own_off, rtot, e->st));   // rows of the refine pass
+    E_CHECK(launch_refine_finish(rp.own_off, rp.own_len, count, count_off, rtot + RT_KR, a.B, a.K, rp.pre_off, rp.eidx, e->st)); }
+  E_HIP(hipMemcpyAsync(e->h_totals + HT_REFINE, rtot, PLAN_TOTALS, hipMemcpyDeviceToHost, e->st));
   E_HIP(hipStreamSynchronize(e->st));  // second (and last) host round trip of the step: the sizes of the refine pass
-  const int M2 = e->h_totals[16], max_len2 = e->h_totals[19], max_branch2 = e->h_totals[20], R = e->h_totals[24], Kr = e->h_totals[25];
+  const int* rt = e->h_totals + HT_REFINE;
+  const int M2 = rt[PT_ROWS], R = rt[RT_R], Kr = rt[RT_KR];
   if (R < 0 || R > n_seq || M2 < 0 || Kr < 0 || Kr > a.K) return fail(e, CZC_ERR_STATE, "refine plan returned impossible sizes%s");
   if (R > 0) {
     float* feat2;
-    e->plan_pairs = (double)e->h_totals[16 + 7];
     // regular B x Kr plan (empty slots have no rows): the packed-branch split attention serves it like the screening plan
-    E_CHECK(clip_tower_on(e, PREC_F16X3, e->ctext_x, e->tproj_wx, "gemm_clip_refine", b.cids, rp, a.B + a.B * Kr, R, M2, max_len2,
-                          a.B, Kr, max_branch2, "c_feat2", &feat2, gen));
+    TowerPlan tp2;
+    tp2.buf = rp; tp2.buf.rep = nullptr /* no de-duplication */; tp2.n_seg = a.B + a.B * Kr; tp2.n_pool = R; tp2.B = a.B; tp2.K = Kr;
+    tp2.M = M2; tp2.max_len = rt[PT_MAX_LEN]; tp2.max_branch = rt[PT_MAX_BRANCH]; tp2.pairs = (double)rt[PT_PAIRS];
+    E_CHECK(clip_tower_on(e, TextTower{PREC_F16X3, &e->ctext_x, e->tproj_wx, "gemm_clip_refine", "c_feat2"}, b.cids, tp2, &feat2, gen));
     ProfScope ps(e, "combine", 0);
     E_CHECK(launch_refine_cosine(feat2, a.img, rlist, count_off + a.B, R, a.K, c.clip_proj, rcos, ca.nonfinite, e->st));
   }
@@ -1049,7 +1044,10 @@ int step_phase_b(czc_engine* e, const StepArgs& a, int M, int max_len, int max_b
 // The resident image batch as a step's image rows: null (step_device refuses the step) unless it holds exactly B images
 const float* resident_images(const czc_engine* e, int B) { return B == e->img_B ? e->d_img_n : nullptr; }
 
-int step_device(czc_engine* e, const StepArgs& a) {
+// what a step hands back to callers that read its results on the device: the winners' cosines [B], its plan's longest branch per image [B]
+struct StepOut { const float* bcos = nullptr; const int* img_max = nullptr; };
+
+int step_device(czc_engine* e, const StepArgs& a, StepOut* out = nullptr) {
   const czc_config& c = e->cfg;
   const int B = a.B, T = a.T, gen_idx = a.gen_idx, n_mask = a.n_mask, K = a.K;
   const czc_hyper* hp = &a.hp; const Ragged* rag = a.rag;
@@ -1069,27 +1067,31 @@ int step_device(czc_engine* e, const StepArgs& a) {
   if (a.rec.hp && (!a.gen_rows || !a.dot_rows)) return fail(e, CZC_ERR_ARG, "step: per-row hyper-parameters need per-row columns%s");
   if (a.rec.draw && !a.gen_rows) return fail(e, CZC_ERR_ARG, "step: per-row draws need per-row columns%s");
   if (rag && (!a.gen_rows || !a.dot_rows || rag->max_T > T || rag->M > B * T)) return fail(e, CZC_ERR_ARG, "step: ragged rows need per-row columns and lengths within T%s");
-  E_CHECK(step_phase_a(e, a));
+  StepBufs b; PlanBufs bufs;
+  E_CHECK(step_bufs(e, B * K, &b));
+  E_CHECK(step_phase_a(e, a, b, &bufs));
   if (n_mask > 0) { e->stat_bert_rows += rag ? rag->M : B * T; e->last_BT = B * T; e->last_B = B; e->last_T = T; }
-  if (hp->control && e->ctl_fn) E_CHECK(control_fetch(e, a));  // ids for the host scorer ride on the same round trip
+  if (hp->control && e->ctl_fn) E_CHECK(control_fetch(e, a, b));  // ids for the host scorer ride on the same round trip
   E_HIP(hipStreamSynchronize(e->st));  // the one host round trip per step (the reference has one too, gen_utils.py:81)
-  int M, max_len, max_branch, n_trunk, n_dist;
-  E_CHECK(read_totals(e, a.branch_floor, &M, &max_len, &max_branch, &n_trunk, &n_dist));
-  E_CHECK(step_phase_b(e, a, M, max_len, max_branch, n_trunk, n_dist));
-  e->stat_clip_rows += M;
+  TowerPlan tp; float* bcos;
+  E_CHECK(read_totals(e, bufs, B, K, a.branch_floor, &tp));
+  E_CHECK(step_phase_b(e, a, b, tp, &bcos));
+  if (out) *out = StepOut{bcos, bufs.img_max};
+  e->stat_clip_rows += tp.M;
   e->stat_clip_seqs += B * K;
-  e->stat_dedup_seqs += e->h_totals[HT_PLAN + 5];
+  e->stat_dedup_seqs += tp.n_dup;
   e->stat_steps += 1;
   return 0;
 }
 
 // the end of a call that ran steps, one read: the steps' cosine check, then their guard and gate statistics
 int finish_steps(czc_engine* e) {
-  E_HIP(hipMemcpyAsync(e->h_totals + 9, e->ws["s_nonfinite"].p, 24, hipMemcpyDeviceToHost, e->st));
+  int* f = e->h_totals + HT_FLAGS;
+  E_HIP(hipMemcpyAsync(f, e->ws["s_nonfinite"].p, NF_READ * 4, hipMemcpyDeviceToHost, e->st));
   E_HIP(hipStreamSynchronize(e->st));
-  if (e->h_totals[9]) return fail(e, CZC_ERR_OVERFLOW, MSG_NONFINITE);
-  { float dev; memcpy(&dev, e->h_totals + 10, 4); e->guard_max_dev = fmaxf(e->guard_max_dev, dev); e->guard_trips += e->h_totals[11];
-    e->stat_gated += e->h_totals[13]; e->stat_gate_images += e->h_totals[14]; }
+  if (f[NF_NONFINITE]) return fail(e, CZC_ERR_OVERFLOW, MSG_NONFINITE);
+  { float dev; memcpy(&dev, f + NF_GUARD_DEV, 4); e->guard_max_dev = fmaxf(e->guard_max_dev, dev); e->guard_trips += f[NF_GUARD_TRIPS];
+    e->stat_gated += f[NF_GATED]; e->stat_gate_images += f[NF_GATE_IMAGES]; }
   return CZC_OK;
 }
 
@@ -1247,10 +1249,10 @@ int memo_step(czc_engine* e, MemoPlan& mp, int s, const StepArgs& full) {
     if (mp.check[s]) {
       E_CHECK(launch_memo_check(d_inp, B, T, gen_idx, n_mask, mask_id, key, mp.imax + (size_t)slot * MEMO_SUB * B, mp.grp.len[s],
                                 mp.hit, mp.list, mp.tot, e->st));
-      E_HIP(hipMemcpyAsync(e->h_totals + 32, mp.tot, 16, hipMemcpyDeviceToHost, e->st));
+      E_HIP(hipMemcpyAsync(e->h_totals + HT_MEMO, mp.tot, 16, hipMemcpyDeviceToHost, e->st));
       E_HIP(hipStreamSynchronize(e->st));
-      mp.n_act = e->h_totals[32];
-      mp.branch_max[0] = e->h_totals[33]; mp.branch_max[1] = e->h_totals[34];
+      mp.n_act = e->h_totals[HT_MEMO + MC_ACTIVE];
+      mp.branch_max[0] = e->h_totals[HT_MEMO + MC_BRANCH0]; mp.branch_max[1] = e->h_totals[HT_MEMO + MC_BRANCH1];
       if (mp.n_act < 0 || mp.n_act > B) return fail(e, CZC_ERR_STATE, "memo check returned an impossible count%s");
       // the split-fp16 text tower picks its GEMM forms (split-K slices, ring / tiled kernels) by row count, so a compact batch
       // moves its cosines in the last bits: that engine skips the steps every image hits and runs the others whole
@@ -1272,8 +1274,9 @@ int memo_step(czc_engine* e, MemoPlan& mp, int s, const StepArgs& full) {
                                mp.img_c, e->st));
     a.d_inp = mp.inp_c; a.B = n_act; a.img = mp.img_c; a.branch_floor = mp.branch_max[j];
   }
-  E_CHECK(step_device(e, a));
-  return launch_memo_scatter(a.d_inp, (const float*)e->ws["s_bcos"].p, (const int*)e->ws["p_img_max"].p, whole ? nullptr : mp.list, n_act, T,
+  StepOut so;
+  E_CHECK(step_device(e, a, &so));
+  return launch_memo_scatter(a.d_inp, so.bcos, so.img_max, whole ? nullptr : mp.list, n_act, T,
                              d_inp, mp.bcos, rows, cos, imax, e->st) ? fail(e, CZC_ERR_HIP, "%s", g_err) : 0;
 }
 
@@ -1486,8 +1489,9 @@ int memo_rows_step(czc_engine* e, MemoRowsPlan& mp, const RowsCall& c, const Sch
     a.branch_floor = j < MEMO_ROWS_SUB ? mp.branch_max[j] : 0;
     E_CHECK(memo_rows_records(e, mp, full.rec, n_act, &a.rec));
   }
-  E_CHECK(step_device(e, a));
-  return launch_memo_rows_scatter(a.d_inp, (const float*)e->ws["s_bcos"].p, (const int*)e->ws["p_img_max"].p, whole ? nullptr : mp.list_d,
+  StepOut so;
+  E_CHECK(step_device(e, a, &so));
+  return launch_memo_rows_scatter(a.d_inp, so.bcos, so.img_max, whole ? nullptr : mp.list_d,
                                   n_act, mp.tab, col0, j, record, d_inp, mp.bcos, e->st) ? fail(e, CZC_ERR_HIP, "%s", g_err) : 0;
 }
 
@@ -1513,9 +1517,9 @@ int score_rows_device(czc_engine* e, const int* d_rows, int n, int T, const int*
   E_HIP(hipMemcpy2DAsync(cand, 4, d_rows, (size_t)T * 4, 4, n, hipMemcpyDeviceToDevice, e->st));  // column 0 of every row
   { ProfScope ps(e, "bridge", 0);
     E_CHECK(launch_bridge_rows(e->bd, d_rows, n, T, gen, cand, 1, nullptr, nullptr, e->d_lex_cls, 0, PosDev{nullptr, nullptr, 0}, cids, clen,
-                               nullptr, nullptr, totals + 2, e->st, d_len)); }
+                               nullptr, nullptr, totals + PT_OVERFLOW, e->st, d_len)); }
   float* feat;
-  E_CHECK(clip_text_forward(e, cids, clen, n, 1, 0, totals, &feat, false, true));  // exact tower; (reads the bridge's overflow flag with the sizes)
+  E_CHECK(clip_text_forward(e, cids, clen, n, 1, 0, totals, &feat, true));  // exact tower; (reads the bridge's overflow flag with the sizes)
   { ProfScope ps(e, "combine", 0);
     if (d_rival) E_CHECK(launch_cosine_rival(feat, img_rows, n, 1, e->cfg.clip_proj, d_rival, M, e->d_img_n, e->img_B, e->logit_scale_exp, d_cos,
                                              d_disc, flag, e->st));
@@ -1935,7 +1939,7 @@ int czc_encode_images(czc_engine* e, const float* pixels, int B, float* out_embe
     E_CHECK(launch_vision_assemble(pe, B, NP, H, cls, pos, x, e->st));
     E_CHECK(launch_layernorm(P, x, nullptr, g0, b0, c.clip_eps, M, H, nullptr, x, e->st)); }
   SegTable vtab{nullptr, nullptr, nullptr, nullptr, B, T};
-  E_CHECK(clip_stack(e, P, "gemm_vision", e->cvis, x, M, H, c.vis_inter, c.vis_heads, c.clip_eps, vtab, T, 0));
+  E_CHECK(clip_stack(e, StackDesc{P, &e->cvis, "gemm_vision", M, H, c.vis_inter, c.vis_heads, c.clip_eps, vtab, T, 0}, x));
   { ProfScope ps(e, "rowops", 0);
     E_CHECK(launch_make_row_index(idx, B, T, 0, e->st));
     E_CHECK(launch_layernorm(P, x, idx, g1, b1, c.clip_eps, B, H, ca, nullptr, e->st)); }
@@ -2064,11 +2068,13 @@ int czc_encode_staged(czc_engine* e, int B, float* out_embeds) {
   return czc_encode_images(e, e->d_staged, B, out_embeds);
 }
 
-int czc_encode_text(czc_engine* e, const int32_t* clip_ids, const int32_t* clip_len, int n, float* out_embeds) {
-  if (!e || !clip_ids || !clip_len || n <= 0 || !out_embeds) return CZC_ERR_ARG;
+// host CLIP id rows of B x K sequences through the engine's own plan and text tower -> features [B * K, proj] on the host
+static int text_features(czc_engine* e, const int32_t* clip_ids, const int32_t* clip_len, int B, int K, int share, bool exact, float* out,
+                         TowerPlan* tp = nullptr) {
   if (!e->finalized) return fail(e, CZC_ERR_STATE, "weights not finalized%s");
   E_HIP(hipSetDevice(e->dev));
   e->err[0] = 0;
+  const int n = B * K;
   int *cids, *clen, *totals;
   E_CHECK(ensure(e, "s_cids", (size_t)n * CZC_CLIP_MAX_LEN * 4, (void**)&cids));
   E_CHECK(ensure(e, "s_clen", (size_t)n * 4, (void**)&clen));
@@ -2078,10 +2084,15 @@ int czc_encode_text(czc_engine* e, const int32_t* clip_ids, const int32_t* clip_
   E_HIP(hipMemsetAsync(totals, 0, PLAN_TOTALS, e->st));
   { int* flag; E_CHECK(ensure(e, "s_nonfinite", 32, (void**)&flag)); E_HIP(hipMemsetAsync(flag, 0, 32, e->st)); }
   float* feat;
-  E_CHECK(clip_text_forward(e, cids, clen, n, 1, 0, totals, &feat, false, true));  // independent sequences: no sharing; exact tower
-  E_HIP(hipMemcpyAsync(out_embeds, feat, (size_t)n * e->cfg.clip_proj * 4, hipMemcpyDefault, e->st));
+  E_CHECK(clip_text_forward(e, cids, clen, B, K, share, totals, &feat, exact, tp));
+  E_HIP(hipMemcpyAsync(out, feat, (size_t)n * e->cfg.clip_proj * 4, hipMemcpyDefault, e->st));
   E_HIP(hipStreamSynchronize(e->st));
   return CZC_OK;
+}
+
+int czc_encode_text(czc_engine* e, const int32_t* clip_ids, const int32_t* clip_len, int n, float* out_embeds) {
+  if (!e || !clip_ids || !clip_len || n <= 0 || !out_embeds) return CZC_ERR_ARG;
+  return text_features(e, clip_ids, clip_len, n, 1, 0, true, out_embeds);  // independent sequences: no sharing; exact tower
 }
 
 // clip/clip.py:86-98 `compute_image_text_similarity_via_embeddings` as a call of its own (the per-step path never needs it:
@@ -2515,6 +2526,7 @@ static int run_steps(czc_engine* e, const RowsCall& c, const Sched& sc, const Ca
   if (memo_rows && sc.at.idle && hipMemsetAsync(mrp.bcos, 0, (size_t)B * 4, e->st) != hipSuccess)
     return fail(e, CZC_ERR_HIP, "generate_rows_from: clearing the cosines%s");
   int snap = 0;
+  StepOut so;  // of the step that ran on the whole batch, without a memo
   for (int s = 0; s < n_steps; ++s) {
     const int pos = c.positions[rows ? (size_t)s * B : (size_t)s];
     const int nm = c.n_mask_at(s), dot = pos == L - 1 ? 1 : 0;
@@ -2529,7 +2541,7 @@ static int run_steps(czc_engine* e, const RowsCall& c, const Sched& sc, const Ca
     }
     if (memo_rows) E_CHECK(memo_rows_step(e, mrp, c, sc, s, a));
     else if (memo) E_CHECK(memo_step(e, mp, s, a));
-    else E_CHECK(step_device(e, a));
+    else E_CHECK(step_device(e, a, &so));
     // the tie: one launch on the full batch, behind whatever the step did (in place, compact batch and scatter, memo fill)
     if (tied && launch_tie_rows(d_inp, B, T, sc.d + sc.at.cols(s), tie.d_gor, tie.d_off, tie.d_rows, e->st)) return fail(e, CZC_ERR_HIP, "%s", g_err);
     // a tied call returns the cosine of the caption as it stands, one score per group
@@ -2537,7 +2549,7 @@ static int run_steps(czc_engine* e, const RowsCall& c, const Sched& sc, const Ca
     if (snap_idx) {
       hipError_t h = c.out_ids ? hipMemcpyAsync(c.out_ids + (size_t)snap * B * T, d_inp, (size_t)B * T * 4, hipMemcpyDefault, e->st) : hipSuccess;
       if (out_cos && h == hipSuccess)  // memo: the full-batch cosines (a compacted step leaves B_act of them in s_bcos)
-        h = hipMemcpyAsync(out_cos + (size_t)snap * B, tied ? tie.cos : memo ? mp.bcos : memo_rows ? mrp.bcos : e->ws["s_bcos"].p, (size_t)B * 4,
+        h = hipMemcpyAsync(out_cos + (size_t)snap * B, tied ? tie.cos : memo ? mp.bcos : memo_rows ? mrp.bcos : so.bcos, (size_t)B * 4,
                            hipMemcpyDefault, e->st);
       if (h != hipSuccess) { snprintf(e->err, sizeof(e->err), "generate: snapshot copy -> %s", hipGetErrorString(h)); return CZC_ERR_HIP; }
       ++snap;
@@ -2919,9 +2931,9 @@ static int score_rows_impl(czc_engine* e, const char* who, const int32_t* rows, 
   if (out_disc && d_disc) E_HIP(hipMemcpyAsync(out_disc, d_disc, (size_t)R * 4, hipMemcpyDefault, e->st));
   if (out_disc && !d_disc)
     for (int r = 0; r < R; ++r) out_disc[r] = 1.0f;  // no table: no row has a rival
-  E_HIP(hipMemcpyAsync(e->h_totals + 9, e->ws["s_nonfinite"].p, 4, hipMemcpyDeviceToHost, e->st));
+  E_HIP(hipMemcpyAsync(e->h_totals + HT_FLAGS, e->ws["s_nonfinite"].p, 4, hipMemcpyDeviceToHost, e->st));
   E_HIP(hipStreamSynchronize(e->st));
-  if (e->h_totals[9]) return fail(e, CZC_ERR_OVERFLOW, MSG_NONFINITE);
+  if (e->h_totals[HT_FLAGS]) return fail(e, CZC_ERR_OVERFLOW, MSG_NONFINITE);
   return CZC_OK;
 }
 
@@ -3029,9 +3041,9 @@ int czc_fluency_rows(czc_engine* e, const int32_t* rows, int R, int T, int seed_
   }
   if (out_logp) E_HIP(hipMemcpyAsync(out_logp, d_logp, (size_t)R * Lmax * 4, hipMemcpyDefault, e->st));
   if (out_rank) E_HIP(hipMemcpyAsync(out_rank, d_rank, (size_t)R * Lmax * 4, hipMemcpyDefault, e->st));
-  E_HIP(hipMemcpyAsync(e->h_totals + 9, flag, 4, hipMemcpyDeviceToHost, e->st));
+  E_HIP(hipMemcpyAsync(e->h_totals + HT_FLAGS, flag, 4, hipMemcpyDeviceToHost, e->st));
   E_HIP(hipStreamSynchronize(e->st));
-  if (e->h_totals[9]) return fail(e, CZC_ERR_OVERFLOW, "fluency_rows: non-finite log-probability (a non-finite BERT logit)%s");
+  if (e->h_totals[HT_FLAGS]) return fail(e, CZC_ERR_OVERFLOW, "fluency_rows: non-finite log-probability (a non-finite BERT logit)%s");
   return CZC_OK;
 }
 
@@ -3245,23 +3257,9 @@ int czc_refine_guard(czc_engine* e, int reset, float* max_dev, int64_t* tripped)
 static int test_text_tower(void* engine, const int32_t* clip_ids, const int32_t* clip_len, int B, int K, float* out, int32_t* n_dup) {
   czc_engine* e = (czc_engine*)engine;
   if (!e || !clip_ids || !clip_len || B <= 0 || K <= 0 || K > CZC_MAX_TOPK || !out) return CZC_ERR_ARG;
-  if (!e->finalized) return fail(e, CZC_ERR_STATE, "weights not finalized%s");
-  E_HIP(hipSetDevice(e->dev));
-  e->err[0] = 0;
-  const int n = B * K;
-  int *cids, *clen, *totals;
-  E_CHECK(ensure(e, "s_cids", (size_t)n * CZC_CLIP_MAX_LEN * 4, (void**)&cids));
-  E_CHECK(ensure(e, "s_clen", (size_t)n * 4, (void**)&clen));
-  E_CHECK(ensure(e, "s_tot", PLAN_TOTALS, (void**)&totals));
-  E_HIP(hipMemcpyAsync(cids, clip_ids, (size_t)n * CZC_CLIP_MAX_LEN * 4, hipMemcpyDefault, e->st));
-  E_HIP(hipMemcpyAsync(clen, clip_len, (size_t)n * 4, hipMemcpyDefault, e->st));
-  E_HIP(hipMemsetAsync(totals, 0, PLAN_TOTALS, e->st));
-  { int* flag; E_CHECK(ensure(e, "s_nonfinite", 32, (void**)&flag)); E_HIP(hipMemsetAsync(flag, 0, 32, e->st)); }
-  float* feat;
-  E_CHECK(clip_text_forward(e, cids, clen, B, K, e->share_prefix, totals, &feat, false));  // outside czc_generate: the engine's own rows
-  if (n_dup) *n_dup = e->h_totals[HT_PLAN + 5];
-  E_HIP(hipMemcpyAsync(out, feat, (size_t)n * e->cfg.clip_proj * 4, hipMemcpyDefault, e->st));
-  E_HIP(hipStreamSynchronize(e->st));
+  TowerPlan tp;
+  E_CHECK(text_features(e, clip_ids, clip_len, B, K, e->share_prefix, false, out, &tp));  // the engine's own rows
+  if (n_dup) *n_dup = tp.n_dup;
   return CZC_OK;
 }
 
